@@ -11,7 +11,12 @@ of 256 synthetic latents per GPU, resident in HBM before the timed region. Weak 
 its own batch, no data-path collective (the path shards by independent latents); timing is barrier +
 synchronize on both sides, max over ranks.
 
-Further legs on the same line (default `--mode all`; each is also a `--mode` of its own for profiling runs):
+A plain run does only what the headline needs: set up, warm up, time the `--steps` steps, write the last step's outputs
+(`--dump-outputs DIR`: DIR/<name>.npy, float32 / float64, at most 64 MB in all: a fixed seeded sample of larger outputs) and
+print the line. Everything below -- the further legs, the scan rooflines and their single-stream passes, the other
+precisions, the box probe and the CPU baselines -- runs only under `--full`.
+
+Further legs on the same line (`--full` with the default `--mode all`; each is also a `--mode` of its own for profiling runs):
   sample_250nfe  configs[3]: REAL 250-NFE fixed-step Euler flow-matching sampling of 128 latents per GPU, one RCCL
                  all-gather of the final latents -- at every N (so the scaling runs exercise the collective)
   block_fwdbwd   configs[2]: one DiMBlockCombined(1024) forward+backward at batch 256, with `roofline_bwd`   (N = 1)
@@ -28,11 +33,13 @@ attached only when the timed launches have exactly the profiled shape and kernel
 import argparse
 import json
 import os
+import re
 import statistics
 import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -305,8 +312,19 @@ class Bench:
         _lib.load()                                   # fail loudly if the HIP library is missing
         self.timer = ScanTimer()
         self.timer.install()
-        if not getattr(args, "no_box_probe", False):
+        self.outputs = None
+        if args.full and not args.no_box_probe:
             box_probe(self.dev)
+
+    def wants_outputs(self):
+        """--dump-outputs: rank 0 keeps the outputs of the first leg of the run (the headline)"""
+        return bool(self.args.dump_outputs) and self.rank == 0 and self.outputs is None
+
+    def keep_outputs(self, arrays):
+        """{name: tensor} the timed path returned in its last step, copied to the host (or sampled, see dump_sample) right after
+        the timed region"""
+        if self.wants_outputs():
+            self.outputs = dump_sample(arrays)
 
     @staticmethod
     def set_matmul(policy):
@@ -424,17 +442,21 @@ class Bench:
         a, r = self.args, image_size // 8
         model = build_model(model_name, self.dev, image_size, scan_type)
         x, t, y, _ = self.inputs(batch, r)
+        last = {}
         if a.hip_graph:
             from dimsum_amd.hip_graph import GraphedForward
             graphed = GraphedForward(model)
 
             def step():
-                return graphed(x, t, y)
+                last["out"] = graphed(x, t, y)
+                return last["out"]
         else:
             def step():
                 with torch.no_grad():
-                    return model(x, t, y)
+                    last["out"] = model(x, t, y)
+                return last["out"]
         elapsed = self.timed(step, steps, warmup, time_scans=False)
+        self.keep_outputs({"denoiser_out": last["out"]})
         out = {"workload": f"{model_name} denoiser forward, {image_size}px (4x{r}x{r} latents, {(r // 2) ** 2} tokens), {batch} latents per GPU, "
                            + WEIGHTS + (f", scan_type={scan_type}" if scan_type != "none" else ""),
                "value": batch * self.world * steps / elapsed, "unit": "latents/s", "ms_per_step": 1e3 * elapsed / steps, "steps": steps,
@@ -442,6 +464,8 @@ class Bench:
                "branch_streams": "one stream (captured graph)" if a.hip_graph else self.streams_note()}
         if self.ranks:
             out["ranks"] = self.ranks
+        if not a.full:                                                        # (a plain run has no leg after this one)
+            return out
         if not a.hip_graph:                                                   # (a replayed graph makes no library calls to time)
             self.scan_rooflines(step, out)
         if extra_precisions and self.world == 1 and a.matmul in ("tf32", "f16s") and not a.hip_graph:
@@ -513,12 +537,16 @@ class Bench:
         cond = torch.randn(batch, hidden, device=self.dev, generator=gen).requires_grad_()
         dy = torch.randn(batch, ntok, hidden, device=self.dev, generator=gen)
 
+        last, keep = {}, self.wants_outputs()         # (only then are the last step's outputs held past the step)
+
         def step():
             for p_ in model.parameters():
                 p_.grad = None
             hs.grad = res.grad = cond.grad = None
             out, res_out = model(hs, res, cond)
             torch.autograd.backward((out, res_out), (dy, dy))
+            if keep:
+                last.update(out=out, res_out=res_out)
 
         def grads():
             g = {"dx": hs.grad, "dc": cond.grad, "d w12": model.mlp.w12.weight.grad, "d w3": model.mlp.w3.weight.grad, "d qkv1": model.proj.qkv1.weight.grad,
@@ -526,6 +554,9 @@ class Bench:
                  "d x_proj (spatial)": model.spatial_mamba.mixer.x_proj.weight.grad}
             return {k: v.detach().clone() for k, v in g.items()}
         elapsed = self.timed(step, steps, warmup)
+        if keep:
+            self.keep_outputs(dict(out=last["out"], res_out=last["res_out"], dres=res.grad, **grads()))
+        last.clear()
         out = {"workload": f"ONE DiMBlockCombined({hidden}) of {model_name} (scan + Haar + attention fusion + gated MLP) forward+backward, "
                            f"{ntok} tokens, batch {batch}, " + WEIGHTS,
                "value": batch * self.world * steps / elapsed, "unit": "latents/s", "ms_per_step": 1e3 * elapsed / steps, "steps": steps, "warmup": warmup, "batch_per_gpu": batch}
@@ -534,7 +565,7 @@ class Bench:
             if rf is not None:
                 out[key] = rf
         out["matmul"] = self.TRAIN_MATMUL[self.args.matmul]
-        if self.args.matmul == "f16s" and not self.args.no_fp32_leg:
+        if self.args.full and self.args.matmul == "f16s" and not self.args.no_fp32_leg:
             # the other two arithmetic legs of the same step and the gradient deviations: max |g - g_exact| / max |g_exact| per checked gradient
             mine = grads()
             self.set_matmul("tf32")
@@ -554,8 +585,9 @@ class Bench:
         self.free()
         return out
 
-    def leg_sample(self, model_name, image_size, batch, nfe):
-        """configs[3]: `nfe` Euler evaluations of dx/dt = model(x, t, y) on `batch` latents per GPU + ONE all-gather"""
+    def leg_sample(self, model_name, image_size, batch, nfe, steps=1, warmup=0):
+        """configs[3]: `nfe` Euler evaluations of dx/dt = model(x, t, y) on `batch` latents per GPU + ONE all-gather; a step = one
+        such batch"""
         from dimsum_amd.sample_ddp import sample_batch
         a, r = self.args, image_size // 8
         model = build_model(model_name, self.dev, image_size)
@@ -569,19 +601,20 @@ class Bench:
 
         def step():
             res["out"] = sample_batch(model, x, y, num_steps=nfe, world_size=self.world, hip_graph=graphs, stats=stats if self.world > 1 else None)
-        elapsed = self.timed(step, 1, 0, time_scans=False)
+        elapsed = self.timed(step, steps, warmup, time_scans=False)
         self.rank_extra = None
+        self.keep_outputs({"samples": res["out"]})
         out = {"workload": f"{model_name} {nfe}-NFE fixed-step Euler flow-matching sampling, {image_size}px, {batch} latents per GPU "
                            f"(global batch {batch * self.world}), one all_gather_into_tensor of the final latents, " + WEIGHTS,
-               "value": batch * self.world / elapsed, "unit": "samples/s", "nfe": nfe, "s_per_batch": elapsed,
-               "ms_per_nfe": 1e3 * elapsed / nfe, "batch_per_gpu": batch,
+               "value": batch * self.world * steps / elapsed, "unit": "samples/s", "nfe": nfe, "s_per_batch": elapsed / steps,
+               "ms_per_nfe": 1e3 * elapsed / (steps * nfe), "batch_per_gpu": batch, "steps": steps, "warmup": warmup,
                "seed_rule": f"global_seed * world + rank = 0 * {self.world} + {self.rank} (sample_ddp.py:64)", "gathered_shape": list(res["out"].shape), "finite": bool(torch.isfinite(res["out"]).all().item()),
                "launch": "hipGraph replay" if a.hip_graph else "eager",
                "branch_streams": "one stream (captured graph)" if a.hip_graph else self.streams_note()}
         if self.ranks:
             out["ranks"] = self.ranks
             assert self.ranks["gathered_block_equals_own_output"], "a rank's block of the gathered latents differs from its own output"
-        if not a.hip_graph:
+        if a.full and not a.hip_graph:
             tt = torch.full((batch,), 0.5, device=self.dev)
 
             def one_nfe():
@@ -600,7 +633,12 @@ class Bench:
         x, _, y, _ = self.inputs(batch, r)
         ddp, ema, opt = build_training(model.train(), self.dev, 1e-4, self.world, [self.local_rank])
         transport = create_transport("GVP", "velocity")
-        elapsed = self.timed(lambda: train_step(ddp, ema, opt, transport, x, y), steps, warmup)
+        last = {}
+
+        def step():
+            last["loss"] = train_step(ddp, ema, opt, transport, x, y)
+        elapsed = self.timed(step, steps, warmup)
+        self.keep_outputs({"loss": last["loss"]})
         out = {"workload": f"{model_name} flow-matching training step (GVP velocity loss, backward, grad all-reduce, clip, AdamW, EMA), "
                            f"{batch} latents per GPU, " + WEIGHTS,
                "value": batch * self.world * steps / elapsed, "unit": "latents/s", "ms_per_step": 1e3 * elapsed / steps, "steps": steps, "warmup": warmup, "batch_per_gpu": batch}
@@ -608,7 +646,7 @@ class Bench:
         if rb is not None:
             out["roofline_bwd"] = rb
         out["matmul"] = self.TRAIN_MATMUL[self.args.matmul]
-        if self.args.matmul == "f16s" and not self.args.no_fp32_leg:
+        if self.args.full and self.args.matmul == "f16s" and not self.args.no_fp32_leg:
             self.set_matmul("tf32")
             e3 = self.timed(lambda: train_step(ddp, ema, opt, transport, x, y), 2, 1, time_scans=False)
             self.set_matmul("f16s")
@@ -616,6 +654,33 @@ class Bench:
         del ddp, ema, opt, model
         self.free()
         return out
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_sample(arrays, budget=DUMP_BYTES):
+    """{name: tensor} -> {file name: numpy array} for --dump-outputs: float32 (float64 stays float64), whole while all of them
+    fit in `budget` bytes; otherwise every tensor above its equal share of the budget becomes a fixed sample of its flattened
+    elements (sorted indices drawn with seed 0 on the host: the same elements in every run with the same shapes)"""
+    dtypes = {n: torch.float64 if t.dtype == torch.float64 else torch.float32 for n, t in arrays.items()}
+    nbytes = {n: t.numel() * dtypes[n].itemsize for n, t in arrays.items()}
+    share = budget // max(1, len(arrays))
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if sum(nbytes.values()) > budget and nbytes[name] > share:
+            gen = torch.Generator().manual_seed(0)
+            idx = torch.randint(t.numel(), (share // dtypes[name].itemsize,), generator=gen).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        out[re.sub(r"[^0-9A-Za-z_.-]+", "_", name).strip("_")] = t.to(dtypes[name]).cpu().numpy()
+    return out
+
+
+def write_outputs(directory, outputs):
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
 
 
 _BOX = {}
@@ -662,6 +727,10 @@ def main():
     ap.add_argument("--sample-batch", type=int, default=128, help="latents per GPU of the sampling leg (configs[3]: 1024 over 8 GPUs)")
     ap.add_argument("--hip-graph", action="store_true", help="fwd / sample: replay the denoiser forward from a captured hipGraph "
                                                              "(dimsum_amd/hip_graph.py): for per-GPU batches below ~32, where eager is launch-bound")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the further legs of --mode all, the scan "
+                                                        "rooflines, the other precisions, the box probe, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the headline leg's last timed step as DIR/<name>.npy "
+                                                          "(float32 / float64, at most 64 MB in all: a fixed seeded sample of larger outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-box-probe", action="store_true", help="skip the 1-GiB copy / add bandwidth probe at process start (kernel-trace runs: keeps its rows out of the stats)")
     ap.add_argument("--no-fp32-leg", action="store_true", help="skip the extra exact-fp32 / fp16-operand timings (for profiling runs)")
@@ -705,10 +774,12 @@ def main():
         head = b.leg_train(args.model, args.image_size, args.batch, args.steps, args.warmup)
         metric = "training latents/sec"
     else:
-        head = b.leg_sample(args.model, args.image_size, args.batch if args.batch != 256 else args.sample_batch, args.nfe)
-        head.update(steps=1, warmup=0, ms_per_step=1e3 * head["s_per_batch"])
+        head = b.leg_sample(args.model, args.image_size, args.batch if args.batch != 256 else args.sample_batch, args.nfe, args.steps, args.warmup)
+        head.update(ms_per_step=1e3 * head["s_per_batch"])
         metric = f"{args.nfe}-NFE samples/sec"
-    if args.mode == "all":
+    if b.outputs is not None:
+        write_outputs(args.dump_outputs, b.outputs)
+    if args.mode == "all" and args.full:
         # configs[3] at every N: the scaling runs then exercise the sampler and its one RCCL collective
         extras["sample_250nfe"] = b.leg_sample(args.model, args.image_size, args.sample_batch, args.nfe)
         if world == 1:
@@ -736,7 +807,7 @@ def main():
                     rf["valu"] = dict(rf["valu"])
                     notes["roofline.valu.what"] = rf["valu"].pop("what")
                 line[k] = rf
-        if world == 1 and not args.no_cpu_baseline and args.mode in ("all", "fwd", "sample"):
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode in ("all", "fwd", "sample"):
             cb = cpu_baseline(args.model, 4, args.image_size)
             # the SHAPE of the reference's own CPU path: its pure-PyTorch selective_scan_ref, at batch 16
             shaped = cpu_baseline(args.model, 16, args.image_size, runs=1, scan="torch_loop", warm=False)   # (33 s per run: the port's runs above warmed the process)
@@ -746,7 +817,8 @@ def main():
                 extra_cpu["config0_S2_batch4"] = cpu_baseline("DiM-S/2", 4, args.image_size)
         else:
             extra_cpu = None
-        line["box"] = dict(_BOX)
+        if _BOX:
+            line["box"] = dict(_BOX)
         line["dist"] = {"world_size": dist.get_world_size() if world > 1 else 1,
                         "backend": (dist.get_backend() + " (RCCL)") if world > 1 else "none (single process)"}
         for k in ("deviation_vs_exact_fp32", "fp32_exact_matmul", "tf32_single_product_f16s",

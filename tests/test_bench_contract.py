@@ -47,6 +47,7 @@ def test_command_line_contract(monkeypatch):
         pass
     a = seen["args"]
     assert (a.gpus, a.steps, a.warmup, a.mode, a.model, a.batch, a.nfe, a.sample_batch) == (1, 10, 2, "all", "DiM-L/2", 256, 250, 128)
+    assert (a.full, a.dump_outputs) == (False, None)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "5"])
     monkeypatch.setenv("WORLD_SIZE", "8")           # as a rank of torch.distributed.run (without it: the launcher, below)
     try:
@@ -55,6 +56,88 @@ def test_command_line_contract(monkeypatch):
         pass
     a = seen["args"]
     assert (a.gpus, a.steps, a.warmup) == (8, 20, 5)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    monkeypatch.delenv("WORLD_SIZE")
+    try:
+        b.main()
+    except Stop:
+        pass
+    a = seen["args"]
+    assert (a.full, a.dump_outputs) == (True, "out")
+
+
+class _FakeBench:
+    """stands in for bench.Bench without a GPU: every leg records its call and returns a minimal leg result"""
+    dump_sample = None
+
+    def __init__(self, args):
+        self.args, self.world, self.rank, self.local_rank, self.outputs, self.calls = args, 1, 0, 0, None, []
+        _FakeBench.last = self
+
+    def _leg(self, name, *a, **kw):
+        import torch
+        self.calls.append(name)
+        if self.args.dump_outputs and self.outputs is None:
+            self.outputs = type(self).dump_sample({"denoiser_out": torch.arange(12, dtype=torch.float32).view(3, 4)})
+        return {"workload": name, "value": 1.0, "unit": "latents/s", "ms_per_step": 2.0, "steps": self.args.steps,
+                "warmup": self.args.warmup, "batch_per_gpu": 1}
+
+    def leg_fwd(self, *a, **kw):
+        return self._leg("fwd" if a[0] != "DiM-XL/2" else "xl512", *a, **kw)
+
+    def leg_sample(self, *a, **kw):
+        return dict(self._leg("sample"), s_per_batch=0.002)
+
+    def leg_block(self, *a, **kw):
+        return self._leg("block")
+
+    def leg_train(self, *a, **kw):
+        return self._leg("train")
+
+
+def _run_main(b, monkeypatch, capsys, argv):
+    monkeypatch.setattr(b, "Bench", _FakeBench)
+    monkeypatch.setattr(b, "cpu_baseline", lambda *a, **kw: _FakeBench.last.calls.append("cpu_baseline") or {"value": 1.0})
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    b.main()
+    import json
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    return line, _FakeBench.last.calls
+
+
+def test_plain_run_is_the_headline_alone_and_full_runs_every_leg(monkeypatch, capsys, tmp_path):
+    """`--gpus 1 --steps N --warmup W` times the headline leg only and prints its line; the further legs and the CPU
+    baselines run only under --full. --dump-outputs writes the headline's outputs as .npy files."""
+    import numpy as np
+    b = _bench()
+    monkeypatch.setattr(_FakeBench, "dump_sample", staticmethod(b.dump_sample))
+    line, calls = _run_main(b, monkeypatch, capsys, ["--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path / "d")])
+    assert calls == ["fwd"]
+    assert (line["metric"], line["value"], line["unit"], line["higher_is_better"], line["dtype"]) == ("denoiser-fwd latents/sec", 1.0, "latents/s", True, "f32")
+    assert (line["steps"], line["warmup"], line["ms_per_step"]) == (7, 3, 2.0)
+    assert "cpu_baseline" not in line and "sample_250nfe" not in line and "box" not in line
+    got = np.load(tmp_path / "d" / "denoiser_out.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, np.arange(12, dtype=np.float32).reshape(3, 4))
+    line, calls = _run_main(b, monkeypatch, capsys, ["--full", "--steps", "2"])
+    assert calls == ["fwd", "sample", "block", "xl512", "train", "cpu_baseline", "cpu_baseline", "cpu_baseline"]
+    assert {"sample_250nfe", "block_fwdbwd", "xl512_zigzag", "train_step", "cpu_baseline", "cpu_baseline_more"} <= set(line)
+
+
+def test_dump_sample_keeps_small_outputs_whole_and_samples_large_ones_the_same_way_every_run():
+    import numpy as np
+    import torch
+    b = _bench()
+    small = {"x": torch.randn(4, 5), "d in_proj (spatial)": torch.randn(3, dtype=torch.float64), "h": torch.randn(6, dtype=torch.float16)}
+    got = b.dump_sample(small)
+    assert set(got) == {"x", "d_in_proj_spatial", "h"}
+    assert got["x"].dtype == np.float32 and np.array_equal(got["x"], small["x"].numpy())
+    assert got["d_in_proj_spatial"].dtype == np.float64 and got["h"].dtype == np.float32
+    big = {"a": torch.randn(1000, 100), "b": torch.randn(10)}
+    s1, s2 = b.dump_sample(big, budget=4000), b.dump_sample(big, budget=4000)
+    assert sum(v.nbytes for v in s1.values()) <= 4000
+    assert s1["a"].shape == (500,) and np.array_equal(s1["a"], s2["a"]) and np.array_equal(s1["b"], big["b"].numpy())
+    assert np.isin(s1["a"], big["a"].numpy()).all()
 
 
 def test_gpus_n_without_rank_env_launches_child_ranks(monkeypatch):

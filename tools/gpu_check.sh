@@ -4,7 +4,7 @@ out=gpurun_out/check; mkdir -p $out
 python -m pytest tests -q -m gpu --timeout 900 > $out/pytest.log 2>&1; echo "pytest rc=$?"
 tail -12 $out/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; tail -2 $out/smoke.log
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench.log 2> $out/bench.err; echo "bench rc=$?"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench.log 2> $out/bench.err; echo "bench rc=$?"
 python - <<'P'
 import json
 d=json.loads(open("gpurun_out/check/bench.log").read().strip().splitlines()[-1])

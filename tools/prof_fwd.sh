@@ -5,7 +5,7 @@ out=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 export DIMSUM_BRANCH_STREAMS=0
 rm -rf /tmp/prof_$name
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python3 bench.py --mode fwd --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe "$@" > $out/${name}.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python3 bench.py --mode fwd --full --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe "$@" > $out/${name}.log 2>&1
 f=$(find /tmp/prof_$name -name "*kernel_stats.csv" | head -1)
 python3 - "$f" "$out/${name}_kernel_stats.csv" <<'P'
 import csv, sys

@@ -23,15 +23,15 @@ P
   tail -1 $out/${name}.log | cut -c1-300
 }
 # (bench.py's default policy is the headline's: --matmul f16s; the three-product carrier of rounds 1-4 is --matmul tf32)
-stats fwd2s --mode fwd --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe
+stats fwd2s --full --mode fwd --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe
 export DIMSUM_BRANCH_STREAMS=0
-stats fwd --mode fwd --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe
-stats fwd_tf32 --mode fwd --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe --matmul tf32
-stats block --mode block --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe
-stats xl512 --mode xl512 --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe
-stats train --mode train --batch 64 --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe
+stats fwd --full --mode fwd --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe
+stats fwd_tf32 --full --mode fwd --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe --matmul tf32
+stats block --full --mode block --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe
+stats xl512 --full --mode xl512 --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe
+stats train --full --mode train --batch 64 --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe
 unset DIMSUM_BRANCH_STREAMS
-stats all --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe --nfe 10
+stats all --full --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-leg --no-box-probe --nfe 10
 # PMC: forward as the headline runs it (inference: no out / x stores, dt_proj fused), the same without the fusion, the full reference
 # interface, forward + saved states, backward (as dimsum_amd.ops calls it: no out_z recompute; and with it; at the training leg's batch 64
 # and the block leg's 256), config-5 forward (inference / full interface), the long-sequence stress shape (one lane per state)

@@ -11,5 +11,5 @@ for l in sys.stdin:
     except Exception: continue
     print('  ', d['shape'], {k: v['ms_median'] for k, v in d.items() if isinstance(v, dict)})
 "
-  python bench.py --mode fwd --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-leg 2>/dev/null > $out/fwd_${v:-shipped}.log; python tools/bench_summary.py $out/fwd_${v:-shipped}.log | head -1
+  python bench.py --mode fwd --full --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-leg 2>/dev/null > $out/fwd_${v:-shipped}.log; python tools/bench_summary.py $out/fwd_${v:-shipped}.log | head -1
 done
