@@ -59,6 +59,19 @@ class SsmBwdParams(_Sized):
                 + [("workspace_bytes", i64)])
 
 
+class SsmBidirParams(_Sized):
+    """dimsum_ssm_bidir_params_t: the shared operands + forward direction in `fwd`, the reversed direction's A / out / saved states"""
+    _fields_ = [("struct_size", u32), ("reserved", u32), ("fwd", SsmParams), ("A_b_ptr", vp), ("A_b_d_stride", i64), ("A_b_dstate_stride", i64),
+                ("out_b_ptr", vp), ("out_b_batch_stride", i64), ("out_b_d_stride", i64), ("ckpt_b_ptr", vp)]
+
+
+class SsmBidirBwdParams(_Sized):
+    """dimsum_ssm_bidir_bwd_params_t"""
+    _fields_ = [("struct_size", u32), ("reserved", u32), ("bwd", SsmBwdParams), ("A_b_ptr", vp), ("A_b_d_stride", i64), ("A_b_dstate_stride", i64),
+                ("out_b_ptr", vp), ("out_b_batch_stride", i64), ("out_b_d_stride", i64), ("ckpt_b_ptr", vp),
+                ("dA_b_ptr", vp), ("dA_b_d_stride", i64), ("dA_b_dstate_stride", i64)]
+
+
 class ConvParams(_Sized):
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "dim", "seqlen", "width", "silu_activation", "dtype", "reserved")]
                 + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "weight_c_stride", "weight_width_stride",
@@ -143,6 +156,7 @@ EXPORTS = (
     "dimsum_status_string", "dimsum_abi_version", "dimsum_target_arch",
     "dimsum_event_create", "dimsum_event_destroy", "dimsum_event_elapsed_ms",
     "dimsum_ssm_scan_fwd", "dimsum_ssm_scan_bwd", "dimsum_ssm_scan_bwd_workspace_bytes", "dimsum_ssm_scan_fwd_variant",
+    "dimsum_ssm_scan_bidir_fwd", "dimsum_ssm_scan_bidir_bwd", "dimsum_ssm_scan_bidir_fwd_variant",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
@@ -170,6 +184,7 @@ def load():
         lib.dimsum_event_destroy.restype, lib.dimsum_event_destroy.argtypes = None, [vp]
         lib.dimsum_event_elapsed_ms.restype, lib.dimsum_event_elapsed_ms.argtypes = C.c_float, [vp, vp]
     for name, ptype in (("dimsum_ssm_scan_fwd", SsmParams), ("dimsum_ssm_scan_bwd", SsmBwdParams),
+                        ("dimsum_ssm_scan_bidir_fwd", SsmBidirParams), ("dimsum_ssm_scan_bidir_bwd", SsmBidirBwdParams),
                         ("dimsum_causal_conv1d_fwd", ConvParams), ("dimsum_causal_conv1d_bwd", ConvBwdParams),
                         ("dimsum_norm_fwd", NormParams), ("dimsum_norm_bwd", NormBwdParams),
                         ("dimsum_token_transform", TtParams), ("dimsum_xattn_fusion_fwd", XattnParams),
@@ -220,7 +235,10 @@ def load():
     if hasattr(lib, "dimsum_ssm_scan_fwd_variant"):
         lib.dimsum_ssm_scan_fwd_variant.restype = C.c_int
         lib.dimsum_ssm_scan_fwd_variant.argtypes = [C.POINTER(SsmParams)]
-    if lib.dimsum_abi_version() != 17:
+    if hasattr(lib, "dimsum_ssm_scan_bidir_fwd_variant"):
+        lib.dimsum_ssm_scan_bidir_fwd_variant.restype = C.c_int
+        lib.dimsum_ssm_scan_bidir_fwd_variant.argtypes = [C.POINTER(SsmBidirParams)]
+    if lib.dimsum_abi_version() != 18:
         raise RuntimeError("dimsum_amd: libdimsum_hip.so ABI version mismatch; rebuild")
     _lib = lib
     return lib

@@ -166,8 +166,14 @@ __device__ __forceinline__ void softplus_and_slope(float x, bool flag, float &dt
 }
 
 // kVec : every row base 4-element aligned and L % 4 == 0 -> 16-byte vector I/O.   kFull: all 64 channel slots are live.
-template <typename T, int kN, bool kHasZ, bool kVec, bool kFull>
+// kRev : the time-reversed direction of the bidirectional scan (bimamba_inner_fn; forward: ssm_scan_fwd_kernel.hpp, kRev). The kernel runs in
+//        reversed time t' = L - 1 - t -- so it walks ORIGINAL time forwards -- and only its global addresses are mirrored: a 4-step group t' ..
+//        t' + 3 is the memory group L - 4 - t' .. L - 1 - t' with its elements swapped in registers. The saved states are indexed in reversed
+//        time (as that forward kernel wrote them), the partial dB / dC too (the reduce kernel mirrors them). It ACCUMULATES: du, ddelta, dz and
+//        the optional out_z are read, added to and stored (the forward direction's launch has written them), dA goes to the caller's dA_b.
+template <typename T, int kN, bool kHasZ, bool kVec, bool kFull, bool kRev = false>
 __global__ __launch_bounds__(kBW * kWave, 2) void ssm_scan_bwd_kernel(const ssm_bwd_args_t q, const float *__restrict__ ckpt, float *__restrict__ part) {
+    static_assert(!kRev || kHasZ, "the bidirectional scan gates with z");
     constexpr int kNL = kN / kBQ;                 // states per lane
     constexpr int kBG = kNL < 4 ? kNL : 4;        // states per register sweep
     constexpr int NV = kBG * kBS;                 // (state, step) values per transposed reduction
@@ -274,17 +280,35 @@ __global__ __launch_bounds__(kBW * kWave, 2) void ssm_scan_bwd_kernel(const ssm_
     // where they are staged. Branch-free: rows beyond nd are clamped to the last live row, columns beyond L to the last 4-column
     // group; the masks are applied when the registers are staged.
     Raw4<T> pu[kNPc], pd[kNPc], pg[kNPc], pz[kNPc], py[kNPc];
+    auto gcol = [&](int c) { return kRev ? L - 4 - c : c; };            // 4-step group at (reversed) column c -> its first element in memory
+    auto gidx = [&](int t) { return kRev ? L - 1 - t : t; };
+    auto rv = [](f32x4 v) -> f32x4 {
+        if constexpr (kRev) return {{v.v[3], v.v[2], v.v[1], v.v[0]}};
+        else return v;
+    };
+    auto acc4 = [&](T *dst, f32x4 v) {                                  // store v (memory order), or add it to what is there
+        if constexpr (kRev) {
+            const f32x4 o = widen(ld4<T>(dst));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { asm volatile("" : "+v"(v.v[e])); v.v[e] = o.v[e] + v.v[e]; }   // (no fma into the add: o + round(v))
+        }
+        st4<T>(dst, v);
+    };
+    auto acc1 = [&](T &dst, float v) {
+        if constexpr (kRev) asm volatile("" : "+v"(v));
+        dst = from_f32<T>(kRev ? to_f32<T>(dst) + v : v);
+    };
     auto tile_addr = [&](const T *base, int ds, int i, int col) -> const T * {
         if constexpr (kFull) return at(base + i * 8 * ds, (unsigned)(lrow * ds + col));
         else return at(base, (unsigned)(min(i * 8 + lrow, nd - 1) * ds + col));
     };
     auto issue_d = [&](int t0n) {
-        const int col = min(t0n + lcol, L - 4);
+        const int col = gcol(min(t0n + lcol, L - 4));
 #pragma unroll
         for (int i = 0; i < kNPc; ++i) { pd[i] = ld4<T>(tile_addr(dl_base, dl_ds, i, col)); pu[i] = ld4<T>(tile_addr(u_base, u_ds, i, col)); }
     };
     auto issue_rest = [&](int t0n) {
-        const int col = min(t0n + lcol, L - 4);
+        const int col = gcol(min(t0n + lcol, L - 4));
 #pragma unroll
         for (int i = 0; i < kNPc; ++i) {
             pg[i] = ld4<T>(tile_addr(do_base, do_ds, i, col));
@@ -303,11 +327,11 @@ __global__ __launch_bounds__(kBW * kWave, 2) void ssm_scan_bwd_kernel(const ssm_
             const int ns = which ? Cns : Bns;
             f32x4 v = {{0.f, 0.f, 0.f, 0.f}};
             if constexpr (kVec) {
-                if (t0 + c4 * 4 < L) v = widen(ld4<T>(at(src, (unsigned)(n * ns + t0 + c4 * 4))));
+                if (t0 + c4 * 4 < L) v = rv(widen(ld4<T>(at(src, (unsigned)(n * ns + gcol(t0 + c4 * 4))))));
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (t0 + c4 * 4 + e < L) v.v[e] = to_f32<T>(src[(unsigned)(n * ns + t0 + c4 * 4 + e)]);
+                    if (t0 + c4 * 4 + e < L) v.v[e] = to_f32<T>(src[(unsigned)(n * ns + gidx(t0 + c4 * 4 + e))]);
             }
             *reinterpret_cast<f32x4 *>(&(which ? tC : tB)[n * kBCS + c4 * 4]) = v;
         }
@@ -321,8 +345,8 @@ __global__ __launch_bounds__(kBW * kWave, 2) void ssm_scan_bwd_kernel(const ssm_
                     const int row = i * 8 + lrow;
                     f32x4 vu = {{0.f, 0.f, 0.f, 0.f}}, vd = {{0.f, 0.f, 0.f, 0.f}}, vs = {{0.f, 0.f, 0.f, 0.f}};
                     if ((kFull || row < nd) && t0 + lcol < L) {
-                        vu = widen(pu[i]);
-                        vd = widen(pd[i]);
+                        vu = rv(widen(pu[i]));
+                        vd = rv(widen(pd[i]));
 #pragma unroll
                         for (int s = 0; s < 4; ++s) softplus_and_slope(vd.v[s] + bias_row[i], softplus, vd.v[s], vs.v[s]);
                     }
@@ -336,8 +360,8 @@ __global__ __launch_bounds__(kBW * kWave, 2) void ssm_scan_bwd_kernel(const ssm_
                     const int row = i * 8 + lrow;
                     f32x4 dy = {{0.f, 0.f, 0.f, 0.f}};
                     if ((kFull || row < nd) && t0 + lcol < L) {
-                        const unsigned col = (unsigned)(t0 + lcol);
-                        const f32x4 go = widen(pg[i]);
+                        const unsigned col = (unsigned)gcol(t0 + lcol);
+                        const f32x4 go = widen(pg[i]);     // (memory order: dz / out_z are formed in it, dy is reordered below)
                         if constexpr (kHasZ) {
                             const f32x4 zv = widen(pz[i]);
                             const f32x4 yv = widen(py[i]);
@@ -349,28 +373,28 @@ __global__ __launch_bounds__(kBW * kWave, 2) void ssm_scan_bwd_kernel(const ssm_
                                 oz.v[e] = yv.v[e] * silu;
                                 dy.v[e] = go.v[e] * silu;
                             }
-                            st4<T>(at(dz_base + i * 8 * dz_ds, (unsigned)(lrow * dz_ds) + col), dz);
-                            if (oz_base) st4<T>(at(oz_base + i * 8 * oz_ds, (unsigned)(lrow * oz_ds) + col), oz);
+                            acc4(at(dz_base + i * 8 * dz_ds, (unsigned)(lrow * dz_ds) + col), dz);
+                            if (oz_base) acc4(at(oz_base + i * 8 * oz_ds, (unsigned)(lrow * oz_ds) + col), oz);
                         } else {
                             dy = go;
                         }
                     }
-                    *reinterpret_cast<f32x4 *>(&tY[btile_off(row, lc4)]) = dy;
+                    *reinterpret_cast<f32x4 *>(&tY[btile_off(row, lc4)]) = rv(dy);
                 }
                 if (tile > 0) issue_d(t0 - kBT);                 // flies under the sweeps below
             } else {
                 for (int i = 0; i < kBC * kBT / kWave; ++i) {
-                    const int idx = i * kWave + lane, row = idx / kBT, col = idx & (kBT - 1), t = t0 + col;
+                    const int idx = i * kWave + lane, row = idx / kBT, col = idx & (kBT - 1), t = gidx(t0 + col);
                     float vu = 0.f, vd = 0.f, dy = 0.f, vs = 0.f;
-                    if (row < nd && t < L) {
+                    if (row < nd && t0 + col < L) {
                         vu = to_f32<T>(u_base[(unsigned)(row * u_ds + t)]);
                         softplus_and_slope(to_f32<T>(dl_base[(unsigned)(row * dl_ds + t)]) + (bias_p ? bias_p[d0 + row] : 0.f), softplus, vd, vs);
                         const float go = to_f32<T>(do_base[(unsigned)(row * do_ds + t)]);
                         if constexpr (kHasZ) {
                             const float zv = to_f32<T>(z_base[(unsigned)(row * z_ds + t)]), yv = to_f32<T>(y_base[(unsigned)(row * y_ds + t)]);
                             const float sgz = sigmoidf_fast(zv), silu = zv * sgz;
-                            dz_base[(unsigned)(row * dz_ds + t)] = from_f32<T>(go * yv * sgz * (1.0f + zv * (1.0f - sgz)));
-                            if (oz_base) oz_base[(unsigned)(row * oz_ds + t)] = from_f32<T>(yv * silu);
+                            acc1(dz_base[(unsigned)(row * dz_ds + t)], go * yv * sgz * (1.0f + zv * (1.0f - sgz)));
+                            if (oz_base) acc1(oz_base[(unsigned)(row * oz_ds + t)], yv * silu);
                             dy = go * silu;
                         } else {
                             dy = go;
@@ -577,16 +601,16 @@ __global__ __launch_bounds__(kBW * kWave, 2) void ssm_scan_bwd_kernel(const ssm_
                     const f32x4 a = *reinterpret_cast<const f32x4 *>(&tU[btile_off(row, lc4)]);
                     const f32x4 cv = *reinterpret_cast<const f32x4 *>(&tY[btile_off(row, lc4)]);
                     if ((kFull || row < nd) && t0 + lcol < L) {
-                        st4<T>(at(du_base + i * 8 * du_ds, (unsigned)(lrow * du_ds + t0 + lcol)), a);
-                        st4<T>(at(dd_base + i * 8 * dd_ds, (unsigned)(lrow * dd_ds + t0 + lcol)), cv);
+                        acc4(at(du_base + i * 8 * du_ds, (unsigned)(lrow * du_ds + gcol(t0 + lcol))), rv(a));
+                        acc4(at(dd_base + i * 8 * dd_ds, (unsigned)(lrow * dd_ds + gcol(t0 + lcol))), rv(cv));
                     }
                 }
             } else {
                 for (int i = 0; i < kBC * kBT / kWave; ++i) {
-                    const int idx = i * kWave + lane, row = idx / kBT, col = idx & (kBT - 1), t = t0 + col;
-                    if (row < nd && t < L) {
-                        du_base[(unsigned)(row * du_ds + t)] = from_f32<T>(tU[btile_off(row, col >> 2) + (col & 3)]);
-                        dd_base[(unsigned)(row * dd_ds + t)] = from_f32<T>(tY[btile_off(row, col >> 2) + (col & 3)]);
+                    const int idx = i * kWave + lane, row = idx / kBT, col = idx & (kBT - 1), t = gidx(t0 + col);
+                    if (row < nd && t0 + col < L) {
+                        acc1(du_base[(unsigned)(row * du_ds + t)], tU[btile_off(row, col >> 2) + (col & 3)]);
+                        acc1(dd_base[(unsigned)(row * dd_ds + t)], tY[btile_off(row, col >> 2) + (col & 3)]);
                     }
                 }
             }
@@ -629,7 +653,8 @@ __global__ __launch_bounds__(kBW * kWave, 2) void ssm_scan_bwd_kernel(const ssm_
 
 // dB[b, g, n, t] = sum over the workgroups w of (b, g), in index order, of part[b, g, w][0][n][t]  (same for dC).
 // One thread owns 4 consecutive steps (16-byte loads when L % 4 == 0); the partial rows of a (b, g) are 2 N L floats apart.
-template <bool kVec4>
+// kRev: the partials of the reversed direction (indexed in reversed time) are mirrored into dB / dC and ADDED to what is there.
+template <bool kVec4, bool kRev = false>
 __global__ __launch_bounds__(256) void ssm_scan_bwd_reduce_kernel(const float *__restrict__ part, const ssm_bwd_args_t q, int waves_per_group) {
     const ssm_args_t &p = q.fwd;
     const int L = p.seqlen, N = p.dstate, L4 = (L + 3) / 4;
@@ -644,8 +669,9 @@ __global__ __launch_bounds__(256) void ssm_scan_bwd_reduce_kernel(const float *_
     const int b = (int)(r / p.n_groups);
     const float *src = part + (((int64_t)(b * p.n_groups + g) * waves_per_group) * 2 + which) * N * L + (int64_t)n * L + t;
     const int64_t ws = (int64_t)2 * N * L;
-    float *dst = which == 0 ? reinterpret_cast<float *>(q.dB_ptr) + (int64_t)b * q.dB_batch_stride + (int64_t)g * q.dB_group_stride + (int64_t)n * q.dB_dstate_stride + t
-                            : reinterpret_cast<float *>(q.dC_ptr) + (int64_t)b * q.dC_batch_stride + (int64_t)g * q.dC_group_stride + (int64_t)n * q.dC_dstate_stride + t;
+    float *dst = which == 0 ? reinterpret_cast<float *>(q.dB_ptr) + (int64_t)b * q.dB_batch_stride + (int64_t)g * q.dB_group_stride + (int64_t)n * q.dB_dstate_stride
+                            : reinterpret_cast<float *>(q.dC_ptr) + (int64_t)b * q.dC_batch_stride + (int64_t)g * q.dC_group_stride + (int64_t)n * q.dC_dstate_stride;
+    if constexpr (!kRev) dst += t;
     if constexpr (kVec4) {
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         int w = 0;
@@ -659,18 +685,26 @@ __global__ __launch_bounds__(256) void ssm_scan_bwd_reduce_kernel(const float *_
             const float4 v = *reinterpret_cast<const float4 *>(src + (int64_t)w * ws);
             acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
         }
-        *reinterpret_cast<float4 *>(dst) = acc;
+        if constexpr (kRev) {
+            float4 *d4 = reinterpret_cast<float4 *>(dst + (L - 4 - t));
+            const float4 o = *d4;
+            *d4 = make_float4(o.x + acc.w, o.y + acc.z, o.z + acc.y, o.w + acc.x);
+        } else {
+            *reinterpret_cast<float4 *>(dst) = acc;
+        }
     } else {
         for (int e = 0; e < 4 && t + e < L; ++e) {
             float acc = 0.f;
             for (int w = 0; w < waves_per_group; ++w) acc += src[(int64_t)w * ws + e];
-            dst[e] = acc;
+            if constexpr (kRev) dst[L - 1 - (t + e)] += acc;
+            else dst[e] = acc;
         }
     }
 }
 
 // ev0: recorded at the begin of the main kernel unless the state-rebuild sweep of this call already took it (then null)
-template <typename T, int kN>
+// kRev: the reversed, accumulating direction of the bidirectional backward (z given)
+template <typename T, int kN, bool kRev = false>
 static int launch_bwd(const ssm_bwd_args_t &q, const float *ckpt, float *part, hipStream_t stream, hipEvent_t ev0) {
     const ssm_args_t &p = q.fwd;
     const int dpg = p.dim / p.n_groups;
@@ -698,8 +732,13 @@ static int launch_bwd(const ssm_bwd_args_t &q, const float *ckpt, float *part, h
     dim3 grid(tiles), block(kBW * kWave);
     const hipEvent_t ev1 = reinterpret_cast<hipEvent_t>(p.timing_stop_event), none = nullptr;   // end of the reduce kernel
 #define DIMSUM_LAUNCH(HASZ, VEC, FULL) \
-    DIMSUM_LAUNCH_EV((ssm_scan_bwd_kernel<T, kN, HASZ, VEC, FULL>), grid, block, stream, ev0, none, q, ckpt, part)
-    if (p.z_ptr) {
+    DIMSUM_LAUNCH_EV((ssm_scan_bwd_kernel<T, kN, HASZ, VEC, FULL, kRev>), grid, block, stream, ev0, none, q, ckpt, part)
+    if constexpr (kRev) {
+        if (!p.z_ptr) return DIMSUM_ERR_NULL;
+        if (full) DIMSUM_LAUNCH(true, true, true);
+        else if (vec) DIMSUM_LAUNCH(true, true, false);
+        else DIMSUM_LAUNCH(true, false, false);
+    } else if (p.z_ptr) {
         if (full) DIMSUM_LAUNCH(true, true, true);
         else if (vec) DIMSUM_LAUNCH(true, true, false);
         else DIMSUM_LAUNCH(true, false, false);
@@ -715,18 +754,18 @@ static int launch_bwd(const ssm_bwd_args_t &q, const float *ckpt, float *part, h
                       q.dB_group_stride % 4 == 0 && q.dB_dstate_stride % 4 == 0 && q.dC_batch_stride % 4 == 0 && q.dC_group_stride % 4 == 0 &&
                       q.dC_dstate_stride % 4 == 0;
     const dim3 rgrid((unsigned)((total + 255) / 256)), rblock(256);
-    if (vec4) DIMSUM_LAUNCH_EV(ssm_scan_bwd_reduce_kernel<true>, rgrid, rblock, stream, none, ev1, part, q, (dpg + kWC - 1) / kWC);
-    else DIMSUM_LAUNCH_EV(ssm_scan_bwd_reduce_kernel<false>, rgrid, rblock, stream, none, ev1, part, q, (dpg + kWC - 1) / kWC);
+    if (vec4) DIMSUM_LAUNCH_EV((ssm_scan_bwd_reduce_kernel<true, kRev>), rgrid, rblock, stream, none, ev1, part, q, (dpg + kWC - 1) / kWC);
+    else DIMSUM_LAUNCH_EV((ssm_scan_bwd_reduce_kernel<false, kRev>), rgrid, rblock, stream, none, ev1, part, q, (dpg + kWC - 1) / kWC);
     return launch_status();
 }
 
-template <typename T>
+template <typename T, bool kRev = false>
 static int dispatch_bwd(const ssm_bwd_args_t &q, const float *ckpt, float *part, hipStream_t stream, hipEvent_t ev0) {
     switch (q.fwd.dstate) {
-        case 4: return launch_bwd<T, 4>(q, ckpt, part, stream, ev0);
-        case 8: return launch_bwd<T, 8>(q, ckpt, part, stream, ev0);
-        case 32: return launch_bwd<T, 32>(q, ckpt, part, stream, ev0);
-        case 16: return launch_bwd<T, 16>(q, ckpt, part, stream, ev0);
+        case 4: return launch_bwd<T, 4, kRev>(q, ckpt, part, stream, ev0);
+        case 8: return launch_bwd<T, 8, kRev>(q, ckpt, part, stream, ev0);
+        case 32: return launch_bwd<T, 32, kRev>(q, ckpt, part, stream, ev0);
+        case 16: return launch_bwd<T, 16, kRev>(q, ckpt, part, stream, ev0);
         default: return DIMSUM_ERR_SHAPE;
     }
 }
@@ -752,11 +791,9 @@ extern "C" int64_t dimsum_ssm_scan_bwd_workspace_bytes(int32_t batch, int32_t di
 
 namespace dimsum { int ssm_scan_fwd_run(const ssm_args_t &a, hipStream_t s); }
 
-extern "C" int dimsum_ssm_scan_bwd(const dimsum_ssm_bwd_params_t *pub, void *stream) {
+// public backward struct -> flat block (the size of `pub` itself is checked by the caller)
+static int bwd_args_from(const dimsum_ssm_bwd_params_t *pub, dimsum::ssm_bwd_args_t &flat) {
     using namespace dimsum;
-    if (!pub) return DIMSUM_ERR_NULL;
-    if (pub->struct_size != sizeof(dimsum_ssm_bwd_params_t)) return DIMSUM_ERR_ABI;
-    ssm_bwd_args_t flat;
     {
         const int arc = ssm_args_from(&pub->fwd, flat.fwd, false);
         if (arc != DIMSUM_OK) return arc;
@@ -771,6 +808,18 @@ extern "C" int dimsum_ssm_scan_bwd(const dimsum_ssm_bwd_params_t *pub, void *str
     flat.dout_ptr = pub->dout_ptr; flat.dA_ptr = pub->dA_ptr; flat.dB_ptr = pub->dB_ptr; flat.dC_ptr = pub->dC_ptr; flat.dD_ptr = pub->dD_ptr;
     flat.du_ptr = pub->du_ptr; flat.dz_ptr = pub->dz_ptr; flat.ddelta_ptr = pub->ddelta_ptr; flat.ddelta_bias_ptr = pub->ddelta_bias_ptr;
     flat.workspace_ptr = pub->workspace_ptr; flat.workspace_bytes = pub->workspace_bytes;
+    return DIMSUM_OK;
+}
+
+extern "C" int dimsum_ssm_scan_bwd(const dimsum_ssm_bwd_params_t *pub, void *stream) {
+    using namespace dimsum;
+    if (!pub) return DIMSUM_ERR_NULL;
+    if (pub->struct_size != sizeof(dimsum_ssm_bwd_params_t)) return DIMSUM_ERR_ABI;
+    ssm_bwd_args_t flat;
+    {
+        const int arc = bwd_args_from(pub, flat);
+        if (arc != DIMSUM_OK) return arc;
+    }
     const ssm_bwd_args_t *q = &flat;
     const int rc = ssm_check(&q->fwd, false);
     if (rc != DIMSUM_OK) return rc;
@@ -801,5 +850,52 @@ extern "C" int dimsum_ssm_scan_bwd(const dimsum_ssm_bwd_params_t *pub, void *str
         case DIMSUM_F16: return dispatch_bwd<__half>(*q, ckpt, part, s, ev0);
         case DIMSUM_BF16: return dispatch_bwd<__hip_bfloat16>(*q, ckpt, part, s, ev0);
         default: return DIMSUM_ERR_DTYPE;
+    }
+}
+
+// Bidirectional backward (bimamba_inner_fn): the forward direction on the plain kernels (du, ddelta, dz, dB, dC, out_z written), then the
+// reversed direction on the kRev instantiations, which add their half in place. dA and dA_b stay apart; dD / ddelta_bias collect both.
+// Both directions' saved states are required (the bidirectional forward writes them); the workspace holds the partial dB / dC only.
+extern "C" int dimsum_ssm_scan_bidir_bwd(const dimsum_ssm_bidir_bwd_params_t *pub, void *stream) {
+    using namespace dimsum;
+    if (!pub) return DIMSUM_ERR_NULL;
+    if (pub->struct_size != sizeof(dimsum_ssm_bidir_bwd_params_t)) return DIMSUM_ERR_ABI;
+    ssm_bwd_args_t qf;
+    {
+        const int arc = bwd_args_from(&pub->bwd, qf);
+        if (arc != DIMSUM_OK) return arc;
+    }
+    if (qf.fwd.dt_w_ptr || qf.fwd.out_z_lo_offset || qf.fwd.out_z_f16) return DIMSUM_ERR_UNSUPPORTED;
+    const int rc = ssm_check(&qf.fwd, false);
+    if (rc != DIMSUM_OK) return rc;
+    if (!qf.dout_ptr || !qf.dA_ptr || !qf.dB_ptr || !qf.dC_ptr || !qf.du_ptr || !qf.ddelta_ptr || !qf.workspace_ptr) return DIMSUM_ERR_NULL;
+    if (!qf.fwd.z_ptr || !qf.dz_ptr || !qf.fwd.out_ptr || !qf.fwd.ckpt_ptr) return DIMSUM_ERR_NULL;
+    if (!pub->A_b_ptr || !pub->out_b_ptr || !pub->ckpt_b_ptr || !pub->dA_b_ptr) return DIMSUM_ERR_NULL;
+    if (!aligned_to<float>(qf.workspace_ptr, 16)) return DIMSUM_ERR_STRIDE;
+    const ssm_args_t &p = qf.fwd;
+    if (qf.workspace_bytes < partial_bytes(p.batch, p.dim, p.seqlen, p.dstate, p.n_groups)) return DIMSUM_ERR_SHAPE;
+    ssm_bwd_args_t qb = qf;
+    qb.fwd.A_ptr = pub->A_b_ptr; qb.fwd.A_d_stride = pub->A_b_d_stride; qb.fwd.A_dstate_stride = pub->A_b_dstate_stride;
+    qb.fwd.out_ptr = const_cast<void *>(pub->out_b_ptr); qb.fwd.out_batch_stride = pub->out_b_batch_stride; qb.fwd.out_d_stride = pub->out_b_d_stride;
+    qb.fwd.ckpt_ptr = const_cast<void *>(pub->ckpt_b_ptr);
+    qb.dA_ptr = pub->dA_b_ptr; qb.dA_d_stride = pub->dA_b_d_stride; qb.dA_dstate_stride = pub->dA_b_dstate_stride;
+    qf.fwd.timing_stop_event = nullptr;         // the events bracket the whole call: begin of the first kernel, end of the last
+    qb.fwd.timing_start_event = nullptr;
+    float *part = reinterpret_cast<float *>(qf.workspace_ptr);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const hipEvent_t ev0 = reinterpret_cast<hipEvent_t>(p.timing_start_event);
+    int frc;
+    switch (p.dtype) {
+        case DIMSUM_F32: frc = dispatch_bwd<float>(qf, reinterpret_cast<const float *>(qf.fwd.ckpt_ptr), part, s, ev0); break;
+        case DIMSUM_F16: frc = dispatch_bwd<__half>(qf, reinterpret_cast<const float *>(qf.fwd.ckpt_ptr), part, s, ev0); break;
+        case DIMSUM_BF16: frc = dispatch_bwd<__hip_bfloat16>(qf, reinterpret_cast<const float *>(qf.fwd.ckpt_ptr), part, s, ev0); break;
+        default: return DIMSUM_ERR_DTYPE;
+    }
+    if (frc != DIMSUM_OK) return frc;
+    const float *ckb = reinterpret_cast<const float *>(qb.fwd.ckpt_ptr);
+    switch (p.dtype) {
+        case DIMSUM_F32: return dispatch_bwd<float, true>(qb, ckb, part, s, nullptr);
+        case DIMSUM_F16: return dispatch_bwd<__half, true>(qb, ckb, part, s, nullptr);
+        default: return dispatch_bwd<__hip_bfloat16, true>(qb, ckb, part, s, nullptr);
     }
 }

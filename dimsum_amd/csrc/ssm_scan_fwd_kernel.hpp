@@ -139,9 +139,16 @@ struct alignas(16) ScanU4 { unsigned w[4]; };
 //        GEMM puts a 32-token group on one scale as it reads the blocks) instead of the library's three bf16 products over fp32 operands, and
 //        the scan writes half the bytes. A lane pair trades halves (one quad_perm DPP each way) so that every lane issues ONE 16-byte store
 //        for two pieces. The reference feeds out_proj under TF32 (selective_scan_interface.py:954-981 under train.py:20-21): 10-bit mantissas.
-template <typename T, int kN, bool kHasZ, bool kVec, bool kFull, bool kCkpt = false, bool kDt = false, bool kZ16 = false>
+// kRev : time-reversed scan (the backward direction of bimamba_inner_fn): the kernel runs in reversed time t' = L - 1 - t and only its global
+//        addresses are mirrored -- tiles are walked from the end of every row, a 4-step group t' .. t' + 3 is the 4-aligned group
+//        L - 4 - t' .. L - 1 - t' read (and written) with its elements swapped in registers, on the way into / out of the LDS transpose. u, delta,
+//        z, B, C, out and out_z stay in their forward layouts (no reversed copy exists); saved states (ckpt, x) are indexed in reversed time.
+//        Bit for bit the forward kernel on flipped copies.
+// kAcc : out_z += out * silu(z) (read, add, store: the second direction's half of the bidirectional sum, in a fixed order) instead of out_z =.
+template <typename T, int kN, bool kHasZ, bool kVec, bool kFull, bool kCkpt = false, bool kDt = false, bool kZ16 = false, bool kRev = false, bool kAcc = false>
 __global__ __launch_bounds__(kWave, kScanWaves) void ssm_scan_fwd_kernel(const ssm_args_t p) {
     static_assert(!kFull || kVec, "kFull implies kVec");
+    static_assert(!(kRev || kAcc) || (kHasZ && !kDt && !kZ16), "the bidirectional scan gates with z and stores plain out_z");
     static_assert(!kZ16 || (kFull && kHasZ && !kCkpt && std::is_same<T, float>::value), "the fp16 out_z rides on the full fp32 inference path");
     static_assert(!kDt || (kFull && kHasZ && !kCkpt && std::is_same<T, float>::value), "the fused dt_proj rides on the full fp32 inference path");
     __shared__ __attribute__((aligned(16))) float tileU[kWave * kLdsStride];
@@ -206,6 +213,12 @@ __global__ __launch_bounds__(kWave, kScanWaves) void ssm_scan_fwd_kernel(const s
     // Address = wave-uniform (base + i * 8 * stride) + one per-lane 32-bit offset per tensor, so the 8 pieces of a tile
     // share a single VGPR offset (saddr + voffset addressing) instead of 8 precomputed per-lane addresses.
     auto col_of = [&](int t0) { return min(t0 + lcol, L - 4); };
+    auto gcol = [&](int c) { return kRev ? L - 4 - c : c; };            // 4-step group at (reversed) column c -> its first element in memory
+    auto gidx = [&](int t) { return kRev ? L - 1 - t : t; };             // one step
+    auto rv = [](f32x4 v) -> f32x4 {                                     // element order of a group in the kernel's time
+        if constexpr (kRev) return {{v.v[3], v.v[2], v.v[1], v.v[0]}};
+        else return v;
+    };
     auto piece = [&](const T *base, int ds, int i, int col) -> const T * {   // address of piece i of a tile
         if constexpr (kFull) return at(base + i * kRPP * ds, (unsigned)(lrow * ds + col));
         else return at(base, (unsigned)(min(i * kRPP + lrow, nd - 1) * ds + col));   // clamped row: never negative
@@ -267,7 +280,7 @@ __global__ __launch_bounds__(kWave, kScanWaves) void ssm_scan_fwd_kernel(const s
                 *reinterpret_cast<scan_f4 *>(&tileD[tile_off(16 * nb + fq, 4 * mt + fkg)]) = dacc[mt][nb];
     };
     auto issue_loads = [&](int t0) {
-        const int col = col_of(t0);
+        const int col = gcol(col_of(t0));
 #pragma unroll
         for (int i = 0; i < kNP; ++i) {
             ru[i] = ld4<T>(piece(u_base, u_ds, i, col));
@@ -292,8 +305,8 @@ __global__ __launch_bounds__(kWave, kScanWaves) void ssm_scan_fwd_kernel(const s
 #pragma unroll
             for (int i = 0; i < kNP; ++i) {
                 const int row = i * kRPP + lrow;
-                *reinterpret_cast<f32x4 *>(&tileU[tile_off(row, lc4)]) = widen(ru[i]);
-                if constexpr (!kDt) *reinterpret_cast<f32x4 *>(&tileD[tile_off(row, lc4)]) = widen(rd[i]);
+                *reinterpret_cast<f32x4 *>(&tileU[tile_off(row, lc4)]) = rv(widen(ru[i]));
+                if constexpr (!kDt) *reinterpret_cast<f32x4 *>(&tileD[tile_off(row, lc4)]) = rv(widen(rd[i]));
             }
             if constexpr (kDt) {                   // this tile's delta from its x_dbl rows (requested a tile ahead), then the next tile's rows
                 mma_delta();
@@ -303,13 +316,13 @@ __global__ __launch_bounds__(kWave, kScanWaves) void ssm_scan_fwd_kernel(const s
             for (int i = 0; i < kBCPieces; ++i) {
                 const int n = i * kRPP + lrow;
                 if (kN * kLPR % kWave == 0 || n < kN) {
-                    *reinterpret_cast<f32x4 *>(&tileB[n * kTC + lcol]) = widen(rb[i]);
-                    *reinterpret_cast<f32x4 *>(&tileC[n * kTC + lcol]) = widen(rc[i]);
+                    *reinterpret_cast<f32x4 *>(&tileB[n * kTC + lcol]) = rv(widen(rb[i]));
+                    *reinterpret_cast<f32x4 *>(&tileC[n * kTC + lcol]) = rv(widen(rc[i]));
                 }
             }
             if (tile + 1 < n_tiles) issue_loads(t0 + kTC);   // flies under the compute below
             if constexpr (kHasZ) {
-                const int col = col_of(t0);
+                const int col = gcol(col_of(t0));
 #pragma unroll
                 for (int i = 0; i < kNP; ++i) rz[i] = ld4<T>(piece(z_base, z_ds, i, col));
             }
@@ -318,11 +331,11 @@ __global__ __launch_bounds__(kWave, kScanWaves) void ssm_scan_fwd_kernel(const s
             for (int i = 0; i < kTC; ++i) {
                 const int idx = i * kWave + lane, row = idx / kTC, col = idx & (kTC - 1);
                 const bool ok = row < nd && t0 + col < L;
-                tileU[tile_off(row, col >> 2) + (col & 3)] = ok ? to_f32<T>(u_base[(unsigned)(row * u_ds + t0 + col)]) : 0.f;
-                tileD[tile_off(row, col >> 2) + (col & 3)] = ok ? to_f32<T>(dl_base[(unsigned)(row * dl_ds + t0 + col)]) : 0.f;
+                tileU[tile_off(row, col >> 2) + (col & 3)] = ok ? to_f32<T>(u_base[(unsigned)(row * u_ds + gidx(t0 + col))]) : 0.f;
+                tileD[tile_off(row, col >> 2) + (col & 3)] = ok ? to_f32<T>(dl_base[(unsigned)(row * dl_ds + gidx(t0 + col))]) : 0.f;
             }
             for (int idx = lane; idx < kN * kTC; idx += kWave) {
-                const int n = idx / kTC, tc = min(t0 + (idx & (kTC - 1)), L - 1);
+                const int n = idx / kTC, tc = gidx(min(t0 + (idx & (kTC - 1)), L - 1));
                 tileB[idx] = to_f32<T>(Bp[(unsigned)(n * Bns + tc)]);
                 tileC[idx] = to_f32<T>(Cp[(unsigned)(n * Cns + tc)]);
             }
@@ -436,12 +449,28 @@ __global__ __launch_bounds__(kWave, kScanWaves) void ssm_scan_fwd_kernel(const s
                     const int row = i * kRPP + lrow;
                     if (kFull || row < nd) {
                         f32x4 y4 = *reinterpret_cast<const f32x4 *>(&tileU[tile_off(row, lc4)]);
+                        if constexpr (kRev || kAcc) {      // (rv: back to memory order; z was loaded in it)
+                            y4 = rv(y4);
+                            const unsigned gc = (unsigned)gcol(t0 + lcol);
+                            if (has_out) st4<T>(at(out_base + i * kRPP * out_ds, (unsigned)(lrow * out_ds) + gc), y4);
+                            const f32x4 z4 = widen(rz[i]);
+#pragma unroll
+                            for (int s = 0; s < 4; ++s) y4.v[s] *= z4.v[s] * sigmoidf_fast(z4.v[s]);
+                            T *dst = at(oz_base + i * kRPP * oz_ds, (unsigned)(lrow * oz_ds) + gc);
+                            if constexpr (kAcc) {          // (the empty asm keeps the product rounded: out_z = o + round(y silu(z)), no fma)
+                                const f32x4 o4 = widen(ld4<T>(dst));
+#pragma unroll
+                                for (int s = 0; s < 4; ++s) { asm volatile("" : "+v"(y4.v[s])); y4.v[s] = o4.v[s] + y4.v[s]; }
+                            }
+                            st4<T>(dst, y4);
+                        } else {
                         if (has_out) st4<T>(at(out_base + i * kRPP * out_ds, (unsigned)(lrow * out_ds + t0 + lcol)), y4);
                         if constexpr (kHasZ) {
                             const f32x4 z4 = widen(rz[i]);
 #pragma unroll
                             for (int s = 0; s < 4; ++s) y4.v[s] *= z4.v[s] * sigmoidf_fast(z4.v[s]);
                             st4_out_z<T>(oz_base + i * kRPP * oz_ds, oz_planes ? oz_planes + i * kRPP * oz_ds : nullptr, p.out_z_lo_offset, (unsigned)(lrow * oz_ds + t0 + lcol), y4);
+                        }
                         }
                     }
                 }
@@ -451,10 +480,14 @@ __global__ __launch_bounds__(kWave, kScanWaves) void ssm_scan_fwd_kernel(const s
                 const int idx = i * kWave + lane, row = idx / kTC, col = idx & (kTC - 1);
                 if (row < nd && t0 + col < L) {
                     const float yv = tileU[tile_off(row, col >> 2) + (col & 3)];
-                    if (out_base) out_base[(unsigned)(row * out_ds + t0 + col)] = from_f32<T>(yv);
+                    const int tg = gidx(t0 + col);
+                    if (out_base) out_base[(unsigned)(row * out_ds + tg)] = from_f32<T>(yv);
                     if constexpr (kHasZ) {
-                        const float zv = to_f32<T>(z_base[(unsigned)(row * z_ds + t0 + col)]);
-                        oz_base[(unsigned)(row * oz_ds + t0 + col)] = from_f32<T>(yv * zv * sigmoidf_fast(zv));
+                        const float zv = to_f32<T>(z_base[(unsigned)(row * z_ds + tg)]);
+                        float oz = yv * zv * sigmoidf_fast(zv);
+                        if constexpr (kAcc) asm volatile("" : "+v"(oz));
+                        T &dst = oz_base[(unsigned)(row * oz_ds + tg)];
+                        dst = from_f32<T>(kAcc ? to_f32<T>(dst) + oz : oz);
                     }
                 }
             }
@@ -492,6 +525,29 @@ void ssm_scan_fwd_launch_v0(const ssm_args_t &p, hipStream_t stream, int tiles, 
     }
 #undef DIMSUM_LAUNCH
 }
+
+// the reversed direction of the bidirectional scan (bimamba_inner_fn, ssm_scan_fwd.hip): adds its half to the out_z the forward direction
+// (ssm_scan_fwd_launch_v0 on the same stream) has written. 64-channel kernel only; z is required.
+template <typename T, int kN>
+void ssm_scan_fwd_launch_rev(const ssm_args_t &p, hipStream_t stream, int tiles, bool vec, bool full) {
+    const dim3 grid(tiles), block(kWave);
+    const hipEvent_t ev0 = reinterpret_cast<hipEvent_t>(p.timing_start_event), ev1 = reinterpret_cast<hipEvent_t>(p.timing_stop_event);
+#define DIMSUM_LAUNCH(VEC, FULL)                                                                                                                 \
+    do {                                                                                                                                         \
+        if (p.ckpt_ptr) DIMSUM_LAUNCH_EV((ssm_scan_fwd_kernel<T, kN, true, VEC, FULL, true, false, false, true, true>), grid, block, stream, ev0, ev1, p); \
+        else DIMSUM_LAUNCH_EV((ssm_scan_fwd_kernel<T, kN, true, VEC, FULL, false, false, false, true, true>), grid, block, stream, ev0, ev1, p);       \
+    } while (0)
+    if (full) DIMSUM_LAUNCH(true, true);
+    else if (vec) DIMSUM_LAUNCH(true, false);
+    else DIMSUM_LAUNCH(false, false);
+#undef DIMSUM_LAUNCH
+}
+
+#define DIMSUM_INSTANTIATE_FWD_REV(T)                                                               \
+    template void ssm_scan_fwd_launch_rev<T, 4>(const ssm_args_t &, hipStream_t, int, bool, bool);  \
+    template void ssm_scan_fwd_launch_rev<T, 8>(const ssm_args_t &, hipStream_t, int, bool, bool);  \
+    template void ssm_scan_fwd_launch_rev<T, 16>(const ssm_args_t &, hipStream_t, int, bool, bool); \
+    template void ssm_scan_fwd_launch_rev<T, 32>(const ssm_args_t &, hipStream_t, int, bool, bool);
 
 #define DIMSUM_INSTANTIATE_FWD_V0(T)                                                                                \
     template void ssm_scan_fwd_launch_v0<T, 4>(const ssm_args_t &, hipStream_t, int, bool, bool);           \

@@ -32,9 +32,11 @@ template <int CTRL> __device__ __forceinline__ float lanes_dpp(float v) {
     return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), CTRL, 0xF, 0xF, true));
 }
 
-template <typename T, bool kHasZ, bool kVec, bool kFull, bool kCkpt = false>
+// kRev / kAcc: the time-reversed, out_z-accumulating direction of the bidirectional scan, exactly as in ssm_scan_fwd_kernel.hpp
+template <typename T, bool kHasZ, bool kVec, bool kFull, bool kCkpt = false, bool kRev = false, bool kAcc = false>
 __global__ __launch_bounds__(kWave, 4) void ssm_scan_fwd_lanes_kernel(const ssm_args_t p) {
     static_assert(!kFull || kVec, "kFull implies kVec");
+    static_assert(!(kRev || kAcc) || kHasZ, "the bidirectional scan gates with z");
     constexpr int kN = 16;
     // one LDS block [dt * u (then y in place) | dt | B | C]: the sequential loop addresses it with byte offsets formed by ONE
     // v_xor per operand pair (the 16-byte slot index enters lt_off / bc_off by XOR and the row bases have no bits below 256)
@@ -88,15 +90,21 @@ __global__ __launch_bounds__(kWave, 4) void ssm_scan_fwd_lanes_kernel(const ssm_
 
     Raw4<T> ru, rd, rz, rb[4], rc[4];
     auto col_of = [&](int t0) { return min(t0 + lcol, L - 4); };
+    auto gcol = [&](int cc) { return kRev ? L - 4 - cc : cc; };         // 4-step group at (reversed) column cc -> its first element in memory
+    auto gidx = [&](int t) { return kRev ? L - 1 - t : t; };
+    auto rv = [](f32x4 v) -> f32x4 {
+        if constexpr (kRev) return {{v.v[3], v.v[2], v.v[1], v.v[0]}};
+        else return v;
+    };
     auto issue_loads = [&](int t0) {
-        const int col = col_of(t0);
+        const int col = gcol(col_of(t0));
         ru = ld4<T>(at(u_base, (unsigned)(ldrow * u_ds + col)));
         rd = ld4<T>(at(dl_base, (unsigned)(ldrow * dl_ds + col)));
     };
     // only the two HBM streams are requested a tile ahead in registers; B / C (L2-resident: shared by all waves of a batch
     // element) are requested where they are staged -- the other waves of the SIMD cover that latency
     auto issue_bc = [&](int t0) {
-        const int col = col_of(t0);
+        const int col = gcol(col_of(t0));
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             rb[i] = ld4<T>(at(Bp, (unsigned)((i * 4 + lrow) * Bns + col)));
@@ -114,8 +122,8 @@ __global__ __launch_bounds__(kWave, 4) void ssm_scan_fwd_lanes_kernel(const ssm_
         if constexpr (kVec) {
             const bool col_ok = t0 + lcol < L;
             issue_bc(t0);
-            uk = widen(ru);
-            f32x4 vd = widen(rd), vdu;
+            uk = rv(widen(ru));
+            f32x4 vd = rv(widen(rd)), vdu;
             float s = 0.f;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -127,8 +135,8 @@ __global__ __launch_bounds__(kWave, 4) void ssm_scan_fwd_lanes_kernel(const ssm_
             *reinterpret_cast<f32x4 *>(&tileD[lt_off(lrow, lc4)]) = vd;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                *reinterpret_cast<f32x4 *>(&tileB[bc_off(i * 4 + lrow, lc4)]) = widen(rb[i]);
-                *reinterpret_cast<f32x4 *>(&tileC[bc_off(i * 4 + lrow, lc4)]) = widen(rc[i]);
+                *reinterpret_cast<f32x4 *>(&tileB[bc_off(i * 4 + lrow, lc4)]) = rv(widen(rb[i]));
+                *reinterpret_cast<f32x4 *>(&tileC[bc_off(i * 4 + lrow, lc4)]) = rv(widen(rc[i]));
             }
             if (p.x_ptr) {   // row sum over the 16 lanes of the DPP row
                 s += lanes_dpp<0x128>(s);   // row_ror:8
@@ -138,21 +146,21 @@ __global__ __launch_bounds__(kWave, 4) void ssm_scan_fwd_lanes_kernel(const ssm_
                 sum_dt += s;
             }
             if (tile + 1 < n_tiles) issue_loads(t0 + kLT);   // flies under the compute below
-            if constexpr (kHasZ) rz = ld4<T>(at(z_base, (unsigned)(ldrow * z_ds + col_of(t0))));
+            if constexpr (kHasZ) rz = ld4<T>(at(z_base, (unsigned)(ldrow * z_ds + gcol(col_of(t0)))));
         } else {
             for (int i = 0; i < kLC * kLT / kWave; ++i) {
                 const int idx = i * kWave + lane, row = idx / kLT, col = idx & (kLT - 1);
                 const bool ok = row < nd && t0 + col < L;
                 float vu = 0.f, vd = 0.f;
                 if (ok) {
-                    vu = to_f32<T>(u_base[(unsigned)(row * u_ds + t0 + col)]);
-                    vd = softplus_if(to_f32<T>(dl_base[(unsigned)(row * dl_ds + t0 + col)]) + (bias_p ? bias_p[d0 + row] : 0.f), softplus);
+                    vu = to_f32<T>(u_base[(unsigned)(row * u_ds + gidx(t0 + col))]);
+                    vd = softplus_if(to_f32<T>(dl_base[(unsigned)(row * dl_ds + gidx(t0 + col))]) + (bias_p ? bias_p[d0 + row] : 0.f), softplus);
                 }
                 tileU[lt_off(row, col >> 2) + (col & 3)] = vd * vu;
                 tileD[lt_off(row, col >> 2) + (col & 3)] = vd;
             }
             for (int idx = lane; idx < kN * kLT; idx += kWave) {
-                const int r = idx / kLT, col = idx & (kLT - 1), tc = min(t0 + col, L - 1);
+                const int r = idx / kLT, col = idx & (kLT - 1), tc = gidx(min(t0 + col, L - 1));
                 tileB[bc_off(r, col >> 2) + (col & 3)] = to_f32<T>(Bp[(unsigned)(r * Bns + tc)]);
                 tileC[bc_off(r, col >> 2) + (col & 3)] = to_f32<T>(Cp[(unsigned)(r * Cns + tc)]);
             }
@@ -237,6 +245,21 @@ __global__ __launch_bounds__(kWave, 4) void ssm_scan_fwd_lanes_kernel(const ssm_
                 f32x4 y4 = *reinterpret_cast<const f32x4 *>(&tileU[lt_off(lrow, lc4)]);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) y4.v[k] = fmaf(Drow, uk.v[k], y4.v[k]);
+                if constexpr (kRev || kAcc) {      // (rv: back to memory order; z was loaded in it)
+                    y4 = rv(y4);
+                    const unsigned gc = (unsigned)gcol(t0 + lcol);
+                    if (has_out) st4<T>(at(out_base, (unsigned)(lrow * out_ds) + gc), y4);
+                    const f32x4 z4 = widen(rz);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) y4.v[k] *= z4.v[k] * sigmoidf_fast(z4.v[k]);
+                    T *dst = at(oz_base, (unsigned)(lrow * oz_ds) + gc);
+                    if constexpr (kAcc) {          // (the empty asm keeps the product rounded: out_z = o + round(y silu(z)), no fma)
+                        const f32x4 o4 = widen(ld4<T>(dst));
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) { asm volatile("" : "+v"(y4.v[k])); y4.v[k] = o4.v[k] + y4.v[k]; }
+                    }
+                    st4<T>(dst, y4);
+                } else {
                 if (has_out) st4<T>(at(out_base, (unsigned)(lrow * out_ds + t0 + lcol)), y4);
                 if constexpr (kHasZ) {
                     const f32x4 z4 = widen(rz);
@@ -244,17 +267,22 @@ __global__ __launch_bounds__(kWave, 4) void ssm_scan_fwd_lanes_kernel(const ssm_
                     for (int k = 0; k < 4; ++k) y4.v[k] *= z4.v[k] * sigmoidf_fast(z4.v[k]);
                     st4_out_z<T>(oz_base, oz_planes, p.out_z_lo_offset, (unsigned)(lrow * oz_ds + t0 + lcol), y4);
                 }
+                }
             }
         } else {
             for (int i = 0; i < kLC * kLT / kWave; ++i) {
                 const int idx = i * kWave + lane, row = idx / kLT, col = idx & (kLT - 1);
                 if (row < nd && t0 + col < L) {
+                    const int tg = gidx(t0 + col);
                     float yv = tileU[lt_off(row, col >> 2) + (col & 3)];
-                    if (p.D_ptr) yv = fmaf(reinterpret_cast<const float *>(p.D_ptr)[d0 + row], to_f32<T>(u_base[(unsigned)(row * u_ds + t0 + col)]), yv);
-                    if (out_base) out_base[(unsigned)(row * out_ds + t0 + col)] = from_f32<T>(yv);
+                    if (p.D_ptr) yv = fmaf(reinterpret_cast<const float *>(p.D_ptr)[d0 + row], to_f32<T>(u_base[(unsigned)(row * u_ds + tg)]), yv);
+                    if (out_base) out_base[(unsigned)(row * out_ds + tg)] = from_f32<T>(yv);
                     if constexpr (kHasZ) {
-                        const float zv = to_f32<T>(z_base[(unsigned)(row * z_ds + t0 + col)]);
-                        oz_base[(unsigned)(row * oz_ds + t0 + col)] = from_f32<T>(yv * zv * sigmoidf_fast(zv));
+                        const float zv = to_f32<T>(z_base[(unsigned)(row * z_ds + tg)]);
+                        float oz = yv * zv * sigmoidf_fast(zv);
+                        if constexpr (kAcc) asm volatile("" : "+v"(oz));
+                        T &dst = oz_base[(unsigned)(row * oz_ds + tg)];
+                        dst = from_f32<T>(kAcc ? to_f32<T>(dst) + oz : oz);
                     }
                 }
             }
@@ -283,6 +311,25 @@ void ssm_scan_fwd_launch_lanes(const ssm_args_t &p, hipStream_t stream, int tile
     }
 #undef DIMSUM_LAUNCH
 }
+
+// the reversed direction of the bidirectional scan on this kernel (launches too small for the 64-channel kernel; ssm_scan_fwd.hip)
+template <typename T>
+void ssm_scan_fwd_launch_lanes_rev(const ssm_args_t &p, hipStream_t stream, int tiles, bool vec, bool full) {
+    const dim3 grid(tiles), block(kWave);
+    const hipEvent_t ev0 = reinterpret_cast<hipEvent_t>(p.timing_start_event), ev1 = reinterpret_cast<hipEvent_t>(p.timing_stop_event);
+#define DIMSUM_LAUNCH(VEC, FULL)                                                                                                         \
+    do {                                                                                                                                 \
+        if (p.ckpt_ptr) DIMSUM_LAUNCH_EV((ssm_scan_fwd_lanes_kernel<T, true, VEC, FULL, true, true, true>), grid, block, stream, ev0, ev1, p); \
+        else DIMSUM_LAUNCH_EV((ssm_scan_fwd_lanes_kernel<T, true, VEC, FULL, false, true, true>), grid, block, stream, ev0, ev1, p);          \
+    } while (0)
+    if (full) DIMSUM_LAUNCH(true, true);
+    else if (vec) DIMSUM_LAUNCH(true, false);
+    else DIMSUM_LAUNCH(false, false);
+#undef DIMSUM_LAUNCH
+}
+
+#define DIMSUM_INSTANTIATE_FWD_LANES_REV(T) \
+    template void ssm_scan_fwd_launch_lanes_rev<T>(const ssm_args_t &, hipStream_t, int, bool, bool);
 
 #define DIMSUM_INSTANTIATE_FWD_LANES(T) \
     template void ssm_scan_fwd_launch_lanes<T>(const ssm_args_t &, hipStream_t, int, bool, bool);

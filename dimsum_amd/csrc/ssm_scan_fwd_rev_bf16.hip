@@ -1,0 +1,9 @@
+// selective-scan forward, bf16 I/O: the time-reversed kernels of the bidirectional scan (64-channel and one-lane-per-state: kRev / kAcc).
+// A translation unit of its own like ssm_scan_fwd_bf16.hip (the scheduled inner blocks make every instantiation slow to compile).
+#include "ssm_scan_fwd_kernel.hpp"
+#include "ssm_scan_fwd_lanes.hpp"
+
+namespace dimsum {
+DIMSUM_INSTANTIATE_FWD_REV(__hip_bfloat16)
+DIMSUM_INSTANTIATE_FWD_LANES_REV(__hip_bfloat16)
+}  // namespace dimsum

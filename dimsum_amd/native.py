@@ -475,6 +475,120 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, out, dz, de
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# bidirectional selective scan: the two selective_scan_cuda calls of BiMambaInnerFn (mamba/mamba_ssm/ops/selective_scan_interface.py:1010-1388,
+# the second one on .flip(-1) copies) as ONE pair of launches that reads the forward layouts backwards (csrc/ssm_scan_fwd_kernel.hpp, kRev)
+# ---------------------------------------------------------------------------------------------------------------------
+def scan_bidir_fwd_kernel_for(batch, dim, seqlen, dstate, n_groups=1):
+    """which forward scan kernel serves both directions of selective_scan_bidir_fwd (dimsum_ssm_scan_bidir_fwd_variant): 16 = one lane per
+    state where the library picks it for the shape (dstate 16, far too few channels to fill the chip), else 1 = the 64-channel kernel (the
+    state-split kernels have no reversed form); -1 = not served (dstate other than 4, 8, 16, 32)"""
+    P = _lib.SsmBidirParams()
+    F = P.fwd
+    F.batch, F.dim, F.seqlen, F.dstate, F.n_groups, F.n_chunks = batch, dim, seqlen, dstate, n_groups, (seqlen + 2047) // 2048
+    if _scan_fwd_variant:
+        _lib.attach_ext(F, _lib.SsmExt).kernel_variant = _scan_fwd_variant
+    return int(_lib.load().dimsum_ssm_scan_bidir_fwd_variant(P))
+
+
+def _check_bidir(A, A_b, z):
+    _gpu(A_b)
+    _check(z is not None, "selective_scan_bidir: z is required")
+    _check(A_b.dtype == torch.float32 and tuple(A_b.shape) == tuple(A.shape), "selective_scan_bidir: A_b must be float32 of A's shape")
+
+
+def selective_scan_bidir_fwd(u, delta, A, A_b, B, C, D, z, delta_bias, delta_softplus, need_out=True, need_ckpt=False):
+    """-> [out, out_b, out_z, (ckpt, ckpt_b)]: out = the forward-time scan with A, out_b = the reversed-time scan with A_b (both ungated, in
+    forward time order; None unless need_out), out_z = (out + out_b) * silu(z) as out * silu(z) + out_b * silu(z). `need_ckpt` appends both
+    directions' saved states (the reversed one's indexed in reversed time), which selective_scan_bidir_bwd consumes."""
+    _check_ssm(u, delta, A, B, C, D, z, delta_bias)
+    _check_bidir(A, A_b, z)
+    batch, dim, seqlen = u.shape
+    dstate = A.shape[1]
+    _check(dstate in (4, 8, 16, 32), "selective_scan_bidir: dstate must be 4, 8, 16 or 32")
+    out = torch.empty_like(delta) if need_out else None
+    out_b = torch.empty_like(delta) if need_out else None
+    out_z = torch.empty_like(z)
+    ckpt = torch.empty(scan_ckpt_shape(batch, dim, seqlen, dstate), device=u.device, dtype=torch.float32) if need_ckpt else None
+    ckpt_b = torch.empty_like(ckpt) if need_ckpt else None
+    if u.numel() > 0:
+        P = _lib.SsmBidirParams()
+        _fill_ssm(P.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, None, out_z, ckpt)
+        P.A_b_ptr, P.A_b_d_stride, P.A_b_dstate_stride = _ptr(A_b), A_b.stride(0), A_b.stride(1)
+        if out_b is not None:
+            P.out_b_ptr, P.out_b_batch_stride, P.out_b_d_stride = _ptr(out_b), out_b.stride(0), out_b.stride(1)
+        P.ckpt_b_ptr = _ptr(ckpt_b)
+        with torch.cuda.device(u.device):
+            _lib.check(_lib.load().dimsum_ssm_scan_bidir_fwd(P, _stream(u)), "selective_scan_bidir_fwd")
+    res = [out, out_b, out_z]
+    if need_ckpt:
+        res += [ckpt, ckpt_b]
+    return res
+
+
+def selective_scan_bidir_bwd(u, delta, A, A_b, B, C, D, z, delta_bias, dout, out, out_b, ckpt, ckpt_b, delta_softplus, recompute_out_z,
+                             dz=None, dB=None, dC=None):
+    """-> [du, ddelta, dA, dA_b, dB, dC, dD, ddelta_bias, dz, (out_z)]: the gradients of selective_scan_bidir_fwd's out_z, both directions
+    summed (dA / dA_b apart). `out`, `out_b`, `ckpt`, `ckpt_b` are what the forward returned with need_out / need_ckpt. dz may be a
+    caller-provided view (dxz's z half); dB / dC fp32 views of B's / C's shape to be written in place (as in selective_scan_bwd)."""
+    _check_ssm(u, delta, A, B, C, D, z, delta_bias)
+    _check_bidir(A, A_b, z)
+    _gpu(dout, out, out_b, ckpt, ckpt_b, dz)
+    batch, dim, seqlen = u.shape
+    dstate = A.shape[1]
+    _check(tuple(dout.shape) == (batch, dim, seqlen) and dout.dtype == u.dtype and (dout.stride(-1) == 1 or seqlen == 1),
+           "selective_scan_bidir_bwd: bad dout")
+    for t in (out, out_b):
+        _check(t is not None and t.shape == u.shape and t.dtype == u.dtype and t.stride(-1) == 1,
+               "selective_scan_bidir_bwd: `out` and `out_b` of the forward are required")
+    for t in (ckpt, ckpt_b):
+        _check(t is not None and tuple(t.shape) == scan_ckpt_shape(batch, dim, seqlen, dstate) and t.dtype == torch.float32 and t.is_contiguous(),
+               "selective_scan_bidir_bwd: both directions' saved states (need_ckpt=True) are required")
+    if dz is None:
+        dz = torch.empty_like(z)
+    else:
+        _check(dz.shape == z.shape and dz.dtype == z.dtype and dz.stride(-1) == 1, "selective_scan_bidir_bwd: bad dz")
+    out_z = torch.empty_like(out) if recompute_out_z else None
+    du = torch.empty_like(u)
+    ddelta = torch.empty_like(delta)
+    nA, nD = A.numel(), (dim if D is not None else 0)
+    acc = _zeros(2 * nA + nD + (dim if delta_bias is not None else 0), u.device)
+    dA, dA_b = acc[:nA].view(A.shape), acc[nA:2 * nA].view(A.shape)
+    for t, like in ((dB, B), (dC, C)):
+        _check(t is None or (t.shape == like.shape and t.dtype == torch.float32 and t.is_cuda and t.stride(-1) == 1), "selective_scan_bidir_bwd: bad dB / dC buffer")
+    dB = torch.empty(B.shape, device=u.device, dtype=torch.float32) if dB is None else dB
+    dC = torch.empty(C.shape, device=u.device, dtype=torch.float32) if dC is None else dC
+    dD = acc[2 * nA:2 * nA + nD] if D is not None else None
+    ddelta_bias = acc[2 * nA + nD:] if delta_bias is not None else None
+    if u.numel() > 0:
+        P = _lib.SsmBidirBwdParams()
+        Q = P.bwd
+        _fill_ssm(Q.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, None, out_z, ckpt)
+        Q.dout_batch_stride, Q.dout_d_stride = dout.stride(0), dout.stride(1)
+        Q.dA_d_stride, Q.dA_dstate_stride = dA.stride(0), dA.stride(1)
+        Q.dB_batch_stride, Q.dB_group_stride, Q.dB_dstate_stride = dB.stride(0), dB.stride(1), dB.stride(2)
+        Q.dC_batch_stride, Q.dC_group_stride, Q.dC_dstate_stride = dC.stride(0), dC.stride(1), dC.stride(2)
+        Q.du_batch_stride, Q.du_d_stride = du.stride(0), du.stride(1)
+        Q.ddelta_batch_stride, Q.ddelta_d_stride = ddelta.stride(0), ddelta.stride(1)
+        Q.dz_batch_stride, Q.dz_d_stride = dz.stride(0), dz.stride(1)
+        Q.dout_ptr, Q.dA_ptr, Q.dB_ptr, Q.dC_ptr, Q.dD_ptr = _ptr(dout), _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD)
+        Q.du_ptr, Q.dz_ptr, Q.ddelta_ptr, Q.ddelta_bias_ptr = _ptr(du), _ptr(dz), _ptr(ddelta), _ptr(ddelta_bias)
+        P.A_b_ptr, P.A_b_d_stride, P.A_b_dstate_stride = _ptr(A_b), A_b.stride(0), A_b.stride(1)
+        P.out_b_ptr, P.out_b_batch_stride, P.out_b_d_stride = _ptr(out_b), out_b.stride(0), out_b.stride(1)
+        P.ckpt_b_ptr = _ptr(ckpt_b)
+        P.dA_b_ptr, P.dA_b_d_stride, P.dA_b_dstate_stride = _ptr(dA_b), dA_b.stride(0), dA_b.stride(1)
+        lib = _lib.load()
+        nbytes = lib.dimsum_ssm_scan_bwd_workspace_bytes(batch, dim, seqlen, dstate, B.shape[1]) - ckpt.numel() * 4    # partial dB / dC only
+        ws = torch.empty((nbytes + 3) // 4, device=u.device, dtype=torch.float32)
+        Q.workspace_ptr, Q.workspace_bytes = _ptr(ws), nbytes
+        with torch.cuda.device(u.device):
+            _lib.check(lib.dimsum_ssm_scan_bidir_bwd(P, _stream(u)), "selective_scan_bidir_bwd")
+    res = [du, ddelta, dA, dA_b, dB.to(B.dtype), dC.to(C.dtype), dD, ddelta_bias, dz]
+    if out_z is not None:
+        res.append(out_z)
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # fused token-space transform (csrc/token_transform.hip) and GatedMLP epilogue
 # ---------------------------------------------------------------------------------------------------------------------
 _TT_KIND = {("none", True): 0, ("none", False): 0, ("haar", True): 1, ("haar", False): 2, ("dct", True): 3, ("dct", False): 4}

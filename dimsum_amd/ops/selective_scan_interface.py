@@ -4,6 +4,7 @@ return conventions as mamba/mamba_ssm/ops/selective_scan_interface.py, implement
   selective_scan_fn                      <- :94-101   (SelectiveScanFn :12-91)
   mamba_inner_fn[_cond]                  <- :1277-1348 (MambaInnerFn :579-790, MambaInnerFnCond :793-1007)
   mamba_inner_fn_no_out_proj[_cond]      <- :1389-1452 (MambaInnerFnNoOutProj[Cond] :174-576)
+  bimamba_inner_fn                       <- :1351-1388 (BiMambaInnerFn :1010-1274), on the bidirectional scan (native.selective_scan_bidir_*)
 
 The four fused variants of the reference are four near-identical 200-line classes; here they are ONE Function with two
 switches (out-projection, conditional conv entry). Semantics kept: checkpoint_lvl=1 recomputation of conv1d_out and
@@ -371,6 +372,125 @@ def mamba_inner_fn_no_out_proj_cond(xz, conv1d_weight, conv1d_bias, x_proj_weigh
                              _will_backprop(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, init_states))
 
 
-def bimamba_inner_fn(*args, **kwargs):
-    raise NotImplementedError("bimamba_inner_fn is defined by the reference but never called by its modules "
-                              "(mamba_simple.py uses two mamba_inner_fn_no_out_proj calls for scan_type='v2')")
+class _BiMambaInner(torch.autograd.Function):
+    """conv1d(silu) -> x_proj -> dt_proj -> forward scan (A) + time-reversed scan (A_b) over the same operands, each gated by silu(z), summed ->
+    out_proj (BiMambaInnerFn, mamba/mamba_ssm/ops/selective_scan_interface.py:1010-1388). The reference runs the second scan on .flip(-1)
+    copies of u, delta, B, C, z and flips its output back; here both directions are one bidirectional launch pair that reads the forward
+    layouts backwards (native.selective_scan_bidir_fwd / _bwd). x_proj is written transposed, (R + 2N, b l), as in _MambaInner's training
+    layout: B and C are read in place and the backward writes dB / dC straight into the rows of d x_dbl^T.
+    Gradients are those of bimamba_inner_ref (:1503-1561): the reference's backward drops the reversed direction's part of dz (it returns a
+    dxz whose z half holds only the forward direction's dz, :1171-1190 / :1218 / :1257); this one does not."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda")
+    def forward(ctx, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
+                A, A_b, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus, checkpoint_lvl, need_ckpt):
+        assert checkpoint_lvl in (0, 1)
+        if A.is_complex() or A_b.is_complex():
+            raise NotImplementedError("bimamba_inner_fn: complex A is outside this build's scope")
+        if B is not None or C is not None:
+            raise NotImplementedError("bimamba_inner_fn: constant B/C is outside this build's scope")
+        native._gpu(xz, conv1d_weight, x_proj_weight, delta_proj_weight, out_proj_weight, A, A_b)
+        L = xz.shape[-1]
+        R = delta_proj_weight.shape[1]
+        N = A.shape[-1]
+        if torch.is_autocast_enabled("cuda"):
+            adt = torch.get_autocast_dtype("cuda")
+            x_proj_weight, delta_proj_weight, out_proj_weight = x_proj_weight.to(adt), delta_proj_weight.to(adt), out_proj_weight.to(adt)
+            out_proj_bias = out_proj_bias.to(adt) if out_proj_bias is not None else None
+        xz = _last_contig(xz)
+        conv_w = conv1d_weight.reshape(conv1d_weight.shape[0], conv1d_weight.shape[-1])     # "d 1 w -> d w"
+        conv_b = conv1d_bias.contiguous() if conv1d_bias is not None else None
+        x, z = xz.chunk(2, dim=1)
+        bsz, d_inner = x.shape[0], x.shape[1]
+        # shared by both directions (the reference's too); written d-major, so that x_proj reads its (d, b l) rows without a transposing copy
+        conv_out = native.causal_conv1d_fwd(x, conv_w, conv_b, True, out=x.new_empty(d_inner, bsz, L).permute(1, 0, 2))
+        conv_rows = _rows(conv_out)
+        conv_rows = conv_rows if conv_rows.stride(1) == 1 else conv_rows.contiguous()
+        x_dbl = x_proj_weight @ conv_rows                                                            # (R + 2N, b l)
+        delta = (delta_proj_weight @ x_dbl[:R]).view(d_inner, bsz, L).permute(1, 0, 2)               # (b, d, l), strides (L, bL, 1)
+        Bm, Cm = x_dbl[R:R + N], x_dbl[R + N:]
+        if B_proj_bias is not None:
+            Bm = Bm + B_proj_bias.to(Bm.dtype)[:, None]
+        if C_proj_bias is not None:
+            Cm = Cm + C_proj_bias.to(Cm.dtype)[:, None]
+        Bm = Bm.view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)                                        # (b, 1, N, l) views, unit stride along l
+        Cm = Cm.view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)
+        D = D.contiguous() if D is not None else None
+        A, A_b = A.contiguous(), A_b.contiguous()
+        out, out_b, out_z, *ck = native.selective_scan_bidir_fwd(conv_out, delta, A, A_b, Bm, Cm, D, z, delta_bias, delta_softplus,
+                                                                need_out=need_ckpt, need_ckpt=need_ckpt)
+        if out_proj_bias is None:
+            y = gemm.linear(out_z.transpose(1, 2), out_proj_weight)                                    # (b, l, d_model)
+        else:
+            y = F.linear(out_z.transpose(1, 2), out_proj_weight, out_proj_bias)
+        if not need_ckpt:
+            return y
+        ctx.delta_softplus, ctx.checkpoint_lvl = delta_softplus, checkpoint_lvl
+        ctx.flags = (conv1d_bias is not None, D is not None, delta_bias is not None, B_proj_bias is not None,
+                     C_proj_bias is not None, out_proj_bias is not None)
+        if checkpoint_lvl >= 1:
+            conv_out, delta = None, None            # recomputed in the backward (:1095-1096)
+        keep_out_z = os.environ.get("DIMSUM_RECOMPUTE_OUT_Z", "0") != "1"
+        ctx.save_for_backward(xz, conv_w, conv_b, x_dbl, x_proj_weight, delta_proj_weight, out_proj_weight, conv_out, delta, A, A_b, Bm, Cm,
+                              D, delta_bias, out, out_b, ck[0], ck[1], out_z if keep_out_z else None)
+        return y
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, dout):
+        (xz, conv_w, conv_b, x_dbl, x_proj_weight, delta_proj_weight, out_proj_weight, conv_out, delta, A, A_b, Bm, Cm, D, delta_bias,
+         out, out_b, ckpt, ckpt_b, kept_out_z) = ctx.saved_tensors
+        has_conv_b, has_D, has_dbias, has_Bb, has_Cb, has_ob = ctx.flags
+        L = xz.shape[-1]
+        R = delta_proj_weight.shape[1]
+        N = A.shape[-1]
+        x, z = xz.chunk(2, dim=1)
+        bsz, d_inner = x.shape[0], x.shape[1]
+        dout = _last_contig(dout)
+        if ctx.checkpoint_lvl == 1:
+            conv_out = native.causal_conv1d_fwd(x, conv_w, conv_b, True)
+            delta = (delta_proj_weight @ x_dbl[:R]).view(d_inner, bsz, L).permute(1, 0, 2)
+        dxz = torch.empty_like(xz)
+        dx, dz = dxz.chunk(2, dim=1)
+        dout2 = dout.reshape(bsz * L, -1).t()                                                          # "b l e -> e (b l)"
+        dout_y = (out_proj_weight.t() @ dout2).view(d_inner, bsz, L).permute(1, 0, 2)                 # d-major like delta
+        recompute = kept_out_z is None
+        dx_dbl = torch.empty_like(x_dbl)                                                               # (R + 2N, b l)
+        into = {}
+        if x_dbl.dtype == torch.float32:     # dB / dC land in rows R .. R + 2N of d x_dbl^T (the kernel's dB / dC are fp32)
+            into = {"dB": dx_dbl[R:R + N].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1), "dC": dx_dbl[R + N:].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)}
+        # dz: both directions' parts, written into dxz's z half (the reference keeps only the forward direction's there)
+        du, ddelta, dA, dA_b, dB, dC, dD, ddelta_bias, dz, *rest = native.selective_scan_bidir_bwd(
+            conv_out, delta, A, A_b, Bm, Cm, D, z, delta_bias, dout_y, out, out_b, ckpt, ckpt_b, ctx.delta_softplus, recompute, dz=dz, **into)
+        if not into:
+            dx_dbl[R:R + N] = dB.squeeze(1).permute(1, 0, 2).reshape(N, bsz * L)
+            dx_dbl[R + N:] = dC.squeeze(1).permute(1, 0, 2).reshape(N, bsz * L)
+        out_z = rest[0] if recompute else kept_out_z
+        dB_proj_bias = dx_dbl[R:R + N].float().sum(1) if has_Bb else None
+        dC_proj_bias = dx_dbl[R + N:].float().sum(1) if has_Cb else None
+        # "eB,dB->ed": a (d_model, d_inner) output over a b*l-long reduction
+        dout_proj_weight = gemm.mm_nn_rows(_rows(out_z), dout.reshape(bsz * L, -1)).t()
+        dout_proj_bias = dout.sum(dim=(0, 1)) if has_ob else None
+        ddelta2, conv_rows = _rows(ddelta), _rows(conv_out)                                             # (d, b l) views
+        conv_rows = conv_rows if conv_rows.stride(1) == 1 else conv_rows.contiguous()
+        ddelta_proj_weight = gemm.mm_nt_rows(ddelta2, x_dbl[:R])                                        # "dB,rB->dr", sliced reduction
+        torch.mm(delta_proj_weight.t(), ddelta2, out=dx_dbl[:R])                                        # "dr,dB->rB"
+        dx_proj_weight = gemm.mm_nt_rows(dx_dbl, conv_rows)                                             # "rB,dB->rd", sliced reduction
+        dconv2 = _rows(du)                      # (d, b l) view of the scan's own du: the product is added in place
+        dconv2 = dconv2.addmm_(x_proj_weight.t(), dx_dbl) if dconv2.stride(1) == 1 else torch.addmm(dconv2, x_proj_weight.t(), dx_dbl)
+        dconv_out = dconv2.view(d_inner, bsz, L).permute(1, 0, 2)
+        _, dconv_w, dconv_b = native.causal_conv1d_bwd(x, conv_w, conv_b, dconv_out, dx, True)
+        return (dxz, dconv_w.unsqueeze(1), dconv_b if has_conv_b else None, dx_proj_weight, ddelta_proj_weight,
+                dout_proj_weight, dout_proj_bias, dA, dA_b, None, None, dD if has_D else None,
+                ddelta_bias if has_dbias else None,
+                dB_proj_bias.to(Bm.dtype) if has_Bb else None, dC_proj_bias.to(Cm.dtype) if has_Cb else None, None, None, None)
+
+
+def bimamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, A_b,
+                     B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True):
+    """the fused bidirectional Mamba mixer (selective_scan_interface.py:1351-1388): real A / A_b, input-dependent B / C, -> (b, l, d_model)"""
+    wb = _will_backprop(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, A_b, B, C, D,
+                        delta_bias, B_proj_bias, C_proj_bias)
+    return _BiMambaInner.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
+                               A, A_b, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus, _checkpoint_lvl(), wb)

@@ -6,6 +6,7 @@
  *
  *   dimsum_ssm_scan_fwd        <- selective_scan_cuda.fwd      mamba/csrc/selective_scan/selective_scan.cpp:226-336
  *   dimsum_ssm_scan_bwd        <- selective_scan_cuda.bwd      mamba/csrc/selective_scan/selective_scan.cpp:338-492
+ *   dimsum_ssm_scan_bidir_fwd / _bwd <- the two selective_scan_cuda calls (+ flips) of BiMambaInnerFn  mamba/mamba_ssm/ops/selective_scan_interface.py:1010-1388
  *   dimsum_causal_conv1d_fwd   <- causal_conv1d_cuda.causal_conv1d_fwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:221-336
  *   dimsum_causal_conv1d_bwd   <- causal_conv1d_cuda.causal_conv1d_bwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:338-509
  *   dimsum_norm_fwd / _bwd     <- _layer_norm_fwd / _layer_norm_bwd (Triton)     mamba/mamba_ssm/ops/triton/layernorm.py:120-364
@@ -24,7 +25,7 @@
  *     (the reference raises RuntimeError from TORCH_CHECK at the same places).
  *   - innermost (sequence / feature) stride must be 1 for every activation tensor, like selective_scan.cpp:252-253.
  *
- * Versioning (ABI 17). Every parameter struct starts with `struct_size`: sizeof() of the struct AS THE CALLER COMPILED IT. An entry point
+ * Versioning (ABI 18). Every parameter struct starts with `struct_size`: sizeof() of the struct AS THE CALLER COMPILED IT. An entry point
  * whose struct_size differs from the library's own sizeof returns DIMSUM_ERR_ABI before it reads anything else -- a caller built against an
  * older or newer header can never make a kernel read past its struct. (Inside the *_bwd_params_t structs only the outer struct_size is
  * checked; `fwd.struct_size` is ignored, `fwd.ext` is honoured.)
@@ -44,7 +45,7 @@
 extern "C" {
 #endif
 
-#define DIMSUM_ABI_VERSION 17
+#define DIMSUM_ABI_VERSION 18
 
 typedef enum {
     DIMSUM_OK = 0,
@@ -185,6 +186,49 @@ int64_t dimsum_ssm_scan_bwd_workspace_bytes(int32_t batch, int32_t dim, int32_t 
  *  16 = ssm_scan_fwd_lanes_kernel  lane = (channel, state), 4 channels per wave, dstate 16 (fewer channels still)
  * -1 on invalid parameters. */
 int dimsum_ssm_scan_fwd_variant(const dimsum_ssm_params_t *p);
+
+/* Bidirectional selective scan (bimamba_inner_fn): a forward-time scan with A and a reversed-time scan with A_b over the SAME u, delta, B, C,
+ * z, D, delta_bias, summed:  out_z = out * silu(z) + out_b * silu(z), where
+ *   out[t]   = C_t.h_t + D u_t,   h_t = exp(dt_t A) h_{t-1} + dt_t B_t u_t
+ *   out_b[t] = C_t.g_t + D u_t,   g_t = exp(dt_t A_b) g_{t+1} + dt_t B_t u_t      (D u counted once per direction, as the reference does)
+ * No reversed copy of any operand is made: the reversed direction reads the forward layouts backwards. One out_z store per direction, the
+ * second one adding to the first (fixed order). z is required; x_ptr must be NULL; the inference fusions of the extension struct: split-bf16 /
+ * fp16 out_z, fused dt_proj, are DIMSUM_ERR_UNSUPPORTED; kernel_variant is ignored: see dimsum_ssm_scan_bidir_fwd_variant. */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_ssm_bidir_params_t) */
+    uint32_t reserved;         /* 0 */
+    dimsum_ssm_params_t fwd;   /* the shared operands + the forward direction: A_ptr = its A, out_ptr = its `out` (or NULL), out_z_ptr = the SUM;
+                                  fwd.ext->ckpt_ptr = its saved states (or NULL). fwd.struct_size is ignored, fwd.ext is honoured */
+    const void *A_b_ptr;       /* (dim, dstate) f32: A of the reversed direction */
+    int64_t A_b_d_stride, A_b_dstate_stride;
+    void *out_b_ptr;           /* the reversed direction's `out` in FORWARD time order (or NULL; training callers keep it for the backward) */
+    int64_t out_b_batch_stride, out_b_d_stride;
+    void *ckpt_b_ptr;          /* its saved states (or NULL): (batch, ceil(seqlen/8), dstate, dim) f32, indexed in REVERSED time */
+} dimsum_ssm_bidir_params_t;
+
+/* The matching backward. du, ddelta, dz, dB, dC, dD, ddelta_bias receive the sum over both directions (dB / dC fully overwritten, fixed
+ * order: no atomics); dA and dA_b stay apart. bwd.fwd.out_z_ptr != NULL recomputes the summed out_z. Both directions' saved states are
+ * required (bwd.fwd.ext->ckpt_ptr, ckpt_b_ptr); the workspace needs only the partial dB / dC part:
+ * dimsum_ssm_scan_bwd_workspace_bytes(...) - batch * ceil(seqlen/8) * dstate * dim * 4 bytes. */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_ssm_bidir_bwd_params_t) */
+    uint32_t reserved;         /* 0 */
+    dimsum_ssm_bwd_params_t bwd;   /* as for dimsum_ssm_scan_bwd, forward direction (bwd.struct_size is ignored) */
+    const void *A_b_ptr;
+    int64_t A_b_d_stride, A_b_dstate_stride;
+    const void *out_b_ptr;     /* the reversed direction's `out` of the forward call (forward time order) */
+    int64_t out_b_batch_stride, out_b_d_stride;
+    const void *ckpt_b_ptr;    /* the reversed direction's saved states of the forward call */
+    void *dA_b_ptr;            /* (dim, dstate) f32, zero-filled by the caller, accumulated with atomics */
+    int64_t dA_b_d_stride, dA_b_dstate_stride;
+} dimsum_ssm_bidir_bwd_params_t;
+
+int dimsum_ssm_scan_bidir_fwd(const dimsum_ssm_bidir_params_t *p, void *stream);
+int dimsum_ssm_scan_bidir_bwd(const dimsum_ssm_bidir_bwd_params_t *p, void *stream);
+/* which forward kernel serves both directions (lanes per channel, as dimsum_ssm_scan_fwd_variant; fwd.ext->kernel_variant honoured the same
+ * way): 16 = one lane per state where that is the choice for the shape (dstate 16, launches far too small to fill the chip), else 1 = the
+ * 64-channel kernel -- the state-split kernels have no reversed form; -1 on invalid parameters (a wrong struct_size included) */
+int dimsum_ssm_scan_bidir_fwd_variant(const dimsum_ssm_bidir_params_t *p);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Causal depthwise conv1d, width 2..4, optional bias, optional SiLU.  Mirrors ConvParamsBase / ConvParamsBwd

@@ -272,6 +272,39 @@ def gen_inner(ns):
          **{"g_" + k: v.grad for k, v in p.items()})
 
 
+def gen_bimamba(ns):
+    """bimamba_inner_ref (selective_scan_interface.py:1503-1561) fwd + autograd (the true derivative: BiMambaInnerFn.backward drops the
+    reversed direction's dz), routed to the reference's own refs. Case 1: width 4, dstate 16, dt_rank 3, out_proj / B / C proj biases;
+    case 2: the reference test's width 3, dstate 8, dt_rank 48 (test_selective_scan.py:312-396) at a smaller dim."""
+    for name, (B, Dm, L, N, W, R, biases, seed) in {
+        "bimamba_w4_n16": (2, 48, 96, 16, 4, 3, True, 0),
+        "bimamba_w3_n8": (2, 64, 77, 8, 3, 48, False, 1),
+    }.items():
+        torch.manual_seed(seed)
+        D = 2 * Dm
+        xz = torch.randn(B, 2 * D, L, requires_grad=True)
+        p = dict(
+            conv_w=torch.randn(D, 1, W) * 0.5, conv_b=torch.randn(D) * 0.1,
+            x_proj_w=torch.randn(R + 2 * N, D) / D ** 0.5, dt_proj_w=torch.randn(D, R) / R ** 0.5,
+            out_proj_w=torch.randn(Dm, D) / D ** 0.5,
+            A=-torch.exp(torch.log(torch.arange(1, N + 1).float()).repeat(D, 1) + 0.1 * torch.randn(D, N)),
+            A_b=-torch.exp(torch.log(torch.arange(1, N + 1).float()).repeat(D, 1) + 0.1 * torch.randn(D, N)),
+            Dv=1 + 0.1 * torch.randn(D), dt_bias=torch.randn(D) * 0.5 - 4.0,
+        )
+        if biases:
+            p.update(out_proj_b=0.1 * torch.randn(Dm), B_proj_b=0.1 * torch.randn(N), C_proj_b=0.1 * torch.randn(N))
+        for v in p.values():
+            v.requires_grad_()
+        out = ns.ssi.bimamba_inner_ref(xz, p["conv_w"], p["conv_b"], p["x_proj_w"], p["dt_proj_w"], p["out_proj_w"], p.get("out_proj_b"),
+                                       p["A"], p["A_b"], None, None, p["Dv"], delta_bias=p["dt_bias"], B_proj_bias=p.get("B_proj_b"),
+                                       C_proj_bias=p.get("C_proj_b"), delta_softplus=True)
+        g = torch.randn_like(out)
+        out.backward(g)
+        save(name, "bimamba_inner_ref fwd+autograd (mamba/mamba_ssm/ops/selective_scan_interface.py:1503-1561)",
+             xz=xz, out=out, dout=g, dxz=xz.grad, **{k: v for k, v in p.items()},
+             **{"g_" + k: v.grad for k, v in p.items()})
+
+
 def gen_mixer(ns):
     """CondMamba / Mamba slow path (mamba_simple.py:562-701) incl. the zigzag gather semantics of :627-657."""
     for name, kw in {
@@ -554,7 +587,7 @@ def main():
     steps = {
         "scan": lambda: gen_scan(ns), "conv": lambda: gen_conv(ns), "norm": lambda: gen_norm(ns),
         "perm": lambda: gen_perm(ns), "orders": lambda: gen_block_orders(ns), "wavelet": lambda: gen_wavelet_dct(ns),
-        "fusion": lambda: gen_fusion(ns), "inner": lambda: gen_inner(ns), "mixer": lambda: gen_mixer(ns),
+        "fusion": lambda: gen_fusion(ns), "inner": lambda: gen_inner(ns), "bimamba": lambda: gen_bimamba(ns), "mixer": lambda: gen_mixer(ns),
         "block": lambda: gen_block(ns), "tiny": lambda: gen_models(ns, {"tiny"}),
         "S2": lambda: gen_models(ns, {"model_S2"}), "L2": lambda: gen_models(ns, {"model_L2"}),
         "XL2": lambda: gen_models(ns, {"model_XL2_512"}),
