@@ -72,6 +72,17 @@ class SsmBidirBwdParams(_Sized):
                 ("dA_b_ptr", vp), ("dA_b_d_stride", i64), ("dA_b_dstate_stride", i64)]
 
 
+class OptimParams(_Sized):
+    """dimsum_optim_params_t: device tables of the tensor list + hyper-parameters of one clip / AdamW / EMA step"""
+    _fields_ = ([("struct_size", u32), ("n_tensors", i32), ("n_chunks", i32), ("n_partials", i32)]
+                + [(n, vp) for n in ("p_ptrs", "g_ptrs", "m_ptrs", "v_ptrs", "ema_ptrs", "step_ptrs", "numel", "chunk_table", "partials", "total_norm")]
+                + [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm", "ema_decay")]
+                + [("reserved", i64 * 4)])
+
+
+OPTIM_CHUNK, OPTIM_MAX_PARTIALS = 4096, 2048       # DIMSUM_OPTIM_CHUNK, DIMSUM_OPTIM_MAX_PARTIALS
+
+
 class ConvParams(_Sized):
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "dim", "seqlen", "width", "silu_activation", "dtype", "reserved")]
                 + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "weight_c_stride", "weight_width_stride",
@@ -157,6 +168,7 @@ EXPORTS = (
     "dimsum_event_create", "dimsum_event_destroy", "dimsum_event_elapsed_ms",
     "dimsum_ssm_scan_fwd", "dimsum_ssm_scan_bwd", "dimsum_ssm_scan_bwd_workspace_bytes", "dimsum_ssm_scan_fwd_variant",
     "dimsum_ssm_scan_bidir_fwd", "dimsum_ssm_scan_bidir_bwd", "dimsum_ssm_scan_bidir_fwd_variant",
+    "dimsum_optim_grad_sumsq", "dimsum_optim_adamw_ema_step", "dimsum_optim_write_ptrs",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
@@ -185,6 +197,7 @@ def load():
         lib.dimsum_event_elapsed_ms.restype, lib.dimsum_event_elapsed_ms.argtypes = C.c_float, [vp, vp]
     for name, ptype in (("dimsum_ssm_scan_fwd", SsmParams), ("dimsum_ssm_scan_bwd", SsmBwdParams),
                         ("dimsum_ssm_scan_bidir_fwd", SsmBidirParams), ("dimsum_ssm_scan_bidir_bwd", SsmBidirBwdParams),
+                        ("dimsum_optim_grad_sumsq", OptimParams), ("dimsum_optim_adamw_ema_step", OptimParams),
                         ("dimsum_causal_conv1d_fwd", ConvParams), ("dimsum_causal_conv1d_bwd", ConvBwdParams),
                         ("dimsum_norm_fwd", NormParams), ("dimsum_norm_bwd", NormBwdParams),
                         ("dimsum_token_transform", TtParams), ("dimsum_xattn_fusion_fwd", XattnParams),
@@ -199,6 +212,9 @@ def load():
             fn = getattr(lib, name)
             fn.restype = C.c_int
             fn.argtypes = [vp] * nptr + [i64, i64, vp]
+    if hasattr(lib, "dimsum_optim_write_ptrs"):
+        lib.dimsum_optim_write_ptrs.restype = C.c_int
+        lib.dimsum_optim_write_ptrs.argtypes = [vp, i64, C.POINTER(vp), i32, vp]
     if hasattr(lib, "dimsum_gated_gelu_bwd_f16s"):
         lib.dimsum_gated_gelu_bwd_f16s.restype = C.c_int
         lib.dimsum_gated_gelu_bwd_f16s.argtypes = [vp] * 6 + [i64, i64, vp]

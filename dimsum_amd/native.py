@@ -1355,3 +1355,45 @@ def xattn_fusion_bwd(qkv1, qkv2, out, lse, dout, heads, bias1=None, bias2=None, 
         with torch.cuda.device(qkv1.device):
             _lib.check(_lib.load().dimsum_xattn_fusion_bwd(Q, _stream(qkv1)), "xattn_fusion_bwd")
     return dqkv1, dqkv2
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the tail of a training step: clip_grad_norm_ + AdamW.step + update_ema over a tensor list (dimsum_optim_*; dimsum_amd/optim.py is the user)
+# ---------------------------------------------------------------------------------------------------------------------
+def optim_tables(numels, device):
+    """the part of the device tables that depends on the tensor sizes only -> (numel int64 (n), chunk table int32 (n_chunks, 2)): one row
+    (tensor, chunk number within the tensor) per DIMSUM_OPTIM_CHUNK elements, in list order"""
+    _check(len(numels) > 0 and all(int(n) > 0 for n in numels), "optim_tables: a non-empty list of non-empty tensors is required")
+    n = torch.tensor([int(v) for v in numels], dtype=torch.int64)
+    per = (n + _lib.OPTIM_CHUNK - 1) // _lib.OPTIM_CHUNK
+    _check(int(per.sum()) < 2 ** 31 and int(per.max()) < 2 ** 31, "optim_tables: too many chunks for int32 indices")
+    tensor = torch.repeat_interleave(torch.arange(len(numels), dtype=torch.int64), per)
+    first = torch.cumsum(per, 0) - per
+    chunk = torch.arange(int(per.sum()), dtype=torch.int64) - first[tensor]
+    return n.to(device), torch.stack([tensor, chunk], 1).to(torch.int32).contiguous().to(device)
+
+
+def optim_write_ptrs(table, first, ptrs):
+    """table[first + i] = ptrs[i] (device int64 tensor <- host integers), ordered on the current stream: the values travel as kernel arguments, so
+    there is no staging buffer to overwrite too early and no synchronisation"""
+    _gpu(table)
+    _check(table.dtype == torch.int64 and table.is_contiguous() and 0 <= first and first + len(ptrs) <= table.numel(),
+           "optim_write_ptrs: the table is a contiguous int64 tensor that holds [first, first + len(ptrs))")
+    if not ptrs:
+        return
+    lib = _lib.load()
+    arr = (_lib.vp * len(ptrs))(*ptrs)
+    with torch.cuda.device(table.device):
+        _lib.check(lib.dimsum_optim_write_ptrs(table.data_ptr(), first, arr, len(ptrs), _stream(table)), "dimsum_optim_write_ptrs")
+
+
+def optim_grad_sumsq(P, device):
+    """dimsum_optim_grad_sumsq on the current stream of `device`; P: a filled _lib.OptimParams"""
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().dimsum_optim_grad_sumsq(P, torch.cuda.current_stream(device).cuda_stream), "dimsum_optim_grad_sumsq")
+
+
+def optim_adamw_ema_step(P, device):
+    """dimsum_optim_adamw_ema_step on the current stream of `device`"""
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().dimsum_optim_adamw_ema_step(P, torch.cuda.current_stream(device).cuda_stream), "dimsum_optim_adamw_ema_step")

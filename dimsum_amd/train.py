@@ -41,6 +41,9 @@ def train_step(model, ema, opt, transport, x, y, max_grad_norm=2.0, ema_decay=0.
     loss = transport.training_losses(model, x, dict(y=y))["loss"].mean()
     opt.zero_grad(set_to_none=True)
     loss.backward()
+    if hasattr(opt, "step_fused"):               # dimsum_amd.optim.FusedAdamWEMA: clip -> AdamW -> EMA as two launches; .grad stays unclipped
+        opt.step_fused(max_grad_norm, ema_decay)
+        return loss.detach()
     torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
     opt.step()
     update_ema(ema, model.module if hasattr(model, "module") else model, ema_decay)
@@ -71,14 +74,23 @@ def load_checkpoint(path, model, ema=None, opt=None, map_location="cpu", lr=None
     return ck.get("epoch", 0), ck.get("train_steps", 0)
 
 
-def build_training(model, device, lr=1e-4, world_size=1, device_ids=None):
-    """-> (ddp_or_model, ema, opt): EMA is a frozen deep copy initialised from the weights every rank agrees on."""
+def build_training(model, device, lr=1e-4, world_size=1, device_ids=None, fused_step=None):
+    """-> (ddp_or_model, ema, opt): EMA is a frozen deep copy initialised from the weights every rank agrees on.
+    `fused_step`: the optimizer is a dimsum_amd.optim.FusedAdamWEMA with the EMA attached, and train_step runs its tail (clip, AdamW, EMA) on
+    the library's two launches; None reads DIMSUM_FUSED_STEP (default "0": torch's AdamW, as before)."""
+    if fused_step is None:
+        fused_step = os.environ.get("DIMSUM_FUSED_STEP", "0") != "0"
     ema = copy.deepcopy(model).to(device)
     requires_grad(ema, False)
     if world_size > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=device_ids, find_unused_parameters=False)
     fused = os.environ.get("DIMSUM_FUSED_ADAMW", "1") != "0" and torch.device(device).type == "cuda"
-    opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=0, fused=fused)      # one multi-tensor kernel for the whole step
+    if fused_step:
+        from .optim import FusedAdamWEMA
+        opt = FusedAdamWEMA(model.parameters(), lr=lr, weight_decay=0)
+        opt.attach_ema(model, ema)
+    else:
+        opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=0, fused=fused)      # one multi-tensor kernel for the whole step
     update_ema(ema, model.module if hasattr(model, "module") else model, decay=0)
     ema.eval()
     return model, ema, opt

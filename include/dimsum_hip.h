@@ -7,6 +7,7 @@
  *   dimsum_ssm_scan_fwd        <- selective_scan_cuda.fwd      mamba/csrc/selective_scan/selective_scan.cpp:226-336
  *   dimsum_ssm_scan_bwd        <- selective_scan_cuda.bwd      mamba/csrc/selective_scan/selective_scan.cpp:338-492
  *   dimsum_ssm_scan_bidir_fwd / _bwd <- the two selective_scan_cuda calls (+ flips) of BiMambaInnerFn  mamba/mamba_ssm/ops/selective_scan_interface.py:1010-1388
+ *   dimsum_optim_grad_sumsq / dimsum_optim_adamw_ema_step <- clip_grad_norm_ + AdamW.step + update_ema   dimsum/train.py:55-64,317-321
  *   dimsum_causal_conv1d_fwd   <- causal_conv1d_cuda.causal_conv1d_fwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:221-336
  *   dimsum_causal_conv1d_bwd   <- causal_conv1d_cuda.causal_conv1d_bwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:338-509
  *   dimsum_norm_fwd / _bwd     <- _layer_norm_fwd / _layer_norm_bwd (Triton)     mamba/mamba_ssm/ops/triton/layernorm.py:120-364
@@ -229,6 +230,53 @@ int dimsum_ssm_scan_bidir_bwd(const dimsum_ssm_bidir_bwd_params_t *p, void *stre
  * way): 16 = one lane per state where that is the choice for the shape (dstate 16, launches far too small to fill the chip), else 1 = the
  * 64-channel kernel -- the state-split kernels have no reversed form; -1 on invalid parameters (a wrong struct_size included) */
 int dimsum_ssm_scan_bidir_fwd_variant(const dimsum_ssm_bidir_params_t *p);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Training-step tail: global gradient-norm clip + AdamW + parameter EMA over a list of fp32 tensors, two launches
+ * (<- torch.nn.utils.clip_grad_norm_, torch.optim.AdamW.step and update_ema of dimsum/train.py:55-64,317-321).
+ * Added under ABI 18 (new symbols only). One struct serves both calls. Everything it points to is DEVICE memory:
+ *   p_ptrs, g_ptrs, m_ptrs, v_ptrs, ema_ptrs, step_ptrs : n_tensors pointers each (tensor t: contiguous fp32 of numel[t] elements at any
+ *       4-byte-aligned address; step_ptrs[t]: ONE fp32, the count of updates so far -- torch's fused AdamW state layout)
+ *       g_ptrs[t] NULL: tensor t takes no part in the norm, p / m / v / step stay untouched (m / v / step pointers may be NULL), only the EMA blends.
+ *       ema_ptrs NULL, or ema_ptrs[t] NULL: no EMA (for that tensor).
+ *   numel       : n_tensors int64
+ *   chunk_table : n_chunks pairs of int32 (tensor index, chunk number c within that tensor): elements [c, c + 1) * DIMSUM_OPTIM_CHUNK of the tensor.
+ *       One workgroup works on one chunk at a time, chunk i on workgroup i % grid: the order of every sum is a function of the tables alone
+ *       (not of addresses or alignment), so equal gradients give bit-equal norms on every run and every rank.
+ *   partials    : n_partials floats (1 .. DIMSUM_OPTIM_MAX_PARTIALS), written by dimsum_optim_grad_sumsq (one per workgroup), read by the step
+ *   total_norm  : one float (or NULL), written by the step: sqrt of the sum of squares of all gradients
+ * dimsum_optim_grad_sumsq: partials[w] = workgroup w's share of sum g^2, and step[t] += 1 for every tensor with a gradient (one lane per tensor:
+ *   the step kernel only reads the counters). partials NULL: only the counters advance (a step without norm).
+ * dimsum_optim_adamw_ema_step, with clip = min(1, max_norm / (total_norm + 1e-6)) (max_norm <= 0 or partials NULL: 1), g' = clip g, t = step[tensor]:
+ *   p = p (1 - lr weight_decay);  m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2
+ *   p = p - lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps);  ema = ema_decay ema + (1 - ema_decay) p
+ *   g is only read. A NaN norm makes clip NaN (torch's clip_grad_norm_ with error_if_nonfinite=False).
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DIMSUM_OPTIM_CHUNK 4096
+#define DIMSUM_OPTIM_MAX_PARTIALS 2048
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_optim_params_t) */
+    int32_t n_tensors;
+    int32_t n_chunks;
+    int32_t n_partials;
+    const void *p_ptrs, *g_ptrs, *m_ptrs, *v_ptrs, *ema_ptrs, *step_ptrs;
+    const void *numel;
+    const void *chunk_table;
+    void *partials;
+    void *total_norm;
+    double lr, beta1, beta2, eps, weight_decay;
+    double max_norm;           /* <= 0: no clipping */
+    double ema_decay;
+    int64_t reserved[4];       /* 0 */
+} dimsum_optim_params_t;
+
+int dimsum_optim_grad_sumsq(const dimsum_optim_params_t *p, void *stream);
+int dimsum_optim_adamw_ema_step(const dimsum_optim_params_t *p, void *stream);
+/* dst_table[first + i] = src[i], i < count: `src` is HOST memory, read before the call returns (the values travel as kernel arguments,
+ * DIMSUM_OPTIM_PTRS_PER_LAUNCH per launch), the writes are ordered on `stream` like any kernel -- how a caller refreshes g_ptrs every step
+ * (autograd allocates new gradients) without a synchronisation or a staging buffer that a later step could overwrite too early. */
+#define DIMSUM_OPTIM_PTRS_PER_LAUNCH 448
+int dimsum_optim_write_ptrs(void *dst_table, int64_t first, const void *const *src, int32_t count, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Causal depthwise conv1d, width 2..4, optional bias, optional SiLU.  Mirrors ConvParamsBase / ConvParamsBwd
