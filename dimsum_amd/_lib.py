@@ -175,6 +175,36 @@ EXPORTS = (
     "dimsum_gemm_nt", "dimsum_gemm_nt_kernel_for", "dimsum_gemm_tn", "dimsum_gemm_nn", "dimsum_row_factors", "dimsum_rows_block_f16s", "dimsum_rows_f16s", "dimsum_rows_f16s_multi",
 )
 
+_P = C.POINTER
+# (symbol, restype, argtypes) of every function load() binds
+_SIGNATURES = (
+    [("dimsum_status_string", C.c_char_p, [C.c_int]), ("dimsum_target_arch", C.c_char_p, None), ("dimsum_abi_version", C.c_int, None),
+     ("dimsum_event_create", vp, []), ("dimsum_event_destroy", None, [vp]), ("dimsum_event_elapsed_ms", C.c_float, [vp, vp])]
+    # the launches that take one parameter struct and a stream
+    + [(name, C.c_int, [_P(ptype), vp]) for name, ptype in (
+        ("dimsum_ssm_scan_fwd", SsmParams), ("dimsum_ssm_scan_bwd", SsmBwdParams), ("dimsum_ssm_scan_bidir_fwd", SsmBidirParams),
+        ("dimsum_ssm_scan_bidir_bwd", SsmBidirBwdParams), ("dimsum_optim_grad_sumsq", OptimParams), ("dimsum_optim_adamw_ema_step", OptimParams),
+        ("dimsum_causal_conv1d_fwd", ConvParams), ("dimsum_causal_conv1d_bwd", ConvBwdParams), ("dimsum_norm_fwd", NormParams),
+        ("dimsum_norm_bwd", NormBwdParams), ("dimsum_token_transform", TtParams), ("dimsum_xattn_fusion_fwd", XattnParams),
+        ("dimsum_xattn_fusion_bwd", XattnBwdParams), ("dimsum_gemm_nt", GemmParams))]
+    # the gated-GeLU passes: n pointers, rows, cols, stream
+    + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
+        ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),
+        ("dimsum_gated_gelu_bwd_pair", 5), ("dimsum_gated_gelu_bwd_f16s", 6))]
+    + [("dimsum_optim_write_ptrs", C.c_int, [vp, i64, _P(vp), i32, vp]),
+       ("dimsum_gemm_nt_kernel_for", C.c_int, [_P(GemmParams)]),
+       ("dimsum_gemm_tn", C.c_int, [_P(GemmParams), i32, i64, vp]),
+       ("dimsum_gemm_nn", C.c_int, [_P(GemmParams), i32, i64, vp]),
+       ("dimsum_rows_block_f16s", C.c_int, [vp, i64, i64, i64, vp, i64, vp, i64, vp]),
+       ("dimsum_row_factors", C.c_int, [vp, vp, i64, vp, vp, vp]),
+       ("dimsum_split3", C.c_int, [vp, i64, i64, i64, vp, i32, vp]),
+       ("dimsum_split3_t", C.c_int, [vp, i64, i64, i64, vp, vp]),
+       ("dimsum_rows_f16s", C.c_int, [vp, i64, i64, i64, vp, i64, vp, vp, vp]),
+       ("dimsum_rows_f16s_multi", C.c_int, [_P(F16sJob), i32, vp]),
+       ("dimsum_ssm_scan_bwd_workspace_bytes", i64, [i32] * 5),
+       ("dimsum_ssm_scan_fwd_variant", C.c_int, [_P(SsmParams)]),
+       ("dimsum_ssm_scan_bidir_fwd_variant", C.c_int, [_P(SsmBidirParams)])])
+
 _lib = None
 
 
@@ -187,73 +217,10 @@ def load():
         raise RuntimeError(f"dimsum_amd: {LIB_PATH} not found. Build it with `python -c 'import __graft_entry__ as g; "
                            f"g.build()'` or `make -C dimsum_amd/csrc`. There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    lib.dimsum_status_string.restype = C.c_char_p
-    lib.dimsum_status_string.argtypes = [C.c_int]
-    lib.dimsum_target_arch.restype = C.c_char_p
-    lib.dimsum_abi_version.restype = C.c_int
-    if hasattr(lib, "dimsum_event_create"):
-        lib.dimsum_event_create.restype, lib.dimsum_event_create.argtypes = vp, []
-        lib.dimsum_event_destroy.restype, lib.dimsum_event_destroy.argtypes = None, [vp]
-        lib.dimsum_event_elapsed_ms.restype, lib.dimsum_event_elapsed_ms.argtypes = C.c_float, [vp, vp]
-    for name, ptype in (("dimsum_ssm_scan_fwd", SsmParams), ("dimsum_ssm_scan_bwd", SsmBwdParams),
-                        ("dimsum_ssm_scan_bidir_fwd", SsmBidirParams), ("dimsum_ssm_scan_bidir_bwd", SsmBidirBwdParams),
-                        ("dimsum_optim_grad_sumsq", OptimParams), ("dimsum_optim_adamw_ema_step", OptimParams),
-                        ("dimsum_causal_conv1d_fwd", ConvParams), ("dimsum_causal_conv1d_bwd", ConvBwdParams),
-                        ("dimsum_norm_fwd", NormParams), ("dimsum_norm_bwd", NormBwdParams),
-                        ("dimsum_token_transform", TtParams), ("dimsum_xattn_fusion_fwd", XattnParams),
-                        ("dimsum_xattn_fusion_bwd", XattnBwdParams), ("dimsum_gemm_nt", GemmParams)):
-        if hasattr(lib, name):
+    for name, restype, argtypes in _SIGNATURES:
+        if hasattr(lib, name):               # a library that misses a symbol is an older ABI: the version check below says so
             fn = getattr(lib, name)
-            fn.restype = C.c_int
-            fn.argtypes = [C.POINTER(ptype), vp]
-    for name, nptr in (("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3),
-                       ("dimsum_gated_gelu_bwd_split3", 5), ("dimsum_gated_gelu_bwd_pair", 5)):
-        if hasattr(lib, name):
-            fn = getattr(lib, name)
-            fn.restype = C.c_int
-            fn.argtypes = [vp] * nptr + [i64, i64, vp]
-    if hasattr(lib, "dimsum_optim_write_ptrs"):
-        lib.dimsum_optim_write_ptrs.restype = C.c_int
-        lib.dimsum_optim_write_ptrs.argtypes = [vp, i64, C.POINTER(vp), i32, vp]
-    if hasattr(lib, "dimsum_gated_gelu_bwd_f16s"):
-        lib.dimsum_gated_gelu_bwd_f16s.restype = C.c_int
-        lib.dimsum_gated_gelu_bwd_f16s.argtypes = [vp] * 6 + [i64, i64, vp]
-    if hasattr(lib, "dimsum_gemm_nt_kernel_for"):
-        lib.dimsum_gemm_nt_kernel_for.restype = C.c_int
-        lib.dimsum_gemm_nt_kernel_for.argtypes = [C.POINTER(GemmParams)]
-    if hasattr(lib, "dimsum_gemm_tn"):
-        lib.dimsum_gemm_tn.restype = C.c_int
-        lib.dimsum_gemm_tn.argtypes = [C.POINTER(GemmParams), i32, i64, vp]
-    if hasattr(lib, "dimsum_rows_block_f16s"):
-        lib.dimsum_rows_block_f16s.restype = C.c_int
-        lib.dimsum_rows_block_f16s.argtypes = [vp, i64, i64, i64, vp, i64, vp, i64, vp]
-    if hasattr(lib, "dimsum_row_factors"):
-        lib.dimsum_row_factors.restype = C.c_int
-        lib.dimsum_row_factors.argtypes = [vp, vp, i64, vp, vp, vp]
-    if hasattr(lib, "dimsum_gemm_nn"):
-        lib.dimsum_gemm_nn.restype = C.c_int
-        lib.dimsum_gemm_nn.argtypes = [C.POINTER(GemmParams), i32, i64, vp]
-    if hasattr(lib, "dimsum_split3"):
-        lib.dimsum_split3.restype = C.c_int
-        lib.dimsum_split3.argtypes = [vp, i64, i64, i64, vp, i32, vp]
-    if hasattr(lib, "dimsum_split3_t"):
-        lib.dimsum_split3_t.restype = C.c_int
-        lib.dimsum_split3_t.argtypes = [vp, i64, i64, i64, vp, vp]
-    if hasattr(lib, "dimsum_rows_f16s"):
-        lib.dimsum_rows_f16s.restype = C.c_int
-        lib.dimsum_rows_f16s.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, vp]
-    if hasattr(lib, "dimsum_rows_f16s_multi"):
-        lib.dimsum_rows_f16s_multi.restype = C.c_int
-        lib.dimsum_rows_f16s_multi.argtypes = [C.POINTER(F16sJob), i32, vp]
-    if hasattr(lib, "dimsum_ssm_scan_bwd_workspace_bytes"):
-        lib.dimsum_ssm_scan_bwd_workspace_bytes.restype = i64
-        lib.dimsum_ssm_scan_bwd_workspace_bytes.argtypes = [i32] * 5
-    if hasattr(lib, "dimsum_ssm_scan_fwd_variant"):
-        lib.dimsum_ssm_scan_fwd_variant.restype = C.c_int
-        lib.dimsum_ssm_scan_fwd_variant.argtypes = [C.POINTER(SsmParams)]
-    if hasattr(lib, "dimsum_ssm_scan_bidir_fwd_variant"):
-        lib.dimsum_ssm_scan_bidir_fwd_variant.restype = C.c_int
-        lib.dimsum_ssm_scan_bidir_fwd_variant.argtypes = [C.POINTER(SsmBidirParams)]
+            fn.restype, fn.argtypes = restype, argtypes
     if lib.dimsum_abi_version() != 18:
         raise RuntimeError("dimsum_amd: libdimsum_hip.so ABI version mismatch; rebuild")
     _lib = lib

@@ -36,7 +36,7 @@
 //     LDS: 4 x 11 KB + 4.6 KB per workgroup; two __syncthreads() per 32-step tile.
 #include <type_traits>
 
-#include "common.hpp"
+#include "ssm_scan_host.hpp"
 
 namespace dimsum {
 
@@ -710,17 +710,15 @@ static int launch_bwd(const ssm_bwd_args_t &q, const float *ckpt, float *part, h
     const int dpg = p.dim / p.n_groups;
     constexpr int kWC = kBW * kBC;            // channels per workgroup
     const int tiles = p.batch * p.n_groups * ((dpg + kWC - 1) / kWC);
-    const size_t va = 4 * sizeof(T);
-    auto ok4 = [&](const void *ptr, int64_t bs, int64_t ds) { return aligned_to<T>(ptr, va) && bs % 4 == 0 && ds % 4 == 0; };
-    bool vec = (p.seqlen % 4 == 0) && ok4(p.u_ptr, p.u_batch_stride, p.u_d_stride) && ok4(p.delta_ptr, p.delta_batch_stride, p.delta_d_stride) &&
-               ok4(q.dout_ptr, q.dout_batch_stride, q.dout_d_stride) && ok4(q.du_ptr, q.du_batch_stride, q.du_d_stride) &&
-               ok4(q.ddelta_ptr, q.ddelta_batch_stride, q.ddelta_d_stride) &&
-               ok4(p.B_ptr, p.B_batch_stride, p.B_dstate_stride) && ok4(p.C_ptr, p.C_batch_stride, p.C_dstate_stride) &&
+    bool vec = (p.seqlen % 4 == 0) && ssm_vec4_ok<T>(p.u_ptr, p.u_batch_stride, p.u_d_stride) && ssm_vec4_ok<T>(p.delta_ptr, p.delta_batch_stride, p.delta_d_stride) &&
+               ssm_vec4_ok<T>(q.dout_ptr, q.dout_batch_stride, q.dout_d_stride) && ssm_vec4_ok<T>(q.du_ptr, q.du_batch_stride, q.du_d_stride) &&
+               ssm_vec4_ok<T>(q.ddelta_ptr, q.ddelta_batch_stride, q.ddelta_d_stride) &&
+               ssm_vec4_ok<T>(p.B_ptr, p.B_batch_stride, p.B_dstate_stride) && ssm_vec4_ok<T>(p.C_ptr, p.C_batch_stride, p.C_dstate_stride) &&
                p.B_group_stride % 4 == 0 && p.C_group_stride % 4 == 0;
     if (p.z_ptr) {
-        vec = vec && ok4(p.z_ptr, p.z_batch_stride, p.z_d_stride) && ok4(p.out_ptr, p.out_batch_stride, p.out_d_stride) &&
-              ok4(q.dz_ptr, q.dz_batch_stride, q.dz_d_stride);
-        if (p.out_z_ptr) vec = vec && ok4(p.out_z_ptr, p.out_z_batch_stride, p.out_z_d_stride);
+        vec = vec && ssm_vec4_ok<T>(p.z_ptr, p.z_batch_stride, p.z_d_stride) && ssm_vec4_ok<T>(p.out_ptr, p.out_batch_stride, p.out_d_stride) &&
+              ssm_vec4_ok<T>(q.dz_ptr, q.dz_batch_stride, q.dz_d_stride);
+        if (p.out_z_ptr) vec = vec && ssm_vec4_ok<T>(p.out_z_ptr, p.out_z_batch_stride, p.out_z_d_stride);
     }
     // in-tile offsets are 32-bit BYTE offsets (saddr + voffset addressing), see offsets_fit_32bit()
     if (!offsets_fit_32bit<T>(p.seqlen, kBC, {p.u_d_stride, p.delta_d_stride, q.dout_d_stride, q.du_d_stride, q.ddelta_d_stride,
@@ -733,20 +731,9 @@ static int launch_bwd(const ssm_bwd_args_t &q, const float *ckpt, float *part, h
     const hipEvent_t ev1 = reinterpret_cast<hipEvent_t>(p.timing_stop_event), none = nullptr;   // end of the reduce kernel
 #define DIMSUM_LAUNCH(HASZ, VEC, FULL) \
     DIMSUM_LAUNCH_EV((ssm_scan_bwd_kernel<T, kN, HASZ, VEC, FULL, kRev>), grid, block, stream, ev0, none, q, ckpt, part)
-    if constexpr (kRev) {
-        if (!p.z_ptr) return DIMSUM_ERR_NULL;
-        if (full) DIMSUM_LAUNCH(true, true, true);
-        else if (vec) DIMSUM_LAUNCH(true, true, false);
-        else DIMSUM_LAUNCH(true, false, false);
-    } else if (p.z_ptr) {
-        if (full) DIMSUM_LAUNCH(true, true, true);
-        else if (vec) DIMSUM_LAUNCH(true, true, false);
-        else DIMSUM_LAUNCH(true, false, false);
-    } else {
-        if (full) DIMSUM_LAUNCH(false, true, true);
-        else if (vec) DIMSUM_LAUNCH(false, true, false);
-        else DIMSUM_LAUNCH(false, false, false);
-    }
+    if (kRev && !p.z_ptr) return DIMSUM_ERR_NULL;
+    if (p.z_ptr) DIMSUM_VEC_FULL_LADDER(DIMSUM_LAUNCH, true, vec, full);
+    else if constexpr (!kRev) DIMSUM_VEC_FULL_LADDER(DIMSUM_LAUNCH, false, vec, full);       // (the reversed kernels exist with z only)
 #undef DIMSUM_LAUNCH
     if (launch_status() != DIMSUM_OK) return DIMSUM_ERR_LAUNCH;
     const int64_t total = (int64_t)p.batch * p.n_groups * 2 * kN * ((p.seqlen + 3) / 4);
@@ -759,45 +746,28 @@ static int launch_bwd(const ssm_bwd_args_t &q, const float *ckpt, float *part, h
     return launch_status();
 }
 
-template <typename T, bool kRev = false>
-static int dispatch_bwd(const ssm_bwd_args_t &q, const float *ckpt, float *part, hipStream_t stream, hipEvent_t ev0) {
-    switch (q.fwd.dstate) {
-        case 4: return launch_bwd<T, 4, kRev>(q, ckpt, part, stream, ev0);
-        case 8: return launch_bwd<T, 8, kRev>(q, ckpt, part, stream, ev0);
-        case 32: return launch_bwd<T, 32, kRev>(q, ckpt, part, stream, ev0);
-        case 16: return launch_bwd<T, 16, kRev>(q, ckpt, part, stream, ev0);
-        default: return DIMSUM_ERR_SHAPE;
-    }
+template <bool kRev>
+static int dispatch_bwd(const ssm_bwd_args_t &q, const void *states, hipStream_t stream, hipEvent_t ev0) {
+    const float *ckpt = reinterpret_cast<const float *>(states);
+    float *part = reinterpret_cast<float *>(q.workspace_ptr);
+    return ssm_dispatch(q.fwd.dtype, q.fwd.dstate, [&](auto t, auto n) { return launch_bwd<DIMSUM_TAG_T(t), DIMSUM_TAG_N(n), kRev>(q, ckpt, part, stream, ev0); });
 }
 
-int ssm_check(const ssm_args_t *p, bool forward);
-
-}  // namespace dimsum
-
-static int64_t partial_bytes(int32_t batch, int32_t dim, int32_t seqlen, int32_t dstate, int32_t n_groups) {
+// workspace = [per-workgroup partial dB / dC | saved states (only when the caller did not keep the forward's)]
+int64_t ssm_bwd_partial_bytes(int32_t batch, int32_t dim, int32_t seqlen, int32_t dstate, int32_t n_groups) {
     const int64_t dpg = dim / n_groups;
-    const int64_t wgs = (int64_t)batch * n_groups * ((dpg + dimsum::kBW * dimsum::kBC - 1) / (dimsum::kBW * dimsum::kBC));
+    const int64_t wgs = (int64_t)batch * n_groups * ((dpg + kBW * kBC - 1) / (kBW * kBC));
     return wgs * 2 * dstate * seqlen * (int64_t)sizeof(float);                      // (workgroups, dB | dC, dstate, seqlen)
 }
-static int64_t ckpt_bytes(int32_t batch, int32_t dim, int32_t seqlen, int32_t dstate) {
-    const int64_t n_halves = (seqlen + dimsum::kBS - 1) / dimsum::kBS;
+int64_t ssm_bwd_ckpt_bytes(int32_t batch, int32_t dim, int32_t seqlen, int32_t dstate) {
+    const int64_t n_halves = (seqlen + kBS - 1) / kBS;
     return (int64_t)batch * n_halves * dstate * dim * (int64_t)sizeof(float);       // (batch, half tiles, dstate, dim)
 }
 
-extern "C" int64_t dimsum_ssm_scan_bwd_workspace_bytes(int32_t batch, int32_t dim, int32_t seqlen, int32_t dstate, int32_t n_groups) {
-    if (batch <= 0 || dim <= 0 || seqlen <= 0 || dstate <= 0 || n_groups <= 0 || dim % n_groups != 0) return 0;
-    return partial_bytes(batch, dim, seqlen, dstate, n_groups) + ckpt_bytes(batch, dim, seqlen, dstate);
-}
-
-namespace dimsum { int ssm_scan_fwd_run(const ssm_args_t &a, hipStream_t s); }
-
 // public backward struct -> flat block (the size of `pub` itself is checked by the caller)
-static int bwd_args_from(const dimsum_ssm_bwd_params_t *pub, dimsum::ssm_bwd_args_t &flat) {
-    using namespace dimsum;
-    {
-        const int arc = ssm_args_from(&pub->fwd, flat.fwd, false);
-        if (arc != DIMSUM_OK) return arc;
-    }
+static int bwd_args_from(const dimsum_ssm_bwd_params_t *pub, ssm_bwd_args_t &flat) {
+    const int arc = ssm_args_from(&pub->fwd, flat.fwd, false);
+    if (arc != DIMSUM_OK) return arc;
     flat.dout_batch_stride = pub->dout_batch_stride; flat.dout_d_stride = pub->dout_d_stride;
     flat.dA_d_stride = pub->dA_d_stride; flat.dA_dstate_stride = pub->dA_dstate_stride;
     flat.dB_batch_stride = pub->dB_batch_stride; flat.dB_group_stride = pub->dB_group_stride; flat.dB_dstate_stride = pub->dB_dstate_stride;
@@ -811,46 +781,49 @@ static int bwd_args_from(const dimsum_ssm_bwd_params_t *pub, dimsum::ssm_bwd_arg
     return DIMSUM_OK;
 }
 
+// what both backward entry points ask of a flat block after ssm_check: the required pointers, z => dz and the forward's `out`, a 16-byte
+// aligned workspace -- in this order
+static int bwd_check(const ssm_bwd_args_t &q) {
+    if (!q.dout_ptr || !q.dA_ptr || !q.dB_ptr || !q.dC_ptr || !q.du_ptr || !q.ddelta_ptr || !q.workspace_ptr) return DIMSUM_ERR_NULL;
+    if (q.fwd.z_ptr && (!q.dz_ptr || !q.fwd.out_ptr)) return DIMSUM_ERR_NULL;
+    if (!aligned_to<float>(q.workspace_ptr, 16)) return DIMSUM_ERR_STRIDE;
+    return DIMSUM_OK;
+}
+
+}  // namespace dimsum
+
+extern "C" int64_t dimsum_ssm_scan_bwd_workspace_bytes(int32_t batch, int32_t dim, int32_t seqlen, int32_t dstate, int32_t n_groups) {
+    if (batch <= 0 || dim <= 0 || seqlen <= 0 || dstate <= 0 || n_groups <= 0 || dim % n_groups != 0) return 0;
+    return dimsum::ssm_bwd_partial_bytes(batch, dim, seqlen, dstate, n_groups) + dimsum::ssm_bwd_ckpt_bytes(batch, dim, seqlen, dstate);
+}
+
 extern "C" int dimsum_ssm_scan_bwd(const dimsum_ssm_bwd_params_t *pub, void *stream) {
     using namespace dimsum;
     if (!pub) return DIMSUM_ERR_NULL;
     if (pub->struct_size != sizeof(dimsum_ssm_bwd_params_t)) return DIMSUM_ERR_ABI;
-    ssm_bwd_args_t flat;
-    {
-        const int arc = bwd_args_from(pub, flat);
-        if (arc != DIMSUM_OK) return arc;
-    }
-    const ssm_bwd_args_t *q = &flat;
-    const int rc = ssm_check(&q->fwd, false);
+    ssm_bwd_args_t q;
+    int rc = bwd_args_from(pub, q);
+    if (rc == DIMSUM_OK) rc = ssm_check(q.fwd, false);
+    if (rc == DIMSUM_OK) rc = bwd_check(q);
     if (rc != DIMSUM_OK) return rc;
-    if (!q->dout_ptr || !q->dA_ptr || !q->dB_ptr || !q->dC_ptr || !q->du_ptr || !q->ddelta_ptr || !q->workspace_ptr) return DIMSUM_ERR_NULL;
-    if (q->fwd.z_ptr && (!q->dz_ptr || !q->fwd.out_ptr)) return DIMSUM_ERR_NULL;
-    const ssm_args_t &p = q->fwd;
-    if (!aligned_to<float>(q->workspace_ptr, 16)) return DIMSUM_ERR_STRIDE;
-    // workspace = [per-wave partial dB / dC | saved states (only when the caller did not keep the forward's)]
-    const int64_t pbytes = partial_bytes(p.batch, p.dim, p.seqlen, p.dstate, p.n_groups);
-    const float *ckpt = reinterpret_cast<const float *>(p.ckpt_ptr);
-    if (q->workspace_bytes < pbytes + (ckpt ? 0 : ckpt_bytes(p.batch, p.dim, p.seqlen, p.dstate))) return DIMSUM_ERR_SHAPE;
-    float *part = reinterpret_cast<float *>(q->workspace_ptr);
+    const ssm_args_t &p = q.fwd;
+    const int64_t pbytes = ssm_bwd_partial_bytes(p.batch, p.dim, p.seqlen, p.dstate, p.n_groups);
+    if (q.workspace_bytes < pbytes + (p.ckpt_ptr ? 0 : ssm_bwd_ckpt_bytes(p.batch, p.dim, p.seqlen, p.dstate))) return DIMSUM_ERR_SHAPE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipEvent_t ev0 = reinterpret_cast<hipEvent_t>(p.timing_start_event);     // begin of the call's FIRST kernel
-    if (!ckpt) {
+    const void *states = p.ckpt_ptr;
+    if (!states) {
         // reference-shaped call (no saved states): one state-only forward sweep rebuilds them in the workspace
         ssm_args_t f = p;
         f.z_ptr = nullptr; f.out_ptr = nullptr; f.out_z_ptr = nullptr; f.x_ptr = nullptr; f.D_ptr = nullptr;
-        f.ckpt_ptr = reinterpret_cast<char *>(q->workspace_ptr) + pbytes;
+        f.ckpt_ptr = reinterpret_cast<char *>(q.workspace_ptr) + pbytes;
         f.timing_stop_event = nullptr;          // (the sweep's begin is the call's begin; its end is not the call's end)
-        const int frc = ssm_scan_fwd_run(f, reinterpret_cast<hipStream_t>(stream));
+        const int frc = ssm_scan_fwd_run(f, s);
         if (frc != DIMSUM_OK) return frc;
         ev0 = nullptr;
-        ckpt = reinterpret_cast<const float *>(f.ckpt_ptr);
+        states = f.ckpt_ptr;
     }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (p.dtype) {
-        case DIMSUM_F32: return dispatch_bwd<float>(*q, ckpt, part, s, ev0);
-        case DIMSUM_F16: return dispatch_bwd<__half>(*q, ckpt, part, s, ev0);
-        case DIMSUM_BF16: return dispatch_bwd<__hip_bfloat16>(*q, ckpt, part, s, ev0);
-        default: return DIMSUM_ERR_DTYPE;
-    }
+    return dispatch_bwd<false>(q, states, s, ev0);
 }
 
 // Bidirectional backward (bimamba_inner_fn): the forward direction on the plain kernels (du, ddelta, dz, dB, dC, out_z written), then the
@@ -861,41 +834,23 @@ extern "C" int dimsum_ssm_scan_bidir_bwd(const dimsum_ssm_bidir_bwd_params_t *pu
     if (!pub) return DIMSUM_ERR_NULL;
     if (pub->struct_size != sizeof(dimsum_ssm_bidir_bwd_params_t)) return DIMSUM_ERR_ABI;
     ssm_bwd_args_t qf;
-    {
-        const int arc = bwd_args_from(&pub->bwd, qf);
-        if (arc != DIMSUM_OK) return arc;
-    }
-    if (qf.fwd.dt_w_ptr || qf.fwd.out_z_lo_offset || qf.fwd.out_z_f16) return DIMSUM_ERR_UNSUPPORTED;
-    const int rc = ssm_check(&qf.fwd, false);
+    int rc = bwd_args_from(&pub->bwd, qf);
     if (rc != DIMSUM_OK) return rc;
-    if (!qf.dout_ptr || !qf.dA_ptr || !qf.dB_ptr || !qf.dC_ptr || !qf.du_ptr || !qf.ddelta_ptr || !qf.workspace_ptr) return DIMSUM_ERR_NULL;
-    if (!qf.fwd.z_ptr || !qf.dz_ptr || !qf.fwd.out_ptr || !qf.fwd.ckpt_ptr) return DIMSUM_ERR_NULL;
+    ssm_args_t &p = qf.fwd;
+    if (p.dt_w_ptr || p.out_z_lo_offset || p.out_z_f16) return DIMSUM_ERR_UNSUPPORTED;
+    rc = ssm_check(p, false);
+    if (rc != DIMSUM_OK) return rc;
+    // (every refusal of bwd_check before its alignment test is DIMSUM_ERR_NULL too: the status does not depend on where these two lines stand)
+    if (!p.z_ptr || !p.ckpt_ptr) return DIMSUM_ERR_NULL;
     if (!pub->A_b_ptr || !pub->out_b_ptr || !pub->ckpt_b_ptr || !pub->dA_b_ptr) return DIMSUM_ERR_NULL;
-    if (!aligned_to<float>(qf.workspace_ptr, 16)) return DIMSUM_ERR_STRIDE;
-    const ssm_args_t &p = qf.fwd;
-    if (qf.workspace_bytes < partial_bytes(p.batch, p.dim, p.seqlen, p.dstate, p.n_groups)) return DIMSUM_ERR_SHAPE;
-    ssm_bwd_args_t qb = qf;
-    qb.fwd.A_ptr = pub->A_b_ptr; qb.fwd.A_d_stride = pub->A_b_d_stride; qb.fwd.A_dstate_stride = pub->A_b_dstate_stride;
-    qb.fwd.out_ptr = const_cast<void *>(pub->out_b_ptr); qb.fwd.out_batch_stride = pub->out_b_batch_stride; qb.fwd.out_d_stride = pub->out_b_d_stride;
-    qb.fwd.ckpt_ptr = const_cast<void *>(pub->ckpt_b_ptr);
-    qb.dA_ptr = pub->dA_b_ptr; qb.dA_d_stride = pub->dA_b_d_stride; qb.dA_dstate_stride = pub->dA_b_dstate_stride;
-    qf.fwd.timing_stop_event = nullptr;         // the events bracket the whole call: begin of the first kernel, end of the last
-    qb.fwd.timing_start_event = nullptr;
-    float *part = reinterpret_cast<float *>(qf.workspace_ptr);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = bwd_check(qf);
+    if (rc != DIMSUM_OK) return rc;
+    if (qf.workspace_bytes < ssm_bwd_partial_bytes(p.batch, p.dim, p.seqlen, p.dstate, p.n_groups)) return DIMSUM_ERR_SHAPE;
     const hipEvent_t ev0 = reinterpret_cast<hipEvent_t>(p.timing_start_event);
-    int frc;
-    switch (p.dtype) {
-        case DIMSUM_F32: frc = dispatch_bwd<float>(qf, reinterpret_cast<const float *>(qf.fwd.ckpt_ptr), part, s, ev0); break;
-        case DIMSUM_F16: frc = dispatch_bwd<__half>(qf, reinterpret_cast<const float *>(qf.fwd.ckpt_ptr), part, s, ev0); break;
-        case DIMSUM_BF16: frc = dispatch_bwd<__hip_bfloat16>(qf, reinterpret_cast<const float *>(qf.fwd.ckpt_ptr), part, s, ev0); break;
-        default: return DIMSUM_ERR_DTYPE;
-    }
-    if (frc != DIMSUM_OK) return frc;
-    const float *ckb = reinterpret_cast<const float *>(qb.fwd.ckpt_ptr);
-    switch (p.dtype) {
-        case DIMSUM_F32: return dispatch_bwd<float, true>(qb, ckb, part, s, nullptr);
-        case DIMSUM_F16: return dispatch_bwd<__half, true>(qb, ckb, part, s, nullptr);
-        default: return dispatch_bwd<__hip_bfloat16, true>(qb, ckb, part, s, nullptr);
-    }
+    ssm_bwd_args_t qb = qf;
+    qb.fwd = ssm_reversed_from(p, *pub);        // (the events bracket the whole call: begin of the first kernel, end of the last)
+    qb.dA_ptr = pub->dA_b_ptr; qb.dA_d_stride = pub->dA_b_d_stride; qb.dA_dstate_stride = pub->dA_b_dstate_stride;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = dispatch_bwd<false>(qf, p.ckpt_ptr, s, ev0);
+    return rc != DIMSUM_OK ? rc : dispatch_bwd<true>(qb, qb.fwd.ckpt_ptr, s, nullptr);
 }

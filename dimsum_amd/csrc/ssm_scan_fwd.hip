@@ -2,32 +2,29 @@
 #include <type_traits>
 #include <cstdlib>
 
-#include "common.hpp"
+#include "ssm_scan_host.hpp"
 
 namespace dimsum {
 
-// kernel launchers, instantiated in ssm_scan_fwd_{f32,f16,bf16}.hip / ssm_scan_fwd_split_{f32,f16,bf16}.hip
-template <typename T, int kN> void ssm_scan_fwd_launch_v0(const ssm_args_t &p, hipStream_t stream, int tiles, bool vec, bool full);
-template <typename T, int kN, int kSP> void ssm_scan_fwd_launch_split(const ssm_args_t &p, hipStream_t stream, int tiles, bool vec, bool full);
-template <typename T> void ssm_scan_fwd_launch_lanes(const ssm_args_t &p, hipStream_t stream, int tiles, bool vec, bool full);
-template <typename T, int kN> void ssm_scan_fwd_launch_rev(const ssm_args_t &p, hipStream_t stream, int tiles, bool vec, bool full);
-template <typename T> void ssm_scan_fwd_launch_lanes_rev(const ssm_args_t &p, hipStream_t stream, int tiles, bool vec, bool full);
-
-int ssm_check(const ssm_args_t *p, bool forward) {
-    if (!p || !p->A_ptr || !p->B_ptr || !p->C_ptr || !p->u_ptr || (!p->delta_ptr && !(forward && p->dt_w_ptr))) return DIMSUM_ERR_NULL;
-    if (p->dt_w_ptr) {          // fused dt_proj (forward only)
+int ssm_check_operands(const ssm_args_t &p, bool forward) {
+    if (!p.A_ptr || !p.B_ptr || !p.C_ptr || !p.u_ptr || (!p.delta_ptr && !(forward && p.dt_w_ptr))) return DIMSUM_ERR_NULL;
+    if (p.dt_w_ptr) {          // fused dt_proj (forward only)
         if (!forward) return DIMSUM_ERR_UNSUPPORTED;
-        if (!p->dt_x_ptr) return DIMSUM_ERR_NULL;
-        if (p->dt_rank <= 0 || p->dt_rank > 32 || p->dt_rank % 4 != 0) return DIMSUM_ERR_SHAPE;
-        if (p->dt_w_row_stride % 4 != 0 || p->dt_w_row_stride < p->dt_rank || p->dt_x_row_stride < (int64_t)p->batch * p->seqlen ||
-            reinterpret_cast<uintptr_t>(p->dt_w_ptr) % 16 != 0 || reinterpret_cast<uintptr_t>(p->dt_x_ptr) % 4 != 0 ||
-            (int64_t)8 * p->dt_x_row_stride * 4 >= ((int64_t)1 << 31))           // (32-bit byte offsets of the 8 r rows a lane reads)
+        if (!p.dt_x_ptr) return DIMSUM_ERR_NULL;
+        if (p.dt_rank <= 0 || p.dt_rank > 32 || p.dt_rank % 4 != 0) return DIMSUM_ERR_SHAPE;
+        if (p.dt_w_row_stride % 4 != 0 || p.dt_w_row_stride < p.dt_rank || p.dt_x_row_stride < (int64_t)p.batch * p.seqlen ||
+            reinterpret_cast<uintptr_t>(p.dt_w_ptr) % 16 != 0 || reinterpret_cast<uintptr_t>(p.dt_x_ptr) % 4 != 0 ||
+            (int64_t)8 * p.dt_x_row_stride * 4 >= ((int64_t)1 << 31))           // (32-bit byte offsets of the 8 r rows a lane reads)
             return DIMSUM_ERR_STRIDE;
     }
-    if (forward && p->z_ptr && !p->out_z_ptr) return DIMSUM_ERR_NULL;   // in the backward out_z is the optional recompute
-    if (p->batch <= 0 || p->dim <= 0 || p->seqlen <= 0 || p->n_groups <= 0 || p->dim % p->n_groups != 0) return DIMSUM_ERR_SHAPE;
-    if (p->dstate > 256) return DIMSUM_ERR_SHAPE;  // selective_scan.cpp:262
-    if (p->n_chunks != (p->seqlen + 2047) / 2048) return DIMSUM_ERR_SHAPE;
+    if (forward && p.z_ptr && !p.out_z_ptr) return DIMSUM_ERR_NULL;   // in the backward out_z is the optional recompute
+    return DIMSUM_OK;
+}
+
+int ssm_check_shape(const ssm_args_t &p) {
+    if (p.batch <= 0 || p.dim <= 0 || p.seqlen <= 0 || p.n_groups <= 0 || p.dim % p.n_groups != 0) return DIMSUM_ERR_SHAPE;
+    if (p.dstate > 256) return DIMSUM_ERR_SHAPE;  // selective_scan.cpp:262
+    if (p.n_chunks != (p.seqlen + 2047) / 2048) return DIMSUM_ERR_SHAPE;
     return DIMSUM_OK;
 }
 
@@ -60,16 +57,13 @@ int ssm_scan_fwd_variant(const ssm_args_t &p) {
 // vector path: every row base 4-element aligned, seqlen % 4 == 0
 template <typename T>
 static bool vec_ok(const ssm_args_t &p) {
-    const size_t va = 4 * sizeof(T);
-    bool vec = (p.seqlen % 4 == 0) && aligned_to<T>(p.u_ptr, va) && aligned_to<T>(p.delta_ptr, va) &&
-               aligned_to<T>(p.B_ptr, va) && aligned_to<T>(p.C_ptr, va) && (p.u_batch_stride % 4 == 0) &&
-               (p.u_d_stride % 4 == 0) && (p.delta_batch_stride % 4 == 0) && (p.delta_d_stride % 4 == 0) &&
-               (p.B_batch_stride % 4 == 0) && (p.B_group_stride % 4 == 0) && (p.B_dstate_stride % 4 == 0) &&
-               (p.C_batch_stride % 4 == 0) && (p.C_group_stride % 4 == 0) && (p.C_dstate_stride % 4 == 0);
-    if (p.out_ptr) vec = vec && aligned_to<T>(p.out_ptr, va) && (p.out_batch_stride % 4 == 0) && (p.out_d_stride % 4 == 0);
+    bool vec = (p.seqlen % 4 == 0) && ssm_vec4_ok<T>(p.u_ptr, p.u_batch_stride, p.u_d_stride) &&
+               ssm_vec4_ok<T>(p.delta_ptr, p.delta_batch_stride, p.delta_d_stride) &&
+               ssm_vec4_ok<T>(p.B_ptr, p.B_batch_stride, p.B_dstate_stride) && (p.B_group_stride % 4 == 0) &&
+               ssm_vec4_ok<T>(p.C_ptr, p.C_batch_stride, p.C_dstate_stride) && (p.C_group_stride % 4 == 0);
+    if (p.out_ptr) vec = vec && ssm_vec4_ok<T>(p.out_ptr, p.out_batch_stride, p.out_d_stride);
     if (p.z_ptr)
-        vec = vec && aligned_to<T>(p.z_ptr, va) && aligned_to<T>(p.out_z_ptr, va) && (p.z_batch_stride % 4 == 0) &&
-              (p.z_d_stride % 4 == 0) && (p.out_z_batch_stride % 4 == 0) && (p.out_z_d_stride % 4 == 0);
+        vec = vec && ssm_vec4_ok<T>(p.z_ptr, p.z_batch_stride, p.z_d_stride) && ssm_vec4_ok<T>(p.out_z_ptr, p.out_z_batch_stride, p.out_z_d_stride);
     return vec;
 }
 
@@ -116,32 +110,60 @@ static int launch_fwd(const ssm_args_t &p, hipStream_t stream) {
     return launch_status();
 }
 
-template <typename T>
-static int ssm_scan_fwd_dispatch(const ssm_args_t &p, hipStream_t stream) {
-    switch (p.dstate) {
-        case 4: return launch_fwd<T, 4>(p, stream);
-        case 8: return launch_fwd<T, 8>(p, stream);
-        case 32: return launch_fwd<T, 32>(p, stream);
-        case 16: return launch_fwd<T, 16>(p, stream);
-        default: return DIMSUM_ERR_SHAPE;
-    }
-}
-
-}  // namespace dimsum
-
 // flat block -> kernels (also the entry of the backward's state-rebuild sweep, ssm_scan_bwd.hip)
-namespace dimsum {
 int ssm_scan_fwd_run(const ssm_args_t &a, hipStream_t s) {
-    const int rc = ssm_check(&a, true);
+    const int rc = ssm_check(a, true);
     if (rc != DIMSUM_OK) return rc;
-    if (a.batch == 0) return DIMSUM_OK;
-    switch (a.dtype) {
-        case DIMSUM_F32: return ssm_scan_fwd_dispatch<float>(a, s);
-        case DIMSUM_F16: return ssm_scan_fwd_dispatch<__half>(a, s);
-        case DIMSUM_BF16: return ssm_scan_fwd_dispatch<__hip_bfloat16>(a, s);
-        default: return DIMSUM_ERR_DTYPE;
-    }
+    return ssm_dispatch(a.dtype, a.dstate, [&](auto t, auto n) { return launch_fwd<DIMSUM_TAG_T(t), DIMSUM_TAG_N(n)>(a, s); });
 }
+
+// ---- bidirectional forward (bimamba_inner_fn): the forward direction first (writes out_z), the reversed one second (adds to it), both
+// on the kernel bidir_variant picks: the 64-channel kernel, or -- where the library's own choice for the shape is one lane per state (dstate
+// 16, launches far too small to fill the chip) -- that kernel. The state-split kernels (2 / 4 lanes per channel) have no reversed form:
+// their launches take the 64-channel kernel. --------------------------------------------------------------------------------------------
+static int bidir_variant(const ssm_args_t &p) {
+    return ssm_scan_fwd_variant(p) == 16 ? 16 : 1;
+}
+
+// f, b: the two directions' blocks (ssm_reversed_from)
+template <typename T, int kN>
+static int launch_bidir(const ssm_args_t &f, const ssm_args_t &b, hipStream_t stream) {
+    const int dpg = f.dim / f.n_groups;
+    const int sp = bidir_variant(f);
+    const int cpw = kWave / sp;                            // channels per wave
+    const int tiles = f.batch * f.n_groups * ((dpg + cpw - 1) / cpw);
+    const bool vec = vec_ok<T>(f) && vec_ok<T>(b);        // (b differs in out: out_b)
+    if (!offsets_ok<T>(f) || !offsets_ok<T>(b)) return DIMSUM_ERR_STRIDE;
+    const bool full = vec && (dpg % cpw == 0);
+    if (sp == 16) {
+        if constexpr (kN == 16) {
+            ssm_scan_fwd_launch_lanes<T>(f, stream, tiles, vec, full);
+            if (launch_status() != DIMSUM_OK) return DIMSUM_ERR_LAUNCH;
+            ssm_scan_fwd_launch_lanes_rev<T>(b, stream, tiles, vec, full);
+        }
+        return launch_status();
+    }
+    ssm_scan_fwd_launch_v0<T, kN>(f, stream, tiles, vec, full);
+    if (launch_status() != DIMSUM_OK) return DIMSUM_ERR_LAUNCH;
+    ssm_scan_fwd_launch_rev<T, kN>(b, stream, tiles, vec, full);
+    return launch_status();
+}
+
+// public struct -> the forward direction's flat block, checked. with_pointers = false: the dispatch query, whose caller fills in the shape
+// only -- the operand checks are left out, the order of the others is the same
+static int bidir_args_from(const dimsum_ssm_bidir_params_t *pub, ssm_args_t &f, bool with_pointers) {
+    if (!pub) return DIMSUM_ERR_NULL;
+    if (pub->struct_size != sizeof(dimsum_ssm_bidir_params_t)) return DIMSUM_ERR_ABI;
+    const int arc = ssm_args_from(&pub->fwd, f, false);
+    if (arc != DIMSUM_OK) return arc;
+    if (f.dt_w_ptr || f.out_z_lo_offset || f.out_z_f16 || f.x_ptr) return DIMSUM_ERR_UNSUPPORTED;
+    const int rc = with_pointers ? ssm_check(f, true) : ssm_check_shape(f);
+    if (rc != DIMSUM_OK) return rc;
+    if (with_pointers && (!f.z_ptr || !pub->A_b_ptr)) return DIMSUM_ERR_NULL;
+    if (f.dstate != 4 && f.dstate != 8 && f.dstate != 16 && f.dstate != 32) return DIMSUM_ERR_SHAPE;
+    return DIMSUM_OK;
+}
+
 }  // namespace dimsum
 
 extern "C" int dimsum_ssm_scan_fwd_variant(const dimsum_ssm_params_t *p) {
@@ -157,91 +179,18 @@ extern "C" int dimsum_ssm_scan_fwd(const dimsum_ssm_params_t *p, void *stream) {
     return dimsum::ssm_scan_fwd_run(a, reinterpret_cast<hipStream_t>(stream));
 }
 
-// ---- bidirectional forward (bimamba_inner_fn): the forward direction first (writes out_z), the reversed one second (adds to it), both
-// on the kernel bidir_variant picks: the 64-channel kernel, or -- where the library's own choice for the shape is one lane per state (dstate
-// 16, launches far too small to fill the chip) -- that kernel. The state-split kernels (2 / 4 lanes per channel) have no reversed form:
-// their launches take the 64-channel kernel. --------------------------------------------------------------------------------------------
-namespace dimsum {
-static int bidir_variant(const ssm_args_t &p) {
-    return ssm_scan_fwd_variant(p) == 16 ? 16 : 1;
-}
-
-template <typename T, int kN>
-static int launch_bidir(const ssm_args_t &pf, const ssm_args_t &pb, hipStream_t stream) {
-    const int dpg = pf.dim / pf.n_groups;
-    const int sp = bidir_variant(pf);
-    const int cpw = kWave / sp;                            // channels per wave
-    const int tiles = pf.batch * pf.n_groups * ((dpg + cpw - 1) / cpw);
-    const bool vec = vec_ok<T>(pf) && vec_ok<T>(pb);      // (pb differs in out: out_b)
-    if (!offsets_ok<T>(pf) || !offsets_ok<T>(pb)) return DIMSUM_ERR_STRIDE;
-    const bool full = vec && (dpg % cpw == 0);
-    ssm_args_t f = pf, b = pb;
-    f.timing_stop_event = nullptr;                         // the events bracket the pair: begin of the first kernel, end of the second
-    b.timing_start_event = nullptr;
-    if (sp == 16) {
-        if constexpr (kN == 16) {
-            ssm_scan_fwd_launch_lanes<T>(f, stream, tiles, vec, full);
-            if (launch_status() != DIMSUM_OK) return DIMSUM_ERR_LAUNCH;
-            ssm_scan_fwd_launch_lanes_rev<T>(b, stream, tiles, vec, full);
-        }
-        return launch_status();
-    }
-    ssm_scan_fwd_launch_v0<T, kN>(f, stream, tiles, vec, full);
-    if (launch_status() != DIMSUM_OK) return DIMSUM_ERR_LAUNCH;
-    ssm_scan_fwd_launch_rev<T, kN>(b, stream, tiles, vec, full);
-    return launch_status();
-}
-
-template <typename T>
-static int bidir_dispatch(const ssm_args_t &pf, const ssm_args_t &pb, hipStream_t stream) {
-    switch (pf.dstate) {
-        case 4: return launch_bidir<T, 4>(pf, pb, stream);
-        case 8: return launch_bidir<T, 8>(pf, pb, stream);
-        case 32: return launch_bidir<T, 32>(pf, pb, stream);
-        case 16: return launch_bidir<T, 16>(pf, pb, stream);
-        default: return DIMSUM_ERR_SHAPE;
-    }
-}
-
-// public struct -> the two directions' flat blocks, checked
-static int bidir_args_from(const dimsum_ssm_bidir_params_t *pub, ssm_args_t &f, ssm_args_t &b) {
-    if (!pub) return DIMSUM_ERR_NULL;
-    if (pub->struct_size != sizeof(dimsum_ssm_bidir_params_t)) return DIMSUM_ERR_ABI;
-    const int arc = ssm_args_from(&pub->fwd, f, false);
-    if (arc != DIMSUM_OK) return arc;
-    if (f.dt_w_ptr || f.out_z_lo_offset || f.out_z_f16 || f.x_ptr) return DIMSUM_ERR_UNSUPPORTED;
-    const int rc = ssm_check(&f, true);
-    if (rc != DIMSUM_OK) return rc;
-    if (!f.z_ptr || !pub->A_b_ptr) return DIMSUM_ERR_NULL;
-    if (f.dstate != 4 && f.dstate != 8 && f.dstate != 16 && f.dstate != 32) return DIMSUM_ERR_SHAPE;
-    b = f;
-    b.A_ptr = pub->A_b_ptr; b.A_d_stride = pub->A_b_d_stride; b.A_dstate_stride = pub->A_b_dstate_stride;
-    b.out_ptr = pub->out_b_ptr; b.out_batch_stride = pub->out_b_batch_stride; b.out_d_stride = pub->out_b_d_stride;
-    b.ckpt_ptr = pub->ckpt_b_ptr;
-    return DIMSUM_OK;
-}
-}  // namespace dimsum
-
+// a pure host function of the shape: the pointers are not looked at
 extern "C" int dimsum_ssm_scan_bidir_fwd_variant(const dimsum_ssm_bidir_params_t *p) {
-    dimsum::ssm_args_t f, b;
-    if (!p || p->struct_size != sizeof(dimsum_ssm_bidir_params_t)) return -1;
-    // a pure host function of the shape: the pointers are not looked at
-    dimsum_ssm_bidir_params_t q = *p;
-    q.fwd.A_ptr = q.fwd.B_ptr = q.fwd.C_ptr = q.fwd.u_ptr = q.fwd.delta_ptr = q.fwd.z_ptr = q.A_b_ptr = reinterpret_cast<const void *>(16);
-    q.fwd.out_z_ptr = reinterpret_cast<void *>(16);
-    if (dimsum::bidir_args_from(&q, f, b) != DIMSUM_OK) return -1;
-    return dimsum::bidir_variant(f);
+    dimsum::ssm_args_t f;
+    return dimsum::bidir_args_from(p, f, false) == DIMSUM_OK ? dimsum::bidir_variant(f) : -1;
 }
 
 extern "C" int dimsum_ssm_scan_bidir_fwd(const dimsum_ssm_bidir_params_t *p, void *stream) {
-    dimsum::ssm_args_t f, b;
-    const int rc = dimsum::bidir_args_from(p, f, b);
+    using namespace dimsum;
+    ssm_args_t f;
+    const int rc = bidir_args_from(p, f, true);
     if (rc != DIMSUM_OK) return rc;
+    const ssm_args_t b = ssm_reversed_from(f, *p);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (f.dtype) {
-        case DIMSUM_F32: return dimsum::bidir_dispatch<float>(f, b, s);
-        case DIMSUM_F16: return dimsum::bidir_dispatch<__half>(f, b, s);
-        case DIMSUM_BF16: return dimsum::bidir_dispatch<__hip_bfloat16>(f, b, s);
-        default: return DIMSUM_ERR_DTYPE;
-    }
+    return ssm_dispatch(f.dtype, f.dstate, [&](auto t, auto n) { return launch_bidir<DIMSUM_TAG_T(t), DIMSUM_TAG_N(n)>(f, b, s); });
 }

@@ -33,7 +33,7 @@
 #pragma once
 #include <type_traits>
 
-#include "common.hpp"
+#include "ssm_scan_host.hpp"   // common.hpp + the launchers' declarations and their (HASZ, VEC, FULL) ladder
 
 namespace dimsum {
 
@@ -514,15 +514,7 @@ void ssm_scan_fwd_launch_v0(const ssm_args_t &p, hipStream_t stream, int tiles, 
             return;
         }
     }
-    if (p.z_ptr) {
-        if (full) DIMSUM_LAUNCH(true, true, true);
-        else if (vec) DIMSUM_LAUNCH(true, true, false);
-        else DIMSUM_LAUNCH(true, false, false);
-    } else {
-        if (full) DIMSUM_LAUNCH(false, true, true);
-        else if (vec) DIMSUM_LAUNCH(false, true, false);
-        else DIMSUM_LAUNCH(false, false, false);
-    }
+    DIMSUM_Z_VEC_FULL_LADDER(DIMSUM_LAUNCH, p.z_ptr, vec, full);
 #undef DIMSUM_LAUNCH
 }
 
@@ -532,14 +524,12 @@ template <typename T, int kN>
 void ssm_scan_fwd_launch_rev(const ssm_args_t &p, hipStream_t stream, int tiles, bool vec, bool full) {
     const dim3 grid(tiles), block(kWave);
     const hipEvent_t ev0 = reinterpret_cast<hipEvent_t>(p.timing_start_event), ev1 = reinterpret_cast<hipEvent_t>(p.timing_stop_event);
-#define DIMSUM_LAUNCH(VEC, FULL)                                                                                                                 \
+#define DIMSUM_LAUNCH(HASZ, VEC, FULL)                                                                                                                \
     do {                                                                                                                                         \
-        if (p.ckpt_ptr) DIMSUM_LAUNCH_EV((ssm_scan_fwd_kernel<T, kN, true, VEC, FULL, true, false, false, true, true>), grid, block, stream, ev0, ev1, p); \
-        else DIMSUM_LAUNCH_EV((ssm_scan_fwd_kernel<T, kN, true, VEC, FULL, false, false, false, true, true>), grid, block, stream, ev0, ev1, p);       \
+        if (p.ckpt_ptr) DIMSUM_LAUNCH_EV((ssm_scan_fwd_kernel<T, kN, HASZ, VEC, FULL, true, false, false, true, true>), grid, block, stream, ev0, ev1, p); \
+        else DIMSUM_LAUNCH_EV((ssm_scan_fwd_kernel<T, kN, HASZ, VEC, FULL, false, false, false, true, true>), grid, block, stream, ev0, ev1, p);       \
     } while (0)
-    if (full) DIMSUM_LAUNCH(true, true);
-    else if (vec) DIMSUM_LAUNCH(true, false);
-    else DIMSUM_LAUNCH(false, false);
+    DIMSUM_VEC_FULL_LADDER(DIMSUM_LAUNCH, true, vec, full);
 #undef DIMSUM_LAUNCH
 }
 

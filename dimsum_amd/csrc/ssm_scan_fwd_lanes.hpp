@@ -300,15 +300,7 @@ void ssm_scan_fwd_launch_lanes(const ssm_args_t &p, hipStream_t stream, int tile
         if (p.ckpt_ptr) DIMSUM_LAUNCH_EV((ssm_scan_fwd_lanes_kernel<T, HASZ, VEC, FULL, true>), grid, block, stream, ev0, ev1, p); \
         else DIMSUM_LAUNCH_EV((ssm_scan_fwd_lanes_kernel<T, HASZ, VEC, FULL, false>), grid, block, stream, ev0, ev1, p);          \
     } while (0)
-    if (p.z_ptr) {
-        if (full) DIMSUM_LAUNCH(true, true, true);
-        else if (vec) DIMSUM_LAUNCH(true, true, false);
-        else DIMSUM_LAUNCH(true, false, false);
-    } else {
-        if (full) DIMSUM_LAUNCH(false, true, true);
-        else if (vec) DIMSUM_LAUNCH(false, true, false);
-        else DIMSUM_LAUNCH(false, false, false);
-    }
+    DIMSUM_Z_VEC_FULL_LADDER(DIMSUM_LAUNCH, p.z_ptr, vec, full);
 #undef DIMSUM_LAUNCH
 }
 
@@ -317,14 +309,12 @@ template <typename T>
 void ssm_scan_fwd_launch_lanes_rev(const ssm_args_t &p, hipStream_t stream, int tiles, bool vec, bool full) {
     const dim3 grid(tiles), block(kWave);
     const hipEvent_t ev0 = reinterpret_cast<hipEvent_t>(p.timing_start_event), ev1 = reinterpret_cast<hipEvent_t>(p.timing_stop_event);
-#define DIMSUM_LAUNCH(VEC, FULL)                                                                                                         \
+#define DIMSUM_LAUNCH(HASZ, VEC, FULL)                                                                                                        \
     do {                                                                                                                                 \
-        if (p.ckpt_ptr) DIMSUM_LAUNCH_EV((ssm_scan_fwd_lanes_kernel<T, true, VEC, FULL, true, true, true>), grid, block, stream, ev0, ev1, p); \
-        else DIMSUM_LAUNCH_EV((ssm_scan_fwd_lanes_kernel<T, true, VEC, FULL, false, true, true>), grid, block, stream, ev0, ev1, p);          \
+        if (p.ckpt_ptr) DIMSUM_LAUNCH_EV((ssm_scan_fwd_lanes_kernel<T, HASZ, VEC, FULL, true, true, true>), grid, block, stream, ev0, ev1, p); \
+        else DIMSUM_LAUNCH_EV((ssm_scan_fwd_lanes_kernel<T, HASZ, VEC, FULL, false, true, true>), grid, block, stream, ev0, ev1, p);          \
     } while (0)
-    if (full) DIMSUM_LAUNCH(true, true);
-    else if (vec) DIMSUM_LAUNCH(true, false);
-    else DIMSUM_LAUNCH(false, false);
+    DIMSUM_VEC_FULL_LADDER(DIMSUM_LAUNCH, true, vec, full);
 #undef DIMSUM_LAUNCH
 }
 

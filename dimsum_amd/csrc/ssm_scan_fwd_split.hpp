@@ -315,15 +315,7 @@ void ssm_scan_fwd_launch_split(const ssm_args_t &p, hipStream_t stream, int tile
         if (p.ckpt_ptr) DIMSUM_LAUNCH_EV((ssm_scan_fwd_split_kernel<T, kN, kSP, HASZ, VEC, FULL, true>), grid, block, stream, ev0, ev1, p); \
         else DIMSUM_LAUNCH_EV((ssm_scan_fwd_split_kernel<T, kN, kSP, HASZ, VEC, FULL, false>), grid, block, stream, ev0, ev1, p);         \
     } while (0)
-    if (p.z_ptr) {
-        if (full) DIMSUM_LAUNCH(true, true, true);
-        else if (vec) DIMSUM_LAUNCH(true, true, false);
-        else DIMSUM_LAUNCH(true, false, false);
-    } else {
-        if (full) DIMSUM_LAUNCH(false, true, true);
-        else if (vec) DIMSUM_LAUNCH(false, true, false);
-        else DIMSUM_LAUNCH(false, false, false);
-    }
+    DIMSUM_Z_VEC_FULL_LADDER(DIMSUM_LAUNCH, p.z_ptr, vec, full);
 #undef DIMSUM_LAUNCH
 }
 

@@ -97,10 +97,15 @@ def scan_fwd_kernel_for(batch, dim, seqlen, dstate, n_groups=1):
     """which forward scan kernel the library runs for this launch shape, as lanes per channel (dimsum_ssm_scan_fwd_variant): 1 = the
     64-channel kernel (a full chip), 2 / 4 / 16 = the state-split kernels of underfilled launches"""
     P = _lib.SsmParams()
+    _fill_ssm_shape(P, batch, dim, seqlen, dstate, n_groups)
+    return int(_lib.load().dimsum_ssm_scan_fwd_variant(P))
+
+
+def _fill_ssm_shape(P, batch, dim, seqlen, dstate, n_groups):
+    """the launch shape of a dispatch query (no operands) into the dimsum_ssm_params_t P, with the kernel asked for by scan_fwd_variant"""
     P.batch, P.dim, P.seqlen, P.dstate, P.n_groups, P.n_chunks = batch, dim, seqlen, dstate, n_groups, (seqlen + 2047) // 2048
     if _scan_fwd_variant:
         _lib.attach_ext(P, _lib.SsmExt).kernel_variant = _scan_fwd_variant
-    return int(_lib.load().dimsum_ssm_scan_fwd_variant(P))
 
 
 def _fill_ssm(P, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, ckpt=None):
@@ -410,6 +415,65 @@ def layer_norm_bwd(dy, x, weight, bias, eps, mean, rstd, dresidual=None, has_res
     return dx, dw.to(weight.dtype), db.to(bias.dtype) if bias is not None else None, dresidual_in
 
 
+def _prep_ssm_bwd(who, u, delta, A, B, C, D, z, delta_bias, dout, dz, dB, dC, n_dirs, also=()):
+    """what the two backward calls share before their struct is filled: the checks of dout / dz / dB / dC (`also`: the caller's own (condition,
+    message) checks, made between those of dout and dz; messages carry the caller's name `who`) and the allocations
+    -> du, ddelta, [dA per direction], dB, dC, dD, ddelta_bias, dz"""
+    batch, dim, seqlen = u.shape
+    _check(tuple(dout.shape) == (batch, dim, seqlen) and dout.dtype == u.dtype and (dout.stride(-1) == 1 or seqlen == 1), f"{who}: bad dout")
+    for cond, msg in also:
+        _check(cond, msg)
+    if z is not None:
+        if dz is None:
+            dz = torch.empty_like(z)
+        else:
+            _check(dz.shape == z.shape and dz.dtype == z.dtype and dz.stride(-1) == 1, f"{who}: bad dz")
+    du = torch.empty_like(u)
+    ddelta = torch.empty_like(delta)
+    # the zero-filled fp32 accumulators (selective_scan.cpp:458-466) out of ONE buffer: one fill launch instead of three
+    nA, nD = A.numel(), (dim if D is not None else 0)
+    acc = _zeros(n_dirs * nA + nD + (dim if delta_bias is not None else 0), u.device)
+    dAs = [acc[i * nA:(i + 1) * nA].view(A.shape) for i in range(n_dirs)]
+    # dB / dC: fp32 then cast (cpp:461-462,488); a caller may hand in fp32 views of B's / C's shape (unit stride along l) to have them written in place
+    for t, like in ((dB, B), (dC, C)):
+        _check(t is None or (t.shape == like.shape and t.dtype == torch.float32 and t.is_cuda and t.stride(-1) == 1), f"{who}: bad dB / dC buffer")
+    dB = torch.empty(B.shape, device=u.device, dtype=torch.float32) if dB is None else dB
+    dC = torch.empty(C.shape, device=u.device, dtype=torch.float32) if dC is None else dC
+    dD = acc[n_dirs * nA:n_dirs * nA + nD] if D is not None else None
+    ddelta_bias = acc[n_dirs * nA + nD:] if delta_bias is not None else None
+    return du, ddelta, dAs, dB, dC, dD, ddelta_bias, dz
+
+
+def _fill_ssm_bwd(Q, dout, du, ddelta, dA, dB, dC, dD, ddelta_bias, dz, ckpt):
+    """the gradient half of Q (dimsum_ssm_bwd_params_t; _fill_ssm has filled Q.fwd) and a fresh workspace for the partial dB / dC (+ the
+    states when no `ckpt` is given) -> the workspace, to be kept until the call is made"""
+    Q.dout_batch_stride, Q.dout_d_stride = dout.stride(0), dout.stride(1)
+    Q.dA_d_stride, Q.dA_dstate_stride = dA.stride(0), dA.stride(1)
+    Q.dB_batch_stride, Q.dB_group_stride, Q.dB_dstate_stride = dB.stride(0), dB.stride(1), dB.stride(2)
+    Q.dC_batch_stride, Q.dC_group_stride, Q.dC_dstate_stride = dC.stride(0), dC.stride(1), dC.stride(2)
+    Q.du_batch_stride, Q.du_d_stride = du.stride(0), du.stride(1)
+    Q.ddelta_batch_stride, Q.ddelta_d_stride = ddelta.stride(0), ddelta.stride(1)
+    if dz is not None:
+        Q.dz_batch_stride, Q.dz_d_stride = dz.stride(0), dz.stride(1)
+    Q.dout_ptr, Q.dA_ptr, Q.dB_ptr, Q.dC_ptr, Q.dD_ptr = _ptr(dout), _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD)
+    Q.du_ptr, Q.dz_ptr, Q.ddelta_ptr, Q.ddelta_bias_ptr = _ptr(du), _ptr(dz), _ptr(ddelta), _ptr(ddelta_bias)
+    F = Q.fwd
+    nbytes = _lib.load().dimsum_ssm_scan_bwd_workspace_bytes(F.batch, F.dim, F.seqlen, F.dstate, F.n_groups)
+    if ckpt is not None:
+        nbytes -= ckpt.numel() * 4          # the states part is only needed when they must be rebuilt
+    ws = torch.empty((nbytes + 3) // 4, device=du.device, dtype=torch.float32)       # per-wave partial dB / dC (+ states)
+    Q.workspace_ptr, Q.workspace_bytes = _ptr(ws), nbytes
+    return ws
+
+
+def _fill_ssm_reversed(P, A_b, out_b, ckpt_b):
+    """the reversed direction's A / out / saved states into a dimsum_ssm_bidir_params_t or dimsum_ssm_bidir_bwd_params_t"""
+    P.A_b_ptr, P.A_b_d_stride, P.A_b_dstate_stride = _ptr(A_b), A_b.stride(0), A_b.stride(1)
+    if out_b is not None:
+        P.out_b_ptr, P.out_b_batch_stride, P.out_b_d_stride = _ptr(out_b), out_b.stride(0), out_b.stride(1)
+    P.ckpt_b_ptr = _ptr(ckpt_b)
+
+
 def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, out, dz, delta_softplus, recompute_out_z, ckpt=None, dB=None, dC=None):
     """-> [du, ddelta, dA, dB, dC, dD, ddelta_bias, (dz), (out_z)] exactly like selective_scan_cuda.bwd
     (selective_scan.cpp:338-492). dz may be a caller-provided view (fused chunk backward, :433-441).
@@ -418,29 +482,10 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, out, dz, de
     _check_ssm(u, delta, A, B, C, D, z, delta_bias)
     _gpu(dout, x, out, dz)
     batch, dim, seqlen = u.shape
-    _check(tuple(dout.shape) == (batch, dim, seqlen) and dout.dtype == u.dtype and (dout.stride(-1) == 1 or seqlen == 1),
-           "selective_scan_bwd: bad dout")
     has_z = z is not None
-    if has_z:
-        _check(out is not None and out.shape == u.shape and out.stride(-1) == 1, "selective_scan_bwd: `out` of the forward is required with z")
-        if dz is None:
-            dz = torch.empty_like(z)
-        else:
-            _check(dz.shape == z.shape and dz.dtype == z.dtype and dz.stride(-1) == 1, "selective_scan_bwd: bad dz")
+    also = [(out is not None and out.shape == u.shape and out.stride(-1) == 1, "selective_scan_bwd: `out` of the forward is required with z")] if has_z else []
+    du, ddelta, (dA,), dB, dC, dD, ddelta_bias, dz = _prep_ssm_bwd("selective_scan_bwd", u, delta, A, B, C, D, z, delta_bias, dout, dz, dB, dC, 1, also)
     out_z = torch.empty_like(out) if (has_z and recompute_out_z) else None
-    du = torch.empty_like(u)
-    ddelta = torch.empty_like(delta)
-    # the three zero-filled fp32 accumulators (selective_scan.cpp:458-466) out of ONE buffer: one fill launch instead of three
-    nA, nD = A.numel(), (dim if D is not None else 0)
-    acc = _zeros(nA + nD + (dim if delta_bias is not None else 0), u.device)
-    dA = acc[:nA].view(A.shape)
-    # dB / dC: fp32 then cast (cpp:461-462,488); a caller may hand in fp32 views of B's / C's shape (unit stride along l) to have them written in place
-    for t, like in ((dB, B), (dC, C)):
-        _check(t is None or (t.shape == like.shape and t.dtype == torch.float32 and t.is_cuda and t.stride(-1) == 1), "selective_scan_bwd: bad dB / dC buffer")
-    dB = torch.empty(B.shape, device=u.device, dtype=torch.float32) if dB is None else dB
-    dC = torch.empty(C.shape, device=u.device, dtype=torch.float32) if dC is None else dC
-    dD = acc[nA:nA + nD] if D is not None else None
-    ddelta_bias = acc[nA + nD:] if delta_bias is not None else None
     if u.numel() > 0:
         Q = _lib.SsmBwdParams()
         if ckpt is not None:
@@ -448,24 +493,10 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, out, dz, de
             _check(tuple(ckpt.shape) == scan_ckpt_shape(batch, dim, seqlen, A.shape[1]) and ckpt.dtype == torch.float32
                    and ckpt.is_contiguous(), "selective_scan_bwd: bad ckpt")
         _fill_ssm(Q.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, ckpt)
-        Q.dout_batch_stride, Q.dout_d_stride = dout.stride(0), dout.stride(1)
-        Q.dA_d_stride, Q.dA_dstate_stride = dA.stride(0), dA.stride(1)
-        Q.dB_batch_stride, Q.dB_group_stride, Q.dB_dstate_stride = dB.stride(0), dB.stride(1), dB.stride(2)
-        Q.dC_batch_stride, Q.dC_group_stride, Q.dC_dstate_stride = dC.stride(0), dC.stride(1), dC.stride(2)
-        Q.du_batch_stride, Q.du_d_stride = du.stride(0), du.stride(1)
-        Q.ddelta_batch_stride, Q.ddelta_d_stride = ddelta.stride(0), ddelta.stride(1)
-        if dz is not None:
-            Q.dz_batch_stride, Q.dz_d_stride = dz.stride(0), dz.stride(1)
-        Q.dout_ptr, Q.dA_ptr, Q.dB_ptr, Q.dC_ptr, Q.dD_ptr = _ptr(dout), _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD)
-        Q.du_ptr, Q.dz_ptr, Q.ddelta_ptr, Q.ddelta_bias_ptr = _ptr(du), _ptr(dz), _ptr(ddelta), _ptr(ddelta_bias)
-        lib = _lib.load()
-        nbytes = lib.dimsum_ssm_scan_bwd_workspace_bytes(batch, dim, seqlen, A.shape[1], B.shape[1])
-        if ckpt is not None:
-            nbytes -= ckpt.numel() * 4          # the states part is only needed when they must be rebuilt
-        ws = torch.empty((nbytes + 3) // 4, device=u.device, dtype=torch.float32)       # per-wave partial dB / dC (+ states)
-        Q.workspace_ptr, Q.workspace_bytes = _ptr(ws), nbytes
+        ws = _fill_ssm_bwd(Q, dout, du, ddelta, dA, dB, dC, dD, ddelta_bias, dz, ckpt)
         with torch.cuda.device(u.device):
-            _lib.check(lib.dimsum_ssm_scan_bwd(Q, _stream(u)), "selective_scan_bwd")
+            _lib.check(_lib.load().dimsum_ssm_scan_bwd(Q, _stream(u)), "selective_scan_bwd")
+        del ws
     res = [du, ddelta, dA, dB.to(B.dtype), dC.to(C.dtype), dD, ddelta_bias]
     if has_z:
         res.append(dz)
@@ -483,10 +514,7 @@ def scan_bidir_fwd_kernel_for(batch, dim, seqlen, dstate, n_groups=1):
     state where the library picks it for the shape (dstate 16, far too few channels to fill the chip), else 1 = the 64-channel kernel (the
     state-split kernels have no reversed form); -1 = not served (dstate other than 4, 8, 16, 32)"""
     P = _lib.SsmBidirParams()
-    F = P.fwd
-    F.batch, F.dim, F.seqlen, F.dstate, F.n_groups, F.n_chunks = batch, dim, seqlen, dstate, n_groups, (seqlen + 2047) // 2048
-    if _scan_fwd_variant:
-        _lib.attach_ext(F, _lib.SsmExt).kernel_variant = _scan_fwd_variant
+    _fill_ssm_shape(P.fwd, batch, dim, seqlen, dstate, n_groups)
     return int(_lib.load().dimsum_ssm_scan_bidir_fwd_variant(P))
 
 
@@ -513,10 +541,7 @@ def selective_scan_bidir_fwd(u, delta, A, A_b, B, C, D, z, delta_bias, delta_sof
     if u.numel() > 0:
         P = _lib.SsmBidirParams()
         _fill_ssm(P.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, None, out_z, ckpt)
-        P.A_b_ptr, P.A_b_d_stride, P.A_b_dstate_stride = _ptr(A_b), A_b.stride(0), A_b.stride(1)
-        if out_b is not None:
-            P.out_b_ptr, P.out_b_batch_stride, P.out_b_d_stride = _ptr(out_b), out_b.stride(0), out_b.stride(1)
-        P.ckpt_b_ptr = _ptr(ckpt_b)
+        _fill_ssm_reversed(P, A_b, out_b, ckpt_b)
         with torch.cuda.device(u.device):
             _lib.check(_lib.load().dimsum_ssm_scan_bidir_fwd(P, _stream(u)), "selective_scan_bidir_fwd")
     res = [out, out_b, out_z]
@@ -534,54 +559,21 @@ def selective_scan_bidir_bwd(u, delta, A, A_b, B, C, D, z, delta_bias, dout, out
     _check_bidir(A, A_b, z)
     _gpu(dout, out, out_b, ckpt, ckpt_b, dz)
     batch, dim, seqlen = u.shape
-    dstate = A.shape[1]
-    _check(tuple(dout.shape) == (batch, dim, seqlen) and dout.dtype == u.dtype and (dout.stride(-1) == 1 or seqlen == 1),
-           "selective_scan_bidir_bwd: bad dout")
-    for t in (out, out_b):
-        _check(t is not None and t.shape == u.shape and t.dtype == u.dtype and t.stride(-1) == 1,
-               "selective_scan_bidir_bwd: `out` and `out_b` of the forward are required")
-    for t in (ckpt, ckpt_b):
-        _check(t is not None and tuple(t.shape) == scan_ckpt_shape(batch, dim, seqlen, dstate) and t.dtype == torch.float32 and t.is_contiguous(),
-               "selective_scan_bidir_bwd: both directions' saved states (need_ckpt=True) are required")
-    if dz is None:
-        dz = torch.empty_like(z)
-    else:
-        _check(dz.shape == z.shape and dz.dtype == z.dtype and dz.stride(-1) == 1, "selective_scan_bidir_bwd: bad dz")
+    also = [(t is not None and t.shape == u.shape and t.dtype == u.dtype and t.stride(-1) == 1,
+             "selective_scan_bidir_bwd: `out` and `out_b` of the forward are required") for t in (out, out_b)]
+    also += [(t is not None and tuple(t.shape) == scan_ckpt_shape(batch, dim, seqlen, A.shape[1]) and t.dtype == torch.float32 and t.is_contiguous(),
+              "selective_scan_bidir_bwd: both directions' saved states (need_ckpt=True) are required") for t in (ckpt, ckpt_b)]
+    du, ddelta, (dA, dA_b), dB, dC, dD, ddelta_bias, dz = _prep_ssm_bwd("selective_scan_bidir_bwd", u, delta, A, B, C, D, z, delta_bias, dout, dz, dB, dC, 2, also)
     out_z = torch.empty_like(out) if recompute_out_z else None
-    du = torch.empty_like(u)
-    ddelta = torch.empty_like(delta)
-    nA, nD = A.numel(), (dim if D is not None else 0)
-    acc = _zeros(2 * nA + nD + (dim if delta_bias is not None else 0), u.device)
-    dA, dA_b = acc[:nA].view(A.shape), acc[nA:2 * nA].view(A.shape)
-    for t, like in ((dB, B), (dC, C)):
-        _check(t is None or (t.shape == like.shape and t.dtype == torch.float32 and t.is_cuda and t.stride(-1) == 1), "selective_scan_bidir_bwd: bad dB / dC buffer")
-    dB = torch.empty(B.shape, device=u.device, dtype=torch.float32) if dB is None else dB
-    dC = torch.empty(C.shape, device=u.device, dtype=torch.float32) if dC is None else dC
-    dD = acc[2 * nA:2 * nA + nD] if D is not None else None
-    ddelta_bias = acc[2 * nA + nD:] if delta_bias is not None else None
     if u.numel() > 0:
         P = _lib.SsmBidirBwdParams()
-        Q = P.bwd
-        _fill_ssm(Q.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, None, out_z, ckpt)
-        Q.dout_batch_stride, Q.dout_d_stride = dout.stride(0), dout.stride(1)
-        Q.dA_d_stride, Q.dA_dstate_stride = dA.stride(0), dA.stride(1)
-        Q.dB_batch_stride, Q.dB_group_stride, Q.dB_dstate_stride = dB.stride(0), dB.stride(1), dB.stride(2)
-        Q.dC_batch_stride, Q.dC_group_stride, Q.dC_dstate_stride = dC.stride(0), dC.stride(1), dC.stride(2)
-        Q.du_batch_stride, Q.du_d_stride = du.stride(0), du.stride(1)
-        Q.ddelta_batch_stride, Q.ddelta_d_stride = ddelta.stride(0), ddelta.stride(1)
-        Q.dz_batch_stride, Q.dz_d_stride = dz.stride(0), dz.stride(1)
-        Q.dout_ptr, Q.dA_ptr, Q.dB_ptr, Q.dC_ptr, Q.dD_ptr = _ptr(dout), _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD)
-        Q.du_ptr, Q.dz_ptr, Q.ddelta_ptr, Q.ddelta_bias_ptr = _ptr(du), _ptr(dz), _ptr(ddelta), _ptr(ddelta_bias)
-        P.A_b_ptr, P.A_b_d_stride, P.A_b_dstate_stride = _ptr(A_b), A_b.stride(0), A_b.stride(1)
-        P.out_b_ptr, P.out_b_batch_stride, P.out_b_d_stride = _ptr(out_b), out_b.stride(0), out_b.stride(1)
-        P.ckpt_b_ptr = _ptr(ckpt_b)
+        _fill_ssm(P.bwd.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, None, out_z, ckpt)
+        ws = _fill_ssm_bwd(P.bwd, dout, du, ddelta, dA, dB, dC, dD, ddelta_bias, dz, ckpt)
+        _fill_ssm_reversed(P, A_b, out_b, ckpt_b)
         P.dA_b_ptr, P.dA_b_d_stride, P.dA_b_dstate_stride = _ptr(dA_b), dA_b.stride(0), dA_b.stride(1)
-        lib = _lib.load()
-        nbytes = lib.dimsum_ssm_scan_bwd_workspace_bytes(batch, dim, seqlen, dstate, B.shape[1]) - ckpt.numel() * 4    # partial dB / dC only
-        ws = torch.empty((nbytes + 3) // 4, device=u.device, dtype=torch.float32)
-        Q.workspace_ptr, Q.workspace_bytes = _ptr(ws), nbytes
         with torch.cuda.device(u.device):
-            _lib.check(lib.dimsum_ssm_scan_bidir_bwd(P, _stream(u)), "selective_scan_bidir_bwd")
+            _lib.check(_lib.load().dimsum_ssm_scan_bidir_bwd(P, _stream(u)), "selective_scan_bidir_bwd")
+        del ws
     res = [du, ddelta, dA, dA_b, dB.to(B.dtype), dC.to(C.dtype), dD, ddelta_bias, dz]
     if out_z is not None:
         res.append(out_z)
