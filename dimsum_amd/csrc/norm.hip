@@ -7,7 +7,7 @@
 // Streaming op: forward prenorm moves 4*M*N*4 bytes (x, residual in; y, residual_out out).
 //
 // MI355X design: one wave64 per row, the row lives in registers (16 B per lane per piece, up to 8 pieces = 2048 columns;
-// wider rows take a re-reading path), statistics by cross-lane butterflies -- no LDS, no block barrier. The backward
+// wider rows are refused: the launchers return DIMSUM_ERR_SHAPE without a launch), statistics by cross-lane butterflies -- no LDS, no block barrier. The backward
 // keeps per-lane dweight/dbias partial sums in registers over all the rows a wave owns and flushes them with one
 // atomic per column per wave (the Triton reference writes per-SM partials and reduces them on the host).
 #include "common.hpp"
