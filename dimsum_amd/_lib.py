@@ -83,6 +83,18 @@ class OptimParams(_Sized):
 OPTIM_CHUNK, OPTIM_MAX_PARTIALS = 4096, 2048       # DIMSUM_OPTIM_CHUNK, DIMSUM_OPTIM_MAX_PARTIALS
 
 
+class FmPlanParams(_Sized):
+    """dimsum_fm_plan_params_t: x_t / u_t of the interpolation plan from a (5, batch) coefficient table, optional DCT blur of x1 for x_t"""
+    _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "channels", "height", "width", "patch")] + [("min_scale", f32), ("reserved", i32)]
+                + [("x1_batch_stride", i64)] + [(n, vp) for n in ("x1", "x0", "coef", "xt", "ut")] + [("reserved2", i64 * 2)])
+
+
+class FmLossParams(_Sized):
+    """dimsum_fm_loss_params_t: loss_b = w_b mean (c_b out + sign tgt)^2 and its gradient with respect to out"""
+    _fields_ = ([("struct_size", u32), ("batch", i32), ("n", i64), ("sign", f32), ("reserved", i32)]
+                + [(n, vp) for n in ("out", "tgt", "w", "c", "loss", "gloss", "dout")] + [("reserved2", i64 * 2)])
+
+
 class ConvParams(_Sized):
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "dim", "seqlen", "width", "silu_activation", "dtype", "reserved")]
                 + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "weight_c_stride", "weight_width_stride",
@@ -169,6 +181,7 @@ EXPORTS = (
     "dimsum_ssm_scan_fwd", "dimsum_ssm_scan_bwd", "dimsum_ssm_scan_bwd_workspace_bytes", "dimsum_ssm_scan_fwd_variant",
     "dimsum_ssm_scan_bidir_fwd", "dimsum_ssm_scan_bidir_bwd", "dimsum_ssm_scan_bidir_fwd_variant",
     "dimsum_optim_grad_sumsq", "dimsum_optim_adamw_ema_step", "dimsum_optim_write_ptrs",
+    "dimsum_fm_plan", "dimsum_fm_loss_fwd", "dimsum_fm_loss_bwd",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
@@ -186,7 +199,8 @@ _SIGNATURES = (
         ("dimsum_ssm_scan_bidir_bwd", SsmBidirBwdParams), ("dimsum_optim_grad_sumsq", OptimParams), ("dimsum_optim_adamw_ema_step", OptimParams),
         ("dimsum_causal_conv1d_fwd", ConvParams), ("dimsum_causal_conv1d_bwd", ConvBwdParams), ("dimsum_norm_fwd", NormParams),
         ("dimsum_norm_bwd", NormBwdParams), ("dimsum_token_transform", TtParams), ("dimsum_xattn_fusion_fwd", XattnParams),
-        ("dimsum_xattn_fusion_bwd", XattnBwdParams), ("dimsum_gemm_nt", GemmParams))]
+        ("dimsum_xattn_fusion_bwd", XattnBwdParams), ("dimsum_gemm_nt", GemmParams), ("dimsum_fm_plan", FmPlanParams),
+        ("dimsum_fm_loss_fwd", FmLossParams), ("dimsum_fm_loss_bwd", FmLossParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

@@ -1389,3 +1389,79 @@ def optim_adamw_ema_step(P, device):
     """dimsum_optim_adamw_ema_step on the current stream of `device`"""
     with torch.cuda.device(device):
         _lib.check(_lib.load().dimsum_optim_adamw_ema_step(P, torch.cuda.current_stream(device).cuda_stream), "dimsum_optim_adamw_ema_step")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the head of a training step: x_t / u_t of the interpolation plan (optionally with the DCT blur of x1) and the per-sample loss with its
+# gradient (dimsum_fm_*; dimsum_amd/transport is the user)
+# ---------------------------------------------------------------------------------------------------------------------
+FM_PATCHES = (2, 4, 8)        # the tile sizes fm_plan's blur has an instantiation for
+
+
+def _fm_f32(what, *ts):
+    for t in ts:
+        if t is not None:
+            _check(t.dtype == torch.float32 and t.is_contiguous(), f"{what}: contiguous float32 tensors are required")
+
+
+def fm_plan(x1, x0, coef, patch=0, min_scale=1e-3, need_ut=True):
+    """-> (xt, ut): xt = alpha_b B(x1) + sigma_b x0, ut = d_alpha_b x1 + d_sigma_b x0 in ONE launch. coef: (5, B) rows alpha, sigma, d_alpha,
+    d_sigma, blur_t = blur_sigma^2 / 2. patch 0: B is the identity; patch in FM_PATCHES: the per-tile DCT blur (ut still takes the unblurred x1).
+    x1: (B, C, H, W), its three inner dimensions contiguous (a batch-strided view is read in place). x0 None: the sigma terms are left out.
+    need_ut False: -> (xt, None)."""
+    _gpu(x1, x0, coef)
+    _check(x1.dim() == 4 and x1.dtype == torch.float32, "fm_plan: x1 is a float32 (B, C, H, W) tensor")
+    B, C, H, W = x1.shape
+    _check(patch == 0 or patch in FM_PATCHES, f"fm_plan: no kernel for patch size {patch} (the blur is instantiated for {FM_PATCHES}; 0 = no blur)")
+    _check(B > 0 and C * H * W > 0, "fm_plan: empty tensors are not supported")
+    align = 0 if patch == 0 else 8 if patch == 2 else 16      # the blur reads whole rows of a tile as one vector; without blur any address works
+    if x1.stride()[1:] != (H * W, W, 1) or (align and (x1.data_ptr() % align or (B > 1 and x1.stride(0) * 4 % align))):
+        x1 = x1.clone(memory_format=torch.contiguous_format)
+    _fm_f32("fm_plan", x0, coef)
+    _check(x0 is None or x0.shape == x1.shape, "fm_plan: x0 has the shape of x1")
+    _check(tuple(coef.shape) == (5, B), "fm_plan: the coefficient table is (5, B)")
+    xt = torch.empty((B, C, H, W), dtype=torch.float32, device=x1.device)
+    ut = torch.empty_like(xt) if need_ut else None
+    P = _lib.FmPlanParams()
+    P.batch, P.channels, P.height, P.width, P.patch, P.min_scale = B, C, H, W, patch, min_scale
+    P.x1_batch_stride = x1.stride(0) if B > 1 else C * H * W
+    P.x1, P.x0, P.coef, P.xt, P.ut = x1.data_ptr(), _ptr(x0), coef.data_ptr(), xt.data_ptr(), _ptr(ut)
+    with torch.cuda.device(x1.device):
+        _lib.check(_lib.load().dimsum_fm_plan(P, _stream(x1)), "dimsum_fm_plan")
+    return xt, ut
+
+
+def _fm_loss_params(what, out, tgt, w, c, sign):
+    _gpu(out, tgt, w, c)
+    _fm_f32(what, out, tgt, w, c)
+    B = out.shape[0]
+    _check(out.dim() >= 2 and out.shape == tgt.shape and out.numel() > 0, f"{what}: out and tgt are (B, ...) tensors of one shape")
+    _check(all(v is None or tuple(v.shape) == (B,) for v in (w, c)), f"{what}: w and c are (B,) tensors (or None = 1)")
+    _check(sign in (1, -1), f"{what}: sign is +1 or -1")
+    P = _lib.FmLossParams()
+    P.batch, P.n, P.sign = B, out.numel() // B, sign
+    P.out, P.tgt, P.w, P.c = out.data_ptr(), tgt.data_ptr(), _ptr(w), _ptr(c)
+    return P
+
+
+def fm_loss_fwd(out, tgt, w=None, c=None, sign=-1):
+    """-> loss (B,): loss_b = w_b mean_i (c_b out_i + sign tgt_i)^2, one fixed summation order (two launches on equal inputs are bit-equal)"""
+    P = _fm_loss_params("fm_loss_fwd", out, tgt, w, c, sign)
+    loss = torch.empty(out.shape[0], dtype=torch.float32, device=out.device)
+    P.loss = loss.data_ptr()
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.load().dimsum_fm_loss_fwd(P, _stream(out)), "dimsum_fm_loss_fwd")
+    return loss
+
+
+def fm_loss_bwd(gloss, out, tgt, w=None, c=None, sign=-1):
+    """-> d loss / d out (shape of out): gloss_b 2 w_b c_b (c_b out + sign tgt) / n"""
+    P = _fm_loss_params("fm_loss_bwd", out, tgt, w, c, sign)
+    _gpu(gloss)
+    _fm_f32("fm_loss_bwd", gloss)
+    _check(tuple(gloss.shape) == (out.shape[0],), "fm_loss_bwd: gloss is (B,)")
+    dout = torch.empty_like(out)
+    P.gloss, P.dout = gloss.data_ptr(), dout.data_ptr()
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.load().dimsum_fm_loss_bwd(P, _stream(out)), "dimsum_fm_loss_bwd")
+    return dout

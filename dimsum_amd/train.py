@@ -96,8 +96,7 @@ def build_training(model, device, lr=1e-4, world_size=1, device_ids=None, fused_
     return model, ema, opt
 
 
-def main(argv=None):
-    from .create_model import create_model, published_config
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="DiM-L/2")
     ap.add_argument("--image-size", type=int, default=256)
@@ -113,7 +112,23 @@ def main(argv=None):
     ap.add_argument("--resume", default=None)
     ap.add_argument("--save", default=None, help="rank 0 writes the checkpoint container here at the end")
     ap.add_argument("--tf32", action=argparse.BooleanOptionalAction, default=True)
-    args, _ = ap.parse_known_args(argv)
+    ap.add_argument("--use-blurring", action="store_true", help="DCT-blur the data end of the path (train.py:184-192)")
+    ap.add_argument("--blur-sigma-max", type=int, default=3)
+    ap.add_argument("--blur-upscale", type=int, default=4)
+    ap.add_argument("--fused-head", action=argparse.BooleanOptionalAction, default=None,
+                    help="plan and loss of the step on one HIP launch each; default: DIMSUM_FUSED_HEAD")
+    return ap
+
+
+def transport_from_args(args):
+    """the transport of a run: the blurring flags travel as path_args, like the reference's driver passes them (train.py:598-600)"""
+    path_args = dict(use_blurring=args.use_blurring, blur_sigma_max=args.blur_sigma_max, blur_upscale=args.blur_upscale)
+    return create_transport(args.path_type, args.prediction, path_args=path_args, fused_head=args.fused_head)
+
+
+def main(argv=None):
+    from .create_model import create_model, published_config
+    args, _ = build_parser().parse_known_args(argv)
     torch.backends.cuda.matmul.allow_tf32 = args.tf32          # train.py:20-21
     torch.backends.cudnn.allow_tf32 = args.tf32
 
@@ -127,7 +142,7 @@ def main(argv=None):
     torch.manual_seed(args.global_seed * world + rank)
     model = create_model(published_config(args.model, args.image_size, args.num_classes)).to(device)
     model, ema, opt = build_training(model, device, args.lr, world, [device])
-    transport = create_transport(args.path_type, args.prediction)
+    transport = transport_from_args(args)
     init_epoch, train_steps = (load_checkpoint(args.resume, model, ema, opt, lr=args.lr) if args.resume else (0, 0))
     model.train()
     r, b = args.image_size // 8, args.global_batch_size // world

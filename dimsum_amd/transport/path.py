@@ -1,8 +1,11 @@
 """Interpolation plans x_t = alpha_t x1 + sigma_t x0 of the flow-matching transport (dimsum/transport/path.py:21-246):
-Linear (ICPlan), GVP (sin/cos) and VP. t runs from noise (0) to data (1)."""
+Linear (ICPlan), GVP (sin/cos) and VP. t runs from noise (0) to data (1). With use_blurring, x1 enters x_t (and only x_t) through the DCT blur
+of blurring.py, strongest at the noise end (path.py:159-169)."""
 import math
 
 import torch as th
+
+from .blurring import check_blur_shape, dct_blur
 
 
 def expand_t_like_x(t, x):
@@ -13,8 +16,11 @@ def expand_t_like_x(t, x):
 class ICPlan:
     """alpha = t, sigma = 1 - t"""
 
-    def __init__(self, sigma=0.0, **_):
+    def __init__(self, sigma=0.0, diffusion_form="none", use_blurring=False, blur_sigma_max=3, blur_upscale=4, **_):
         self.sigma = sigma
+        self.diffusion_form = diffusion_form
+        self.use_blurring, self.blur_sigma_max, self.blur_upscale = use_blurring, blur_sigma_max, blur_upscale
+        self.fused_head = False          # Transport(fused_head=True): plan() is one dimsum_fm_plan launch also without blurring
 
     def compute_alpha_t(self, t):
         return t, 1
@@ -61,17 +67,39 @@ class ICPlan:
         var = sigma_t ** 2 - reverse_alpha_ratio * d_sigma_t * sigma_t
         return (reverse_alpha_ratio * velocity - x) / var
 
+    def blur_sigmas(self, sigma_t):
+        """blur level along the path: blur_sigma_max at the noise end (sigma_t = 1), none at the data end (path.py:165-167)"""
+        return self.blur_sigma_max * th.sin(sigma_t * math.pi / 2) ** 2
+
     def compute_mu_t(self, t, x0, x1):
         t = expand_t_like_x(t, x1)
+        if self.use_blurring:
+            x1 = dct_blur(x1, self.blur_upscale, self.blur_sigmas(self.compute_sigma_t(t)[0]))
         return self.compute_alpha_t(t)[0] * x1 + self.compute_sigma_t(t)[0] * x0
 
     compute_xt = compute_mu_t
 
     def compute_ut(self, t, x0, x1, xt):
+        """from the UNBLURRED x1, with or without blurring (path.py:176-181)"""
         t = expand_t_like_x(t, x1)
         return self.compute_alpha_t(t)[1] * x1 + self.compute_sigma_t(t)[1] * x0
 
+    def coef_table(self, t):
+        """(5, B) rows alpha_t, sigma_t, d alpha_t, d sigma_t, blur_sigma^2 / 2 from the methods above on the (B,) times: what dimsum_fm_plan reads"""
+        (a, da), (s, ds) = self.compute_alpha_t(t), self.compute_sigma_t(t)
+        bt = self.blur_sigmas(s) ** 2 / 2 if self.use_blurring else 0.0
+        return th.stack([v if isinstance(v, th.Tensor) else th.full_like(t, float(v)) for v in (a, s, da, ds, bt)])
+
     def plan(self, t, x0, x1):
+        if (self.use_blurring or self.fused_head) and x1.is_cuda and x1.dtype == th.float32 and x1.dim() == 4 and x0.dtype == th.float32:
+            from .. import native
+            if self.use_blurring:
+                check_blur_shape(x1, self.blur_upscale)
+                if self.blur_upscale not in native.FM_PATCHES:
+                    raise RuntimeError(f"ICPlan: no HIP kernel for blur_upscale {self.blur_upscale} (instantiated for {native.FM_PATCHES}) and no "
+                                       "torch path on CUDA")
+            xt, ut = native.fm_plan(x1, x0.contiguous(), self.coef_table(t.to(x1)), self.blur_upscale if self.use_blurring else 0)
+            return t, xt, ut
         xt = self.compute_xt(t, x0, x1)
         return t, xt, self.compute_ut(t, x0, x1, xt)
 

@@ -1,7 +1,10 @@
 """Flow-matching transport: training loss, ODE / SDE samplers and the likelihood ODE around the denoiser
-(dimsum/transport/transport.py). The DCT blurring of the path (never enabled by the published configs) is left out."""
+(dimsum/transport/transport.py). The DCT blurring of the path (path_args use_blurring / blur_sigma_max / blur_upscale, never enabled by the
+published configs) lives in path.py and blurring.py. `fused_head` puts both ends of the head of a training step on one HIP launch each: the
+plan (x_t, u_t) before the model, the per-sample loss and its gradient after it."""
 import enum
 import math
+import os
 
 import torch as th
 
@@ -31,11 +34,33 @@ def mean_flat(x):
     return th.mean(x, dim=list(range(1, x.dim())))
 
 
+class FusedLoss(th.autograd.Function):
+    """loss_b = w_b mean (c_b out + sign tgt)^2 on dimsum_fm_loss_fwd, its gradient with respect to `out` (the model's output, nothing else) on
+    dimsum_fm_loss_bwd. w, c: (B,) or None = 1."""
+
+    @staticmethod
+    def forward(ctx, out, tgt, w, c, sign):
+        from .. import native
+        out, tgt = out.contiguous(), tgt.contiguous()
+        ctx.save_for_backward(out, tgt, w, c)
+        ctx.sign = sign
+        return native.fm_loss_fwd(out, tgt, w, c, sign)
+
+    @staticmethod
+    def backward(ctx, gloss):
+        from .. import native
+        out, tgt, w, c = ctx.saved_tensors
+        return native.fm_loss_bwd(gloss.contiguous(), out, tgt, w, c, ctx.sign), None, None, None, None
+
+
 class Transport:
-    def __init__(self, *, model_type, path_type, loss_type, train_eps, sample_eps, path_args={}, t_sample_mode="uniform"):
+    def __init__(self, *, model_type, path_type, loss_type, train_eps, sample_eps, path_args={}, t_sample_mode="uniform", fused_head=None):
         plans = {PathType.LINEAR: path.ICPlan, PathType.GVP: path.GVPCPlan, PathType.VP: path.VPCPlan}
         self.loss_type, self.model_type = loss_type, model_type
         self.path_sampler = plans[path_type](**path_args)
+        # None reads DIMSUM_FUSED_HEAD (default "0": the torch expressions, as before); applies to CUDA float32 tensors only
+        self.fused_head = os.environ.get("DIMSUM_FUSED_HEAD", "0") != "0" if fused_head is None else bool(fused_head)
+        self.path_sampler.fused_head = self.fused_head
         self.train_eps, self.sample_eps, self.t_sample_mode = train_eps, sample_eps, t_sample_mode
 
     def prior_logp(self, z):
@@ -72,6 +97,9 @@ class Transport:
         out = model(xt, t, **model_kwargs)
         assert out.size() == xt.size()
         terms = {"pred": out}
+        if self.fused_head and out.is_cuda and out.dtype == th.float32 and ut.dtype == th.float32:
+            terms["loss"] = self._fused_loss(out, t, x0, ut)
+            return terms
         if self.model_type == ModelType.VELOCITY:
             terms["loss"] = mean_flat((out - ut) ** 2)
             return terms
@@ -84,6 +112,21 @@ class Transport:
         else:
             terms["loss"] = mean_flat(weight * ((out * sigma_t + x0) ** 2))
         return terms
+
+    def _fused_loss(self, out, t, x0, ut):
+        """the three loss expressions of training_losses as loss_b = w_b mean (c_b out + sign tgt)^2, the per-sample scalars from the path's
+        own methods on the (B,) times: velocity (c = 1, tgt = u_t, -), noise (c = 1, tgt = x0, -, w), score (c = sigma_t, tgt = x0, +, w)"""
+        if self.model_type == ModelType.VELOCITY:
+            return FusedLoss.apply(out, ut, None, None, -1)
+        ps = self.path_sampler
+        sigma_t = ps.compute_sigma_t(t)[0]
+        w = None
+        if self.loss_type != WeightType.NONE:
+            drift_var = ps.compute_drift(t, t)[1]                      # the variance term depends on t alone; the drift of the dummy x is dropped
+            w = ((drift_var / sigma_t) ** 2 if self.loss_type == WeightType.VELOCITY else drift_var / (sigma_t ** 2)).contiguous()
+        if self.model_type == ModelType.NOISE:
+            return FusedLoss.apply(out, x0, w, None, -1)
+        return FusedLoss.apply(out, x0, w, sigma_t.contiguous(), 1)
 
     def get_drift(self):
         """drift of the probability-flow ODE (transport.py:166-197)"""

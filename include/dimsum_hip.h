@@ -8,6 +8,7 @@
  *   dimsum_ssm_scan_bwd        <- selective_scan_cuda.bwd      mamba/csrc/selective_scan/selective_scan.cpp:338-492
  *   dimsum_ssm_scan_bidir_fwd / _bwd <- the two selective_scan_cuda calls (+ flips) of BiMambaInnerFn  mamba/mamba_ssm/ops/selective_scan_interface.py:1010-1388
  *   dimsum_optim_grad_sumsq / dimsum_optim_adamw_ema_step <- clip_grad_norm_ + AdamW.step + update_ema   dimsum/train.py:55-64,317-321
+ *   dimsum_fm_plan / dimsum_fm_loss_fwd / _bwd <- ICPlan.plan + DCTBlur, the loss of Transport.training_losses   dimsum/transport/path.py:159-259, transport.py:127-164
  *   dimsum_causal_conv1d_fwd   <- causal_conv1d_cuda.causal_conv1d_fwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:221-336
  *   dimsum_causal_conv1d_bwd   <- causal_conv1d_cuda.causal_conv1d_bwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:338-509
  *   dimsum_norm_fwd / _bwd     <- _layer_norm_fwd / _layer_norm_bwd (Triton)     mamba/mamba_ssm/ops/triton/layernorm.py:120-364
@@ -277,6 +278,60 @@ int dimsum_optim_adamw_ema_step(const dimsum_optim_params_t *p, void *stream);
  * (autograd allocates new gradients) without a synchronisation or a staging buffer that a later step could overwrite too early. */
 #define DIMSUM_OPTIM_PTRS_PER_LAUNCH 448
 int dimsum_optim_write_ptrs(void *dst_table, int64_t first, const void *const *src, int32_t count, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Training-step head: the interpolation plan of the flow-matching transport with the optional DCT blur of the data, and the per-sample
+ * loss with its gradient (<- ICPlan.plan + DCTBlur  dimsum/transport/path.py:159-188,249-259 and the three loss expressions of
+ * Transport.training_losses  dimsum/transport/transport.py:127-164). Added under ABI 18 (new symbols only). fp32 only, no atomics, no
+ * synchronisation; the caller allocates every output.
+ *
+ * dimsum_fm_plan, one launch. x1: (batch, channels, height, width), innermost three dimensions contiguous, x1_batch_stride elements
+ * between samples (a batch-strided view); x0, xt, ut: contiguous tensors of the same shape. coef: (5, batch) contiguous, rows alpha, sigma,
+ * d_alpha, d_sigma, blur_t (= blur_sigma^2 / 2) -- the path's formulas stay with the caller.
+ *   xt = alpha_b * B(x1) + sigma_b * x0        ut = d_alpha_b * x1 + d_sigma_b * x0        (ut from the UNBLURRED x1, like the reference)
+ *   patch == 0: B is the identity (the blur_t row is not read). patch in {2, 4, 8}: height == width, a multiple of patch; every patch x patch
+ *   tile X of every channel becomes C^T (G_b o (C X C^T)) C, C the orthonormal patch-point DCT-II matrix,
+ *   G_b[i][j] = exp(-(f_i^2 + f_j^2) blur_t_b) (1 - min_scale) + min_scale, f_k = pi k / patch. One tile per lane, in registers.
+ *   x0 NULL: the sigma terms are left out (xt = alpha_b * B(x1): the blur alone with alpha = 1). ut NULL: not written.
+ *   Each product is rounded before the sum (no contraction), so patch == 0 gives bit for bit what the expression gives in separate passes.
+ *   Alignment: patch 4 and 8 read and write 16-byte vectors, patch 2 8-byte ones (base pointers and x1_batch_stride), else DIMSUM_ERR_STRIDE.
+ *
+ * dimsum_fm_loss_fwd / dimsum_fm_loss_bwd. out, tgt, dout: (batch, n) contiguous; w, c, gloss, loss: (batch); w or c NULL: 1; sign: +1 or -1.
+ *   forward : loss_b = w_b * mean_i (c_b * out_i + sign * tgt_i)^2
+ *   backward: dout_i = gloss_b * 2 * w_b * c_b * (c_b * out_i + sign * tgt_i) / n
+ *   velocity prediction: c = 1, tgt = ut, sign = -1, w = 1; noise: c = 1, tgt = x0, sign = -1, w = weight; score: c = sigma_t, tgt = x0, sign = +1.
+ *   One workgroup per sample. Lane l of the workgroup owns the elements [1024 k + 4 l, + 4), k = 0, 1, ..., whatever the alignment and the
+ *   tail; the lanes of a wave are summed by a butterfly, the four waves in order through LDS: the order of every sum is a function of n
+ *   alone, so equal inputs give bit-equal losses. n is arbitrary (1 <= n < 2^31).
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_fm_plan_params_t) */
+    int32_t batch, channels, height, width;
+    int32_t patch;             /* 0 (no blur), 2, 4 or 8 */
+    float min_scale;           /* the floor of the blur's gain (the reference: 1e-3) */
+    int32_t reserved;          /* 0 */
+    int64_t x1_batch_stride;   /* elements */
+    const void *x1, *x0, *coef;
+    void *xt, *ut;
+    int64_t reserved2[2];      /* 0 */
+} dimsum_fm_plan_params_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_fm_loss_params_t) */
+    int32_t batch;
+    int64_t n;                 /* elements per sample */
+    float sign;                /* +1 or -1 */
+    int32_t reserved;          /* 0 */
+    const void *out, *tgt, *w, *c;
+    void *loss;                /* forward: written; backward: not read */
+    const void *gloss;         /* backward: the gradient of each loss_b */
+    void *dout;                /* backward: written */
+    int64_t reserved2[2];      /* 0 */
+} dimsum_fm_loss_params_t;
+
+int dimsum_fm_plan(const dimsum_fm_plan_params_t *p, void *stream);
+int dimsum_fm_loss_fwd(const dimsum_fm_loss_params_t *p, void *stream);
+int dimsum_fm_loss_bwd(const dimsum_fm_loss_params_t *p, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Causal depthwise conv1d, width 2..4, optional bias, optional SiLU.  Mirrors ConvParamsBase / ConvParamsBwd

@@ -578,6 +578,52 @@ def gen_transport(_ns=None):
          "euler stand-in of tools/ref_shim.py:load_transport), path.py:21-246; denoiser = tests/golden/procedural.py:toy_denoiser", **arrs)
 
 
+BLUR_CASES = (("p4", (5, 3, 8, 8), 4), ("p8", (3, 2, 8, 8), 8), ("p2", (3, 2, 8, 8), 2), ("p4_32", (2, 4, 32, 32), 4))
+BLUR_LOSS_CASES = (("GVP", "velocity", None), ("Linear", "velocity", None), ("VP", "velocity", None), ("GVP", "noise", "velocity"),
+                   ("GVP", "score", "likelihood"))
+BLUR_SIGMA_MAX = 3
+
+
+def gen_transport_blur(_ns=None):
+    """The reference's DCT-blurred path: DCTBlur(x, p, sigmas, 1e-3) (dimsum/transport/path.py:249-259 over blurring.py's FFT-based DCT) for
+    BLUR_CASES (x = procedural.seeded(shape, x_seed), not stored), the per-sample sigmas including exactly 0 and exactly blur_sigma_max; and Transport.training_losses with
+    path_args use_blurring=True (path.py:159-169) around toy_denoiser for BLUR_LOSS_CASES. A fixture of its own: transport.npz stays as it is."""
+    tp = ref_shim.load_transport()
+    ref_path = sys.modules[tp.__name__ + ".path"]
+    arrs = {}
+    for i, (tag, shape, p) in enumerate(BLUR_CASES):
+        x = T(seeded(shape, 91 + i))
+        sig = torch.linspace(0, BLUR_SIGMA_MAX, shape[0]) if shape[0] > 2 else torch.tensor([0.0, float(BLUR_SIGMA_MAX)])
+        if shape[0] > 3:
+            sig[1:-1] = T(seeded((shape[0] - 2,), 95 + i)).abs().clamp(0.05, 2.9)          # uneven levels between the two ends
+        assert sig[0] == 0 and sig[-1] == BLUR_SIGMA_MAX
+        out = ref_path.DCTBlur(x, p, sig.view(-1, 1, 1, 1), 1e-3, x.device)
+        arrs.update({f"blur_{tag}_x_seed": np.array(91 + i), f"blur_{tag}_shape": np.array(shape), f"blur_{tag}_p": np.array(p), f"blur_{tag}_sigmas": sig, f"blur_{tag}_out": out})
+    arrs["blur_cases"] = np.array([c[0] for c in BLUR_CASES])
+    x1 = T(seeded((5, 3, 8, 8), 83))
+    y = torch.tensor([3, 0, 7, 1, 5])
+    arrs.update(loss_x1=x1, y=y, blur_sigma_max=np.array(BLUR_SIGMA_MAX), blur_upscale=np.array(4))
+    for n, (pt, pred, lw) in enumerate(BLUR_LOSS_CASES):
+        tr = tp.create_transport(pt, pred, lw, **TRANSPORT_EPS,
+                                 path_args=dict(use_blurring=True, blur_sigma_max=BLUR_SIGMA_MAX, blur_upscale=4))
+        seen = {}
+
+        def model(xt, t, y=None):
+            seen["xt"], seen["t"] = xt, t
+            return toy_denoiser(xt, t, y)
+
+        seed = 4000 + n
+        torch.manual_seed(seed)
+        terms = tr.training_losses(model, x1, dict(y=y))
+        tag = f"loss_{pt}_{pred}_{lw}"
+        arrs.update({tag + "_seed": np.array(seed), tag + "_t": seen["t"], tag + "_xt": seen["xt"], tag + "_loss": terms["loss"],
+                     tag + "_pred": terms["pred"]})
+    arrs["loss_cases"] = np.array([repr(c) for c in BLUR_LOSS_CASES])
+    save("transport_blur", "dimsum/transport: DCTBlur (path.py:249-259, blurring.py:32-149) and Transport.training_losses "
+         "(transport.py:127-164) with path_args use_blurring=True, blur_sigma_max=3, blur_upscale=4 (path.py:159-169); "
+         "denoiser = tests/golden/procedural.py:toy_denoiser", **arrs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -594,6 +640,7 @@ def main():
         "zigzag": lambda: gen_models(ns, {"tiny"}, only_tags=("tiny_zigma8", "tiny_jpeg8", "tiny_sweep8")),
         "XL2zigzag": lambda: gen_models(ns, {"model_XL2_512_zigma8"}),
         "transport": lambda: gen_transport(ns), "block1024": lambda: gen_block_1024(ns),
+        "transport_blur": lambda: gen_transport_blur(ns),
     }
     for k, fn in steps.items():
         if args.only is None or k in args.only:
