@@ -1,6 +1,7 @@
 """DiM denoiser -- same module tree, constructor flags and state_dict keys as dimsum/models_dim.py
 (DiM :1557-1930, DiMBlockCombined :974-1117, DiMBlockCombinedFourier :1120-1264, DiMBlockRaw :1402-1529,
-WaveDiMBlock :505-710, DCTBlock :778-933, DiTBlock :1532-1554, embedders/FinalLayer :129-220, create_block :2001-2160,
+DiMBlock :223-358, DiMBlockWindow :361-502, WaveDiMBlock :505-710, DCTBlock :778-933, DiTBlock :1532-1554,
+embedders/FinalLayer :129-220, create_block :2001-2160,
 zoo :2163-2236), composed from the HIP operators of dimsum_amd.ops.
 
 What is structured differently (results equal to fp32 roundoff; pinned by tests/golden/*):
@@ -8,7 +9,7 @@ What is structured differently (results equal to fp32 roundoff; pinned by tests/
     construction into one gather table; the pre-mixer path  modulate(P(T(x)))  and the post-mixer path
     x + T^-1(P^-1(gate * mixer(...)))  are each ONE fused pass (ops/token_ops.py), T = Haar / DCT / identity;
   * the GatedMLP activation is a fused epilogue; RMSNorm is the HIP fused add+norm, not Triton.
-Out of scope (constructor raises): block types linear/window/combined_einfft, MoE, rope/cpe positional encodings and
+Out of scope (constructor raises): block type combined_einfft, MoE, rope/cpe positional encodings and
 `enable_fourier_layers` -- unused by every published config.
 """
 import math
@@ -309,6 +310,38 @@ def _mlp_tail(mlp, x, normed, shift, scale, gate):
     return token_ops.gate_residual(x, mlp(h), gate, None)
 
 
+def _fast_tail(norm_2, mlp, hidden_states):
+    return (not torch.is_grad_enabled() and isinstance(norm_2, RMSNorm) and hasattr(mlp, "forward_deferred")
+            and hidden_states.dtype == torch.float32)
+
+
+def _norm_mlp_tail(norm_2, mlp, hidden_states, shift, scale, gate, fused=None, pb=None, in_epilogue=False):
+    """h' + gate * mlp(modulate(norm_2(h'), shift, scale)),  h' = hidden_states [+ fused + pb]: the FFN tail of the combined blocks (fused, pb: the
+    fusion's deferred projection and its bias; in_epilogue: the proj GEMM already added hidden_states to `fused`) and of DiMBlock / DiMBlockWindow"""
+    if _fast_tail(norm_2, mlp, hidden_states):
+        # inference: h' = h + proj(..) + b, RMSNorm(h'), modulate -- ONE pass (csrc/norm.hip with x_bias + modulation)
+        from . import native
+        B, L, H = hidden_states.shape
+        x, res = (hidden_states, None) if fused is None else (fused, None if in_epilogue else hidden_states)
+        # ... written directly as the split-bf16 operand image of the w12 GEMM when the library would split it anyway (gemm.py)
+        s3 = getattr(mlp, "_fused", False) and gemm.split3_enabled(hidden_states, mlp.w12.weight, producer="norm")   # False / True / "f16s"
+        y, _, _, hnew = native.layer_norm_fwd(x.reshape(B * L, H), norm_2.weight, norm_2.bias, norm_2.eps,
+                                              residual=None if res is None else res.reshape(B * L, H), is_rms_norm=True, x_bias=pb,
+                                              mod_scale=scale, mod_shift=shift, rows_per_batch=L, **({"split3": s3} if s3 else {}))
+        if s3 and hnew.is_contiguous():       # ... and the residual tail "h + gate * (mlp + b)" in the epilogue of the w3 GEMM
+            return mlp.forward_deferred(hidden_states, x3=y, residual=hnew.view(B, L, H), gate=gate)[0]
+        m, mb = mlp.forward_deferred(hidden_states, x3=y) if s3 else mlp.forward_deferred(y.view(B, L, H))
+        return token_ops.gate_residual(hnew.view(B, L, H), m, gate, mb)
+    if fused is not None:
+        hidden_states = token_ops.gate_residual(hidden_states, fused, None, pb)
+    if isinstance(norm_2, RMSNorm) and hidden_states.is_cuda and torch.is_grad_enabled():
+        # training: the norm hands the stream on (prenorm), so that "d norm + d tail" is formed inside the norm's backward kernel
+        # (its dresidual input) instead of by an add of two (B, L, dim) gradients in the autograd engine
+        normed, hidden_states = norm_2(hidden_states, prenorm=True)
+        return _mlp_tail(mlp, hidden_states, normed, shift, scale, gate)
+    return _mlp_tail(mlp, hidden_states, norm_2(hidden_states), shift, scale, gate)
+
+
 def _mix_through_images(mixer, hidden_states, kind, table, shift, scale, c, fork=False):
     """mixer(pre_mixer(hidden_states)); at inference under allow_tf32 the pre-mixer pass writes the in_proj operand as a
     split-bf16 image (gemm.py, split3) instead of fp32.
@@ -395,6 +428,60 @@ class DiMBlockRaw(_BlockBase):
         shift, scale, gate = _modulation(self.adaLN_modulation, c).chunk(3, dim=1)
         m, hidden_states = _mix_through_images(self.mixer, hidden_states, "none", table, shift, scale, c, fork=True)
         return token_ops.post_mixer(hidden_states, m, gate, "none", table, **({"split3": out_split3} if out_split3 else {})), residual
+
+
+class DiMBlock(_BlockBase):
+    """plain Mamba block with an FFN, block_type "linear": reorder -> h + gate * mixer(modulate(h)) -> h + gate * mlp(modulate(norm_2(h)))
+    -> undo (models_dim.py:223-358). The reference keeps the stream in the reordered token order through norm_2 and the MLP and undoes the
+    order last; both act on one token at a time, so they commute with the permutation, P^-1(u + g mlp(n(u))) = P^-1(u) + g mlp(n(P^-1(u))):
+    the post-mixer pass undoes the order (the two token passes of DiMBlockRaw, no reordered copy of the stream) and the FFN tail is the
+    combined blocks' (the norm pass writes the w12 operand image). `skip` and `use_gated_mlp` are accepted and unused, as there (:235-274)."""
+
+    def __init__(self, dim, mixer_cls, norm_cls=nn.LayerNorm, fused_add_norm=False, residual_in_fp32=False, drop_path=0.0,
+                 reverse=False, transpose=False, scanning_continuity=False, skip=False, use_gated_mlp=True):
+        super().__init__()
+        self.residual_in_fp32, self.fused_add_norm = residual_in_fp32, fused_add_norm
+        self.reverse, self.transpose, self.scanning_continuity = reverse, transpose, scanning_continuity
+        self.mixer = mixer_cls(dim)
+        self.norm = norm_cls(dim)
+        self.norm_2 = norm_cls(dim)
+        self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
+        self.adaLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(dim, 6 * dim, bias=True))
+        self.mlp = _make_mlp(dim)
+
+    def _order(self, H):
+        if not (self.reverse or self.transpose or self.scanning_continuity):
+            return None
+        return so.block_order_table(H, self.reverse, self.transpose, self.scanning_continuity)
+
+    def forward(self, hidden_states, residual=None, c=None, inference_params=None):
+        hidden_states, residual = self._prenorm(hidden_states, residual)
+        table = self._table(hidden_states.shape[1], hidden_states.device, self._order)
+        shift, scale, gate, shift_mlp, scale_mlp, gate_mlp = _modulation(self.adaLN_modulation, c).chunk(6, dim=1)
+        m, hidden_states = _mix_through_images(self.mixer, hidden_states, "none", table, shift, scale, c, fork=True)
+        hidden_states = token_ops.post_mixer(hidden_states, m, gate, "none", table)
+        return _norm_mlp_tail(self.norm_2, self.mlp, hidden_states, shift_mlp, scale_mlp, gate_mlp), residual
+
+
+class DiMBlockWindow(DiMBlock):
+    """DiMBlock over the 4x4 local-window scan, block_type "window": local_scan(w=4, column_first=transpose) [-> roll by (-1, -1) of the
+    scanned sequence viewed as a grid, shift_window] [-> flip, reverse] -> mixer + FFN -> undo (models_dim.py:361-502). All three steps are
+    token permutations and compose into the block's one table; `scanning_continuity` is stored and unused, as there."""
+
+    def __init__(self, dim, mixer_cls, norm_cls=nn.LayerNorm, fused_add_norm=False, residual_in_fp32=False, drop_path=0.0,
+                 reverse=False, transpose=False, scanning_continuity=False, skip=False, shift_window=False):
+        super().__init__(dim, mixer_cls, norm_cls=norm_cls, fused_add_norm=fused_add_norm, residual_in_fp32=residual_in_fp32,
+                         drop_path=drop_path, reverse=reverse, transpose=transpose, scanning_continuity=scanning_continuity, skip=skip)
+        self.shift_window = shift_window
+
+    def _order(self, H):
+        if H % 4:
+            raise NotImplementedError("DiMBlockWindow: the reference zero-pads a token grid that 4x4 windows do not tile "
+                                      "(scanning_orders.py:358-360), which lengthens the sequence -- not a token permutation")
+        tab = so.local_scan_table(H, 4, column_first=bool(self.transpose))
+        if self.shift_window:
+            tab = so.compose(tab, np.roll(np.arange(H * H).reshape(H, H), (-1, -1), axis=(0, 1)).reshape(-1))
+        return tab[::-1].copy() if self.reverse else tab
 
 
 class _FreqBlock(_BlockBase):
@@ -540,32 +627,12 @@ class _CombinedBase(_BlockBase):
             x1, _ = self.spatial_mamba(x1, None, c, inference_params, **kw)
             x2, _ = self.freq_mamba(x2, None, c, inference_params, **kw)
         # residual tails as single fused passes; the Linear biases ride along (mlp.py / attention_fusion.py docstrings)
-        fast_tail = (not torch.is_grad_enabled() and isinstance(self.norm_2, RMSNorm) and hasattr(self.mlp, "forward_deferred")
-                     and hidden_states.dtype == torch.float32)
+        fast_tail = _fast_tail(self.norm_2, self.mlp, hidden_states)
         # (inference on operand images: "h + proj(..) + b" already in the proj GEMM's epilogue, the norm pass then reads ONE tensor)
         in_epilogue = bool(img) and fast_tail and hidden_states.is_contiguous()
         fused, pb = self.proj.forward_deferred(x1, x2, **({"images": True} if img else {}), **({"residual": hidden_states} if in_epilogue else {}))
         shift, scale, gate = _modulation(self.adaLN_modulation, c).chunk(3, dim=1)
-        if fast_tail:
-            # inference: h' = h + proj(..) + b, RMSNorm(h'), modulate -- ONE pass (csrc/norm.hip with x_bias + modulation)
-            from . import native
-            B, L, H = hidden_states.shape
-            # ... written directly as the split-bf16 operand image of the w12 GEMM when the library would split it anyway (gemm.py)
-            s3 = getattr(self.mlp, "_fused", False) and gemm.split3_enabled(hidden_states, self.mlp.w12.weight, producer="norm")   # False / True / "f16s"
-            y, _, _, hnew = native.layer_norm_fwd(fused.reshape(B * L, H), self.norm_2.weight, self.norm_2.bias, self.norm_2.eps,
-                                                  residual=None if in_epilogue else hidden_states.reshape(B * L, H), is_rms_norm=True, x_bias=pb,
-                                                  mod_scale=scale, mod_shift=shift, rows_per_batch=L, **({"split3": s3} if s3 else {}))
-            if s3 and hnew.is_contiguous():       # ... and the residual tail "h + gate * (mlp + b)" in the epilogue of the w3 GEMM
-                return self.mlp.forward_deferred(hidden_states, x3=y, residual=hnew.view(B, L, H), gate=gate)[0], residual
-            m, mb = self.mlp.forward_deferred(hidden_states, x3=y) if s3 else self.mlp.forward_deferred(y.view(B, L, H))
-            return token_ops.gate_residual(hnew.view(B, L, H), m, gate, mb), residual
-        hidden_states = token_ops.gate_residual(hidden_states, fused, None, pb)
-        if isinstance(self.norm_2, RMSNorm) and hidden_states.is_cuda and torch.is_grad_enabled():
-            # training: the norm hands the stream on (prenorm), so that "d norm + d tail" is formed inside the norm's backward kernel
-            # (its dresidual input) instead of by an add of two (B, L, dim) gradients in the autograd engine
-            normed, hidden_states = self.norm_2(hidden_states, prenorm=True)
-            return _mlp_tail(self.mlp, hidden_states, normed, shift, scale, gate), residual
-        return _mlp_tail(self.mlp, hidden_states, self.norm_2(hidden_states), shift, scale, gate), residual
+        return _norm_mlp_tail(self.norm_2, self.mlp, hidden_states, shift, scale, gate, fused, pb, in_epilogue), residual
 
 
 class DiMBlockCombined(_CombinedBase):
@@ -681,9 +748,13 @@ def create_block(d_model, ssm_cfg=None, norm_epsilon=1e-5, drop_path=0.0, rms_no
         mixer_cls_2 = partial(CondMamba, layer_idx=layer_idx, d_cond=d_model, **ssm_cfg, **block_kwargs2, **fk)
         block = DiMBlockCombinedFourier(d_model, mixer_cls, mixer_cls_2, reverse=reverse, transpose=transpose,
                                         use_gated_mlp=use_gated_mlp, **common)
-    else:
-        raise NotImplementedError(f"block_type={block_type!r} is outside the denoiser hot path "
-                                  "(published configs use 'combined'; also available: raw, wave, combined_fourier)")
+    elif block_type == "window":        # (the flag mapping is the reference's own: models_dim.py:2072-2085)
+        block = DiMBlockWindow(d_model, mixer_cls, reverse=False, transpose=reverse, skip=skip, shift_window=False, **common)
+    elif block_type == "combined_einfft":
+        raise NotImplementedError("block_type='combined_einfft' is outside the denoiser hot path (published configs use 'combined'; "
+                                  "also available: raw, wave, window, combined_fourier, and 'linear' for every other value)")
+    else:                               # "linear" and every unlisted value (models_dim.py:2129-2141)
+        block = DiMBlock(d_model, mixer_cls, reverse=reverse, transpose=transpose, skip=skip, **common)
     block.layer_idx = layer_idx
     return block
 

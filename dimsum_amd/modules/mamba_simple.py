@@ -141,8 +141,9 @@ class _MambaBase(nn.Module):
 
 
 class Mamba(_MambaBase):
-    def forward(self, hidden_states, inference_params=None, x3=None):
-        """hidden_states: (B, L, D) -> (B, L, D).  x3: the input as a split-bf16 operand image instead (inference, gemm.py)."""
+    def forward(self, hidden_states, cond_emb=None, inference_params=None, x3=None):
+        """hidden_states: (B, L, D) -> (B, L, D).  cond_emb: accepted and unused, as in the reference (mamba_simple.py:162): the DiM blocks
+        call every mixer as mixer(x, c).  x3: the input as a split-bf16 operand image instead (inference, gemm.py)."""
         assert inference_params is None, "autoregressive decode is outside the denoiser hot path"
         return self._mix(hidden_states, None, x3=x3)
 

@@ -421,6 +421,81 @@ def gen_block_1024(ns):
          g_w3_rows16=f(blk.mlp.w3.weight.grad[:16]), g_adaLN_bias=f(blk.adaLN_modulation[1].bias.grad))
 
 
+def _window_order(ns, transpose, reverse, shift, H):
+    """Order seen by the mixer inside DiMBlockWindow.forward (models_dim.py:465-477); the chain of :488-497 must undo it."""
+    from einops import rearrange
+    so = ns.scanning_orders
+    L = H * H
+    hs = so.local_scan(torch.arange(L, dtype=torch.float32).view(1, L, 1), w=4, H=H, W=H, column_first=bool(transpose)).contiguous()
+    if shift:
+        hs = torch.roll(rearrange(hs, "b (h w) c -> b h w c", h=H), shifts=(-1, -1), dims=(1, 2)).reshape(-1, L, 1)
+    if reverse:
+        hs = hs.flip(1)
+    back = hs.flip(1) if reverse else hs
+    if shift:
+        back = torch.roll(rearrange(back, "b (h w) c -> b h w c", h=H), shifts=(1, 1), dims=(1, 2)).reshape(-1, L, 1)
+    back = so.local_reverse(back, w=4, H=H, W=H, column_first=bool(transpose))
+    assert torch.equal(back.view(-1), torch.arange(L, dtype=torch.float32))
+    return hs.view(-1).long().numpy()
+
+
+_LW_FLAGS = dict(norm_epsilon=1e-5, rms_norm=True, residual_in_fp32=True, fused_add_norm=True, layer_idx=1, scan_type="none",
+                 cond_mamba=True, use_gated_mlp=True, block_kwargs={}, block_kwargs2={})
+# (file tag, create_block keywords): DiMBlock over every (reverse, transpose, continuity); the same block with create_block's OWN defaults
+# (LayerNorm, unfused add + norm, the unconditional Mamba); DiMBlockWindow for both values of the flag it is built from (create_block
+# maps its `reverse` to the window block's `transpose`, models_dim.py:2080-2081)
+LW_CASES = ([(f"linear_r{r}t{t}c{c}", dict(_LW_FLAGS, block_type="linear", reverse=bool(r), transpose=bool(t), scanning_continuity=bool(c)))
+             for r in (0, 1) for t in (0, 1) for c in (0, 1)]
+            + [("linear_default", dict(layer_idx=1, reverse=True, transpose=True))]
+            + [(f"window_t{t}", dict(_LW_FLAGS, block_type="window", reverse=bool(t), transpose=False, scanning_continuity=False)) for t in (0, 1)])
+LW_BIG, LW_STEP = 16384, 16      # parameters with more elements than LW_BIG: the gradient rows [::LW_STEP] (keeps every file below 1 MiB)
+
+
+def gen_block_linear_window(ns):
+    """DiMBlock / DiMBlockWindow (dimsum/models_dim.py:223-502 via create_block :2001-2160): forward, residual output, input / c gradients and
+    every parameter gradient at hidden 128, 16x16 tokens, batch 2; and the token orders of both blocks as index vectors."""
+    hidden, B, L = 128, 2, 256
+    x, res, c = T(seeded((B, L, hidden), 101)), T(seeded((B, L, hidden), 102)), T(seeded((B, hidden), 103))
+    gy, gr = T(seeded((B, L, hidden), 104)), T(seeded((B, L, hidden), 105))
+    common = {}
+    for H in (4, 16):
+        for r in (0, 1):
+            for t in (0, 1):
+                for k in (0, 1):
+                    common[f"linear_H{H}_r{r}_t{t}_c{k}"] = _block_order(ns, r, t, k, H).astype(np.int16)
+                    common[f"window_H{H}_t{t}_r{r}_s{k}"] = _window_order(ns, t, r, k, H).astype(np.int16)
+    for tag, kw in LW_CASES:
+        blk = ref_shim.slow_path(ns.models_dim.create_block(hidden, **kw))
+        procedural_fill(blk, seed=9)
+        xi, ri, ci = x.clone().requires_grad_(), res.clone().requires_grad_(), c.clone().requires_grad_()
+        y, ro = blk(xi, ri, ci)
+        ((y * gy).sum() + (ro * gr).sum()).backward()
+        assert torch.equal(ro, common.setdefault("res_out", ro.detach()))      # x + residual whatever the block: stored once
+        arrs = dict(y=y, dx=xi.grad, dres=ri.grad, dc=ci.grad, keys=np.array(sorted(blk.state_dict().keys())))
+        for k, v in blk.named_parameters():
+            if v.grad is not None:
+                arrs[("g16_" if v.numel() > LW_BIG else "g_") + k] = v.grad[::LW_STEP] if v.numel() > LW_BIG else v.grad
+        save("block_" + tag, f"{type(blk).__name__}.forward + every gradient (dimsum/models_dim.py:223-502) via create_block({kw}), hidden 128, "
+             f"procedural weights seed 9; inputs = seeded(101..105); g16_*: rows [::{LW_STEP}] of the gradient", **arrs)
+    save("block_linear_window", "token orders seen by the mixer in DiMBlock.forward (dimsum/models_dim.py:322-333) and DiMBlockWindow.forward "
+         "(:465-477) as index vectors; res_out shared by the block_linear_* / block_window_* fixtures", **common)
+
+
+def gen_model_tiny_linear_window(ns):
+    """model_tiny with block_type linear / window: forward, dx and the state_dict key list"""
+    for bt in ("linear", "window"):
+        m = _mk_model(ns, "tiny", block_type=bt)
+        procedural_fill(m, seed=3)
+        x = T(seeded((2, 4, 32, 32), 61)).requires_grad_()
+        t, y = T(seeded((2,), 62, kind="uniform")), torch.tensor([3, 7])
+        out = m(x, t, y)
+        g = T(seeded(tuple(out.shape), 63))
+        out.backward(g)
+        save("model_tiny_" + bt, f"DiM.forward (dimsum/models_dim.py:1796-1884), depth 4 hidden 64, published flags (scripts/train.sh) with "
+             f"block_type={bt!r}, procedural weights seed 3", x=x, t=t, y=y, out=out, dout=g, dx=x.grad,
+             n_keys=np.array(len(m.state_dict())), keys=np.array(sorted(m.state_dict().keys())))
+
+
 def _mk_model(ns, name, **over):
     md = ns.models_dim
     kw = dict(img_resolution=32, in_channels=4, label_dropout=0.15, num_classes=1000, learn_sigma=False,
@@ -641,6 +716,7 @@ def main():
         "XL2zigzag": lambda: gen_models(ns, {"model_XL2_512_zigma8"}),
         "transport": lambda: gen_transport(ns), "block1024": lambda: gen_block_1024(ns),
         "transport_blur": lambda: gen_transport_blur(ns),
+        "block_linear_window": lambda: gen_block_linear_window(ns), "tiny_linear_window": lambda: gen_model_tiny_linear_window(ns),
     }
     for k, fn in steps.items():
         if args.only is None or k in args.only:
