@@ -95,6 +95,29 @@ class FmLossParams(_Sized):
                 + [(n, vp) for n in ("out", "tgt", "w", "c", "loss", "gloss", "dout")] + [("reserved2", i64 * 2)])
 
 
+class PosRopeParams(_Sized):
+    """dimsum_pos_rope_params_t: y = x cos + rotate_half(x) sin over channel pairs, or (inverse) the transpose of that map"""
+    _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "tokens", "channels", "inverse", "reserved")]
+                + [(n, i64) for n in ("x_batch_stride", "x_token_stride", "y_batch_stride", "y_token_stride")]
+                + [(n, vp) for n in ("x", "sin", "cos", "y")] + [("reserved2", i64 * 2)])
+
+
+class PosCpeParams(_Sized):
+    """dimsum_pos_cpe_params_t: depthwise 3x3 conv on the token grid + x, LayerNorm, affine, modulate"""
+    _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "grid", "channels")] + [("eps", f32), ("reserved", i32)]
+                + [(n, i64) for n in ("x_batch_stride", "x_token_stride", "y_batch_stride", "y_token_stride", "mod_batch_stride")]
+                + [(n, vp) for n in ("x", "weight", "conv_bias", "gamma", "beta", "shift", "scale", "y", "mean", "rstd", "v")]
+                + [("reserved2", i64 * 2)])
+
+
+class PosCpeBwdParams(_Sized):
+    """dimsum_pos_cpe_bwd_params_t"""
+    _fields_ = ([("struct_size", u32), ("reserved", u32), ("fwd", PosCpeParams)]
+                + [(n, i64) for n in ("dy_batch_stride", "dy_token_stride", "dmod_batch_stride")]
+                + [(n, vp) for n in ("dy", "dv", "dx", "dweight", "dconv_bias", "dgamma", "dbeta", "dshift", "dscale")]
+                + [("reserved2", i64 * 2)])
+
+
 class ConvParams(_Sized):
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "dim", "seqlen", "width", "silu_activation", "dtype", "reserved")]
                 + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "weight_c_stride", "weight_width_stride",
@@ -182,6 +205,7 @@ EXPORTS = (
     "dimsum_ssm_scan_bidir_fwd", "dimsum_ssm_scan_bidir_bwd", "dimsum_ssm_scan_bidir_fwd_variant",
     "dimsum_optim_grad_sumsq", "dimsum_optim_adamw_ema_step", "dimsum_optim_write_ptrs",
     "dimsum_fm_plan", "dimsum_fm_loss_fwd", "dimsum_fm_loss_bwd",
+    "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
@@ -200,7 +224,8 @@ _SIGNATURES = (
         ("dimsum_causal_conv1d_fwd", ConvParams), ("dimsum_causal_conv1d_bwd", ConvBwdParams), ("dimsum_norm_fwd", NormParams),
         ("dimsum_norm_bwd", NormBwdParams), ("dimsum_token_transform", TtParams), ("dimsum_xattn_fusion_fwd", XattnParams),
         ("dimsum_xattn_fusion_bwd", XattnBwdParams), ("dimsum_gemm_nt", GemmParams), ("dimsum_fm_plan", FmPlanParams),
-        ("dimsum_fm_loss_fwd", FmLossParams), ("dimsum_fm_loss_bwd", FmLossParams))]
+        ("dimsum_fm_loss_fwd", FmLossParams), ("dimsum_fm_loss_bwd", FmLossParams), ("dimsum_pos_rope", PosRopeParams),
+        ("dimsum_pos_cpe_fwd", PosCpeParams), ("dimsum_pos_cpe_bwd", PosCpeBwdParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

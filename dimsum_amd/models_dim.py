@@ -9,8 +9,10 @@ What is structured differently (results equal to fp32 roundoff; pinned by tests/
     construction into one gather table; the pre-mixer path  modulate(P(T(x)))  and the post-mixer path
     x + T^-1(P^-1(gate * mixer(...)))  are each ONE fused pass (ops/token_ops.py), T = Haar / DCT / identity;
   * the GatedMLP activation is a fused epilogue; RMSNorm is the HIP fused add+norm, not Triton.
-Out of scope (constructor raises): block type combined_einfft, MoE, rope/cpe positional encodings and
-`enable_fourier_layers` -- unused by every published config.
+  * pe_type "rope" / "cpe": the embed pass is one HIP launch (ops/pos_embed.py: the rotation of the channel pairs; the depthwise 3x3 conv on
+    the token grid + LayerNorm + adaLN modulation), "ape" the add it always was.
+Out of scope (constructor raises): block type combined_einfft, MoE and `enable_fourier_layers` -- unused by every published config
+(SURVEY.md section 2.1).
 """
 import math
 import os
@@ -29,6 +31,8 @@ from .mlp import GatedMLP
 from .modules.mamba_simple import CondMamba, Mamba
 from .ops import token_ops
 from .ops.layernorm import RMSNorm, layer_norm_fn, rms_norm_fn
+from .pe.cpe import AdaInPosCNN
+from .pe.my_rotary import apply_rotary, get_2d_sincos_rotary_embed
 from .wavelet_layer import DWT_2D, IDWT_2D
 
 
@@ -768,8 +772,8 @@ class DiM(nn.Module):
                  learnable_pe=False, skip=False, drop_path=0.0, use_final_norm=False, use_attn_every_k_layers=-1,
                  use_gated_mlp=True, use_independent_attn=False):
         super().__init__()
-        if pe_type != "ape":
-            raise NotImplementedError("only the absolute positional embedding of the published configs is implemented")
+        if pe_type not in ("ape", "rope", "cpe"):
+            raise ValueError(f"pe_type must be 'ape', 'rope' or 'cpe' (got {pe_type!r})")
         if enable_fourier_layers:
             raise NotImplementedError("enable_fourier_layers is broken in the reference (models_dim.py:1702) and unused")
         self.depth = int(depth * 3) if block_type == "raw" else depth
@@ -788,6 +792,12 @@ class DiM(nn.Module):
         self.y_embedder = LabelEmbedder(num_classes, hidden_size, label_dropout)
         num_patches = self.x_embedder.num_patches
         self.pos_embed = nn.Parameter(torch.zeros(1, num_patches, hidden_size), requires_grad=learnable_pe)
+        if pe_type == "rope":       # (models_dim.py:1627-1630; plain attributes there, buffers outside the state_dict here: they follow .to())
+            sin, cos = get_2d_sincos_rotary_embed(hidden_size, int(num_patches ** 0.5))
+            self.register_buffer("emb_sin", torch.from_numpy(sin).to(dtype=torch.float32), persistent=False)
+            self.register_buffer("emb_cos", torch.from_numpy(cos).to(dtype=torch.float32), persistent=False)
+        elif pe_type == "cpe":
+            self.pos_cnn = AdaInPosCNN(hidden_size, hidden_size)
         dpr = [x.item() for x in torch.linspace(0, drop_path, self.depth, device="cpu")]
         inter_dpr = [0.0] + dpr
         self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
@@ -865,7 +875,13 @@ class DiM(nn.Module):
             gemm._tls.cond = None
 
     def _forward_blocks(self, x, c, inference_params):
-        x = self.x_embedder(x) + self.pos_embed
+        if self.pe_type == "ape":
+            x = self.x_embedder(x) + self.pos_embed
+        elif self.pe_type == "rope":        # (pos_embed stays an unused parameter, as in the reference: models_dim.py:1815-1818)
+            x = apply_rotary(self.x_embedder(x), self.emb_sin, self.emb_cos)
+        else:
+            g = int(self.x_embedder.num_patches ** 0.5)
+            x = self.pos_cnn(self.x_embedder(x), c, H=g, W=g)
         residual = None
         for idx, block in enumerate(self.blocks):
             x, residual = block(x, residual, c, inference_params=inference_params)

@@ -1465,3 +1465,113 @@ def fm_loss_bwd(gloss, out, tgt, w=None, c=None, sign=-1):
     with torch.cuda.device(out.device):
         _lib.check(_lib.load().dimsum_fm_loss_bwd(P, _stream(out)), "dimsum_fm_loss_bwd")
     return dout
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the rope and cpe positional encodings of the embed pass (dimsum_pos_*; dimsum_amd/ops/pos_embed.py is the user)
+# ---------------------------------------------------------------------------------------------------------------------
+CPE_MAX_CHANNELS = 2048       # one lane per 4 channels, workgroups of up to 512 lanes
+
+
+def _pos_tokens(what, x):
+    """x as the (B, L, C) float32 tensor the positional passes read: channels contiguous, 16-byte aligned rows"""
+    _check(x.dim() == 3 and x.dtype == torch.float32, f"{what}: x is a float32 (B, L, C) tensor")
+    B, L, C = x.shape
+    _check(B > 0 and L > 0, f"{what}: empty tensors are not supported")
+    _check(C >= 4 and C % 4 == 0, f"{what}: the channel count must be a multiple of 4 (got {C})")
+    _gpu(x)
+    if x.stride(2) != 1 or x.stride(0) % 4 or x.stride(1) % 4 or x.stride(1) < C or x.data_ptr() % 16:
+        x = x.contiguous()
+    return x
+
+
+def _square_grid(what, L, grid):
+    _check(grid >= 1 and grid * grid == L, f"{what}: the tokens must form a square grid (L = {L}, grid = {grid}); other grids are out of scope")
+
+
+def pos_rope(x, sin, cos, inverse=False):
+    """-> y (B, L, C): x cos + rotate_half(x) sin, rotate_half(x)[2i] = -x[2i+1], rotate_half(x)[2i+1] = x[2i], in ONE launch. sin, cos: (L, C)
+    float32 tables. inverse: the transpose of that map -- the backward of the forward, and for rotary tables (equal within a channel pair,
+    sin^2 + cos^2 = 1) its inverse."""
+    x = _pos_tokens("pos_rope", x)
+    B, L, C = x.shape
+    _gpu(sin, cos)
+    for t in (sin, cos):
+        _check(t.dtype == torch.float32 and tuple(t.shape) == (L, C) and t.is_contiguous() and t.data_ptr() % 16 == 0,
+               f"pos_rope: sin and cos are contiguous float32 (L, C) = ({L}, {C}) tables")
+    y = torch.empty((B, L, C), dtype=torch.float32, device=x.device)
+    P = _lib.PosRopeParams()
+    P.batch, P.tokens, P.channels, P.inverse = B, L, C, int(bool(inverse))
+    P.x_batch_stride, P.x_token_stride, P.y_batch_stride, P.y_token_stride = x.stride(0), x.stride(1), L * C, C
+    P.x, P.sin, P.cos, P.y = x.data_ptr(), sin.data_ptr(), cos.data_ptr(), y.data_ptr()
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dimsum_pos_rope(P, _stream(x)), "dimsum_pos_rope")
+    return y
+
+
+def _pos_cpe_params(what, x, weight, bias, gamma, beta, shift, scale, grid, eps):
+    """-> (x as read, the dimsum_pos_cpe_params_t with everything but the outputs, the tensors it points to)"""
+    x = _pos_tokens(what, x)
+    B, L, C = x.shape
+    _square_grid(what, L, grid)
+    _check(C <= CPE_MAX_CHANNELS, f"{what}: at most {CPE_MAX_CHANNELS} channels (got {C})")
+    _gpu(weight, bias, gamma, beta, shift, scale)
+    _check(weight.numel() == 9 * C and tuple(weight.shape[-2:]) == (3, 3), f"{what}: weight is the (C, 1, 3, 3) kernel of a depthwise 3x3 convolution")
+    for t in (bias, gamma, beta):
+        _check(tuple(t.shape) == (C,), f"{what}: the convolution's bias and the LayerNorm's weight and bias are (C,) tensors")
+    weight, bias, gamma, beta = (t.detach().float().contiguous() for t in (weight, bias, gamma, beta))
+    for t in (shift, scale):
+        _check(tuple(t.shape) == (B, C) and t.dtype == torch.float32, f"{what}: shift and scale are float32 (B, C) tensors")
+    if not (shift.stride(1) == 1 and scale.stride(1) == 1 and (B == 1 or shift.stride(0) == scale.stride(0)) and shift.stride(0) % 4 == 0
+            and shift.data_ptr() % 16 == 0 and scale.data_ptr() % 16 == 0):
+        shift, scale = shift.contiguous(), scale.contiguous()
+    P = _lib.PosCpeParams()
+    P.batch, P.grid, P.channels, P.eps = B, grid, C, eps
+    P.x_batch_stride, P.x_token_stride, P.mod_batch_stride = x.stride(0), x.stride(1), shift.stride(0) if B > 1 else C
+    P.x, P.weight, P.conv_bias, P.gamma, P.beta, P.shift, P.scale = (t.data_ptr() for t in (x, weight, bias, gamma, beta, shift, scale))
+    return x, P, (x, weight, bias, gamma, beta, shift, scale)
+
+
+def pos_cpe_fwd(x, weight, bias, gamma, beta, shift, scale, grid, eps=1e-5, need_stats=False, need_v=False):
+    """-> (y, mean, rstd, v): v = x + bias + depthwise 3x3 conv(x) on the (grid, grid) token grid (zero padding 1, token l = h * grid + w),
+    y = (LayerNorm(v) gamma + beta) (1 + scale[b]) + shift[b], in ONE launch. x: (B, grid^2, C); weight (C, 1, 3, 3); bias, gamma, beta (C,);
+    shift, scale (B, C) (the two halves of an adaLN head's output are read in place). need_stats: mean, rstd (B * L,) for the backward, else None.
+    need_v (tests): v itself, else None -- the backward rebuilds it from x."""
+    x, P, keep = _pos_cpe_params("pos_cpe_fwd", x, weight, bias, gamma, beta, shift, scale, grid, eps)
+    B, L, C = x.shape
+    y = torch.empty((B, L, C), dtype=torch.float32, device=x.device)
+    mean, rstd = (torch.empty(B * L, dtype=torch.float32, device=x.device) for _ in range(2)) if need_stats else (None, None)
+    v = torch.empty_like(y) if need_v else None
+    P.y_batch_stride, P.y_token_stride = L * C, C
+    P.y, P.mean, P.rstd, P.v = y.data_ptr(), _ptr(mean), _ptr(rstd), _ptr(v)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dimsum_pos_cpe_fwd(P, _stream(x)), "dimsum_pos_cpe_fwd")
+    return y, mean, rstd, v
+
+
+def pos_cpe_bwd(dy, x, weight, bias, gamma, beta, shift, scale, mean, rstd, grid, eps=1e-5):
+    """-> (dx, dweight, dbias, dgamma, dbeta, dmod) of pos_cpe_fwd in TWO launches: the row pass (v again from x, the modulation and LayerNorm
+    backward, every parameter gradient) and dx = dv + conv^T(dv). dweight has weight's shape; dmod (B, 2 C) = [dshift | dscale], the gradient of
+    the adaLN head's output. Every parameter gradient is a tensor of its own (fp32, accumulated by atomic adds of per-workgroup sums)."""
+    x, P0, keep = _pos_cpe_params("pos_cpe_bwd", x, weight, bias, gamma, beta, shift, scale, grid, eps)
+    B, L, C = x.shape
+    dy = _pos_tokens("pos_cpe_bwd", dy)
+    _check(dy.shape == x.shape, "pos_cpe_bwd: dy has the shape of x")
+    _gpu(mean, rstd)
+    for t in (mean, rstd):
+        _check(t.dtype == torch.float32 and t.numel() == B * L and t.is_contiguous(), "pos_cpe_bwd: mean and rstd are the forward's float32 (B * L,) tensors")
+    dev = x.device
+    dv, dx = torch.empty((B, L, C), dtype=torch.float32, device=dev), torch.empty((B, L, C), dtype=torch.float32, device=dev)
+    dweight = torch.zeros(weight.shape, dtype=torch.float32, device=dev)
+    dbias, dgamma, dbeta = (torch.zeros(C, dtype=torch.float32, device=dev) for _ in range(3))
+    dmod = torch.zeros((B, 2 * C), dtype=torch.float32, device=dev)
+    P = _lib.PosCpeBwdParams()
+    P.fwd = P0
+    P.fwd.mean, P.fwd.rstd = mean.data_ptr(), rstd.data_ptr()
+    P.dy_batch_stride, P.dy_token_stride, P.dmod_batch_stride = dy.stride(0), dy.stride(1), 2 * C
+    P.dy, P.dv, P.dx = dy.data_ptr(), dv.data_ptr(), dx.data_ptr()
+    P.dweight, P.dconv_bias, P.dgamma, P.dbeta = dweight.data_ptr(), dbias.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
+    P.dshift, P.dscale = dmod.data_ptr(), dmod.data_ptr() + 4 * C
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().dimsum_pos_cpe_bwd(P, _stream(x)), "dimsum_pos_cpe_bwd")
+    return dx, dweight, dbias, dgamma, dbeta, dmod

@@ -96,6 +96,7 @@ def main(argv=None):
     ap.add_argument("--model", default="DiM-L/2")
     ap.add_argument("--image-size", type=int, default=256)
     ap.add_argument("--num-classes", type=int, default=1000)
+    ap.add_argument("--pe-type", default="ape", choices=["ape", "rope", "cpe"], help="positional encoding the checkpoint was trained with")
     ap.add_argument("--per-proc-batch-size", type=int, default=128)
     ap.add_argument("--num-fid-samples", type=int, default=1024)
     ap.add_argument("--num-sampling-steps", type=int, default=250)
@@ -119,7 +120,7 @@ def main(argv=None):
     rank, world = dist.get_rank(), dist.get_world_size()
     device = local_rank
     torch.manual_seed(args.global_seed * world + rank)
-    model = create_model(published_config(args.model, args.image_size, args.num_classes)).to(device).eval()
+    model = create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type)).to(device).eval()
     if args.ckpt:
         load_denoiser_weights(model, args.ckpt)                  # EMA preferred (download.py:26-27)
     r = args.image_size // 8

@@ -83,6 +83,10 @@ def build_training(model, device, lr=1e-4, world_size=1, device_ids=None, fused_
     ema = copy.deepcopy(model).to(device)
     requires_grad(ema, False)
     if world_size > 1:
+        if getattr(model, "pe_type", "ape") != "ape":
+            # rope / cpe never read pos_embed (models_dim.py:1815-1822): it gets no gradient, and DDP without find_unused_parameters waits
+            # for one in the next iteration. Frozen, it is what it is on one GPU: a parameter the optimizer never moves.
+            model.pos_embed.requires_grad_(False)
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=device_ids, find_unused_parameters=False)
     fused = os.environ.get("DIMSUM_FUSED_ADAMW", "1") != "0" and torch.device(device).type == "cuda"
     if fused_step:
@@ -102,6 +106,7 @@ def build_parser():
     ap.add_argument("--image-size", type=int, default=256)
     ap.add_argument("--num-classes", type=int, default=1000)
     ap.add_argument("--global-batch-size", type=int, default=704)       # scripts/train.sh:86-112
+    ap.add_argument("--pe-type", default="ape", choices=["ape", "rope", "cpe"], help="positional encoding of the embed pass (train.py --pe-type)")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--max-grad-norm", type=float, default=2.0)
     ap.add_argument("--path-type", default="GVP")
@@ -140,7 +145,7 @@ def main(argv=None):
     assert args.global_batch_size % world == 0, "Batch size must be divisible by world size."
     device = local_rank
     torch.manual_seed(args.global_seed * world + rank)
-    model = create_model(published_config(args.model, args.image_size, args.num_classes)).to(device)
+    model = create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type)).to(device)
     model, ema, opt = build_training(model, device, args.lr, world, [device])
     transport = transport_from_args(args)
     init_epoch, train_steps = (load_checkpoint(args.resume, model, ema, opt, lr=args.lr) if args.resume else (0, 0))

@@ -9,6 +9,7 @@
  *   dimsum_ssm_scan_bidir_fwd / _bwd <- the two selective_scan_cuda calls (+ flips) of BiMambaInnerFn  mamba/mamba_ssm/ops/selective_scan_interface.py:1010-1388
  *   dimsum_optim_grad_sumsq / dimsum_optim_adamw_ema_step <- clip_grad_norm_ + AdamW.step + update_ema   dimsum/train.py:55-64,317-321
  *   dimsum_fm_plan / dimsum_fm_loss_fwd / _bwd <- ICPlan.plan + DCTBlur, the loss of Transport.training_losses   dimsum/transport/path.py:159-259, transport.py:127-164
+ *   dimsum_pos_rope / dimsum_pos_cpe_fwd / _bwd <- apply_rotary, AdaInPosCNN.forward (+ autograd)   dimsum/pe/my_rotary.py:63-72, pe/cpe.py:37-48
  *   dimsum_causal_conv1d_fwd   <- causal_conv1d_cuda.causal_conv1d_fwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:221-336
  *   dimsum_causal_conv1d_bwd   <- causal_conv1d_cuda.causal_conv1d_bwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:338-509
  *   dimsum_norm_fwd / _bwd     <- _layer_norm_fwd / _layer_norm_bwd (Triton)     mamba/mamba_ssm/ops/triton/layernorm.py:120-364
@@ -332,6 +333,69 @@ typedef struct {
 int dimsum_fm_plan(const dimsum_fm_plan_params_t *p, void *stream);
 int dimsum_fm_loss_fwd(const dimsum_fm_loss_params_t *p, void *stream);
 int dimsum_fm_loss_bwd(const dimsum_fm_loss_params_t *p, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Positional encodings of the embed pass: DiM(pe_type = "rope" | "cpe") (<- apply_rotary  dimsum/pe/my_rotary.py:63-72 and AdaInPosCNN.forward
+ * dimsum/pe/cpe.py:37-48, as called at dimsum/models_dim.py:1815-1822). Added under ABI 18 (new symbols only). fp32 only; activations are
+ * (batch, tokens, channels) with the channels contiguous, channels % 4 == 0, every pointer and stride 16-byte aligned; no allocation, no
+ * synchronisation; the caller allocates every output, including the zero-filled accumulators of the backward.
+ *
+ * dimsum_pos_rope, one launch. sin, cos: (tokens, channels) contiguous.
+ *   inverse == 0:  y[2i] = x[2i] cos[2i] - x[2i+1] sin[2i]         y[2i+1] = x[2i+1] cos[2i+1] + x[2i] sin[2i+1]      (x cos + rotate_half(x) sin)
+ *   inverse != 0:  y[2i] = x[2i] cos[2i] + x[2i+1] sin[2i+1]       y[2i+1] = x[2i+1] cos[2i+1] - x[2i] sin[2i]        (its transpose)
+ *   The transpose is the backward of the forward for ANY tables; for the rotary tables (sin and cos equal within a channel pair,
+ *   sin^2 + cos^2 = 1) the map is a rotation, so the transpose is also its inverse: the flag is the sign of sin.
+ *
+ * dimsum_pos_cpe_fwd, one launch. tokens == grid * grid, token l = h * grid + w. weight: (channels, 3, 3) contiguous (nn.Conv2d's
+ * (channels, 1, 3, 3) of a depthwise convolution), conv_bias, gamma, beta: (channels); shift, scale: (batch, channels) rows mod_batch_stride apart.
+ *   v[b, l, c] = x[b, l, c] + conv_bias[c] + sum_{i, j} weight[c, i, j] x[b, (h + i - 1) grid + (w + j - 1), c]      (neighbours off the grid: 0)
+ *   y = ((v - mean) rstd gamma + beta) (1 + scale[b]) + shift[b],   mean, rstd over the channels of the row, rstd = 1 / sqrt(var + eps)
+ *   mean, rstd: (batch * tokens) each, written when non-NULL. v is written only when asked for (tests): the backward rebuilds it from x.
+ *   A workgroup owns consecutive token rows of one batch element, a lane 4 adjacent channels: channels <= 2048.
+ *
+ * dimsum_pos_cpe_bwd, two launches. Reads x, dy, mean, rstd and the parameters of the forward.
+ *   launch 1, per row: v again, the LayerNorm / modulation backward -> dv (written to dv, a (batch, tokens, channels) contiguous scratch tensor);
+ *             dgamma, dbeta, dconv_bias (channels), dweight (channels, 3, 3), dshift, dscale (batch, channels; rows dmod_batch_stride apart) as
+ *             fp32 atomic adds of per-workgroup partial sums into the caller's ZERO-FILLED tensors.
+ *   launch 2, per row: dx = dv + conv^T(dv)     (dx contiguous)
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_pos_rope_params_t) */
+    int32_t batch, tokens, channels;
+    int32_t inverse;           /* 0: the forward, != 0: its transpose (= the backward, = the inverse rotation) */
+    int32_t reserved;          /* 0 */
+    int64_t x_batch_stride, x_token_stride, y_batch_stride, y_token_stride;   /* elements */
+    const void *x, *sin, *cos;
+    void *y;
+    int64_t reserved2[2];      /* 0 */
+} dimsum_pos_rope_params_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_pos_cpe_params_t) */
+    int32_t batch, grid, channels;   /* tokens = grid * grid */
+    float eps;
+    int32_t reserved;          /* 0 */
+    int64_t x_batch_stride, x_token_stride, y_batch_stride, y_token_stride, mod_batch_stride;   /* elements */
+    const void *x, *weight, *conv_bias, *gamma, *beta, *shift, *scale;
+    void *y, *mean, *rstd;     /* mean, rstd: forward written (optional), backward read */
+    void *v;                   /* forward, optional (tests): v as a (batch, tokens, channels) contiguous tensor; the backward never reads it */
+    int64_t reserved2[2];      /* 0 */
+} dimsum_pos_cpe_params_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_pos_cpe_bwd_params_t) */
+    uint32_t reserved;         /* 0 */
+    dimsum_pos_cpe_params_t fwd;     /* the forward's operands; y is not read */
+    int64_t dy_batch_stride, dy_token_stride, dmod_batch_stride;    /* elements */
+    const void *dy;
+    void *dv, *dx;             /* (batch, tokens, channels) contiguous: scratch of launch 1, the result */
+    void *dweight, *dconv_bias, *dgamma, *dbeta, *dshift, *dscale;   /* zero-filled by the caller */
+    int64_t reserved2[2];      /* 0 */
+} dimsum_pos_cpe_bwd_params_t;
+
+int dimsum_pos_rope(const dimsum_pos_rope_params_t *p, void *stream);
+int dimsum_pos_cpe_fwd(const dimsum_pos_cpe_params_t *p, void *stream);
+int dimsum_pos_cpe_bwd(const dimsum_pos_cpe_bwd_params_t *p, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Causal depthwise conv1d, width 2..4, optional bias, optional SiLU.  Mirrors ConvParamsBase / ConvParamsBwd

@@ -496,6 +496,63 @@ def gen_model_tiny_linear_window(ns):
              n_keys=np.array(len(m.state_dict())), keys=np.array(sorted(m.state_dict().keys())))
 
 
+PE_ROPE_CASES = ((64, 4), (128, 16))                  # (hidden, grid) of the stored rotary tables
+PE_CPE_CASES = ((2, 4, 64), (2, 6, 136))              # (B, grid, C) of the stored AdaInPosCNN cases
+PE_BIG = 4096                                         # parameters with more elements: the gradient rows [::LW_STEP] (the adaLN head's weight)
+
+
+def gen_pe(ns):
+    """The rope and cpe positional encodings: get_2d_sincos_rotary_embed / apply_rotary (dimsum/pe/my_rotary.py:11-72), AdaInPosCNN
+    (dimsum/pe/cpe.py:29-48) forward + every gradient, and DiM(pe_type="rope" | "cpe") on the tiny recipe (models_dim.py:1627-1633,1812-1822).
+    The reference's block loop tests `self.pe_tpe == "cpe"` (models_dim.py:1843), an attribute that does not exist: the cpe model gets the
+    instance attribute `pe_tpe = pe_type` (all three branches of that loop make the same call); no reference file is touched."""
+    rot, cpe = sys.modules["pe.my_rotary"], sys.modules["pe.cpe"]
+    arrs = {}
+    for i, (H, grid) in enumerate(PE_ROPE_CASES):
+        sin, cos = rot.get_2d_sincos_rotary_embed(H, grid)
+        sin, cos = T(sin).to(torch.float32), T(cos).to(torch.float32)         # as DiM.__init__ stores them (models_dim.py:1629-1630)
+        x = T(seeded((2, grid * grid, H), 111 + i)).requires_grad_()
+        y = rot.apply_rotary(x, sin, cos)
+        g = T(seeded(tuple(y.shape), 113 + i))
+        y.backward(g)
+        tag = f"H{H}_g{grid}"
+        arrs.update({tag + "_sin": sin, tag + "_cos": cos})
+        if i == 0:          # (y and dx of the larger case alone would be 512 KiB)
+            arrs.update({tag + "_y": y, tag + "_dx": x.grad})
+    save("pe_rope", "get_2d_sincos_rotary_embed as float32 (dimsum/pe/my_rotary.py:11-60) for (hidden, grid) in "
+         f"{PE_ROPE_CASES}; apply_rotary fwd / autograd (:63-72) for the first, batch 2, x = seeded(111), dy = seeded(113)", **arrs)
+    arrs = {}
+    for i, (B, grid, C) in enumerate(PE_CPE_CASES):
+        m = cpe.AdaInPosCNN(C, C)
+        procedural_fill(m, seed=13)
+        x = T(seeded((B, grid * grid, C), 121 + i)).requires_grad_()
+        c = T(seeded((B, C), 123 + i)).requires_grad_()
+        y = m(x, c, H=grid, W=grid)
+        g = T(seeded(tuple(y.shape), 125 + i))
+        y.backward(g)
+        tag = f"B{B}_g{grid}_C{C}"
+        arrs.update({tag + "_y": y, tag + "_dx": x.grad, tag + "_dc": c.grad})
+        for k, v in m.named_parameters():
+            big = v.numel() > PE_BIG
+            arrs[f"{tag}_{'g16' if big else 'g'}_{k}"] = v.grad[::LW_STEP] if big else v.grad
+    save("pe_cpe", "AdaInPosCNN.forward + every gradient (dimsum/pe/cpe.py:29-48) for (B, grid, C) in "
+         f"{PE_CPE_CASES}, procedural weights seed 13; x = seeded(121 + i), c = seeded(123 + i), dy = seeded(125 + i); "
+         f"g16_*: rows [::{LW_STEP}] of the gradient (parameters above {PE_BIG} elements)", **arrs)
+    for pe in ("rope", "cpe"):
+        m = _mk_model(ns, "tiny", pe_type=pe)
+        if pe == "cpe":
+            m.pe_tpe = m.pe_type
+        procedural_fill(m, seed=3)
+        x = T(seeded((2, 4, 32, 32), 61)).requires_grad_()
+        t, y = T(seeded((2,), 62, kind="uniform")), torch.tensor([3, 7])
+        out = m(x, t, y)
+        g = T(seeded(tuple(out.shape), 63))
+        out.backward(g)
+        save("model_tiny_" + pe, f"DiM.forward (dimsum/models_dim.py:1796-1884), depth 4 hidden 64, published flags (scripts/train.sh) with "
+             f"pe_type={pe!r}" + (" and the instance attribute pe_tpe = pe_type (:1843)" if pe == "cpe" else "") + ", procedural weights seed 3",
+             x=x, t=t, y=y, out=out, dout=g, dx=x.grad, n_keys=np.array(len(m.state_dict())), keys=np.array(sorted(m.state_dict().keys())))
+
+
 def _mk_model(ns, name, **over):
     md = ns.models_dim
     kw = dict(img_resolution=32, in_channels=4, label_dropout=0.15, num_classes=1000, learn_sigma=False,
@@ -717,6 +774,7 @@ def main():
         "transport": lambda: gen_transport(ns), "block1024": lambda: gen_block_1024(ns),
         "transport_blur": lambda: gen_transport_blur(ns),
         "block_linear_window": lambda: gen_block_linear_window(ns), "tiny_linear_window": lambda: gen_model_tiny_linear_window(ns),
+        "pe": lambda: gen_pe(ns),
     }
     for k, fn in steps.items():
         if args.only is None or k in args.only:
