@@ -838,6 +838,30 @@ def rows_f16s_multi(jobs, n_slots=None):
     return images, scal
 
 
+def _gemm_operands_ok(a, b):
+    """what every GEMM entry point asks of its two operands: 2-D, the same 16-bit type, rows of unit column stride whose stride is a multiple of
+    8 elements, 16-byte aligned"""
+    return (a.is_cuda and a.dim() == 2 and b.dim() == 2 and a.dtype == b.dtype and a.dtype in (torch.bfloat16, torch.float16)
+            and a.stride(1) == 1 and b.stride(1) == 1 and a.stride(0) % 8 == 0 and b.stride(0) % 8 == 0
+            and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0)
+
+
+def _fill_gemm(G, a, b, out, m, n, k, epilogue=_lib.GEMM_EPI_F32, out_scale=1.0, bias=None, scales=(None, None), events=None, **ext):
+    """the shape, operand type, epilogue, leading dimensions and pointers of one launch into G (out: rows of the last dimension); scales = the
+    (a, b) inverse scales, events = (start, stop) raw hipEvent_t handles, ext = further fields of dimsum_gemm_ext_t -> the attached GemmExt"""
+    G.m, G.n, G.k = m, n, k
+    G.operand_dtype, G.epilogue, G.out_scale = _DT[a.dtype], epilogue, float(out_scale)
+    G.lda, G.ldb, G.ldc = a.stride(0), b.stride(0), out.stride(-2)
+    G.a_ptr, G.b_ptr, G.bias_ptr, G.c_ptr = _ptr(a), _ptr(b), _ptr(bias), _ptr(out)
+    G.a_inv_scale_ptr, G.b_inv_scale_ptr = _ptr(scales[0]), _ptr(scales[1])
+    X = _lib.attach_ext(G, _lib.GemmExt)            # fused-epilogue operands, image read modes, timing, tuning (dimsum_gemm_ext_t)
+    if events is not None:
+        X.timing_start_event, X.timing_stop_event = events
+    for field, value in ext.items():
+        setattr(X, field, value)
+    return X
+
+
 def gemm_nt_supported(a, b, gated=False, pair=False, pair_b=False):
     """shapes the hand-written NT GEMM takes (csrc/gemm_nt_kernel.hpp): 256-row panels of 16-bit rows, 64-deep K tiles.
     pair / pair_b (or a PairImage operand): that operand is the [hi | lo] pair (rows of 2C) of a split-bf16 image over K = 3C (C % 64 == 0)"""
@@ -845,7 +869,7 @@ def gemm_nt_supported(a, b, gated=False, pair=False, pair_b=False):
         a, pair = a.data, True
     if isinstance(b, PairImage):
         b, pair_b = b.data, True
-    if not (a.is_cuda and a.dim() == 2 and b.dim() == 2 and a.dtype == b.dtype and a.dtype in (torch.bfloat16, torch.float16)):
+    if not _gemm_operands_ok(a, b):
         return False
     M, K = a.shape
     N, Kb = b.shape
@@ -858,22 +882,20 @@ def gemm_nt_supported(a, b, gated=False, pair=False, pair_b=False):
             return False
         Kb = Kb // 2 * 3
     return (Kb == K and M > 0 and M % 256 == 0 and K % 64 == 0 and K >= 128 and N % (16 if gated else 4) == 0
-            and a.stride(1) == 1 and b.stride(1) == 1 and a.stride(0) % 8 == 0 and b.stride(0) % 8 == 0
-            and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0 and 512 * max(a.stride(0), b.stride(0)) < 2 ** 31)
+            and 512 * max(a.stride(0), b.stride(0)) < 2 ** 31)
 
 
 def gemm_tn_supported(a, b):
     """shapes the TN variant takes (csrc/gemm_nt_kernel.hpp, kVarTN): a (R, P), b (R, Q) 16-bit rows over the reduction index R, whole
     256 x 256 output tiles, 64-row reduction tiles"""
-    if not (a.is_cuda and a.dim() == 2 and b.dim() == 2 and a.dtype == b.dtype and a.dtype in (torch.bfloat16, torch.float16)):
+    if not _gemm_operands_ok(a, b):
         return False
     R, P = a.shape
     Q = b.shape[1]
     # (Q % 256 != 0: b must be a column slice of rows ZERO-PADDED to whole 256-column tiles -- its row stride says so; gemm.weight_f16s_t pads)
     q_ok = Q % 256 == 0 or (Q % 4 == 0 and b.stride(0) >= (Q + 255) // 256 * 256)
     return (b.shape[0] == R and R % 64 == 0 and R >= 128 and P % 256 == 0 and q_ok and P > 0 and Q > 0
-            and a.stride(1) == 1 and b.stride(1) == 1 and a.stride(0) % 8 == 0 and b.stride(0) % 8 == 0
-            and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0 and 128 * max(a.stride(0), b.stride(0)) + 512 < 2 ** 31)
+            and 128 * max(a.stride(0), b.stride(0)) + 512 < 2 ** 31)
 
 
 def gemm_tn_splits(R, P, Q, second_round=True):
@@ -889,6 +911,15 @@ def gemm_tn_splits(R, P, Q, second_round=True):
     if second_round and tiles >= 64 and tiles * s < 512 and ok(2 * s):       # ... and a second round where the partial results are few (tools/scratch/tn_perf.py)
         s *= 2
     return s
+
+
+def _rowfac_splits(R, P, Q):
+    """reduction ranges of a launch with per-reduction-row factors (gemm_tn with row_scales / row_invs, gemm_nn): one round of workgroups, then
+    doubled while a range exceeds 16384 rows (the factors of one range live in 32 KB of LDS)"""
+    splits = gemm_tn_splits(R, P, Q, second_round=False)
+    while R // splits > 16384 and R % (2 * splits * 64) == 0:
+        splits *= 2
+    return splits
 
 
 def gemm_tn_pairs(a, b, splits=None):
@@ -908,12 +939,7 @@ def gemm_tn_pairs(a, b, splits=None):
     _check(M % (splits * 64) == 0 and M // splits >= 128, "gemm_tn_pairs: splits must cut M into ranges of whole 64-row tiles")
     out = torch.empty((3 * splits, P, Q), device=ad.device, dtype=torch.float32)
     G = _lib.GemmParams()
-    G.m, G.n, G.k = P, Q, M
-    G.operand_dtype, G.epilogue, G.out_scale = _DT[ad.dtype], _lib.GEMM_EPI_F32, 1.0
-    G.lda, G.ldb, G.ldc = ad.stride(0), bd.stride(0), Q
-    G.a_ptr, G.b_ptr, G.c_ptr = _ptr(ad), _ptr(bd), _ptr(out)
-    X = _lib.attach_ext(G, _lib.GemmExt)
-    X.tn_pair_a_cols, X.tn_pair_b_cols = P, Q
+    _fill_gemm(G, ad, bd, out, P, Q, M, tn_pair_a_cols=P, tn_pair_b_cols=Q)
     with torch.cuda.device(ad.device):
         _lib.check(_lib.load().dimsum_gemm_tn(G, 3 * splits, P * Q, _stream(ad)), "gemm_tn_pairs")
     return out.sum(0)
@@ -985,36 +1011,23 @@ def gemm_tn(a, b, splits=None, events=None, alias_rows=0, scales=None, row_scale
         _check(gemm_tn_supported(a, b), "gemm_tn: unsupported operands (R % 64, P % 256, Q % 256, 16-bit rows, 16-byte aligned)")
         R, P = a.shape
     Q = b.shape[1]
+    rowfac = row_scales is not None or row_invs is not None
     if splits is None:
-        rowfac = row_scales is not None or row_invs is not None
-        splits = gemm_tn_splits(R, P, Q, second_round=not rowfac)
-        while rowfac and R // splits > 16384 and R % (2 * splits * 64) == 0:          # (the factors of one range live in 32 KB of LDS)
-            splits *= 2
-    if row_scales is not None or row_invs is not None:
+        splits = _rowfac_splits(R, P, Q) if rowfac else gemm_tn_splits(R, P, Q)
+    if rowfac:
         _check(R // splits <= 16384, "gemm_tn: row factors need ranges of at most 16384 reduction rows")
     _check(splits >= 1 and R % (splits * 64) == 0 and R // splits >= 128, "gemm_tn: splits must cut R into ranges of whole 64-row tiles (>= 2)")
     out = torch.empty((splits, P, Q), device=a.device, dtype=torch.float32)
-    G = _lib.GemmParams()
-    G.m, G.n, G.k = P, Q, R
-    G.operand_dtype = _DT[a.dtype]
-    G.epilogue = _lib.GEMM_EPI_F32
-    G.out_scale = 1.0
-    G.lda, G.ldb, G.ldc = a.stride(0), b.stride(0), Q
-    G.a_ptr, G.b_ptr, G.c_ptr = _ptr(a), _ptr(b), _ptr(out)
-    X = _lib.attach_ext(G, _lib.GemmExt)
-    X.a_alias_rows = alias_rows
-    if scales is not None:
-        G.b_inv_scale_ptr = _ptr(scales[1])
-        if blocks is not None:
-            X.a_block_inv_ptr, X.a_block_inv_ld = _ptr(blocks), blocks.stride(0)
-        else:
-            G.a_inv_scale_ptr = _ptr(scales[0])
+    ext = dict(a_alias_rows=alias_rows)
+    if blocks is not None:
+        ext.update(a_block_inv_ptr=_ptr(blocks), a_block_inv_ld=blocks.stride(0))
+        scales = (None, scales[1])
     if row_scales is not None:
-        X.k_scale_ptr, X.c_scale_ptr = _ptr(row_scales[0]), _ptr(row_scales[1])
+        ext.update(k_scale_ptr=_ptr(row_scales[0]), c_scale_ptr=_ptr(row_scales[1]))
     if row_invs is not None:
-        X.k_inv_a_ptr, X.k_inv_b_ptr = _ptr(row_invs[0]), _ptr(row_invs[1])
-    if events is not None:
-        X.timing_start_event, X.timing_stop_event = events
+        ext.update(k_inv_a_ptr=_ptr(row_invs[0]), k_inv_b_ptr=_ptr(row_invs[1]))
+    G = _lib.GemmParams()
+    _fill_gemm(G, a, b, out, P, Q, R, scales=scales or (None, None), events=events, **ext)
     with torch.cuda.device(a.device):
         _lib.check(_lib.load().dimsum_gemm_tn(G, splits, P * Q, _stream(a)), "gemm_tn")
     return out[0] if splits == 1 else out.sum(0)
@@ -1038,12 +1051,11 @@ def gemm_kernel_log():
 def gemm_nn_supported(a, b):
     """shapes dimsum_gemm_nn takes: a (P, R) float16 rows contiguous along the reduction, b (R, Q) float16 rows over it; whole 256 x 256 output
     tiles, whole 64-row reduction tiles"""
-    if not (a.is_cuda and a.dim() == 2 and b.dim() == 2 and a.dtype == torch.float16 and b.dtype == torch.float16):
+    if not (_gemm_operands_ok(a, b) and a.dtype == torch.float16):
         return False
     P, R = a.shape
     Q = b.shape[1]
-    return (b.shape[0] == R and R % 64 == 0 and R >= 128 and P % 256 == 0 and Q % 256 == 0 and a.stride(1) == 1 and b.stride(1) == 1
-            and a.stride(0) % 8 == 0 and b.stride(0) % 8 == 0 and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0
+    return (b.shape[0] == R and R % 64 == 0 and R >= 128 and P % 256 == 0 and Q % 256 == 0
             and 256 * a.stride(0) * 2 < 2 ** 31 and 64 * b.stride(0) * 2 + 512 < 2 ** 31)
 
 
@@ -1058,23 +1070,13 @@ def gemm_nn(a, a_inv, b, b_inv, splits=None):
     P, R = a.shape
     Q = b.shape[1]
     if splits is None:
-        splits = gemm_tn_splits(R, P, Q, second_round=False)
-        while R // splits > 16384 and R % (2 * splits * 64) == 0:
-            splits *= 2
+        splits = _rowfac_splits(R, P, Q)
     _check(splits >= 1 and R % (splits * 64) == 0 and 128 <= R // splits <= 16384, "gemm_nn: splits must cut R into ranges of 2 .. 256 whole 64-row tiles")
     in_kernel = os.environ.get("DIMSUM_ROW_FACTORS_KERNEL", "0") != "1" and b_inv.is_contiguous()       # factors formed inside the GEMM (no launch in front)
     fac, top = (None, None) if in_kernel else row_factors(b_inv)
     out = torch.empty((splits, P, Q), device=a.device, dtype=torch.float32)
     G = _lib.GemmParams()
-    G.m, G.n, G.k = P, Q, R
-    G.operand_dtype, G.epilogue, G.out_scale = _DT[a.dtype], _lib.GEMM_EPI_F32, 1.0
-    G.lda, G.ldb, G.ldc = a.stride(0), b.stride(0), Q
-    G.a_ptr, G.b_ptr, G.c_ptr, G.a_inv_scale_ptr = _ptr(a), _ptr(b), _ptr(out), _ptr(a_inv)
-    X = _lib.attach_ext(G, _lib.GemmExt)
-    if in_kernel:
-        X.k_inv_a_ptr = _ptr(b_inv)
-    else:
-        X.k_scale_ptr, X.c_scale_ptr = _ptr(fac), _ptr(top)
+    _fill_gemm(G, a, b, out, P, Q, R, scales=(a_inv, None), **(dict(k_inv_a_ptr=_ptr(b_inv)) if in_kernel else dict(k_scale_ptr=_ptr(fac), c_scale_ptr=_ptr(top))))
     with torch.cuda.device(a.device):
         _lib.check(_lib.load().dimsum_gemm_nn(G, splits, P * Q, _stream(a)), "gemm_nn")
     return out[0] if splits == 1 else out.sum(0)
@@ -1107,21 +1109,15 @@ def gemm_nt(a, b, bias=None, epilogue="f32", out=None, out_scale=1.0, events=Non
     _check(gemm_nt_supported(a, b, gated, pair=pair_in, pair_b=pair_b), "gemm_nt: unsupported operands (M % 256, K % 64, K >= 128, 16-bit K-contiguous rows, 16-byte aligned)")
     M, K = a.shape[0], (a.shape[1] if pair_b else b.shape[1])
     N = b.shape[0]
-    P = _lib.GemmParams()
-    X = _lib.attach_ext(P, _lib.GemmExt)            # fused-epilogue operands, image read modes, timing, tuning (dimsum_gemm_ext_t)
-    P.m, P.n, P.k = M, N, K
+    ext = {}                                        # fields of dimsum_gemm_ext_t beyond the zeros
     if pair_in:
-        X.a_alias_rows = K // 3
-        X.a_alias_weight_order = int(bool(weight_order))       # the pair read as [hi | lo | hi] (a gradient image x a left-order weight image)
+        ext.update(a_alias_rows=K // 3, a_alias_weight_order=int(bool(weight_order)))      # weight order: the pair read as [hi | lo | hi] (a gradient image x a left-order weight image)
     if pair_b:
-        X.b_alias_rows = K // 3
-    P.operand_dtype = _DT[a.dtype]
-    P.out_scale = float(out_scale)
-    P.lda, P.ldb = a.stride(0), b.stride(0)
+        ext.update(b_alias_rows=K // 3)
     if bias is not None:
         _check(bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N, "gemm_nt: bias must be (N,) float32")
     if epilogue == "f32":
-        P.epilogue = _lib.GEMM_EPI_F32 if bias is None else _lib.GEMM_EPI_F32_BIAS
+        epi = _lib.GEMM_EPI_F32 if bias is None else _lib.GEMM_EPI_F32_BIAS
         if out is None:
             out = torch.empty((M, N), device=a.device, dtype=torch.float32)
         _check(out.dtype == torch.float32 and out.shape == (M, N) and out.stride(1) == 1, "gemm_nt: out must be (M, N) float32 rows")
@@ -1134,71 +1130,66 @@ def gemm_nt(a, b, bias=None, epilogue="f32", out=None, out_scale=1.0, events=Non
                    and cw.shape[0] <= M and 2 <= cw.shape[1] <= 4 and 256 % seq == 0 and seq % 4 == 0 and N % seq == 0
                    and (cb is None or (cb.dtype == torch.float32 and cb.is_contiguous() and cb.numel() == cw.shape[0])),
                    "gemm_nt: conv = (weight (rows % 256 == 0, width 2..4) f32, bias or None, seq with 256 % seq == 0)")
-            P.epilogue = _lib.GEMM_EPI_F32_CONV
-            X.conv_weight_ptr, X.conv_bias_ptr = _ptr(cw), _ptr(cb)
-            X.conv_rows, X.conv_width, X.conv_seq, X.conv_weight_ld = cw.shape[0], cw.shape[1], seq, cw.stride(0)
+            epi = _lib.GEMM_EPI_F32_CONV
+            ext.update(conv_weight_ptr=_ptr(cw), conv_bias_ptr=_ptr(cb), conv_rows=cw.shape[0], conv_width=cw.shape[1], conv_seq=seq, conv_weight_ld=cw.stride(0))
         if residual is not None:
             _gpu(residual, gate)
             _check(residual.dtype == torch.float32 and residual.shape == (M, N) and residual.stride(1) == 1, "gemm_nt: residual must be (M, N) float32 rows")
-            P.epilogue = _lib.GEMM_EPI_F32_GATE_RESIDUAL
-            X.residual_ptr, X.residual_ld = _ptr(residual), residual.stride(0)
+            epi = _lib.GEMM_EPI_F32_GATE_RESIDUAL
+            ext.update(residual_ptr=_ptr(residual), residual_ld=residual.stride(0))
             if gate is not None:
                 _check(rows_per_batch and rows_per_batch % 256 == 0 and M % rows_per_batch == 0 and gate.dtype == torch.float32
                        and gate.shape == (M // rows_per_batch, N) and gate.stride(1) == 1, "gemm_nt: gate must be (M / rows_per_batch, N) float32, rows_per_batch % 256 == 0")
-                X.gate_ptr, X.gate_ld, X.rows_per_batch = _ptr(gate), gate.stride(0), rows_per_batch
+                ext.update(gate_ptr=_ptr(gate), gate_ld=gate.stride(0), rows_per_batch=rows_per_batch)
     elif epilogue == "gated_split3":
-        P.epilogue = _lib.GEMM_EPI_GATED_GELU_SPLIT3
+        epi = _lib.GEMM_EPI_GATED_GELU_SPLIT3
         pieces = 2 if pair_out else 3
-        X.c_image_pieces = pieces
+        ext.update(c_image_pieces=pieces)
         if out is None:
             out = torch.empty((M, pieces * (N // 2)), device=a.device, dtype=torch.bfloat16)
         _check(out.dtype == torch.bfloat16 and out.shape == (M, pieces * (N // 2)) and out.stride(1) == 1, "gemm_nt: out must be (M, 3F) / (M, 2F) bfloat16 rows")
     elif epilogue == "f16_qkv":
         # the qkv Linear of the attention fusion as scaled fp16 (include/dimsum_hip.h, DIMSUM_GEMM_EPI_F16_QKV): q_cols = the width of q
-        P.epilogue = _lib.GEMM_EPI_F16_QKV
+        epi = _lib.GEMM_EPI_F16_QKV
         _check(scales is not None and gate_bound is not None and rows_per_batch and rows_per_batch % 256 == 0 and M % rows_per_batch == 0
                and q_cols and q_cols % 16 == 0 and N % 8 == 0, "gemm_nt: f16_qkv needs scales, gate_bound = {wl1, bmax}, rows_per_batch % 256 == 0, q_cols % 16 == 0")
-        X.rows_per_batch, X.qkv_q_cols = rows_per_batch, q_cols
+        ext.update(rows_per_batch=rows_per_batch, qkv_q_cols=q_cols)
         if out is None:
             out = torch.empty((M, N), device=a.device, dtype=torch.float16)
         _check(out.dtype == torch.float16 and out.shape == (M, N) and out.stride(1) == 1, "gemm_nt: out must be (M, N) float16 rows")
     elif epilogue == "gated_f16":
-        P.epilogue = _lib.GEMM_EPI_GATED_GELU_F16
+        epi = _lib.GEMM_EPI_GATED_GELU_F16
         if out is None:
             out = torch.empty((M, N // 2), device=a.device, dtype=torch.float16)
         _check(out.dtype == torch.float16 and out.shape == (M, N // 2) and out.stride(1) == 1, "gemm_nt: out must be (M, F) float16 rows")
     else:
         raise ValueError(f"gemm_nt: unknown epilogue {epilogue!r}")
-    P.ldc = out.stride(0)
     h_inv = None
     if scales is not None:
         sa, sb = scales
         _gpu(sa, sb)
         _check(sa.dtype == torch.float32 and sb.dtype == torch.float32 and sa.is_contiguous() and sb.is_contiguous() and sa.numel() == M
                and sb.numel() == N, "gemm_nt: scales must be contiguous float32 (M,) and (N,)")
-        P.a_inv_scale_ptr, P.b_inv_scale_ptr = _ptr(sa), _ptr(sb)
         if gate_bound is not None:
             _gpu(gate_bound)
             _check(epilogue in ("gated_f16", "f16_qkv") and gate_bound.dtype == torch.float32 and gate_bound.numel() == 2 and gate_bound.is_contiguous(),
                    "gemm_nt: gate_bound is a 2-element float32 tensor for the gated_f16 / f16_qkv epilogues")
-            X.gate_bound_ptr = _ptr(gate_bound)
+            ext.update(gate_bound_ptr=_ptr(gate_bound))
             if epilogue == "gated_f16":
                 h_inv = torch.empty((M,), device=a.device, dtype=torch.float32)
-                X.h_inv_scale_ptr = _ptr(h_inv)
-    P.a_ptr, P.b_ptr, P.bias_ptr, P.c_ptr = _ptr(a), _ptr(b), _ptr(bias), _ptr(out)
+                ext.update(h_inv_scale_ptr=_ptr(h_inv))
     x12 = None
     if keep_x12:
         _check((epilogue == "gated_split3" and a.dtype == torch.bfloat16 and scales is None) or (epilogue == "gated_f16" and a.dtype == torch.float16 and h_inv is not None),
                "gemm_nt: keep_x12 goes with the gated_split3 epilogue over bf16 images or the gated_f16 epilogue over scaled-fp16 operands with gate_bound")
         x12 = torch.empty((M, N), device=a.device, dtype=torch.float32)
-        X.x12_ptr, X.x12_ld = _ptr(x12), N
-    if events is not None:
-        X.timing_start_event, X.timing_stop_event = events
+        ext.update(x12_ptr=_ptr(x12), x12_ld=N)
     if tune is not None:
-        X.tune_variant, X.tune_group_m = tune[:2]
-        X.tune_reserved = tune[2] if len(tune) > 2 else 0
+        ext.update(tune_variant=tune[0], tune_group_m=tune[1], tune_reserved=tune[2] if len(tune) > 2 else 0)
     elif epilogue == "gated_f16" and os.environ.get("DIMSUM_GEMM_PERSIST", "1") == "0":
-        X.tune_variant = 513          # A / B switch: the gated GEMM one workgroup per tile instead of the persistent stream (csrc/gemm_nt_kernel.hpp, kVarPersist)
+        ext.update(tune_variant=513)  # A / B switch: the gated GEMM one workgroup per tile instead of the persistent stream (csrc/gemm_nt_kernel.hpp, kVarPersist)
+    P = _lib.GemmParams()
+    _fill_gemm(P, a, b, out, M, N, K, epi, out_scale, bias=bias, scales=scales or (None, None), events=events, **ext)
     with torch.cuda.device(a.device):
         if _gemm_kernel_log is not None:            # tests / bench: which kernel family the library picks for this call
             _gemm_kernel_log.append((epilogue if conv is None else "f32_conv", int(_lib.load().dimsum_gemm_nt_kernel_for(P))))

@@ -463,3 +463,63 @@ def test_persistent_stream_is_the_one_tile_per_workgroup_kernel_bit_for_bit(M, F
         res, gate = _rnd((M, N), torch.float32, 4), _rnd((M // 256, N), torch.float32, 5)
         kw = dict(bias=b12, residual=res, gate=gate, rows_per_batch=256, scales=(x.inv, w16.inv))
         assert torch.equal(native.gemm_nt(x.data, w16.data, tune=(514, 0, 0), **kw), native.gemm_nt(x.data, w16.data, tune=(513, 0, 0), **kw))
+
+
+def _timed_cases():
+    """name -> (call(events) -> tensors of the result, kernel family of a gemm_nt call or None): the smallest shape each family takes"""
+    from dimsum_amd import native
+
+    def nt_f16():       # f32 epilogue over scaled fp16 operands, K = 128: the 128-row tiles
+        a, b = native.rows_f16s(_rnd((256, 128), torch.float32, 1)), native.rows_f16s(_rnd((256, 128), torch.float32, 2))
+        return lambda ev: [native.gemm_nt(a.data, b.data, scales=(a.inv, b.inv), events=ev)]
+
+    def nt_bf16():      # the same shape in bf16: the 256-row tiles
+        a, b = _rnd((256, 128), torch.bfloat16, 1), _rnd((256, 128), torch.bfloat16, 2)
+        return lambda ev: [native.gemm_nt(a, b, events=ev)]
+
+    def nt_gated():     # 17 x 16 = 272 tiles > 256 workgroups, 4 K tiles: the persistent stream
+        M, F, K = 4352, 2048, 256
+        x = native.rows_f16s(_rnd((M, K), torch.float32, 1))
+        w, l1 = native.rows_f16s(_rnd((2 * F, K), torch.float32, 2, scale=K ** -0.5), want_l1=True)
+        bias = _rnd((2 * F,), torch.float32, 3, scale=0.1)
+        bound = torch.cat([l1 * (1.0 + 2.0 ** -10), bias.abs().max().reshape(1)]).contiguous()
+
+        def call(ev):
+            h = native.gemm_nt(x.data, w.data, bias=bias, epilogue="gated_f16", scales=(x.inv, w.inv), gate_bound=bound, events=ev)
+            return [h.data.view(torch.int16), h.inv]
+        return call
+
+    def tn_f16():       # row factors formed in the kernel: gemm_tn_rowfac_kernel
+        a, b = native.rows_f16s(_rnd((128, 256), torch.float32, 1)), native.rows_f16s(_rnd((128, 256), torch.float32, 2))
+        return lambda ev: [native.gemm_tn(a.data, b.data, row_invs=(a.inv, b.inv), events=ev)]
+
+    def tn_bf16():
+        a, b = _rnd((128, 256), torch.bfloat16, 1), _rnd((128, 256), torch.bfloat16, 2)
+        return lambda ev: [native.gemm_tn(a, b, events=ev)]
+
+    return {"nt_f16_m128": (nt_f16, 1), "nt_bf16_m256": (nt_bf16, 0), "nt_gated_f16_persistent": (nt_gated, 2), "tn_f16_row_invs": (tn_f16, None), "tn_bf16": (tn_bf16, None)}
+
+
+@pytest.mark.parametrize("case", ["nt_f16_m128", "nt_bf16_m256", "nt_gated_f16_persistent", "tn_f16_row_invs", "tn_bf16"])
+def test_timed_launch_is_the_plain_launch(case):
+    """events=(start, stop): the same kernel goes out through hipExtLaunchKernelGGL with the two events at its dispatch boundaries (bench.py's
+    per-kernel times) -- the same bits as the plain launch, and a positive time between the events; one case per kernel family of the
+    host layer's one launcher (the gemm_nt families asserted through gemm_kernel_log)"""
+    from dimsum_amd import _lib, native
+    make, family = _timed_cases()[case]
+    call = make()
+    lib = _lib.load()
+    start, stop = lib.dimsum_event_create(), lib.dimsum_event_create()
+    try:
+        with native.gemm_kernel_log() as log:
+            plain = call(None)
+            timed = call((start, stop))
+        torch.cuda.synchronize()
+        if family is not None:
+            assert [k for _, k in log] == [family, family], log
+        for p, t in zip(plain, timed):
+            assert torch.equal(p, t)
+        assert float(lib.dimsum_event_elapsed_ms(start, stop)) > 0
+    finally:
+        lib.dimsum_event_destroy(start)
+        lib.dimsum_event_destroy(stop)
