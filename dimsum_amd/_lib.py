@@ -118,6 +118,25 @@ class PosCpeBwdParams(_Sized):
                 + [("reserved2", i64 * 2)])
 
 
+class EinfftDftParams(_Sized):
+    """dimsum_einfft_dft_params_t: the real tensor x and the two planes of its spectrum (dft reads x, idft_real writes it)"""
+    _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "tokens", "channels")] + [("x_batch_stride", i64), ("x_token_stride", i64)]
+                + [(n, vp) for n in ("x", "re", "im")] + [("reserved2", i64 * 2)])
+
+
+class EinfftMlpParams(_Sized):
+    """dimsum_einfft_mlp_params_t: the block-diagonal complex two-layer MLP + softshrink over (rows, channels) plane pairs"""
+    _fields_ = ([("struct_size", u32), ("channels", i32), ("rows", i64), ("lam", f32), ("reserved", i32)]
+                + [(n, vp) for n in ("xr", "xi", "w1", "b1", "w2", "b2", "zr", "zi")] + [("reserved2", i64 * 2)])
+
+
+class EinfftMlpBwdParams(_Sized):
+    """dimsum_einfft_mlp_bwd_params_t"""
+    _fields_ = ([("struct_size", u32), ("reserved", u32), ("fwd", EinfftMlpParams)]
+                + [(n, vp) for n in ("w1t", "w2t", "dzr", "dzi", "dxr", "dxi", "h1r", "h1i", "dz2r", "dz2i", "dp1r", "dp1i")]
+                + [("reserved2", i64 * 2)])
+
+
 class ConvParams(_Sized):
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "dim", "seqlen", "width", "silu_activation", "dtype", "reserved")]
                 + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "weight_c_stride", "weight_width_stride",
@@ -206,6 +225,7 @@ EXPORTS = (
     "dimsum_optim_grad_sumsq", "dimsum_optim_adamw_ema_step", "dimsum_optim_write_ptrs",
     "dimsum_fm_plan", "dimsum_fm_loss_fwd", "dimsum_fm_loss_bwd",
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
+    "dimsum_einfft_dft", "dimsum_einfft_idft_real", "dimsum_einfft_mlp_fwd", "dimsum_einfft_mlp_bwd",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
@@ -225,7 +245,8 @@ _SIGNATURES = (
         ("dimsum_norm_bwd", NormBwdParams), ("dimsum_token_transform", TtParams), ("dimsum_xattn_fusion_fwd", XattnParams),
         ("dimsum_xattn_fusion_bwd", XattnBwdParams), ("dimsum_gemm_nt", GemmParams), ("dimsum_fm_plan", FmPlanParams),
         ("dimsum_fm_loss_fwd", FmLossParams), ("dimsum_fm_loss_bwd", FmLossParams), ("dimsum_pos_rope", PosRopeParams),
-        ("dimsum_pos_cpe_fwd", PosCpeParams), ("dimsum_pos_cpe_bwd", PosCpeBwdParams))]
+        ("dimsum_pos_cpe_fwd", PosCpeParams), ("dimsum_pos_cpe_bwd", PosCpeBwdParams), ("dimsum_einfft_dft", EinfftDftParams),
+        ("dimsum_einfft_idft_real", EinfftDftParams), ("dimsum_einfft_mlp_fwd", EinfftMlpParams), ("dimsum_einfft_mlp_bwd", EinfftMlpBwdParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

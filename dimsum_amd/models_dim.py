@@ -594,6 +594,11 @@ class _ForkHalves(torch.autograd.Function):
 
 
 class _CombinedBase(_BlockBase):
+    _branch_images = True       # the branches can hand their results over as operand images of the qkv Linears (inference under allow_tf32)
+
+    def _freq(self, x2, c, inference_params, kw):
+        return self.freq_mamba(x2, None, c, inference_params, **kw)[0]
+
     def _init_tail(self, dim, norm_cls, drop_path, use_gated_mlp, swap_k_kw):
         self.proj = CrossAttentionFusion(dim, num_heads=8, qkv_bias=True, **swap_k_kw)
         self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
@@ -608,7 +613,7 @@ class _CombinedBase(_BlockBase):
         else:
             x1, x2 = hidden_states.chunk(2, dim=2)
         # inference under allow_tf32: the branches hand their results over as split-bf16 operand images of the qkv Linears
-        img = self.proj.takes_images(hidden_states) and gemm.split3_enabled(x1, self.proj.qkv1.weight)      # False / True / "f16s"
+        img = self._branch_images and self.proj.takes_images(hidden_states) and gemm.split3_enabled(x1, self.proj.qkv1.weight)      # False / True / "f16s"
         kw = {"out_split3": img} if img else {}
         if ((not torch.is_grad_enabled()) and hidden_states.is_cuda and branch_streams_enabled()
                 and not torch.cuda.is_current_stream_capturing()):
@@ -623,13 +628,13 @@ class _CombinedBase(_BlockBase):
                 side = self.__dict__["_side_stream"] = torch.cuda.Stream(device=hidden_states.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                x2, _ = self.freq_mamba(x2, None, c, inference_params, **kw)
+                x2 = self._freq(x2, c, inference_params, kw)
             x1, _ = self.spatial_mamba(x1, None, c, inference_params, **kw)
             cur.wait_stream(side)
             x2.record_stream(cur)       # allocated on the side stream, consumed (and released) on the current one
         else:
             x1, _ = self.spatial_mamba(x1, None, c, inference_params, **kw)
-            x2, _ = self.freq_mamba(x2, None, c, inference_params, **kw)
+            x2 = self._freq(x2, c, inference_params, kw)
         # residual tails as single fused passes; the Linear biases ride along (mlp.py / attention_fusion.py docstrings)
         fast_tail = _fast_tail(self.norm_2, self.mlp, hidden_states)
         # (inference on operand images: "h + proj(..) + b" already in the proj GEMM's epilogue, the norm pass then reads ONE tensor)
@@ -669,6 +674,58 @@ class DiMBlockCombinedFourier(_CombinedBase):
         self.spatial_mamba = DiMBlockRaw(dim // 2, mixer_cls, reverse=reverse, transpose=transpose, **kw)
         self.freq_mamba = DCTBlock(dim // 2, mixer_cls_2, reverse=False, transpose=False, no_ffn=True, dct_size=4, **kw)
         self._init_tail(dim, norm_cls, drop_path, use_gated_mlp, {})
+
+
+class EinFFT(nn.Module):
+    """fft2 over (tokens, 4 channel blocks) -> block-diagonal complex two-layer MLP (ReLU, softshrink 0.01) -> the real part of ifft2
+    (models_dim.py:713-775), as one fused operator (ops/einfft.py: three HIP launches). Parameters and state-dict keys are the reference's."""
+
+    def __init__(self, dim):
+        super().__init__()
+        from . import native
+        if dim % native.EINFFT_CHANNEL_GRANULE or not 0 < dim <= native.EINFFT_MAX_CHANNELS:
+            raise NotImplementedError(f"block_type='combined_einfft': the spectral branch's width must be a multiple of "
+                                      f"{native.EINFFT_CHANNEL_GRANULE}, at most {native.EINFFT_MAX_CHANNELS} (got {dim}: hidden size {2 * dim})")
+        self.hidden_size, self.num_blocks, self.block_size = dim, 4, dim // 4
+        self.sparsity_threshold, self.scale = 0.01, 0.02
+        shape = (2, self.num_blocks, self.block_size)
+        self.complex_weight_1 = nn.Parameter(torch.randn(*shape, self.block_size, dtype=torch.float32) * self.scale)
+        self.complex_weight_2 = nn.Parameter(torch.randn(*shape, self.block_size, dtype=torch.float32) * self.scale)
+        self.complex_bias_1 = nn.Parameter(torch.randn(*shape, dtype=torch.float32) * self.scale)
+        self.complex_bias_2 = nn.Parameter(torch.randn(*shape, dtype=torch.float32) * self.scale)
+
+    def forward(self, x):
+        from .ops.einfft import einfft
+        return einfft(x, self.complex_weight_1, self.complex_bias_1, self.complex_weight_2, self.complex_bias_2, self.sparsity_threshold)
+
+
+def einfft_check_tokens(n_tokens):
+    """the token counts the spectral branch's LDS FFT takes; DiM.__init__ and the block's first forward both ask"""
+    from . import native
+    if not (native.EINFFT_MIN_TOKENS <= n_tokens <= native.EINFFT_MAX_TOKENS and n_tokens & (n_tokens - 1) == 0):
+        raise NotImplementedError(f"block_type='combined_einfft': the token count must be a power of two in [{native.EINFFT_MIN_TOKENS}, "
+                                  f"{native.EINFFT_MAX_TOKENS}] (got {n_tokens})")
+
+
+class DiMBlockCombinedEinFFT(_CombinedBase):
+    """spatial Mamba || EinFFT spectral MLP -> cross-attention fusion -> gated MLP (models_dim.py:1267-1399). The spectral branch takes no
+    conditioning and returns a plain fp32 tensor, so neither branch writes an operand image."""
+    _branch_images = False
+
+    def __init__(self, dim, mixer_cls, norm_cls=nn.LayerNorm, fused_add_norm=False, residual_in_fp32=False, drop_path=0.0,
+                 reverse=False, transpose=False, scanning_continuity=False, use_gated_mlp=True):
+        super().__init__()
+        self.residual_in_fp32, self.fused_add_norm = residual_in_fp32, fused_add_norm
+        self.reverse, self.transpose, self.scanning_continuity = reverse, transpose, scanning_continuity
+        self.norm = norm_cls(dim)
+        kw = dict(norm_cls=nn.Identity, drop_path=0.0, fused_add_norm=False, residual_in_fp32=residual_in_fp32,
+                  scanning_continuity=scanning_continuity, c_dim=dim)
+        self.spatial_mamba = DiMBlockRaw(dim // 2, mixer_cls, reverse=reverse, transpose=transpose, **kw)
+        self.freq_mamba = EinFFT(dim // 2)
+        self._init_tail(dim, norm_cls, drop_path, use_gated_mlp, {})
+
+    def _freq(self, x2, c, inference_params, kw):
+        return self.freq_mamba(x2)
 
 
 class DiTBlock(nn.Module):
@@ -755,8 +812,7 @@ def create_block(d_model, ssm_cfg=None, norm_epsilon=1e-5, drop_path=0.0, rms_no
     elif block_type == "window":        # (the flag mapping is the reference's own: models_dim.py:2072-2085)
         block = DiMBlockWindow(d_model, mixer_cls, reverse=False, transpose=reverse, skip=skip, shift_window=False, **common)
     elif block_type == "combined_einfft":
-        raise NotImplementedError("block_type='combined_einfft' is outside the denoiser hot path (published configs use 'combined'; "
-                                  "also available: raw, wave, window, combined_fourier, and 'linear' for every other value)")
+        block = DiMBlockCombinedEinFFT(d_model, mixer_cls, reverse=reverse, transpose=transpose, use_gated_mlp=use_gated_mlp, **common)
     else:                               # "linear" and every unlisted value (models_dim.py:2129-2141)
         block = DiMBlock(d_model, mixer_cls, reverse=reverse, transpose=transpose, skip=skip, **common)
     block.layer_idx = layer_idx
@@ -802,6 +858,8 @@ class DiM(nn.Module):
         inter_dpr = [0.0] + dpr
         self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
         grid = int(math.sqrt(num_patches))
+        if block_type == "combined_einfft":
+            einfft_check_tokens(num_patches)
 
         def gen_paths(N, st):           # models_dim.py:1640-1658
             kind, n = st.split("_")[0], int(st.split("_")[1])

@@ -1566,3 +1566,121 @@ def pos_cpe_bwd(dy, x, weight, bias, gamma, beta, shift, scale, mean, rstd, grid
     with torch.cuda.device(dev):
         _lib.check(_lib.load().dimsum_pos_cpe_bwd(P, _stream(x)), "dimsum_pos_cpe_bwd")
     return dx, dweight, dbias, dgamma, dbeta, dmod
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the spectral branch of block type "combined_einfft" (dimsum_einfft_*; dimsum_amd/ops/einfft.py is the user)
+# ---------------------------------------------------------------------------------------------------------------------
+EINFFT_MIN_TOKENS, EINFFT_MAX_TOKENS = 16, 1024       # the N-point part is an FFT in LDS
+EINFFT_CHANNEL_GRANULE = 32                           # 4 channel blocks of a multiple of 8 columns
+EINFFT_MAX_CHANNELS = 1024                            # the MLP keeps two (2 bs, 32) operand tiles in LDS: bs <= 256
+
+
+def einfft_check_shape(what, N, C):
+    """the limits of the einfft passes, checked before any launch: N a power of two in [16, 1024], C % 32 == 0, C <= 1024"""
+    _check(EINFFT_MIN_TOKENS <= N <= EINFFT_MAX_TOKENS and N & (N - 1) == 0,
+           f"{what}: the token count must be a power of two in [{EINFFT_MIN_TOKENS}, {EINFFT_MAX_TOKENS}] (got {N})")
+    _check(C >= EINFFT_CHANNEL_GRANULE and C % EINFFT_CHANNEL_GRANULE == 0 and C <= EINFFT_MAX_CHANNELS,
+           f"{what}: the channel count must be a multiple of {EINFFT_CHANNEL_GRANULE}, at most {EINFFT_MAX_CHANNELS} (got {C})")
+
+
+def _einfft_planes(what, B, N, C, *ts):
+    for t in ts:
+        _check(t.dtype == torch.float32 and tuple(t.shape) == (B, N, C) and t.is_contiguous(),
+               f"{what}: the spectrum planes are contiguous float32 (B, N, C) = ({B}, {N}, {C}) tensors")
+    _gpu(*ts)
+
+
+def _einfft_dft_params(x, re, im):
+    B, N, C = x.shape
+    P = _lib.EinfftDftParams()
+    P.batch, P.tokens, P.channels = B, N, C
+    P.x_batch_stride, P.x_token_stride = x.stride(0), x.stride(1)
+    P.x, P.re, P.im = x.data_ptr(), re.data_ptr(), im.data_ptr()
+    return P
+
+
+def _einfft_real(what, x):
+    _check(x.dim() == 3 and x.dtype == torch.float32, f"{what}: x is a float32 (B, N, C) tensor (got {tuple(x.shape)}, {x.dtype})")
+    B, N, C = x.shape
+    _check(B > 0, f"{what}: empty tensors are not supported")
+    einfft_check_shape(what, N, C)
+    _gpu(x)
+    return x.stride(2) == 1 and x.stride(1) >= C and (B == 1 or x.stride(0) >= (N - 1) * x.stride(1) + C)
+
+
+def einfft_dft(x):
+    """-> (re, im), contiguous (B, N, C) each: the ortho-normalised 2-D DFT of the real x over (the N tokens, the 4 channel blocks
+    {j, j + C/4, j + 2 C/4, j + 3 C/4}), in ONE launch. A channel-half view of a wider tensor is read in place."""
+    if not _einfft_real("einfft_dft", x):
+        x = x.contiguous()
+    B, N, C = x.shape
+    re, im = (torch.empty((B, N, C), dtype=torch.float32, device=x.device) for _ in range(2))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dimsum_einfft_dft(_einfft_dft_params(x, re, im), _stream(x)), "dimsum_einfft_dft")
+    return re, im
+
+
+def einfft_idft_real(re, im, out=None):
+    """-> y (B, N, C): the real part of the inverse of einfft_dft (its transpose), in ONE launch. out: written in place when given (any row
+    stride, e.g. a channel-half view)."""
+    _check(re.dim() == 3 and re.dtype == torch.float32, f"einfft_idft_real: re, im are float32 (B, N, C) tensors (got {tuple(re.shape)}, {re.dtype})")
+    B, N, C = re.shape
+    einfft_check_shape("einfft_idft_real", N, C)
+    _einfft_planes("einfft_idft_real", B, N, C, re, im)
+    if out is None:
+        out = torch.empty((B, N, C), dtype=torch.float32, device=re.device)
+    _check(tuple(out.shape) == (B, N, C) and _einfft_real("einfft_idft_real", out), "einfft_idft_real: out is a float32 (B, N, C) tensor with contiguous channels and rows that do not overlap")
+    with torch.cuda.device(re.device):
+        _lib.check(_lib.load().dimsum_einfft_idft_real(_einfft_dft_params(out, re, im), _stream(re)), "dimsum_einfft_idft_real")
+    return out
+
+
+def _einfft_mlp_params(what, re, im, w1, b1, w2, b2, lam):
+    _check(re.dim() == 3 and re.dtype == torch.float32, f"{what}: re, im are float32 (B, N, C) tensors (got {tuple(re.shape)}, {re.dtype})")
+    B, N, C = re.shape
+    _check(C >= EINFFT_CHANNEL_GRANULE and C % EINFFT_CHANNEL_GRANULE == 0 and C <= EINFFT_MAX_CHANNELS,
+           f"{what}: the channel count must be a multiple of {EINFFT_CHANNEL_GRANULE}, at most {EINFFT_MAX_CHANNELS} (got {C})")
+    _check(B * N > 0, f"{what}: empty tensors are not supported")
+    _einfft_planes(what, B, N, C, re, im)
+    bs = C // 4
+    _gpu(w1, b1, w2, b2)
+    for w, b in ((w1, b1), (w2, b2)):
+        _check(w.dtype == torch.float32 and tuple(w.shape) == (2, 4, bs, bs) and b.dtype == torch.float32 and tuple(b.shape) == (2, 4, bs),
+               f"{what}: the weights are float32 (2, 4, {bs}, {bs}) tensors, the biases (2, 4, {bs})")
+    keep = tuple(t.detach().contiguous() for t in (w1, b1, w2, b2))
+    P = _lib.EinfftMlpParams()
+    P.channels, P.rows, P.lam = C, B * N, float(lam)
+    P.xr, P.xi = re.data_ptr(), im.data_ptr()
+    P.w1, P.b1, P.w2, P.b2 = (t.data_ptr() for t in keep)
+    return P, keep
+
+
+def einfft_mlp_fwd(re, im, w1, b1, w2, b2, lam):
+    """-> (zr, zi): per row and channel block the complex two-layer MLP h = relu(x W1 + b1) (both parts), z = softshrink(h W2 + b2, lam) (both
+    parts), in ONE launch; h stays on the chip. re, im: (B, N, C) planes; w: (2, 4, bs, bs) = [re | im][block][in][out]; b: (2, 4, bs)."""
+    P, keep = _einfft_mlp_params("einfft_mlp_fwd", re, im, w1, b1, w2, b2, lam)
+    zr, zi = torch.empty_like(re), torch.empty_like(im)
+    P.zr, P.zi = zr.data_ptr(), zi.data_ptr()
+    with torch.cuda.device(re.device):
+        _lib.check(_lib.load().dimsum_einfft_mlp_fwd(P, _stream(re)), "dimsum_einfft_mlp_fwd")
+    return zr, zi
+
+
+def einfft_mlp_bwd(dzr, dzi, re, im, zr, zi, w1, b1, w2, b2, lam):
+    """-> (dxr, dxi, (h1r, h1i), (dz2r, dz2i), (dp1r, dp1i)) in ONE launch: the gradient of the spectrum planes and the three plane pairs whose
+    products are the parameter gradients (layer 1's output again, the gradient behind the softshrink mask z != 0, the gradient behind the ReLU
+    mask). zr, zi: the forward's output."""
+    P0, keep = _einfft_mlp_params("einfft_mlp_bwd", re, im, w1, b1, w2, b2, lam)
+    B, N, C = re.shape
+    _einfft_planes("einfft_mlp_bwd", B, N, C, dzr, dzi, zr, zi)
+    w1t, w2t = (w.transpose(-1, -2).contiguous() for w in (keep[0], keep[2]))
+    outs = [torch.empty_like(re) for _ in range(8)]
+    P = _lib.EinfftMlpBwdParams()
+    P.fwd = P0
+    P.fwd.zr, P.fwd.zi = zr.data_ptr(), zi.data_ptr()
+    P.w1t, P.w2t, P.dzr, P.dzi = w1t.data_ptr(), w2t.data_ptr(), dzr.data_ptr(), dzi.data_ptr()
+    P.dxr, P.dxi, P.h1r, P.h1i, P.dz2r, P.dz2i, P.dp1r, P.dp1i = (t.data_ptr() for t in outs)
+    with torch.cuda.device(re.device):
+        _lib.check(_lib.load().dimsum_einfft_mlp_bwd(P, _stream(re)), "dimsum_einfft_mlp_bwd")
+    return outs[0], outs[1], (outs[2], outs[3]), (outs[4], outs[5]), (outs[6], outs[7])

@@ -90,13 +90,14 @@ def shard_range(total, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
-def main(argv=None):
-    from .create_model import create_model, published_config
+def build_parser():
+    from .train import BLOCK_TYPES
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="DiM-L/2")
     ap.add_argument("--image-size", type=int, default=256)
     ap.add_argument("--num-classes", type=int, default=1000)
     ap.add_argument("--pe-type", default="ape", choices=["ape", "rope", "cpe"], help="positional encoding the checkpoint was trained with")
+    ap.add_argument("--block-type", default="combined", choices=list(BLOCK_TYPES), help="block type the checkpoint was trained with")
     ap.add_argument("--per-proc-batch-size", type=int, default=128)
     ap.add_argument("--num-fid-samples", type=int, default=1024)
     ap.add_argument("--num-sampling-steps", type=int, default=250)
@@ -109,7 +110,12 @@ def main(argv=None):
     ap.add_argument("--hip-graph", action="store_true", help="replay the denoiser forward from a captured hipGraph (small per-GPU batches)")
     ap.add_argument("--tf32", action=argparse.BooleanOptionalAction, default=True,
                     help="library-GEMM policy of the reference (sample_ddp.py:56,267-272); exact fp32 with --no-tf32")
-    args, _ = ap.parse_known_args(argv)          # unknown flags are ignored like sample_ddp.py:369
+    return ap
+
+
+def main(argv=None):
+    from .create_model import create_model, published_config
+    args, _ = build_parser().parse_known_args(argv)          # unknown flags are ignored like sample_ddp.py:369
     torch.backends.cuda.matmul.allow_tf32 = args.tf32
     torch.backends.cudnn.allow_tf32 = args.tf32
 
@@ -120,7 +126,7 @@ def main(argv=None):
     rank, world = dist.get_rank(), dist.get_world_size()
     device = local_rank
     torch.manual_seed(args.global_seed * world + rank)
-    model = create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type)).to(device).eval()
+    model = create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type, block_type=args.block_type)).to(device).eval()
     if args.ckpt:
         load_denoiser_weights(model, args.ckpt)                  # EMA preferred (download.py:26-27)
     r = args.image_size // 8

@@ -100,6 +100,9 @@ def build_training(model, device, lr=1e-4, world_size=1, device_ids=None, fused_
     return model, ema, opt
 
 
+BLOCK_TYPES = ("raw", "wave", "combined", "combined_fourier", "combined_einfft", "linear", "window")      # train.py --block-type
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="DiM-L/2")
@@ -107,6 +110,7 @@ def build_parser():
     ap.add_argument("--num-classes", type=int, default=1000)
     ap.add_argument("--global-batch-size", type=int, default=704)       # scripts/train.sh:86-112
     ap.add_argument("--pe-type", default="ape", choices=["ape", "rope", "cpe"], help="positional encoding of the embed pass (train.py --pe-type)")
+    ap.add_argument("--block-type", default="combined", choices=list(BLOCK_TYPES), help="block of the denoiser (train.py --block-type)")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--max-grad-norm", type=float, default=2.0)
     ap.add_argument("--path-type", default="GVP")
@@ -145,7 +149,7 @@ def main(argv=None):
     assert args.global_batch_size % world == 0, "Batch size must be divisible by world size."
     device = local_rank
     torch.manual_seed(args.global_seed * world + rank)
-    model = create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type)).to(device)
+    model = create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type, block_type=args.block_type)).to(device)
     model, ema, opt = build_training(model, device, args.lr, world, [device])
     transport = transport_from_args(args)
     init_epoch, train_steps = (load_checkpoint(args.resume, model, ema, opt, lr=args.lr) if args.resume else (0, 0))

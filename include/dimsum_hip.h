@@ -10,6 +10,7 @@
  *   dimsum_optim_grad_sumsq / dimsum_optim_adamw_ema_step <- clip_grad_norm_ + AdamW.step + update_ema   dimsum/train.py:55-64,317-321
  *   dimsum_fm_plan / dimsum_fm_loss_fwd / _bwd <- ICPlan.plan + DCTBlur, the loss of Transport.training_losses   dimsum/transport/path.py:159-259, transport.py:127-164
  *   dimsum_pos_rope / dimsum_pos_cpe_fwd / _bwd <- apply_rotary, AdaInPosCNN.forward (+ autograd)   dimsum/pe/my_rotary.py:63-72, pe/cpe.py:37-48
+ *   dimsum_einfft_dft / _idft_real / _mlp_fwd / _mlp_bwd <- EinFFT.forward (+ autograd)   dimsum/models_dim.py:713-775
  *   dimsum_causal_conv1d_fwd   <- causal_conv1d_cuda.causal_conv1d_fwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:221-336
  *   dimsum_causal_conv1d_bwd   <- causal_conv1d_cuda.causal_conv1d_bwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:338-509
  *   dimsum_norm_fwd / _bwd     <- _layer_norm_fwd / _layer_norm_bwd (Triton)     mamba/mamba_ssm/ops/triton/layernorm.py:120-364
@@ -396,6 +397,63 @@ typedef struct {
 int dimsum_pos_rope(const dimsum_pos_rope_params_t *p, void *stream);
 int dimsum_pos_cpe_fwd(const dimsum_pos_cpe_params_t *p, void *stream);
 int dimsum_pos_cpe_bwd(const dimsum_pos_cpe_bwd_params_t *p, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The spectral branch of block type "combined_einfft" (<- EinFFT.forward  dimsum/models_dim.py:713-775 + autograd). Added under ABI 18 (new
+ * symbols only). fp32 only, fp32 arithmetic; no allocation, no synchronisation. channels = 4 bs, channel c = k bs + j is column j of block k;
+ * channels % 32 == 0 (bs % 8 == 0).
+ *
+ * dimsum_einfft_dft, one launch. x: real (batch, tokens, channels), channels contiguous, rows x_token_stride apart (a channel-half view is
+ * read in place). re, im: the two planes of the spectrum, (batch, tokens, channels) contiguous each:
+ *   (re + i im)[b, m, q bs + j] = (4 tokens)^-1/2 sum_{n, k} x[b, n, k bs + j] exp(-2 pi i (n m / tokens + k q / 4))
+ *   tokens: a power of two in [16, 1024].
+ * dimsum_einfft_idft_real, one launch, the same struct: reads re, im, WRITES x (any row stride >= channels):
+ *   x[b, n, k bs + j] = Re (4 tokens)^-1/2 sum_{m, q} (re + i im)[b, m, q bs + j] exp(+2 pi i (n m / tokens + k q / 4))
+ *   Each pass is the transpose of the other (the transform matrix is symmetric and unitary): the backward of one is the other.
+ *
+ * dimsum_einfft_mlp_fwd, one launch. xr, xi, zr, zi: (rows, channels) contiguous planes. w1, w2: (2, 4, bs, bs) = [re | im][block][in][out],
+ * b1, b2: (2, 4, bs), all contiguous. Per row and block, with W = Wr + i Wi, b = br + i bi:
+ *   h = relu(Re(x W1 + b1)) + i relu(Im(x W1 + b1)),  z = softshrink(Re(h W2 + b2), lambda) + i softshrink(Im(h W2 + b2), lambda)
+ *   h never leaves the chip. bs <= 256.
+ * dimsum_einfft_mlp_bwd, one launch. fwd: the forward's operands AND its output (zr, zi are read: softshrink passes the gradient exactly where
+ * z != 0). w1t, w2t: the weights with the last two axes swapped, contiguous. dzr, dzi: the gradient of z. Written, all (rows, channels) planes:
+ *   h1 = h again;  dz2 = dz where z != 0;  dp1 = (dz2 conj-transpose(W2)) where h > 0;  dx = dp1 conj-transpose(W1)
+ *   The parameter gradients are products of these planes (dW2 = h1^T dz2, dW1 = x^T dp1 per block, in complex arithmetic) and the bias
+ *   gradients their column sums: the caller's library GEMMs.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_einfft_dft_params_t) */
+    int32_t batch, tokens, channels;
+    int64_t x_batch_stride, x_token_stride;   /* elements */
+    void *x;                   /* dft: read; idft_real: written */
+    void *re, *im;             /* dft: written; idft_real: read */
+    int64_t reserved2[2];      /* 0 */
+} dimsum_einfft_dft_params_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_einfft_mlp_params_t) */
+    int32_t channels;
+    int64_t rows;
+    float lam;                 /* softshrink threshold lambda, >= 0 */
+    int32_t reserved;          /* 0 */
+    const void *xr, *xi, *w1, *b1, *w2, *b2;
+    void *zr, *zi;             /* forward: written; backward: read */
+    int64_t reserved2[2];      /* 0 */
+} dimsum_einfft_mlp_params_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_einfft_mlp_bwd_params_t) */
+    uint32_t reserved;         /* 0 */
+    dimsum_einfft_mlp_params_t fwd;
+    const void *w1t, *w2t, *dzr, *dzi;
+    void *dxr, *dxi, *h1r, *h1i, *dz2r, *dz2i, *dp1r, *dp1i;
+    int64_t reserved2[2];      /* 0 */
+} dimsum_einfft_mlp_bwd_params_t;
+
+int dimsum_einfft_dft(const dimsum_einfft_dft_params_t *p, void *stream);
+int dimsum_einfft_idft_real(const dimsum_einfft_dft_params_t *p, void *stream);
+int dimsum_einfft_mlp_fwd(const dimsum_einfft_mlp_params_t *p, void *stream);
+int dimsum_einfft_mlp_bwd(const dimsum_einfft_mlp_bwd_params_t *p, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Causal depthwise conv1d, width 2..4, optional bias, optional SiLU.  Mirrors ConvParamsBase / ConvParamsBwd

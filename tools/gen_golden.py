@@ -553,6 +553,91 @@ def gen_pe(ns):
              x=x, t=t, y=y, out=out, dout=g, dx=x.grad, n_keys=np.array(len(m.state_dict())), keys=np.array(sorted(m.state_dict().keys())))
 
 
+EINFFT_CASES = (("small", (2, 16, 32), "module", 131), ("unit", (2, 64, 192), "unit", 133))      # (tag, (B, N, C), parameter regime, seed)
+
+
+def _einfft_fractions(m, x):
+    """fractions of layer-1 elements with ReLU on and of layer-2 elements outside the shrink zone, per channel block: (4,), (4,)"""
+    with torch.no_grad():
+        B, N, C = x.shape
+        s = torch.fft.fft2(x.view(B, N, 4, C // 4), dim=(1, 2), norm="ortho")
+        mul = m.multiply
+        w1, b1, w2, b2 = m.complex_weight_1, m.complex_bias_1, m.complex_weight_2, m.complex_bias_2
+        pr, pi = mul(s.real, w1[0]) - mul(s.imag, w1[1]) + b1[0], mul(s.real, w1[1]) + mul(s.imag, w1[0]) + b1[1]
+        hr, hi = pr.relu(), pi.relu()
+        qr, qi = mul(hr, w2[0]) - mul(hi, w2[1]) + b2[0], mul(hr, w2[1]) + mul(hi, w2[0]) + b2[1]
+        relu_on = torch.stack((pr > 0, pi > 0)).float().mean(dim=(0, 1, 2, 4))
+        passed = (torch.stack((qr, qi)).abs() > m.sparsity_threshold).float().mean(dim=(0, 1, 2, 4))
+    return relu_on, passed
+
+
+def gen_einfft(ns):
+    """EinFFT.forward + every gradient (dimsum/models_dim.py:713-775) in the module's own 0.02-scale parameter regime and in a unit-gain one
+    (weights randn * bs^-0.5, biases randn * 0.1); one DiMBlockCombinedEinFFT (:1267-1399) at hidden 64 on a 4 x 4 grid; the tiny model with
+    block_type="combined_einfft". Every case records the fractions of ReLU-on and shrink-pass elements and refuses a degenerate one."""
+    md = ns.models_dim
+    arrs = {}
+    for tag, (B, N, C), regime, seed in EINFFT_CASES:
+        torch.manual_seed(seed)
+        m = md.EinFFT(C)
+        if regime == "unit":
+            bs = C // 4
+            with torch.no_grad():
+                for w in (m.complex_weight_1, m.complex_weight_2):
+                    w.copy_(torch.randn_like(w) * bs ** -0.5)
+                for b in (m.complex_bias_1, m.complex_bias_2):
+                    b.copy_(torch.randn_like(b) * 0.1)
+        x = T(seeded((B, N, C), seed + 1)).requires_grad_()
+        y = m(x)
+        g = T(seeded((B, N, C), seed + 2))
+        y.backward(g)
+        relu_on, passed = _einfft_fractions(m, x.detach())
+        for f in (relu_on.mean().item(), passed.mean().item()):
+            assert 0.2 <= f <= 0.995, (tag, f)
+        arrs.update({f"{tag}_x": x, f"{tag}_dy": g, f"{tag}_y": y, f"{tag}_dx": x.grad, f"{tag}_relu_on": relu_on.mean(), f"{tag}_shrink_pass": passed.mean()})
+        for k, v in m.named_parameters():
+            arrs[f"{tag}_{k}"], arrs[f"{tag}_g_{k}"] = v.detach(), v.grad
+    save("einfft", f"EinFFT.forward + every gradient (dimsum/models_dim.py:713-775) for (tag, (B, N, C), regime, seed) in {EINFFT_CASES}: 'module' = the "
+         "constructor's randn * 0.02 parameters, 'unit' = weights randn * bs^-0.5, biases randn * 0.1; x = seeded(seed + 1), dy = seeded(seed + 2); "
+         "relu_on / shrink_pass: the fractions of layer-1 elements with ReLU on and of layer-2 elements outside the shrink zone", **arrs)
+
+    hidden, B, L = 64, 2, 16
+    x, res, c = T(seeded((B, L, hidden), 141)), T(seeded((B, L, hidden), 142)), T(seeded((B, hidden), 143))
+    gy, gr = T(seeded((B, L, hidden), 144)), T(seeded((B, L, hidden), 145))
+    kw = dict(_LW_FLAGS, block_type="combined_einfft", reverse=True, transpose=True, scanning_continuity=False)
+    blk = ref_shim.slow_path(md.create_block(hidden, **kw))
+    procedural_fill(blk, seed=9)
+    xi, ri, ci = x.clone().requires_grad_(), res.clone().requires_grad_(), c.clone().requires_grad_()
+    y, ro = blk(xi, ri, ci)
+    ((y * gy).sum() + (ro * gr).sum()).backward()
+    relu_on, passed = _einfft_fractions(blk.freq_mamba, blk.norm(xi.detach() + ri.detach())[..., hidden // 2:].contiguous())
+    arrs = dict(y=y, res_out=ro, dx=xi.grad, dres=ri.grad, dc=ci.grad, keys=np.array(sorted(blk.state_dict().keys())), relu_on=relu_on, shrink_pass=passed)
+    for k, v in blk.named_parameters():
+        if v.grad is not None:
+            arrs[("g16_" if v.numel() > LW_BIG else "g_") + k] = v.grad[::LW_STEP] if v.numel() > LW_BIG else v.grad
+    save("block_einfft", f"DiMBlockCombinedEinFFT.forward + every gradient (dimsum/models_dim.py:1267-1399) via create_block({kw}), hidden 64, 4 x 4 tokens, "
+         f"procedural weights seed 9; inputs = seeded(141..145); g16_*: rows [::{LW_STEP}] of the gradient", **arrs)
+
+    m = _mk_model(ns, "tiny", block_type="combined_einfft")
+    procedural_fill(m, seed=3)
+    seen = []
+    hooks = [b.freq_mamba.register_forward_pre_hook(lambda mod, inp: seen.append(_einfft_fractions(mod, inp[0].detach().contiguous()))) for b in m.blocks]
+    x = T(seeded((2, 4, 32, 32), 61)).requires_grad_()
+    t, y = T(seeded((2,), 62, kind="uniform")), torch.tensor([3, 7])
+    out = m(x, t, y)
+    for h in hooks:
+        h.remove()
+    g = T(seeded(tuple(out.shape), 63))
+    out.backward(g)
+    passed = torch.stack([p for _, p in seen])            # (layers, 4): the fraction of non-zero Z per layer and channel block
+    assert passed.max().item() >= 0.2, passed
+    save("model_tiny_einfft", "DiM.forward (dimsum/models_dim.py:1796-1884), depth 4 hidden 64, published flags (scripts/train.sh) with "
+         "block_type='combined_einfft', procedural weights seed 3 (complex weights: std 1 / (2 bs)); shrink_pass: the fraction of non-zero Z per "
+         "layer and channel block", x=x, t=t, y=y, out=out, dout=g, dx=x.grad, n_keys=np.array(len(m.state_dict())),
+         keys=np.array(sorted(m.state_dict().keys())), relu_on=torch.stack([r for r, _ in seen]), shrink_pass=passed)
+
+
+
 def _mk_model(ns, name, **over):
     md = ns.models_dim
     kw = dict(img_resolution=32, in_channels=4, label_dropout=0.15, num_classes=1000, learn_sigma=False,
@@ -774,7 +859,7 @@ def main():
         "transport": lambda: gen_transport(ns), "block1024": lambda: gen_block_1024(ns),
         "transport_blur": lambda: gen_transport_blur(ns),
         "block_linear_window": lambda: gen_block_linear_window(ns), "tiny_linear_window": lambda: gen_model_tiny_linear_window(ns),
-        "pe": lambda: gen_pe(ns),
+        "pe": lambda: gen_pe(ns), "einfft": lambda: gen_einfft(ns),
     }
     for k, fn in steps.items():
         if args.only is None or k in args.only:
