@@ -209,12 +209,26 @@ class GemmParams(_Sized):
                 + [("ext", C.POINTER(GemmExt))])
 
 
+class GeluExt(_Sized):
+    """dimsum_gelu_ext_t: the bound-derived row scale of the forward's scaled-fp16 image"""
+    _fields_ = [("struct_size", u32), ("reserved", i32), ("row_inv_ptr", vp), ("bound_ptr", vp)]
+
+
+class GeluParams(_Sized):
+    """dimsum_gelu_params_t: bias + GELU(tanh) of the plain MLP as a row pass, forward and backward"""
+    _fields_ = ([("struct_size", u32), ("out_image", i32), ("rows", i64), ("hidden", i64)]
+                + [(n, vp) for n in ("x_ptr", "bias_ptr", "dh_ptr", "out_ptr", "inv_scale_ptr", "dbias_ptr")] + [("ext", C.POINTER(GeluExt))])
+
+
+GELU_OUT_F32, GELU_OUT_SPLIT3, GELU_OUT_PAIR, GELU_OUT_F16S = 0, 1, 2, 3
+
+
 class F16sJob(C.Structure):
     _fields_ = ([(n, vp) for n in ("src", "dst", "inv_scale_ptr", "l1max_ptr", "absmax_ptr")]
                 + [(n, i64) for n in ("rows", "cols", "src_row_stride", "dst_row_stride")] + [("l1_factor", f32), ("reserved", i32)])
 
 
-GEMM_EPI_F32, GEMM_EPI_GATED_GELU_SPLIT3, GEMM_EPI_GATED_GELU_F16, GEMM_EPI_F32_BIAS, GEMM_EPI_F32_GATE_RESIDUAL, GEMM_EPI_F16_QKV, GEMM_EPI_F32_CONV = 0, 1, 2, 3, 4, 5, 6
+GEMM_EPI_F32, GEMM_EPI_GATED_GELU_SPLIT3, GEMM_EPI_GATED_GELU_F16, GEMM_EPI_F32_BIAS, GEMM_EPI_F32_GATE_RESIDUAL, GEMM_EPI_F16_QKV, GEMM_EPI_F32_CONV, GEMM_EPI_GELU_F16 = 0, 1, 2, 3, 4, 5, 6, 7
 
 # every symbol include/dimsum_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -229,6 +243,7 @@ EXPORTS = (
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
+    "dimsum_gelu_fwd", "dimsum_gelu_bwd",
     "dimsum_gemm_nt", "dimsum_gemm_nt_kernel_for", "dimsum_gemm_tn", "dimsum_gemm_nn", "dimsum_row_factors", "dimsum_rows_block_f16s", "dimsum_rows_f16s", "dimsum_rows_f16s_multi",
 )
 
@@ -246,7 +261,8 @@ _SIGNATURES = (
         ("dimsum_xattn_fusion_bwd", XattnBwdParams), ("dimsum_gemm_nt", GemmParams), ("dimsum_fm_plan", FmPlanParams),
         ("dimsum_fm_loss_fwd", FmLossParams), ("dimsum_fm_loss_bwd", FmLossParams), ("dimsum_pos_rope", PosRopeParams),
         ("dimsum_pos_cpe_fwd", PosCpeParams), ("dimsum_pos_cpe_bwd", PosCpeBwdParams), ("dimsum_einfft_dft", EinfftDftParams),
-        ("dimsum_einfft_idft_real", EinfftDftParams), ("dimsum_einfft_mlp_fwd", EinfftMlpParams), ("dimsum_einfft_mlp_bwd", EinfftMlpBwdParams))]
+        ("dimsum_einfft_idft_real", EinfftDftParams), ("dimsum_einfft_mlp_fwd", EinfftMlpParams), ("dimsum_einfft_mlp_bwd", EinfftMlpBwdParams),
+        ("dimsum_gelu_fwd", GeluParams), ("dimsum_gelu_bwd", GeluParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

@@ -1,11 +1,20 @@
-"""create_model(args) -- argparse namespace -> DiM constructor, like dimsum/create_model.py:5-38 (DiT baselines are not
-part of this build)."""
+"""create_model(args) -- argparse namespace -> DiM or DiT constructor, like dimsum/create_model.py:5-38."""
 from .models_dim import DiM_models
+from .models_dit import DiT_models
+
+DIM_ONLY_FLAGS = ("block_type", "pe_type")      # what a DiT name ignores (the CLIs say so in one logged line)
+
+
+def is_dit(name):
+    return name in DiT_models
 
 
 def create_model(config):
-    if "DiM" not in config.model:
-        raise NotImplementedError(f"{config.model}: only the DiM family is part of the MI355X hot-path build")
+    if config.model in DiT_models:              # the baseline takes the five arguments the reference passes (create_model.py:31-38)
+        return DiT_models[config.model](img_resolution=config.image_size // 8, in_channels=config.num_in_channels,
+                                        label_dropout=config.label_dropout, num_classes=config.num_classes, learn_sigma=config.learn_sigma)
+    if config.model not in DiM_models:
+        raise NotImplementedError(f"{config.model}: only the DiM and DiT families are part of the MI355X hot-path build")
     return DiM_models[config.model](
         img_resolution=config.image_size // 8, in_channels=config.num_in_channels, label_dropout=config.label_dropout,
         num_classes=config.num_classes, gated_linear_unit=getattr(config, "gated_linear_unit", True),
@@ -27,3 +36,11 @@ def published_config(model="DiM-L/2", image_size=256, num_classes=1000, **over):
                learnable_pe=True, use_final_norm=False, use_attn_every_k_layers=4, not_use_gated_mlp=False)
     cfg.update(over)
     return SimpleNamespace(**cfg)
+
+
+def model_from_cli(args, log=print):
+    """the model a CLI builds from its --model / --image-size / --num-classes / --pe-type / --block-type flags (train.py, sample_ddp.py); for a DiT
+    name the DiM-only flags are ignored, with one logged line"""
+    if is_dit(args.model):
+        log(f"{args.model}: " + " / ".join("--" + f.replace("_", "-") for f in DIM_ONLY_FLAGS) + " are DiM-only flags and are ignored for the DiT baseline")
+    return create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type, block_type=args.block_type))

@@ -138,7 +138,7 @@ template <int kEpi, int kVar = 0> int launch_f16(const Args &a, const Where &w, 
 // 128-row / 256-row tiles (A / B runs, tools/bench_gemm.py) and 514 keeps the 256-row ones; 0 = by shape: scaled-fp16 operands (one product
 // per element) with a short K spend a third to a half of a 256 x 256 tile's time in its epilogue. Per epilogue, for fp16 operands:
 //   f32, f32 + bias, f16_qkv, f32_conv   k <= 576, or tune_variant 512
-//   f32 gate + residual, gated f16       tune_variant 512 only
+//   f32 gate + residual, gated f16, gelu f16   tune_variant 512 only
 //   gated split3                         never (no 128-row build)
 inline bool m128_tiles(int epilogue, bool bf, int k, int tune_variant) {
     if (bf || epilogue == DIMSUM_GEMM_EPI_GATED_GELU_SPLIT3) return false;
@@ -226,6 +226,21 @@ static int gemm_nt_run(const dimsum_gemm_params_t *pub, void *stream, int *probe
         a.rows_per_batch = p.rows_per_batch;
         a.q_cols = p.qkv_q_cols;
         return launch_f16<kEpiF16Qkv>(a, w, m128);
+    }
+    if (p.epilogue == DIMSUM_GEMM_EPI_GELU_F16) {
+        // fc1 of the plain MLP: h = gelu_tanh(A B^T + bias) as the scaled-fp16 image of fc2's GEMM. Built for scaled-fp16 operands with the
+        // bound-derived row scale only, on the tile shapes of the gated f16 epilogue's per-tile kernels (256-row; 128-row under tune_variant 512)
+        // (unscaled fp16 operands or no bound -- a constant out_scale, as GATED_GELU_F16 allows -- are combinations that are not built either)
+        if (bf || !a.sa || !p.gate_bound_ptr || p.a_alias_rows != 0 || p.x12_ptr || p.c_image_pieces != 0) return DIMSUM_ERR_UNSUPPORTED;
+        if (!p.h_inv_scale_ptr) return DIMSUM_ERR_NULL;
+        if (p.n % 8 != 0) return DIMSUM_ERR_SHAPE;
+        if (p.ldc % 8 != 0 || p.ldc < p.n || !aligned_to<char>(p.c_ptr, 16) || (p.bias_ptr && !aligned_to<char>(p.bias_ptr, 16)) ||
+            !aligned_to<char>(p.h_inv_scale_ptr, 4) || (int64_t)257 * p.ldc * 2 >= ((int64_t)1 << 31))
+            return DIMSUM_ERR_STRIDE;
+        fill_right(a, p, p.n, kBN);
+        a.gate_bound = reinterpret_cast<const float *>(p.gate_bound_ptr);
+        a.inv_out = reinterpret_cast<float *>(p.h_inv_scale_ptr);
+        return launch_f16<kEpiGeluF16>(a, w, m128);
     }
     if (p.epilogue == DIMSUM_GEMM_EPI_F32_CONV) {
         if (!p.conv_weight_ptr) return DIMSUM_ERR_NULL;

@@ -63,15 +63,15 @@ constexpr int kParity = 4 * kHalf;         // bytes of one K tile in LDS
 constexpr int kSlotA0 = 0, kSlotA1 = kHalf, kSlotB0 = 2 * kHalf, kSlotB1 = 3 * kHalf;
 
 enum { kOpBf16 = 0, kOpF16 = 1 };
-enum { kEpiF32 = 0, kEpiGatedSplit3 = 1, kEpiGatedF16 = 2, kEpiF32Bias = 3, kEpiF32GateRes = 4, kEpiF16Qkv = 5, kEpiF32Conv = 6 };
+enum { kEpiF32 = 0, kEpiGatedSplit3 = 1, kEpiGatedF16 = 2, kEpiF32Bias = 3, kEpiF32GateRes = 4, kEpiF16Qkv = 5, kEpiF32Conv = 6, kEpiGeluF16 = 7 };
 
 struct Args {
     const char *A, *B0, *B1;       // B0 / B1: first weight row of the two 128-row halves' matrices (B1 = B0 + 128 rows for a plain GEMM)
     void *C;
     const float *bias0, *bias1;    // per output column (gated: of x1 / x2), may be NULL
     const float *sa, *sb;          // scaled-fp16 operands: inverse scale per A row (M) / per B row (N; gated: 2 F), NULL = 1
-    const float *gate_bound;       // kEpiGatedF16 with per-row scales: {max_n sum_k |w_nk| (true units), max |bias|}; NULL = out_scale
-    float *inv_out;                // kEpiGatedF16 with per-row scales: (M) inverse scales of the h image
+    const float *gate_bound;       // kEpiGatedF16 with per-row scales: {max_n sum_k |w_nk| (true units), max |bias|}; NULL = out_scale. kEpiGeluF16: required
+    float *inv_out;                // kEpiGatedF16 with per-row scales, kEpiGeluF16: (M) inverse scales of the h image
     const float *res, *gate;       // kEpiF32GateRes: C = res + gate[row / rows_per_batch] * (A B^T + bias); res (M, N), gate (M / rows_per_batch, N) or NULL (= 1)
     int64_t ldr, ldg;
     int rows_per_batch;            // a multiple of 256: a tile lies inside one batch element
@@ -980,12 +980,17 @@ __device__ __forceinline__ void gemm_body(const Args &p, char *lds) {
                     }
                 }
         }
-    } else if constexpr (kEpi == kEpiF16Qkv) {
+    } else if constexpr (kEpi == kEpiF16Qkv || kEpi == kEpiGeluF16) {
         // q | k | v of the attention fusion as scaled fp16 (include/dimsum_hip.h, DIMSUM_GEMM_EPI_F16_QKV): the attention kernel reads half the
         // bytes and stages K / V without a conversion. Scales from the bound |x W^T + b| <= 2^15 a_inv wl1 + bmax: q per row, k / v per
         // batch element (the maximum of a_inv over the element's rows: a tile lies inside one element).
+        // kEpiGeluF16 (the plain MLP's fc1, DIMSUM_GEMM_EPI_GELU_F16): the same tile walk with every column on the per-row scale of the same
+        // bound (|gelu_tanh(x)| <= |x|), h = gelu_tanh(x W^T + b) stored, and the rows' inverse scales written once (column tile 0) to inv_out:
+        // the scaled-fp16 image fc2's GEMM reads. No pairing, no interleave: an output element depends on its own accumulator only.
+        constexpr bool kGelu = kEpi == kEpiGeluF16;
         constexpr int kNW = kM1 ? 4 : 8;
         float *red = reinterpret_cast<float *>(lds);              // (the ring is free: no DMA pending, every operand read retired)
+        (void)red;
         // every load of the epilogue is issued here, in one batch (the round-4 form paid a memory round trip for the batch maximum, one for the
         // row scales and one per column vector: 6 in a row)
         const float wl1 = p.gate_bound[0], bmax = p.gate_bound[1];
@@ -1007,26 +1012,31 @@ __device__ __forceinline__ void gemm_body(const Args &p, char *lds) {
                     csb[ni][j] = *reinterpret_cast<const f4 *>(p.sb + lc);
                 }
         }
-        {
-            const float *sab = p.sa + (int64_t)(m0 / p.rows_per_batch) * p.rows_per_batch;
-            float mloc = 0.f;
-            for (int t = threadIdx.x; t < p.rows_per_batch; t += kNW * 64) mloc = fmaxf(mloc, sab[t]);
-            mloc = wave_allmax(mloc);
-            if (lane == 0) red[w] = mloc;
-        }
-        __syncthreads();
-        float mb = red[0];
+        float kv_scale = 0.f, kv_inv;
+        if constexpr (!kGelu) {
+            {
+                const float *sab = p.sa + (int64_t)(m0 / p.rows_per_batch) * p.rows_per_batch;
+                float mloc = 0.f;
+                for (int t = threadIdx.x; t < p.rows_per_batch; t += kNW * 64) mloc = fmaxf(mloc, sab[t]);
+                mloc = wave_allmax(mloc);
+                if (lane == 0) red[w] = mloc;
+            }
+            __syncthreads();
+            float mb = red[0];
 #pragma unroll
-        for (int i = 1; i < kNW; ++i) mb = fmaxf(mb, red[i]);
-        __syncthreads();                                            // (the staging below overwrites `red`)
-        float kv_scale, kv_inv;
-        f16s_scales(2.0f * (32768.0f * mb * wl1 + bmax), kv_scale, kv_inv);
+            for (int i = 1; i < kNW; ++i) mb = fmaxf(mb, red[i]);
+            __syncthreads();                                            // (the staging below overwrites `red`)
+            f16s_scales(2.0f * (32768.0f * mb * wl1 + bmax), kv_scale, kv_inv);
+        }
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float qinv;
                 f16s_scales(2.0f * (32768.0f * row_sa[mi][i] * wl1 + bmax), row_qs[mi][i], qinv);
+                if constexpr (kGelu) {
+                    if (tile_n == 0 && wc == 0 && lane < 16) p.inv_out[m0 + mi * kMiRows + wr * 64 + i * 16 + lane] = qinv;
+                }
             }
         // the tile through LDS: [kTileM rows][256 cols] fp16, 512 B per row; the 8-byte unit u (4 columns) of row r sits at u ^ (r & 15)
 #pragma unroll
@@ -1035,14 +1045,18 @@ __device__ __forceinline__ void gemm_body(const Args &p, char *lds) {
             for (int j = 0; j < 2; ++j) {
                 const int tcol = ni * 128 + ecol + j * 16, col = n0 + tcol;
                 const f4 bv = cbv[ni][j], sbv = csb[ni][j];       // (columns past N hold column 0's values: computed, never stored)
-                const bool is_q = col < p.q_cols;
+                const bool is_q = kGelu || col < p.q_cols;
                 const int unit = tcol >> 2;
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int r = mi * kMiRows + wr * 64 + i * 16 + (lane & 15);
-                        const f4 x = acc[mi][ni][i][j] * (sbv * row_sa[mi][i]) + bv;
+                        f4 x = acc[mi][ni][i][j] * (sbv * row_sa[mi][i]) + bv;
+                        if constexpr (kGelu) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) x[e] = gelu_tanh_f(x[e]);
+                        }
                         const float sc = is_q ? row_qs[mi][i] : kv_scale;
                         const __half2 a = __floats2half2_rn(x[0] * sc, x[1] * sc), b = __floats2half2_rn(x[2] * sc, x[3] * sc);
                         *reinterpret_cast<uint2 *>(lds + r * 512 + ((unit ^ (lane & 15)) << 3)) = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));

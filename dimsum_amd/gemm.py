@@ -450,12 +450,13 @@ def qkv_f16s(x, weight, bias, rows_per_batch, bound2):
 
 def f16s_plan(model):
     """what a forward of `model` under the scaled-fp16 policy converts: [(weight, kind, bias, partner)] over its large bias-free-GEMM
-    Linears -- the mixers' in_proj, the fusion's qkv1 / qkv2 / proj, the shared attention's qkv / proj, the gated MLP's w12 / w3
+    Linears -- the mixers' in_proj, the fusion's qkv1 / qkv2 / proj, the shared attention's qkv / proj, the gated MLP's w12 / w3, the plain
+    Mlp's fc1 / fc2
     (dimsum/models_dim.py:974-1117, mlp.py:49-70, attention_fusion.py:44-79). kind: "plain" (image), "gated" (image + the gate epilogue's
     bound with `bias`), "kv" (image + its half of the attention kernel's bound; `partner` = the other qkv Linear's weight or None),
     "plain_t" (the mixers' out_proj: the image transposed, the right operand of out_proj_f16's TN product)."""
     from .attention_fusion import CrossAttentionFusion
-    from .mlp import GatedMLP
+    from .mlp import GatedMLP, Mlp
     plan = []
     for m in model.modules():
         if hasattr(m, "in_proj") and hasattr(m, "x_proj") and hasattr(m, "dt_proj"):
@@ -466,6 +467,8 @@ def f16s_plan(model):
             plan += [(m.qkv1.weight, "kv", m.qkv1.bias, m.qkv2), (m.proj.weight, "plain", None, None)]
         elif isinstance(m, GatedMLP):
             plan += [(m.w12.weight, "gated", m.w12.bias, None), (m.w3.weight, "plain", None, None)]
+        elif isinstance(m, Mlp) and m._fused:       # (fc1's GELU epilogue takes the gated epilogue's bound {wl1 (1 + 2^-10), max|b|})
+            plan += [(m.fc1.weight, "gated", m.fc1.bias, None), (m.fc2.weight, "plain", None, None)]
         elif type(m).__name__ == "Attention" and hasattr(m, "qkv") and hasattr(m, "proj"):
             plan += [(m.qkv.weight, "kv", m.qkv.bias, None), (m.proj.weight, "plain", None, None)]
     return plan
@@ -697,6 +700,30 @@ def gated_mlp_hidden_split3(x3, w12, b12):
     if isinstance(x3, native.PairImage):
         x3 = x3.image3()
     return native.gated_gelu_fwd(torch.mm(x3, w3i.t(), out_dtype=torch.float32), b12, split3=True)
+
+
+def mlp_hidden_split3(x3, w1, b1):
+    """x3 = the left operand image of x (split-bf16 (M, 3K), PairImage or F16Image), w1 (F, K), b1 (F) or None -> the left image of
+    gelu_tanh(x W1^T + b1), the hidden activation of the plain Mlp (dimsum/models_dit.py:124), in x3's own carrier. Scaled fp16: ONE kernel, the
+    activation in the GEMM's epilogue (DIMSUM_GEMM_EPI_GELU_F16, row scales from gated_bound's {wl1, bmax}) where the library builds it
+    (DIMSUM_GELU_EPILOGUE=0 switches it off); everywhere else the bias-free GEMM + the row pass (csrc/gelu.hip), which writes the image."""
+    from . import native
+    F_ = w1.shape[0]
+    if isinstance(x3, native.F16Image):
+        x3 = x3.reshape(-1, x3.shape[-1])
+        w16 = weight_f16s(w1)
+        if (os.environ.get("DIMSUM_GELU_EPILOGUE", "1") != "0" and own_gemm_enabled() and native.gemm_nt_supported(x3.data, w16.data) and F_ % 8 == 0):
+            return native.gemm_nt(x3.data, w16.data, bias=b1, epilogue="gelu_f16", scales=(x3.inv, w16.inv), gate_bound=gated_bound(w1, b1))
+        x1 = _nt_f16s(x3, w16)
+        return native.gelu_fwd(x1, b1, split3="f16s") if F_ <= 5120 else native.rows_f16s(native.gelu_fwd(x1, b1))
+    x3 = x3.reshape(-1, x3.shape[-1])
+    w3i = weight_image(w1)
+    own = own_gemm_enabled() and native.gemm_nt_supported(x3, w3i)
+    if isinstance(x3, native.PairImage) and not own:
+        x3 = x3.image3()
+    # the h image as the pair [hi | lo] where its consumer (the fc2 GEMM on the hand-written kernel) reads it as [hi | hi | lo]
+    pair = own and F_ % 64 == 0 and os.environ.get("DIMSUM_PAIR_IMAGES", "1") != "0"
+    return native.gelu_fwd(_nt(x3, w3i), b1, split3="pair" if pair else True)
 
 
 def train_pairs_enabled(M, *widths):

@@ -1,4 +1,4 @@
-"""GatedMLP -- dimsum/mlp.py:49-70: w3( act(x W12a + b) * (x W12b + b) ) + b3. With the tanh-GELU the DiM blocks use,
+"""GatedMLP and the plain Mlp (at the end of the file). GatedMLP -- dimsum/mlp.py:49-70: w3( act(x W12a + b) * (x W12b + b) ) + b3. With the tanh-GELU the DiM blocks use,
 bias + activation + gate run as ONE fused HIP pass over the bias-free w12 GEMM output (csrc/token_transform.hip,
 gated GeLU); the w3 bias can be handed to the caller's fused residual pass (`forward_deferred`). Keeping the biases out
 of the GEMMs matters on gfx950: hipBLASLt serves bias-free fp32 matmuls under the reference's TF32 policy
@@ -28,6 +28,24 @@ class _GatedGeluFn(torch.autograd.Function):
 def gated_gelu(x12, bias=None):
     """gelu_tanh(x12[..., :H] + bias[:H]) * (x12[..., H:] + bias[H:])"""
     return _GatedGeluFn.apply(x12, bias)
+
+
+class _GeluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, bias):
+        x = x.contiguous()
+        ctx.save_for_backward(x, bias)
+        return native.gelu_fwd(x, bias)
+
+    @staticmethod
+    def backward(ctx, dh):
+        x, bias = ctx.saved_tensors
+        return native.gelu_bwd(x, bias, dh, need_dbias=bias is not None and ctx.needs_input_grad[1])
+
+
+def bias_gelu(x, bias=None):
+    """gelu_tanh(x + bias): the activation of the plain Mlp as one HIP row pass, forward and backward (csrc/gelu.hip)"""
+    return _GeluFn.apply(x, bias)
 
 
 class _ModGatedMlpImagesFn(torch.autograd.Function):
@@ -199,6 +217,46 @@ class GatedMLP(nn.Module):
             x1, x2 = self.w12(x).chunk(2, dim=-1)
             h = self.act_layer(x1) * x2
         return gemm.linear(h, self.w3.weight), self.w3.bias
+
+    def forward(self, x):
+        y, b = self.forward_deferred(x)
+        return y if b is None else y + b
+
+
+class Mlp(nn.Module):
+    """timm 0.9.12 Mlp as the reference builds it (dimsum/models_dit.py:124; models_dim.py with use_gated_mlp=False): fc2(act(fc1(x))), 4x wide,
+    with biases, parameters `fc1` / `fc2`. With the tanh-GELU every block uses, bias + activation run as ONE HIP pass over the bias-free fc1 GEMM
+    output (csrc/gelu.hip) -- at inference under the scaled-fp16 policy inside that GEMM's epilogue (DIMSUM_GEMM_EPI_GELU_F16) -- and the fc2 bias
+    can be handed to the caller's fused residual pass (`forward_deferred`), as GatedMLP does."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.0, bias=True):
+        super().__init__()
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        self.fc1 = nn.Linear(in_features, hidden_features, bias=bias)
+        self.act = act_layer()
+        self.fc2 = nn.Linear(hidden_features, out_features, bias=bias)
+        self._fused = isinstance(self.act, nn.GELU) and self.act.approximate == "tanh"
+
+    def forward_deferred(self, x, x3=None, residual=None, gate=None):
+        """-> (y, b): the module's output is y + b; b (fc2's bias or None) is left to the caller's fused residual pass. The contract of
+        GatedMLP.forward_deferred: x3 = x as the operand image the caller's producer kernel wrote (split-bf16, pair or scaled fp16; x then only
+        carries the shape) -- the activation writes fc2's operand image; residual (B, L, H) [, gate (B, H)] (with x3): the block's residual tail
+        rides in the fc2 GEMM's epilogue and the call returns (residual + gate * (mlp(x) + b2), None)."""
+        b1 = None if self.fc1.bias is None else self.fc1.bias.float()
+        if x3 is not None:
+            h = gemm.mlp_hidden_split3(x3, self.fc1.weight, b1)
+            if residual is not None:
+                H = self.fc2.weight.shape[0]
+                b2 = None if self.fc2.bias is None else self.fc2.bias.float()
+                y = gemm.linear_split3(h, self.fc2.weight, bias=b2, residual=residual.reshape(-1, H), gate=gate, rows_per_batch=residual.shape[-2])
+                return y.view(residual.shape), None
+            return gemm.linear_split3(h, self.fc2.weight).view(*x.shape[:-1], self.fc2.weight.shape[0]), self.fc2.bias
+        if self._fused and x.dtype == torch.float32:
+            h = bias_gelu(gemm.linear(x, self.fc1.weight), b1)
+        else:
+            h = self.act(self.fc1(x))
+        return gemm.linear(h, self.fc2.weight), self.fc2.bias
 
     def forward(self, x):
         y, b = self.forward_deferred(x)

@@ -11,7 +11,8 @@ What is structured differently (results equal to fp32 roundoff; pinned by tests/
   * the GatedMLP activation is a fused epilogue; RMSNorm is the HIP fused add+norm, not Triton.
   * pe_type "rope" / "cpe": the embed pass is one HIP launch (ops/pos_embed.py: the rotation of the channel pairs; the depthwise 3x3 conv on
     the token grid + LayerNorm + adaLN modulation), "ape" the add it always was.
-Out of scope (constructor raises): block type combined_einfft, MoE and `enable_fourier_layers` -- unused by every published config
+The DiT baseline built from these pieces lives in models_dit.py; the plain Mlp of `use_gated_mlp=False` in mlp.py.
+Out of scope (constructor raises): MoE and `enable_fourier_layers` -- unused by every published config
 (SURVEY.md section 2.1).
 """
 import math
@@ -27,7 +28,7 @@ from . import scanning_orders as so
 from . import gemm
 from .attention_fusion import CrossAttentionFusion
 from .dct_layer import init_dct_kernel, init_idct_kernel
-from .mlp import GatedMLP
+from .mlp import GatedMLP, Mlp
 from .modules.mamba_simple import CondMamba, Mamba
 from .ops import token_ops
 from .ops.layernorm import RMSNorm, layer_norm_fn, rms_norm_fn
@@ -254,17 +255,6 @@ class Attention(nn.Module):
         return y if b is None else y + b
 
 
-class Mlp(nn.Module):
-    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.0):
-        super().__init__()
-        self.fc1 = nn.Linear(in_features, hidden_features or in_features)
-        self.act = act_layer()
-        self.fc2 = nn.Linear(hidden_features or in_features, out_features or in_features)
-
-    def forward(self, x):
-        return self.fc2(self.act(self.fc1(x)))
-
-
 def drop_path(x, drop_prob=0.0, training=False, scale_by_keep=True):
     if drop_prob == 0.0 or not training:
         return x
@@ -301,9 +291,14 @@ def _modulation(seq, c):
     return seq(c)
 
 
+def _mlp_in_weight(mlp):
+    """the weight of the MLP's first Linear: what decides whether a producer kernel writes that Linear's operand image"""
+    return (mlp.w12 if isinstance(mlp, GatedMLP) else mlp.fc1).weight
+
+
 def _mlp_tail(mlp, x, normed, shift, scale, gate):
     """x + gate * mlp(modulate(normed, shift, scale))  (models_dim.py:1111-1115, 1551-1553)"""
-    if getattr(mlp, "_fused", False) and gemm.split3_train_enabled(normed, mlp.w12.weight):
+    if isinstance(mlp, GatedMLP) and mlp._fused and gemm.split3_train_enabled(normed, mlp.w12.weight):
         from .mlp import mod_gated_mlp_images
         m, mb = mod_gated_mlp_images(mlp, normed, shift, scale)              # training: every MLP GEMM on operand images
         return token_ops.gate_residual(x, m, gate, mb)
@@ -328,7 +323,7 @@ def _norm_mlp_tail(norm_2, mlp, hidden_states, shift, scale, gate, fused=None, p
         B, L, H = hidden_states.shape
         x, res = (hidden_states, None) if fused is None else (fused, None if in_epilogue else hidden_states)
         # ... written directly as the split-bf16 operand image of the w12 GEMM when the library would split it anyway (gemm.py)
-        s3 = getattr(mlp, "_fused", False) and gemm.split3_enabled(hidden_states, mlp.w12.weight, producer="norm")   # False / True / "f16s"
+        s3 = getattr(mlp, "_fused", False) and gemm.split3_enabled(hidden_states, _mlp_in_weight(mlp), producer="norm")   # False / True / "f16s"
         y, _, _, hnew = native.layer_norm_fwd(x.reshape(B * L, H), norm_2.weight, norm_2.bias, norm_2.eps,
                                               residual=None if res is None else res.reshape(B * L, H), is_rms_norm=True, x_bias=pb,
                                               mod_scale=scale, mod_shift=shift, rows_per_batch=L, **({"split3": s3} if s3 else {}))

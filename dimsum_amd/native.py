@@ -677,6 +677,73 @@ def gated_gelu_fwd(x12, bias=None, split3=False):
     return h
 
 
+_GELU_OUT = {False: _lib.GELU_OUT_F32, True: _lib.GELU_OUT_SPLIT3, "pair": _lib.GELU_OUT_PAIR, "f16s": _lib.GELU_OUT_F16S}
+
+
+def _gelu_call(fn, what, x, bias, dh, split3, need_dbias, scales):
+    """one launch of dimsum_gelu_fwd / _bwd: the output tensor (or image) of the asked mode, the struct, the call"""
+    H = x.shape[-1]
+    rows = x.numel() // H
+    mode = _GELU_OUT[split3]
+    inv = None
+    if mode == _lib.GELU_OUT_F16S:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float16)
+        inv = torch.empty(x.shape[:-1], device=x.device, dtype=torch.float32)
+    elif mode == _lib.GELU_OUT_F32:
+        out = torch.empty_like(x)
+    else:
+        out = torch.empty(x.shape[:-1] + ((2 if mode == _lib.GELU_OUT_PAIR else 3) * H,), device=x.device, dtype=torch.bfloat16)
+    dbias = _zeros(H, x.device) if need_dbias else None
+    P = _lib.GeluParams()
+    P.out_image, P.rows, P.hidden = mode, rows, H
+    P.x_ptr, P.bias_ptr, P.dh_ptr, P.out_ptr, P.inv_scale_ptr, P.dbias_ptr = _ptr(x), _ptr(bias), _ptr(dh), _ptr(out), _ptr(inv), _ptr(dbias)
+    if scales is not None:
+        E = _lib.attach_ext(P, _lib.GeluExt)
+        E.row_inv_ptr, E.bound_ptr = _ptr(scales[0]), _ptr(scales[1])
+    with torch.cuda.device(x.device):
+        _lib.check(fn(P, _stream(x)), what)
+    if mode == _lib.GELU_OUT_F16S:
+        out = F16Image(out, inv)
+    elif mode == _lib.GELU_OUT_PAIR:
+        out = PairImage(out)
+    return out, dbias
+
+
+def gelu_fwd(x, bias=None, split3=False, scales=None):
+    """x: (..., H) fp32 contiguous (fc1 GEMM output WITHOUT bias), bias (H) or None -> gelu_tanh(x + bias)   (timm Mlp's act, models_dit.py:124)
+    split3: the result as the left operand image of the fc2 GEMM -- True: split-bf16 (..., 3H) bfloat16 [hi | hi | lo]; "pair": PairImage
+    [hi | lo]; "f16s": F16Image (H <= 5120) with the exact row maximum's scale, or -- scales = (row_inv (rows,), bound (2,) {wl1, bmax}), the
+    fc1 GEMM's left-image scales and weight bound -- the bound-derived scale of gemm_nt(epilogue="gelu_f16")"""
+    _gpu(x, bias)
+    _check(x.dtype == torch.float32 and x.is_contiguous() and x.shape[-1] % 4 == 0, "gelu: x must be contiguous float32 with H % 4 == 0")
+    H = x.shape[-1]
+    if bias is not None:
+        _check(bias.dtype == torch.float32 and tuple(bias.shape) == (H,) and bias.is_contiguous(), "gelu: bias must be (H,) float32")
+    _check(split3 in (False, True, "pair", "f16s"), "gelu: split3 is False, True, 'pair' or 'f16s'")
+    _check(split3 != "f16s" or H <= 5120, "gelu: the f16s image needs H <= 5120")
+    if scales is not None:
+        _gpu(*scales)
+        _check(split3 == "f16s" and scales[0].dtype == torch.float32 and scales[0].is_contiguous() and scales[0].numel() == x.numel() // H
+               and scales[1].dtype == torch.float32 and scales[1].is_contiguous() and scales[1].numel() == 2,
+               "gelu: scales = (row_inv (rows,), bound (2,)) float32 go with the f16s image")
+    return _gelu_call(_lib.load().dimsum_gelu_fwd, "gelu_fwd", x, bias, None, split3, False, scales)[0]
+
+
+def gelu_bwd(x, bias, dh, need_dbias=True, split3=False):
+    """-> (dx, dbias or None), dx = dh * gelu_tanh'(x + bias).  split3: dx as the operand image of fc1's two gradient GEMMs -- True: split-bf16 in
+    weight order (..., 3H) bfloat16 [hi | lo | hi]; "pair": PairImage [hi | lo]; "f16s": F16Image (exact row maxima; H <= 5120)"""
+    _gpu(x, bias, dh)
+    dh = dh.contiguous()
+    H = x.shape[-1]
+    _check(x.dtype == torch.float32 and x.is_contiguous() and H % 4 == 0 and dh.dtype == torch.float32 and dh.shape == x.shape,
+           "gelu_bwd: x and dh must be contiguous float32 of one shape with H % 4 == 0")
+    if bias is not None:
+        _check(bias.dtype == torch.float32 and tuple(bias.shape) == (H,) and bias.is_contiguous(), "gelu_bwd: bias must be (H,) float32")
+    _check(split3 in (False, True, "pair", "f16s"), "gelu_bwd: split3 is False, True, 'pair' or 'f16s'")
+    _check(split3 != "f16s" or H <= 5120, "gelu_bwd: the f16s image needs H <= 5120")
+    return _gelu_call(_lib.load().dimsum_gelu_bwd, "gelu_bwd", x, bias, dh, split3, bias is not None and need_dbias, None)
+
+
 def split3_rows(x, left):
     """(R, K) float32 rows (stride(1) == 1) -> (R, 3K) bfloat16 split operand image: x = hi + lo, hi = bf16(x), lo = bf16(x - hi);
     left: [hi | hi | lo] (activations), else [hi | lo | hi] (weights), so that  left_image @ weight_image.T  accumulates
@@ -1091,6 +1158,8 @@ def gemm_nt(a, b, bias=None, epilogue="f32", out=None, out_scale=1.0, events=Non
                                  gelu_tanh(x1 + b1) * (x2 + b2)   (mlp.py:66-70; the fp32 (M, 2F) x12 never exists)
                                  keep_x12 (training forward): the bias-free float32 (M, 2F) [x1 | x2] is stored too -> (image, x12)
                "gated_f16"    -> same, (M, F) float16 of h * out_scale
+               "gelu_f16"     -> F16Image (M, N) of gelu_tanh(a b^T + bias): fc1 of the plain MLP over scaled-fp16 operands (scales and gate_bound
+                                 = {wl1, bmax} required: the row scale is derived from the bound); bfloat16 operands are refused by the library
     residual (M, N) float32 [, gate (M / rows_per_batch, N) float32]: epilogue "f32" becomes residual + gate[row // rows_per_batch] * (a b^T + bias)
     -- the residual tail of a block in the epilogue of its last Linear (rows_per_batch % 256 == 0).
     scales: (a_inv (M,), b_inv (N,)) float32 inverse scales of scaled-fp16 operand images (F16Image): C[m, n] *= a_inv[m] * b_inv[n].
@@ -1157,6 +1226,12 @@ def gemm_nt(a, b, bias=None, epilogue="f32", out=None, out_scale=1.0, events=Non
         if out is None:
             out = torch.empty((M, N), device=a.device, dtype=torch.float16)
         _check(out.dtype == torch.float16 and out.shape == (M, N) and out.stride(1) == 1, "gemm_nt: out must be (M, N) float16 rows")
+    elif epilogue == "gelu_f16":
+        epi = _lib.GEMM_EPI_GELU_F16
+        _check(scales is not None and gate_bound is not None and N % 8 == 0, "gemm_nt: gelu_f16 needs scales, gate_bound = {wl1, bmax} and N % 8 == 0")
+        if out is None:
+            out = torch.empty((M, N), device=a.device, dtype=torch.float16)
+        _check(out.dtype == torch.float16 and out.shape == (M, N) and out.stride(1) == 1, "gemm_nt: out must be (M, N) float16 rows")
     elif epilogue == "gated_f16":
         epi = _lib.GEMM_EPI_GATED_GELU_F16
         if out is None:
@@ -1172,10 +1247,10 @@ def gemm_nt(a, b, bias=None, epilogue="f32", out=None, out_scale=1.0, events=Non
                and sb.numel() == N, "gemm_nt: scales must be contiguous float32 (M,) and (N,)")
         if gate_bound is not None:
             _gpu(gate_bound)
-            _check(epilogue in ("gated_f16", "f16_qkv") and gate_bound.dtype == torch.float32 and gate_bound.numel() == 2 and gate_bound.is_contiguous(),
-                   "gemm_nt: gate_bound is a 2-element float32 tensor for the gated_f16 / f16_qkv epilogues")
+            _check(epilogue in ("gated_f16", "f16_qkv", "gelu_f16") and gate_bound.dtype == torch.float32 and gate_bound.numel() == 2 and gate_bound.is_contiguous(),
+                   "gemm_nt: gate_bound is a 2-element float32 tensor for the gated_f16 / f16_qkv / gelu_f16 epilogues")
             ext.update(gate_bound_ptr=_ptr(gate_bound))
-            if epilogue == "gated_f16":
+            if epilogue in ("gated_f16", "gelu_f16"):
                 h_inv = torch.empty((M,), device=a.device, dtype=torch.float32)
                 ext.update(h_inv_scale_ptr=_ptr(h_inv))
     x12 = None

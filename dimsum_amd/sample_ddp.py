@@ -114,7 +114,7 @@ def build_parser():
 
 
 def main(argv=None):
-    from .create_model import create_model, published_config
+    from .create_model import model_from_cli
     args, _ = build_parser().parse_known_args(argv)          # unknown flags are ignored like sample_ddp.py:369
     torch.backends.cuda.matmul.allow_tf32 = args.tf32
     torch.backends.cudnn.allow_tf32 = args.tf32
@@ -126,7 +126,7 @@ def main(argv=None):
     rank, world = dist.get_rank(), dist.get_world_size()
     device = local_rank
     torch.manual_seed(args.global_seed * world + rank)
-    model = create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type, block_type=args.block_type)).to(device).eval()
+    model = model_from_cli(args, log=print if rank == 0 else (lambda *a: None)).to(device).eval()
     if args.ckpt:
         load_denoiser_weights(model, args.ckpt)                  # EMA preferred (download.py:26-27)
     r = args.image_size // 8

@@ -136,7 +136,7 @@ def transport_from_args(args):
 
 
 def main(argv=None):
-    from .create_model import create_model, published_config
+    from .create_model import model_from_cli
     args, _ = build_parser().parse_known_args(argv)
     torch.backends.cuda.matmul.allow_tf32 = args.tf32          # train.py:20-21
     torch.backends.cudnn.allow_tf32 = args.tf32
@@ -149,7 +149,7 @@ def main(argv=None):
     assert args.global_batch_size % world == 0, "Batch size must be divisible by world size."
     device = local_rank
     torch.manual_seed(args.global_seed * world + rank)
-    model = create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type, block_type=args.block_type)).to(device)
+    model = model_from_cli(args, log=print if rank == 0 else (lambda *a: None)).to(device)
     model, ema, opt = build_training(model, device, args.lr, world, [device])
     transport = transport_from_args(args)
     init_epoch, train_steps = (load_checkpoint(args.resume, model, ema, opt, lr=args.lr) if args.resume else (0, 0))

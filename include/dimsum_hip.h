@@ -17,6 +17,7 @@
  *   dimsum_token_transform     <- einops/flip/local_scan/DWT/DCT chains          dimsum/models_dim.py:572-604,656-705,876-928,1496-1524
  *   dimsum_xattn_fusion_fwd/_bwd <- F.scaled_dot_product_attention x2 (+ autograd)  dimsum/attention_fusion.py:44-75
  *   dimsum_gated_gelu_fwd/_bwd <- gelu_tanh(x1) * x2                             dimsum/mlp.py:66-70
+ *   dimsum_gelu_fwd/_bwd       <- timm Mlp's act: gelu_tanh(fc1(x) + b)                  dimsum/models_dit.py:124
  *   dimsum_gemm_nt             <- nn.Linear / F.linear of the bias-free projections (cuBLAS TF32 GEMMs under train.py:20-21), and
  *                                 w12 + bias + gelu_tanh(x1) * x2 of the GatedMLP as ONE kernel    dimsum/mlp.py:49-70
  *
@@ -725,6 +726,46 @@ int dimsum_gated_gelu_bwd_f16s(const void *x12, const void *bias, const void *dh
                                int64_t hidden, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The plain (non-gated) MLP's activation (timm Mlp as dimsum/models_dit.py:124 and use_gated_mlp=False build it: fc1 -> GELU(tanh) -> fc2),
+ * x : (rows, hidden) f32 contiguous = output of the fc1 GEMM WITHOUT its bias, hidden % 4 == 0:
+ *   fwd: h[m, j]  = gelu_tanh(x[m, j] + bias[j])                       bias (hidden) f32 or NULL
+ *   bwd: dx[m, j] = dh[m, j] * gelu_tanh'(x[m, j] + bias[j]);  dbias (hidden) f32 zero-filled by the caller (column sums of dx, f32 atomics:
+ *        one per column per 64-row workgroup, like dimsum_gated_gelu_bwd) or NULL.
+ * out_image: what out_ptr receives --
+ *   DIMSUM_GELU_OUT_F32     (rows, hidden) f32
+ *   DIMSUM_GELU_OUT_SPLIT3  the split-bf16 operand image (rows, 3 hidden) bf16: fwd in LEFT order [hi | hi | lo] (fc2's left operand),
+ *                           bwd in WEIGHT order [hi | lo | hi] (both gradient GEMMs of fc1), as the gated passes write them
+ *   DIMSUM_GELU_OUT_PAIR    the pair [hi | lo] (rows, 2 hidden) bf16 (dimsum_gemm_ext_t.a_alias_rows / a_alias_weight_order / tn_pair_a_cols)
+ *   DIMSUM_GELU_OUT_F16S    the scaled-fp16 image (rows, hidden) float16 + inv_scale_ptr (rows) f32, hidden <= 5120. The row scale is the
+ *                           exact row maximum's power of two (dimsum_rows_f16s) -- or, fwd with ext->row_inv_ptr and ext->bound_ptr, the
+ *                           bound-derived one of DIMSUM_GEMM_EPI_GELU_F16 (same inputs -> the same scales and the same image as that epilogue)
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef enum { DIMSUM_GELU_OUT_F32 = 0, DIMSUM_GELU_OUT_SPLIT3 = 1, DIMSUM_GELU_OUT_PAIR = 2, DIMSUM_GELU_OUT_F16S = 3 } dimsum_gelu_out_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_gelu_ext_t) as the caller compiled it (see "Versioning" at the top) */
+    int32_t reserved;          /* 0 */
+    /* fwd, DIMSUM_GELU_OUT_F16S: both or none. row_inv (rows) f32 = the inverse row scales of the fc1 GEMM's left image, bound = {wl1, bmax}
+     * 2 f32 on the device: scale(2 (2^15 row_inv[m] wl1 + bmax)) instead of the row maximum (no reduction over the row). */
+    const void *row_inv_ptr, *bound_ptr;
+} dimsum_gelu_ext_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_gelu_params_t) as the caller compiled it; anything else -> DIMSUM_ERR_ABI */
+    int32_t out_image;         /* dimsum_gelu_out_t */
+    int64_t rows, hidden;
+    const void *x_ptr, *bias_ptr;
+    const void *dh_ptr;        /* bwd only: (rows, hidden) f32 contiguous */
+    void *out_ptr;             /* fwd: h, bwd: dx -- or their image */
+    void *inv_scale_ptr;       /* DIMSUM_GELU_OUT_F16S: (rows) f32 */
+    void *dbias_ptr;           /* bwd only, or NULL */
+    const dimsum_gelu_ext_t *ext;   /* NULL = none */
+} dimsum_gelu_params_t;
+
+int dimsum_gelu_fwd(const dimsum_gelu_params_t *p, void *stream);
+int dimsum_gelu_bwd(const dimsum_gelu_params_t *p, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * NT GEMM with a fused Linear epilogue: C (m, n) = A (m, k) . B (n, k)^T, 16-bit operands (bf16 or fp16 rows, k contiguous), fp32
  * accumulation on v_mfma_f32_16x16x32_*. Replaces the library GEMM behind F.linear(x, weight) for the large bias-free projections
  * of the denoiser (dimsum/mlp.py:66-70 w12 / w3, mamba_simple.py in_proj / out_proj, attention_fusion.py qkv / proj). The operands are
@@ -736,6 +777,7 @@ int dimsum_gated_gelu_bwd_f16s(const void *x12, const void *bias, const void *dh
  *                             C = the LEFT split-bf16 image (m, 3 F) of h = gelu_tanh(x1 + b1) * (x2 + b2), ldc in bf16 elements:
  *                             the fp32 x12 tensor of mlp.py:68 never exists
  *            GATED_GELU_F16 : same, C = fp16 (m, F) of h * out_scale
+ *            GELU_F16       : C = the scaled-fp16 image (m, n) of h = gelu_tanh(A B^T + bias) -- fc1 of the plain MLP (see the enum)
  *            F32_GATE_RESIDUAL : C = residual + gate[row / rows_per_batch] * (A B^T + bias): the residual tail of a block
  *                             ("x = x + gate * mlp(...)", models_dim.py:1107-1113) in the epilogue of its last Linear; residual (m, n) f32,
  *                             gate (m / rows_per_batch, n) f32 or NULL (= 1), rows_per_batch % 256 == 0, bias NULL or (n)
@@ -750,13 +792,20 @@ typedef enum {
                                        [0, conv_rows) hold silu(conv(A B^T) + conv_bias) along the columns, in sequences of conv_seq columns (256 % conv_seq == 0,
                                        n % conv_seq == 0: zero history at every sequence start), the other rows the plain product. conv_weight (conv_rows,
                                        conv_width 2..4) f32 row stride conv_weight_ld, conv_bias (conv_rows) f32 or NULL. conv_rows % 128 == 0. */
-    DIMSUM_GEMM_EPI_F16_QKV = 5     /* the qkv Linear of the attention fusion under the scaled-fp16 policy (attention_fusion.py:52-60, models_dim.py:1470):
+    DIMSUM_GEMM_EPI_F16_QKV = 5,    /* the qkv Linear of the attention fusion under the scaled-fp16 policy (attention_fusion.py:52-60, models_dim.py:1470):
                                        C (m, n = 3 C') fp16 = fp16((A B^T + bias) 2^s), scaled-fp16 operands (a / b_inv_scale_ptr required). Columns
                                        [0, qkv_q_cols) (q) take one power-of-two scale per ROW, the rest (k, v) one per BATCH ELEMENT (rows_per_batch rows,
                                        a multiple of 256), both from the bound |x W^T + b| <= 2^15 a_inv * wl1 + bmax with gate_bound_ptr = {wl1, bmax}:
                                            s_row = scale(2 (2^15 a_inv[row] wl1 + bmax)),  s_batch = scale(2 (2^15 max_t a_inv[b, t] wl1 + bmax))
                                        -- exactly what dimsum_xattn_fusion_fwd (precision 2, qkv_f16 = 1) assumes of its fp16 inputs: it recomputes the
                                        same scales from the same a_inv and bound. Halves the bytes between the two kernels (no fp32 qkv tensor). */
+    DIMSUM_GEMM_EPI_GELU_F16 = 7    /* fc1 of the plain MLP (dimsum/models_dit.py:124; use_gated_mlp=False) under the scaled-fp16 policy, inference:
+                                       C (m, n) fp16 = fp16(gelu_tanh(A B^T + bias) 2^s_row), scaled-fp16 operands (a / b_inv_scale_ptr required), not
+                                       paired, no column interleave. One power-of-two scale per row from the bound |gelu(x)| <= |x| <= 2^15 a_inv wl1 + bmax
+                                       with gate_bound_ptr = {wl1, bmax}: s_row = scale(2 (2^15 a_inv[row] wl1 + bmax)); its inverse goes to
+                                       h_inv_scale_ptr[row] (required) -- the a_inv_scale of fc2's GEMM. n % 8 == 0, ldc % 8 == 0. bf16 operands, unscaled
+                                       operands, a missing bound (no constant out_scale form), aliased operands, x12_ptr and c_image_pieces are not built:
+                                       DIMSUM_ERR_UNSUPPORTED (the caller runs F32 + dimsum_gelu_fwd). */
 } dimsum_gemm_epilogue_t;
 
 /* Everything beyond C = A B^T (+ bias): fused epilogue operands, operand-image read modes, timing, tuning. All 0 / NULL by default. */
@@ -776,7 +825,7 @@ typedef struct {
      * |x1|, |x2| <= max|a_m| * gate_bound[0] + gate_bound[1]  (gate_bound = {max_n sum_k |w_nk|, max |bias|}, 2 f32 on the device);
      * its inverse goes to h_inv_scale[m] -- the a_inv_scale of the w3 GEMM. NULL: out_scale for every row. */
     const void *gate_bound_ptr;
-    void *h_inv_scale_ptr;        /* (m) f32 */
+    void *h_inv_scale_ptr;        /* (m) f32; GELU_F16: required */
     /* F32_GATE_RESIDUAL */
     const void *residual_ptr, *gate_ptr;
     int64_t residual_ld, gate_ld;

@@ -841,6 +841,21 @@ def gen_transport_blur(_ns=None):
          "denoiser = tests/golden/procedural.py:toy_denoiser", **arrs)
 
 
+def gen_dit_keys(_ns=None):
+    """tests/golden/dit_keys.json: [[state_dict key, shape], ...] of the reference's DiT-S/2 (dimsum/models_dit.py, imported with the timm
+    stand-ins of tools/ref_shim.py: timm 0.9.12's PatchEmbed / Attention / Mlp parameter names), in state_dict order"""
+    import json
+    import models_dit          # (ref_shim.load() put the reference's dimsum/ on sys.path)
+    assert os.path.realpath(models_dit.__file__).startswith(os.path.realpath(ref_shim.REF)), models_dit.__file__
+    m = models_dit.DiT_models["DiT-S/2"]()
+    keys = [[k, list(v.shape)] for k, v in m.state_dict().items()]
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "dit_keys.json")
+    with open(path, "w") as f:
+        json.dump(keys, f, indent=0)
+        f.write("\n")
+    print(f"  dit_keys.json: {len(keys)} keys")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -859,7 +874,7 @@ def main():
         "transport": lambda: gen_transport(ns), "block1024": lambda: gen_block_1024(ns),
         "transport_blur": lambda: gen_transport_blur(ns),
         "block_linear_window": lambda: gen_block_linear_window(ns), "tiny_linear_window": lambda: gen_model_tiny_linear_window(ns),
-        "pe": lambda: gen_pe(ns), "einfft": lambda: gen_einfft(ns),
+        "pe": lambda: gen_pe(ns), "einfft": lambda: gen_einfft(ns), "dit_keys": lambda: gen_dit_keys(ns),
     }
     for k, fn in steps.items():
         if args.only is None or k in args.only:
