@@ -151,6 +151,30 @@ class ConvBwdParams(_Sized):
                 + [(n, vp) for n in ("dout_ptr", "dx_ptr", "dweight_ptr", "dbias_ptr")])
 
 
+class ConvUpdateParams(_Sized):
+    """dimsum_conv_update_params_t: one step of the causal conv1d on a carried (batch, dim, width) state, in place"""
+    _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "dim", "width", "silu_activation", "dtype")] + [("reserved", i32 * 2)]
+                + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "state_batch_stride", "state_c_stride", "state_w_stride",
+                                      "weight_c_stride", "weight_width_stride", "out_batch_stride", "out_c_stride")]
+                + [(n, vp) for n in ("x_ptr", "weight_ptr", "bias_ptr", "conv_state_ptr", "out_ptr")])
+
+
+class StateUpdateExt(_Sized):
+    """dimsum_state_update_ext_t: dt_proj formed inside the step, dt[b, d] = dt_w[d, :] . dt_x[b, :]"""
+    _fields_ = ([("struct_size", u32), ("dt_rank", i32), ("dt_w_ptr", vp), ("dt_x_ptr", vp)]
+                + [(n, i64) for n in ("dt_w_d_stride", "dt_w_r_stride", "dt_x_batch_stride", "dt_x_r_stride")])
+
+
+class StateUpdateParams(_Sized):
+    """dimsum_state_update_params_t: one step of the selective scan on a carried (batch, dim, dstate) state, in place"""
+    _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "dim", "dstate", "dt_softplus", "dtype", "state_dtype", "bc_dtype")]
+                + [(n, i64) for n in ("state_batch_stride", "state_d_stride", "state_n_stride", "x_batch_stride", "x_d_stride",
+                                      "dt_batch_stride", "dt_d_stride", "A_d_stride", "A_n_stride", "B_batch_stride", "B_n_stride",
+                                      "C_batch_stride", "C_n_stride", "z_batch_stride", "z_d_stride", "out_batch_stride", "out_d_stride")]
+                + [(n, vp) for n in ("state_ptr", "x_ptr", "dt_ptr", "A_ptr", "B_ptr", "C_ptr", "D_ptr", "z_ptr", "dt_bias_ptr", "out_ptr")]
+                + [("ext", C.POINTER(StateUpdateExt))])
+
+
 class NormParams(_Sized):
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("rows", "cols", "is_rms_norm", "x_dtype", "residual_dtype", "out_dtype")]
                 + [("eps", f32)]
@@ -240,7 +264,7 @@ EXPORTS = (
     "dimsum_fm_plan", "dimsum_fm_loss_fwd", "dimsum_fm_loss_bwd",
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
     "dimsum_einfft_dft", "dimsum_einfft_idft_real", "dimsum_einfft_mlp_fwd", "dimsum_einfft_mlp_bwd",
-    "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd",
+    "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd", "dimsum_causal_conv1d_update", "dimsum_selective_state_update",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
     "dimsum_gelu_fwd", "dimsum_gelu_bwd",
@@ -262,7 +286,8 @@ _SIGNATURES = (
         ("dimsum_fm_loss_fwd", FmLossParams), ("dimsum_fm_loss_bwd", FmLossParams), ("dimsum_pos_rope", PosRopeParams),
         ("dimsum_pos_cpe_fwd", PosCpeParams), ("dimsum_pos_cpe_bwd", PosCpeBwdParams), ("dimsum_einfft_dft", EinfftDftParams),
         ("dimsum_einfft_idft_real", EinfftDftParams), ("dimsum_einfft_mlp_fwd", EinfftMlpParams), ("dimsum_einfft_mlp_bwd", EinfftMlpBwdParams),
-        ("dimsum_gelu_fwd", GeluParams), ("dimsum_gelu_bwd", GeluParams))]
+        ("dimsum_gelu_fwd", GeluParams), ("dimsum_gelu_bwd", GeluParams), ("dimsum_causal_conv1d_update", ConvUpdateParams),
+        ("dimsum_selective_state_update", StateUpdateParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

@@ -282,6 +282,16 @@ def _make_mlp(dim, use_gated_mlp=True):
     return cls(in_features=dim, hidden_features=int(dim * 4), act_layer=_approx_gelu, drop=0)
 
 
+_NOT_CAUSAL = ("the DiM blocks reorder their tokens, mix them with Haar / DCT transforms and cross-attend between branches: none of that is "
+               "causal, so a block (and the model) has no token-by-token form. The recurrent form exists on the mixers themselves: "
+               "Mamba / CondMamba.allocate_inference_cache, forward(inference_params=...) and step (modules/mamba_simple.py)")
+
+
+def _refuse_cache(inference_params):
+    if inference_params is not None:
+        raise NotImplementedError("inference_params: " + _NOT_CAUSAL)
+
+
 def _modulation(seq, c):
     """seq(c) for an adaLN head `nn.Sequential(nn.SiLU(), nn.Linear)` (models_dim.py:1455, 1544): every block of a DiM applies the SAME SiLU to the
     same conditioning vector -- inside one DiM forward it is computed once (54 launches per DiM-L/2 forward otherwise), bit-identical"""
@@ -398,7 +408,7 @@ class _BlockBase(nn.Module):
         return cache[key]
 
     def allocate_inference_cache(self, *a, **k):
-        raise NotImplementedError("autoregressive decode caches are outside the denoiser hot path")
+        raise NotImplementedError("allocate_inference_cache: " + _NOT_CAUSAL)
 
 
 class DiMBlockRaw(_BlockBase):
@@ -422,6 +432,7 @@ class DiMBlockRaw(_BlockBase):
 
     def forward(self, hidden_states, residual=None, c=None, inference_params=None, out_split3=False):
         """out_split3 (inference, set by an enclosing combined block): the result as the split-bf16 operand image of the qkv Linear"""
+        _refuse_cache(inference_params)
         hidden_states, residual = self._prenorm(hidden_states, residual)
         table = self._table(hidden_states.shape[1], hidden_states.device, self._order)
         shift, scale, gate = _modulation(self.adaLN_modulation, c).chunk(3, dim=1)
@@ -454,6 +465,7 @@ class DiMBlock(_BlockBase):
         return so.block_order_table(H, self.reverse, self.transpose, self.scanning_continuity)
 
     def forward(self, hidden_states, residual=None, c=None, inference_params=None):
+        _refuse_cache(inference_params)
         hidden_states, residual = self._prenorm(hidden_states, residual)
         table = self._table(hidden_states.shape[1], hidden_states.device, self._order)
         shift, scale, gate, shift_mlp, scale_mlp, gate_mlp = _modulation(self.adaLN_modulation, c).chunk(6, dim=1)
@@ -501,6 +513,7 @@ class _FreqBlock(_BlockBase):
             self.mlp = _make_mlp(dim)
 
     def forward(self, hidden_states, residual=None, c=None, inference_params=None, out_split3=False):
+        _refuse_cache(inference_params)
         hidden_states, residual = self._prenorm(hidden_states, residual)
         table = self._table(hidden_states.shape[1], hidden_states.device, self._order)
         mods = _modulation(self.adaLN_modulation, c).chunk(3 if self.no_ffn else 6, dim=1)
@@ -602,6 +615,7 @@ class _CombinedBase(_BlockBase):
         self.mlp = _make_mlp(dim, use_gated_mlp)
 
     def forward(self, hidden_states, residual=None, c=None, inference_params=None):
+        _refuse_cache(inference_params)
         hidden_states, residual = self._prenorm(hidden_states, residual)
         if hidden_states.is_cuda and torch.is_grad_enabled() and hidden_states.requires_grad:
             x1, x2, hidden_states = _ForkHalves.apply(hidden_states)        # training: ONE consumer of hidden_states in the graph (see there)
@@ -912,6 +926,7 @@ class DiM(nn.Module):
 
     def forward(self, x, t, y=None, inference_params=None, **kwargs):
         """x: (N, C, H, W) latents, t: (N,) times, y: (N,) labels -> (N, out_channels, H, W)."""
+        _refuse_cache(inference_params)
         if t is None:
             t = torch.randint(0, 1000, (x.shape[0],), device=x.device)
         if y is None:

@@ -1,7 +1,16 @@
 """Mamba / CondMamba mixers -- same constructor arguments, parameter names (state_dict keys) and forward contract as
 mamba/mamba_ssm/modules/mamba_simple.py (Mamba :42-297, CondMamba :438-701), running on the HIP operators of
-dimsum_amd.ops. Only the diffusion path exists here: the autoregressive `step`/inference-cache API is decode-only and
-out of scope.
+dimsum_amd.ops, including the recurrent form (`allocate_inference_cache`, `forward(inference_params=...)`, `step`: :299-380, :703-784).
+
+The recurrent form: `forward(x, inference_params=p)` at `p.seqlen_offset == 0` processes a prompt on the fused path and leaves the layer's
+(conv_state, ssm_state) in `p.key_value_memory_dict[layer_idx]`; at `seqlen_offset > 0` it is one `step` (one token) on those states, which
+the two kernels of csrc/mixer_step.hip update in place. The caller advances `seqlen_offset`, as with the reference. One deliberate difference:
+a prompt shorter than d_conv leaves its tokens zero-padded on the left in conv_state (what a causal conv sees before the first token; upstream
+Mamba pads the same way) where the reference's `conv_state.copy_(x[:, :, -d_conv:])` (:258) raises a shape error. Refused, with the reason in
+the message: scan_type "v2" (the backward-direction twin has no causal recurrence), the zigzag scan types (a permuted sequence has no
+token-by-token order) and the operand-image input `x3` (inference images and a cache do not combine). Continuing a cached sequence with
+more than one token per call is not implemented (it would need a scan that starts from a carried state). The recurrent form is for inference:
+the cache is filled without autograd edges and the two step kernels have no backward.
 
 Differences that do not change results:
   * `cond_proj(c)` is numerically dead in the reference (its output only donates a buffer to the conv kernel,
@@ -15,9 +24,12 @@ import math
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
-from .. import gemm
+from .. import gemm, native
+from ..ops.causal_conv1d_interface import causal_conv1d_update
 from ..ops.selective_scan_interface import (mamba_inner_fn_cond, mamba_inner_fn_no_out_proj_cond)
+from ..ops.selective_state_update import selective_state_update
 
 _ZIGZAG = ("zigma", "sweep", "jpeg")
 
@@ -90,7 +102,8 @@ class _MambaBase(nn.Module):
         gathers its tokens itself"""
         return not (self._is_zigzag() and not getattr(self, "_zigzag_folded", False))
 
-    def _mix(self, hidden_states, cond, x3=None):
+    def _mix(self, hidden_states, cond, x3=None, states=None):
+        """states: the (conv_state, ssm_state) of an inference cache, filled from this call's sequence (forward(inference_params=...))"""
         bsz, L, _ = (hidden_states if x3 is None else x3).shape
         own_gather = self._is_zigzag() and not getattr(self, "_zigzag_folded", False)   # folded: the enclosing block's token
         if own_gather:                                                                  # tables already include the path
@@ -115,6 +128,11 @@ class _MambaBase(nn.Module):
             xz = gemm.matmul_wx(self.in_proj.weight, hidden_states.reshape(bsz * L, -1).t()).view(2 * self.d_inner, bsz, L).permute(1, 0, 2)
         if self.in_proj.bias is not None:
             xz = xz + self.in_proj.bias.to(xz.dtype).view(1, -1, 1)
+        if states is not None:
+            # the last d_conv inputs of the conv (mamba_simple.py:258), zero-padded on the left when the prompt is shorter (module docstring)
+            xin = xz[:, :self.d_inner]
+            with torch.no_grad():       # the cache is data for the next calls, never an autograd edge
+                states[0].copy_(xin[:, :, -self.d_conv:] if L >= self.d_conv else F.pad(xin, (self.d_conv - L, 0)))
         # recomputed on every call (two tiny launches): a cached copy could not see in-place parameter updates made through
         # `.data` (EMA, load_state_dict), which do not bump the version counter, and would be frozen into a captured hipGraph
         A = gemm.neg_exp(self.A_log)
@@ -131,29 +149,94 @@ class _MambaBase(nn.Module):
             return nn.functional.linear(y, self.out_proj.weight, self.out_proj.bias)
         out = mamba_inner_fn_cond(xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
                                   self.out_proj.weight, self.out_proj.bias, A, None, None, self.D.float(),
-                                  delta_bias=self.dt_proj.bias.float(), delta_softplus=True, init_states=cond, conv_done=conv_done)
+                                  delta_bias=self.dt_proj.bias.float(), delta_softplus=True, init_states=cond, conv_done=conv_done,
+                                  last_state=None if states is None else states[1])
         if own_gather:
             out = out.index_select(1, self.zigzag_paths_reverse[self.layer_idx])
         return out
 
-    def allocate_inference_cache(self, *a, **k):
-        raise NotImplementedError("autoregressive decode caches are outside the denoiser hot path")
+    # ---- the recurrent form (mamba_simple.py:299-380) ------------------------------------------------------------------------------------------
+    def _refuse_recurrent(self, x3=None):
+        if self.scan_type == "v2":
+            raise NotImplementedError('scan_type "v2" cannot run token by token: its backward-direction twin reads the sequence from its end, '
+                                      "which has no causal recurrence")
+        if self._is_zigzag():
+            raise NotImplementedError(f'scan_type "{self.scan_type}" cannot run token by token: the mixer scans a permuted sequence, which has '
+                                      "no token-by-token order")
+        if x3 is not None:
+            raise NotImplementedError("inference_params with an operand-image input (x3): inference images and a state cache do not combine; "
+                                      "pass hidden_states")
+
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+        """-> zeroed (conv_state (batch, d_inner, d_conv), ssm_state (batch, d_inner, d_state)), as mamba_simple.py:346-353"""
+        device = self.out_proj.weight.device
+        conv_dtype = self.conv1d.weight.dtype if dtype is None else dtype
+        ssm_dtype = self.dt_proj.weight.dtype if dtype is None else dtype
+        return (torch.zeros(batch_size, self.d_inner, self.d_conv, device=device, dtype=conv_dtype),
+                torch.zeros(batch_size, self.d_inner, self.d_state, device=device, dtype=ssm_dtype))
+
+    def _get_states_from_cache(self, inference_params, batch_size, initialize_states=False):
+        """this layer's (conv_state, ssm_state) in inference_params.key_value_memory_dict, created on first use (mamba_simple.py:355-380)"""
+        assert self.layer_idx is not None
+        if self.layer_idx not in inference_params.key_value_memory_dict:
+            conv_state = torch.zeros(batch_size, self.d_inner, self.d_conv, device=self.conv1d.weight.device, dtype=self.conv1d.weight.dtype)
+            ssm_state = torch.zeros(batch_size, self.d_inner, self.d_state, device=self.dt_proj.weight.device, dtype=self.dt_proj.weight.dtype)
+            inference_params.key_value_memory_dict[self.layer_idx] = (conv_state, ssm_state)
+        else:
+            conv_state, ssm_state = inference_params.key_value_memory_dict[self.layer_idx]
+            if initialize_states:
+                conv_state.zero_()
+                ssm_state.zero_()
+        return conv_state, ssm_state
+
+    def step(self, hidden_states, conv_state, ssm_state):
+        """one token: hidden_states (B, 1, d_model) -> (out (B, 1, d_model), conv_state, ssm_state), both states updated in place
+        (mamba_simple.py:299-344): in_proj -> causal_conv1d_update -> x_proj -> selective_state_update -> out_proj"""
+        self._refuse_recurrent()
+        assert hidden_states.shape[1] == 1, "Only support decoding with 1 token at a time for now"
+        xz = F.linear(hidden_states.squeeze(1), self.in_proj.weight, self.in_proj.bias)     # (B, 2 d_inner)
+        x, z = xz.chunk(2, dim=-1)                                                            # views: the kernels take the strides
+        cw = self.conv1d.weight
+        x = causal_conv1d_update(x, conv_state, cw.reshape(cw.shape[0], cw.shape[-1]), self.conv1d.bias, self.activation)
+        x_db = F.linear(x, self.x_proj.weight)                                                # (B, dt_rank + 2 d_state)
+        dt, B, C = torch.split(x_db, [self.dt_rank, self.d_state, self.d_state], dim=-1)
+        A = gemm.neg_exp(self.A_log)
+        if x.dtype == torch.float32 and self.dt_proj.weight.dtype == torch.float32:
+            # dt_proj inside the state update (csrc/mixer_step.hip): one GEMV launch less per step, which is bound by its launches
+            y = native.selective_state_update(ssm_state, x, None, A, B, C, self.D, z, self.dt_proj.bias, True, dt_proj=(self.dt_proj.weight, dt))
+        else:
+            dt = F.linear(dt, self.dt_proj.weight)                                            # without the bias: the kernel adds it (:324-325)
+            y = selective_state_update(ssm_state, x, dt, A, B, C, self.D, z=z, dt_bias=self.dt_proj.bias, dt_softplus=True)
+        out = F.linear(y, self.out_proj.weight, self.out_proj.bias)
+        return out.unsqueeze(1), conv_state, ssm_state
+
+    def _forward_cached(self, hidden_states, cond, inference_params, x3):
+        """forward(inference_params=...): a prompt at seqlen_offset 0 (fused path + the states it leaves behind), one step after it"""
+        self._refuse_recurrent(x3)
+        conv_state, ssm_state = self._get_states_from_cache(inference_params, hidden_states.shape[0])
+        if inference_params.seqlen_offset > 0:
+            return self.step(hidden_states, conv_state, ssm_state)[0]       # the states are updated in place
+        return self._mix(hidden_states, cond, states=(conv_state, ssm_state))
 
 
 class Mamba(_MambaBase):
     def forward(self, hidden_states, cond_emb=None, inference_params=None, x3=None):
         """hidden_states: (B, L, D) -> (B, L, D).  cond_emb: accepted and unused, as in the reference (mamba_simple.py:162): the DiM blocks
-        call every mixer as mixer(x, c).  x3: the input as a split-bf16 operand image instead (inference, gemm.py)."""
-        assert inference_params is None, "autoregressive decode is outside the denoiser hot path"
+        call every mixer as mixer(x, c).  x3: the input as a split-bf16 operand image instead (inference, gemm.py).
+        inference_params: a dimsum_amd.utils.InferenceParams -- the recurrent form, see the module docstring."""
+        if inference_params is not None:
+            return self._forward_cached(hidden_states, None, inference_params, x3)
         return self._mix(hidden_states, None, x3=x3)
 
 
 class CondMamba(_MambaBase):
     def forward(self, hidden_states, cond_emb=None, inference_params=None, x3=None):
         """hidden_states: (B, L, D), cond_emb: (B, d_cond) -> (B, L, D). See the module docstring about cond_proj.
-        x3: the input as a split-bf16 operand image instead (inference, gemm.py)."""
-        assert inference_params is None, "autoregressive decode is outside the denoiser hot path"
+        x3: the input as a split-bf16 operand image instead (inference, gemm.py).
+        inference_params: a dimsum_amd.utils.InferenceParams -- the recurrent form, see the module docstring."""
         cond = None
         if cond_emb is not None and torch.is_grad_enabled() and self.d_cond is not None:
             cond = self.cond_proj(cond_emb)       # (B, d_inner): graph edge only, never read by a kernel
+        if inference_params is not None:
+            return self._forward_cached(hidden_states, cond, inference_params, x3)
         return self._mix(hidden_states, cond, x3=x3)

@@ -316,6 +316,99 @@ def causal_conv1d_bwd(x, weight, bias, dout, dx, silu_activation):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the recurrent form: causal_conv1d_cuda.causal_conv1d_update (causal_conv1d.cpp:512-569) and the Triton
+# selective_state_update (ops/triton/selective_state_update.py:115-190). Both update their state IN PLACE; every operand
+# may be a strided view (csrc/mixer_step.hip addresses with one element stride per dim).
+# ---------------------------------------------------------------------------------------------------------------------
+def causal_conv1d_update(x, conv_state, weight, bias, silu_activation):
+    """-> out (batch, dim), like causal_conv1d_cuda.causal_conv1d_update: conv_state (batch, dim, width) is shifted left by one and x
+    appended, in place; out = act(sum_w conv_state * weight + bias). Weights are used in fp32."""
+    _gpu(x, conv_state, weight, bias)
+    _check(x.dim() == 2 and x.dtype in _DT, "causal_conv1d_update: x must be (batch, dim) in float32, float16 or bfloat16")
+    batch, dim = x.shape
+    _check(weight.dim() == 2 and weight.shape[0] == dim, "causal_conv1d_update: weight must be (dim, width)")
+    width = weight.shape[1]
+    _check(2 <= width <= 4, "causal_conv1d_update only supports width between 2 and 4")
+    _check(tuple(conv_state.shape) == (batch, dim, width) and conv_state.dtype == x.dtype,
+           "causal_conv1d_update: conv_state must be (batch, dim, width) of x's dtype")
+    if bias is not None:
+        _check(tuple(bias.shape) == (dim,), "causal_conv1d_update: bias must be (dim,)")
+    weight = weight.float()
+    bias = bias.float().contiguous() if bias is not None else None
+    out = torch.empty_like(x)
+    if x.numel() > 0:
+        P = _lib.ConvUpdateParams()
+        P.batch, P.dim, P.width, P.silu_activation, P.dtype = batch, dim, width, int(bool(silu_activation)), _DT[x.dtype]
+        P.x_batch_stride, P.x_c_stride = x.stride()
+        P.state_batch_stride, P.state_c_stride, P.state_w_stride = conv_state.stride()
+        P.weight_c_stride, P.weight_width_stride = weight.stride()
+        P.out_batch_stride, P.out_c_stride = out.stride()
+        P.x_ptr, P.weight_ptr, P.bias_ptr, P.conv_state_ptr, P.out_ptr = _ptr(x), _ptr(weight), _ptr(bias), _ptr(conv_state), _ptr(out)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dimsum_causal_conv1d_update(P, _stream(x)), "causal_conv1d_update")
+    return out
+
+
+def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False, dt_proj=None):
+    """-> out (batch, dim), like the reference's selective_state_update: state (batch, dim, dstate) <- state exp(dt' A) + dt' B x in place,
+    dt' = [softplus](dt + dt_bias); out = sum_n state C + D x, times silu(z). fp32 arithmetic; x, dt, z share one dtype, state and B / C
+    are float32 or that dtype.
+    `dt_proj=(dt_w (dim, R) float32, dt_x (batch, R))` (no reference counterpart): dt = dt_x @ dt_w^T is formed inside the kernel and `dt`
+    must be None -- one GEMV launch less per step."""
+    _gpu(state, x, dt, A, B, C, D, z, dt_bias)
+    _check(x.dim() == 2 and x.dtype in _DT, "selective_state_update: x must be (batch, dim) in float32, float16 or bfloat16")
+    batch, dim = x.shape
+    _check(state.dim() == 3 and tuple(state.shape[:2]) == (batch, dim), "selective_state_update: state must be (batch, dim, dstate)")
+    dstate = state.shape[2]
+    _check(1 <= dstate <= 256 or state.numel() == 0, "selective_state_update only supports state dimension between 1 and 256")
+    _check(state.dtype in (torch.float32, x.dtype), "selective_state_update: state must be float32 or of x's dtype")
+    _check(A.dtype == torch.float32 and tuple(A.shape) == (dim, dstate), "selective_state_update: A must be float32 (dim, dstate)")
+    _check(tuple(B.shape) == (batch, dstate) and tuple(C.shape) == (batch, dstate) and B.dtype == C.dtype and B.dtype in (torch.float32, x.dtype),
+           "selective_state_update: B and C must be (batch, dstate), both float32 or both of x's dtype")
+    if dt_proj is None:
+        _check(dt is not None and dt.shape == x.shape and dt.dtype == x.dtype, "selective_state_update: dt must be (batch, dim) of x's dtype")
+    else:
+        dt_w, dt_x = dt_proj
+        _gpu(dt_w, dt_x)
+        _check(dt is None, "selective_state_update: dt_proj = (dt_w, dt_x) replaces dt, which must be None")
+        _check(dt_w.dim() == 2 and dt_w.shape[0] == dim and dt_w.shape[1] >= 1 and dt_w.dtype == torch.float32
+               and tuple(dt_x.shape) == (batch, dt_w.shape[1]) and dt_x.dtype == x.dtype,
+               "selective_state_update: dt_proj must be (dt_w (dim, R) float32, dt_x (batch, R) of x's dtype), R >= 1")
+    for t, name in ((D, "D"), (dt_bias, "dt_bias")):
+        if t is not None:
+            _check(tuple(t.shape) == (dim,), f"selective_state_update: {name} must be (dim,)")
+    D = D.float().contiguous() if D is not None else None
+    dt_bias = dt_bias.float().contiguous() if dt_bias is not None else None
+    if z is not None:
+        _check(z.shape == x.shape and z.dtype == x.dtype, "selective_state_update: z must be (batch, dim) of x's dtype")
+    out = torch.empty_like(x)
+    if state.numel() > 0:
+        P = _lib.StateUpdateParams()
+        P.batch, P.dim, P.dstate, P.dt_softplus = batch, dim, dstate, int(bool(dt_softplus))
+        P.dtype, P.state_dtype, P.bc_dtype = _DT[x.dtype], _DT[state.dtype], _DT[B.dtype]
+        P.state_batch_stride, P.state_d_stride, P.state_n_stride = state.stride()
+        P.x_batch_stride, P.x_d_stride = x.stride()
+        P.A_d_stride, P.A_n_stride = A.stride()
+        P.B_batch_stride, P.B_n_stride = B.stride()
+        P.C_batch_stride, P.C_n_stride = C.stride()
+        P.out_batch_stride, P.out_d_stride = out.stride()
+        if z is not None:
+            P.z_batch_stride, P.z_d_stride = z.stride()
+        if dt_proj is None:
+            P.dt_batch_stride, P.dt_d_stride = dt.stride()
+        else:
+            E = _lib.attach_ext(P, _lib.StateUpdateExt)
+            E.dt_rank, E.dt_w_ptr, E.dt_x_ptr = dt_w.shape[1], _ptr(dt_w), _ptr(dt_x)
+            E.dt_w_d_stride, E.dt_w_r_stride = dt_w.stride()
+            E.dt_x_batch_stride, E.dt_x_r_stride = dt_x.stride()
+        P.state_ptr, P.x_ptr, P.dt_ptr, P.A_ptr, P.B_ptr, P.C_ptr = _ptr(state), _ptr(x), _ptr(dt), _ptr(A), _ptr(B), _ptr(C)
+        P.D_ptr, P.z_ptr, P.dt_bias_ptr, P.out_ptr = _ptr(D), _ptr(z), _ptr(dt_bias), _ptr(out)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dimsum_selective_state_update(P, _stream(x)), "selective_state_update")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # fused add + RMSNorm / LayerNorm   (Triton _layer_norm_fwd / _layer_norm_bwd, ops/triton/layernorm.py:120-364)
 # ---------------------------------------------------------------------------------------------------------------------
 def layer_norm_fwd(x, weight, bias, eps, residual=None, out_dtype=None, residual_dtype=None, is_rms_norm=False,

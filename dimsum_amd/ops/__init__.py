@@ -1,5 +1,5 @@
 """Operator API of the hot path (same names as the reference's Python op modules)."""
-from .causal_conv1d_interface import causal_conv1d_fn  # noqa: F401
+from .causal_conv1d_interface import causal_conv1d_fn, causal_conv1d_update, causal_conv1d_update_torch  # noqa: F401
 from .layernorm import RMSNorm, layer_norm_fn, rms_norm_fn  # noqa: F401
 from .selective_scan_interface import (  # noqa: F401
     bimamba_inner_fn,
@@ -9,3 +9,4 @@ from .selective_scan_interface import (  # noqa: F401
     mamba_inner_fn_no_out_proj_cond,
     selective_scan_fn,
 )
+from .selective_state_update import selective_state_update, selective_state_update_torch  # noqa: F401

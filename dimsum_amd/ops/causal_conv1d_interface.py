@@ -1,4 +1,4 @@
-"""causal_conv1d_fn -- same API as causal-conv1d/causal_conv1d/causal_conv1d_interface.py:8-45, on the HIP kernels."""
+"""causal_conv1d_fn / causal_conv1d_update -- same API as causal-conv1d/causal_conv1d/causal_conv1d_interface.py:8-45, :64-76, on the HIP kernels."""
 import torch
 
 from .. import native
@@ -30,5 +30,28 @@ def causal_conv1d_fn(x, weight, bias=None, activation=None):
     return CausalConv1dFn.apply(x, weight, bias, activation)
 
 
-def causal_conv1d_update(*args, **kwargs):
-    raise NotImplementedError("causal_conv1d_update (single-token decode) is outside the denoiser hot path")
+def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None):
+    """one token of the causal conv1d on a carried state (causal_conv1d_interface.py:64-76), on the HIP kernel.
+    x: (batch, dim), conv_state: (batch, dim, width) -- shifted left by one and x appended, IN PLACE --, weight: (dim, width), bias: (dim,)
+    -> out (batch, dim). Every operand may be a strided view."""
+    if activation not in (None, "silu", "swish"):
+        raise NotImplementedError("activation must be None, silu, or swish")
+    return native.causal_conv1d_update(x, conv_state, weight, bias, activation in ("silu", "swish"))
+
+
+def causal_conv1d_update_torch(x, conv_state, weight, bias=None, activation=None):
+    """The step of the causal conv1d written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer):
+    the window a causal conv of width W sees at the new token is the last W - 1 columns of the state followed by x; the output is the dot
+    product of that window with the taps, plus bias, through SiLU if asked. conv_state receives the window. What the tests compare the
+    kernel with; never a fallback: nothing in the package calls it."""
+    silu = {None: False, "silu": True, "swish": True}.get(activation)
+    if silu is None:
+        raise NotImplementedError(f"causal_conv1d_update_torch: activation {activation!r} (None, 'silu' or 'swish')")
+    width = weight.shape[-1]
+    window = torch.cat([conv_state[..., 1:], x.unsqueeze(-1)], dim=-1)                  # (batch, dim, width)
+    assert window.shape == conv_state.shape and weight.shape == (x.shape[1], width)
+    pre = (window * weight.unsqueeze(0)).sum(-1)
+    if bias is not None:
+        pre = pre + bias.unsqueeze(0)
+    conv_state.copy_(window)
+    return (pre * torch.sigmoid(pre) if silu else pre).to(x.dtype)

@@ -118,11 +118,14 @@ class _MambaInner(torch.autograd.Function):
     @custom_fwd(device_type="cuda")
     def forward(ctx, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                 A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus, init_states, has_out_proj, checkpoint_lvl,
-                need_ckpt=False, conv_done=False, f16s_train=False):
+                need_ckpt=False, conv_done=False, f16s_train=False, last_state=None):
         # conv_done (inference extra, not in the reference's signature): xz[:, :d_inner] already holds the causal conv1d + SiLU of the in_proj
         # output (the GEMM's epilogue formed it, modules/mamba_simple.py) -- the conv kernel is skipped
         # f16s_train (training extra, decided by the caller like need_ckpt: grad mode is off in here): out_proj's forward, input-gradient and
         # weight-gradient GEMMs as ONE fp16 product per element over scaled-fp16 images (gemm.py, policy "f16s")
+        # last_state (recurrent-form extra): a (batch, d_inner, dstate) buffer that receives the scan's state after the last step, as
+        # selective_scan_fn(return_last_state=True) returns it (:39) -- the ssm_state a prompt leaves in an inference cache. The launch keeps the
+        # reference interface's `x` store then.
         assert checkpoint_lvl in (0, 1)
         assert not (conv_done and need_ckpt), "conv_done is an inference extra"
         if A.is_complex():
@@ -152,7 +155,7 @@ class _MambaInner(torch.autograd.Function):
         else:
             conv_out = native.causal_conv1d_fwd(x, conv_w, conv_b, True)
         bsz, d_inner = conv_out.shape[0], conv_out.shape[1]
-        keep_stores = need_ckpt or os.environ.get("DIMSUM_SCAN_INFER_STORES", "0") == "1"      # (see `keep` below)
+        keep_stores = need_ckpt or last_state is not None or os.environ.get("DIMSUM_SCAN_INFER_STORES", "0") == "1"      # (see `keep` below)
         # layouts chosen like the reference (:622-626): the GEMM writes delta d-major so that it needs no transpose
         conv_rows = _rows(conv_out)
         if not need_ckpt and B_proj_bias is None and C_proj_bias is None and conv_rows.stride(1) == 1:
@@ -224,6 +227,8 @@ class _MambaInner(torch.autograd.Function):
                                                               need_out=keep, need_x=keep, need_ckpt=need, **({"out_z_planes": True} if planes else {}),
                                                               **({"out_z_f16": True} if z16 else {}),
                                                               **({"dt_proj": (delta_proj_weight, x_dbl_t[:R])} if delta is None else {}))
+        if last_state is not None:
+            last_state.copy_(scan_x[:, :, -1, 1::2])
         if z16:
             return gemm.out_proj_f16(out_z[0], out_z[1], out_proj_weight).view(bsz, L, out_proj_weight.shape[0])
         if conv16:
@@ -318,7 +323,7 @@ class _MambaInner(torch.autograd.Function):
             _, dconv_w, dconv_b = native.causal_conv1d_bwd(x, conv_w, conv_b, dconv_out, dx, True)
             return (dxz, dconv_w.unsqueeze(1), dconv_b if has_conv_b else None, dx_proj_weight, ddelta_proj_weight,
                     dout_proj_weight, dout_proj_bias, dA, None, None, dD if has_D else None,
-                    ddelta_bias if has_dbias else None, None, None, None, None, None, None, None, None, None)
+                    ddelta_bias if has_dbias else None, None, None, None, None, None, None, None, None, None, None)
         dBf = dB.squeeze(1).permute(0, 2, 1).reshape(bsz * L, N)                                        # "b 1 n l -> (b l) n"
         dCf = dC.squeeze(1).permute(0, 2, 1).reshape(bsz * L, N)
         dB_proj_bias = dBf.sum(0) if has_Bb else None
@@ -335,7 +340,7 @@ class _MambaInner(torch.autograd.Function):
         _, dconv_w, dconv_b = native.causal_conv1d_bwd(x, conv_w, conv_b, dconv_out, dx, True)
         return (dxz, dconv_w.unsqueeze(1), dconv_b if has_conv_b else None, dx_proj_weight, ddelta_proj_weight,
                 dout_proj_weight, dout_proj_bias, dA, None, None, dD if has_D else None,
-                ddelta_bias if has_dbias else None, dB_proj_bias, dC_proj_bias, None, None, None, None, None, None, None)
+                ddelta_bias if has_dbias else None, dB_proj_bias, dC_proj_bias, None, None, None, None, None, None, None, None)
 
 
 def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A,
@@ -349,12 +354,12 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
 
 def mamba_inner_fn_cond(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                         A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None,
-                        delta_softplus=True, init_states=None, conv_done=False):
+                        delta_softplus=True, init_states=None, conv_done=False, last_state=None):
     wb = _will_backprop(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias,
                         B_proj_bias, C_proj_bias, init_states)
     return _MambaInner.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight,
                              out_proj_bias, A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus, init_states,
-                             True, _checkpoint_lvl(), wb, conv_done, _f16s_train(xz, out_proj_weight, wb))
+                             True, _checkpoint_lvl(), wb, conv_done, _f16s_train(xz, out_proj_weight, wb), last_state)
 
 
 def mamba_inner_fn_no_out_proj(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, B=None, C=None,

@@ -1,5 +1,21 @@
 """small host utilities"""
+import dataclasses
+
 import torch
+
+
+@dataclasses.dataclass
+class InferenceParams:
+    """what a caller hands to Mamba / CondMamba.forward(inference_params=...) to run a sequence token by token: the per-layer
+    (conv_state, ssm_state) caches keyed by layer_idx and how many tokens they have seen. Same fields and `reset` as the reference's
+    (mamba/mamba_ssm/utils/generation.py:12-28), minus what only its generation loop reads."""
+    max_seqlen: int
+    max_batch_size: int
+    seqlen_offset: int = 0
+    key_value_memory_dict: dict = dataclasses.field(default_factory=dict)
+
+    def reset(self, max_seqlen, max_batch_size):
+        self.max_seqlen, self.max_batch_size, self.seqlen_offset = max_seqlen, max_batch_size, 0
 
 
 @torch.no_grad()

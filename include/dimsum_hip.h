@@ -13,6 +13,8 @@
  *   dimsum_einfft_dft / _idft_real / _mlp_fwd / _mlp_bwd <- EinFFT.forward (+ autograd)   dimsum/models_dim.py:713-775
  *   dimsum_causal_conv1d_fwd   <- causal_conv1d_cuda.causal_conv1d_fwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:221-336
  *   dimsum_causal_conv1d_bwd   <- causal_conv1d_cuda.causal_conv1d_bwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:338-509
+ *   dimsum_causal_conv1d_update <- causal_conv1d_cuda.causal_conv1d_update        causal-conv1d/csrc/causal_conv1d.cpp:512-569
+ *   dimsum_selective_state_update <- selective_state_update (Triton)              mamba/mamba_ssm/ops/triton/selective_state_update.py:115-190
  *   dimsum_norm_fwd / _bwd     <- _layer_norm_fwd / _layer_norm_bwd (Triton)     mamba/mamba_ssm/ops/triton/layernorm.py:120-364
  *   dimsum_token_transform     <- einops/flip/local_scan/DWT/DCT chains          dimsum/models_dim.py:572-604,656-705,876-928,1496-1524
  *   dimsum_xattn_fusion_fwd/_bwd <- F.scaled_dot_product_attention x2 (+ autograd)  dimsum/attention_fusion.py:44-75
@@ -489,6 +491,69 @@ typedef struct {
 
 int dimsum_causal_conv1d_fwd(const dimsum_conv_params_t *p, void *stream);
 int dimsum_causal_conv1d_bwd(const dimsum_conv_bwd_params_t *p, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The recurrent (token by token) form of the mixer: one step of the causal conv1d and one step of the selective scan on
+ * carried states, both updated IN PLACE. One work-item owns one (batch, channel) row; every dim of every tensor has its
+ * own ELEMENT stride (cache slices, the two halves of a (batch, 2 dim) in_proj output and transposed caches are views).
+ *
+ * dimsum_causal_conv1d_update  <- causal_conv1d_cuda.causal_conv1d_update   causal-conv1d/csrc/causal_conv1d.cpp:512-569
+ *   (semantics of causal_conv1d_update_ref, causal_conv1d_interface.py:79-100)
+ *   conv_state (batch, dim, width) <- its last width - 1 columns, then x;   out = act(sum_w conv_state[.., w] weight[d, w] + bias[d])
+ *   x, out (batch, dim) and conv_state share `dtype`; weight (dim, width), bias (dim) f32. The state written back holds the
+ *   input values themselves (moved, never converted). width 2..4, else DIMSUM_ERR_SHAPE; batch or dim < 1: DIMSUM_ERR_SHAPE.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_conv_update_params_t) */
+    int32_t batch, dim, width;
+    int32_t silu_activation;  /* bool */
+    int32_t dtype;            /* of x / conv_state / out */
+    int32_t reserved[2];      /* 0 */
+    int64_t x_batch_stride, x_c_stride;
+    int64_t state_batch_stride, state_c_stride, state_w_stride;
+    int64_t weight_c_stride, weight_width_stride;
+    int64_t out_batch_stride, out_c_stride;
+    const void *x_ptr, *weight_ptr, *bias_ptr;   /* bias_ptr may be NULL */
+    void *conv_state_ptr, *out_ptr;
+} dimsum_conv_update_params_t;
+
+int dimsum_causal_conv1d_update(const dimsum_conv_update_params_t *p, void *stream);
+
+/* dimsum_selective_state_update  <- selective_state_update (Triton, no ROCm path)   mamba/mamba_ssm/ops/triton/selective_state_update.py:115-190
+ *   (semantics of selective_state_update_ref, :193-228), f32 arithmetic throughout:
+ *   dt' = dt + dt_bias, softplus(dt') when dt_softplus (threshold 20, as in the scan kernels)
+ *   state (batch, dim, dstate) <- state exp(dt' A) + dt' B x;   out = sum_n state C + D x, times silu(z) when z is given
+ *   x, dt, z, out (batch, dim): `dtype`. state: `state_dtype`, B, C (batch, dstate): `bc_dtype` -- each DIMSUM_F32 or == dtype.
+ *   A (dim, dstate), D, dt_bias (dim): f32; D, z, dt_bias may be NULL. dstate 1..256, else DIMSUM_ERR_SHAPE.
+ * The extension fuses dt_proj into the step (no reference counterpart as a kernel: Mamba.step computes F.linear(dt, dt_proj.weight) as a
+ * GEMV launch of its own): with dt_w_ptr set, dt[b, d] = sum_r dt_w[d, r] dt_x[b, r] is formed here and dt_ptr is not read (may be NULL). */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_state_update_ext_t) as the caller compiled it (see "Versioning" at the top) */
+    int32_t dt_rank;          /* >= 1 when dt_w_ptr is set */
+    const void *dt_w_ptr;     /* (dim, dt_rank) f32 */
+    const void *dt_x_ptr;     /* (batch, dt_rank), `dtype` */
+    int64_t dt_w_d_stride, dt_w_r_stride, dt_x_batch_stride, dt_x_r_stride;
+} dimsum_state_update_ext_t;
+
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_state_update_params_t) as the caller compiled it; anything else -> DIMSUM_ERR_ABI */
+    int32_t batch, dim, dstate;
+    int32_t dt_softplus;      /* bool */
+    int32_t dtype, state_dtype, bc_dtype;
+    int64_t state_batch_stride, state_d_stride, state_n_stride;
+    int64_t x_batch_stride, x_d_stride;
+    int64_t dt_batch_stride, dt_d_stride;
+    int64_t A_d_stride, A_n_stride;
+    int64_t B_batch_stride, B_n_stride, C_batch_stride, C_n_stride;
+    int64_t z_batch_stride, z_d_stride;
+    int64_t out_batch_stride, out_d_stride;
+    void *state_ptr;
+    const void *x_ptr, *dt_ptr, *A_ptr, *B_ptr, *C_ptr, *D_ptr, *z_ptr, *dt_bias_ptr;
+    void *out_ptr;
+    const dimsum_state_update_ext_t *ext;   /* NULL = the reference interface */
+} dimsum_state_update_params_t;
+
+int dimsum_selective_state_update(const dimsum_state_update_params_t *p, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused residual-add + RMSNorm / LayerNorm over rows (M, N), f32 statistics.

@@ -342,6 +342,82 @@ def gen_mixer(ns):
              **{"g_" + k: v.grad for k, v in m.named_parameters() if v.grad is not None})
 
 
+STEP_CONV_CASES = ((2, 5, 2), (2, 5, 3), (3, 65, 4))              # (B, D, W)
+STEP_SSU_CASES = ((2, 5, 1), (2, 65, 16), (1, 7, 64))             # (B, D, N)
+STEP_MIXER = dict(d_model=32, d_state=16, d_conv=4, expand=2)     # B = 2, 12 tokens: 5 as a prompt, 7 steps
+STEP_B, STEP_L, STEP_PREFILL = 2, 12, 5
+
+
+def gen_step(ns):
+    """the recurrent form: causal_conv1d_update_ref (causal_conv1d_interface.py:79-100), selective_state_update_ref
+    (ops/triton/selective_state_update.py:193-228), Mamba / CondMamba forward(inference_params=...) + step (mamba_simple.py:162-380, :562-784)"""
+    import dataclasses
+    from mamba_ssm.ops.triton.selective_state_update import selective_state_update_ref as ssu_ref      # (plain torch + einops)
+    arrs = {}
+    for B, D, W in STEP_CONV_CASES:
+        for has_bias in (False, True):
+            for silu in (False, True):
+                torch.manual_seed(0)        # distributions of causal-conv1d/tests/test_causal_conv1d.py:101-108
+                x, state, w = torch.randn(B, D), torch.randn(B, D, W), torch.randn(D, W)
+                b = torch.randn(D) if has_bias else None
+                tag = f"conv_B{B}D{D}W{W}_b{int(has_bias)}s{int(silu)}_"
+                arrs.update({tag + "x": x, tag + "state_in": state.clone(), tag + "weight": w})
+                if has_bias:
+                    arrs[tag + "bias"] = b
+                arrs[tag + "out"] = ns.cci.causal_conv1d_update_ref(x, state, w, b, "silu" if silu else None)
+                arrs[tag + "state_out"] = state
+    for B, D, N in STEP_SSU_CASES:
+        for has_z in (False, True):
+            for has_D in (False, True):
+                torch.manual_seed(0)        # distributions of mamba/tests/ops/triton/test_selective_state_update.py:24-36
+                state, x, dt = torch.randn(B, D, N), torch.randn(B, D), torch.randn(B, D)
+                dt_bias, A = torch.rand(D) - 4.0, -torch.rand(D, N) - 1.0
+                Bm, Cm, Dv, z = torch.randn(B, N), torch.randn(B, N), torch.randn(D), torch.randn(B, D)
+                tag = f"ssu_B{B}D{D}N{N}_z{int(has_z)}d{int(has_D)}_"
+                arrs.update({tag + "state_in": state.clone(), tag + "x": x, tag + "dt": dt, tag + "dt_bias": dt_bias, tag + "A": A,
+                             tag + "B": Bm, tag + "C": Cm})
+                if has_D:
+                    arrs[tag + "D"] = Dv
+                if has_z:
+                    arrs[tag + "z"] = z
+                arrs[tag + "out"] = ssu_ref(state, x, dt, A, Bm, Cm, D=Dv if has_D else None, z=z if has_z else None, dt_bias=dt_bias,
+                                            dt_softplus=True)
+                arrs[tag + "state_out"] = state
+
+    @dataclasses.dataclass
+    class Params:       # the fields of mamba_ssm/utils/generation.py:12-21 that the mixers read
+        max_seqlen: int
+        max_batch_size: int
+        seqlen_offset: int = 0
+        key_value_memory_dict: dict = dataclasses.field(default_factory=dict)
+
+    # the step's two operators as their own *_ref functions (the module's inline fallbacks, :306-312 / :329-337, are the same arithmetic)
+    ns.ms.causal_conv1d_update = ns.cci.causal_conv1d_update_ref
+    ns.ms.selective_state_update = ssu_ref
+    for cls in ("Mamba", "CondMamba"):
+        kw = dict(STEP_MIXER, layer_idx=3, scan_type="none", **({"d_cond": 48} if cls == "CondMamba" else {}))
+        m = getattr(ns.ms, cls)(**kw)
+        procedural_fill(m, seed=7)
+        m.use_fast_path = False
+        x = T(seeded((STEP_B, STEP_L, STEP_MIXER["d_model"]), 51))
+        c = T(seeded((STEP_B, 48), 52))
+        args = (c,) if cls == "CondMamba" else ()
+        with torch.no_grad():
+            y_full = m(x, *args)
+            p = Params(max_seqlen=STEP_L, max_batch_size=STEP_B)
+            ys = [m(x[:, :STEP_PREFILL], *args, inference_params=p)]
+            for t in range(STEP_PREFILL, STEP_L):
+                p.seqlen_offset = t
+                ys.append(m(x[:, t:t + 1], *args, inference_params=p))
+            conv_state, ssm_state = p.key_value_memory_dict[3]
+        arrs.update({f"{cls}_x": x, f"{cls}_c": c, f"{cls}_y_full": y_full, f"{cls}_y_steps": torch.cat(ys, 1),
+                     f"{cls}_conv_state": conv_state, f"{cls}_ssm_state": ssm_state})
+    save("mixer_step", "causal_conv1d_update_ref (causal-conv1d/causal_conv1d/causal_conv1d_interface.py:79-100); selective_state_update_ref "
+         "(mamba/mamba_ssm/ops/triton/selective_state_update.py:193-228), distributions of the reference tests; Mamba / CondMamba slow path "
+         "(mamba/mamba_ssm/modules/mamba_simple.py): one forward of 12 tokens, and forward(inference_params) over 5 tokens + 7 steps with the "
+         "final conv / SSM states; procedural weights seed 7", **arrs)
+
+
 def _mk_block(ns, hidden, reverse, transpose, cont=False, fourier=False):
     md = ns.models_dim
     blk = md.create_block(hidden, norm_epsilon=1e-5, rms_norm=True, residual_in_fp32=True, fused_add_norm=True,
@@ -874,7 +950,7 @@ def main():
         "transport": lambda: gen_transport(ns), "block1024": lambda: gen_block_1024(ns),
         "transport_blur": lambda: gen_transport_blur(ns),
         "block_linear_window": lambda: gen_block_linear_window(ns), "tiny_linear_window": lambda: gen_model_tiny_linear_window(ns),
-        "pe": lambda: gen_pe(ns), "einfft": lambda: gen_einfft(ns), "dit_keys": lambda: gen_dit_keys(ns),
+        "pe": lambda: gen_pe(ns), "einfft": lambda: gen_einfft(ns), "dit_keys": lambda: gen_dit_keys(ns), "step": lambda: gen_step(ns),
     }
     for k, fn in steps.items():
         if args.only is None or k in args.only:
