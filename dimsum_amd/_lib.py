@@ -72,6 +72,30 @@ class SsmBidirBwdParams(_Sized):
                 ("dA_b_ptr", vp), ("dA_b_d_stride", i64), ("dA_b_dstate_stride", i64)]
 
 
+class SsmGeneralParams(_Sized):
+    """dimsum_ssm_general_params_t: the general scan -- any dstate in 1..256, constant B / C, complex A"""
+    _fields_ = ([("struct_size", u32)]
+                + [(n, i32) for n in ("batch", "dim", "seqlen", "dstate", "n_groups", "n_chunks", "delta_softplus", "dtype", "is_variable_B",
+                                      "is_variable_C", "is_complex", "reserved")]
+                + [(n, i64) for n in ("A_d_stride", "A_dstate_stride", "B_batch_stride", "B_d_stride", "B_group_stride", "B_dstate_stride",
+                                      "C_batch_stride", "C_d_stride", "C_group_stride", "C_dstate_stride", "u_batch_stride", "u_d_stride",
+                                      "delta_batch_stride", "delta_d_stride", "z_batch_stride", "z_d_stride", "out_batch_stride", "out_d_stride",
+                                      "out_z_batch_stride", "out_z_d_stride")]
+                + [(n, vp) for n in ("A_ptr", "B_ptr", "C_ptr", "D_ptr", "u_ptr", "delta_ptr", "delta_bias_ptr", "z_ptr", "out_ptr", "x_ptr",
+                                     "out_z_ptr")])
+
+
+class SsmGeneralBwdParams(_Sized):
+    """dimsum_ssm_general_bwd_params_t"""
+    _fields_ = ([("struct_size", u32), ("reserved", u32), ("fwd", SsmGeneralParams)]
+                + [(n, i64) for n in ("dout_batch_stride", "dout_d_stride", "dA_d_stride", "dA_dstate_stride", "dB_batch_stride", "dB_d_stride",
+                                      "dB_group_stride", "dB_dstate_stride", "dC_batch_stride", "dC_d_stride", "dC_group_stride", "dC_dstate_stride",
+                                      "du_batch_stride", "du_d_stride", "dz_batch_stride", "dz_d_stride", "ddelta_batch_stride", "ddelta_d_stride")]
+                + [(n, vp) for n in ("dout_ptr", "dA_ptr", "dB_ptr", "dC_ptr", "dD_ptr", "du_ptr", "dz_ptr", "ddelta_ptr", "ddelta_bias_ptr",
+                                     "workspace_ptr")]
+                + [("workspace_bytes", i64)])
+
+
 class OptimParams(_Sized):
     """dimsum_optim_params_t: device tables of the tensor list + hyper-parameters of one clip / AdamW / EMA step"""
     _fields_ = ([("struct_size", u32), ("n_tensors", i32), ("n_chunks", i32), ("n_partials", i32)]
@@ -260,6 +284,7 @@ EXPORTS = (
     "dimsum_event_create", "dimsum_event_destroy", "dimsum_event_elapsed_ms",
     "dimsum_ssm_scan_fwd", "dimsum_ssm_scan_bwd", "dimsum_ssm_scan_bwd_workspace_bytes", "dimsum_ssm_scan_fwd_variant",
     "dimsum_ssm_scan_bidir_fwd", "dimsum_ssm_scan_bidir_bwd", "dimsum_ssm_scan_bidir_fwd_variant",
+    "dimsum_ssm_scan_general_fwd", "dimsum_ssm_scan_general_bwd", "dimsum_ssm_scan_general_bwd_workspace_bytes",
     "dimsum_optim_grad_sumsq", "dimsum_optim_adamw_ema_step", "dimsum_optim_write_ptrs",
     "dimsum_fm_plan", "dimsum_fm_loss_fwd", "dimsum_fm_loss_bwd",
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
@@ -287,7 +312,8 @@ _SIGNATURES = (
         ("dimsum_pos_cpe_fwd", PosCpeParams), ("dimsum_pos_cpe_bwd", PosCpeBwdParams), ("dimsum_einfft_dft", EinfftDftParams),
         ("dimsum_einfft_idft_real", EinfftDftParams), ("dimsum_einfft_mlp_fwd", EinfftMlpParams), ("dimsum_einfft_mlp_bwd", EinfftMlpBwdParams),
         ("dimsum_gelu_fwd", GeluParams), ("dimsum_gelu_bwd", GeluParams), ("dimsum_causal_conv1d_update", ConvUpdateParams),
-        ("dimsum_selective_state_update", StateUpdateParams))]
+        ("dimsum_selective_state_update", StateUpdateParams), ("dimsum_ssm_scan_general_fwd", SsmGeneralParams),
+        ("dimsum_ssm_scan_general_bwd", SsmGeneralBwdParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),
@@ -303,6 +329,7 @@ _SIGNATURES = (
        ("dimsum_rows_f16s", C.c_int, [vp, i64, i64, i64, vp, i64, vp, vp, vp]),
        ("dimsum_rows_f16s_multi", C.c_int, [_P(F16sJob), i32, vp]),
        ("dimsum_ssm_scan_bwd_workspace_bytes", i64, [i32] * 5),
+       ("dimsum_ssm_scan_general_bwd_workspace_bytes", i64, [i32] * 6),
        ("dimsum_ssm_scan_fwd_variant", C.c_int, [_P(SsmParams)]),
        ("dimsum_ssm_scan_bidir_fwd_variant", C.c_int, [_P(SsmBidirParams)])])
 

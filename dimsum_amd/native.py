@@ -599,6 +599,175 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, out, dz, de
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the general selective scan (csrc/ssm_scan_general.hip): any dstate in 1..256, constant B / C, complex A
+# ---------------------------------------------------------------------------------------------------------------------
+SCAN_TUNED_DSTATES = (4, 8, 16, 32)      # what ssm_dispatch (csrc/ssm_scan_host.hpp) instantiates the tuned kernels for
+_scan_force_general = False
+
+
+@contextlib.contextmanager
+def scan_force_general(on=True):
+    """tests / measurement: the calls made inside take the general kernels even where a tuned kernel serves them (host-side, not thread-safe)"""
+    global _scan_force_general
+    old, _scan_force_general = _scan_force_general, bool(on)
+    try:
+        yield
+    finally:
+        _scan_force_general = old
+
+
+def scan_general_forced():
+    """the scan_force_general setting"""
+    return _scan_force_general
+
+
+def scan_takes_general_path(dstate, is_complex=False, is_variable_B=True, is_variable_C=True, force=False):
+    """THE routing rule of selective_scan_fn / mamba_inner_fn, a pure function of its arguments (callers pass force=scan_general_forced()):
+    the general kernels serve what the tuned ones are not built for -- complex A, constant B or C, a dstate outside SCAN_TUNED_DSTATES.
+    Every call the tuned kernels serve keeps going to them."""
+    return bool(force) or bool(is_complex) or not is_variable_B or not is_variable_C or int(dstate) not in SCAN_TUNED_DSTATES
+
+
+def _check_ssm_general(u, delta, A, B, C, D, z, delta_bias):
+    """-> (is_complex, is_variable_B, is_variable_C, n_groups). Dtypes, shapes and strides first (no GPU needed to be refused), the device last."""
+    _check(u.dim() == 3 and u.dtype in _DT, "selective_scan_general: u must be (batch, dim, seqlen) float32, float16 or bfloat16")
+    batch, dim, seqlen = u.shape
+    cplx = A.is_complex()
+    wdt = torch.complex64 if cplx else torch.float32
+    _check(A.dim() == 2 and A.dtype == wdt, "selective_scan_general: A must be a float32 or complex64 (dim, dstate) matrix")
+    dstate = A.shape[1]
+    _check(1 <= dstate <= 256, "selective_scan only supports state dimension <= 256")
+    _check(A.shape[0] == dim, "selective_scan_general: A must have shape (dim, dstate)")
+    _check(delta.dtype == u.dtype and tuple(delta.shape) == (batch, dim, seqlen), "selective_scan_general: delta must be like u")
+    var, groups = [], 1
+    for t, name in ((B, "B"), (C, "C")):
+        v = t.dim() >= 3
+        var.append(v)
+        if v:
+            _check(t.dim() == 4 and t.dtype == u.dtype and t.shape[0] == batch and t.shape[2] == dstate and t.shape[3] == seqlen * (2 if cplx else 1),
+                   f"selective_scan_general: input-dependent {name} must be (batch, groups, dstate, seqlen) of u's dtype (2 * seqlen with complex A)")
+            _check(t.stride(-1) == 1 or t.shape[-1] == 1, f"selective_scan_general: {name}.stride(-1) must be 1")
+        else:
+            _check(t.dtype == wdt and tuple(t.shape) == (dim, dstate), f"selective_scan_general: constant {name} must be (dim, dstate) of A's dtype")
+    if var[0] and var[1]:
+        _check(B.shape[1] == C.shape[1], "selective_scan_general: B and C must have the same number of groups")
+    if var[0] or var[1]:
+        groups = (B if var[0] else C).shape[1]
+        _check(groups >= 1 and dim % groups == 0, "selective_scan_general: dim must be a multiple of the number of groups")
+    for t, name in ((u, "u"), (delta, "delta"), (z, "z")):
+        if t is not None:
+            _check(t.stride(-1) == 1 or t.shape[-1] == 1, f"selective_scan_general: {name}.stride(-1) must be 1")
+    if z is not None:
+        _check(z.dtype == u.dtype and tuple(z.shape) == (batch, dim, seqlen), "selective_scan_general: bad z")
+    for t, name in ((D, "D"), (delta_bias, "delta_bias")):
+        if t is not None:
+            _check(t.dtype == torch.float32 and tuple(t.shape) == (dim,) and t.stride(-1) == 1, f"selective_scan_general: bad {name}")
+    _check(batch <= 65535, "selective_scan_general: batch <= 65535")
+    _gpu(u, delta, A, B, C, D, z, delta_bias)
+    return cplx, var[0], var[1], groups
+
+
+def _fill_ssm_general(P, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags):
+    cplx, var_B, var_C, groups = flags
+    batch, dim, seqlen = u.shape
+    P.batch, P.dim, P.seqlen, P.dstate, P.n_groups, P.n_chunks = batch, dim, seqlen, A.shape[1], groups, (seqlen + 2047) // 2048
+    P.delta_softplus, P.dtype = int(bool(delta_softplus)), _DT[u.dtype]
+    P.is_variable_B, P.is_variable_C, P.is_complex = int(var_B), int(var_C), int(cplx)
+    P.A_d_stride, P.A_dstate_stride = A.stride(0), A.stride(1)
+    for t, name, var in ((B, "B", var_B), (C, "C", var_C)):
+        if var:
+            setattr(P, name + "_batch_stride", t.stride(0)), setattr(P, name + "_group_stride", t.stride(1)), setattr(P, name + "_dstate_stride", t.stride(2))
+        else:
+            setattr(P, name + "_d_stride", t.stride(0)), setattr(P, name + "_dstate_stride", t.stride(1))
+    P.u_batch_stride, P.u_d_stride = u.stride(0), u.stride(1)
+    P.delta_batch_stride, P.delta_d_stride = delta.stride(0), delta.stride(1)
+    if z is not None:
+        P.z_batch_stride, P.z_d_stride = z.stride(0), z.stride(1)
+    if out is not None:
+        P.out_batch_stride, P.out_d_stride = out.stride(0), out.stride(1)
+    if out_z is not None:
+        P.out_z_batch_stride, P.out_z_d_stride = out_z.stride(0), out_z.stride(1)
+    P.A_ptr, P.B_ptr, P.C_ptr, P.D_ptr = _ptr(A), _ptr(B), _ptr(C), _ptr(D)
+    P.u_ptr, P.delta_ptr, P.delta_bias_ptr, P.z_ptr = _ptr(u), _ptr(delta), _ptr(delta_bias), _ptr(z)
+    P.out_ptr, P.x_ptr, P.out_z_ptr = _ptr(out), _ptr(x), _ptr(out_z)
+
+
+def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=True, need_x=True):
+    """-> [out, x, (out_z)] like selective_scan_cuda.fwd, on the general kernels: A float32 or complex64 (dim, dstate), dstate 1..256; B / C
+    input-dependent (batch, groups, dstate, seqlen) -- (.., 2 seqlen) reals with complex A -- or constant (dim, dstate) of A's dtype.
+    x is (batch, dim, n_chunks, 2 dstate) of A's dtype. None of the inference extras of selective_scan_fwd."""
+    flags = _check_ssm_general(u, delta, A, B, C, D, z, delta_bias)
+    batch, dim, seqlen = u.shape
+    dstate = A.shape[1]
+    out = torch.empty_like(delta) if need_out else None
+    x = torch.empty((batch, dim, (seqlen + 2047) // 2048, dstate * 2), device=u.device, dtype=A.dtype) if need_x else None
+    out_z = torch.empty_like(z) if z is not None else None
+    if u.numel() > 0:
+        P = _lib.SsmGeneralParams()
+        _fill_ssm_general(P, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags)
+        with torch.cuda.device(u.device):
+            _lib.check(_lib.load().dimsum_ssm_scan_general_fwd(P, _stream(u)), "selective_scan_general_fwd")
+    return [out, x] + ([out_z] if z is not None else [])
+
+
+def selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, dB=None, dC=None):
+    """-> [du, ddelta, dA, dB, dC, dD, ddelta_bias, (dz)] like selective_scan_cuda.bwd (without recompute_out_z), on the general kernels.
+    dA / constant dB / dC come back in A's dtype, input-dependent dB / dC in B's / C's; a caller may hand in fp32 buffers of B's / C's shape
+    (unit stride along the sequence) for input-dependent dB / dC: they are zero-filled here (the kernel adds into them) and returned as they are."""
+    flags = _check_ssm_general(u, delta, A, B, C, D, z, delta_bias)
+    cplx, var_B, var_C, groups = flags
+    _gpu(dout, out, dz)
+    batch, dim, seqlen = u.shape
+    dstate = A.shape[1]
+    _check(tuple(dout.shape) == (batch, dim, seqlen) and dout.dtype == u.dtype and (dout.stride(-1) == 1 or seqlen == 1), "selective_scan_general_bwd: bad dout")
+    if z is not None:
+        _check(out is not None and out.shape == u.shape and out.dtype == u.dtype and out.stride(-1) == 1,
+               "selective_scan_general_bwd: `out` of the forward is required with z")
+        if dz is None:
+            dz = torch.empty_like(z)
+        else:
+            _check(dz.shape == z.shape and dz.dtype == z.dtype and dz.stride(-1) == 1, "selective_scan_general_bwd: bad dz")
+    du, ddelta = torch.empty_like(u), torch.empty_like(delta)
+    dA = torch.zeros_like(A)
+    own = []
+    for t, like, var in ((dB, B, var_B), (dC, C, var_C)):
+        if t is not None:
+            _check(var and t.shape == like.shape and t.dtype == torch.float32 and t.is_cuda and t.stride(-1) == 1, "selective_scan_general_bwd: bad dB / dC buffer")
+            t.zero_()
+        own.append(t is None)
+    dB = torch.zeros(B.shape, device=u.device, dtype=torch.float32 if var_B else A.dtype) if dB is None else dB
+    dC = torch.zeros(C.shape, device=u.device, dtype=torch.float32 if var_C else A.dtype) if dC is None else dC
+    dD = torch.zeros_like(D) if D is not None else None
+    ddelta_bias = torch.zeros_like(delta_bias) if delta_bias is not None else None
+    if u.numel() > 0:
+        Q = _lib.SsmGeneralBwdParams()
+        _fill_ssm_general(Q.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out if z is not None else None, None, None, flags)
+        Q.dout_batch_stride, Q.dout_d_stride = dout.stride(0), dout.stride(1)
+        Q.dA_d_stride, Q.dA_dstate_stride = dA.stride(0), dA.stride(1)
+        for t, name, var in ((dB, "dB", var_B), (dC, "dC", var_C)):
+            if var:
+                setattr(Q, name + "_batch_stride", t.stride(0)), setattr(Q, name + "_group_stride", t.stride(1)), setattr(Q, name + "_dstate_stride", t.stride(2))
+            else:
+                setattr(Q, name + "_d_stride", t.stride(0)), setattr(Q, name + "_dstate_stride", t.stride(1))
+        Q.du_batch_stride, Q.du_d_stride = du.stride(0), du.stride(1)
+        Q.ddelta_batch_stride, Q.ddelta_d_stride = ddelta.stride(0), ddelta.stride(1)
+        if dz is not None:
+            Q.dz_batch_stride, Q.dz_d_stride = dz.stride(0), dz.stride(1)
+        Q.dout_ptr, Q.dA_ptr, Q.dB_ptr, Q.dC_ptr, Q.dD_ptr = _ptr(dout), _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD)
+        Q.du_ptr, Q.dz_ptr, Q.ddelta_ptr, Q.ddelta_bias_ptr = _ptr(du), _ptr(dz if z is not None else None), _ptr(ddelta), _ptr(ddelta_bias)
+        nbytes = _lib.load().dimsum_ssm_scan_general_bwd_workspace_bytes(batch, dim, seqlen, dstate, groups, int(cplx))
+        ws = torch.empty((nbytes + 3) // 4, device=u.device, dtype=torch.float32)
+        Q.workspace_ptr, Q.workspace_bytes = _ptr(ws), nbytes
+        with torch.cuda.device(u.device):
+            _lib.check(_lib.load().dimsum_ssm_scan_general_bwd(Q, _stream(u)), "selective_scan_general_bwd")
+        del ws
+    res = [du, ddelta, dA, dB.to(B.dtype) if var_B and own[0] else dB, dC.to(C.dtype) if var_C and own[1] else dC, dD, ddelta_bias]
+    if z is not None:
+        res.append(dz)
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # bidirectional selective scan: the two selective_scan_cuda calls of BiMambaInnerFn (mamba/mamba_ssm/ops/selective_scan_interface.py:1010-1388,
 # the second one on .flip(-1) copies) as ONE pair of launches that reads the forward layouts backwards (csrc/ssm_scan_fwd_kernel.hpp, kRev)
 # ---------------------------------------------------------------------------------------------------------------------

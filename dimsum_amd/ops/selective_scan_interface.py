@@ -16,7 +16,12 @@ activation tensor on 40-80 GB GPUs. With 288 GB of HBM the forward's `out_z` is 
 backward kernel skips that store (0.27 GB less traffic per call at DiM-L/2, batch 256). DIMSUM_RECOMPUTE_OUT_Z=1 restores
 the reference's trade.
 
-Not implemented (raise): complex A, constant (non input-dependent) B/C -- unused by DiMSUM (mamba_simple.py:586,602-603).
+selective_scan_fn takes everything the reference's does: any dstate in 1..256, constant (dim, dstate) B / C, complex A (B / C then complex, or
+real with a last axis of 2 seqlen). What the tuned kernels are not built for -- native.scan_takes_general_path -- runs on the general kernels
+(csrc/ssm_scan_general.hip); every other call takes the path it always took. mamba_inner_fn and its _cond / _no_out_proj forms run any dstate
+in 1..256 the same way, without the fused extras (dt_proj inside the scan, out_z operand images, f16s training).
+Not implemented (raise): complex A and constant B / C inside mamba_inner_fn* and bimamba_inner_fn; a dstate outside {4, 8, 16, 32} inside
+bimamba_inner_fn.
 """
 import os
 
@@ -37,20 +42,26 @@ class SelectiveScanFn(torch.autograd.Function):
                 need_ckpt=False):
         u, delta, B, C, z = (_last_contig(t) for t in (u, delta, B, C, z))
         D = D.contiguous() if D is not None else None
-        if B.dim() < 3 or C.dim() < 3:
-            raise NotImplementedError("selective_scan_fn: constant B/C (shape (dim, dstate)) is outside this build's scope")
+        var_B, var_C = B.dim() >= 3, C.dim() >= 3
         ctx.squeeze_B, ctx.squeeze_C = B.dim() == 3, C.dim() == 3
         if ctx.squeeze_B:
             B = B.unsqueeze(1)
         if ctx.squeeze_C:
             C = C.unsqueeze(1)
-        # training extra: saved states for the backward kernel (`need_ckpt` is decided by the caller: inside forward()
-        # grad mode is off and ctx.needs_input_grad ignores torch.no_grad())
-        out, x, *rest = native.selective_scan_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_ckpt=need_ckpt)
-        ckpt = rest.pop() if need_ckpt else None
         ctx.delta_softplus = delta_softplus
         ctx.has_z = z is not None
         ctx.has_D, ctx.has_bias = D is not None, delta_bias is not None
+        # the general kernels (csrc/ssm_scan_general.hip) serve what the tuned ones are not built for: constant B / C, complex A, other dstates
+        # (GPU tensors only: anything else keeps going to native.selective_scan_fwd, which refuses it -- or to what stands in for it in tests)
+        ctx.general = u.is_cuda and native.scan_takes_general_path(A.shape[-1], A.is_complex(), var_B, var_C, force=native.scan_general_forced())
+        if ctx.general:
+            out, x, *rest = native.selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus)
+            ckpt = None
+        else:
+            # training extra: saved states for the backward kernel (`need_ckpt` is decided by the caller: inside forward()
+            # grad mode is off and ctx.needs_input_grad ignores torch.no_grad())
+            out, x, *rest = native.selective_scan_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_ckpt=need_ckpt)
+            ckpt = rest.pop() if need_ckpt else None
         last_state = x[:, :, -1, 1::2]                     # (batch, dim, dstate)   (:39)
         ctx.save_for_backward(u, delta, A, B, C, D, z, delta_bias, x, out if ctx.has_z else None, ckpt)
         res = rest[0] if ctx.has_z else out
@@ -60,8 +71,12 @@ class SelectiveScanFn(torch.autograd.Function):
     def backward(ctx, dout, *args):
         u, delta, A, B, C, D, z, delta_bias, x, out, ckpt = ctx.saved_tensors
         dout = _last_contig(dout)
-        du, ddelta, dA, dB, dC, dD, ddelta_bias, *rest = native.selective_scan_bwd(
-            u, delta, A, B, C, D, z, delta_bias, dout, x, out, None, ctx.delta_softplus, False, ckpt=ckpt)
+        if ctx.general:
+            du, ddelta, dA, dB, dC, dD, ddelta_bias, *rest = native.selective_scan_general_bwd(
+                u, delta, A, B, C, D, z, delta_bias, dout, out, None, ctx.delta_softplus)
+        else:
+            du, ddelta, dA, dB, dC, dD, ddelta_bias, *rest = native.selective_scan_bwd(
+                u, delta, A, B, C, D, z, delta_bias, dout, x, out, None, ctx.delta_softplus, False, ckpt=ckpt)
         dz = rest[0] if ctx.has_z else None
         dB = dB.squeeze(1) if ctx.squeeze_B else dB
         dC = dC.squeeze(1) if ctx.squeeze_C else dC
@@ -119,6 +134,7 @@ class _MambaInner(torch.autograd.Function):
     def forward(ctx, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                 A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus, init_states, has_out_proj, checkpoint_lvl,
                 need_ckpt=False, conv_done=False, f16s_train=False, last_state=None):
+        # complex A and constant B / C are refused here (selective_scan_fn takes them); any dstate in 1..256 runs
         # conv_done (inference extra, not in the reference's signature): xz[:, :d_inner] already holds the causal conv1d + SiLU of the in_proj
         # output (the GEMM's epilogue formed it, modules/mamba_simple.py) -- the conv kernel is skipped
         # f16s_train (training extra, decided by the caller like need_ckpt: grad mode is off in here): out_proj's forward, input-gradient and
@@ -135,6 +151,9 @@ class _MambaInner(torch.autograd.Function):
         L = xz.shape[-1]
         R = delta_proj_weight.shape[1]
         N = A.shape[-1]
+        # a dstate the tuned kernels are not built for: the plain sequence on the general kernels (csrc/ssm_scan_general.hip), none of the fused
+        # extras below. conv_done is honoured: it says what xz already holds.
+        general = xz.is_cuda and native.scan_takes_general_path(N, force=native.scan_general_forced())
         if torch.is_autocast_enabled("cuda"):
             adt = torch.get_autocast_dtype("cuda")
             x_proj_weight, delta_proj_weight = x_proj_weight.to(adt), delta_proj_weight.to(adt)
@@ -169,7 +188,7 @@ class _MambaInner(torch.autograd.Function):
             # Only under allow_tf32 (the reference's own setting, train.py:20-21): the in-scan product is three bf16 products per fp32 product
             # (2e-5 relative, what the library's TF32-policy GEMM spends) -- with the flag off the reference multiplies in exact fp32 and so
             # does this path (the library's fp32 GEMM), which also keeps bench.py's exact-fp32 reference leg exact.
-            dt_fused = (not keep_stores and not torch.is_autocast_enabled("cuda") and os.environ.get("DIMSUM_SCAN_DT_PROJ", "1") != "0"
+            dt_fused = (not general and not keep_stores and not torch.is_autocast_enabled("cuda") and os.environ.get("DIMSUM_SCAN_DT_PROJ", "1") != "0"
                         and torch.backends.cuda.matmul.allow_tf32
                         and native.scan_dt_proj_supported(conv_out, z, A, delta_proj_weight, x_dbl_t[:R]))
             delta = None if dt_fused else (delta_proj_weight @ x_dbl_t[:R]).view(d_inner, bsz, L).permute(1, 0, 2)
@@ -208,25 +227,29 @@ class _MambaInner(torch.autograd.Function):
         keep = need or keep_stores
         # inference under allow_tf32: out_z leaves the scan as its split-bf16 pair of planes (the same 4 bytes per element) and out_proj runs
         # on the hand-written kernel's transposing-read variant straight from them (0.26 -> 0.17 ms per mixer at 65536 tokens)
-        scan_k = native.scan_fwd_kernel_for(bsz, d_inner, L, N, Bm.shape[1]) if xz.is_cuda else 1
+        scan_k = native.scan_fwd_kernel_for(bsz, d_inner, L, N, Bm.shape[1]) if xz.is_cuda and not general else 1
         # ... under the scaled-fp16 policy where a state-split kernel serves the launch (fp32 out_z: 16 channels per wave, no wave sees a 64-channel
         # block): ONE fp16 product behind a conversion pass that builds the block-scaled image (gemm.out_proj_f16_convert_enabled); takes precedence
         # over the planes (three products): 22.97 -> 22.77 ms per DiM-L/2 forward at batch 32, 176.6 -> 170.6 ms at DiM-XL/2 512 px (whose d_model
         # 576 the planes' TN product does not take)
-        conv16 = (has_out_proj and not keep and out_proj_bias is None and xz.is_cuda and not torch.is_autocast_enabled("cuda")
+        conv16 = (not general and has_out_proj and not keep and out_proj_bias is None and xz.is_cuda and not torch.is_autocast_enabled("cuda")
                   and gemm.out_proj_f16_convert_enabled(xz, out_proj_weight, bsz * L, L, scan_k))
-        planes = (has_out_proj and not need and not conv16 and out_proj_bias is None and L % 8 == 0
+        planes = (not general and has_out_proj and not need and not conv16 and out_proj_bias is None and L % 8 == 0
                   and d_inner % 64 == 0 and xz.is_cuda
                   and gemm.out_proj_planes_enabled(xz, out_proj_weight, bsz * L, scan_k))
         # inference under the scaled-fp16 policy on the 64-channel kernel: out_z leaves the scan as block-scaled fp16 (half the bytes) and
         # out_proj is ONE fp16 product per element on the hand-written TN GEMM (gemm.out_proj_f16) instead of the library's fp32 GEMM
-        z16 = (has_out_proj and not keep and not planes and not conv16 and out_proj_bias is None and xz.is_cuda and not torch.is_autocast_enabled("cuda")
+        z16 = (not general and has_out_proj and not keep and not planes and not conv16 and out_proj_bias is None and xz.is_cuda and not torch.is_autocast_enabled("cuda")
                and native.scan_out_z_f16_supported(conv_out, z, A, Bm.shape[1])
                and gemm.out_proj_f16_enabled(xz, out_proj_weight, bsz * L, L, scan_k))
-        out, scan_x, out_z, *rest = native.selective_scan_fwd(conv_out, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus,
-                                                              need_out=keep, need_x=keep, need_ckpt=need, **({"out_z_planes": True} if planes else {}),
-                                                              **({"out_z_f16": True} if z16 else {}),
-                                                              **({"dt_proj": (delta_proj_weight, x_dbl_t[:R])} if delta is None else {}))
+        if general:
+            out, scan_x, out_z = native.selective_scan_general_fwd(conv_out, delta, A.contiguous(), Bm, Cm, D, z, delta_bias, delta_softplus, need_out=keep, need_x=keep)
+            rest = [None]
+        else:
+            out, scan_x, out_z, *rest = native.selective_scan_fwd(conv_out, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus,
+                                                                  need_out=keep, need_x=keep, need_ckpt=need, **({"out_z_planes": True} if planes else {}),
+                                                                  **({"out_z_f16": True} if z16 else {}),
+                                                                  **({"dt_proj": (delta_proj_weight, x_dbl_t[:R])} if delta is None else {}))
         if last_state is not None:
             last_state.copy_(scan_x[:, :, -1, 1::2])
         if z16:
@@ -239,14 +262,15 @@ class _MambaInner(torch.autograd.Function):
         if planes:
             return gemm.out_proj_planes(out_z, out_proj_weight).view(bsz, L, out_proj_weight.shape[0])
         ckpt = rest[0] if need else None
+        ctx.general = general
         ctx.delta_softplus, ctx.has_out_proj, ctx.checkpoint_lvl = delta_softplus, has_out_proj, checkpoint_lvl
         ctx.xdbl_t = x_dbl is not None and x_dbl is x_dbl_t       # (training: x_dbl is saved as its transpose)
         ctx.flags = (conv1d_bias is not None, D is not None, delta_bias is not None, B_proj_bias is not None,
                      C_proj_bias is not None, has_out_proj and out_proj_bias is not None)
         if checkpoint_lvl >= 1:
             conv_out, delta = None, None            # recomputed in the backward (:663-664)
-        keep_out_z = has_out_proj and need and os.environ.get("DIMSUM_RECOMPUTE_OUT_Z", "0") != "1"
-        f16s = bool(f16s_train) and has_out_proj and need and out_proj_bias is None and keep_out_z
+        keep_out_z = has_out_proj and need and (general or os.environ.get("DIMSUM_RECOMPUTE_OUT_Z", "0") != "1")     # (the general backward does not recompute it)
+        f16s = bool(f16s_train) and not general and has_out_proj and need and out_proj_bias is None and keep_out_z
         ctx.f16s = f16s
         if f16s:
             # out = out_z^T W_out^T as the TN product of two images whose rows are the reduction index (channels): out_z (d, b l) with one scale per
@@ -299,8 +323,13 @@ class _MambaInner(torch.autograd.Function):
         into = {}
         if ctx.xdbl_t:      # dB / dC land in rows R .. R + 2N of d x_dbl^T (R + 2N, b l)
             into = {"dB": dx_dbl[R:R + N].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1), "dC": dx_dbl[R + N:].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)}
-        dconv_out, ddelta, dA, dB, dC, dD, ddelta_bias, dz, *rest = native.selective_scan_bwd(
-            conv_out, delta, A, Bm, Cm, D, z, delta_bias, dout_y, scan_x, out, dz, ctx.delta_softplus, recompute, ckpt=ckpt, **into)
+        if ctx.general:
+            dconv_out, ddelta, dA, dB, dC, dD, ddelta_bias, dz = native.selective_scan_general_bwd(
+                conv_out, delta, A.contiguous(), Bm, Cm, D, z, delta_bias, dout_y, out, dz, ctx.delta_softplus, **into)
+            rest = []
+        else:
+            dconv_out, ddelta, dA, dB, dC, dD, ddelta_bias, dz, *rest = native.selective_scan_bwd(
+                conv_out, delta, A, Bm, Cm, D, z, delta_bias, dout_y, scan_x, out, dz, ctx.delta_softplus, recompute, ckpt=ckpt, **into)
         out_z = rest[0] if recompute else kept_out_z
         dout_proj_weight = dout_proj_bias = None
         if ctx.f16s:

@@ -60,7 +60,7 @@ typedef enum {
     DIMSUM_ERR_DTYPE = 2,         /* unsupported dtype code */
     DIMSUM_ERR_SHAPE = 3,         /* bad size (dstate, width, n_groups, ...) */
     DIMSUM_ERR_STRIDE = 4,        /* stride not supported (innermost != 1, overflow) */
-    DIMSUM_ERR_UNSUPPORTED = 5,   /* valid in the reference but out of scope here (complex A, constant B/C) */
+    DIMSUM_ERR_UNSUPPORTED = 5,   /* valid in the reference but not served by THIS entry point (the tuned scan: complex A, constant B/C -> dimsum_ssm_scan_general_*; fusions a kernel does not offer) */
     DIMSUM_ERR_LAUNCH = 6,        /* hipGetLastError() after the launch */
     DIMSUM_ERR_ABI = 7            /* struct_size of a parameter struct does not match this library (stale / foreign header) */
 } dimsum_status_t;
@@ -236,6 +236,74 @@ int dimsum_ssm_scan_bidir_bwd(const dimsum_ssm_bidir_bwd_params_t *p, void *stre
  * way): 16 = one lane per state where that is the choice for the shape (dstate 16, launches far too small to fill the chip), else 1 = the
  * 64-channel kernel -- the state-split kernels have no reversed form; -1 on invalid parameters (a wrong struct_size included) */
 int dimsum_ssm_scan_bidir_fwd_variant(const dimsum_ssm_bidir_params_t *p);
+
+/* General selective scan: what selective_scan_cuda takes and the entry points above refuse -- any dstate in 1..256, constant B and / or C,
+ * complex A (selective_scan.cpp:226-492; the axes of mamba/tests/ops/test_selective_scan.py). One kernel family (csrc/ssm_scan_general.hip),
+ * none of the extensions of dimsum_ssm_ext_t. The entry points above are unchanged: they keep refusing these calls. Shapes as above, and
+ *   A : (dim, dstate) f32, or complex64 when is_complex (strides in elements of A's type: a complex element is a float pair)
+ *   B, C input-dependent (is_variable_* != 0): (batch, n_groups, dstate, seqlen) of `dtype`; with is_complex (batch, n_groups, dstate,
+ *       2 * seqlen): real and imaginary part interleaved along the last axis, as selective_scan_ref reads them (:131-134)
+ *   B, C constant (is_variable_* == 0): (dim, dstate) f32 / complex64 like A; *_d_stride and *_dstate_stride in elements of that type.
+ *       Both constant => n_groups must be 1.
+ *   x : (batch, dim, n_chunks, 2 * dstate) f32 / complex64: [2n] = running product of exp(delta A_n), [2n + 1] = state h_n
+ *   out = sum_n C h + D u; with is_complex out = 2 Re(sum_n C h) + D u -- the reference's convention (selective_scan_ref :163-164, its
+ *   kernel likewise): a complex state stands for itself and its conjugate. batch <= 65535.
+ * Checks, in this order: NULL struct / struct_size (DIMSUM_ERR_ABI) / required pointers / shape / dtype / negative strides or a
+ * misaligned x (DIMSUM_ERR_STRIDE); the backward then its own pointers, strides, workspace alignment and size (DIMSUM_ERR_SHAPE). */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_ssm_general_params_t) */
+    int32_t batch, dim, seqlen, dstate, n_groups, n_chunks;
+    int32_t delta_softplus;   /* bool */
+    int32_t dtype;            /* dimsum_dtype_t of u / delta / z / out / out_z and of input-dependent B / C */
+    int32_t is_variable_B, is_variable_C;   /* SSMParamsBase::is_variable_B / is_variable_C */
+    int32_t is_complex;       /* weight_t of the reference is complex: A (and constant B / C) complex64 */
+    int32_t reserved;         /* 0 */
+
+    int64_t A_d_stride, A_dstate_stride;
+    int64_t B_batch_stride, B_d_stride, B_group_stride, B_dstate_stride;   /* batch / group: input-dependent; d: constant */
+    int64_t C_batch_stride, C_d_stride, C_group_stride, C_dstate_stride;
+    int64_t u_batch_stride, u_d_stride;
+    int64_t delta_batch_stride, delta_d_stride;
+    int64_t z_batch_stride, z_d_stride;
+    int64_t out_batch_stride, out_d_stride;
+    int64_t out_z_batch_stride, out_z_d_stride;
+
+    const void *A_ptr, *B_ptr, *C_ptr, *D_ptr, *u_ptr, *delta_ptr, *delta_bias_ptr, *z_ptr;
+    void *out_ptr;    /* may be NULL in the forward */
+    void *x_ptr;      /* may be NULL */
+    void *out_z_ptr;  /* forward: required iff z_ptr != NULL; the backward does not recompute out_z */
+} dimsum_ssm_general_params_t;
+
+/* The backward. du, ddelta, dz are fully written. Everything summed over channels, batch or time -- dA (complex64 with is_complex), dB, dC,
+ * dD, ddelta_bias -- is ADDED with fp32 atomics into buffers the caller zero-fills: the result is not bit-repeatable between two launches.
+ *   input-dependent dB / dC : (batch, n_groups, dstate, seqlen) f32 always (2 * seqlen with is_complex), summed over a group's channels
+ *   constant dB / dC        : (dim, dstate) f32 / complex64, summed over batch and time
+ * Complex gradients are torch.autograd's (dL/dRe + i dL/dIm). fwd.out_ptr = the forward's `out`, required with z. */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_ssm_general_bwd_params_t) */
+    uint32_t reserved;         /* 0 */
+    dimsum_ssm_general_params_t fwd;   /* fwd.struct_size is ignored */
+    int64_t dout_batch_stride, dout_d_stride;
+    int64_t dA_d_stride, dA_dstate_stride;
+    int64_t dB_batch_stride, dB_d_stride, dB_group_stride, dB_dstate_stride;
+    int64_t dC_batch_stride, dC_d_stride, dC_group_stride, dC_dstate_stride;
+    int64_t du_batch_stride, du_d_stride;
+    int64_t dz_batch_stride, dz_d_stride;
+    int64_t ddelta_batch_stride, ddelta_d_stride;
+    const void *dout_ptr;
+    void *dA_ptr, *dB_ptr, *dC_ptr;
+    void *dD_ptr;              /* (dim) f32 zero-filled, or NULL */
+    void *du_ptr, *dz_ptr, *ddelta_ptr;
+    void *ddelta_bias_ptr;     /* (dim) f32 zero-filled, or NULL */
+    void *workspace_ptr;       /* scratch, 16-byte aligned: the states before every tile of the sequence, rebuilt by the kernel's own forward
+                                  sweep; dimsum_ssm_scan_general_bwd_workspace_bytes(...) bytes */
+    int64_t workspace_bytes;
+} dimsum_ssm_general_bwd_params_t;
+
+int dimsum_ssm_scan_general_fwd(const dimsum_ssm_general_params_t *p, void *stream);
+int dimsum_ssm_scan_general_bwd(const dimsum_ssm_general_bwd_params_t *p, void *stream);
+/* the backward's workspace; -1 on an invalid shape */
+int64_t dimsum_ssm_scan_general_bwd_workspace_bytes(int32_t batch, int32_t dim, int32_t seqlen, int32_t dstate, int32_t n_groups, int32_t is_complex);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Training-step tail: global gradient-norm clip + AdamW + parameter EMA over a list of fp32 tensors, two launches

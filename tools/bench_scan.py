@@ -38,6 +38,9 @@ def main():
     ap.add_argument("--train-fwd", action="store_true", help="time the forward's training variant (also stores the states the backward consumes)")
     ap.add_argument("--z16", action="store_true", help="--dt-fused with out_z as block-scaled fp16 (the launch of the headline forward: out_proj's operand image)")
     ap.add_argument("--dt-fused", action="store_true", help="forward with dt_proj inside the kernel (implies --infer): delta = W_dt x_dbl[:32] per tile on the matrix cores")
+    ap.add_argument("--general", action="store_true", help="the general kernels (csrc/ssm_scan_general.hip), forward or --bwd: any --N in 1..256; at a tuned "
+                                                            "shape this is the forced-general run, to be set against the same command without the flag")
+    ap.add_argument("--complex", action="store_true", help="--general with complex A (B / C real with a last axis of 2 L)")
     a = ap.parse_args()
     from dimsum_amd import _lib
     native._scan_fwd_variant = max(a.variant, 0)          # per-call field of the C ABI (dimsum_ssm_ext_t.kernel_variant)
@@ -68,7 +71,26 @@ def main():
         z = xz.chunk(2, 1)[1]
         u = torch.randn(B, D, L, device=dev, dtype=dt)
         dm = lambda t: t.permute(1, 0, 2).contiguous()      # noqa: E731  (dout below)
-    if a.bwd:
+    if a.general:
+        k = 2 if a.complex else 1
+        if a.complex:
+            A = torch.complex(A, torch.randn(D, N, device=dev))
+            Bm, Cm = torch.randn(B, 1, N, 2 * L, device=dev, dtype=dt), torch.randn(B, 1, N, 2 * L, device=dev, dtype=dt)
+        s_ = u.element_size()
+        if a.bwd:
+            out = native.selective_scan_general_fwd(u, delta, A, Bm, Cm, Dv, z, bias, True)[0]
+            dout, dz = dm(torch.randn(D, B, L, device=dev).to(dt)), torch.empty_like(xz).chunk(2, 1)[1]
+
+            def call():
+                return native.selective_scan_general_bwd(u, delta, A, Bm, Cm, Dv, z, bias, dout, out, dz, True)
+            # u, delta, z, out, dout in; du, ddelta, dz out; B, C in, dB, dC (fp32) out; the saved states written and read once
+            ws = _lib.load().dimsum_ssm_scan_general_bwd_workspace_bytes(B, D, L, N, 1, int(a.complex))
+            nbytes = 8 * B * D * L * s_ + 2 * B * N * L * k * (s_ + 4) + 2 * ws + (2 * D * N * k + 2 * D) * 4
+        else:
+            def call():
+                return native.selective_scan_general_fwd(u, delta, A, Bm, Cm, Dv, z, bias, True)
+            nbytes = 5 * B * D * L * s_ + 2 * B * N * L * k * s_ + B * D * ((L + 2047) // 2048) * 2 * N * k * 4 + (D * N * k + 2 * D) * 4
+    elif a.bwd:
         out, x, out_z, ckpt = native.selective_scan_fwd(u, delta, A, Bm, Cm, Dv, z, bias, True, need_ckpt=True)
         dout = dm(torch.randn(D, B, L, device=dev).to(dt))
         dxz = torch.empty_like(xz)
@@ -114,7 +136,8 @@ def main():
     P = _lib.SsmParams()
     P.batch, P.dim, P.seqlen, P.dstate, P.n_groups, P.n_chunks = B, D, L, N, 1, (L + 2047) // 2048
     _lib.attach_ext(P, _lib.SsmExt).kernel_variant = native._scan_fwd_variant
-    print(json.dumps({"kernel": "bwd" if a.bwd else "fwd", "fwd_variant": _lib.load().dimsum_ssm_scan_fwd_variant(P), "shape": [B, D, L, N], "dtype": a.dtype, "ms_median": med, "ms_min": ms[0], "algorithmic_GB": nbytes / 1e9,
+    print(json.dumps({"kernel": ("general_" if a.general else "") + ("bwd" if a.bwd else "fwd") + ("_complex" if a.general and a.complex else ""),
+                      "fwd_variant": 0 if a.general else _lib.load().dimsum_ssm_scan_fwd_variant(P), "shape": [B, D, L, N], "dtype": a.dtype, "ms_median": med, "ms_min": ms[0], "algorithmic_GB": nbytes / 1e9,
                       "GBps": nbytes / med / 1e6, "frac_of_8TBps": nbytes / med / 1e6 / 8000,
                       "box_copy_GBps": copy_gbps, "frac_of_box_copy": nbytes / med / 1e6 / copy_gbps, "timed_by": "HIP events, this process"}))
 

@@ -80,6 +80,47 @@ def gen_scan(ns):
              "distributions of mamba/tests/ops/test_selective_scan.py:62-95", **arrs)
 
 
+def gen_scan_general(ns):
+    """selective_scan_ref in float64 / complex128 over the axes of mamba/tests/ops/test_selective_scan.py (is_variable_B, is_variable_C, real /
+    complex weights) at state sizes the tuned kernels do not take: forward, last state and autograd gradients."""
+    cases = {
+        # name: (B, D, L, N, complex, variable B, variable C, groups, has_D, has_z, has_bias, softplus)
+        "scang_real_vv_n12": (2, 6, 21, 12, False, True, True, 2, True, True, True, True),
+        "scang_real_cv_n3": (2, 5, 19, 3, False, False, True, 1, True, False, True, True),
+        "scang_real_cc_n20": (1, 4, 17, 20, False, False, False, 1, False, True, False, False),
+        "scang_cplx_vv_n5": (2, 6, 21, 5, True, True, True, 2, True, True, True, True),
+        "scang_cplx_vc_n12": (2, 5, 19, 12, True, True, False, 1, True, True, False, True),
+        "scang_cplx_cc_n3": (1, 4, 17, 3, True, False, False, 1, False, False, True, False),
+    }
+    f8 = torch.float64
+    for name, (B, D, L, N, cplx, vB, vC, G, has_D, has_z, has_b, sp) in cases.items():
+        torch.manual_seed(0)
+        wdt = torch.complex128 if cplx else f8
+        A = -0.5 * torch.rand(D, N, dtype=f8)
+        A = (A + 1j * torch.randn(D, N, dtype=f8) if cplx else A).requires_grad_()
+        Bm = (torch.randn(B, G, N, L * (2 if cplx else 1), dtype=f8) if vB else torch.randn(D, N, dtype=wdt)).requires_grad_()
+        Cm = (torch.randn(B, G, N, L * (2 if cplx else 1), dtype=f8) if vC else torch.randn(D, N, dtype=wdt)).requires_grad_()
+        Dv = torch.randn(D, dtype=f8, requires_grad=True) if has_D else None
+        z = torch.randn(B, D, L, dtype=f8, requires_grad=True) if has_z else None
+        db = (0.5 * torch.rand(D, dtype=f8)).requires_grad_() if has_b else None
+        u = torch.randn(B, D, L, dtype=f8, requires_grad=True)
+        delta = (0.5 * torch.rand(B, D, L, dtype=f8)).requires_grad_()
+        # selective_scan_ref works in float32 (`.float()`); the float64 run goes through a module copy whose Tensor.float is the identity
+        out, last = ref_shim.in_float64(ns.ssi.selective_scan_ref, u, delta, A, Bm, Cm, Dv, z, db, sp, return_last_state=True)
+        assert out.dtype == f8
+        g = torch.randn_like(out)
+        out.backward(g)
+        arrs = dict(u=u, delta=delta, A=A, B=Bm, C=Cm, dout=g, out=out, last_state=last, du=u.grad, ddelta=delta.grad, dA=A.grad, dB=Bm.grad,
+                    dC=Cm.grad, softplus=np.array(sp))
+        if has_D:
+            arrs.update(D=Dv, dD=Dv.grad)
+        if has_z:
+            arrs.update(z=z, dz=z.grad)
+        if has_b:
+            arrs.update(delta_bias=db, ddelta_bias=db.grad)
+        save(name, "selective_scan_ref fwd + autograd in float64 / complex128 (mamba/mamba_ssm/ops/selective_scan_interface.py:104-171)", **arrs)
+
+
 def gen_conv(ns):
     """causal_conv1d_ref fwd + autograd (causal_conv1d_interface.py:48-64)."""
     cases = {
@@ -951,6 +992,7 @@ def main():
         "transport_blur": lambda: gen_transport_blur(ns),
         "block_linear_window": lambda: gen_block_linear_window(ns), "tiny_linear_window": lambda: gen_model_tiny_linear_window(ns),
         "pe": lambda: gen_pe(ns), "einfft": lambda: gen_einfft(ns), "dit_keys": lambda: gen_dit_keys(ns), "step": lambda: gen_step(ns),
+        "scan_general": lambda: gen_scan_general(ns),
     }
     for k, fn in steps.items():
         if args.only is None or k in args.only:

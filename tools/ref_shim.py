@@ -273,3 +273,15 @@ def rerandomize_zeros(model, std=0.02, seed=1234):
             if p.numel() > 0 and torch.count_nonzero(p) == 0:
                 p.copy_(torch.randn(p.shape, generator=g) * std)
     return model
+
+
+def in_float64(fn, *args, **kw):
+    """fn(*args, **kw) with Tensor.float() as the identity for the duration of the call: the reference's *_ref functions cast their operands
+    with .float(); float64 / complex128 operands then stay what they are and the function becomes its own double-precision restatement"""
+    import torch
+    orig = torch.Tensor.float
+    torch.Tensor.float = lambda self, *a, **k: self
+    try:
+        return fn(*args, **kw)
+    finally:
+        torch.Tensor.float = orig
