@@ -271,6 +271,34 @@ class GeluParams(_Sized):
 GELU_OUT_F32, GELU_OUT_SPLIT3, GELU_OUT_PAIR, GELU_OUT_F16S = 0, 1, 2, 3
 
 
+class MoeExt(_Sized):
+    """dimsum_moe_ext_t: nothing yet"""
+    _fields_ = [("struct_size", u32), ("reserved", i32)]
+
+
+class MoeRouteParams(_Sized):
+    """dimsum_moe_route_params_t: the router, top-1 choice and counting sort (fwd); the router's adjoint (bwd)"""
+    _fields_ = ([("struct_size", u32), ("mode", i32), ("num_experts", i32), ("reserved", i32), ("tokens", i64), ("hidden", i64)]
+                + [(n, vp) for n in ("x_ptr", "w_ptr", "b_ptr", "prob_ptr", "expert_ptr", "logits_ptr", "offsets_ptr", "perm_ptr", "inv_ptr",
+                                     "row_expert_ptr", "work_ptr")]
+                + [("work_bytes", i64)] + [(n, vp) for n in ("dprob_ptr", "dxp_ptr", "dx_ptr", "dw_ptr", "db_ptr")] + [("ext", C.POINTER(MoeExt))])
+
+
+class MoeRowsParams(_Sized):
+    """dimsum_moe_rows_params_t: permute, combine forward and backward"""
+    _fields_ = ([("struct_size", u32), ("reserved", i32), ("rows", i64), ("hidden", i64)]
+                + [(n, vp) for n in ("src_ptr", "perm_ptr", "prob_ptr", "y_ptr", "dst_ptr", "dprob_ptr")] + [("ext", C.POINTER(MoeExt))])
+
+
+class MoeActParams(_Sized):
+    """dimsum_moe_act_params_t: the experts' exact-GELU activation over the sorted rows"""
+    _fields_ = ([("struct_size", u32), ("gated", i32), ("num_experts", i32), ("reserved", i32), ("rows", i64), ("width", i64)]
+                + [(n, vp) for n in ("x_ptr", "bias_ptr", "row_expert_ptr", "dh_ptr", "out_ptr", "dbias_ptr")] + [("ext", C.POINTER(MoeExt))])
+
+
+MOE_ROUTE_SOFTMAX, MOE_ROUTE_SIGMOID = 0, 1
+
+
 class F16sJob(C.Structure):
     _fields_ = ([(n, vp) for n in ("src", "dst", "inv_scale_ptr", "l1max_ptr", "absmax_ptr")]
                 + [(n, i64) for n in ("rows", "cols", "src_row_stride", "dst_row_stride")] + [("l1_factor", f32), ("reserved", i32)])
@@ -293,6 +321,8 @@ EXPORTS = (
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
     "dimsum_gelu_fwd", "dimsum_gelu_bwd",
+    "dimsum_moe_route_work_bytes", "dimsum_moe_route_fwd", "dimsum_moe_route_bwd", "dimsum_moe_permute", "dimsum_moe_combine_fwd",
+    "dimsum_moe_combine_bwd", "dimsum_moe_act_fwd", "dimsum_moe_act_bwd",
     "dimsum_gemm_nt", "dimsum_gemm_nt_kernel_for", "dimsum_gemm_tn", "dimsum_gemm_nn", "dimsum_row_factors", "dimsum_rows_block_f16s", "dimsum_rows_f16s", "dimsum_rows_f16s_multi",
 )
 
@@ -313,7 +343,9 @@ _SIGNATURES = (
         ("dimsum_einfft_idft_real", EinfftDftParams), ("dimsum_einfft_mlp_fwd", EinfftMlpParams), ("dimsum_einfft_mlp_bwd", EinfftMlpBwdParams),
         ("dimsum_gelu_fwd", GeluParams), ("dimsum_gelu_bwd", GeluParams), ("dimsum_causal_conv1d_update", ConvUpdateParams),
         ("dimsum_selective_state_update", StateUpdateParams), ("dimsum_ssm_scan_general_fwd", SsmGeneralParams),
-        ("dimsum_ssm_scan_general_bwd", SsmGeneralBwdParams))]
+        ("dimsum_ssm_scan_general_bwd", SsmGeneralBwdParams), ("dimsum_moe_route_fwd", MoeRouteParams), ("dimsum_moe_route_bwd", MoeRouteParams),
+        ("dimsum_moe_permute", MoeRowsParams), ("dimsum_moe_combine_fwd", MoeRowsParams), ("dimsum_moe_combine_bwd", MoeRowsParams),
+        ("dimsum_moe_act_fwd", MoeActParams), ("dimsum_moe_act_bwd", MoeActParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),
@@ -328,6 +360,7 @@ _SIGNATURES = (
        ("dimsum_split3_t", C.c_int, [vp, i64, i64, i64, vp, vp]),
        ("dimsum_rows_f16s", C.c_int, [vp, i64, i64, i64, vp, i64, vp, vp, vp]),
        ("dimsum_rows_f16s_multi", C.c_int, [_P(F16sJob), i32, vp]),
+       ("dimsum_moe_route_work_bytes", i64, [i64, i32]),
        ("dimsum_ssm_scan_bwd_workspace_bytes", i64, [i32] * 5),
        ("dimsum_ssm_scan_general_bwd_workspace_bytes", i64, [i32] * 6),
        ("dimsum_ssm_scan_fwd_variant", C.c_int, [_P(SsmParams)]),

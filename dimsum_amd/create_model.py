@@ -2,7 +2,7 @@
 from .models_dim import DiM_models
 from .models_dit import DiT_models
 
-DIM_ONLY_FLAGS = ("block_type", "pe_type")      # what a DiT name ignores (the CLIs say so in one logged line)
+DIM_ONLY_FLAGS = ("block_type", "pe_type", "is_moe", "num_moe_experts", "mamba_moe_layers")      # what a DiT name ignores (the CLIs say so in one logged line)
 
 
 def is_dit(name):
@@ -19,7 +19,7 @@ def create_model(config):
         img_resolution=config.image_size // 8, in_channels=config.num_in_channels, label_dropout=config.label_dropout,
         num_classes=config.num_classes, gated_linear_unit=getattr(config, "gated_linear_unit", True),
         routing_mode=getattr(config, "routing_mode", "top1"), num_moe_experts=getattr(config, "num_moe_experts", 8),
-        is_moe=getattr(config, "is_moe", False), learn_sigma=config.learn_sigma, scan_type=config.bimamba_type,
+        mamba_moe_layers=getattr(config, "mamba_moe_layers", None), is_moe=getattr(config, "is_moe", False), learn_sigma=config.learn_sigma, scan_type=config.bimamba_type,
         pe_type=config.pe_type, block_type=config.block_type, cond_mamba=config.cond_mamba,
         scanning_continuity=config.scanning_continuity, enable_fourier_layers=config.enable_fourier_layers,
         drop_path=config.drop_path, rms_norm=config.rms_norm, fused_add_norm=config.fused_add_norm,
@@ -39,8 +39,10 @@ def published_config(model="DiM-L/2", image_size=256, num_classes=1000, **over):
 
 
 def model_from_cli(args, log=print):
-    """the model a CLI builds from its --model / --image-size / --num-classes / --pe-type / --block-type flags (train.py, sample_ddp.py); for a DiT
+    """the model a CLI builds from its --model / --image-size / --num-classes / --pe-type / --block-type / --is-moe / --num-moe-experts / --mamba-moe-layers flags (train.py, sample_ddp.py); for a DiT
     name the DiM-only flags are ignored, with one logged line"""
     if is_dit(args.model):
         log(f"{args.model}: " + " / ".join("--" + f.replace("_", "-") for f in DIM_ONLY_FLAGS) + " are DiM-only flags and are ignored for the DiT baseline")
-    return create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type, block_type=args.block_type))
+    return create_model(published_config(args.model, args.image_size, args.num_classes, pe_type=args.pe_type, block_type=args.block_type,
+                                         is_moe=getattr(args, "is_moe", False), num_moe_experts=getattr(args, "num_moe_experts", 8),
+                                         mamba_moe_layers=getattr(args, "mamba_moe_layers", None)))

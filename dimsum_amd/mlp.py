@@ -261,3 +261,26 @@ class Mlp(nn.Module):
     def forward(self, x):
         y, b = self.forward_deferred(x)
         return y if b is None else y + b
+
+
+class MLP(nn.Module):
+    """The expert of the mixture-of-experts layer, with the reference's signature and parameter names (dimsum/mlp.py:7-46): linear_fc2(act(linear_fc1(x))),
+    `linear_fc1` dim -> 8 dim with the gated linear unit (act = gelu(a) * g over the two halves) else dim -> 4 dim (act = gelu), `linear_fc2`
+    4 dim -> dim, biases only with add_bias_linear. The GELU is the exact (erf) one. Inside a SwitchMLP the layer's own function runs the experts
+    over row slices (ops/moe.py); called on its own, bias + activation are the same HIP pass with one expert (csrc/moe.hip)."""
+
+    def __init__(self, dim, add_bias_linear=False, gated_linear_unit=True, is_expert=False, layer_idx=None, device=None):
+        super().__init__()
+        self.layer, self.gated_linear_unit = layer_idx, gated_linear_unit
+        self.linear_fc1 = nn.Linear(dim, (8 if gated_linear_unit else 4) * dim, bias=add_bias_linear, device=device)
+        self.linear_fc1.is_expert = is_expert
+        self.linear_fc2 = nn.Linear(4 * dim, dim, bias=add_bias_linear, device=device)
+
+    def forward(self, hidden_states, inference_params=None):
+        from .ops.moe import moe_act
+        if hidden_states.dtype != torch.float32:
+            raise RuntimeError("MLP: float32 tokens only (there is no other kernel and no fallback)")
+        h1 = gemm.linear(hidden_states, self.linear_fc1.weight)
+        h = moe_act(h1.reshape(-1, h1.shape[-1]), self.linear_fc1.bias, self.gated_linear_unit).view(*h1.shape[:-1], -1)
+        y = gemm.linear(h, self.linear_fc2.weight)
+        return y if self.linear_fc2.bias is None else y + self.linear_fc2.bias

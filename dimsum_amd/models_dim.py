@@ -12,7 +12,9 @@ What is structured differently (results equal to fp32 roundoff; pinned by tests/
   * pe_type "rope" / "cpe": the embed pass is one HIP launch (ops/pos_embed.py: the rotation of the channel pairs; the depthwise 3x3 conv on
     the token grid + LayerNorm + adaLN modulation), "ape" the add it always was.
 The DiT baseline built from these pieces lives in models_dit.py; the plain Mlp of `use_gated_mlp=False` in mlp.py.
-Out of scope (constructor raises): MoE and `enable_fourier_layers` -- unused by every published config
+`is_moe=True`: every odd layer is a MoEBlock over a SwitchMLP (switch_mlp.py; fused HIP routing passes). The reference
+cannot construct that model (its initialize_weights reads adaLN_modulation on every block); the intended semantics are built here.
+Out of scope (constructor raises): `enable_fourier_layers` -- broken in the reference and unused by every published config
 (SURVEY.md section 2.1).
 """
 import math
@@ -29,6 +31,7 @@ from . import gemm
 from .attention_fusion import CrossAttentionFusion
 from .dct_layer import init_dct_kernel, init_idct_kernel
 from .mlp import GatedMLP, Mlp
+from .switch_mlp import SwitchMLP
 from .modules.mamba_simple import CondMamba, Mamba
 from .ops import token_ops
 from .ops.layernorm import RMSNorm, layer_norm_fn, rms_norm_fn
@@ -774,6 +777,34 @@ class DiTBlock(nn.Module):
         return token_ops.gate_residual(x, self.mlp(h), gm, None)
 
 
+class MoEBlock(nn.Module):
+    """add -> norm -> mixer (a SwitchMLP): models_dim.py:936-971. No adaLN, no drop-path; the block returns the mixer's output and the
+    residual stream, like the Mamba blocks of the reference's language models."""
+
+    def __init__(self, dim, mixer_cls, norm_cls=nn.LayerNorm, fused_add_norm=False, residual_in_fp32=False):
+        super().__init__()
+        self.residual_in_fp32, self.fused_add_norm = residual_in_fp32, fused_add_norm
+        self.mixer = mixer_cls(dim)
+        self.norm = norm_cls(dim)
+        if fused_add_norm and not isinstance(self.norm, (nn.LayerNorm, RMSNorm)):
+            raise ValueError("MoEBlock: fused_add_norm needs a LayerNorm or an RMSNorm")
+
+    def forward(self, hidden_states, residual=None, inference_params=None):
+        if not self.fused_add_norm:
+            residual = hidden_states if residual is None else hidden_states + residual
+            hidden_states = self.norm(residual.to(dtype=self.norm.weight.dtype))
+            if self.residual_in_fp32:
+                residual = residual.to(torch.float32)
+        else:
+            fn = rms_norm_fn if isinstance(self.norm, RMSNorm) else layer_norm_fn
+            hidden_states, residual = fn(hidden_states, self.norm.weight, self.norm.bias, residual=residual, prenorm=True,
+                                         residual_in_fp32=self.residual_in_fp32, eps=self.norm.eps)
+        return self.mixer(hidden_states), residual
+
+    def allocate_inference_cache(self, *a, **k):
+        raise NotImplementedError("allocate_inference_cache: " + _NOT_CAUSAL)
+
+
 def _init_weights(module, n_layer, initializer_range=0.02, rescale_prenorm_residual=True, n_residuals_per_layer=1):
     """GPT-2 style init (models_dim.py:1969-1998): zero Linear biases (except dt_proj), scaled out_proj/fc2."""
     if isinstance(module, nn.Linear):
@@ -794,11 +825,15 @@ def create_block(d_model, ssm_cfg=None, norm_epsilon=1e-5, drop_path=0.0, rms_no
                  gated_linear_unit=True, routing_mode="sinkhorn", num_moe_experts=8, mamba_moe_layers=None, is_moe=False,
                  block_type="linear", reverse=False, transpose=False, cond_mamba=False, scanning_continuity=False,
                  skip=False, use_gated_mlp=True, block_kwargs={}, block_kwargs2={}):
-    if is_moe:
-        raise NotImplementedError("MoE blocks are outside the denoiser hot path (never enabled by a published config)")
     ssm_cfg = ssm_cfg or {}
     fk = {"device": device, "dtype": dtype}
     norm_cls = partial(nn.LayerNorm if not rms_norm else RMSNorm, eps=norm_epsilon, **fk)
+    if is_moe and layer_idx % 2 == 1:       # every odd layer of a mixture-of-experts model (models_dim.py:2033,2142-2158)
+        mixer_cls = partial(SwitchMLP, layer_idx=layer_idx, add_bias_linear=add_bias_linear, gated_linear_unit=gated_linear_unit,
+                            routing_mode=routing_mode, num_moe_experts=num_moe_experts, mamba_moe_layers=mamba_moe_layers)
+        block = MoEBlock(d_model, mixer_cls=mixer_cls, norm_cls=norm_cls, fused_add_norm=fused_add_norm, residual_in_fp32=residual_in_fp32)
+        block.layer_idx = layer_idx
+        return block
     if cond_mamba:
         # the reference passes scan_type twice here when block_kwargs carries one (SURVEY finding 2); block_kwargs wins
         kw = dict(layer_idx=layer_idx, scan_type=scan_type, d_cond=d_model, **ssm_cfg, **fk)
@@ -909,6 +944,8 @@ class DiM(nn.Module):
         nn.init.normal_(self.t_embedder.mlp[0].weight, std=0.02)
         nn.init.normal_(self.t_embedder.mlp[2].weight, std=0.02)
         for block in self.blocks:
+            if not hasattr(block, "adaLN_modulation"):       # a MoEBlock: no conditioning head (the reference's loop fails here, :1762-1764)
+                continue
             nn.init.constant_(block.adaLN_modulation[-1].weight, 0)
             nn.init.constant_(block.adaLN_modulation[-1].bias, 0)
         nn.init.constant_(self.final_layer.adaLN_modulation[-1].weight, 0)
@@ -952,7 +989,10 @@ class DiM(nn.Module):
             x = self.pos_cnn(self.x_embedder(x), c, H=g, W=g)
         residual = None
         for idx, block in enumerate(self.blocks):
-            x, residual = block(x, residual, c, inference_params=inference_params)
+            if isinstance(block, MoEBlock):      # (the reference would hand it c twice: positionally and by keyword)
+                x, residual = block(x, residual)
+            else:
+                x, residual = block(x, residual, c, inference_params=inference_params)
             if self.use_attn_every_k_layers > 0 and (idx + 1) % self.use_attn_every_k_layers == 0:
                 if self.use_independent_attn:
                     x = self.attn_block[(idx + 1) // self.use_attn_every_k_layers - 1](x, c)

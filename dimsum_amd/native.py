@@ -1006,6 +1006,152 @@ def gelu_bwd(x, bias, dh, need_dbias=True, split3=False):
     return _gelu_call(_lib.load().dimsum_gelu_bwd, "gelu_bwd", x, bias, dh, split3, bias is not None and need_dbias, None)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the top-1 mixture-of-experts layer's row passes (csrc/moe.hip; SwitchMLP, dimsum/switch_mlp.py:69-99)
+# ---------------------------------------------------------------------------------------------------------------------
+MOE_MAX_EXPERTS = 64
+_MOE_MODE = {"softmax": _lib.MOE_ROUTE_SOFTMAX, "sigmoid": _lib.MOE_ROUTE_SIGMOID}
+
+
+def _moe_rows(t, what, name="x"):
+    _check(t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.shape[1] % 4 == 0 and t.shape[1] > 0,
+           f"{what}: {name} must be contiguous float32 (rows, H) with H % 4 == 0")
+
+
+def _moe_index(t, n, what, name):
+    _check(t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (n,), f"{what}: {name} must be contiguous int32 ({n},)")
+
+
+def _moe_route_check(x, w, b, mode, what):
+    _moe_rows(x, what)
+    _check(mode in _MOE_MODE, f"{what}: mode is 'softmax' or 'sigmoid'")
+    _check(w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and w.shape[1] == x.shape[1] and 1 <= w.shape[0] <= MOE_MAX_EXPERTS,
+           f"{what}: the router weight must be contiguous float32 (E, H) with 1 <= E <= {MOE_MAX_EXPERTS}")
+    _check(b is None or (b.dtype == torch.float32 and b.is_contiguous() and tuple(b.shape) == (w.shape[0],)), f"{what}: the router bias must be float32 (E,)")
+
+
+def moe_route_fwd(x, w, b, mode):
+    """x (T, H), router weight (E, H) and bias (E) or None, mode 'softmax' | 'sigmoid' -> prob (T), expert (T) int32 = max(route, 1) (first maximum),
+    logits (T, E), and the stable counting sort of the tokens by expert: offsets (E + 1), perm (T), inv (T), row_expert (T), all int32.
+    Three launches, no host synchronisation."""
+    _gpu(x, w, b)
+    _moe_route_check(x, w, b, mode, "moe_route_fwd")
+    T, H = x.shape
+    E = w.shape[0]
+    dev = x.device
+    lib = _lib.load()
+    prob = torch.empty(T, device=dev, dtype=torch.float32)
+    logits = torch.empty(T, E, device=dev, dtype=torch.float32)
+    expert, perm, inv, row_expert = (torch.empty(T, device=dev, dtype=torch.int32) for _ in range(4))
+    offsets = torch.empty(E + 1, device=dev, dtype=torch.int32)
+    nbytes = int(lib.dimsum_moe_route_work_bytes(T, E))
+    work = torch.empty(max(nbytes // 4, 1), device=dev, dtype=torch.int32)
+    P = _lib.MoeRouteParams()
+    P.mode, P.num_experts, P.tokens, P.hidden = _MOE_MODE[mode], E, T, H
+    P.x_ptr, P.w_ptr, P.b_ptr, P.prob_ptr, P.expert_ptr, P.logits_ptr = _ptr(x), _ptr(w), _ptr(b), _ptr(prob), _ptr(expert), _ptr(logits)
+    P.offsets_ptr, P.perm_ptr, P.inv_ptr, P.row_expert_ptr, P.work_ptr, P.work_bytes = _ptr(offsets), _ptr(perm), _ptr(inv), _ptr(row_expert), _ptr(work), nbytes
+    with torch.cuda.device(dev):
+        _lib.check(lib.dimsum_moe_route_fwd(P, _stream(x)), "moe_route_fwd")
+    return prob, expert, logits, offsets, perm, inv, row_expert
+
+
+def moe_route_bwd(x, w, logits, prob, expert, inv, dprob, dxp, mode):
+    """the router's adjoint -> (dx (T, H) = dxp[inv] + dlogit w, dw (E, H), db (E)); dlogit is formed in the kernel from the saved logits"""
+    _gpu(x, w, logits, prob, expert, inv, dprob, dxp)
+    _moe_route_check(x, w, None, mode, "moe_route_bwd")
+    T, H = x.shape
+    E = w.shape[0]
+    _moe_rows(dxp, "moe_route_bwd", "dxp")
+    _check(dxp.shape == x.shape and logits.dtype == torch.float32 and logits.is_contiguous() and tuple(logits.shape) == (T, E),
+           "moe_route_bwd: dxp (T, H) and logits (T, E) float32")
+    for t, n in ((prob, "prob"), (dprob, "dprob")):
+        _check(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (T,), f"moe_route_bwd: {n} must be contiguous float32 (T,)")
+    _moe_index(expert, T, "moe_route_bwd", "expert")
+    _moe_index(inv, T, "moe_route_bwd", "inv")
+    dx = torch.empty_like(x)
+    acc = _zeros(E * H + E, x.device)
+    dw, db = acc[:E * H].view(E, H), acc[E * H:]
+    P = _lib.MoeRouteParams()
+    P.mode, P.num_experts, P.tokens, P.hidden = _MOE_MODE[mode], E, T, H
+    P.x_ptr, P.w_ptr, P.prob_ptr, P.expert_ptr, P.logits_ptr, P.inv_ptr = _ptr(x), _ptr(w), _ptr(prob), _ptr(expert), _ptr(logits), _ptr(inv)
+    P.dprob_ptr, P.dxp_ptr, P.dx_ptr, P.dw_ptr, P.db_ptr = _ptr(dprob), _ptr(dxp), _ptr(dx), _ptr(dw), _ptr(db)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dimsum_moe_route_bwd(P, _stream(x)), "moe_route_bwd")
+    return dx, dw, db
+
+
+def _moe_rows_call(fn, what, src, perm, prob=None, y=None, want_dprob=False):
+    _gpu(src, perm, prob, y)
+    _moe_rows(src, what, "the rows")
+    T, H = src.shape
+    _moe_index(perm, T, what, "perm")
+    _check(prob is None or (prob.dtype == torch.float32 and prob.is_contiguous() and tuple(prob.shape) == (T,)), f"{what}: prob must be contiguous float32 (T,)")
+    _check(y is None or (y.dtype == torch.float32 and y.is_contiguous() and y.shape == src.shape), f"{what}: y must be contiguous float32 like the rows")
+    dst = torch.empty_like(src)
+    dprob = torch.empty(T, device=src.device, dtype=torch.float32) if want_dprob else None
+    P = _lib.MoeRowsParams()
+    P.rows, P.hidden = T, H
+    P.src_ptr, P.perm_ptr, P.prob_ptr, P.y_ptr, P.dst_ptr, P.dprob_ptr = _ptr(src), _ptr(perm), _ptr(prob), _ptr(y), _ptr(dst), _ptr(dprob)
+    with torch.cuda.device(src.device):
+        _lib.check(fn(P, _stream(src)), what)
+    return dst, dprob
+
+
+def moe_permute(x, perm):
+    """xp[j, :] = x[perm[j], :]  (perm: int32, entries in [0, T))"""
+    return _moe_rows_call(_lib.load().dimsum_moe_permute, "moe_permute", x, perm)[0]
+
+
+def moe_combine_fwd(y, perm, prob):
+    """out[perm[j], :] = prob[perm[j]] * y[j, :]: perm is a permutation, every token's row is written exactly once"""
+    _check(prob is not None, "moe_combine_fwd: prob is required")
+    return _moe_rows_call(_lib.load().dimsum_moe_combine_fwd, "moe_combine_fwd", y, perm, prob=prob)[0]
+
+
+def moe_combine_bwd(dout, y, perm, prob):
+    """-> (dy (sorted order) = prob[t] dout[t], dprob (T) = <dout[t], y[j]>), t = perm[j], in one pass over (dout, y)"""
+    _check(prob is not None and y is not None, "moe_combine_bwd: prob and y are required")
+    return _moe_rows_call(_lib.load().dimsum_moe_combine_bwd, "moe_combine_bwd", dout, perm, prob=prob, y=y, want_dprob=True)
+
+
+def _moe_act_call(fn, what, x, bias, row_expert, dh, gated, need_dbias):
+    _gpu(x, bias, row_expert, dh)
+    _moe_rows(x, what)
+    rows, S = x.shape
+    _check(not gated or S % 8 == 0, f"{what}: the gated input is (rows, 2 W) with W % 4 == 0")
+    W = S // 2 if gated else S
+    E = 1
+    if bias is not None:
+        _check(bias.dtype == torch.float32 and bias.is_contiguous() and bias.dim() == 2 and bias.shape[1] == S and 1 <= bias.shape[0] <= MOE_MAX_EXPERTS,
+               f"{what}: bias must be contiguous float32 (E, {S}) with 1 <= E <= {MOE_MAX_EXPERTS}")
+        E = bias.shape[0]
+    if row_expert is not None:
+        _moe_index(row_expert, rows, what, "row_expert")
+    _check(row_expert is not None or bias is None or bias.shape[0] == 1, f"{what}: a bias with more than one row needs row_expert")
+    if dh is not None:
+        _check(dh.dtype == torch.float32 and dh.is_contiguous() and tuple(dh.shape) == (rows, W), f"{what}: dh must be contiguous float32 (rows, W)")
+    out = torch.empty(rows, S if dh is not None else W, device=x.device, dtype=torch.float32)
+    dbias = _zeros(bias.numel(), x.device).view(bias.shape) if (need_dbias and bias is not None) else None
+    P = _lib.MoeActParams()
+    P.gated, P.num_experts, P.rows, P.width = int(bool(gated)), E, rows, W
+    P.x_ptr, P.bias_ptr, P.row_expert_ptr, P.dh_ptr, P.out_ptr, P.dbias_ptr = _ptr(x), _ptr(bias), _ptr(row_expert), _ptr(dh), _ptr(out), _ptr(dbias)
+    with torch.cuda.device(x.device):
+        _lib.check(fn(P, _stream(x)), what)
+    return out, dbias
+
+
+def moe_act_fwd(x, bias=None, row_expert=None, gated=True):
+    """x (rows, 2 W | W) = fc1's output WITHOUT bias, bias (E, 2 W | W) or None picked per row by row_expert (int32; None: row 0) ->
+    gelu_erf(a + b_a) * (g + b_g) (gated) or gelu_erf(x + b): the exact GELU of the reference's expert MLP (dimsum/mlp.py:30-38)"""
+    return _moe_act_call(_lib.load().dimsum_moe_act_fwd, "moe_act_fwd", x, bias, row_expert, None, gated, False)[0]
+
+
+def moe_act_bwd(x, bias, row_expert, dh, gated=True, need_dbias=True):
+    """-> (dx like x, dbias (E, 2 W | W) or None): the adjoint of moe_act_fwd with the bias gradient summed per expert"""
+    _check(dh is not None, "moe_act_bwd: dh is required")
+    return _moe_act_call(_lib.load().dimsum_moe_act_bwd, "moe_act_bwd", x, bias, row_expert, dh.contiguous() if dh is not None else None, gated, need_dbias)
+
+
 def split3_rows(x, left):
     """(R, K) float32 rows (stride(1) == 1) -> (R, 3K) bfloat16 split operand image: x = hi + lo, hi = bf16(x), lo = bf16(x - hi);
     left: [hi | hi | lo] (activations), else [hi | lo | hi] (weights), so that  left_image @ weight_image.T  accumulates

@@ -1,6 +1,7 @@
 """Operator API of the hot path (same names as the reference's Python op modules)."""
 from .causal_conv1d_interface import causal_conv1d_fn, causal_conv1d_update, causal_conv1d_update_torch  # noqa: F401
 from .layernorm import RMSNorm, layer_norm_fn, rms_norm_fn  # noqa: F401
+from .moe import moe_act, moe_act_torch, switch_mlp_fn, switch_mlp_torch  # noqa: F401
 from .selective_scan_interface import (  # noqa: F401
     bimamba_inner_fn,
     mamba_inner_fn,

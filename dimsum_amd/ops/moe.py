@@ -1,0 +1,163 @@
+"""The top-1 mixture-of-experts layer as ONE autograd function over the HIP row passes of csrc/moe.hip and per-expert GEMMs on contiguous row
+slices (SwitchMLP.forward, dimsum/switch_mlp.py:69-99; the expert, dimsum/mlp.py:42-46):
+
+    forward : route (router dot products, sigmoid / softmax, first-argmax, stable counting sort by expert)  ->  ONE host read of the E + 1 offsets
+              xp = x[perm]  ->  per expert e over rows [o_e, o_e+1): h1 = xp W1_e^T  ->  h = gelu_erf(h1a + b) (h1g + b)  [one pass, bias by row]
+              ->  y = h W2_e^T + b2_e  ->  out[perm[j]] = prob y[j]
+    backward: (dy, dprob) from (dout, y) in one pass  ->  per expert dW2, db2, dh  ->  the activation's adjoint (dbias per expert)  ->  per expert
+              dW1, dxp  ->  dx = dxp[inv] + dlogit W_r, dW_r, db_r in one pass (dlogit from the saved logits)
+An expert without tokens gets zero gradients (the reference calls every expert, with zero rows). The reference's forward runs E nonzero() host
+synchronisations, E indexed gathers and E indexed scatters into a zero-filled buffer instead.
+
+`switch_mlp_torch` / `moe_act_torch`: float64 restatements of the reference's expressions -- checkers, not product paths."""
+import torch
+import torch.nn.functional as F
+
+from .. import gemm, native
+
+
+def route_kind(routing_mode):
+    """the reference applies a sigmoid for routing_mode == 'sinkhorn' and a softmax for every other value (switch_mlp.py:75-80)"""
+    return "sigmoid" if routing_mode == "sinkhorn" else "softmax"
+
+
+def _mm_nt(a, w, out, bias=None, fp16=False):
+    """out (a view of the layer's buffer) = a w^T (+ bias); fp16: the "fp16" inference policy's operands (decided by the caller OUTSIDE the
+    autograd function: inside its forward grad mode is off and the policy's training guard could not fire)"""
+    if fp16:
+        y = gemm.linear(a, w)
+        out.copy_(y if bias is None else y + bias)
+    elif bias is None:
+        torch.mm(a, w.t(), out=out)
+    else:
+        torch.addmm(bias, a, w.t(), out=out)
+
+
+class _MoeActFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, bias, gated):
+        x = x.contiguous()
+        ctx.save_for_backward(x, bias)
+        ctx.gated = gated
+        return native.moe_act_fwd(x, bias, None, gated)
+
+    @staticmethod
+    def backward(ctx, dh):
+        x, bias = ctx.saved_tensors
+        dx, dbias = native.moe_act_bwd(x, bias, None, dh.contiguous(), ctx.gated, need_dbias=bias is not None and ctx.needs_input_grad[1])
+        return dx, dbias, None
+
+
+def moe_act(x, bias=None, gated=True):
+    """x (rows, 2 W | W), bias (2 W | W) or None -> gelu_erf(a + b) (g + b) or gelu_erf(x + b): the expert MLP's activation outside a SwitchMLP
+    (the pass of the mixture with one expert)"""
+    return _MoeActFn.apply(x, None if bias is None else bias.float().reshape(1, -1), gated)
+
+
+class _SwitchMlpFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, rw, rb, kind, gated, n_exp, has_bias, fp16, *ws):
+        E = n_exp
+        w1, w2 = ws[:E], ws[E:2 * E]
+        b1 = torch.stack(ws[2 * E:3 * E]).contiguous() if has_bias else None
+        b2 = ws[3 * E:4 * E] if has_bias else None
+        H = x.shape[-1]
+        x2 = x.reshape(-1, H).contiguous()
+        T = x2.shape[0]
+        prob, expert, logits, offsets, perm, inv, row_expert = native.moe_route_fwd(x2, rw.contiguous(), rb, kind)
+        off = offsets.tolist()                          # the layer's one device-to-host copy: E + 1 ints
+        xp = native.moe_permute(x2, perm)
+        h1 = x2.new_empty(T, w1[0].shape[0])
+        for e in range(E):
+            if off[e + 1] > off[e]:
+                _mm_nt(xp[off[e]:off[e + 1]], w1[e], h1[off[e]:off[e + 1]], fp16=fp16)
+        h = native.moe_act_fwd(h1, b1, row_expert, gated)
+        y = x2.new_empty(T, H)
+        for e in range(E):
+            if off[e + 1] > off[e]:
+                _mm_nt(h[off[e]:off[e + 1]], w2[e], y[off[e]:off[e + 1]], None if b2 is None else b2[e], fp16=fp16)
+        out = native.moe_combine_fwd(y, perm, prob)
+        ctx.save_for_backward(x2, rw, logits, prob, expert, perm, inv, row_expert, xp, h1, h, y, b1, *w1, *w2)
+        ctx.off, ctx.kind, ctx.gated, ctx.E, ctx.has_bias = off, kind, gated, E, has_bias
+        return out.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, rw, logits, prob, expert, perm, inv, row_expert, xp, h1, h, y, b1 = ctx.saved_tensors[:13]
+        E, off = ctx.E, ctx.off
+        w1, w2 = ctx.saved_tensors[13:13 + E], ctx.saved_tensors[13 + E:13 + 2 * E]
+        T, H = x2.shape
+        dy, dprob = native.moe_combine_bwd(dout.reshape(T, H).contiguous(), y, perm, prob)
+        dh = torch.empty_like(h)
+        dw1, dw2, db2 = [], [], []
+        for e in range(E):
+            o0, o1 = off[e], off[e + 1]
+            if o1 == o0:
+                dw2.append(torch.zeros_like(w2[e]))
+                db2.append(torch.zeros(H, device=dy.device, dtype=dy.dtype))
+                continue
+            dw2.append(gemm.mm_tn(dy[o0:o1], h[o0:o1]))
+            if ctx.has_bias:
+                db2.append(dy[o0:o1].sum(0))
+            torch.mm(dy[o0:o1], w2[e], out=dh[o0:o1])
+        dh1, db1 = native.moe_act_bwd(h1, b1, row_expert, dh, ctx.gated, need_dbias=ctx.has_bias)
+        dxp = torch.empty_like(xp)
+        for e in range(E):
+            o0, o1 = off[e], off[e + 1]
+            if o1 == o0:
+                dw1.append(torch.zeros_like(w1[e]))
+                continue
+            dw1.append(gemm.mm_tn(dh1[o0:o1], xp[o0:o1]))
+            torch.mm(dh1[o0:o1], w1[e], out=dxp[o0:o1])
+        dx, drw, drb = native.moe_route_bwd(x2, rw.contiguous(), logits, prob, expert, inv, dprob, dxp, ctx.kind)
+        grads = dw1 + dw2 + ((list(db1.unbind(0)) + db2) if ctx.has_bias else [])
+        return (dx.view(dout.shape), drw, drb if ctx.needs_input_grad[2] else None, None, None, None, None, None, *grads)
+
+
+def switch_mlp_fn(x, router_weight, router_bias, fc1_weights, fc2_weights, fc1_biases=None, fc2_biases=None, routing_mode="top1", gated=True):
+    """x (..., H) float32 on the GPU -> prob * expert_e(x) per token, e = the first maximum of sigmoid / softmax of the router logits"""
+    if x.dtype != torch.float32 or any(w.dtype != torch.float32 for w in (router_weight, *fc1_weights, *fc2_weights)):
+        raise RuntimeError("switch_mlp: float32 tokens and parameters only (there is no other kernel and no fallback)")
+    E = len(fc1_weights)
+    has_bias = fc1_biases is not None
+    ws = list(fc1_weights) + list(fc2_weights) + ((list(fc1_biases) + list(fc2_biases)) if has_bias else [])
+    # the "fp16" policy serves inference only (gemm._use_fp16): asked here, where grad mode and requires_grad still say whether this call trains
+    fp16 = all(gemm._use_fp16(x, w) for w in (router_weight, *ws))
+    return _SwitchMlpFn.apply(x, router_weight, router_bias, route_kind(routing_mode), bool(gated), E, has_bias, fp16, *ws)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# float64 restatements (checkers)
+# ---------------------------------------------------------------------------------------------------------------------
+def moe_act_torch(x, bias=None, row_expert=None, gated=True):
+    """float64: gelu_erf(a + b_a) * (g + b_g) over the halves of x (gated) or gelu_erf(x + b); bias (E, S) rows picked by row_expert (None: row 0)"""
+    x = x.double()
+    if bias is not None:
+        b = bias.double()
+        x = x + (b[row_expert.long()] if row_expert is not None else b.reshape(-1, x.shape[-1])[0])
+    if gated:
+        a, g = x.chunk(2, dim=-1)
+        return F.gelu(a) * g
+    return F.gelu(x)
+
+
+def switch_mlp_torch(x, router_weight, router_bias, fc1_weights, fc2_weights, fc1_biases=None, fc2_biases=None, routing_mode="top1", gated=True):
+    """float64, differentiable -> (out like x, expert (T) int64): SwitchMLP.forward as the reference writes it (switch_mlp.py:69-99) with the
+    indexed scatter as an index_copy"""
+    H = x.shape[-1]
+    x2 = x.double().reshape(-1, H)
+    logits = x2 @ router_weight.double().t()
+    if router_bias is not None:
+        logits = logits + router_bias.double()
+    route = torch.sigmoid(logits) if routing_mode == "sinkhorn" else torch.softmax(logits, dim=1)
+    p, e = torch.max(route, dim=1)
+    out = torch.zeros_like(x2)
+    for i in range(len(fc1_weights)):
+        idx = (e == i).nonzero().squeeze(1)
+        h1 = x2[idx] @ fc1_weights[i].double().t()
+        h = moe_act_torch(h1, None if fc1_biases is None else fc1_biases[i].double().reshape(1, -1), None, gated)
+        y = h @ fc2_weights[i].double().t()
+        if fc2_biases is not None:
+            y = y + fc2_biases[i].double()
+        out = out.index_copy(0, idx, y)
+    return (out * p.unsqueeze(1)).view(x.shape), e

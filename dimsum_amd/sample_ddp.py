@@ -98,6 +98,10 @@ def build_parser():
     ap.add_argument("--num-classes", type=int, default=1000)
     ap.add_argument("--pe-type", default="ape", choices=["ape", "rope", "cpe"], help="positional encoding the checkpoint was trained with")
     ap.add_argument("--block-type", default="combined", choices=list(BLOCK_TYPES), help="block type the checkpoint was trained with")
+    ap.add_argument("--is-moe", action="store_true", help="every odd layer is a top-1 mixture-of-experts block (train.py --is-moe)")
+    ap.add_argument("--num-moe-experts", type=int, default=8, help="experts per mixture-of-experts layer")
+    ap.add_argument("--mamba-moe-layers", type=lambda v: None if v == "None" else v, nargs="*", default=None,
+                    help="one entry per layer; the last character of entry layer_idx - 1 is that layer's expert count")
     ap.add_argument("--per-proc-batch-size", type=int, default=128)
     ap.add_argument("--num-fid-samples", type=int, default=1024)
     ap.add_argument("--num-sampling-steps", type=int, default=250)

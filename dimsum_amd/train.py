@@ -111,6 +111,10 @@ def build_parser():
     ap.add_argument("--global-batch-size", type=int, default=704)       # scripts/train.sh:86-112
     ap.add_argument("--pe-type", default="ape", choices=["ape", "rope", "cpe"], help="positional encoding of the embed pass (train.py --pe-type)")
     ap.add_argument("--block-type", default="combined", choices=list(BLOCK_TYPES), help="block of the denoiser (train.py --block-type)")
+    ap.add_argument("--is-moe", action="store_true", help="every odd layer is a top-1 mixture-of-experts block (train.py --is-moe)")
+    ap.add_argument("--num-moe-experts", type=int, default=8, help="experts per mixture-of-experts layer")
+    ap.add_argument("--mamba-moe-layers", type=lambda v: None if v == "None" else v, nargs="*", default=None,
+                    help="one entry per layer; the last character of entry layer_idx - 1 is that layer's expert count")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--max-grad-norm", type=float, default=2.0)
     ap.add_argument("--path-type", default="GVP")

@@ -20,6 +20,7 @@
  *   dimsum_xattn_fusion_fwd/_bwd <- F.scaled_dot_product_attention x2 (+ autograd)  dimsum/attention_fusion.py:44-75
  *   dimsum_gated_gelu_fwd/_bwd <- gelu_tanh(x1) * x2                             dimsum/mlp.py:66-70
  *   dimsum_gelu_fwd/_bwd       <- timm Mlp's act: gelu_tanh(fc1(x) + b)                  dimsum/models_dit.py:124
+ *   dimsum_moe_*               <- SwitchMLP's routing, nonzero() gathers / scatters and exact-GELU experts  dimsum/switch_mlp.py:69-99, mlp.py:7-46
  *   dimsum_gemm_nt             <- nn.Linear / F.linear of the bias-free projections (cuBLAS TF32 GEMMs under train.py:20-21), and
  *                                 w12 + bias + gelu_tanh(x1) * x2 of the GatedMLP as ONE kernel    dimsum/mlp.py:49-70
  *
@@ -897,6 +898,86 @@ typedef struct {
 
 int dimsum_gelu_fwd(const dimsum_gelu_params_t *p, void *stream);
 int dimsum_gelu_bwd(const dimsum_gelu_params_t *p, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The row passes of the top-1 mixture-of-experts layer (SwitchMLP, dimsum/switch_mlp.py:69-99; the expert MLP, dimsum/mlp.py:7-46) around the
+ * per-expert GEMMs, which the host runs over contiguous row slices of the tokens sorted by expert. Everything is f32 rows, width % 4 == 0,
+ * 16-byte aligned; 1 <= num_experts <= 64; other shapes are DIMSUM_ERR_SHAPE. Index tables are int32.
+ *
+ * dimsum_moe_route_fwd (three launches): x (tokens, hidden), w (E, hidden), b (E) or NULL ->
+ *   logits (tokens, E) = x w^T + b: f32 accumulation, the same reduction order for every expert (identical router rows give identical logits);
+ *   route = softmax(logits, 1) (DIMSUM_MOE_ROUTE_SOFTMAX) or sigmoid(logits) (DIMSUM_MOE_ROUTE_SIGMOID);
+ *   prob (tokens), expert (tokens) = max(route, 1), the first maximum on ties;
+ *   the stable counting sort of the tokens by expert: offsets (E + 1), perm (tokens) = the token in sorted row j, inv (tokens) = perm's inverse,
+ *   row_expert (tokens) = expert[perm[j]]. Deterministic: no atomic decides a position. work: dimsum_moe_route_work_bytes() bytes of scratch.
+ *   tokens == 0 is a valid call of every dimsum_moe_* entry (the row pointers may then be NULL): route_fwd writes E + 1 zero offsets, the others do nothing.
+ * dimsum_moe_route_bwd: reads x, w, logits, prob, expert, inv, dprob (tokens), dxp (tokens, hidden) in sorted order ->
+ *   dlogit = dprob p (1 - p) at the chosen expert (sigmoid) or dprob p* (delta - p_e) (softmax), formed in the kernel;
+ *   dx[t] = dxp[inv[t]] + sum_e dlogit[t, e] w[e];  dw (E, hidden) and db (E): zero-filled by the caller, f32 atomics (one per element per
+ *   workgroup). num_experts > 8: dx is written once and updated in place per group of 8 experts.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef enum { DIMSUM_MOE_ROUTE_SOFTMAX = 0, DIMSUM_MOE_ROUTE_SIGMOID = 1 } dimsum_moe_route_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_moe_ext_t) as the caller compiled it (see "Versioning" at the top) */
+    int32_t reserved;          /* 0 */
+} dimsum_moe_ext_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_moe_route_params_t) as the caller compiled it; anything else -> DIMSUM_ERR_ABI */
+    int32_t mode;              /* dimsum_moe_route_t */
+    int32_t num_experts;
+    int32_t reserved;          /* 0 */
+    int64_t tokens, hidden;
+    const void *x_ptr, *w_ptr, *b_ptr;
+    void *prob_ptr, *expert_ptr, *logits_ptr;                   /* fwd: written; bwd: read */
+    void *offsets_ptr, *perm_ptr, *inv_ptr, *row_expert_ptr;    /* fwd: written; bwd: inv is read, the others are ignored */
+    void *work_ptr;            /* fwd */
+    int64_t work_bytes;
+    const void *dprob_ptr, *dxp_ptr;                            /* bwd */
+    void *dx_ptr, *dw_ptr, *db_ptr;                             /* bwd */
+    const dimsum_moe_ext_t *ext;   /* NULL = none */
+} dimsum_moe_route_params_t;
+
+int64_t dimsum_moe_route_work_bytes(int64_t tokens, int32_t num_experts);
+int dimsum_moe_route_fwd(const dimsum_moe_route_params_t *p, void *stream);
+int dimsum_moe_route_bwd(const dimsum_moe_route_params_t *p, void *stream);
+
+/* dimsum_moe_permute    : dst[j, :] = src[perm[j], :]
+ * dimsum_moe_combine_fwd: dst[perm[j], :] = prob[perm[j]] src[j, :]       (perm is a permutation: every row of dst is written exactly once)
+ * dimsum_moe_combine_bwd: src = dout (token order), y (sorted order): dst[j, :] = prob[t] dout[t, :], dprob[t] = <dout[t, :], y[j, :]>, t = perm[j]
+ * perm's entries must lie in [0, rows). */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_moe_rows_params_t) */
+    int32_t reserved;          /* 0 */
+    int64_t rows, hidden;
+    const void *src_ptr, *perm_ptr, *prob_ptr, *y_ptr;
+    void *dst_ptr, *dprob_ptr;
+    const dimsum_moe_ext_t *ext;   /* NULL = none */
+} dimsum_moe_rows_params_t;
+
+int dimsum_moe_permute(const dimsum_moe_rows_params_t *p, void *stream);
+int dimsum_moe_combine_fwd(const dimsum_moe_rows_params_t *p, void *stream);
+int dimsum_moe_combine_bwd(const dimsum_moe_rows_params_t *p, void *stream);
+
+/* The experts' activation over the sorted rows, exact (erf) GELU. S = gated ? 2 width : width; x (rows, S) = the fc1 GEMM output WITHOUT bias;
+ * bias (num_experts, S) or NULL, the row taken by row_expert[r] (row_expert NULL: num_experts == 1, row 0 for every r).
+ *   fwd: out (rows, width) = gelu_erf(x[:, :width] + b) * (x[:, width:] + b)   (gated)   or   gelu_erf(x + b)
+ *   bwd: out (rows, S) = d x from dh (rows, width), derivative Phi(a) + a phi(a); dbias (num_experts, S) zero-filled by the caller or NULL:
+ *        column sums per expert, held in registers over 64 rows, one f32 atomic per column at an expert boundary and at the chunk's end. */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_moe_act_params_t) */
+    int32_t gated;             /* bool */
+    int32_t num_experts;
+    int32_t reserved;          /* 0 */
+    int64_t rows, width;
+    const void *x_ptr, *bias_ptr, *row_expert_ptr, *dh_ptr;
+    void *out_ptr, *dbias_ptr;
+    const dimsum_moe_ext_t *ext;   /* NULL = none */
+} dimsum_moe_act_params_t;
+
+int dimsum_moe_act_fwd(const dimsum_moe_act_params_t *p, void *stream);
+int dimsum_moe_act_bwd(const dimsum_moe_act_params_t *p, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * NT GEMM with a fused Linear epilogue: C (m, n) = A (m, k) . B (n, k)^T, 16-bit operands (bf16 or fp16 rows, k contiguous), fp32

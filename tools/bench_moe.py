@@ -1,0 +1,113 @@
+"""tools/bench_moe.py (GPU box): one SwitchMLP (dimsum_amd/switch_mlp.py) at DiM-L/2's token shape -- 65536 tokens x 1024 channels, 8 experts,
+float32 -- forward and forward + backward, against a torch composition written as the reference writes it (a loop over the experts with
+nonzero(), indexed gathers and indexed scatters into a zero-filled buffer; switch_mlp.py:69-99) in the same process on the same weights; then
+each row pass of csrc/moe.hip alone with its algorithmic bytes over its time, next to gelu_fwd at equal bytes. Device events around windows of
+calls, minimum and median over the windows. Prints figures only: no threshold is asserted anywhere.   [--tokens N --dim H --experts E]"""
+import argparse
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from dimsum_amd import native  # noqa: E402
+from dimsum_amd.switch_mlp import SwitchMLP  # noqa: E402
+
+
+def window(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def timed(fn, n=10, rounds=5):
+    for _ in range(3):
+        fn()
+    t = sorted(window(fn, n) for _ in range(rounds))
+    return t[0], t[rounds // 2]
+
+
+def reference_forward(m, x):
+    """SwitchMLP.forward as the reference composes it from torch operators"""
+    shape = x.shape
+    route = torch.softmax(m.router(x).view(-1, m.num_moe_experts), dim=1) if m.routing != "sinkhorn" else torch.sigmoid(m.router(x).view(-1, m.num_moe_experts))
+    p, ind = torch.max(route, dim=1)
+    h = x.view(-1, shape[-1])
+    total = torch.zeros_like(h)
+    for i, ex in enumerate(m.local_experts):
+        idx = (ind == i).nonzero()
+        a = F.linear(h[idx, :], ex.linear_fc1.weight, ex.linear_fc1.bias)
+        if m.gated_linear_unit:
+            a1, a2 = torch.chunk(a, 2, dim=-1)
+            a = F.gelu(a1) * a2
+        else:
+            a = F.gelu(a)
+        total[idx, :] = F.linear(a, ex.linear_fc2.weight, ex.linear_fc2.bias)
+    return (total * p.unsqueeze(1)).view(shape)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tokens", type=int, default=65536)
+    ap.add_argument("--dim", type=int, default=1024)
+    ap.add_argument("--experts", type=int, default=8)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_moe.py needs the GPU"
+    T, H, E = args.tokens, args.dim, args.experts
+    torch.manual_seed(0)
+    m = SwitchMLP(H, layer_idx=1, num_moe_experts=E).cuda()
+    x = torch.randn(1, T, H, device="cuda", requires_grad=True)
+    dout = torch.randn_like(x)
+
+    def fb(fwd):
+        def run():
+            m.zero_grad(set_to_none=True)
+            x.grad = None
+            fwd(m, x).backward(dout)
+        return run
+
+    with torch.no_grad():
+        ours, ref = m(x), reference_forward(m, x)
+    print(f"SwitchMLP {T} x {H}, {E} experts, float32; max |ours - composition| = {(ours - ref).abs().max().item():.3e} (max |out| {ref.abs().max().item():.3e})")
+    with torch.no_grad():
+        for name, fn in (("fused passes", lambda: m(x)), ("torch composition", lambda: reference_forward(m, x))):
+            lo, med = timed(fn)
+            print(f"  forward            {name:18s} min {lo:8.3f} ms  median {med:8.3f} ms")
+    for name, fn in (("fused passes", fb(lambda mm, xx: mm(xx))), ("torch composition", fb(reference_forward))):
+        lo, med = timed(fn, n=5)
+        print(f"  forward + backward {name:18s} min {lo:8.3f} ms  median {med:8.3f} ms")
+
+    # the passes alone: algorithmic bytes / time
+    with torch.no_grad():
+        x2 = x.detach().view(T, H)
+        w, b = m.router.weight.detach(), m.router.bias.detach()
+        prob, expert, logits, offsets, perm, inv, row_expert = native.moe_route_fwd(x2, w, b, "softmax")
+        xp = native.moe_permute(x2, perm)
+        h1 = torch.randn(T, 8 * H, device="cuda")
+        hh = native.moe_act_fwd(h1, None, row_expert, True)
+        dh = torch.randn_like(hh)
+        y, dprob = torch.randn_like(x2), torch.randn(T, device="cuda")
+        f4 = 4.0
+        passes = [
+            ("moe_route_fwd (+ sort)", lambda: native.moe_route_fwd(x2, w, b, "softmax"), T * H * f4),
+            ("moe_permute", lambda: native.moe_permute(x2, perm), 2 * T * H * f4),
+            ("moe_act_fwd (gated)", lambda: native.moe_act_fwd(h1, None, row_expert, True), 12 * T * H * f4),
+            ("moe_act_bwd (gated)", lambda: native.moe_act_bwd(h1, None, row_expert, dh, True), 20 * T * H * f4),
+            ("moe_combine_fwd", lambda: native.moe_combine_fwd(y, perm, prob), 2 * T * H * f4),
+            ("moe_combine_bwd", lambda: native.moe_combine_bwd(x2, y, perm, prob), 3 * T * H * f4),
+            ("moe_route_bwd", lambda: native.moe_route_bwd(x2, w, logits, prob, expert, inv, dprob, xp, "softmax"), 3 * T * H * f4),
+            ("gelu_fwd (2 T H 4 bytes)", lambda: native.gelu_fwd(x2), 2 * T * H * f4),
+            ("gelu_fwd (12 T H 4 bytes)", lambda: native.gelu_fwd(h1.view(-1)[:6 * T * H].view(T, 6 * H)), 12 * T * H * f4),
+        ]
+        for name, fn, nbytes in passes:
+            lo, med = timed(fn, n=20)
+            print(f"  {name:28s} min {lo * 1e3:9.1f} us  median {med * 1e3:9.1f} us  {nbytes / lo / 1e6:8.1f} GB/s")
+
+
+if __name__ == "__main__":
+    main()

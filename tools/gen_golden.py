@@ -973,6 +973,51 @@ def gen_dit_keys(_ns=None):
     print(f"  dit_keys.json: {len(keys)} keys")
 
 
+def gen_moe(ns):
+    """tests/golden/moe_switch.npz (routing_mode "top1": softmax) and moe_switch_sinkhorn.npz (routing_mode "sinkhorn": sigmoid) -- the reference's
+    SwitchMLP (dimsum/switch_mlp.py) on the CPU at dim 32, tokens (2, 24), 4 experts over {gated, plain} x {bias, no bias}: output, chosen expert
+    per token, d x and every parameter gradient; weights = procedural_fill(module, seed) (not stored: the test fills its own module the same
+    way). One file per routing mode keeps each under the repository's size limit. moe_switch.npz also holds one sinkhorn() input / output pair,
+    one MLP forward and one MoEBlock(SwitchMLP, nn.LayerNorm) forward. tests/golden/moe_keys.json: state_dict keys and shapes of that block."""
+    import json
+    from functools import partial
+    md = ns.models_dim
+    import switch_mlp as sw
+    assert os.path.realpath(sw.__file__).startswith(os.path.realpath(ref_shim.REF)), sw.__file__
+    dim, E = 32, 4
+    x, dout = T(seeded((2, 24, dim), 501)), T(seeded((2, 24, dim), 502))
+    for mode, name in (("top1", "moe_switch"), ("sinkhorn", "moe_switch_sinkhorn")):
+        arrs = {"x": x, "dout": dout}
+        for ci, (gated, bias) in enumerate(((True, True), (True, False), (False, True), (False, False))):
+            tag = f"{'gated' if gated else 'plain'}_{'bias' if bias else 'nobias'}"
+            seed = 40 + ci
+            m = procedural_fill(sw.SwitchMLP(dim, layer_idx=1, num_moe_experts=E, add_bias_linear=bias, gated_linear_unit=gated, routing_mode=mode), seed=seed)
+            xr = x.clone().requires_grad_()
+            out = m(xr)
+            out.backward(dout)
+            with torch.no_grad():
+                logits = m.router(x).view(-1, E)
+                route = torch.sigmoid(logits) if mode == "sinkhorn" else torch.softmax(logits, dim=1)
+            arrs.update({f"{tag}.seed": np.int64(seed), f"{tag}.out": out, f"{tag}.dx": xr.grad, f"{tag}.expert": torch.max(route, dim=1)[1]})
+            for k, p_ in m.named_parameters():
+                arrs[f"{tag}.grad.{k}"] = torch.zeros_like(p_) if p_.grad is None else p_.grad
+        if mode == "top1":
+            cost = T(seeded((6, E), 503, scale=0.5))
+            arrs.update({"sinkhorn.cost": cost, "sinkhorn.out": sw.sinkhorn(cost)})
+            mlp = procedural_fill(ns.mlp.MLP(dim, add_bias_linear=True, gated_linear_unit=True), seed=50)
+            arrs["mlp.out"] = mlp(x)
+            blk = procedural_fill(md.MoEBlock(dim, mixer_cls=partial(md.SwitchMLP, layer_idx=1, num_moe_experts=E), norm_cls=torch.nn.LayerNorm), seed=51)
+            h, r = blk(x, dout)
+            arrs.update({"block.out": h, "block.residual": r})
+            keys = [[k, list(v.shape)] for k, v in blk.state_dict().items()]
+            with open(os.path.join(OUT, "moe_keys.json"), "w") as f:
+                json.dump(keys, f, indent=0)
+                f.write("\n")
+            print(f"  moe_keys.json: {len(keys)} keys")
+        save(name, f"reference SwitchMLP (dimsum/switch_mlp.py:24-99) on the CPU, routing_mode={mode}, dim {dim}, tokens (2, 24), {E} experts; weights: "
+                   "procedural_fill(module, <tag>.seed); x, dout: stored", **arrs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -992,7 +1037,7 @@ def main():
         "transport_blur": lambda: gen_transport_blur(ns),
         "block_linear_window": lambda: gen_block_linear_window(ns), "tiny_linear_window": lambda: gen_model_tiny_linear_window(ns),
         "pe": lambda: gen_pe(ns), "einfft": lambda: gen_einfft(ns), "dit_keys": lambda: gen_dit_keys(ns), "step": lambda: gen_step(ns),
-        "scan_general": lambda: gen_scan_general(ns),
+        "scan_general": lambda: gen_scan_general(ns), "moe": lambda: gen_moe(ns),
     }
     for k, fn in steps.items():
         if args.only is None or k in args.only:
