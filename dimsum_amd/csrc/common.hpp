@@ -29,6 +29,8 @@ template <typename T> __device__ __forceinline__ Raw4<T> ld4(const T *p);
 template <> __device__ __forceinline__ Raw4<float> ld4<float>(const float *p) { return {*reinterpret_cast<const float4 *>(p)}; }
 template <> __device__ __forceinline__ Raw4<__half> ld4<__half>(const __half *p) { return {*reinterpret_cast<const uint2 *>(p)}; }
 template <> __device__ __forceinline__ Raw4<__hip_bfloat16> ld4<__hip_bfloat16>(const __hip_bfloat16 *p) { return {*reinterpret_cast<const uint2 *>(p)}; }
+__device__ __forceinline__ float4 ldf4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ void stf4(float *p, const float4 &v) { *reinterpret_cast<float4 *>(p) = v; }
 
 __device__ __forceinline__ f32x4 widen(const Raw4<float> &a) { return {{a.r.x, a.r.y, a.r.z, a.r.w}}; }
 __device__ __forceinline__ f32x4 widen(const Raw4<__half> &a) {
@@ -263,6 +265,14 @@ inline int launch_status() { return hipGetLastError() == hipSuccess ? DIMSUM_OK 
         if ((EV0) || (EV1)) hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, STREAM, EV0, EV1, 0, __VA_ARGS__);      \
         else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, STREAM, __VA_ARGS__);                                     \
     } while (0)
+
+// the grid of a flat pass (one thread = one 16-byte piece, 4 pieces per thread a grid stride apart): one round; false if it does not fit
+inline bool flat_grid(int64_t total, dim3 &grid) {
+    const int64_t blocks = (total + 256 * 4 - 1) / (256 * 4);
+    if (blocks > 0x7fffffff) return false;
+    grid = dim3((unsigned)blocks);
+    return true;
+}
 
 template <typename T> inline bool aligned_to(const void *p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) % bytes) == 0; }
 

@@ -161,7 +161,7 @@ __device__ __forceinline__ f4 pick(unsigned m, const f4 &a, const f4 &b) {
 #define DIMSUM_WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
 __device__ __forceinline__ float gelu_tanh_f(float x) {
-    // 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) = x sigmoid(2 u): the same form as token_transform.hip's gated GeLU pass
+    // 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) = x sigmoid(2 u): the form of act_rows.hip's GeluSigmoid (the plain Mlp's row pass)
     const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
     return x * fast_rcp(1.0f + fast_exp2(-2.0f * kLog2e * u));
 }

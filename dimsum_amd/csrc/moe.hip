@@ -3,7 +3,7 @@
 //   route_fwd   : router dot products + sigmoid / softmax + first-argmax per token, then a stable counting sort of the tokens by expert
 //                 (three launches: route + per-block counts, scan of the counts, placement). No atomic decides a position.
 //   permute     : xp[j] = x[perm[j]]                                  combine_fwd : out[perm[j]] = prob[perm[j]] y[j] (every token written once)
-//   act_fwd/bwd : gelu_erf(a + b_a) (g + b_g) or gelu_erf(a + b), the bias row picked by the row's expert; dbias per expert
+//   (the experts' activation between the two GEMMs, dimsum_moe_act_fwd / _bwd, is one of the activation row passes of act_rows.hip)
 //   combine_bwd : dy[j] = prob[t] dout[t], dprob[t] = <dout[t], y[j]>   route_bwd : dx = dxp[inv] + dlogit W_r, dW_r, db_r
 // All fp32 rows with width % 4 == 0 and 16-byte accesses; 1 <= E <= 64. HBM-bound: bytes per element are listed in DESIGN.md section 3.15.
 #include "common.hpp"
@@ -13,7 +13,7 @@ namespace {
 
 constexpr int kBlk = 64;          // tokens per workgroup of the route pass = per wave of the placement pass: the unit of the counting sort
 constexpr int kXr = 8;            // 16-byte pieces of a token's row a lane keeps in registers across the experts (rows up to 2048 columns)
-constexpr int kRows = 64;         // rows per chunk of the passes that keep column sums in registers (gelu_bwd_kernel's shape)
+constexpr int kRows = 64;         // tokens per tile of the router's backward (their dlogit values sit in LDS)
 constexpr int kEG = 8;            // experts per register group of the router's backward
 
 __device__ __forceinline__ float wave_allsum(float v) {        // butterfly: every lane ends with the same bits
@@ -23,14 +23,6 @@ __device__ __forceinline__ float wave_allsum(float v) {        // butterfly: eve
 }
 __device__ __forceinline__ float dot4(const float4 &a, const float4 &b, float acc) {
     return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, acc))));
-}
-__device__ __forceinline__ float4 ldf4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void stf4(float *p, const float4 &v) { *reinterpret_cast<float4 *>(p) = v; }
-
-// exact GELU and its derivative Phi(a) + a phi(a)
-__device__ __forceinline__ float gelu_erf(float a) { return 0.5f * a * (1.0f + erff(a * 0.7071067811865476f)); }
-__device__ __forceinline__ float gelu_erf_grad(float a) {
-    return 0.5f * (1.0f + erff(a * 0.7071067811865476f)) + a * 0.3989422804014327f * expf(-0.5f * a * a);
 }
 
 // ---- pass a: one wave per token, 16 tokens per wave, kBlk tokens per workgroup. The E dot products of a token run through the same loop and the
@@ -156,7 +148,7 @@ __global__ __launch_bounds__(64) void moe_place_kernel(const int *expert, const 
 }
 
 // ---- passes c and e (forward): rows moved through the sort's table. One thread = one 16-byte piece, 4 independent pieces in flight a grid stride
-// apart (gelu_fwd_kernel's flat mapping). kScatter: dst[perm[j]] = prob[perm[j]] src[j], else dst[j] = src[perm[j]].
+// apart (the flat mapping of act_rows.hip's forward). kScatter: dst[perm[j]] = prob[perm[j]] src[j], else dst[j] = src[perm[j]].
 template <bool kScatter>
 __global__ __launch_bounds__(256) void moe_rows_kernel(const float *src, const int *perm, const float *prob, float *dst, int64_t rows, int64_t H) {
     const int64_t q = H / 4, total = rows * q;
@@ -210,87 +202,6 @@ __global__ __launch_bounds__(256) void moe_combine_bwd_kernel(const float *dout,
     }
     acc = wave_allsum(acc);
     if (lane == 0) dprob[t] = acc;
-}
-
-// ---- pass d, forward: x (rows, kGated ? 2 W : W) -> h (rows, W); the flat mapping of moe_rows_kernel
-template <bool kGated>
-__global__ __launch_bounds__(256) void moe_act_fwd_kernel(const float *x, const float *bias, const int *row_expert, float *h, int64_t rows, int64_t W) {
-    const int64_t q = W / 4, total = rows * q, S = kGated ? 2 * W : W;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x; i0 < total; i0 += 4 * stride) {
-        float4 a[4], g[4];
-        int64_t rr[4], cc[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t i = min(i0 + k * stride, total - 1);
-            rr[k] = i / q; cc[k] = (i - rr[k] * q) * 4;
-            a[k] = ldf4(x + rr[k] * S + cc[k]);
-            if constexpr (kGated) g[k] = ldf4(x + rr[k] * S + W + cc[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (i0 + k * stride >= total) break;
-            const float *br = bias ? bias + (row_expert ? (int64_t)row_expert[rr[k]] : 0) * S : nullptr;
-            const float4 ba = br ? ldf4(br + cc[k]) : zero;
-            float4 o = make_float4(gelu_erf(a[k].x + ba.x), gelu_erf(a[k].y + ba.y), gelu_erf(a[k].z + ba.z), gelu_erf(a[k].w + ba.w));
-            if constexpr (kGated) {
-                const float4 bg = br ? ldf4(br + W + cc[k]) : zero;
-                o = make_float4(o.x * (g[k].x + bg.x), o.y * (g[k].y + bg.y), o.z * (g[k].z + bg.z), o.w * (g[k].w + bg.w));
-            }
-            stf4(h + rr[k] * W + cc[k], o);
-        }
-    }
-}
-
-// ---- pass d, backward: one workgroup = a strip of 1024 columns x a chunk of kRows rows (gelu_bwd_kernel's shape). The column sums of dx stay in
-// registers while the rows' expert stays the same: flushed with one atomic per column at an expert boundary and at the end of the chunk.
-template <bool kGated>
-__global__ __launch_bounds__(256) void moe_act_bwd_kernel(const float *x, const float *bias, const int *row_expert, const float *dh, float *dx,
-                                                          float *dbias, int64_t rows, int64_t W) {
-    const int64_t c = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (c >= W) return;
-    const int64_t S = kGated ? 2 * W : W;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int64_t r0 = (int64_t)blockIdx.y * kRows, r1 = min(rows, r0 + kRows);
-    int cur = -1;
-    float4 ba = zero, bg = zero;
-    f32x4 sa = {{0.f, 0.f, 0.f, 0.f}}, sg = {{0.f, 0.f, 0.f, 0.f}};
-    auto flush = [&]() {
-        if (dbias && cur >= 0) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                atomicAdd(dbias + cur * S + c + e, sa.v[e]);
-                if constexpr (kGated) atomicAdd(dbias + cur * S + W + c + e, sg.v[e]);
-            }
-        }
-        sa = f32x4{{0.f, 0.f, 0.f, 0.f}}; sg = f32x4{{0.f, 0.f, 0.f, 0.f}};
-    };
-    for (int64_t r = r0; r < r1; ++r) {
-        const int ex = row_expert ? row_expert[r] : 0;       // (uniform over the workgroup)
-        if (ex != cur) {
-            flush();
-            cur = ex;
-            if (bias) { ba = ldf4(bias + cur * S + c); if constexpr (kGated) bg = ldf4(bias + cur * S + W + c); }
-        }
-        const float4 a4 = ldf4(x + r * S + c), d4 = ldf4(dh + r * W + c);
-        const float a[4] = {a4.x + ba.x, a4.y + ba.y, a4.z + ba.z, a4.w + ba.w}, d[4] = {d4.x, d4.y, d4.z, d4.w};
-        f32x4 da, dg;
-        if constexpr (kGated) {
-            const float4 g4 = ldf4(x + r * S + W + c);
-            const float g[4] = {g4.x + bg.x, g4.y + bg.y, g4.z + bg.z, g4.w + bg.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { da.v[e] = d[e] * g[e] * gelu_erf_grad(a[e]); dg.v[e] = d[e] * gelu_erf(a[e]); sg.v[e] += dg.v[e]; }
-            stf4(dx + r * S + W + c, make_float4(dg.v[0], dg.v[1], dg.v[2], dg.v[3]));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) da.v[e] = d[e] * gelu_erf_grad(a[e]);
-        }
-        stf4(dx + r * S + c, make_float4(da.v[0], da.v[1], da.v[2], da.v[3]));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sa.v[e] += da.v[e];
-    }
-    flush();
 }
 
 // ---- pass f: the router's adjoint. One workgroup = a strip of 1024 columns x rows_per_wg tokens, walked in tiles of kRows rows whose dlogit
@@ -372,14 +283,6 @@ __global__ __launch_bounds__(256) void moe_route_bwd_kernel(const float *x, cons
 inline bool al16(const void *p) { return aligned_to<char>(p, 16); }
 inline bool al4(const void *p) { return aligned_to<char>(p, 4); }
 
-// the flat passes' grid: one round of 4 pieces per thread
-inline bool flat_grid(int64_t total, dim3 &grid) {
-    const int64_t blocks = (total + 256 * 4 - 1) / (256 * 4);
-    if (blocks > 0x7fffffff) return false;
-    grid = dim3((unsigned)blocks);
-    return true;
-}
-
 // (every check below: struct sizes, then shapes, then -- for a call with rows -- pointers and alignment; an empty call needs no row pointers)
 int route_params_ok(const dimsum_moe_route_params_t *p, bool bwd) {
     if (!p) return DIMSUM_ERR_NULL;
@@ -411,19 +314,6 @@ int rows_params_ok(const dimsum_moe_rows_params_t *p, bool need_prob, bool bwd) 
     if (p->rows == 0) return DIMSUM_OK;
     if (!p->src_ptr || !p->perm_ptr || !p->dst_ptr || (need_prob && !p->prob_ptr) || (bwd && (!p->y_ptr || !p->dprob_ptr))) return DIMSUM_ERR_NULL;
     if (!al16(p->src_ptr) || !al16(p->dst_ptr) || !al16(p->y_ptr) || !al4(p->perm_ptr) || !al4(p->prob_ptr) || !al4(p->dprob_ptr)) return DIMSUM_ERR_STRIDE;
-    return DIMSUM_OK;
-}
-
-int act_params_ok(const dimsum_moe_act_params_t *p, bool bwd) {
-    if (!p) return DIMSUM_ERR_NULL;
-    if (p->struct_size != sizeof(dimsum_moe_act_params_t)) return DIMSUM_ERR_ABI;
-    dimsum_moe_ext_t e;
-    if (const int rc = ext_from<dimsum_moe_ext_t>(p->ext, e)) return rc;
-    if (p->rows < 0 || p->width <= 0 || p->width % 4 != 0 || p->num_experts < 1 || p->num_experts > 64) return DIMSUM_ERR_SHAPE;
-    if (p->rows == 0) return DIMSUM_OK;
-    if (!p->x_ptr || !p->out_ptr || (bwd && !p->dh_ptr) || (p->dbias_ptr && !p->bias_ptr)) return DIMSUM_ERR_NULL;
-    if (!p->row_expert_ptr && p->num_experts != 1) return DIMSUM_ERR_NULL;
-    if (!al16(p->x_ptr) || !al16(p->out_ptr) || !al16(p->bias_ptr) || !al16(p->dh_ptr) || !al4(p->row_expert_ptr) || !al4(p->dbias_ptr)) return DIMSUM_ERR_STRIDE;
     return DIMSUM_OK;
 }
 
@@ -511,36 +401,5 @@ extern "C" int dimsum_moe_combine_bwd(const dimsum_moe_rows_params_t *p, void *s
                        reinterpret_cast<const float *>(p->src_ptr), reinterpret_cast<const float *>(p->y_ptr), reinterpret_cast<const int *>(p->perm_ptr),
                        reinterpret_cast<const float *>(p->prob_ptr), reinterpret_cast<float *>(p->dst_ptr), reinterpret_cast<float *>(p->dprob_ptr),
                        p->rows, p->hidden);
-    return launch_status();
-}
-
-extern "C" int dimsum_moe_act_fwd(const dimsum_moe_act_params_t *p, void *stream) {
-    using namespace dimsum;
-    if (const int rc = act_params_ok(p, false)) return rc;
-    if (p->rows == 0) return DIMSUM_OK;
-    dim3 grid;
-    if (!flat_grid(p->rows * (p->width / 4), grid)) return DIMSUM_ERR_SHAPE;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const float *x = reinterpret_cast<const float *>(p->x_ptr), *bias = reinterpret_cast<const float *>(p->bias_ptr);
-    const int *re = reinterpret_cast<const int *>(p->row_expert_ptr);
-    if (p->gated) hipLaunchKernelGGL(moe_act_fwd_kernel<true>, grid, dim3(256), 0, s, x, bias, re, reinterpret_cast<float *>(p->out_ptr), p->rows, p->width);
-    else hipLaunchKernelGGL(moe_act_fwd_kernel<false>, grid, dim3(256), 0, s, x, bias, re, reinterpret_cast<float *>(p->out_ptr), p->rows, p->width);
-    return launch_status();
-}
-
-extern "C" int dimsum_moe_act_bwd(const dimsum_moe_act_params_t *p, void *stream) {
-    using namespace dimsum;
-    if (const int rc = act_params_ok(p, true)) return rc;
-    if (p->rows == 0) return DIMSUM_OK;
-    const int64_t chunks = (p->rows + kRows - 1) / kRows;
-    if (chunks > 65535) return DIMSUM_ERR_SHAPE;           // (grid.y: 4 M rows)
-    const dim3 grid((unsigned)((p->width / 4 + 255) / 256), (unsigned)chunks);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const float *x = reinterpret_cast<const float *>(p->x_ptr), *bias = reinterpret_cast<const float *>(p->bias_ptr);
-    const float *dh = reinterpret_cast<const float *>(p->dh_ptr);
-    const int *re = reinterpret_cast<const int *>(p->row_expert_ptr);
-    float *dx = reinterpret_cast<float *>(p->out_ptr), *dbias = reinterpret_cast<float *>(p->dbias_ptr);
-    if (p->gated) hipLaunchKernelGGL(moe_act_bwd_kernel<true>, grid, dim3(256), 0, s, x, bias, re, dh, dx, dbias, p->rows, p->width);
-    else hipLaunchKernelGGL(moe_act_bwd_kernel<false>, grid, dim3(256), 0, s, x, bias, re, dh, dx, dbias, p->rows, p->width);
     return launch_status();
 }

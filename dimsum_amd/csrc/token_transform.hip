@@ -587,163 +587,6 @@ static int launch_tt(const dimsum_tt_params_t &p, hipStream_t s) {
     return launch_status();
 }
 
-// ---- GatedMLP epilogue (mlp.py:66-70): h = gelu_tanh(x1) * x2 --------------------------------------------------------
-__device__ __forceinline__ float tanh_fast(float x) {           // tanh(x) = 1 - 2 / (exp(2x) + 1)
-    return 1.0f - 2.0f * fast_rcp(fast_exp(2.0f * x) + 1.0f);
-}
-__device__ __forceinline__ float gelu_tanh(float a) {
-    const float u = 0.7978845608028654f * (a + 0.044715f * a * a * a);
-    return 0.5f * a * (1.0f + tanh_fast(u));
-}
-__device__ __forceinline__ float gelu_tanh_grad(float a) {
-    const float u = 0.7978845608028654f * (a + 0.044715f * a * a * a);
-    const float t = tanh_fast(u);
-    return 0.5f * (1.0f + t) + 0.5f * a * (1.0f - t * t) * 0.7978845608028654f * (1.0f + 3.0f * 0.044715f * a * a);
-}
-
-// backward: one workgroup = a strip of 1024 columns (4 per thread, 16 B) x a chunk of kGGRows rows: bias in registers,
-// fully coalesced rows, the column sums of dx12 (= d bias) accumulate in registers: one atomic per column per workgroup.
-constexpr int kGGRows = 64;
-// forward: one thread = 4 columns of one row, consecutive threads = consecutive 16-byte pieces of h (and of each half of
-// x12); 4 independent pieces in flight per thread, a grid stride apart
-// kSplit: h is the split-bf16 left operand image of the w3 GEMM (rows of 3 H bf16 [hi | hi | lo], common.hpp) instead of fp32
-template <bool kSplit>
-__global__ __launch_bounds__(256) void gated_gelu_fwd_kernel(const float *x12, const float *bias, void *hv, int64_t rows, int64_t H) {
-    float *h = reinterpret_cast<float *>(hv);
-    const int64_t q = H / 4, total = rows * q;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x; i0 < total; i0 += 4 * stride) {
-        float4 a[4], g[4];
-        int64_t rr[4], cc[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t i = min(i0 + k * stride, total - 1);
-            rr[k] = i / q; cc[k] = (i - rr[k] * q) * 4;
-            a[k] = *reinterpret_cast<const float4 *>(x12 + rr[k] * 2 * H + cc[k]);
-            g[k] = *reinterpret_cast<const float4 *>(x12 + rr[k] * 2 * H + H + cc[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (i0 + k * stride >= total) break;
-            float4 ba = make_float4(0.f, 0.f, 0.f, 0.f), bg = ba;
-            if (bias) { ba = *reinterpret_cast<const float4 *>(bias + cc[k]); bg = *reinterpret_cast<const float4 *>(bias + H + cc[k]); }
-            const float4 av = make_float4(a[k].x + ba.x, a[k].y + ba.y, a[k].z + ba.z, a[k].w + ba.w);
-            const float4 gv = make_float4(g[k].x + bg.x, g[k].y + bg.y, g[k].z + bg.z, g[k].w + bg.w);
-            const f32x4 o = {{gelu_tanh(av.x) * gv.x, gelu_tanh(av.y) * gv.y, gelu_tanh(av.z) * gv.z, gelu_tanh(av.w) * gv.w}};
-            if constexpr (kSplit) st_split3<true>(reinterpret_cast<unsigned short *>(hv) + rr[k] * 3 * H, cc[k], H, o);
-            else *reinterpret_cast<float4 *>(h + rr[k] * H + cc[k]) = make_float4(o.v[0], o.v[1], o.v[2], o.v[3]);
-        }
-    }
-}
-// kSplit: dx12 is written as the split-bf16 operand image of the two GEMMs that consume it (d input = dx12 W12, d weight = dx12^T h):
-// rows of 3 x 2H bf16 in WEIGHT order [hi | lo | hi] (common.hpp), to be paired with left-order images of W12^T and of h
-template <int kSplit>        // 0: fp32 dx12, 1: the weight-order image [hi | lo | hi], 2: the pair [hi | lo]
-__global__ __launch_bounds__(256) void gated_gelu_bwd_kernel(const float *x12, const float *bias, const float *dh, void *dx12v, float *dbias,
-                                                             int64_t rows, int64_t H) {
-    float *dx12 = reinterpret_cast<float *>(dx12v);
-    const int64_t c = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (c >= H) return;
-    float4 ba = make_float4(0.f, 0.f, 0.f, 0.f), bg = ba, sa = ba, sg = ba;
-    if (bias) { ba = *reinterpret_cast<const float4 *>(bias + c); bg = *reinterpret_cast<const float4 *>(bias + H + c); }
-    const int64_t r0 = (int64_t)blockIdx.y * kGGRows, r1 = min(rows, r0 + kGGRows);
-    for (int64_t r = r0; r < r1; ++r) {
-        float4 a = *reinterpret_cast<const float4 *>(x12 + r * 2 * H + c);
-        float4 g = *reinterpret_cast<const float4 *>(x12 + r * 2 * H + H + c);
-        const float4 d = *reinterpret_cast<const float4 *>(dh + r * H + c);
-        a.x += ba.x; a.y += ba.y; a.z += ba.z; a.w += ba.w;
-        g.x += bg.x; g.y += bg.y; g.z += bg.z; g.w += bg.w;
-        const float4 da = make_float4(d.x * g.x * gelu_tanh_grad(a.x), d.y * g.y * gelu_tanh_grad(a.y), d.z * g.z * gelu_tanh_grad(a.z), d.w * g.w * gelu_tanh_grad(a.w));
-        const float4 dg = make_float4(d.x * gelu_tanh(a.x), d.y * gelu_tanh(a.y), d.z * gelu_tanh(a.z), d.w * gelu_tanh(a.w));
-        if constexpr (kSplit == 2) {
-            unsigned short *row = reinterpret_cast<unsigned short *>(dx12v) + r * 4 * H;
-            st_split_left(row, c, 2 * H, f32x4{{da.x, da.y, da.z, da.w}}, true);
-            st_split_left(row, H + c, 2 * H, f32x4{{dg.x, dg.y, dg.z, dg.w}}, true);
-        } else if constexpr (kSplit == 1) {
-            unsigned short *row = reinterpret_cast<unsigned short *>(dx12v) + r * 6 * H;
-            st_split3<false>(row, c, 2 * H, f32x4{{da.x, da.y, da.z, da.w}});
-            st_split3<false>(row, H + c, 2 * H, f32x4{{dg.x, dg.y, dg.z, dg.w}});
-        } else {
-            *reinterpret_cast<float4 *>(dx12 + r * 2 * H + c) = da;
-            *reinterpret_cast<float4 *>(dx12 + r * 2 * H + H + c) = dg;
-        }
-        sa.x += da.x; sa.y += da.y; sa.z += da.z; sa.w += da.w;
-        sg.x += dg.x; sg.y += dg.y; sg.z += dg.z; sg.w += dg.w;
-    }
-    if (dbias) {
-        atomicAdd(dbias + c, sa.x); atomicAdd(dbias + c + 1, sa.y); atomicAdd(dbias + c + 2, sa.z); atomicAdd(dbias + c + 3, sa.w);
-        atomicAdd(dbias + H + c, sg.x); atomicAdd(dbias + H + c + 1, sg.y); atomicAdd(dbias + H + c + 2, sg.z); atomicAdd(dbias + H + c + 3, sg.w);
-    }
-}
-
-// The same adjoint with dx12 written as a scaled-fp16 operand image (common.hpp, f16s): rows of 2H fp16 = fp16(dx12_r 2^s_r) with the exact row
-// maximum's power of two, inv[r] = 2^-s_r -- the operand of BOTH backward GEMMs of w12 under the scaled-fp16 policy (d input = dx12 W12 as an NT
-// product, d weight = dx12^T h as a TN product with per-reduction-row factors, dimsum_gemm_ext_t.k_scale_ptr). A row's maximum needs the whole
-// row: one workgroup walks rows_per_wg rows (rows / 512: one round of 512 workgroups), a thread holding its 4-column pieces of both halves (H <= 1024 kStrips) in registers between the
-// maximum and the store; the column sums (d bias) accumulate in registers across the rows.
-template <int kStrips>
-__global__ __launch_bounds__(256) void gated_gelu_bwd_f16s_kernel(const float *x12, const float *bias, const float *dh, __half *img, float *inv, float *dbias,
-                                                                  int64_t rows, int64_t H, int rows_per_wg) {
-    __shared__ float red[2][4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    float4 ba[kStrips], bg[kStrips], sa[kStrips], sg[kStrips];
-#pragma unroll
-    for (int s = 0; s < kStrips; ++s) {
-        const int64_t c = ((int64_t)s * 256 + threadIdx.x) * 4;
-        ba[s] = bg[s] = sa[s] = sg[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (bias && c < H) { ba[s] = *reinterpret_cast<const float4 *>(bias + c); bg[s] = *reinterpret_cast<const float4 *>(bias + H + c); }
-    }
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_wg, r1 = min(rows, r0 + rows_per_wg);
-    for (int64_t r = r0; r < r1; ++r) {
-        float4 da[kStrips], dg[kStrips];
-        float m = 0.f;
-#pragma unroll
-        for (int s = 0; s < kStrips; ++s) {
-            const int64_t c = ((int64_t)s * 256 + threadIdx.x) * 4;
-            da[s] = dg[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < H) {
-                float4 a = *reinterpret_cast<const float4 *>(x12 + r * 2 * H + c);
-                float4 g = *reinterpret_cast<const float4 *>(x12 + r * 2 * H + H + c);
-                const float4 d = *reinterpret_cast<const float4 *>(dh + r * H + c);
-                a.x += ba[s].x; a.y += ba[s].y; a.z += ba[s].z; a.w += ba[s].w;
-                g.x += bg[s].x; g.y += bg[s].y; g.z += bg[s].z; g.w += bg[s].w;
-                da[s] = make_float4(d.x * g.x * gelu_tanh_grad(a.x), d.y * g.y * gelu_tanh_grad(a.y), d.z * g.z * gelu_tanh_grad(a.z), d.w * g.w * gelu_tanh_grad(a.w));
-                dg[s] = make_float4(d.x * gelu_tanh(a.x), d.y * gelu_tanh(a.y), d.z * gelu_tanh(a.z), d.w * gelu_tanh(a.w));
-                m = fmaxf(m, fmaxf(fmaxf(fmaxf(fabsf(da[s].x), fabsf(da[s].y)), fmaxf(fabsf(da[s].z), fabsf(da[s].w))),
-                                   fmaxf(fmaxf(fabsf(dg[s].x), fabsf(dg[s].y)), fmaxf(fabsf(dg[s].z), fabsf(dg[s].w)))));
-                sa[s].x += da[s].x; sa[s].y += da[s].y; sa[s].z += da[s].z; sa[s].w += da[s].w;
-                sg[s].x += dg[s].x; sg[s].y += dg[s].y; sg[s].z += dg[s].z; sg[s].w += dg[s].w;
-            }
-        }
-        m = wave_allmax(m);
-        const int par = (int)(r & 1);               // two slots: the next row's maxima are written while slow waves still read this row's
-        if (lane == 0) red[par][w] = m;
-        __syncthreads();
-        m = fmaxf(fmaxf(red[par][0], red[par][1]), fmaxf(red[par][2], red[par][3]));
-        float scale, iv;
-        f16s_scales(m, scale, iv);
-        if (threadIdx.x == 0) inv[r] = iv;
-        __half *row = img + r * 2 * H;
-#pragma unroll
-        for (int s = 0; s < kStrips; ++s) {
-            const int64_t c = ((int64_t)s * 256 + threadIdx.x) * 4;
-            if (c < H) {
-                *reinterpret_cast<uint2 *>(row + c) = f16s_pack4(f32x4{{da[s].x, da[s].y, da[s].z, da[s].w}}, scale);
-                *reinterpret_cast<uint2 *>(row + H + c) = f16s_pack4(f32x4{{dg[s].x, dg[s].y, dg[s].z, dg[s].w}}, scale);
-            }
-        }
-    }
-    if (dbias) {
-#pragma unroll
-        for (int s = 0; s < kStrips; ++s) {
-            const int64_t c = ((int64_t)s * 256 + threadIdx.x) * 4;
-            if (c < H) {
-                atomicAdd(dbias + c, sa[s].x); atomicAdd(dbias + c + 1, sa[s].y); atomicAdd(dbias + c + 2, sa[s].z); atomicAdd(dbias + c + 3, sa[s].w);
-                atomicAdd(dbias + H + c, sg[s].x); atomicAdd(dbias + H + c + 1, sg[s].y); atomicAdd(dbias + H + c + 2, sg[s].z); atomicAdd(dbias + H + c + 3, sg[s].w);
-            }
-        }
-    }
-}
-
 }  // namespace dimsum
 
 extern "C" int dimsum_token_transform(const dimsum_tt_params_t *p, void *stream) {
@@ -770,90 +613,4 @@ extern "C" int dimsum_token_transform(const dimsum_tt_params_t *p, void *stream)
     } else
     if (p->y_split3 && (!vec || !p->y_ptr || p->y_token_stride < (p->y_split3 == 3 ? 2 : 3) * (int64_t)p->channels)) return DIMSUM_ERR_STRIDE;   // image rows: 8-byte pieces
     return vec ? launch_tt<4>(*p, s) : launch_tt<1>(*p, s);
-}
-
-template <bool kSplit>
-static int launch_gated_gelu_fwd(const void *x12, const void *bias, void *h, int64_t rows, int64_t hidden, void *stream) {
-    using namespace dimsum;
-    if (!x12 || !h) return DIMSUM_ERR_NULL;
-    if (rows < 0 || hidden <= 0 || hidden % 4 != 0) return DIMSUM_ERR_SHAPE;
-    if (!aligned_to<float>(x12, 16) || !aligned_to<float>(h, 16) || (bias && !aligned_to<float>(bias, 16))) return DIMSUM_ERR_STRIDE;
-    if (rows == 0) return DIMSUM_OK;
-    // flat mapping: 4 pieces per thread a quarter of the tensor apart, no row loop: 0.60 ms at (65536, 2 x 4096) against 0.67 ms
-    // for the strip-per-workgroup form the backward keeps (it needs the row loop for the d bias column sums)
-    const int64_t total = rows * (hidden / 4);
-    const int64_t blocks = (total + 256 * 4 - 1) / (256 * 4);
-    if (blocks > 0x7fffffff) return DIMSUM_ERR_SHAPE;
-    hipLaunchKernelGGL(gated_gelu_fwd_kernel<kSplit>, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<const float *>(x12), reinterpret_cast<const float *>(bias), h, rows, hidden);
-    return launch_status();
-}
-
-extern "C" int dimsum_gated_gelu_fwd(const void *x12, const void *bias, void *h, int64_t rows, int64_t hidden, void *stream) {
-    return launch_gated_gelu_fwd<false>(x12, bias, h, rows, hidden, stream);
-}
-
-extern "C" int dimsum_gated_gelu_fwd_split3(const void *x12, const void *bias, void *h3, int64_t rows, int64_t hidden, void *stream) {
-    return launch_gated_gelu_fwd<true>(x12, bias, h3, rows, hidden, stream);
-}
-
-template <int kSplit>
-static int launch_gated_gelu_bwd(const void *x12, const void *bias, const void *dh, void *dx12, void *dbias, int64_t rows, int64_t hidden, void *stream) {
-    using namespace dimsum;
-    if (!x12 || !dh || !dx12) return DIMSUM_ERR_NULL;
-    if (rows < 0 || hidden <= 0 || hidden % 4 != 0) return DIMSUM_ERR_SHAPE;
-    if (!aligned_to<float>(x12, 16) || !aligned_to<float>(dh, 16) || !aligned_to<float>(dx12, 16) || (bias && !aligned_to<float>(bias, 16)))
-        return DIMSUM_ERR_STRIDE;
-    if (rows == 0) return DIMSUM_OK;
-    const dim3 grid((unsigned)((hidden / 4 + 255) / 256), (unsigned)((rows + kGGRows - 1) / kGGRows));
-    hipLaunchKernelGGL(gated_gelu_bwd_kernel<kSplit>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<const float *>(x12), reinterpret_cast<const float *>(bias), reinterpret_cast<const float *>(dh),
-                       dx12, reinterpret_cast<float *>(dbias), rows, hidden);
-    return launch_status();
-}
-
-extern "C" int dimsum_gated_gelu_bwd(const void *x12, const void *bias, const void *dh, void *dx12, void *dbias, int64_t rows,
-                                     int64_t hidden, void *stream) {
-    return launch_gated_gelu_bwd<0>(x12, bias, dh, dx12, dbias, rows, hidden, stream);
-}
-
-extern "C" int dimsum_gated_gelu_bwd_split3(const void *x12, const void *bias, const void *dh, void *dx12_image, void *dbias, int64_t rows,
-                                            int64_t hidden, void *stream) {
-    return launch_gated_gelu_bwd<1>(x12, bias, dh, dx12_image, dbias, rows, hidden, stream);
-}
-
-extern "C" int dimsum_gated_gelu_bwd_pair(const void *x12, const void *bias, const void *dh, void *dx12_pair, void *dbias, int64_t rows,
-                                          int64_t hidden, void *stream) {
-    return launch_gated_gelu_bwd<2>(x12, bias, dh, dx12_pair, dbias, rows, hidden, stream);
-}
-
-/* dx12 as the scaled-fp16 image (rows, 2 hidden) float16 + inv_scale (rows) f32: see gated_gelu_bwd_f16s_kernel */
-extern "C" int dimsum_gated_gelu_bwd_f16s(const void *x12, const void *bias, const void *dh, void *dx12_image, void *inv_scale, void *dbias, int64_t rows,
-                                          int64_t hidden, void *stream) {
-    using namespace dimsum;
-    if (!x12 || !dh || !dx12_image || !inv_scale) return DIMSUM_ERR_NULL;
-    if (rows < 0 || hidden <= 0 || hidden % 4 != 0 || hidden > 5 * 1024) return DIMSUM_ERR_SHAPE;
-    if (!aligned_to<char>(x12, 16) || !aligned_to<char>(dh, 16) || !aligned_to<char>(dx12_image, 8) || (bias && !aligned_to<char>(bias, 16))) return DIMSUM_ERR_STRIDE;
-    if (rows == 0) return DIMSUM_OK;
-    // rows per workgroup: ONE round of 512 workgroups (two per CU; three fit), whatever the batch size. Measured (tools/scratch/gg_bwd_time.py,
-    // rows per workgroup = rows / div): 16384 rows: 128 workgroups 538 us, 256: 320, 390-512: 262, 780: 348 (a dozen workgroups left over for a
-    // second round run alone for a whole workgroup's duration), 1024: 309, 2048+: 350; 65536 rows: 512 workgroups 862 us, 1024: 937, 2048: 882,
-    // 8192: 1117 (the column sums cost one atomic per column and workgroup: 8192 each).
-    int rpw = (int)((rows + 511) / 512);
-    rpw = rpw < 8 ? 8 : rpw;
-    const dim3 grid((unsigned)((rows + rpw - 1) / rpw));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int strips = (int)((hidden + 1023) / 1024);
-#define DIMSUM_GGF(K) hipLaunchKernelGGL(gated_gelu_bwd_f16s_kernel<K>, grid, dim3(256), 0, s, reinterpret_cast<const float *>(x12), reinterpret_cast<const float *>(bias), \
-                                         reinterpret_cast<const float *>(dh), reinterpret_cast<__half *>(dx12_image), reinterpret_cast<float *>(inv_scale),                \
-                                         reinterpret_cast<float *>(dbias), rows, hidden, rpw)
-    switch (strips) {
-        case 1: DIMSUM_GGF(1); break;
-        case 2: DIMSUM_GGF(2); break;
-        case 3: DIMSUM_GGF(3); break;
-        case 4: DIMSUM_GGF(4); break;
-        default: DIMSUM_GGF(5); break;
-    }
-#undef DIMSUM_GGF
-    return launch_status();
 }

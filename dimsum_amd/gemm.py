@@ -681,7 +681,7 @@ def matmul_wx_split3(weight, x3, conv=None):
 def gated_mlp_hidden_split3(x3, w12, b12):
     """x3 (M, 3K) left image, w12 (2F, K), b12 (2F) or None -> the left image (M, 3F) of gelu_tanh(x W12a^T + b) * (x W12b^T + b)
     (dimsum/mlp.py:66-70): ONE kernel, the gate in the GEMM's epilogue -- the fp32 (M, 2F) tensor never exists; the library GEMM + the
-    gated-GeLU pass (csrc/token_transform.hip) when the shape does not fit the kernel's tiling."""
+    gated-GeLU pass (csrc/act_rows.hip) when the shape does not fit the kernel's tiling."""
     from . import native
     if isinstance(x3, native.F16Image):
         w16 = weight_f16s(w12)
@@ -706,7 +706,7 @@ def mlp_hidden_split3(x3, w1, b1):
     """x3 = the left operand image of x (split-bf16 (M, 3K), PairImage or F16Image), w1 (F, K), b1 (F) or None -> the left image of
     gelu_tanh(x W1^T + b1), the hidden activation of the plain Mlp (dimsum/models_dit.py:124), in x3's own carrier. Scaled fp16: ONE kernel, the
     activation in the GEMM's epilogue (DIMSUM_GEMM_EPI_GELU_F16, row scales from gated_bound's {wl1, bmax}) where the library builds it
-    (DIMSUM_GELU_EPILOGUE=0 switches it off); everywhere else the bias-free GEMM + the row pass (csrc/gelu.hip), which writes the image."""
+    (DIMSUM_GELU_EPILOGUE=0 switches it off); everywhere else the bias-free GEMM + the row pass (csrc/act_rows.hip), which writes the image."""
     from . import native
     F_ = w1.shape[0]
     if isinstance(x3, native.F16Image):

@@ -1,5 +1,5 @@
 """GatedMLP and the plain Mlp (at the end of the file). GatedMLP -- dimsum/mlp.py:49-70: w3( act(x W12a + b) * (x W12b + b) ) + b3. With the tanh-GELU the DiM blocks use,
-bias + activation + gate run as ONE fused HIP pass over the bias-free w12 GEMM output (csrc/token_transform.hip,
+bias + activation + gate run as ONE fused HIP pass over the bias-free w12 GEMM output (csrc/act_rows.hip,
 gated GeLU); the w3 bias can be handed to the caller's fused residual pass (`forward_deferred`). Keeping the biases out
 of the GEMMs matters on gfx950: hipBLASLt serves bias-free fp32 matmuls under the reference's TF32 policy
 (train.py:20-21) with its split-bf16 MFMA path (2.5x the fp32 rate at 4e-6 relative error), but not its bias-epilogue
@@ -44,7 +44,7 @@ class _GeluFn(torch.autograd.Function):
 
 
 def bias_gelu(x, bias=None):
-    """gelu_tanh(x + bias): the activation of the plain Mlp as one HIP row pass, forward and backward (csrc/gelu.hip)"""
+    """gelu_tanh(x + bias): the activation of the plain Mlp as one HIP row pass, forward and backward (csrc/act_rows.hip)"""
     return _GeluFn.apply(x, bias)
 
 
@@ -226,7 +226,7 @@ class GatedMLP(nn.Module):
 class Mlp(nn.Module):
     """timm 0.9.12 Mlp as the reference builds it (dimsum/models_dit.py:124; models_dim.py with use_gated_mlp=False): fc2(act(fc1(x))), 4x wide,
     with biases, parameters `fc1` / `fc2`. With the tanh-GELU every block uses, bias + activation run as ONE HIP pass over the bias-free fc1 GEMM
-    output (csrc/gelu.hip) -- at inference under the scaled-fp16 policy inside that GEMM's epilogue (DIMSUM_GEMM_EPI_GELU_F16) -- and the fc2 bias
+    output (csrc/act_rows.hip) -- at inference under the scaled-fp16 policy inside that GEMM's epilogue (DIMSUM_GEMM_EPI_GELU_F16) -- and the fc2 bias
     can be handed to the caller's fused residual pass (`forward_deferred`), as GatedMLP does."""
 
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.0, bias=True):
@@ -267,7 +267,7 @@ class MLP(nn.Module):
     """The expert of the mixture-of-experts layer, with the reference's signature and parameter names (dimsum/mlp.py:7-46): linear_fc2(act(linear_fc1(x))),
     `linear_fc1` dim -> 8 dim with the gated linear unit (act = gelu(a) * g over the two halves) else dim -> 4 dim (act = gelu), `linear_fc2`
     4 dim -> dim, biases only with add_bias_linear. The GELU is the exact (erf) one. Inside a SwitchMLP the layer's own function runs the experts
-    over row slices (ops/moe.py); called on its own, bias + activation are the same HIP pass with one expert (csrc/moe.hip)."""
+    over row slices (ops/moe.py); called on its own, bias + activation are the same HIP pass with one expert (csrc/act_rows.hip)."""
 
     def __init__(self, dim, add_bias_linear=False, gated_linear_unit=True, is_expert=False, layer_idx=None, device=None):
         super().__init__()

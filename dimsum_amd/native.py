@@ -843,7 +843,7 @@ def selective_scan_bidir_bwd(u, delta, A, A_b, B, C, D, z, delta_bias, dout, out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# fused token-space transform (csrc/token_transform.hip) and GatedMLP epilogue
+# fused token-space transform (csrc/token_transform.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 _TT_KIND = {("none", True): 0, ("none", False): 0, ("haar", True): 1, ("haar", False): 2, ("dct", True): 3, ("dct", False): 4}
 
@@ -922,6 +922,26 @@ def token_transform(x, kind, forward, in_index=None, out_index=None, gate=None, 
     return y if w is None else (y, wdot, wsum)
 
 
+# ---- bias + GELU between two GEMMs as a row pass (csrc/act_rows.hip): GatedMLP, the plain Mlp; the experts' form is moe_act_* below ----
+def _act_out(lead, H, split3, device, n_dbias=0):
+    """what an activation row pass (csrc/act_rows.hip) writes for rows of H columns over the leading shape `lead` -> (out, inv, dbias):
+    split3 False: (..., H) float32; True: the split-bf16 image (..., 3H) bfloat16; "pair": (..., 2H) bfloat16; "f16s": (..., H) float16 with
+    inv (...) float32 (else None). dbias: n_dbias zeros for the kernel's atomics, or None"""
+    inv = None
+    if split3 == "f16s":
+        out = torch.empty(lead + (H,), device=device, dtype=torch.float16)
+        inv = torch.empty(lead, device=device, dtype=torch.float32)
+    elif split3:
+        out = torch.empty(lead + ((2 if split3 == "pair" else 3) * H,), device=device, dtype=torch.bfloat16)
+    else:
+        out = torch.empty(lead + (H,), device=device, dtype=torch.float32)
+    return out, inv, (_zeros(n_dbias, device) if n_dbias else None)
+
+
+def _act_image(out, inv, split3):
+    return F16Image(out, inv) if split3 == "f16s" else PairImage(out) if split3 == "pair" else out
+
+
 def gated_gelu_fwd(x12, bias=None, split3=False):
     """x12: (..., 2H) fp32 contiguous (w12 GEMM output WITHOUT bias), bias (2H) or None
     -> gelu_tanh(x12[..., :H] + bias[:H]) * (x12[..., H:] + bias[H:])   (mlp.py:66-70)
@@ -931,12 +951,30 @@ def gated_gelu_fwd(x12, bias=None, split3=False):
     H = x12.shape[-1] // 2
     if bias is not None:
         _check(bias.dtype == torch.float32 and tuple(bias.shape) == (2 * H,) and bias.is_contiguous(), "gated_gelu: bias must be (2H,) float32")
-    h = torch.empty(x12.shape[:-1] + ((3 * H,) if split3 else (H,)), device=x12.device, dtype=torch.bfloat16 if split3 else torch.float32)
+    h = _act_out(x12.shape[:-1], H, bool(split3), x12.device)[0]
     rows = x12.numel() // (2 * H)
     fn = _lib.load().dimsum_gated_gelu_fwd_split3 if split3 else _lib.load().dimsum_gated_gelu_fwd
     with torch.cuda.device(x12.device):
         _lib.check(fn(_ptr(x12), _ptr(bias), _ptr(h), rows, H, _stream(x12)), "gated_gelu_fwd")
     return h
+
+
+def gated_gelu_bwd(x12, bias, dh, need_dbias=True, split3=False):
+    """-> (dx12, dbias or None).  split3: dx12 as a split-bf16 operand image in weight order, (..., 3 * 2H) bfloat16 [hi | lo | hi];
+    split3="pair": (..., 2 * 2H) bfloat16 [hi | lo] (PairImage);
+    split3="f16s": as a scaled-fp16 image (F16Image: (..., 2H) float16 + one inverse scale per row, the exact row maximum; H <= 5120)"""
+    _gpu(x12, bias, dh)
+    dh = dh.contiguous()
+    H = x12.shape[-1] // 2
+    split3 = split3 if split3 in ("pair", "f16s") else bool(split3)
+    f16s = split3 == "f16s"
+    _check(not f16s or (x12.is_contiguous() and x12.dtype == torch.float32 and dh.dtype == torch.float32 and H % 4 == 0 and H <= 5120), "gated_gelu_bwd: the f16s image needs contiguous float32 rows, H % 4 == 0, H <= 5120")
+    dx12, inv, dbias = _act_out(x12.shape[:-1], 2 * H, split3, x12.device, 2 * H if (bias is not None and need_dbias) else 0)
+    lib = _lib.load()
+    fn = {False: lib.dimsum_gated_gelu_bwd, True: lib.dimsum_gated_gelu_bwd_split3, "pair": lib.dimsum_gated_gelu_bwd_pair, "f16s": lib.dimsum_gated_gelu_bwd_f16s}[split3]
+    with torch.cuda.device(x12.device):
+        _lib.check(fn(_ptr(x12), _ptr(bias), _ptr(dh), _ptr(dx12), *((_ptr(inv),) if f16s else ()), _ptr(dbias), x12.numel() // (2 * H), H, _stream(x12)), "gated_gelu_bwd")
+    return _act_image(dx12, inv, split3), dbias
 
 
 _GELU_OUT = {False: _lib.GELU_OUT_F32, True: _lib.GELU_OUT_SPLIT3, "pair": _lib.GELU_OUT_PAIR, "f16s": _lib.GELU_OUT_F16S}
@@ -946,29 +984,16 @@ def _gelu_call(fn, what, x, bias, dh, split3, need_dbias, scales):
     """one launch of dimsum_gelu_fwd / _bwd: the output tensor (or image) of the asked mode, the struct, the call"""
     H = x.shape[-1]
     rows = x.numel() // H
-    mode = _GELU_OUT[split3]
-    inv = None
-    if mode == _lib.GELU_OUT_F16S:
-        out = torch.empty(x.shape, device=x.device, dtype=torch.float16)
-        inv = torch.empty(x.shape[:-1], device=x.device, dtype=torch.float32)
-    elif mode == _lib.GELU_OUT_F32:
-        out = torch.empty_like(x)
-    else:
-        out = torch.empty(x.shape[:-1] + ((2 if mode == _lib.GELU_OUT_PAIR else 3) * H,), device=x.device, dtype=torch.bfloat16)
-    dbias = _zeros(H, x.device) if need_dbias else None
+    out, inv, dbias = _act_out(x.shape[:-1], H, split3, x.device, H if need_dbias else 0)
     P = _lib.GeluParams()
-    P.out_image, P.rows, P.hidden = mode, rows, H
+    P.out_image, P.rows, P.hidden = _GELU_OUT[split3], rows, H
     P.x_ptr, P.bias_ptr, P.dh_ptr, P.out_ptr, P.inv_scale_ptr, P.dbias_ptr = _ptr(x), _ptr(bias), _ptr(dh), _ptr(out), _ptr(inv), _ptr(dbias)
     if scales is not None:
         E = _lib.attach_ext(P, _lib.GeluExt)
         E.row_inv_ptr, E.bound_ptr = _ptr(scales[0]), _ptr(scales[1])
     with torch.cuda.device(x.device):
         _lib.check(fn(P, _stream(x)), what)
-    if mode == _lib.GELU_OUT_F16S:
-        out = F16Image(out, inv)
-    elif mode == _lib.GELU_OUT_PAIR:
-        out = PairImage(out)
-    return out, dbias
+    return _act_image(out, inv, split3), dbias
 
 
 def gelu_fwd(x, bias=None, split3=False, scales=None):
@@ -1007,7 +1032,7 @@ def gelu_bwd(x, bias, dh, need_dbias=True, split3=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the top-1 mixture-of-experts layer's row passes (csrc/moe.hip; SwitchMLP, dimsum/switch_mlp.py:69-99)
+# the top-1 mixture-of-experts layer's row passes (csrc/moe.hip, the experts' activation: csrc/act_rows.hip; SwitchMLP, dimsum/switch_mlp.py:69-99)
 # ---------------------------------------------------------------------------------------------------------------------
 MOE_MAX_EXPERTS = 64
 _MOE_MODE = {"softmax": _lib.MOE_ROUTE_SOFTMAX, "sigmoid": _lib.MOE_ROUTE_SIGMOID}
@@ -1130,8 +1155,8 @@ def _moe_act_call(fn, what, x, bias, row_expert, dh, gated, need_dbias):
     _check(row_expert is not None or bias is None or bias.shape[0] == 1, f"{what}: a bias with more than one row needs row_expert")
     if dh is not None:
         _check(dh.dtype == torch.float32 and dh.is_contiguous() and tuple(dh.shape) == (rows, W), f"{what}: dh must be contiguous float32 (rows, W)")
-    out = torch.empty(rows, S if dh is not None else W, device=x.device, dtype=torch.float32)
-    dbias = _zeros(bias.numel(), x.device).view(bias.shape) if (need_dbias and bias is not None) else None
+    out, _, dbias = _act_out((rows,), S if dh is not None else W, False, x.device, bias.numel() if (need_dbias and bias is not None) else 0)
+    dbias = dbias.view(bias.shape) if dbias is not None else None
     P = _lib.MoeActParams()
     P.gated, P.num_experts, P.rows, P.width = int(bool(gated)), E, rows, W
     P.x_ptr, P.bias_ptr, P.row_expert_ptr, P.dh_ptr, P.out_ptr, P.dbias_ptr = _ptr(x), _ptr(bias), _ptr(row_expert), _ptr(dh), _ptr(out), _ptr(dbias)
@@ -1684,32 +1709,6 @@ def gemm_nt(a, b, bias=None, epilogue="f32", out=None, out_scale=1.0, events=Non
     if pair_out:
         return PairImage(out)
     return out if h_inv is None else F16Image(out, h_inv)
-
-
-def gated_gelu_bwd(x12, bias, dh, need_dbias=True, split3=False):
-    """-> (dx12, dbias or None).  split3: dx12 as a split-bf16 operand image in weight order, (..., 3 * 2H) bfloat16 [hi | lo | hi];
-    split3="f16s": as a scaled-fp16 image (F16Image: (..., 2H) float16 + one inverse scale per row, the exact row maximum; H <= 5120)"""
-    _gpu(x12, bias, dh)
-    dh = dh.contiguous()
-    H = x12.shape[-1] // 2
-    if split3 == "f16s":
-        _check(x12.is_contiguous() and x12.dtype == torch.float32 and dh.dtype == torch.float32 and H % 4 == 0 and H <= 5120, "gated_gelu_bwd: the f16s image needs contiguous float32 rows, H % 4 == 0, H <= 5120")
-        rows = x12.numel() // (2 * H)
-        img = torch.empty(x12.shape, device=x12.device, dtype=torch.float16)
-        inv = torch.empty(x12.shape[:-1], device=x12.device, dtype=torch.float32)
-        dbias = _zeros(2 * H, x12.device) if (bias is not None and need_dbias) else None
-        with torch.cuda.device(x12.device):
-            _lib.check(_lib.load().dimsum_gated_gelu_bwd_f16s(_ptr(x12), _ptr(bias), _ptr(dh), _ptr(img), _ptr(inv), _ptr(dbias), rows, H, _stream(x12)), "gated_gelu_bwd")
-        return F16Image(img, inv), dbias
-    pair = split3 == "pair"        # (..., 2 * 2H) bfloat16 [hi | lo] (PairImage)
-    dx12 = torch.empty(x12.shape[:-1] + ((4 if pair else 6) * H,), device=x12.device, dtype=torch.bfloat16) if split3 else torch.empty_like(x12)
-    dbias = _zeros(2 * H, x12.device) if (bias is not None and need_dbias) else None
-    rows = x12.numel() // (2 * H)
-    with torch.cuda.device(x12.device):
-        lib = _lib.load()
-        fn = lib.dimsum_gated_gelu_bwd_pair if pair else (lib.dimsum_gated_gelu_bwd_split3 if split3 else lib.dimsum_gated_gelu_bwd)
-        _lib.check(fn(_ptr(x12), _ptr(bias), _ptr(dh), _ptr(dx12), _ptr(dbias), rows, H, _stream(x12)), "gated_gelu_bwd")
-    return (PairImage(dx12) if pair else dx12), dbias
 
 
 # ---------------------------------------------------------------------------------------------------------------------

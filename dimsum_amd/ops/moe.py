@@ -1,4 +1,4 @@
-"""The top-1 mixture-of-experts layer as ONE autograd function over the HIP row passes of csrc/moe.hip and per-expert GEMMs on contiguous row
+"""The top-1 mixture-of-experts layer as ONE autograd function over the HIP row passes of csrc/moe.hip (the experts' activation: csrc/act_rows.hip) and per-expert GEMMs on contiguous row
 slices (SwitchMLP.forward, dimsum/switch_mlp.py:69-99; the expert, dimsum/mlp.py:42-46):
 
     forward : route (router dot products, sigmoid / softmax, first-argmax, stable counting sort by expert)  ->  ONE host read of the E + 1 offsets

@@ -1,4 +1,4 @@
-"""The plain MLP's HIP path (csrc/gelu.hip, DIMSUM_GEMM_EPI_GELU_F16, dimsum_amd.mlp.Mlp) and the DiT family on it (models_dit.py).
+"""The plain MLP's HIP path (csrc/act_rows.hip, DIMSUM_GEMM_EPI_GELU_F16, dimsum_amd.mlp.Mlp) and the DiT family on it (models_dit.py).
 
 Row pass: against float64 F.gelu(approximate="tanh") (and its float64 autograd) on the CPU, with the bound MEASURED per case -- the max error
 of the CPU's own fp32 evaluation against float64 on the same input, times 4 (the margin covers tanhf / expf implementation differences and
@@ -137,6 +137,33 @@ def test_row_pass_images_decode_to_the_fp32_output(shape):
     want = native.gelu_bwd(x, bias, dh)[1]
     for mode in (True, "pair", "f16s"):
         assert_close(n(native.gelu_bwd(x, bias, dh, split3=mode)[1]), n(want), 0, 0, f"dbias ({mode})", scale_atol=shape[0] * 2.0 ** -23)
+
+
+@pytest.mark.parametrize("shape", [(9, 2052), (130, 2052), (9, 4100), (130, 4100)])
+def test_row_pass_f16s_images_against_float64(shape):
+    """The three- and five-strip instantiations of the scaled-fp16 row pass (H in (2048, 3072] and (4096, 5120]; ROW_SHAPES stops at one, two and
+    four strips), forward and backward, decoded against the float64 expression: one fp16 ulp of the row maximum (the image tolerance of
+    test_row_pass_images_decode_to_the_fp32_output) plus the fp32 pass's own bound, 4 x the CPU's fp32 error (the tests above). 9 rows = one full
+    workgroup of 8 rows and a ragged one, 130 = 17 workgroups. d bias against the float64 column sum: every one of the `rows` summands carries the
+    dx bound, and the fp32 accumulation rows * 2^-23 * max|dx| as above."""
+    from dimsum_amd import native
+    x, bias, dh, h64, dx64, ferr, berr = _row_ref(shape, True)
+    rows, H = shape
+    img = native.gelu_fwd(x.cuda(), bias.cuda(), split3="f16s")
+    dimg, db = native.gelu_bwd(x.cuda(), bias.cuda(), dh.cuda(), split3="f16s")
+    for name, im, ref, cpu_err in (("fwd", img, h64, ferr), ("bwd", dimg, dx64, berr)):
+        assert im.data.dtype == torch.float16 and im.data.shape == shape and im.inv.shape == (rows,)
+        top = im.data.float().abs().amax(1)
+        assert torch.all(torch.frexp(im.inv)[0] == 0.5) and torch.all(top >= 2.0 ** 14) and torch.all(top < 2.0 ** 15), name
+        rmax = ref.abs().amax(1)
+        err = (im.float().cpu().double() - ref).abs().amax(1)
+        bound = _ulp16(rmax.float()).double() + 4 * cpu_err
+        print(f"{name} f16s image {shape} vs float64: max err / bound {(err / bound).max().item():.3f}")
+        assert (err <= bound).all(), name
+    berr_got = (db.cpu().double() - dx64.sum(0)).abs().max().item()
+    bbound = rows * (2.0 ** -23 * dx64.abs().max().item() + 4 * berr)
+    print(f"    dbias err {berr_got:.3e}, bound {bbound:.3e}")
+    assert db.shape == (H,) and berr_got <= bbound
 
 
 def _epi_case(M, K, N):

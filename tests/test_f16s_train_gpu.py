@@ -118,6 +118,34 @@ def test_gated_gelu_adjoint_as_scaled_fp16_image(rows, H):
     assert (db - db_ref).abs().max().item() <= 1e-5 * db_ref.abs().max().item() + 1e-6
 
 
+@pytest.mark.parametrize("rows,H", [(9, 1028), (130, 1028), (9, 2052), (130, 2052)])
+def test_gated_gelu_adjoint_image_against_float64(rows, H):
+    """dimsum_gated_gelu_bwd_f16s on two and three strips of 1024 columns (the test above runs one, four and five), 9 rows (one full workgroup
+    of 8 rows and a ragged one) and 130 (17 workgroups), against float64 autograd of gelu_tanh(x1 + b1) (x2 + b2). Per row: half an fp16 ulp
+    of the row maximum (the image tolerance of the test above) plus the fp32 adjoint's own tolerance, 1e-4 |ref| + 1e-5 max (tests/
+    test_token_ops_gpu.py::test_gated_gelu), the maximum taken over the row because dh scales every row differently. d bias: that test's
+    2e-4 |ref| + 2e-5 max."""
+    from dimsum_amd import native
+    g = torch.Generator().manual_seed(rows + H)
+    x12, bias = torch.randn(rows, 2 * H, generator=g), 0.1 * torch.randn(2 * H, generator=g)
+    dh = torch.randn(rows, H, generator=g) * torch.exp2(-20 * torch.rand(rows, 1, generator=g))
+    xr, br = x12.double().requires_grad_(), bias.double().requires_grad_()
+    xb = xr + br
+    (torch.nn.functional.gelu(xb[:, :H], approximate="tanh") * xb[:, H:]).backward(dh.double())
+    ref, db_ref = xr.grad, br.grad
+    img, db = native.gated_gelu_bwd(x12.cuda(), bias.cuda(), dh.cuda(), split3="f16s")
+    assert img.data.dtype == torch.float16 and img.data.shape == (rows, 2 * H) and img.inv.shape == (rows,)
+    top = img.data.float().abs().amax(1)
+    assert torch.all(top >= 2.0 ** 14) and torch.all(top < 2.0 ** 15) and torch.all(torch.frexp(img.inv)[0] == 0.5)
+    rmax = ref.abs().amax(1, keepdim=True)
+    err = (img.float().cpu().double() - ref).abs()
+    bound = 2.0 ** -11 * rmax * 1.001 + 1e-4 * ref.abs() + 1e-5 * rmax
+    print(f"gated f16s adjoint ({rows}, {H}) vs float64: max err / bound {(err / bound).max().item():.3f}")
+    assert torch.all(err <= bound)
+    derr = (db.cpu().double() - db_ref).abs()
+    assert torch.all(derr <= 2e-4 * db_ref.abs() + 2e-5 * db_ref.abs().max()), derr.max().item()
+
+
 def test_training_gate_epilogue_keeps_x12_in_true_units():
     """gated_f16 + keep_x12 over scaled-fp16 operands (the training forward of w12): the stored fp32 [x1 | x2] is the bias-free product in TRUE
     units (accumulator x row scale x column scale) -- bit for bit the plain fp32-output launch of the same operands -- and the h image is the

@@ -1,6 +1,6 @@
 """The hand-written NT GEMM (csrc/gemm_nt_kernel.hpp, dimsum_gemm_nt) through the C ABI: plain fp32 output against float64 products of
 the same 16-bit operands, ragged N, biases, and the gated-GeLU epilogues (dimsum/mlp.py:66-70) against the float64 expression and
-against the unfused pair (library GEMM + csrc/token_transform.hip gated GeLU pass) they replace."""
+against the unfused pair (library GEMM + csrc/act_rows.hip gated GeLU pass) they replace."""
 import numpy as np
 import pytest
 

@@ -1,4 +1,4 @@
-"""The mixture-of-experts row passes (csrc/moe.hip) and layers on the GPU, against float64 restatements on the CPU, the fixtures of the
+"""The mixture-of-experts row passes (csrc/moe.hip, csrc/act_rows.hip) and layers on the GPU, against float64 restatements on the CPU, the fixtures of the
 reference (tests/golden/moe_switch*.npz) and the CPU stand-ins of test_moe_cpu.
 
 Routing inputs are seeded so that, in float64, every token's best and second-best route values differ by at least 1e-4 (asserted on the CPU

@@ -1,4 +1,4 @@
-"""Host side of the token passes (csrc/token_transform.hip, ops/token_ops.py), CPU-only.
+"""Host side of the token passes (csrc/token_transform.hip, ops/token_ops.py) and of the gated-GeLU row passes (csrc/act_rows.hip), CPU-only.
 
 (a) The plain torch expressions of the transforms in ops/token_ops.py (haar_dwt_tokens, dct_tokens, ...) are the reference the GPU tests of
     the token passes use (tests/test_token_paths_gpu.py evaluates them in float64). Here they are pinned themselves: against the reference's
@@ -209,6 +209,7 @@ def test_token_transform_cases_break_a_base_that_passes_the_checks():
 # ---- (b) refusals of the gated-GeLU entry points ------------------------------------------------------------------------------------------
 X12, BIAS, H_OUT, DH, DX12, DBIAS, INV_S = (_addr(20 + i) for i in range(7))
 BIG_ROWS = 1 << 42                                   # x hidden / 4 pieces / 1024 per workgroup: 2^32 workgroups > 2^31 - 1
+BIG_CHUNKS = 65536 * 64                              # 65536 chunks of 64 rows: one more than the backward's grid.y takes
 GG_FWD = ("dimsum_gated_gelu_fwd", "dimsum_gated_gelu_fwd_split3")
 GG_BWD = ("dimsum_gated_gelu_bwd", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair")
 _GG_SHAPE = [({"rows": -1}, SHAPE), ({"hidden": 0}, SHAPE), ({"hidden": -8}, SHAPE), ({"hidden": 10}, SHAPE)]
@@ -223,6 +224,7 @@ GG_CASES = (
     + [(n, m, s) for n in GG_BWD for m, s in _GG_SHAPE + [
         ({"x12": None}, NULL), ({"dh": None}, NULL), ({"dx12": None}, NULL),
         ({"x12": X12 + 8}, STRIDE), ({"dh": DH + 4}, STRIDE), ({"dx12": DX12 + 8}, STRIDE), ({"bias": BIAS + 8}, STRIDE),
+        ({"rows": BIG_CHUNKS}, SHAPE),
         ({"dh": None, "rows": -1}, NULL), ({"hidden": 10, "dh": DH + 4}, SHAPE), ({"rows": 0, "dx12": DX12 + 8}, STRIDE), ({"rows": 0, "hidden": 10}, SHAPE)]]
     + [("dimsum_gated_gelu_bwd_f16s", m, s) for m, s in _GG_SHAPE + [
         ({"x12": None}, NULL), ({"dh": None}, NULL), ({"dx12": None}, NULL), ({"inv": None}, NULL), ({"hidden": 5124}, SHAPE),

@@ -1,5 +1,5 @@
 """tools/bench_dit.py (GPU box): the plain MLP's HIP path and the DiT baseline on it, in one process --
-  1. the bias + GELU row pass (csrc/gelu.hip) at (65536, 4096): forward (fp32 and the scaled-fp16 image) and backward, microseconds and GB/s of
+  1. the bias + GELU row pass (csrc/act_rows.hip) at (65536, 4096): forward (fp32 and the scaled-fp16 image) and backward, microseconds and GB/s of
      algorithmic traffic, next to the torch-eager expression;
   2. fc1 + GELU epilogue (DIMSUM_GEMM_EPI_GELU_F16) at 65536 x (1024 -> 4096) against the F32_BIAS GEMM + the row pass writing the same image;
   3. one DiT-L/2 inference forward at batch 256 under the scaled-fp16 policy and in exact fp32.

@@ -1,7 +1,7 @@
 """tools/bench_moe.py (GPU box): one SwitchMLP (dimsum_amd/switch_mlp.py) at DiM-L/2's token shape -- 65536 tokens x 1024 channels, 8 experts,
 float32 -- forward and forward + backward, against a torch composition written as the reference writes it (a loop over the experts with
 nonzero(), indexed gathers and indexed scatters into a zero-filled buffer; switch_mlp.py:69-99) in the same process on the same weights; then
-each row pass of csrc/moe.hip alone with its algorithmic bytes over its time, next to gelu_fwd at equal bytes. Device events around windows of
+each row pass of csrc/moe.hip and the experts' activation (csrc/act_rows.hip) alone with its algorithmic bytes over its time, next to gelu_fwd at equal bytes. Device events around windows of
 calls, minimum and median over the windows. Prints figures only: no threshold is asserted anywhere.   [--tokens N --dim H --experts E]"""
 import argparse
 import os
