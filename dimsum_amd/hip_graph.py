@@ -12,11 +12,11 @@ import torch
 class GraphedForward:
     def __init__(self, fn, warmup=3):
         owner = getattr(fn, "__self__", fn)
-        if isinstance(owner, torch.nn.Module) and any(type(m).__name__ == "MoEBlock" for m in owner.modules()):
-            # SwitchMLP reads its E + 1 expert offsets on the host between the sort and the per-expert GEMMs: a capture cannot contain that
-            # copy, and a replay would reuse the captured batch's row slices for every later batch
-            raise NotImplementedError("hip_graph: a model with a MoEBlock cannot be captured -- its SwitchMLP reads the expert offsets on the host "
-                                      "in every forward (is_moe=True runs eagerly)")
+        if isinstance(owner, torch.nn.Module) and any(type(m).__name__ == "SwitchMLP" and not getattr(m, "grouped", False) for m in owner.modules()):
+            # an ungrouped SwitchMLP reads its E + 1 expert offsets on the host between the sort and the per-expert GEMMs: a capture cannot contain
+            # that copy, and a replay would reuse the captured batch's row slices for every later batch. A grouped one reads them on the device.
+            raise NotImplementedError("hip_graph: a model with a MoEBlock whose SwitchMLP is not grouped cannot be captured -- it reads the expert "
+                                      "offsets on the host in every forward (switch_mlp.set_grouped(model, True), sample_ddp.py --moe-grouped)")
         self.fn, self.warmup, self.graphs = fn, warmup, {}
 
     @staticmethod

@@ -2166,3 +2166,43 @@ def einfft_mlp_bwd(dzr, dzi, re, im, zr, zi, w1, b1, w2, b2, lam):
     with torch.cuda.device(re.device):
         _lib.check(_lib.load().dimsum_einfft_mlp_bwd(P, _stream(re)), "dimsum_einfft_mlp_bwd")
     return outs[0], outs[1], (outs[2], outs[3]), (outs[4], outs[5]), (outs[6], outs[7])
+
+
+MOE_GEMM_BM, MOE_GEMM_BN = _lib.MOE_GEMM_BM, _lib.MOE_GEMM_BN      # the output tile of moe_gemm (rows, columns)
+
+
+def moe_gemm_serves(k, n, num_experts):
+    """whether moe_gemm has a kernel for (rows, k) x num_experts (n, k) matrices"""
+    return k > 0 and n > 0 and k % 32 == 0 and n % 32 == 0 and 1 <= num_experts <= MOE_MAX_EXPERTS
+
+
+def moe_gemm(xp, offsets, weights, bias=None, out=None):
+    """xp (T, K) rows sorted by expert, offsets (E + 1) int32 ON THE DEVICE (moe_route_fwd's: non-decreasing in [0, T]; another table is clamped to [0, T] and its ranges are cut where they overlap an earlier one), weights: E
+    (N, K) matrices, bias (E, N) or None -> out (T, N): out[j] = xp[j] W_e^T (+ bias[e]) for offsets[e] <= j < offsets[e + 1]. One launch, no host
+    read of the offsets; fp32 as three bf16 MFMA products (hi hi + hi lo + lo hi), bit-reproducible. out: a (T, N) float32 view with unit column
+    stride (its row stride may exceed N); rows outside every range keep what they held."""
+    _gpu(xp, offsets, bias, out, *weights)
+    E = len(weights)
+    _check(1 <= E <= MOE_MAX_EXPERTS, f"moe_gemm: 1 <= experts <= {MOE_MAX_EXPERTS}")
+    _check(xp.dtype == torch.float32 and xp.dim() == 2 and xp.is_contiguous(), "moe_gemm: xp must be contiguous float32 (T, K)")
+    T, K = xp.shape
+    N = weights[0].shape[0]
+    _check(all(w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and tuple(w.shape) == (N, K) and w.device == xp.device for w in weights),
+           f"moe_gemm: every weight must be contiguous float32 ({N}, {K}) on the rows' device")
+    _check(moe_gemm_serves(K, N, E), f"moe_gemm: K % 32 == 0 and N % 32 == 0 (got K {K}, N {N}); there is no other kernel and no fallback")
+    _check(offsets.dtype == torch.int32 and offsets.is_contiguous() and tuple(offsets.shape) == (E + 1,) and offsets.device == xp.device,
+           f"moe_gemm: offsets must be contiguous int32 ({E + 1},) on the rows' device")
+    _check(bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and tuple(bias.shape) == (E, N)), f"moe_gemm: bias must be contiguous float32 ({E}, {N})")
+    if out is None:
+        out = torch.empty(T, N, device=xp.device, dtype=torch.float32)
+    _check(out.dtype == torch.float32 and tuple(out.shape) == (T, N) and out.device == xp.device and (T == 0 or (out.stride(1) == 1 and out.stride(0) >= N)),
+           f"moe_gemm: out must be a float32 ({T}, {N}) view with unit column stride and row stride >= {N}")
+    if T == 0:
+        return out
+    P = _lib.MoeGemmParams()
+    P.num_experts, P.tokens, P.k, P.n, P.ldc = E, T, K, N, out.stride(0)
+    table = (_lib.vp * E)(*[w.data_ptr() for w in weights])
+    P.x_ptr, P.offsets_ptr, P.w_ptrs, P.bias_ptr, P.out_ptr = _ptr(xp), _ptr(offsets), table, _ptr(bias), _ptr(out)
+    with torch.cuda.device(xp.device):
+        _lib.check(_lib.load().dimsum_moe_gemm(P, _stream(xp)), "moe_gemm")
+    return out

@@ -9,6 +9,9 @@ slices (SwitchMLP.forward, dimsum/switch_mlp.py:69-99; the expert, dimsum/mlp.py
 An expert without tokens gets zero gradients (the reference calls every expert, with zero rows). The reference's forward runs E nonzero() host
 synchronisations, E indexed gathers and E indexed scatters into a zero-filled buffer instead.
 
+A layer built with grouped=True serves calls that do not train from switch_mlp_grouped_fwd instead: the same passes around ONE grouped GEMM launch per
+projection (native.moe_gemm, csrc/moe_gemm.hip) that reads the offsets on the device -- no host read, so the layer can sit inside a captured hipGraph.
+
 `switch_mlp_torch` / `moe_act_torch`: float64 restatements of the reference's expressions -- checkers, not product paths."""
 import torch
 import torch.nn.functional as F
@@ -114,13 +117,36 @@ class _SwitchMlpFn(torch.autograd.Function):
         return (dx.view(dout.shape), drw, drb if ctx.needs_input_grad[2] else None, None, None, None, None, None, *grads)
 
 
-def switch_mlp_fn(x, router_weight, router_bias, fc1_weights, fc2_weights, fc1_biases=None, fc2_biases=None, routing_mode="top1", gated=True):
-    """x (..., H) float32 on the GPU -> prob * expert_e(x) per token, e = the first maximum of sigmoid / softmax of the router logits"""
+def switch_mlp_grouped_fwd(x, router_weight, router_bias, fc1_weights, fc2_weights, fc1_biases, fc2_biases, kind, gated):
+    """the inference forward on the grouped expert GEMM (native.moe_gemm, csrc/moe_gemm.hip): route -> permute -> fc1 -> activation -> fc2 (+ bias) ->
+    combine, the expert offsets never leaving the device. No host synchronisation anywhere: the whole layer can be captured into a hipGraph. No
+    autograd: the caller sends a call that trains to _SwitchMlpFn."""
+    H = x.shape[-1]
+    x2 = x.detach().reshape(-1, H).contiguous()
+    prob, _, _, offsets, perm, _, row_expert = native.moe_route_fwd(x2, router_weight.detach().contiguous(), None if router_bias is None else router_bias.detach(), kind)
+    xp = native.moe_permute(x2, perm)
+    h1 = native.moe_gemm(xp, offsets, [w.detach() for w in fc1_weights])
+    b1 = None if fc1_biases is None else torch.stack([b.detach() for b in fc1_biases]).contiguous()
+    h = native.moe_act_fwd(h1, b1, row_expert, gated)
+    b2 = None if fc2_biases is None else torch.stack([b.detach() for b in fc2_biases]).contiguous()
+    y = native.moe_gemm(h, offsets, [w.detach() for w in fc2_weights], bias=b2)
+    return native.moe_combine_fwd(y, perm, prob).view(x.shape)
+
+
+def switch_mlp_fn(x, router_weight, router_bias, fc1_weights, fc2_weights, fc1_biases=None, fc2_biases=None, routing_mode="top1", gated=True,
+                  grouped=False):
+    """x (..., H) float32 on the GPU -> prob * expert_e(x) per token, e = the first maximum of sigmoid / softmax of the router logits.
+    grouped: a call that does not train (grad mode off, or nothing requires grad) runs on the grouped expert GEMM with no host read of the expert
+    offsets (switch_mlp_grouped_fwd); a call that trains takes _SwitchMlpFn whatever `grouped` says."""
     if x.dtype != torch.float32 or any(w.dtype != torch.float32 for w in (router_weight, *fc1_weights, *fc2_weights)):
         raise RuntimeError("switch_mlp: float32 tokens and parameters only (there is no other kernel and no fallback)")
     E = len(fc1_weights)
     has_bias = fc1_biases is not None
     ws = list(fc1_weights) + list(fc2_weights) + ((list(fc1_biases) + list(fc2_biases)) if has_bias else [])
+    # decided here, OUTSIDE the autograd function (inside its forward grad mode is always off), like fp16 below
+    trains = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, router_weight, router_bias, *ws))
+    if grouped and not trains:
+        return switch_mlp_grouped_fwd(x, router_weight, router_bias, fc1_weights, fc2_weights, fc1_biases, fc2_biases, route_kind(routing_mode), bool(gated))
     # the "fp16" policy serves inference only (gemm._use_fp16): asked here, where grad mode and requires_grad still say whether this call trains
     fp16 = all(gemm._use_fp16(x, w) for w in (router_weight, *ws))
     return _SwitchMlpFn.apply(x, router_weight, router_bias, route_kind(routing_mode), bool(gated), E, has_bias, fp16, *ws)

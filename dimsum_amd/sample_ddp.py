@@ -102,6 +102,8 @@ def build_parser():
     ap.add_argument("--num-moe-experts", type=int, default=8, help="experts per mixture-of-experts layer")
     ap.add_argument("--mamba-moe-layers", type=lambda v: None if v == "None" else v, nargs="*", default=None,
                     help="one entry per layer; the last character of entry layer_idx - 1 is that layer's expert count")
+    ap.add_argument("--moe-grouped", action="store_true",
+                    help="run the experts as one grouped GEMM that reads the expert offsets on the device (no host read per layer: needed by --hip-graph)")
     ap.add_argument("--per-proc-batch-size", type=int, default=128)
     ap.add_argument("--num-fid-samples", type=int, default=1024)
     ap.add_argument("--num-sampling-steps", type=int, default=250)
@@ -133,6 +135,9 @@ def main(argv=None):
     model = model_from_cli(args, log=print if rank == 0 else (lambda *a: None)).to(device).eval()
     if args.ckpt:
         load_denoiser_weights(model, args.ckpt)                  # EMA preferred (download.py:26-27)
+    if args.moe_grouped:
+        from .switch_mlp import set_grouped
+        set_grouped(model, True)
     r = args.image_size // 8
     n_iter = -(-args.num_fid_samples // (args.per_proc_batch_size * world))
     chunks = []

@@ -3,10 +3,16 @@
 routing_mode == "sinkhorn", softmax(logits, 1) for every other value; (p, e) = max(route, 1) (the first maximum on ties);
 out = p * expert_e(x). The forward is ONE autograd function over fused HIP routing passes and per-expert GEMMs on contiguous row slices
 (ops/moe.py, csrc/moe.hip) with one host read of E + 1 ints, where the reference runs E nonzero() synchronisations, E gathers and E scatters.
+With `grouped=True` (or DIMSUM_MOE_GROUPED=1 at construction; `set_grouped(model, True)` on a built model) a call that does not train runs the
+experts as ONE grouped GEMM launch per projection that reads the offsets on the device (csrc/moe_gemm.hip): no host read at all, which is what lets
+hip_graph.GraphedForward capture an is_moe model. Off by default; a call that trains always takes the autograd function above.
 `sinkhorn` is ported for API parity: the reference's forward never calls it."""
+import os
+
 import torch
 import torch.nn as nn
 
+from . import native
 from .mlp import MLP
 from .ops.moe import switch_mlp_fn
 
@@ -31,7 +37,7 @@ class SwitchMLP(nn.Module):
     """Top-1 mixture of experts: routes every token to one of E MLP experts"""
 
     def __init__(self, dim, layer_idx=None, mamba_moe_layers=None, num_moe_experts=None, add_bias_linear=False, gated_linear_unit=True,
-                 routing_mode="top1"):
+                 routing_mode="top1", grouped=None):
         super().__init__()
         self.layer = layer_idx
         if mamba_moe_layers:            # (the last character of the layer's entry: switch_mlp.py:43-44)
@@ -52,6 +58,21 @@ class SwitchMLP(nn.Module):
         self.local_experts = nn.ModuleList(
             MLP(dim, add_bias_linear=add_bias_linear, gated_linear_unit=gated_linear_unit, is_expert=True, layer_idx=layer_idx)
             for _ in range(self.num_local_experts))
+        self.grouped = False
+        self.set_grouped(os.environ.get("DIMSUM_MOE_GROUPED") == "1" if grouped is None else grouped)
+
+    def check_grouped(self):
+        """raises when the grouped expert GEMM does not serve this layer's widths (refused, not emulated)"""
+        for w in (self.local_experts[0].linear_fc1.weight, self.local_experts[0].linear_fc2.weight):
+            if not native.moe_gemm_serves(w.shape[1], w.shape[0], self.num_local_experts):
+                raise NotImplementedError(f"SwitchMLP(grouped=True): the grouped GEMM serves widths that are multiples of 32 (an expert projection "
+                                          f"is {w.shape[1]} -> {w.shape[0]}); there is no fallback")
+
+    def set_grouped(self, on):
+        """serve the calls that do not train from the grouped expert GEMM (no host read of the expert offsets)"""
+        if on:
+            self.check_grouped()
+        self.grouped = bool(on)
 
     def gather_indices(self, local_indices):
         return local_indices
@@ -61,4 +82,15 @@ class SwitchMLP(nn.Module):
         biased = ex[0].linear_fc1.bias is not None
         return switch_mlp_fn(hidden_states, self.router.weight, self.router.bias, [m.linear_fc1.weight for m in ex], [m.linear_fc2.weight for m in ex],
                              [m.linear_fc1.bias for m in ex] if biased else None, [m.linear_fc2.bias for m in ex] if biased else None,
-                             routing_mode=self.routing, gated=self.gated_linear_unit)
+                             routing_mode=self.routing, gated=self.gated_linear_unit, grouped=self.grouped)
+
+
+def set_grouped(model, on=True):
+    """flips `grouped` on every SwitchMLP of a built model -> the number of layers touched"""
+    layers = [m for m in model.modules() if isinstance(m, SwitchMLP)]
+    if on:                                  # every layer is checked before any is flipped: a refusal leaves the model as it was
+        for m in layers:
+            m.check_grouped()
+    for m in layers:
+        m.set_grouped(on)
+    return len(layers)

@@ -979,6 +979,33 @@ typedef struct {
 int dimsum_moe_act_fwd(const dimsum_moe_act_params_t *p, void *stream);
 int dimsum_moe_act_bwd(const dimsum_moe_act_params_t *p, void *stream);
 
+/* dimsum_moe_gemm: the grouped expert GEMM over the sorted rows, out[j, :] = x[j, :] . W_e^T (+ bias[e, :]) for offsets[e] <= j < offsets[e + 1].
+ *   x (tokens, k) f32 contiguous; offsets (num_experts + 1) int32 ON THE DEVICE (what dimsum_moe_route_fwd writes: the host never reads them, so a
+ *   layer built on this entry has no device-to-host copy and can be captured into a hipGraph); w_ptrs: a HOST array of num_experts device pointers to
+ *   (n, k) f32 contiguous matrices (they are copied into the kernel arguments: no device pointer table); bias (num_experts, n) f32 or NULL;
+ *   out (tokens, n) f32 with row stride ldc >= n. Rows outside every expert's range are not written. The offsets are expected to be non-decreasing in [0, tokens]; any other table is made so
+ *   on the device (entries clamped to [0, tokens], a range starts no earlier than the previous non-empty range ended): no row is written twice.
+ *   One launch of (ceil(tokens / DIMSUM_MOE_GEMM_BM) + num_experts) x ceil(n / DIMSUM_MOE_GEMM_BN) workgroups; a workgroup finds its expert from the
+ *   offsets, a tile never spans two experts. fp32 operands are split into bf16 hi + lo while they are staged and multiplied as hi.hi + hi.lo + lo.hi
+ *   on the bf16 MFMA with fp32 accumulation (the three products of the library's fp32 GEMM under allow_tf32); no split-K, no atomics: bit-reproducible.
+ *   Served: k % 32 == 0, n % 32 == 0, 1 <= num_experts <= 64, tokens >= 0 (else DIMSUM_ERR_SHAPE); all pointers 16-byte aligned (offsets: 4),
+ *   ldc % 4 == 0 (else DIMSUM_ERR_STRIDE). tokens == 0 is a valid call that launches nothing (the pointers may then be NULL). */
+#define DIMSUM_MOE_GEMM_BM 64      /* rows of an output tile */
+#define DIMSUM_MOE_GEMM_BN 128     /* columns of an output tile */
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_moe_gemm_params_t) */
+    int32_t num_experts;
+    int64_t tokens, k, n, ldc;
+    const void *x_ptr, *offsets_ptr;
+    const void *const *w_ptrs; /* host array [num_experts] of device pointers */
+    const void *bias_ptr;
+    void *out_ptr;
+    const dimsum_moe_ext_t *ext;   /* NULL = none */
+} dimsum_moe_gemm_params_t;
+
+int dimsum_moe_gemm(const dimsum_moe_gemm_params_t *p, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * NT GEMM with a fused Linear epilogue: C (m, n) = A (m, k) . B (n, k)^T, 16-bit operands (bf16 or fp16 rows, k contiguous), fp32
  * accumulation on v_mfma_f32_16x16x32_*. Replaces the library GEMM behind F.linear(x, weight) for the large bias-free projections

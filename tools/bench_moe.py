@@ -2,7 +2,8 @@
 float32 -- forward and forward + backward, against a torch composition written as the reference writes it (a loop over the experts with
 nonzero(), indexed gathers and indexed scatters into a zero-filled buffer; switch_mlp.py:69-99) in the same process on the same weights; then
 each row pass of csrc/moe.hip and the experts' activation (csrc/act_rows.hip) alone with its algorithmic bytes over its time, next to gelu_fwd at equal bytes. Device events around windows of
-calls, minimum and median over the windows. Prints figures only: no threshold is asserted anywhere.   [--tokens N --dim H --experts E]"""
+calls, minimum and median over the windows. The grouped rows: the same layer with grouped=True (the inference forward on the grouped expert GEMM of
+csrc/moe_gemm.hip, no host read of the offsets) and its two GEMM launches alone with their FLOP rate. Prints figures only: no threshold is asserted anywhere.   [--tokens N --dim H --experts E]"""
 import argparse
 import os
 import sys
@@ -78,6 +79,12 @@ def main():
         for name, fn in (("fused passes", lambda: m(x)), ("torch composition", lambda: reference_forward(m, x))):
             lo, med = timed(fn)
             print(f"  forward            {name:18s} min {lo:8.3f} ms  median {med:8.3f} ms")
+        m.set_grouped(True)
+        grouped = m(x)
+        print(f"  grouped: max |grouped - fused passes| = {(grouped - ours).abs().max().item():.3e}")
+        lo, med = timed(lambda: m(x))
+        print(f"  forward            {'grouped GEMM':18s} min {lo:8.3f} ms  median {med:8.3f} ms")
+        m.set_grouped(False)
     for name, fn in (("fused passes", fb(lambda mm, xx: mm(xx))), ("torch composition", fb(reference_forward))):
         lo, med = timed(fn, n=5)
         print(f"  forward + backward {name:18s} min {lo:8.3f} ms  median {med:8.3f} ms")
@@ -107,6 +114,12 @@ def main():
         for name, fn, nbytes in passes:
             lo, med = timed(fn, n=20)
             print(f"  {name:28s} min {lo * 1e3:9.1f} us  median {med * 1e3:9.1f} us  {nbytes / lo / 1e6:8.1f} GB/s")
+        w1 = [ex.linear_fc1.weight.detach() for ex in m.local_experts]
+        w2 = [ex.linear_fc2.weight.detach() for ex in m.local_experts]
+        for name, a, ws in (("moe_gemm fc1", xp, w1), ("moe_gemm fc2", hh, w2)):
+            lo, med = timed(lambda: native.moe_gemm(a, offsets, ws), n=10)
+            flop = 2.0 * T * ws[0].shape[0] * ws[0].shape[1]
+            print(f"  {name:28s} min {lo * 1e3:9.1f} us  median {med * 1e3:9.1f} us  {flop / lo / 1e9:8.1f} TFLOP/s (fp32-equivalent; 3 bf16 products each)")
 
 
 if __name__ == "__main__":
