@@ -302,6 +302,18 @@ class MoeGemmParams(_Sized):
                  ("w_ptrs", C.POINTER(vp)), ("bias_ptr", vp), ("out_ptr", vp), ("ext", C.POINTER(MoeExt))])
 
 
+class MoeGemmDgradParams(_Sized):
+    """dimsum_moe_gemm_dgrad_params_t: the data gradient of the grouped expert GEMM (w_ptrs: a host array of device pointers)"""
+    _fields_ = ([("struct_size", u32), ("num_experts", i32), ("tokens", i64), ("k", i64), ("n", i64), ("ldc", i64), ("dy_ptr", vp), ("offsets_ptr", vp),
+                 ("w_ptrs", C.POINTER(vp)), ("dx_ptr", vp), ("ext", C.POINTER(MoeExt))])
+
+
+class MoeGemmWgradParams(_Sized):
+    """dimsum_moe_gemm_wgrad_params_t: the weight (and bias) gradients of the grouped expert GEMM (dw_ptrs: a host array of device pointers)"""
+    _fields_ = ([("struct_size", u32), ("num_experts", i32), ("tokens", i64), ("k", i64), ("n", i64), ("dy_ptr", vp), ("x_ptr", vp), ("offsets_ptr", vp),
+                 ("dw_ptrs", C.POINTER(vp)), ("db_ptr", vp), ("ext", C.POINTER(MoeExt))])
+
+
 MOE_ROUTE_SOFTMAX, MOE_ROUTE_SIGMOID = 0, 1
 MOE_GEMM_BM, MOE_GEMM_BN = 64, 128      # DIMSUM_MOE_GEMM_BM / _BN: the output tile of dimsum_moe_gemm
 
@@ -330,6 +342,7 @@ EXPORTS = (
     "dimsum_gelu_fwd", "dimsum_gelu_bwd",
     "dimsum_moe_route_work_bytes", "dimsum_moe_route_fwd", "dimsum_moe_route_bwd", "dimsum_moe_permute", "dimsum_moe_combine_fwd",
     "dimsum_moe_combine_bwd", "dimsum_moe_act_fwd", "dimsum_moe_act_bwd", "dimsum_moe_gemm",
+    "dimsum_moe_gemm_dgrad", "dimsum_moe_gemm_wgrad",
     "dimsum_gemm_nt", "dimsum_gemm_nt_kernel_for", "dimsum_gemm_tn", "dimsum_gemm_nn", "dimsum_row_factors", "dimsum_rows_block_f16s", "dimsum_rows_f16s", "dimsum_rows_f16s_multi",
 )
 
@@ -352,7 +365,8 @@ _SIGNATURES = (
         ("dimsum_selective_state_update", StateUpdateParams), ("dimsum_ssm_scan_general_fwd", SsmGeneralParams),
         ("dimsum_ssm_scan_general_bwd", SsmGeneralBwdParams), ("dimsum_moe_route_fwd", MoeRouteParams), ("dimsum_moe_route_bwd", MoeRouteParams),
         ("dimsum_moe_permute", MoeRowsParams), ("dimsum_moe_combine_fwd", MoeRowsParams), ("dimsum_moe_combine_bwd", MoeRowsParams),
-        ("dimsum_moe_act_fwd", MoeActParams), ("dimsum_moe_act_bwd", MoeActParams), ("dimsum_moe_gemm", MoeGemmParams))]
+        ("dimsum_moe_act_fwd", MoeActParams), ("dimsum_moe_act_bwd", MoeActParams), ("dimsum_moe_gemm", MoeGemmParams),
+        ("dimsum_moe_gemm_dgrad", MoeGemmDgradParams), ("dimsum_moe_gemm_wgrad", MoeGemmWgradParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

@@ -2206,3 +2206,70 @@ def moe_gemm(xp, offsets, weights, bias=None, out=None):
     with torch.cuda.device(xp.device):
         _lib.check(_lib.load().dimsum_moe_gemm(P, _stream(xp)), "moe_gemm")
     return out
+
+
+def _moe_gemm_rows(name, t, what, T=None):
+    _check(t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and (T is None or t.shape[0] == T), f"{name}: {what} must be contiguous float32 ({'T' if T is None else T}, width)")
+
+
+def _moe_gemm_offsets(name, offsets, E, device):
+    _check(offsets.dtype == torch.int32 and offsets.is_contiguous() and tuple(offsets.shape) == (E + 1,) and offsets.device == device,
+           f"{name}: offsets must be contiguous int32 ({E + 1},) on the rows' device")
+
+
+def moe_gemm_dgrad(dy, offsets, weights, out=None):
+    """the data gradient of moe_gemm: dy (T, N) rows sorted by expert, offsets (E + 1) int32 ON THE DEVICE (read, clamped and cut as moe_gemm does),
+    weights: the forward's E (N, K) matrices -> dx (T, K): dx[j] = dy[j] W_e for offsets[e] <= j < offsets[e + 1]. One launch, no host read of the
+    offsets, no W^T in memory; the forward's three bf16 products, bit-reproducible. out: a (T, K) float32 view with unit column stride; rows outside
+    every range keep what they held."""
+    E = len(weights)                                      # (dtypes, shapes and widths first: refused without a GPU; the device last)
+    _check(1 <= E <= MOE_MAX_EXPERTS, f"moe_gemm_dgrad: 1 <= experts <= {MOE_MAX_EXPERTS}")
+    _moe_gemm_rows("moe_gemm_dgrad", dy, "dy")
+    T, N = dy.shape
+    K = weights[0].shape[1] if weights[0].dim() == 2 else -1
+    _check(all(w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and tuple(w.shape) == (N, K) and w.device == dy.device for w in weights),
+           f"moe_gemm_dgrad: every weight must be contiguous float32 ({N}, {K}) on the rows' device")
+    _check(moe_gemm_serves(K, N, E), f"moe_gemm_dgrad: the widths must be multiples of 32 (got K {K}, N {N}); there is no other kernel and no fallback")
+    _moe_gemm_offsets("moe_gemm_dgrad", offsets, E, dy.device)
+    if out is None:
+        out = torch.empty(T, K, device=dy.device, dtype=torch.float32)
+    _check(out.dtype == torch.float32 and tuple(out.shape) == (T, K) and out.device == dy.device and (T == 0 or (out.stride(1) == 1 and out.stride(0) >= K)),
+           f"moe_gemm_dgrad: out must be a float32 ({T}, {K}) view with unit column stride and row stride >= {K}")
+    _gpu(dy, offsets, out, *weights)
+    if T == 0:
+        return out
+    P = _lib.MoeGemmDgradParams()
+    P.num_experts, P.tokens, P.k, P.n, P.ldc = E, T, K, N, out.stride(0)
+    table = (_lib.vp * E)(*[w.data_ptr() for w in weights])
+    P.dy_ptr, P.offsets_ptr, P.w_ptrs, P.dx_ptr = _ptr(dy), _ptr(offsets), table, _ptr(out)
+    with torch.cuda.device(dy.device):
+        _lib.check(_lib.load().dimsum_moe_gemm_dgrad(P, _stream(dy)), "moe_gemm_dgrad")
+    return out
+
+
+def moe_gemm_wgrad(dy, x, offsets, num_experts, need_dbias=False):
+    """the weight gradient of moe_gemm: dy (T, N), x (T, K) rows sorted by expert, offsets (E + 1) int32 ON THE DEVICE -> (E tensors (N, K), db (E, N)
+    or None): dW_e = dy[o_e:o_e+1]^T x[o_e:o_e+1], db[e] = dy[o_e:o_e+1].sum(0). One launch writes every element -- zeros for an expert without rows,
+    decided on the device; no atomics, bit-reproducible."""
+    E = int(num_experts)
+    _check(1 <= E <= MOE_MAX_EXPERTS, f"moe_gemm_wgrad: 1 <= experts <= {MOE_MAX_EXPERTS}")
+    _moe_gemm_rows("moe_gemm_wgrad", dy, "dy")
+    T, N = dy.shape
+    _moe_gemm_rows("moe_gemm_wgrad", x, "x", T)
+    _check(x.device == dy.device, "moe_gemm_wgrad: dy and x must be on one device")
+    K = x.shape[1]
+    _check(moe_gemm_serves(K, N, E), f"moe_gemm_wgrad: the widths must be multiples of 32 (got K {K}, N {N}); there is no other kernel and no fallback")
+    _moe_gemm_offsets("moe_gemm_wgrad", offsets, E, dy.device)
+    _gpu(dy, x, offsets)
+    if T == 0:
+        return list(torch.zeros(E, N, K, device=dy.device, dtype=torch.float32).unbind(0)), (torch.zeros(E, N, device=dy.device, dtype=torch.float32) if need_dbias else None)
+    dw = torch.empty(E, N, K, device=dy.device, dtype=torch.float32)      # (N K % 1024 == 0: every slice is 16-byte aligned)
+    db = torch.empty(E, N, device=dy.device, dtype=torch.float32) if need_dbias else None
+    dws = list(dw.unbind(0))
+    P = _lib.MoeGemmWgradParams()
+    P.num_experts, P.tokens, P.k, P.n = E, T, K, N
+    table = (_lib.vp * E)(*[w.data_ptr() for w in dws])
+    P.dy_ptr, P.x_ptr, P.offsets_ptr, P.dw_ptrs, P.db_ptr = _ptr(dy), _ptr(x), _ptr(offsets), table, _ptr(db)
+    with torch.cuda.device(dy.device):
+        _lib.check(_lib.load().dimsum_moe_gemm_wgrad(P, _stream(dy)), "moe_gemm_wgrad")
+    return dws, db

@@ -12,6 +12,12 @@ synchronisations, E indexed gathers and E indexed scatters into a zero-filled bu
 A layer built with grouped=True serves calls that do not train from switch_mlp_grouped_fwd instead: the same passes around ONE grouped GEMM launch per
 projection (native.moe_gemm, csrc/moe_gemm.hip) that reads the offsets on the device -- no host read, so the layer can sit inside a captured hipGraph.
 
+A layer built with grouped_train=True sends the calls that TRAIN through _SwitchMlpGroupedFn: the grouped forward's launches, and a backward of
+    combine_bwd -> wgrad(dy, h) (+ db2) -> dgrad(dy, W2) -> the activation's adjoint -> wgrad(dh1, xp) -> dgrad(dh1, W1) -> route_bwd
+on the grouped GEMM's data and weight gradients (native.moe_gemm_dgrad / moe_gemm_wgrad, csrc/moe_gemm_bwd.hip). The offsets stay a device tensor from
+the routing pass to the last gradient: no host read in a training step, 4 GEMM launches backward instead of 4 E, and an expert without tokens gets
+the zeros the wgrad kernel stores for an empty range. Opt-in and independent of `grouped`.
+
 `switch_mlp_torch` / `moe_act_torch`: float64 restatements of the reference's expressions -- checkers, not product paths."""
 import torch
 import torch.nn.functional as F
@@ -117,6 +123,61 @@ class _SwitchMlpFn(torch.autograd.Function):
         return (dx.view(dout.shape), drw, drb if ctx.needs_input_grad[2] else None, None, None, None, None, None, *grads)
 
 
+class _SwitchMlpGroupedFn(torch.autograd.Function):
+    """the layer that TRAINS on the grouped expert GEMM: switch_mlp_grouped_fwd's launches forward (so its output is the grouped inference forward's,
+    bit for bit), and a backward on the grouped GEMM's two gradients (native.moe_gemm_dgrad / moe_gemm_wgrad, csrc/moe_gemm_bwd.hip). The offsets
+    are saved as the device tensor they are: no host read in either direction, one launch per product whatever the number of experts, and the
+    zero gradients of an expert without tokens are written by the wgrad kernel."""
+
+    @staticmethod
+    def forward(ctx, x, rw, rb, kind, gated, n_exp, has_bias, *ws):
+        E = n_exp
+        w1, w2 = ws[:E], ws[E:2 * E]
+        b1 = torch.stack(ws[2 * E:3 * E]).contiguous() if has_bias else None
+        b2 = torch.stack(ws[3 * E:4 * E]).contiguous() if has_bias else None
+        H = x.shape[-1]
+        x2 = x.reshape(-1, H).contiguous()
+        rw = rw.contiguous()
+        prob, expert, logits, offsets, perm, inv, row_expert = native.moe_route_fwd(x2, rw, rb, kind)
+        xp = native.moe_permute(x2, perm)
+        h1 = native.moe_gemm(xp, offsets, list(w1))
+        h = native.moe_act_fwd(h1, b1, row_expert, gated)
+        y = native.moe_gemm(h, offsets, list(w2), bias=b2)
+        out = native.moe_combine_fwd(y, perm, prob)
+        ctx.save_for_backward(x2, rw, logits, prob, expert, perm, inv, row_expert, offsets, xp, h1, h, y, b1, *w1, *w2)
+        ctx.kind, ctx.gated, ctx.E, ctx.has_bias = kind, gated, E, has_bias
+        return out.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, rw, logits, prob, expert, perm, inv, row_expert, offsets, xp, h1, h, y, b1 = ctx.saved_tensors[:14]
+        E, need = ctx.E, ctx.needs_input_grad
+        w1, w2 = list(ctx.saved_tensors[14:14 + E]), list(ctx.saved_tensors[14 + E:14 + 2 * E])
+        T, H = x2.shape
+        need_w1, need_w2 = any(need[7:7 + E]), any(need[7 + E:7 + 2 * E])
+        need_b1, need_b2 = ctx.has_bias and any(need[7 + 2 * E:7 + 3 * E]), ctx.has_bias and any(need[7 + 3 * E:7 + 4 * E])
+        need_route = any(need[:3])                          # x or the router: the last dgrad and the router's adjoint
+        dy, dprob = native.moe_combine_bwd(dout.reshape(T, H).contiguous(), y, perm, prob)
+        none = [None] * E
+        dw1, dw2, db1, db2 = none, none, none, none
+        if need_w2 or need_b2:                              # frozen experts: no launch
+            dw2, db = native.moe_gemm_wgrad(dy, h, offsets, E, need_dbias=need_b2)
+            db2 = none if db is None else list(db.unbind(0))
+        dx = drw = drb = None
+        if need_w1 or need_b1 or need_route:
+            dh = native.moe_gemm_dgrad(dy, offsets, w2)
+            dh1, db = native.moe_act_bwd(h1, b1, row_expert, dh, ctx.gated, need_dbias=need_b1)
+            db1 = none if db is None else list(db.unbind(0))
+            if need_w1:
+                dw1, _ = native.moe_gemm_wgrad(dh1, xp, offsets, E)
+            if need_route:
+                dxp = native.moe_gemm_dgrad(dh1, offsets, w1)
+                dx, drw, drb = native.moe_route_bwd(x2, rw, logits, prob, expert, inv, dprob, dxp, ctx.kind)
+                dx = dx.view(dout.shape)
+        grads = dw1 + dw2 + ((db1 + db2) if ctx.has_bias else [])
+        return (dx, drw, drb if need[2] else None, None, None, None, None, *[g if n else None for g, n in zip(grads, need[7:])])
+
+
 def switch_mlp_grouped_fwd(x, router_weight, router_bias, fc1_weights, fc2_weights, fc1_biases, fc2_biases, kind, gated):
     """the inference forward on the grouped expert GEMM (native.moe_gemm, csrc/moe_gemm.hip): route -> permute -> fc1 -> activation -> fc2 (+ bias) ->
     combine, the expert offsets never leaving the device. No host synchronisation anywhere: the whole layer can be captured into a hipGraph. No
@@ -134,10 +195,12 @@ def switch_mlp_grouped_fwd(x, router_weight, router_bias, fc1_weights, fc2_weigh
 
 
 def switch_mlp_fn(x, router_weight, router_bias, fc1_weights, fc2_weights, fc1_biases=None, fc2_biases=None, routing_mode="top1", gated=True,
-                  grouped=False):
+                  grouped=False, grouped_train=False):
     """x (..., H) float32 on the GPU -> prob * expert_e(x) per token, e = the first maximum of sigmoid / softmax of the router logits.
     grouped: a call that does not train (grad mode off, or nothing requires grad) runs on the grouped expert GEMM with no host read of the expert
-    offsets (switch_mlp_grouped_fwd); a call that trains takes _SwitchMlpFn whatever `grouped` says."""
+    offsets (switch_mlp_grouped_fwd); a call that trains takes _SwitchMlpFn whatever `grouped` says.
+    grouped_train: a call that trains takes _SwitchMlpGroupedFn (the grouped GEMM and its two gradients: no host read forward or backward); it
+    changes nothing for a call that does not train."""
     if x.dtype != torch.float32 or any(w.dtype != torch.float32 for w in (router_weight, *fc1_weights, *fc2_weights)):
         raise RuntimeError("switch_mlp: float32 tokens and parameters only (there is no other kernel and no fallback)")
     E = len(fc1_weights)
@@ -147,6 +210,8 @@ def switch_mlp_fn(x, router_weight, router_bias, fc1_weights, fc2_weights, fc1_b
     trains = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, router_weight, router_bias, *ws))
     if grouped and not trains:
         return switch_mlp_grouped_fwd(x, router_weight, router_bias, fc1_weights, fc2_weights, fc1_biases, fc2_biases, route_kind(routing_mode), bool(gated))
+    if grouped_train and trains:
+        return _SwitchMlpGroupedFn.apply(x, router_weight, router_bias, route_kind(routing_mode), bool(gated), E, has_bias, *ws)
     # the "fp16" policy serves inference only (gemm._use_fp16): asked here, where grad mode and requires_grad still say whether this call trains
     fp16 = all(gemm._use_fp16(x, w) for w in (router_weight, *ws))
     return _SwitchMlpFn.apply(x, router_weight, router_bias, route_kind(routing_mode), bool(gated), E, has_bias, fp16, *ws)

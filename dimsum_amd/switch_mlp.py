@@ -6,6 +6,9 @@ out = p * expert_e(x). The forward is ONE autograd function over fused HIP routi
 With `grouped=True` (or DIMSUM_MOE_GROUPED=1 at construction; `set_grouped(model, True)` on a built model) a call that does not train runs the
 experts as ONE grouped GEMM launch per projection that reads the offsets on the device (csrc/moe_gemm.hip): no host read at all, which is what lets
 hip_graph.GraphedForward capture an is_moe model. Off by default; a call that trains always takes the autograd function above.
+With `grouped_train=True` (or DIMSUM_MOE_GROUPED_TRAIN=1 at construction; `set_grouped_train(model, True)` on a built model) a call that TRAINS
+runs on the grouped GEMM too, with its data and weight gradients in the backward (csrc/moe_gemm_bwd.hip): a training step then has no host read in
+any SwitchMLP. Off by default and independent of `grouped`.
 `sinkhorn` is ported for API parity: the reference's forward never calls it."""
 import os
 
@@ -37,7 +40,7 @@ class SwitchMLP(nn.Module):
     """Top-1 mixture of experts: routes every token to one of E MLP experts"""
 
     def __init__(self, dim, layer_idx=None, mamba_moe_layers=None, num_moe_experts=None, add_bias_linear=False, gated_linear_unit=True,
-                 routing_mode="top1", grouped=None):
+                 routing_mode="top1", grouped=None, grouped_train=None):
         super().__init__()
         self.layer = layer_idx
         if mamba_moe_layers:            # (the last character of the layer's entry: switch_mlp.py:43-44)
@@ -60,6 +63,8 @@ class SwitchMLP(nn.Module):
             for _ in range(self.num_local_experts))
         self.grouped = False
         self.set_grouped(os.environ.get("DIMSUM_MOE_GROUPED") == "1" if grouped is None else grouped)
+        self.grouped_train = False
+        self.set_grouped_train(os.environ.get("DIMSUM_MOE_GROUPED_TRAIN") == "1" if grouped_train is None else grouped_train)
 
     def check_grouped(self):
         """raises when the grouped expert GEMM does not serve this layer's widths (refused, not emulated)"""
@@ -67,6 +72,12 @@ class SwitchMLP(nn.Module):
             if not native.moe_gemm_serves(w.shape[1], w.shape[0], self.num_local_experts):
                 raise NotImplementedError(f"SwitchMLP(grouped=True): the grouped GEMM serves widths that are multiples of 32 (an expert projection "
                                           f"is {w.shape[1]} -> {w.shape[0]}); there is no fallback")
+
+    def set_grouped_train(self, on):
+        """serve the calls that train from the grouped expert GEMM and its two gradients (no host read forward or backward)"""
+        if on:                              # the backward's four products run over the forward's two width pairs: what check_grouped passes they serve
+            self.check_grouped()
+        self.grouped_train = bool(on)
 
     def set_grouped(self, on):
         """serve the calls that do not train from the grouped expert GEMM (no host read of the expert offsets)"""
@@ -82,7 +93,7 @@ class SwitchMLP(nn.Module):
         biased = ex[0].linear_fc1.bias is not None
         return switch_mlp_fn(hidden_states, self.router.weight, self.router.bias, [m.linear_fc1.weight for m in ex], [m.linear_fc2.weight for m in ex],
                              [m.linear_fc1.bias for m in ex] if biased else None, [m.linear_fc2.bias for m in ex] if biased else None,
-                             routing_mode=self.routing, gated=self.gated_linear_unit, grouped=self.grouped)
+                             routing_mode=self.routing, gated=self.gated_linear_unit, grouped=self.grouped, grouped_train=self.grouped_train)
 
 
 def set_grouped(model, on=True):
@@ -93,4 +104,15 @@ def set_grouped(model, on=True):
             m.check_grouped()
     for m in layers:
         m.set_grouped(on)
+    return len(layers)
+
+
+def set_grouped_train(model, on=True):
+    """flips `grouped_train` on every SwitchMLP of a built model -> the number of layers touched"""
+    layers = [m for m in model.modules() if isinstance(m, SwitchMLP)]
+    if on:                                  # every layer is checked before any is flipped: a refusal leaves the model as it was
+        for m in layers:
+            m.check_grouped()
+    for m in layers:
+        m.set_grouped_train(on)
     return len(layers)

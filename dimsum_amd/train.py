@@ -115,6 +115,8 @@ def build_parser():
     ap.add_argument("--num-moe-experts", type=int, default=8, help="experts per mixture-of-experts layer")
     ap.add_argument("--mamba-moe-layers", type=lambda v: None if v == "None" else v, nargs="*", default=None,
                     help="one entry per layer; the last character of entry layer_idx - 1 is that layer's expert count")
+    ap.add_argument("--moe-grouped-train", action="store_true",
+                    help="train the experts on the grouped GEMM and its data / weight gradients: no host read of the expert offsets in a step")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--max-grad-norm", type=float, default=2.0)
     ap.add_argument("--path-type", default="GVP")
@@ -154,6 +156,9 @@ def main(argv=None):
     device = local_rank
     torch.manual_seed(args.global_seed * world + rank)
     model = model_from_cli(args, log=print if rank == 0 else (lambda *a: None)).to(device)
+    if args.moe_grouped_train:
+        from .switch_mlp import set_grouped_train
+        set_grouped_train(model, True)
     model, ema, opt = build_training(model, device, args.lr, world, [device])
     transport = transport_from_args(args)
     init_epoch, train_steps = (load_checkpoint(args.resume, model, ema, opt, lr=args.lr) if args.resume else (0, 0))

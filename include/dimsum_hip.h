@@ -1006,6 +1006,40 @@ typedef struct {
 
 int dimsum_moe_gemm(const dimsum_moe_gemm_params_t *p, void *stream);
 
+/* The two gradients of dimsum_moe_gemm (csrc/moe_gemm_bwd.hip), on the same device offsets (clamped and cut the same way), the same three bf16
+ * products and the same widths (k % 32 == 0, n % 32 == 0, 1 <= num_experts <= 64; else DIMSUM_ERR_SHAPE). No split-K, no atomics: bit-reproducible.
+ * The host never reads the offsets: a backward built on these entries has no device-to-host copy. tokens == 0 launches nothing (pointers may be NULL).
+ * dimsum_moe_gemm_dgrad: dx[j, :] = dy[j, :] . W_e for offsets[e] <= j < offsets[e + 1]; dy (tokens, n) f32 contiguous, w_ptrs: a HOST array of
+ *   num_experts device pointers to the (n, k) f32 matrices of the forward (read transposed while they are staged: no W^T in memory), dx (tokens, k)
+ *   f32 with row stride ldc >= k, ldc % 4 == 0. Rows outside every range are not written. Grid: the forward's, over ceil(k / DIMSUM_MOE_GEMM_BN) columns.
+ * dimsum_moe_gemm_wgrad: dW_e[n', k'] = sum over offsets[e] <= j < offsets[e + 1] of dy[j, n'] x[j, k']; dy (tokens, n), x (tokens, k) f32 contiguous;
+ *   dw_ptrs: a HOST array of num_experts device pointers to (n, k) f32 contiguous outputs, every element of which is written (zeros for an empty
+ *   range: no memset before the call); db (num_experts, n) f32 or NULL: db[e, n'] = sum_j dy[j, n'], zeros for an empty range. Grid:
+ *   ceil(k / DIMSUM_MOE_GEMM_BN) x ceil(n / DIMSUM_MOE_GEMM_BM) x num_experts; a workgroup walks its expert's rows 32 at a time, rows past the
+ *   range's end contribute zeros. All row pointers 16-byte aligned (offsets, db: 4), else DIMSUM_ERR_STRIDE. */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_moe_gemm_dgrad_params_t) */
+    int32_t num_experts;
+    int64_t tokens, k, n, ldc;
+    const void *dy_ptr, *offsets_ptr;
+    const void *const *w_ptrs; /* host array [num_experts] of device pointers */
+    void *dx_ptr;
+    const dimsum_moe_ext_t *ext;   /* NULL = none */
+} dimsum_moe_gemm_dgrad_params_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_moe_gemm_wgrad_params_t) */
+    int32_t num_experts;
+    int64_t tokens, k, n;
+    const void *dy_ptr, *x_ptr, *offsets_ptr;
+    void *const *dw_ptrs;      /* host array [num_experts] of device pointers */
+    void *db_ptr;
+    const dimsum_moe_ext_t *ext;   /* NULL = none */
+} dimsum_moe_gemm_wgrad_params_t;
+
+int dimsum_moe_gemm_dgrad(const dimsum_moe_gemm_dgrad_params_t *p, void *stream);
+int dimsum_moe_gemm_wgrad(const dimsum_moe_gemm_wgrad_params_t *p, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * NT GEMM with a fused Linear epilogue: C (m, n) = A (m, k) . B (n, k)^T, 16-bit operands (bf16 or fp16 rows, k contiguous), fp32
  * accumulation on v_mfma_f32_16x16x32_*. Replaces the library GEMM behind F.linear(x, weight) for the large bias-free projections
