@@ -314,6 +314,24 @@ class MoeGemmWgradParams(_Sized):
                  ("dw_ptrs", C.POINTER(vp)), ("db_ptr", vp), ("ext", C.POINTER(MoeExt))])
 
 
+class MoeGemmF16sParams(_Sized):
+    """dimsum_moe_gemm_f16s_params_t: the grouped expert GEMM on scaled-fp16 images (w_ptrs / w_inv_ptrs: host arrays of device pointers)"""
+    _fields_ = ([("struct_size", u32), ("num_experts", i32), ("tokens", i64), ("k", i64), ("n", i64), ("ldc", i64), ("x_ptr", vp), ("x_inv_ptr", vp),
+                 ("offsets_ptr", vp), ("w_ptrs", C.POINTER(vp)), ("w_inv_ptrs", C.POINTER(vp)), ("bias_ptr", vp), ("out_ptr", vp), ("ext", C.POINTER(MoeExt))])
+
+
+class MoePermuteF16sParams(_Sized):
+    """dimsum_moe_permute_f16s_params_t: the permute pass writing the scaled-fp16 image of the sorted rows"""
+    _fields_ = ([("struct_size", u32), ("reserved", i32), ("rows", i64), ("hidden", i64)]
+                + [(n, vp) for n in ("src_ptr", "perm_ptr", "dst_ptr", "inv_scale_ptr")] + [("ext", C.POINTER(MoeExt))])
+
+
+class MoeActF16sParams(_Sized):
+    """dimsum_moe_act_f16s_params_t: the experts' activation writing the scaled-fp16 image of h"""
+    _fields_ = ([("struct_size", u32), ("gated", i32), ("num_experts", i32), ("reserved", i32), ("rows", i64), ("width", i64)]
+                + [(n, vp) for n in ("x_ptr", "bias_ptr", "row_expert_ptr", "out_ptr", "inv_scale_ptr")] + [("ext", C.POINTER(MoeExt))])
+
+
 MOE_ROUTE_SOFTMAX, MOE_ROUTE_SIGMOID = 0, 1
 MOE_GEMM_BM, MOE_GEMM_BN = 64, 128      # DIMSUM_MOE_GEMM_BM / _BN: the output tile of dimsum_moe_gemm
 
@@ -342,7 +360,7 @@ EXPORTS = (
     "dimsum_gelu_fwd", "dimsum_gelu_bwd",
     "dimsum_moe_route_work_bytes", "dimsum_moe_route_fwd", "dimsum_moe_route_bwd", "dimsum_moe_permute", "dimsum_moe_combine_fwd",
     "dimsum_moe_combine_bwd", "dimsum_moe_act_fwd", "dimsum_moe_act_bwd", "dimsum_moe_gemm",
-    "dimsum_moe_gemm_dgrad", "dimsum_moe_gemm_wgrad",
+    "dimsum_moe_gemm_dgrad", "dimsum_moe_gemm_wgrad", "dimsum_moe_gemm_f16s", "dimsum_moe_permute_f16s", "dimsum_moe_act_fwd_f16s",
     "dimsum_gemm_nt", "dimsum_gemm_nt_kernel_for", "dimsum_gemm_tn", "dimsum_gemm_nn", "dimsum_row_factors", "dimsum_rows_block_f16s", "dimsum_rows_f16s", "dimsum_rows_f16s_multi",
 )
 
@@ -366,7 +384,8 @@ _SIGNATURES = (
         ("dimsum_ssm_scan_general_bwd", SsmGeneralBwdParams), ("dimsum_moe_route_fwd", MoeRouteParams), ("dimsum_moe_route_bwd", MoeRouteParams),
         ("dimsum_moe_permute", MoeRowsParams), ("dimsum_moe_combine_fwd", MoeRowsParams), ("dimsum_moe_combine_bwd", MoeRowsParams),
         ("dimsum_moe_act_fwd", MoeActParams), ("dimsum_moe_act_bwd", MoeActParams), ("dimsum_moe_gemm", MoeGemmParams),
-        ("dimsum_moe_gemm_dgrad", MoeGemmDgradParams), ("dimsum_moe_gemm_wgrad", MoeGemmWgradParams))]
+        ("dimsum_moe_gemm_dgrad", MoeGemmDgradParams), ("dimsum_moe_gemm_wgrad", MoeGemmWgradParams),
+        ("dimsum_moe_gemm_f16s", MoeGemmF16sParams), ("dimsum_moe_permute_f16s", MoePermuteF16sParams), ("dimsum_moe_act_fwd_f16s", MoeActF16sParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

@@ -177,9 +177,12 @@ __device__ __forceinline__ float block_allmax(float m, float (*red)[4], int par)
 // 4-column pieces (kStrips x 1024 columns, both halves if gated) in registers between the maximum and the store; the column sums (d bias)
 // accumulate in registers across the rows. row_inv / bound (forward only): the bound-derived scale of the GEMM's GELU_F16 epilogue instead -- no
 // reduction, the LDS is not touched.
-template <class Act, bool kGated, bool kBwd, int kStrips>
+// kPerExpert (forward only): bias is a table (E, S) and row_expert (or NULL: row 0) picks the row's line of it; the registers are reloaded where the
+// expert changes (the rows are sorted by expert: at most E - 1 times over the whole pass).
+template <class Act, bool kGated, bool kBwd, int kStrips, bool kPerExpert = false>
 __global__ __launch_bounds__(256) void act_f16s_kernel(const float *x, const float *bias, const float *dh, __half *img, float *inv, float *dbias,
-                                                       const float *row_inv, const float *bound, int64_t rows, int64_t W, int rows_per_wg) {
+                                                       const float *row_inv, const float *bound, int64_t rows, int64_t W, int rows_per_wg,
+                                                       const int *row_expert = nullptr) {
     __shared__ float red[2][4];
     const int64_t S = kGated ? 2 * W : W;
     float4 ba[kStrips], bg[kStrips];
@@ -189,11 +192,23 @@ __global__ __launch_bounds__(256) void act_f16s_kernel(const float *x, const flo
         const int64_t c = ((int64_t)s * 256 + threadIdx.x) * 4;
         ba[s] = bg[s] = zero4();
         sa[s] = sg[s] = f32x4{};
-        if (bias && c < W) { ba[s] = ldf4(bias + c); if constexpr (kGated) bg[s] = ldf4(bias + W + c); }
+        if (!kPerExpert && bias && c < W) { ba[s] = ldf4(bias + c); if constexpr (kGated) bg[s] = ldf4(bias + W + c); }
     }
+    int cur = -1;                                 // kPerExpert: the expert whose bias row the registers hold
     const float wl1 = (!kBwd && row_inv) ? bound[0] : 0.f, bmax = (!kBwd && row_inv) ? bound[1] : 0.f;
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_wg, r1 = min(rows, r0 + rows_per_wg);
     for (int64_t r = r0; r < r1; ++r) {
+        if constexpr (kPerExpert) {
+            const int ex = row_expert ? row_expert[r] : 0;       // (uniform over the workgroup)
+            if (bias && ex != cur) {
+                cur = ex;
+#pragma unroll
+                for (int s = 0; s < kStrips; ++s) {
+                    const int64_t c = ((int64_t)s * 256 + threadIdx.x) * 4;
+                    if (c < W) { ba[s] = ldf4(bias + cur * S + c); if constexpr (kGated) bg[s] = ldf4(bias + cur * S + W + c); }
+                }
+            }
+        }
         f32x4 va[kStrips], vg[kStrips];          // h (forward); da, dg (backward)
         float m = 0.f;
 #pragma unroll
@@ -273,9 +288,9 @@ int launch_bwd(const void *x, const void *bias, const void *row_expert, const vo
 
 constexpr int64_t kF16sMaxHidden = 5 * 1024;      // five 1024-column strips of registers per thread
 
-template <class Act, bool kGated, bool kBwd>
+template <class Act, bool kGated, bool kBwd, bool kPerExpert = false>
 int launch_f16s(const void *x, const void *bias, const void *dh, void *img, void *inv, void *dbias, const void *row_inv, const void *bound,
-                int64_t rows, int64_t W, void *stream) {
+                int64_t rows, int64_t W, void *stream, const void *row_expert = nullptr) {
     // rows per workgroup: ONE round of 512 workgroups (two per CU; three fit), whatever the batch size, 8 rows at least. Measured on the gated
     // backward (tools/scratch/gg_bwd_time.py, rows per workgroup = rows / div): 16384 rows: 128 workgroups 538 us, 256: 320, 390-512: 262,
     // 780: 348 (a dozen workgroups left over for a second round run alone for a whole workgroup's duration), 1024: 309, 2048+: 350; 65536 rows:
@@ -283,9 +298,10 @@ int launch_f16s(const void *x, const void *bias, const void *dh, void *img, void
     int rpw = (int)((rows + 511) / 512);
     rpw = rpw < 8 ? 8 : rpw;
     const dim3 grid((unsigned)((rows + rpw - 1) / rpw));
-#define DIMSUM_AF(K) hipLaunchKernelGGL((act_f16s_kernel<Act, kGated, kBwd, K>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), f32p(x),     \
-                                        f32p(bias), f32p(dh), reinterpret_cast<__half *>(img), reinterpret_cast<float *>(inv),                          \
-                                        reinterpret_cast<float *>(dbias), f32p(row_inv), f32p(bound), rows, W, rpw)
+#define DIMSUM_AF(K) hipLaunchKernelGGL((act_f16s_kernel<Act, kGated, kBwd, K, kPerExpert>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), \
+                                        f32p(x), f32p(bias), f32p(dh), reinterpret_cast<__half *>(img), reinterpret_cast<float *>(inv),                 \
+                                        reinterpret_cast<float *>(dbias), f32p(row_inv), f32p(bound), rows, W, rpw,                                     \
+                                        reinterpret_cast<const int *>(row_expert))
     switch ((int)((W + 1023) / 1024)) {
         case 1: DIMSUM_AF(1); break;
         case 2: DIMSUM_AF(2); break;
@@ -426,6 +442,24 @@ extern "C" int dimsum_moe_act_fwd(const dimsum_moe_act_params_t *p, void *stream
     if (p->rows == 0) return DIMSUM_OK;
     if (p->gated) return launch_fwd<GeluErf, true, kImgF32, true>(p->x_ptr, p->bias_ptr, p->row_expert_ptr, p->out_ptr, p->rows, p->width, stream);
     return launch_fwd<GeluErf, false, kImgF32, true>(p->x_ptr, p->bias_ptr, p->row_expert_ptr, p->out_ptr, p->rows, p->width, stream);
+}
+
+/* the experts' activation with h as the scaled-fp16 left operand image of the fc2 grouped GEMM (dimsum_moe_gemm_f16s): exact row maxima */
+extern "C" int dimsum_moe_act_fwd_f16s(const dimsum_moe_act_f16s_params_t *p, void *stream) {
+    if (!p) return DIMSUM_ERR_NULL;
+    if (p->struct_size != sizeof(dimsum_moe_act_f16s_params_t)) return DIMSUM_ERR_ABI;
+    dimsum_moe_ext_t e;
+    if (const int rc = ext_from<dimsum_moe_ext_t>(p->ext, e)) return rc;
+    if (p->rows < 0 || p->width <= 0 || p->width % 4 != 0 || p->width > kF16sMaxHidden || p->num_experts < 1 || p->num_experts > 64) return DIMSUM_ERR_SHAPE;
+    if (p->rows == 0) return DIMSUM_OK;
+    if (!p->x_ptr || !p->out_ptr || !p->inv_scale_ptr) return DIMSUM_ERR_NULL;
+    if (!p->row_expert_ptr && p->num_experts != 1) return DIMSUM_ERR_NULL;
+    if (!al16(p->x_ptr) || !aligned_to<char>(p->out_ptr, 8) || !al16(p->bias_ptr) || !al4(p->row_expert_ptr) || !al4(p->inv_scale_ptr)) return DIMSUM_ERR_STRIDE;
+    if (p->gated)
+        return launch_f16s<GeluErf, true, false, true>(p->x_ptr, p->bias_ptr, nullptr, p->out_ptr, p->inv_scale_ptr, nullptr, nullptr, nullptr, p->rows,
+                                                       p->width, stream, p->row_expert_ptr);
+    return launch_f16s<GeluErf, false, false, true>(p->x_ptr, p->bias_ptr, nullptr, p->out_ptr, p->inv_scale_ptr, nullptr, nullptr, nullptr, p->rows,
+                                                    p->width, stream, p->row_expert_ptr);
 }
 
 extern "C" int dimsum_moe_act_bwd(const dimsum_moe_act_params_t *p, void *stream) {

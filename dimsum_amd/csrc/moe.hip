@@ -175,6 +175,42 @@ __global__ __launch_bounds__(256) void moe_rows_kernel(const float *src, const i
     }
 }
 
+// ---- pass c with the result as a scaled-fp16 operand image (common.hpp, f16s): one wave per sorted row j, the row x[perm[j]] held in registers
+// (kXr pieces per lane: rows up to 2048 columns; wider rows read their tail twice) between the exact row maximum and the store. The image is
+// rows_f16s_kernel's of the permuted rows, bit for bit: the same maximum, f16s_scales and f16s_pack4.
+__global__ __launch_bounds__(256) void moe_permute_f16s_kernel(const float *src, const int *perm, __half *dst, float *inv_scale, int64_t rows, int64_t H) {
+    const int lane = threadIdx.x & 63;
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= rows) return;                                   // (wave-uniform)
+    const float *xr = src + (int64_t)perm[j] * H;
+    float4 xv[kXr];
+    float m = 0.f;
+#pragma unroll
+    for (int k = 0; k < kXr; ++k) {
+        const int64_t c = ((int64_t)k * 64 + lane) * 4;
+        xv[k] = c < H ? ldf4(xr + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        m = fmaxf(fmaxf(m, fmaxf(fabsf(xv[k].x), fabsf(xv[k].y))), fmaxf(fabsf(xv[k].z), fabsf(xv[k].w)));
+    }
+    for (int64_t c = ((int64_t)kXr * 64 + lane) * 4; c < H; c += 256) {
+        const float4 v = ldf4(xr + c);
+        m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    }
+    m = wave_allmax(m);
+    float sc, inv;
+    f16s_scales(m, sc, inv);
+    if (lane == 0) inv_scale[j] = inv;
+    __half *row = dst + j * H;
+#pragma unroll
+    for (int k = 0; k < kXr; ++k) {
+        const int64_t c = ((int64_t)k * 64 + lane) * 4;
+        if (c < H) *reinterpret_cast<uint2 *>(row + c) = f16s_pack4(f32x4{{xv[k].x, xv[k].y, xv[k].z, xv[k].w}}, sc);
+    }
+    for (int64_t c = ((int64_t)kXr * 64 + lane) * 4; c < H; c += 256) {
+        const float4 v = ldf4(xr + c);
+        *reinterpret_cast<uint2 *>(row + c) = f16s_pack4(f32x4{{v.x, v.y, v.z, v.w}}, sc);
+    }
+}
+
 // ---- pass e (backward): one wave per permuted row j, t = perm[j]: dy[j] = prob[t] dout[t], dprob[t] = <dout[t], y[j]>; 8 loads in flight per lane
 __global__ __launch_bounds__(256) void moe_combine_bwd_kernel(const float *dout, const float *y, const int *perm, const float *prob, float *dy,
                                                               float *dprob, int64_t rows, int64_t H) {
@@ -378,6 +414,22 @@ extern "C" int dimsum_moe_permute(const dimsum_moe_rows_params_t *p, void *strea
     if (!flat_grid(p->rows * (p->hidden / 4), grid)) return DIMSUM_ERR_SHAPE;
     hipLaunchKernelGGL(moe_rows_kernel<false>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const float *>(p->src_ptr),
                        reinterpret_cast<const int *>(p->perm_ptr), (const float *)nullptr, reinterpret_cast<float *>(p->dst_ptr), p->rows, p->hidden);
+    return launch_status();
+}
+
+extern "C" int dimsum_moe_permute_f16s(const dimsum_moe_permute_f16s_params_t *p, void *stream) {
+    using namespace dimsum;
+    if (!p) return DIMSUM_ERR_NULL;
+    if (p->struct_size != sizeof(dimsum_moe_permute_f16s_params_t)) return DIMSUM_ERR_ABI;
+    dimsum_moe_ext_t e;
+    if (const int rc = ext_from<dimsum_moe_ext_t>(p->ext, e)) return rc;
+    if (p->rows < 0 || p->rows >= ((int64_t)1 << 31) || p->hidden <= 0 || p->hidden % 4 != 0) return DIMSUM_ERR_SHAPE;
+    if (p->rows == 0) return DIMSUM_OK;
+    if (!p->src_ptr || !p->perm_ptr || !p->dst_ptr || !p->inv_scale_ptr) return DIMSUM_ERR_NULL;
+    if (!al16(p->src_ptr) || !aligned_to<char>(p->dst_ptr, 8) || !al4(p->perm_ptr) || !al4(p->inv_scale_ptr)) return DIMSUM_ERR_STRIDE;
+    hipLaunchKernelGGL(moe_permute_f16s_kernel, dim3((unsigned)((p->rows + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       reinterpret_cast<const float *>(p->src_ptr), reinterpret_cast<const int *>(p->perm_ptr), reinterpret_cast<__half *>(p->dst_ptr),
+                       reinterpret_cast<float *>(p->inv_scale_ptr), p->rows, p->hidden);
     return launch_status();
 }
 

@@ -448,6 +448,44 @@ def qkv_f16s(x, weight, bias, rows_per_batch, bound2):
                           q_cols=N // 3)
 
 
+def moe_f16s_enabled(x, fc1_weights, fc2_weights, trains=False):
+    """whether a grouped SwitchMLP forward runs its two expert GEMMs on scaled-fp16 images (native.moe_gemm_f16s: one fp16 product instead of the
+    fp32 grouped kernel's three bf16 products): policy "f16s" under allow_tf32, a call that does not train, float32 tokens and weights on the GPU,
+    widths the kernel serves, and at least DIMSUM_SPLIT3_MIN_ROWS (8192) tokens -- the threshold of every other image carrier: measured, the layer
+    wins 1.65x at 65536 tokens and loses 4 % of a DiM-L/2 forward at 2048 (the row-walking image passes are latency-bound there).
+    DIMSUM_MOE_F16S=0 keeps the fp32 grouped GEMM."""
+    from . import native
+    if not (_policy == "f16s" and torch.backends.cuda.matmul.allow_tf32 and os.environ.get("DIMSUM_MOE_F16S", "1") != "0" and not trains):
+        return False
+    if x.numel() // max(x.shape[-1], 1) < int(os.environ.get("DIMSUM_SPLIT3_MIN_ROWS", "8192")):
+        return False
+    ws = list(fc1_weights) + list(fc2_weights)
+    if not ws or len(fc1_weights) != len(fc2_weights) or x.dtype != torch.float32 or any(w.dtype != torch.float32 or w.dim() != 2 for w in ws):
+        return False
+    (n1, k1), (n2, k2), E = fc1_weights[0].shape, fc2_weights[0].shape, len(fc1_weights)
+    return bool(x.shape[-1] == k1 and native.moe_gemm_serves(k1, n1, E) and native.moe_gemm_serves(k2, n2, E))
+
+
+def expert_images_f16s(weights):
+    """the scaled-fp16 images of a layer's expert matrices: what forward_scope (or a frozen_weights() scope) already holds, and ONE multi-job
+    launch per 24 matrices for the rest -- never one conversion launch per expert (a captured forward has no cache: the launches become part of
+    the graph, 2 E / 24 of them per layer instead of 2 E)."""
+    from . import native
+    frozen = _tls.frozen
+    use_cache = frozen is not None and not (weights[0].is_cuda and torch.cuda.is_current_stream_capturing())
+    key = lambda w: ("w16s", w.data_ptr(), tuple(w.shape), tuple(w.stride()), w.dtype)      # noqa: E731  (_cached's key)
+    hits = [frozen.get(key(w)) if use_cache else None for w in weights]
+    missing = [i for i, h in enumerate(hits) if h is None]
+    images = [None if h is None else h[0][0] for h in hits]
+    if missing:
+        made, scal = native.rows_f16s_multi([(weights[i].detach(), True, n, None, 1.0) for n, i in enumerate(missing)])
+        for n, i in enumerate(missing):
+            images[i] = made[n]
+            if use_cache:
+                frozen[key(weights[i])] = ((made[n], scal[n:n + 1]), weights[i])
+    return images
+
+
 def f16s_plan(model):
     """what a forward of `model` under the scaled-fp16 policy converts: [(weight, kind, bias, partner)] over its large bias-free-GEMM
     Linears -- the mixers' in_proj, the fusion's qkv1 / qkv2 / proj, the shared attention's qkv / proj, the gated MLP's w12 / w3, the plain
@@ -471,6 +509,9 @@ def f16s_plan(model):
             plan += [(m.fc1.weight, "gated", m.fc1.bias, None), (m.fc2.weight, "plain", None, None)]
         elif type(m).__name__ == "Attention" and hasattr(m, "qkv") and hasattr(m, "proj"):
             plan += [(m.qkv.weight, "kv", m.qkv.bias, None), (m.proj.weight, "plain", None, None)]
+        elif type(m).__name__ == "SwitchMLP" and getattr(m, "grouped", False) and os.environ.get("DIMSUM_MOE_F16S", "1") != "0":
+            # the experts of a grouped layer (moe_f16s_enabled): 2 E images per layer ride along in the multi-job launch
+            plan += [(lin.weight, "plain", None, None) for ex in m.local_experts for lin in (ex.linear_fc1, ex.linear_fc2)]
     return plan
 
 

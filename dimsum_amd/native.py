@@ -1122,9 +1122,24 @@ def _moe_rows_call(fn, what, src, perm, prob=None, y=None, want_dprob=False):
     return dst, dprob
 
 
-def moe_permute(x, perm):
-    """xp[j, :] = x[perm[j], :]  (perm: int32, entries in [0, T))"""
-    return _moe_rows_call(_lib.load().dimsum_moe_permute, "moe_permute", x, perm)[0]
+def moe_permute(x, perm, split3=False):
+    """xp[j, :] = x[perm[j], :]  (perm: int32, entries in [0, T))
+    split3="f16s": xp as the scaled-fp16 image (F16Image, exact row maxima) moe_gemm_f16s reads -- rows_f16s(moe_permute(x, perm)) bit for bit, in
+    one pass that writes 2 bytes per element instead of 4 + (4 + 2)"""
+    _check(split3 in (False, "f16s"), "moe_permute: split3 is False or 'f16s'")
+    if not split3:
+        return _moe_rows_call(_lib.load().dimsum_moe_permute, "moe_permute", x, perm)[0]
+    _gpu(x, perm)
+    _moe_rows(x, "moe_permute", "the rows")
+    T, H = x.shape
+    _moe_index(perm, T, "moe_permute", "perm")
+    out, inv, _ = _act_out((T,), H, "f16s", x.device)
+    P = _lib.MoePermuteF16sParams()
+    P.rows, P.hidden = T, H
+    P.src_ptr, P.perm_ptr, P.dst_ptr, P.inv_scale_ptr = _ptr(x), _ptr(perm), _ptr(out), _ptr(inv)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dimsum_moe_permute_f16s(P, _stream(x)), "moe_permute")
+    return F16Image(out, inv)
 
 
 def moe_combine_fwd(y, perm, prob):
@@ -1139,7 +1154,10 @@ def moe_combine_bwd(dout, y, perm, prob):
     return _moe_rows_call(_lib.load().dimsum_moe_combine_bwd, "moe_combine_bwd", dout, perm, prob=prob, y=y, want_dprob=True)
 
 
-def _moe_act_call(fn, what, x, bias, row_expert, dh, gated, need_dbias):
+MOE_ACT_F16S_MAX_WIDTH = 5120      # kF16sMaxHidden of csrc/act_rows.hip: the widest row the image-writing activation pass holds in registers
+
+
+def _moe_act_call(fn, what, x, bias, row_expert, dh, gated, need_dbias, f16s=False):
     _gpu(x, bias, row_expert, dh)
     _moe_rows(x, what)
     rows, S = x.shape
@@ -1155,6 +1173,14 @@ def _moe_act_call(fn, what, x, bias, row_expert, dh, gated, need_dbias):
     _check(row_expert is not None or bias is None or bias.shape[0] == 1, f"{what}: a bias with more than one row needs row_expert")
     if dh is not None:
         _check(dh.dtype == torch.float32 and dh.is_contiguous() and tuple(dh.shape) == (rows, W), f"{what}: dh must be contiguous float32 (rows, W)")
+    if f16s:
+        out, inv, _ = _act_out((rows,), W, "f16s", x.device)
+        P = _lib.MoeActF16sParams()
+        P.gated, P.num_experts, P.rows, P.width = int(bool(gated)), E, rows, W
+        P.x_ptr, P.bias_ptr, P.row_expert_ptr, P.out_ptr, P.inv_scale_ptr = _ptr(x), _ptr(bias), _ptr(row_expert), _ptr(out), _ptr(inv)
+        with torch.cuda.device(x.device):
+            _lib.check(fn(P, _stream(x)), what)
+        return F16Image(out, inv), None
     out, _, dbias = _act_out((rows,), S if dh is not None else W, False, x.device, bias.numel() if (need_dbias and bias is not None) else 0)
     dbias = dbias.view(bias.shape) if dbias is not None else None
     P = _lib.MoeActParams()
@@ -1165,10 +1191,17 @@ def _moe_act_call(fn, what, x, bias, row_expert, dh, gated, need_dbias):
     return out, dbias
 
 
-def moe_act_fwd(x, bias=None, row_expert=None, gated=True):
+def moe_act_fwd(x, bias=None, row_expert=None, gated=True, split3=False):
     """x (rows, 2 W | W) = fc1's output WITHOUT bias, bias (E, 2 W | W) or None picked per row by row_expert (int32; None: row 0) ->
-    gelu_erf(a + b_a) * (g + b_g) (gated) or gelu_erf(x + b): the exact GELU of the reference's expert MLP (dimsum/mlp.py:30-38)"""
-    return _moe_act_call(_lib.load().dimsum_moe_act_fwd, "moe_act_fwd", x, bias, row_expert, None, gated, False)[0]
+    gelu_erf(a + b_a) * (g + b_g) (gated) or gelu_erf(x + b): the exact GELU of the reference's expert MLP (dimsum/mlp.py:30-38)
+    split3="f16s": h as the scaled-fp16 image (F16Image, exact row maxima) of the fc2 grouped GEMM -- rows_f16s(moe_act_fwd(...)) bit for bit; the
+    pass writes it itself up to W = 5120, wider rows are converted from the fp32 result by rows_f16s"""
+    _check(split3 in (False, "f16s"), "moe_act_fwd: split3 is False or 'f16s'")
+    W = x.shape[-1] // 2 if gated else x.shape[-1]
+    if split3 and W <= MOE_ACT_F16S_MAX_WIDTH:
+        return _moe_act_call(_lib.load().dimsum_moe_act_fwd_f16s, "moe_act_fwd", x, bias, row_expert, None, gated, False, f16s=True)[0]
+    h = _moe_act_call(_lib.load().dimsum_moe_act_fwd, "moe_act_fwd", x, bias, row_expert, None, gated, False)[0]
+    return rows_f16s(h) if split3 else h
 
 
 def moe_act_bwd(x, bias, row_expert, dh, gated=True, need_dbias=True):
@@ -2205,6 +2238,45 @@ def moe_gemm(xp, offsets, weights, bias=None, out=None):
     P.x_ptr, P.offsets_ptr, P.w_ptrs, P.bias_ptr, P.out_ptr = _ptr(xp), _ptr(offsets), table, _ptr(bias), _ptr(out)
     with torch.cuda.device(xp.device):
         _lib.check(_lib.load().dimsum_moe_gemm(P, _stream(xp)), "moe_gemm")
+    return out
+
+
+def moe_gemm_f16s(x16, offsets, weight_images, bias=None, out=None):
+    """moe_gemm on scaled-fp16 operand images (csrc/moe_gemm_f16.hip): x16 an F16Image of the (T, K) rows sorted by expert (moe_permute / moe_act_fwd
+    with split3="f16s", rows_f16s), weight_images: E F16Images of the (N, K) matrices (rows_f16s, gemm.weight_f16s), offsets (E + 1) int32 ON THE
+    DEVICE (read, clamped and cut as moe_gemm does), bias (E, N) float32 or None -> out (T, N) float32:
+    out[j, n] = x_inv[j] w_inv_e[n] sum_k x16[j, k] w16_e[n, k] (+ bias[e, n]) for offsets[e] <= j < offsets[e + 1]. One launch, ONE fp16 MFMA product
+    per element with fp32 accumulation, no host read of the offsets, bit-reproducible. out: a (T, N) float32 view with unit column stride (its row
+    stride may exceed N); rows outside every range keep what they held."""
+    E = len(weight_images)                               # (dtypes, shapes and widths first: refused without a GPU; the device last)
+    _check(1 <= E <= MOE_MAX_EXPERTS, f"moe_gemm_f16s: 1 <= experts <= {MOE_MAX_EXPERTS}")
+    _check(isinstance(x16, F16Image) and all(isinstance(w, F16Image) for w in weight_images), "moe_gemm_f16s: the operands must be F16Images (float16 rows + float32 inverse scales)")
+    xd, xi = x16.data, x16.inv
+    _check(xd.dtype == torch.float16 and xd.dim() == 2 and xd.is_contiguous() and xi.dtype == torch.float32 and xi.is_contiguous() and tuple(xi.shape) == (xd.shape[0],)
+           and xi.device == xd.device, "moe_gemm_f16s: x16 must be contiguous float16 (T, K) with float32 (T,) inverse scales")
+    T, K = xd.shape
+    w0 = weight_images[0].data
+    N = w0.shape[0] if w0.dim() == 2 else -1
+    _check(all(w.data.dtype == torch.float16 and w.data.dim() == 2 and w.data.is_contiguous() and tuple(w.data.shape) == (N, K) and w.data.device == xd.device
+               and w.inv.dtype == torch.float32 and w.inv.is_contiguous() and tuple(w.inv.shape) == (N,) and w.inv.device == xd.device for w in weight_images),
+           f"moe_gemm_f16s: every weight image must be contiguous float16 ({N}, {K}) with float32 ({N},) inverse scales on the rows' device")
+    _check(moe_gemm_serves(K, N, E), f"moe_gemm_f16s: K % 32 == 0 and N % 32 == 0 (got K {K}, N {N}); there is no other kernel and no fallback")
+    _moe_gemm_offsets("moe_gemm_f16s", offsets, E, xd.device)
+    _check(bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and tuple(bias.shape) == (E, N)), f"moe_gemm_f16s: bias must be contiguous float32 ({E}, {N})")
+    if out is None:
+        out = torch.empty(T, N, device=xd.device, dtype=torch.float32)
+    _check(out.dtype == torch.float32 and tuple(out.shape) == (T, N) and out.device == xd.device and (T == 0 or (out.stride(1) == 1 and out.stride(0) >= N)),
+           f"moe_gemm_f16s: out must be a float32 ({T}, {N}) view with unit column stride and row stride >= {N}")
+    _gpu(xd, xi, offsets, bias, out, *[t for w in weight_images for t in (w.data, w.inv)])
+    if T == 0:
+        return out
+    P = _lib.MoeGemmF16sParams()
+    P.num_experts, P.tokens, P.k, P.n, P.ldc = E, T, K, N, out.stride(0)
+    table = (_lib.vp * E)(*[w.data.data_ptr() for w in weight_images])
+    inv_table = (_lib.vp * E)(*[w.inv.data_ptr() for w in weight_images])
+    P.x_ptr, P.x_inv_ptr, P.offsets_ptr, P.w_ptrs, P.w_inv_ptrs, P.bias_ptr, P.out_ptr = _ptr(xd), _ptr(xi), _ptr(offsets), table, inv_table, _ptr(bias), _ptr(out)
+    with torch.cuda.device(xd.device):
+        _lib.check(_lib.load().dimsum_moe_gemm_f16s(P, _stream(xd)), "moe_gemm_f16s")
     return out
 
 

@@ -12,6 +12,10 @@ synchronisations, E indexed gathers and E indexed scatters into a zero-filled bu
 A layer built with grouped=True serves calls that do not train from switch_mlp_grouped_fwd instead: the same passes around ONE grouped GEMM launch per
 projection (native.moe_gemm, csrc/moe_gemm.hip) that reads the offsets on the device -- no host read, so the layer can sit inside a captured hipGraph.
 
+Under the "f16s" policy with allow_tf32 (gemm.moe_f16s_enabled: from DIMSUM_SPLIT3_MIN_ROWS tokens on; DIMSUM_MOE_F16S=0 switches it off) that forward runs on scaled-fp16 images instead:
+the permute and the activation write the images, native.moe_gemm_f16s (csrc/moe_gemm_f16.hip) multiplies them with ONE fp16 product per element.
+Still six launches and no host read; calls that train, grouped_train and the "fp16" policy are untouched.
+
 A layer built with grouped_train=True sends the calls that TRAIN through _SwitchMlpGroupedFn: the grouped forward's launches, and a backward of
     combine_bwd -> wgrad(dy, h) (+ db2) -> dgrad(dy, W2) -> the activation's adjoint -> wgrad(dh1, xp) -> dgrad(dh1, W1) -> route_bwd
 on the grouped GEMM's data and weight gradients (native.moe_gemm_dgrad / moe_gemm_wgrad, csrc/moe_gemm_bwd.hip). The offsets stay a device tensor from
@@ -185,6 +189,18 @@ def switch_mlp_grouped_fwd(x, router_weight, router_bias, fc1_weights, fc2_weigh
     H = x.shape[-1]
     x2 = x.detach().reshape(-1, H).contiguous()
     prob, _, _, offsets, perm, _, row_expert = native.moe_route_fwd(x2, router_weight.detach().contiguous(), None if router_bias is None else router_bias.detach(), kind)
+    if gemm.moe_f16s_enabled(x2, fc1_weights, fc2_weights):
+        # policy "f16s": the same six launches on scaled-fp16 images -- the permute and the activation write the left operands of the two grouped
+        # GEMMs themselves (csrc/moe_gemm_f16.hip: one fp16 product). The router and the routing pass above are the fp32 path's: the same experts.
+        E = len(fc1_weights)
+        images = gemm.expert_images_f16s([w.detach() for w in (*fc1_weights, *fc2_weights)])
+        xp = native.moe_permute(x2, perm, split3="f16s")
+        h1 = native.moe_gemm_f16s(xp, offsets, images[:E])
+        b1 = None if fc1_biases is None else torch.stack([b.detach() for b in fc1_biases]).contiguous()
+        h = native.moe_act_fwd(h1, b1, row_expert, gated, split3="f16s")
+        b2 = None if fc2_biases is None else torch.stack([b.detach() for b in fc2_biases]).contiguous()
+        y = native.moe_gemm_f16s(h, offsets, images[E:], bias=b2)
+        return native.moe_combine_fwd(y, perm, prob).view(x.shape)
     xp = native.moe_permute(x2, perm)
     h1 = native.moe_gemm(xp, offsets, [w.detach() for w in fc1_weights])
     b1 = None if fc1_biases is None else torch.stack([b.detach() for b in fc1_biases]).contiguous()

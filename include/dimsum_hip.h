@@ -1040,6 +1040,52 @@ typedef struct {
 int dimsum_moe_gemm_dgrad(const dimsum_moe_gemm_dgrad_params_t *p, void *stream);
 int dimsum_moe_gemm_wgrad(const dimsum_moe_gemm_wgrad_params_t *p, void *stream);
 
+/* The grouped expert GEMM on scaled-fp16 operand images (csrc/moe_gemm_f16.hip; the images: dimsum_rows_f16s above) -- inference under the
+ * scaled-fp16 policy: ONE v_mfma_f32_16x16x32_f16 product per element instead of dimsum_moe_gemm's three bf16 products, fp32 accumulation.
+ *   out[j, n] = x_inv[j] * w_inv_e[n] * sum_k x[j, k] w_e[n, k] (+ bias[e, n])  for offsets[e] <= j < offsets[e + 1]
+ *   x (tokens, k) f16 contiguous with x_inv (tokens) f32; w_ptrs / w_inv_ptrs: HOST arrays of num_experts device pointers to the (n, k) f16
+ *   images and their (n) f32 inverse scales (copied into the kernel arguments); bias (num_experts, n) f32 or NULL; out (tokens, n) f32, row
+ *   stride ldc >= n. Offsets, grid, tiles (DIMSUM_MOE_GEMM_BM x _BN), served shapes, alignment rules and the empty call: dimsum_moe_gemm's.
+ *   No split-K, no atomics: bit-reproducible. The inverse scales are powers of two: the only rounding is the fp32 accumulation (and the bias add).
+ * The two producers write the operand images themselves, bit for bit what dimsum_rows_f16s makes of the f32 pass's output (exact row maxima):
+ * dimsum_moe_permute_f16s: dst[j, :] = f16(src[perm[j], :] 2^s_j), inv_scale[j] = 2^-s_j; src (rows, hidden) f32, hidden % 4 == 0.
+ * dimsum_moe_act_fwd_f16s: dimsum_moe_act_fwd with out (rows, width) f16 and inv_scale (rows); width <= 5120 (else DIMSUM_ERR_SHAPE). */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_moe_gemm_f16s_params_t) */
+    int32_t num_experts;
+    int64_t tokens, k, n, ldc;
+    const void *x_ptr, *x_inv_ptr, *offsets_ptr;
+    const void *const *w_ptrs;     /* host array [num_experts] of device pointers: (n, k) f16 */
+    const void *const *w_inv_ptrs; /* host array [num_experts] of device pointers: (n) f32 */
+    const void *bias_ptr;
+    void *out_ptr;
+    const dimsum_moe_ext_t *ext;   /* NULL = none */
+} dimsum_moe_gemm_f16s_params_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_moe_permute_f16s_params_t) */
+    int32_t reserved;          /* 0 */
+    int64_t rows, hidden;
+    const void *src_ptr, *perm_ptr;
+    void *dst_ptr, *inv_scale_ptr;
+    const dimsum_moe_ext_t *ext;   /* NULL = none */
+} dimsum_moe_permute_f16s_params_t;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(dimsum_moe_act_f16s_params_t) */
+    int32_t gated;             /* bool */
+    int32_t num_experts;
+    int32_t reserved;          /* 0 */
+    int64_t rows, width;
+    const void *x_ptr, *bias_ptr, *row_expert_ptr;
+    void *out_ptr, *inv_scale_ptr;
+    const dimsum_moe_ext_t *ext;   /* NULL = none */
+} dimsum_moe_act_f16s_params_t;
+
+int dimsum_moe_gemm_f16s(const dimsum_moe_gemm_f16s_params_t *p, void *stream);
+int dimsum_moe_permute_f16s(const dimsum_moe_permute_f16s_params_t *p, void *stream);
+int dimsum_moe_act_fwd_f16s(const dimsum_moe_act_f16s_params_t *p, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * NT GEMM with a fused Linear epilogue: C (m, n) = A (m, k) . B (n, k)^T, 16-bit operands (bf16 or fp16 rows, k contiguous), fp32
  * accumulation on v_mfma_f32_16x16x32_*. Replaces the library GEMM behind F.linear(x, weight) for the large bias-free projections

@@ -3,7 +3,8 @@ float32 -- forward and forward + backward, against a torch composition written a
 nonzero(), indexed gathers and indexed scatters into a zero-filled buffer; switch_mlp.py:69-99) in the same process on the same weights; then
 each row pass of csrc/moe.hip and the experts' activation (csrc/act_rows.hip) alone with its algorithmic bytes over its time, next to gelu_fwd at equal bytes. Device events around windows of
 calls, minimum and median over the windows. The grouped rows: the same layer with grouped=True (the inference forward on the grouped expert GEMM of
-csrc/moe_gemm.hip, no host read of the offsets) and its two GEMM launches alone with their FLOP rate. Prints figures only: no threshold is asserted anywhere.   [--tokens N --dim H --experts E]"""
+csrc/moe_gemm.hip, no host read of the offsets) and its two GEMM launches alone with their FLOP rate; the same grouped layer under the "f16s" policy
+(csrc/moe_gemm_f16.hip) next to DIMSUM_MOE_F16S=0, and the fp16 GEMM and its two image producers alone. Prints figures only: no threshold is asserted anywhere.   [--tokens N --dim H --experts E]"""
 import argparse
 import os
 import sys
@@ -84,6 +85,26 @@ def main():
         print(f"  grouped: max |grouped - fused passes| = {(grouped - ours).abs().max().item():.3e}")
         lo, med = timed(lambda: m(x))
         print(f"  forward            {'grouped GEMM':18s} min {lo:8.3f} ms  median {med:8.3f} ms")
+        # the same grouped layer under the "f16s" policy (allow_tf32): the expert GEMMs on scaled-fp16 images (csrc/moe_gemm_f16.hip), next to the same
+        # policy with DIMSUM_MOE_F16S=0 -- the fp32 grouped kernel, what the layer ran under the policy before -- inside one frozen_weights() scope
+        # each (a sampler's: the weight images are built once) and bare (2 E images per call in one multi-job launch)
+        from dimsum_amd import gemm
+        old_tf32 = torch.backends.cuda.matmul.allow_tf32
+        torch.backends.cuda.matmul.allow_tf32 = True
+        gemm.set_policy("f16s")
+        try:
+            one = m(x)
+            print(f"  grouped, policy f16s: max |f16s - fused passes| = {(one - ours).abs().max().item():.3e}")
+            for label, env in (("grouped f16s", "1"), ("grouped f16s off", "0")):
+                os.environ["DIMSUM_MOE_F16S"] = env
+                lo, med = timed(lambda: m(x))
+                with gemm.frozen_weights():
+                    lo_f, med_f = timed(lambda: m(x))
+                print(f"  forward            {label:18s} min {lo:8.3f} ms  median {med:8.3f} ms   frozen weights: min {lo_f:8.3f} ms  median {med_f:8.3f} ms")
+        finally:
+            os.environ.pop("DIMSUM_MOE_F16S", None)
+            gemm.set_policy("default")
+            torch.backends.cuda.matmul.allow_tf32 = old_tf32
         m.set_grouped(False)
     for name, fn in (("fused passes", fb(lambda mm, xx: mm(xx))), ("torch composition", fb(reference_forward))):
         lo, med = timed(fn, n=5)
@@ -120,6 +141,16 @@ def main():
             lo, med = timed(lambda: native.moe_gemm(a, offsets, ws), n=10)
             flop = 2.0 * T * ws[0].shape[0] * ws[0].shape[1]
             print(f"  {name:28s} min {lo * 1e3:9.1f} us  median {med * 1e3:9.1f} us  {flop / lo / 1e9:8.1f} TFLOP/s (fp32-equivalent; 3 bf16 products each)")
+        xp16, hh16 = native.moe_permute(x2, perm, split3="f16s"), native.moe_act_fwd(h1, None, row_expert, True, split3="f16s")
+        for name, a, ws in (("moe_gemm_f16s fc1", xp16, w1), ("moe_gemm_f16s fc2", hh16, w2)):
+            imgs = [native.rows_f16s(w_) for w_ in ws]
+            lo, med = timed(lambda: native.moe_gemm_f16s(a, offsets, imgs), n=10)
+            flop = 2.0 * T * ws[0].shape[0] * ws[0].shape[1]
+            print(f"  {name:28s} min {lo * 1e3:9.1f} us  median {med * 1e3:9.1f} us  {flop / lo / 1e9:8.1f} TFLOP/s (one fp16 product)")
+        for name, fn, nbytes in (("moe_permute (f16s image)", lambda: native.moe_permute(x2, perm, split3="f16s"), T * H * (f4 + 2)),
+                                 ("moe_act_fwd (gated, f16s)", lambda: native.moe_act_fwd(h1, None, row_expert, True, split3="f16s"), T * H * (8 * f4 + 4 * 2))):
+            lo, med = timed(fn, n=20)
+            print(f"  {name:28s} min {lo * 1e3:9.1f} us  median {med * 1e3:9.1f} us  {nbytes / lo / 1e6:8.1f} GB/s")
 
 
 if __name__ == "__main__":
