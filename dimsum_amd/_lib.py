@@ -175,6 +175,23 @@ class ConvBwdParams(_Sized):
                 + [(n, vp) for n in ("dout_ptr", "dx_ptr", "dweight_ptr", "dbias_ptr")])
 
 
+class ConvClParams(_Sized):
+    """dimsum_conv_cl_params_t: the causal conv1d on channel-last operands, (batch, seqlen, dim) with channel stride 1"""
+    _fields_ = ([("struct_size", u32), ("reserved", u32)]
+                + [(n, i32) for n in ("batch", "dim", "seqlen", "width", "silu_activation", "dtype")]
+                + [(n, i64) for n in ("x_batch_stride", "x_l_stride", "weight_c_stride", "weight_width_stride",
+                                      "out_batch_stride", "out_l_stride")]
+                + [(n, vp) for n in ("x_ptr", "weight_ptr", "bias_ptr", "out_ptr")])
+
+
+class ConvClBwdParams(_Sized):
+    """dimsum_conv_cl_bwd_params_t"""
+    _fields_ = ([("struct_size", u32), ("reserved", u32), ("fwd", ConvClParams)]
+                + [(n, i64) for n in ("dout_batch_stride", "dout_l_stride", "dx_batch_stride", "dx_l_stride",
+                                      "dweight_c_stride", "dweight_width_stride")]
+                + [(n, vp) for n in ("dout_ptr", "dx_ptr", "dweight_ptr", "dbias_ptr")])
+
+
 class ConvUpdateParams(_Sized):
     """dimsum_conv_update_params_t: one step of the causal conv1d on a carried (batch, dim, width) state, in place"""
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "dim", "width", "silu_activation", "dtype")] + [("reserved", i32 * 2)]
@@ -355,6 +372,7 @@ EXPORTS = (
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
     "dimsum_einfft_dft", "dimsum_einfft_idft_real", "dimsum_einfft_mlp_fwd", "dimsum_einfft_mlp_bwd",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd", "dimsum_causal_conv1d_update", "dimsum_selective_state_update",
+    "dimsum_causal_conv1d_cl_fwd", "dimsum_causal_conv1d_cl_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
     "dimsum_gelu_fwd", "dimsum_gelu_bwd",
@@ -385,7 +403,8 @@ _SIGNATURES = (
         ("dimsum_moe_permute", MoeRowsParams), ("dimsum_moe_combine_fwd", MoeRowsParams), ("dimsum_moe_combine_bwd", MoeRowsParams),
         ("dimsum_moe_act_fwd", MoeActParams), ("dimsum_moe_act_bwd", MoeActParams), ("dimsum_moe_gemm", MoeGemmParams),
         ("dimsum_moe_gemm_dgrad", MoeGemmDgradParams), ("dimsum_moe_gemm_wgrad", MoeGemmWgradParams),
-        ("dimsum_moe_gemm_f16s", MoeGemmF16sParams), ("dimsum_moe_permute_f16s", MoePermuteF16sParams), ("dimsum_moe_act_fwd_f16s", MoeActF16sParams))]
+        ("dimsum_moe_gemm_f16s", MoeGemmF16sParams), ("dimsum_moe_permute_f16s", MoePermuteF16sParams), ("dimsum_moe_act_fwd_f16s", MoeActF16sParams),
+        ("dimsum_causal_conv1d_cl_fwd", ConvClParams), ("dimsum_causal_conv1d_cl_bwd", ConvClBwdParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

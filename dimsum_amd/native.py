@@ -244,16 +244,26 @@ def selective_scan_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need
 # causal_conv1d_cuda.*   (causal-conv1d/csrc/causal_conv1d.cpp:221-577)
 # ---------------------------------------------------------------------------------------------------------------------
 def _check_conv(x, weight, bias):
+    """the checks of both layouts -> True when x is channel-last and goes to the (batch, seqlen, dim) kernels. A tensor the
+    seqlen-contiguous kernels serve stays with them (causal_conv1d.cpp:242-247 picks the layout the same way)"""
     _gpu(x, weight, bias)
     _check(x.dim() == 3, "causal_conv1d: x must be (batch, dim, seqlen)")
     _check(x.dtype in _DT, "causal_conv1d: input must be float32, float16 or bfloat16")
-    _check(x.stride(2) == 1 or x.shape[2] == 1, "causal_conv1d: only seqlen-contiguous (batch, dim, seqlen) inputs are "
-                                                "supported here (DiMSUM never feeds channel-last)")
+    channel_last = not (x.stride(2) == 1 or x.shape[2] == 1)
+    _check(not channel_last or x.stride(1) == 1 or x.shape[1] == 1,
+           "causal_conv1d: only seqlen-contiguous (batch, dim, seqlen) inputs are "
+           "supported here (DiMSUM never feeds channel-last)")
     dim, width = weight.shape
     _check(dim == x.shape[1], "causal_conv1d: weight must be (dim, width)")
     _check(2 <= width <= 4, "causal_conv1d only supports width between 2 and 4")
     if bias is not None:
         _check(tuple(bias.shape) == (dim,) and bias.stride(-1) == 1, "causal_conv1d: bias must be (dim,)")
+    return channel_last
+
+
+def _is_channel_last(t):
+    """(batch, dim, seqlen) with channel stride 1: what the channel-last kernels address"""
+    return t.stride(1) == 1 or t.shape[1] == 1
 
 
 def _fill_conv(P, x, weight, bias, silu, out):
@@ -266,11 +276,45 @@ def _fill_conv(P, x, weight, bias, silu, out):
         P.out_batch_stride, P.out_c_stride, P.out_ptr = out.stride(0), out.stride(1), _ptr(out)
 
 
+def _fill_conv_cl(P, x, weight, bias, silu, out):
+    """dimsum_conv_cl_params_t from (batch, dim, seqlen) VIEWS with channel stride 1: the token stride is the view's stride(2)"""
+    P.batch, P.dim, P.seqlen = x.shape
+    P.width, P.silu_activation, P.dtype = weight.shape[1], int(bool(silu)), _DT[x.dtype]
+    P.x_batch_stride, P.x_l_stride = x.stride(0), x.stride(2)
+    P.weight_c_stride, P.weight_width_stride = weight.stride(0), weight.stride(1)
+    P.x_ptr, P.weight_ptr, P.bias_ptr = _ptr(x), _ptr(weight), _ptr(bias)
+    if out is not None:
+        P.out_batch_stride, P.out_l_stride, P.out_ptr = out.stride(0), out.stride(2), _ptr(out)
+
+
+CONV_CL_CHUNK = 64        # DIMSUM_CONV_CL_CHUNK: tokens one wave of the channel-last kernels walks; the next chunk re-reads width - 1 halo rows
+
+
+def _new_channel_last(x):
+    """an uninitialised (batch, dim, seqlen) tensor like x whose memory is (batch, seqlen, dim)"""
+    batch, dim, seqlen = x.shape
+    return x.new_empty(batch, seqlen, dim).transpose(1, 2)
+
+
 def causal_conv1d_fwd(x, weight, bias, silu_activation, out=None):
-    """-> out (batch, dim, seqlen), like causal_conv1d_cuda.causal_conv1d_fwd. Weights are used in fp32."""
-    _check_conv(x, weight, bias)
+    """-> out (batch, dim, seqlen), like causal_conv1d_cuda.causal_conv1d_fwd. Weights are used in fp32. A channel-last x (channel stride 1,
+    e.g. the transpose of a (batch, seqlen, dim) activation or of one half of a (batch, seqlen, 2 dim) buffer) is read as it is and out
+    is channel-last too."""
+    channel_last = _check_conv(x, weight, bias)
     weight = weight.float()
     bias = bias.float().contiguous() if bias is not None else None
+    if channel_last:
+        if out is None:
+            out = _new_channel_last(x)
+        else:
+            _gpu(out)
+            _check(out.shape == x.shape and out.dtype == x.dtype and _is_channel_last(out), "causal_conv1d_fwd: out must be channel-last like x")
+        if x.numel() > 0:
+            P = _lib.ConvClParams()
+            _fill_conv_cl(P, x, weight, bias, silu_activation, out)
+            with torch.cuda.device(x.device):
+                _lib.check(_lib.load().dimsum_causal_conv1d_cl_fwd(P, _stream(x)), "causal_conv1d_fwd")
+        return out
     if out is None:
         out = torch.empty_like(x)       # inherits x's layout like the reference (causal_conv1d.cpp:262): d-major in Mamba
     if x.numel() > 0:
@@ -289,14 +333,24 @@ def causal_conv1d_fwd_cond(x, weight, bias, silu_activation, init_x):
 
 
 def causal_conv1d_bwd(x, weight, bias, dout, dx, silu_activation):
-    """-> [dx, dweight, dbias] like causal_conv1d_cuda.causal_conv1d_bwd (dx may be a caller-provided view)."""
-    _check_conv(x, weight, bias)
+    """-> [dx, dweight, dbias] like causal_conv1d_cuda.causal_conv1d_bwd (dx may be a caller-provided view). With a channel-last x, dx is
+    channel-last and a dout of any other layout is brought there once (causal_conv1d.cpp:379)."""
+    channel_last = _check_conv(x, weight, bias)
     _gpu(dout, dx)
-    _check(dout.shape == x.shape and dout.dtype == x.dtype and (dout.stride(2) == 1 or dout.shape[2] == 1), "causal_conv1d_bwd: bad dout")
-    if dx is None:
-        dx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+    if channel_last:
+        _check(dout.shape == x.shape and dout.dtype == x.dtype, "causal_conv1d_bwd: bad dout")
+        if not _is_channel_last(dout):
+            dout = dout.transpose(1, 2).contiguous().transpose(1, 2)
+        if dx is None:
+            dx = _new_channel_last(x)
+        else:
+            _check(dx.shape == x.shape and dx.dtype == x.dtype and _is_channel_last(dx), "causal_conv1d_bwd: bad dx")
     else:
-        _check(dx.shape == x.shape and dx.dtype == x.dtype and dx.stride(2) == 1, "causal_conv1d_bwd: bad dx")
+        _check(dout.shape == x.shape and dout.dtype == x.dtype and (dout.stride(2) == 1 or dout.shape[2] == 1), "causal_conv1d_bwd: bad dout")
+        if dx is None:
+            dx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+        else:
+            _check(dx.shape == x.shape and dx.dtype == x.dtype and dx.stride(2) == 1, "causal_conv1d_bwd: bad dx")
     w32 = weight.float()
     b32 = bias.float().contiguous() if bias is not None else None
     # fp32 accumulate, then cast (cpp:405-425); ONE zero-filled buffer for both accumulators (one fill launch instead of two)
@@ -304,14 +358,21 @@ def causal_conv1d_bwd(x, weight, bias, dout, dx, silu_activation):
     dweight = acc[:weight.numel()].view(weight.shape)
     dbias = acc[weight.numel():] if bias is not None else None
     if x.numel() > 0:
-        Q = _lib.ConvBwdParams()
-        _fill_conv(Q.fwd, x, w32, b32, silu_activation, None)
-        Q.dout_batch_stride, Q.dout_c_stride = dout.stride(0), dout.stride(1)
-        Q.dx_batch_stride, Q.dx_c_stride = dx.stride(0), dx.stride(1)
+        Q = _lib.ConvClBwdParams() if channel_last else _lib.ConvBwdParams()
+        if channel_last:
+            _fill_conv_cl(Q.fwd, x, w32, b32, silu_activation, None)
+            Q.dout_batch_stride, Q.dout_l_stride = dout.stride(0), dout.stride(2)
+            Q.dx_batch_stride, Q.dx_l_stride = dx.stride(0), dx.stride(2)
+        else:
+            _fill_conv(Q.fwd, x, w32, b32, silu_activation, None)
+            Q.dout_batch_stride, Q.dout_c_stride = dout.stride(0), dout.stride(1)
+            Q.dx_batch_stride, Q.dx_c_stride = dx.stride(0), dx.stride(1)
         Q.dweight_c_stride, Q.dweight_width_stride = dweight.stride(0), dweight.stride(1)
         Q.dout_ptr, Q.dx_ptr, Q.dweight_ptr, Q.dbias_ptr = _ptr(dout), _ptr(dx), _ptr(dweight), _ptr(dbias)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dimsum_causal_conv1d_bwd(Q, _stream(x)), "causal_conv1d_bwd")
+            lib = _lib.load()
+            launch = lib.dimsum_causal_conv1d_cl_bwd if channel_last else lib.dimsum_causal_conv1d_bwd
+            _lib.check(launch(Q, _stream(x)), "causal_conv1d_bwd")
     return [dx, dweight.to(weight.dtype), dbias.to(bias.dtype) if bias is not None else None]
 
 

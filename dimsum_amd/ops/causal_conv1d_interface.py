@@ -9,8 +9,8 @@ class CausalConv1dFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias=None, activation=None):
         if activation not in (None, "silu", "swish"):
             raise NotImplementedError("activation must be None, silu, or swish")
-        if x.stride(2) != 1:
-            x = x.contiguous()          # the reference also accepts channel-last; here it is made seqlen-contiguous
+        if x.stride(2) != 1 and x.stride(1) != 1:
+            x = x.contiguous()          # neither seqlen-contiguous nor channel-last (causal_conv1d_interface.py:15-16)
         bias = bias.contiguous() if bias is not None else None
         ctx.save_for_backward(x, weight, bias)
         ctx.activation = activation in ("silu", "swish")
@@ -19,8 +19,9 @@ class CausalConv1dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, weight, bias = ctx.saved_tensors
-        if dout.stride(2) != 1:
-            dout = dout.contiguous()
+        channel_last = not (x.stride(2) == 1 or x.shape[2] == 1)
+        if not channel_last and dout.stride(2) != 1:
+            dout = dout.contiguous()    # a channel-last x takes dout as it comes: native brings it to x's layout once if need be (causal_conv1d.cpp:378-379)
         dx, dweight, dbias = native.causal_conv1d_bwd(x, weight, bias, dout, None, ctx.activation)
         return dx, dweight, dbias if bias is not None else None, None
 

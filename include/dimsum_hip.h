@@ -13,6 +13,7 @@
  *   dimsum_einfft_dft / _idft_real / _mlp_fwd / _mlp_bwd <- EinFFT.forward (+ autograd)   dimsum/models_dim.py:713-775
  *   dimsum_causal_conv1d_fwd   <- causal_conv1d_cuda.causal_conv1d_fwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:221-336
  *   dimsum_causal_conv1d_bwd   <- causal_conv1d_cuda.causal_conv1d_bwd[_cond]   causal-conv1d/csrc/causal_conv1d.cpp:338-509
+ *   dimsum_causal_conv1d_cl_fwd / _cl_bwd <- the same two entries on channel-last operands   causal-conv1d/csrc/causal_conv1d.cpp:242-247, 376-379
  *   dimsum_causal_conv1d_update <- causal_conv1d_cuda.causal_conv1d_update        causal-conv1d/csrc/causal_conv1d.cpp:512-569
  *   dimsum_selective_state_update <- selective_state_update (Triton)              mamba/mamba_ssm/ops/triton/selective_state_update.py:115-190
  *   dimsum_norm_fwd / _bwd     <- _layer_norm_fwd / _layer_norm_bwd (Triton)     mamba/mamba_ssm/ops/triton/layernorm.py:120-364
@@ -560,6 +561,46 @@ typedef struct {
 
 int dimsum_causal_conv1d_fwd(const dimsum_conv_params_t *p, void *stream);
 int dimsum_causal_conv1d_bwd(const dimsum_conv_bwd_params_t *p, void *stream);
+
+/* The same conv on CHANNEL-LAST operands (causal_conv1d_channellast_fwd_kernel / _bwd_kernel, causal-conv1d/csrc/
+ * causal_conv1d_fwd.cu:193-319, causal_conv1d_bwd.cu:306-494; host checks causal_conv1d.cpp:242-247, 376-379, 395-396):
+ *   out[b, t, d] = act(bias[d] + sum_k W[d, k] * x[b, t - (width-1-k), d]),   x[.., t < 0, ..] = 0
+ * x, out, dout, dx are addressed as (batch, seqlen, dim) with channel stride 1; every tensor has its own batch and token
+ * ELEMENT strides (64-bit), so a channel slice of a wider buffer -- one half of a (batch, seqlen, 2 dim) xz -- is a view.
+ * Any dim >= 1 and seqlen >= 1 (the reference's dim % 8 == 0 is not required): 16-byte accesses along the channels where
+ * dim, the strides and the base pointers are multiples of 16 bytes, element accesses otherwise. batch == 0 launches
+ * nothing. weight (dim, width), bias (dim): f32. dweight / dbias: f32, zero-filled by the caller, added to with atomics.
+ * Checks in order: NULL struct, struct_size (DIMSUM_ERR_ABI), required pointers, width / sizes (DIMSUM_ERR_SHAPE), dtype,
+ * negative strides (DIMSUM_ERR_STRIDE). Each chunk of DIMSUM_CONV_CL_CHUNK tokens is walked by one wave per 64 channel
+ * vectors, its width - 1 halo rows re-read from memory. */
+#define DIMSUM_CONV_CL_CHUNK 64
+
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_conv_cl_params_t) */
+    uint32_t reserved;        /* 0 */
+    int32_t batch, dim, seqlen, width;
+    int32_t silu_activation;  /* bool */
+    int32_t dtype;            /* of x/out */
+    int64_t x_batch_stride, x_l_stride;
+    int64_t weight_c_stride, weight_width_stride;
+    int64_t out_batch_stride, out_l_stride;
+    const void *x_ptr, *weight_ptr, *bias_ptr;   /* bias_ptr may be NULL */
+    void *out_ptr;
+} dimsum_conv_cl_params_t;
+
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_conv_cl_bwd_params_t) */
+    uint32_t reserved;        /* 0 */
+    dimsum_conv_cl_params_t fwd; /* out_ptr and the out strides unused */
+    int64_t dout_batch_stride, dout_l_stride;
+    int64_t dx_batch_stride, dx_l_stride;
+    int64_t dweight_c_stride, dweight_width_stride;
+    const void *dout_ptr;
+    void *dx_ptr, *dweight_ptr, *dbias_ptr;      /* dbias_ptr may be NULL */
+} dimsum_conv_cl_bwd_params_t;
+
+int dimsum_causal_conv1d_cl_fwd(const dimsum_conv_cl_params_t *p, void *stream);
+int dimsum_causal_conv1d_cl_bwd(const dimsum_conv_cl_bwd_params_t *p, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The recurrent (token by token) form of the mixer: one step of the causal conv1d and one step of the selective scan on
