@@ -2270,35 +2270,73 @@ def moe_gemm_serves(k, n, num_experts):
     return k > 0 and n > 0 and k % 32 == 0 and n % 32 == 0 and 1 <= num_experts <= MOE_MAX_EXPERTS
 
 
+# ---- what the four wrappers of the grouped expert GEMM share. Every check names the wrapper it refuses for; the ORDER of the checks is each
+# wrapper's own (moe_gemm asks for the device first, the other three refuse dtypes, shapes and widths without a GPU and ask for the device last)
+def _moe_gemm_experts(name, E):
+    _check(1 <= E <= MOE_MAX_EXPERTS, f"{name}: 1 <= experts <= {MOE_MAX_EXPERTS}")
+    return E
+
+
+def _moe_gemm_rows(name, t, what, T=None):
+    _check(t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and (T is None or t.shape[0] == T), f"{name}: {what} must be contiguous float32 ({'T' if T is None else T}, width)")
+
+
+def _moe_gemm_weights(name, weights, N, K, device, f16=False):
+    """the E (N, K) matrices of the experts: float32 tensors, or (f16) F16Images -> (matrices, their (N,) inverse scales or [])"""
+    mats, invs = ([w.data for w in weights], [w.inv for w in weights]) if f16 else (list(weights), [])
+    ok = lambda t, dtype, shape: t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape and t.device == device
+    _check(all(ok(m, torch.float16 if f16 else torch.float32, (N, K)) for m in mats) and all(ok(i, torch.float32, (N,)) for i in invs),
+           f"{name}: every weight image must be contiguous float16 ({N}, {K}) with float32 ({N},) inverse scales on the rows' device" if f16
+           else f"{name}: every weight must be contiguous float32 ({N}, {K}) on the rows' device")
+    return mats, invs
+
+
+def _moe_gemm_offsets(name, offsets, E, device, K, N, rule="the widths must be multiples of 32"):
+    """the served widths, then the offset table"""
+    _check(moe_gemm_serves(K, N, E), f"{name}: {rule} (got K {K}, N {N}); there is no other kernel and no fallback")
+    _check(offsets.dtype == torch.int32 and offsets.is_contiguous() and tuple(offsets.shape) == (E + 1,) and offsets.device == device,
+           f"{name}: offsets must be contiguous int32 ({E + 1},) on the rows' device")
+
+
+def _moe_gemm_out(name, out, T, W, device, bias=None, E=0):
+    """the (E, W) bias where the entry takes one, then the output view (allocated unless given) -> out"""
+    _check(bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and tuple(bias.shape) == (E, W)), f"{name}: bias must be contiguous float32 ({E}, {W})")
+    if out is None:
+        out = torch.empty(T, W, device=device, dtype=torch.float32)
+    _check(out.dtype == torch.float32 and tuple(out.shape) == (T, W) and out.device == device and (T == 0 or (out.stride(1) == 1 and out.stride(0) >= W)),
+           f"{name}: out must be a float32 ({T}, {W}) view with unit column stride and row stride >= {W}")
+    return out
+
+
+def _moe_gemm_launch(name, P, shape, tables, **ptrs):
+    """dimsum_<name>(P) on the device and stream of the first tensor of ptrs; an empty call launches nothing. shape: (E, T, K, N); ptrs: field =
+    tensor or None; tables: field -> the E tensors whose addresses the kernel takes by value"""
+    if shape[1] == 0:
+        return
+    P.num_experts, P.tokens, P.k, P.n = shape
+    for field, t in ptrs.items():
+        setattr(P, field, _ptr(t))
+    for field, ts in tables.items():
+        setattr(P, field, (_lib.vp * len(ts))(*[t.data_ptr() for t in ts]))      # (P holds on to the array)
+    rows = next(iter(ptrs.values()))
+    with torch.cuda.device(rows.device):
+        _lib.check(getattr(_lib.load(), "dimsum_" + name)(P, _stream(rows)), name)
+
+
 def moe_gemm(xp, offsets, weights, bias=None, out=None):
     """xp (T, K) rows sorted by expert, offsets (E + 1) int32 ON THE DEVICE (moe_route_fwd's: non-decreasing in [0, T]; another table is clamped to [0, T] and its ranges are cut where they overlap an earlier one), weights: E
     (N, K) matrices, bias (E, N) or None -> out (T, N): out[j] = xp[j] W_e^T (+ bias[e]) for offsets[e] <= j < offsets[e + 1]. One launch, no host
     read of the offsets; fp32 as three bf16 MFMA products (hi hi + hi lo + lo hi), bit-reproducible. out: a (T, N) float32 view with unit column
     stride (its row stride may exceed N); rows outside every range keep what they held."""
     _gpu(xp, offsets, bias, out, *weights)
-    E = len(weights)
-    _check(1 <= E <= MOE_MAX_EXPERTS, f"moe_gemm: 1 <= experts <= {MOE_MAX_EXPERTS}")
+    E = _moe_gemm_experts("moe_gemm", len(weights))
     _check(xp.dtype == torch.float32 and xp.dim() == 2 and xp.is_contiguous(), "moe_gemm: xp must be contiguous float32 (T, K)")
     T, K = xp.shape
     N = weights[0].shape[0]
-    _check(all(w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and tuple(w.shape) == (N, K) and w.device == xp.device for w in weights),
-           f"moe_gemm: every weight must be contiguous float32 ({N}, {K}) on the rows' device")
-    _check(moe_gemm_serves(K, N, E), f"moe_gemm: K % 32 == 0 and N % 32 == 0 (got K {K}, N {N}); there is no other kernel and no fallback")
-    _check(offsets.dtype == torch.int32 and offsets.is_contiguous() and tuple(offsets.shape) == (E + 1,) and offsets.device == xp.device,
-           f"moe_gemm: offsets must be contiguous int32 ({E + 1},) on the rows' device")
-    _check(bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and tuple(bias.shape) == (E, N)), f"moe_gemm: bias must be contiguous float32 ({E}, {N})")
-    if out is None:
-        out = torch.empty(T, N, device=xp.device, dtype=torch.float32)
-    _check(out.dtype == torch.float32 and tuple(out.shape) == (T, N) and out.device == xp.device and (T == 0 or (out.stride(1) == 1 and out.stride(0) >= N)),
-           f"moe_gemm: out must be a float32 ({T}, {N}) view with unit column stride and row stride >= {N}")
-    if T == 0:
-        return out
-    P = _lib.MoeGemmParams()
-    P.num_experts, P.tokens, P.k, P.n, P.ldc = E, T, K, N, out.stride(0)
-    table = (_lib.vp * E)(*[w.data_ptr() for w in weights])
-    P.x_ptr, P.offsets_ptr, P.w_ptrs, P.bias_ptr, P.out_ptr = _ptr(xp), _ptr(offsets), table, _ptr(bias), _ptr(out)
-    with torch.cuda.device(xp.device):
-        _lib.check(_lib.load().dimsum_moe_gemm(P, _stream(xp)), "moe_gemm")
+    _moe_gemm_weights("moe_gemm", weights, N, K, xp.device)
+    _moe_gemm_offsets("moe_gemm", offsets, E, xp.device, K, N, "K % 32 == 0 and N % 32 == 0")
+    out = _moe_gemm_out("moe_gemm", out, T, N, xp.device, bias, E)
+    _moe_gemm_launch("moe_gemm", _lib.MoeGemmParams(ldc=out.stride(0)), (E, T, K, N), dict(w_ptrs=weights), x_ptr=xp, offsets_ptr=offsets, bias_ptr=bias, out_ptr=out)
     return out
 
 
@@ -2309,8 +2347,7 @@ def moe_gemm_f16s(x16, offsets, weight_images, bias=None, out=None):
     out[j, n] = x_inv[j] w_inv_e[n] sum_k x16[j, k] w16_e[n, k] (+ bias[e, n]) for offsets[e] <= j < offsets[e + 1]. One launch, ONE fp16 MFMA product
     per element with fp32 accumulation, no host read of the offsets, bit-reproducible. out: a (T, N) float32 view with unit column stride (its row
     stride may exceed N); rows outside every range keep what they held."""
-    E = len(weight_images)                               # (dtypes, shapes and widths first: refused without a GPU; the device last)
-    _check(1 <= E <= MOE_MAX_EXPERTS, f"moe_gemm_f16s: 1 <= experts <= {MOE_MAX_EXPERTS}")
+    E = _moe_gemm_experts("moe_gemm_f16s", len(weight_images))
     _check(isinstance(x16, F16Image) and all(isinstance(w, F16Image) for w in weight_images), "moe_gemm_f16s: the operands must be F16Images (float16 rows + float32 inverse scales)")
     xd, xi = x16.data, x16.inv
     _check(xd.dtype == torch.float16 and xd.dim() == 2 and xd.is_contiguous() and xi.dtype == torch.float32 and xi.is_contiguous() and tuple(xi.shape) == (xd.shape[0],)
@@ -2318,36 +2355,13 @@ def moe_gemm_f16s(x16, offsets, weight_images, bias=None, out=None):
     T, K = xd.shape
     w0 = weight_images[0].data
     N = w0.shape[0] if w0.dim() == 2 else -1
-    _check(all(w.data.dtype == torch.float16 and w.data.dim() == 2 and w.data.is_contiguous() and tuple(w.data.shape) == (N, K) and w.data.device == xd.device
-               and w.inv.dtype == torch.float32 and w.inv.is_contiguous() and tuple(w.inv.shape) == (N,) and w.inv.device == xd.device for w in weight_images),
-           f"moe_gemm_f16s: every weight image must be contiguous float16 ({N}, {K}) with float32 ({N},) inverse scales on the rows' device")
-    _check(moe_gemm_serves(K, N, E), f"moe_gemm_f16s: K % 32 == 0 and N % 32 == 0 (got K {K}, N {N}); there is no other kernel and no fallback")
-    _moe_gemm_offsets("moe_gemm_f16s", offsets, E, xd.device)
-    _check(bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and tuple(bias.shape) == (E, N)), f"moe_gemm_f16s: bias must be contiguous float32 ({E}, {N})")
-    if out is None:
-        out = torch.empty(T, N, device=xd.device, dtype=torch.float32)
-    _check(out.dtype == torch.float32 and tuple(out.shape) == (T, N) and out.device == xd.device and (T == 0 or (out.stride(1) == 1 and out.stride(0) >= N)),
-           f"moe_gemm_f16s: out must be a float32 ({T}, {N}) view with unit column stride and row stride >= {N}")
-    _gpu(xd, xi, offsets, bias, out, *[t for w in weight_images for t in (w.data, w.inv)])
-    if T == 0:
-        return out
-    P = _lib.MoeGemmF16sParams()
-    P.num_experts, P.tokens, P.k, P.n, P.ldc = E, T, K, N, out.stride(0)
-    table = (_lib.vp * E)(*[w.data.data_ptr() for w in weight_images])
-    inv_table = (_lib.vp * E)(*[w.inv.data_ptr() for w in weight_images])
-    P.x_ptr, P.x_inv_ptr, P.offsets_ptr, P.w_ptrs, P.w_inv_ptrs, P.bias_ptr, P.out_ptr = _ptr(xd), _ptr(xi), _ptr(offsets), table, inv_table, _ptr(bias), _ptr(out)
-    with torch.cuda.device(xd.device):
-        _lib.check(_lib.load().dimsum_moe_gemm_f16s(P, _stream(xd)), "moe_gemm_f16s")
+    mats, invs = _moe_gemm_weights("moe_gemm_f16s", weight_images, N, K, xd.device, f16=True)
+    _moe_gemm_offsets("moe_gemm_f16s", offsets, E, xd.device, K, N, "K % 32 == 0 and N % 32 == 0")
+    out = _moe_gemm_out("moe_gemm_f16s", out, T, N, xd.device, bias, E)
+    _gpu(xd, xi, offsets, bias, out, *[t for pair in zip(mats, invs) for t in pair])
+    _moe_gemm_launch("moe_gemm_f16s", _lib.MoeGemmF16sParams(ldc=out.stride(0)), (E, T, K, N), dict(w_ptrs=mats, w_inv_ptrs=invs),
+                     x_ptr=xd, x_inv_ptr=xi, offsets_ptr=offsets, bias_ptr=bias, out_ptr=out)
     return out
-
-
-def _moe_gemm_rows(name, t, what, T=None):
-    _check(t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and (T is None or t.shape[0] == T), f"{name}: {what} must be contiguous float32 ({'T' if T is None else T}, width)")
-
-
-def _moe_gemm_offsets(name, offsets, E, device):
-    _check(offsets.dtype == torch.int32 and offsets.is_contiguous() and tuple(offsets.shape) == (E + 1,) and offsets.device == device,
-           f"{name}: offsets must be contiguous int32 ({E + 1},) on the rows' device")
 
 
 def moe_gemm_dgrad(dy, offsets, weights, out=None):
@@ -2355,28 +2369,15 @@ def moe_gemm_dgrad(dy, offsets, weights, out=None):
     weights: the forward's E (N, K) matrices -> dx (T, K): dx[j] = dy[j] W_e for offsets[e] <= j < offsets[e + 1]. One launch, no host read of the
     offsets, no W^T in memory; the forward's three bf16 products, bit-reproducible. out: a (T, K) float32 view with unit column stride; rows outside
     every range keep what they held."""
-    E = len(weights)                                      # (dtypes, shapes and widths first: refused without a GPU; the device last)
-    _check(1 <= E <= MOE_MAX_EXPERTS, f"moe_gemm_dgrad: 1 <= experts <= {MOE_MAX_EXPERTS}")
+    E = _moe_gemm_experts("moe_gemm_dgrad", len(weights))
     _moe_gemm_rows("moe_gemm_dgrad", dy, "dy")
     T, N = dy.shape
     K = weights[0].shape[1] if weights[0].dim() == 2 else -1
-    _check(all(w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and tuple(w.shape) == (N, K) and w.device == dy.device for w in weights),
-           f"moe_gemm_dgrad: every weight must be contiguous float32 ({N}, {K}) on the rows' device")
-    _check(moe_gemm_serves(K, N, E), f"moe_gemm_dgrad: the widths must be multiples of 32 (got K {K}, N {N}); there is no other kernel and no fallback")
-    _moe_gemm_offsets("moe_gemm_dgrad", offsets, E, dy.device)
-    if out is None:
-        out = torch.empty(T, K, device=dy.device, dtype=torch.float32)
-    _check(out.dtype == torch.float32 and tuple(out.shape) == (T, K) and out.device == dy.device and (T == 0 or (out.stride(1) == 1 and out.stride(0) >= K)),
-           f"moe_gemm_dgrad: out must be a float32 ({T}, {K}) view with unit column stride and row stride >= {K}")
+    _moe_gemm_weights("moe_gemm_dgrad", weights, N, K, dy.device)
+    _moe_gemm_offsets("moe_gemm_dgrad", offsets, E, dy.device, K, N)
+    out = _moe_gemm_out("moe_gemm_dgrad", out, T, K, dy.device)
     _gpu(dy, offsets, out, *weights)
-    if T == 0:
-        return out
-    P = _lib.MoeGemmDgradParams()
-    P.num_experts, P.tokens, P.k, P.n, P.ldc = E, T, K, N, out.stride(0)
-    table = (_lib.vp * E)(*[w.data_ptr() for w in weights])
-    P.dy_ptr, P.offsets_ptr, P.w_ptrs, P.dx_ptr = _ptr(dy), _ptr(offsets), table, _ptr(out)
-    with torch.cuda.device(dy.device):
-        _lib.check(_lib.load().dimsum_moe_gemm_dgrad(P, _stream(dy)), "moe_gemm_dgrad")
+    _moe_gemm_launch("moe_gemm_dgrad", _lib.MoeGemmDgradParams(ldc=out.stride(0)), (E, T, K, N), dict(w_ptrs=weights), dy_ptr=dy, offsets_ptr=offsets, dx_ptr=out)
     return out
 
 
@@ -2384,25 +2385,19 @@ def moe_gemm_wgrad(dy, x, offsets, num_experts, need_dbias=False):
     """the weight gradient of moe_gemm: dy (T, N), x (T, K) rows sorted by expert, offsets (E + 1) int32 ON THE DEVICE -> (E tensors (N, K), db (E, N)
     or None): dW_e = dy[o_e:o_e+1]^T x[o_e:o_e+1], db[e] = dy[o_e:o_e+1].sum(0). One launch writes every element -- zeros for an expert without rows,
     decided on the device; no atomics, bit-reproducible."""
-    E = int(num_experts)
-    _check(1 <= E <= MOE_MAX_EXPERTS, f"moe_gemm_wgrad: 1 <= experts <= {MOE_MAX_EXPERTS}")
+    E = _moe_gemm_experts("moe_gemm_wgrad", int(num_experts))
     _moe_gemm_rows("moe_gemm_wgrad", dy, "dy")
     T, N = dy.shape
     _moe_gemm_rows("moe_gemm_wgrad", x, "x", T)
     _check(x.device == dy.device, "moe_gemm_wgrad: dy and x must be on one device")
     K = x.shape[1]
-    _check(moe_gemm_serves(K, N, E), f"moe_gemm_wgrad: the widths must be multiples of 32 (got K {K}, N {N}); there is no other kernel and no fallback")
-    _moe_gemm_offsets("moe_gemm_wgrad", offsets, E, dy.device)
+    _moe_gemm_offsets("moe_gemm_wgrad", offsets, E, dy.device, K, N)
     _gpu(dy, x, offsets)
-    if T == 0:
-        return list(torch.zeros(E, N, K, device=dy.device, dtype=torch.float32).unbind(0)), (torch.zeros(E, N, device=dy.device, dtype=torch.float32) if need_dbias else None)
-    dw = torch.empty(E, N, K, device=dy.device, dtype=torch.float32)      # (N K % 1024 == 0: every slice is 16-byte aligned)
-    db = torch.empty(E, N, device=dy.device, dtype=torch.float32) if need_dbias else None
+    new = torch.empty if T > 0 else torch.zeros          # (an empty call launches nothing: its zeros are made here)
+    dw = new(E, N, K, device=dy.device, dtype=torch.float32)              # (N K % 1024 == 0: every slice is 16-byte aligned)
+    db = new(E, N, device=dy.device, dtype=torch.float32) if need_dbias else None
     dws = list(dw.unbind(0))
-    P = _lib.MoeGemmWgradParams()
-    P.num_experts, P.tokens, P.k, P.n = E, T, K, N
-    table = (_lib.vp * E)(*[w.data_ptr() for w in dws])
-    P.dy_ptr, P.x_ptr, P.offsets_ptr, P.dw_ptrs, P.db_ptr = _ptr(dy), _ptr(x), _ptr(offsets), table, _ptr(db)
-    with torch.cuda.device(dy.device):
-        _lib.check(_lib.load().dimsum_moe_gemm_wgrad(P, _stream(dy)), "moe_gemm_wgrad")
+    _moe_gemm_launch("moe_gemm_wgrad", _lib.MoeGemmWgradParams(), (E, T, K, N), dict(dw_ptrs=dws), dy_ptr=dy, x_ptr=x, offsets_ptr=offsets, db_ptr=db)
     return dws, db
+
+
