@@ -96,6 +96,13 @@ class SsmGeneralBwdParams(_Sized):
                 + [("workspace_bytes", i64)])
 
 
+class SsmCarryParams(_Sized):
+    """dimsum_ssm_carry_params_t: the general forward entered with a carried (batch, dim, dstate) state h0, leaving hT (may be h0: in place)"""
+    _fields_ = ([("struct_size", u32), ("state_dtype", i32), ("scan", SsmGeneralParams)]
+                + [(n, i64) for n in ("h0_batch_stride", "h0_d_stride", "h0_dstate_stride", "hT_batch_stride", "hT_d_stride", "hT_dstate_stride")]
+                + [("h0_ptr", vp), ("hT_ptr", vp)])
+
+
 class OptimParams(_Sized):
     """dimsum_optim_params_t: device tables of the tensor list + hyper-parameters of one clip / AdamW / EMA step"""
     _fields_ = ([("struct_size", u32), ("n_tensors", i32), ("n_chunks", i32), ("n_partials", i32)]
@@ -195,6 +202,14 @@ class ConvClBwdParams(_Sized):
 class ConvUpdateParams(_Sized):
     """dimsum_conv_update_params_t: one step of the causal conv1d on a carried (batch, dim, width) state, in place"""
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "dim", "width", "silu_activation", "dtype")] + [("reserved", i32 * 2)]
+                + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "state_batch_stride", "state_c_stride", "state_w_stride",
+                                      "weight_c_stride", "weight_width_stride", "out_batch_stride", "out_c_stride")]
+                + [(n, vp) for n in ("x_ptr", "weight_ptr", "bias_ptr", "conv_state_ptr", "out_ptr")])
+
+
+class ConvChunkParams(_Sized):
+    """dimsum_conv_chunk_params_t: any number of tokens of the causal conv1d on a carried (batch, dim, width) state, in place"""
+    _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("batch", "dim", "seqlen", "width", "silu_activation", "dtype", "reserved")]
                 + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "state_batch_stride", "state_c_stride", "state_w_stride",
                                       "weight_c_stride", "weight_width_stride", "out_batch_stride", "out_c_stride")]
                 + [(n, vp) for n in ("x_ptr", "weight_ptr", "bias_ptr", "conv_state_ptr", "out_ptr")])
@@ -367,6 +382,7 @@ EXPORTS = (
     "dimsum_ssm_scan_fwd", "dimsum_ssm_scan_bwd", "dimsum_ssm_scan_bwd_workspace_bytes", "dimsum_ssm_scan_fwd_variant",
     "dimsum_ssm_scan_bidir_fwd", "dimsum_ssm_scan_bidir_bwd", "dimsum_ssm_scan_bidir_fwd_variant",
     "dimsum_ssm_scan_general_fwd", "dimsum_ssm_scan_general_bwd", "dimsum_ssm_scan_general_bwd_workspace_bytes",
+    "dimsum_ssm_scan_carry_fwd", "dimsum_causal_conv1d_chunk",
     "dimsum_optim_grad_sumsq", "dimsum_optim_adamw_ema_step", "dimsum_optim_write_ptrs",
     "dimsum_fm_plan", "dimsum_fm_loss_fwd", "dimsum_fm_loss_bwd",
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
@@ -404,7 +420,8 @@ _SIGNATURES = (
         ("dimsum_moe_act_fwd", MoeActParams), ("dimsum_moe_act_bwd", MoeActParams), ("dimsum_moe_gemm", MoeGemmParams),
         ("dimsum_moe_gemm_dgrad", MoeGemmDgradParams), ("dimsum_moe_gemm_wgrad", MoeGemmWgradParams),
         ("dimsum_moe_gemm_f16s", MoeGemmF16sParams), ("dimsum_moe_permute_f16s", MoePermuteF16sParams), ("dimsum_moe_act_fwd_f16s", MoeActF16sParams),
-        ("dimsum_causal_conv1d_cl_fwd", ConvClParams), ("dimsum_causal_conv1d_cl_bwd", ConvClBwdParams))]
+        ("dimsum_causal_conv1d_cl_fwd", ConvClParams), ("dimsum_causal_conv1d_cl_bwd", ConvClBwdParams),
+        ("dimsum_ssm_scan_carry_fwd", SsmCarryParams), ("dimsum_causal_conv1d_chunk", ConvChunkParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

@@ -1,4 +1,4 @@
-// causal_conv1d.hip -- depthwise causal conv1d (width 2..4) + bias + SiLU, forward and backward, for gfx950.
+// causal_conv1d.hip -- depthwise causal conv1d (width 2..4) + bias + SiLU, forward, backward and the forward on a carried state, for gfx950.
 //
 // Replaces causal_conv1d_cuda.causal_conv1d_fwd[_cond] / _bwd[_cond] (causal-conv1d/csrc/causal_conv1d.cpp:221-509;
 // kernels causal_conv1d_fwd.cu:39-130, causal_conv1d_bwd.cu:46-240):
@@ -112,6 +112,81 @@ __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(const dimsum_con
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// the forward on a carried state (dimsum_causal_conv1d_chunk): the same row walk, the left halo of the first 256-element step taken from
+// conv_state instead of zeros, and conv_state <- the last W values of concat(conv_state, x) afterwards. One row per wave and pass (a
+// continuation is a short sequence: the rows, not the loads of one wave, fill the chip). Lane k < W is the only lane that reads or
+// writes conv_state[k] of the wave's row -- the others get the old values through cross-lane moves -- so the in-place update is
+// ordered by that lane's own program order. The values travel as raw bits: moved, never converted.
+template <typename T> __device__ __forceinline__ unsigned raw_bits(T v) {
+    if constexpr (sizeof(T) == 4) {
+        unsigned r;
+        __builtin_memcpy(&r, &v, 4);
+        return r;
+    } else {
+        unsigned short r;
+        __builtin_memcpy(&r, &v, 2);
+        return r;
+    }
+}
+template <typename T> __device__ __forceinline__ T from_bits(unsigned r) {
+    T v;
+    if constexpr (sizeof(T) == 4) {
+        __builtin_memcpy(&v, &r, 4);
+    } else {
+        const unsigned short h = (unsigned short)r;
+        __builtin_memcpy(&v, &h, 2);
+    }
+    return v;
+}
+
+template <typename T, bool kVec>
+__global__ __launch_bounds__(256) void causal_conv1d_chunk_kernel(const dimsum_conv_chunk_params_t p) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t rows = (int64_t)p.batch * p.dim;
+    const int L = p.seqlen, W = p.width;
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
+        const int b = (int)(row / p.dim), d = (int)(row - (int64_t)b * p.dim);
+        const T *x = reinterpret_cast<const T *>(p.x_ptr) + (int64_t)b * p.x_batch_stride + (int64_t)d * p.x_c_stride;
+        T *o = reinterpret_cast<T *>(p.out_ptr) + (int64_t)b * p.out_batch_stride + (int64_t)d * p.out_c_stride;
+        T *st = reinterpret_cast<T *>(p.conv_state_ptr) + (int64_t)b * p.state_batch_stride + (int64_t)d * p.state_c_stride;
+        const float *wp = reinterpret_cast<const float *>(p.weight_ptr) + (int64_t)d * p.weight_c_stride;
+        float w4[4];                                             // taps right-aligned into 4 slots, as in the forward kernel
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w4[k] = (k >= 4 - W) ? wp[(k - (4 - W)) * p.weight_width_stride] : 0.f;
+        const float bias = p.bias_ptr ? reinterpret_cast<const float *>(p.bias_ptr)[d] : 0.f;
+        const unsigned own = lane < W ? raw_bits<T>(st[lane * p.state_w_stride]) : 0u;      // the old state, element `lane`
+        // x[-1], x[-2], x[-3] = the state's last W - 1 elements (its first one has left the window); what a narrower conv has no tap for is 0
+        const float s1 = to_f32<T>(from_bits<T>(__shfl(own, W - 1, kWave)));
+        const float s2 = to_f32<T>(from_bits<T>(__shfl(own, W >= 3 ? W - 2 : 0, kWave)));
+        const float s3 = to_f32<T>(from_bits<T>(__shfl(own, 1, kWave)));
+        float c1 = s1, c2 = W >= 3 ? s2 : 0.f, c3 = W >= 4 ? s3 : 0.f;
+        for (int t0 = 0; t0 < L; t0 += 4 * kWave) {
+            const int t = t0 + lane * 4;
+            const f32x4 v = load_row4<T, kVec>(x, t, L);
+            const float m1 = lane_up(v.v[3], c1), m2 = lane_up(v.v[2], c2), m3 = lane_up(v.v[1], c3);
+            f32x4 q;
+            q.v[0] = bias + w4[0] * m3 + w4[1] * m2 + w4[2] * m1 + w4[3] * v.v[0];
+            q.v[1] = bias + w4[0] * m2 + w4[1] * m1 + w4[2] * v.v[0] + w4[3] * v.v[1];
+            q.v[2] = bias + w4[0] * m1 + w4[1] * v.v[0] + w4[2] * v.v[1] + w4[3] * v.v[2];
+            q.v[3] = bias + w4[0] * v.v[0] + w4[1] * v.v[1] + w4[2] * v.v[2] + w4[3] * v.v[3];
+            if (p.silu_activation) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) q.v[e] *= sigmoidf_fast(q.v[e]);
+            }
+            store_row4<T, kVec>(o, t, L, q);
+            c1 = __shfl(v.v[3], kWave - 1, kWave);
+            c2 = __shfl(v.v[2], kWave - 1, kWave);
+            c3 = __shfl(v.v[1], kWave - 1, kWave);
+        }
+        // the new state: element k = element k + L of concat(old state, x) -- an old value (seqlen < width) or x[k + L - W]
+        const int64_t j = (int64_t)lane + L;
+        const unsigned moved = __shfl(own, j < W ? (int)j : 0, kWave);
+        if (lane < W) st[lane * p.state_w_stride] = j < W ? from_bits<T>(moved) : x[j - W];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // backward. grid = (dim, n_split): wave (d, s) owns batch rows b = s, s + n_split*4, ... of channel d.
 template <typename T, bool kVec>
 __global__ __launch_bounds__(256) void causal_conv1d_bwd_kernel(const dimsum_conv_bwd_params_t q) {
@@ -213,7 +288,35 @@ template <typename T> static int launch_conv_bwd(const dimsum_conv_bwd_params_t 
     return launch_status();
 }
 
+template <typename T> static int launch_conv_chunk(const dimsum_conv_chunk_params_t &p, hipStream_t s) {
+    const bool vec = vec_ok<T>(p.x_ptr, p.x_batch_stride, p.x_c_stride, p.seqlen) &&
+                     vec_ok<T>(p.out_ptr, p.out_batch_stride, p.out_c_stride, p.seqlen);
+    const int64_t rows = (int64_t)p.batch * p.dim;
+    const int grid = (int)((rows + 3) / 4 < 256 * 32 ? (rows + 3) / 4 : 256 * 32);   // 4 waves per workgroup, one row per wave and pass
+    if (vec) hipLaunchKernelGGL((causal_conv1d_chunk_kernel<T, true>), dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((causal_conv1d_chunk_kernel<T, false>), dim3(grid), dim3(256), 0, s, p);
+    return launch_status();
+}
+
 }  // namespace dimsum
+
+extern "C" int dimsum_causal_conv1d_chunk(const dimsum_conv_chunk_params_t *p, void *stream) {
+    using namespace dimsum;
+    if (!p) return DIMSUM_ERR_NULL;
+    if (p->struct_size != sizeof(dimsum_conv_chunk_params_t)) return DIMSUM_ERR_ABI;
+    if (!p->x_ptr || !p->weight_ptr || !p->conv_state_ptr || !p->out_ptr) return DIMSUM_ERR_NULL;
+    if (p->width < 2 || p->width > 4 || p->batch < 1 || p->dim < 1 || p->seqlen < 1) return DIMSUM_ERR_SHAPE;
+    if (p->dtype < DIMSUM_F32 || p->dtype > DIMSUM_BF16) return DIMSUM_ERR_DTYPE;
+    for (int64_t s : {p->x_batch_stride, p->x_c_stride, p->state_batch_stride, p->state_c_stride, p->state_w_stride, p->weight_c_stride,
+                      p->weight_width_stride, p->out_batch_stride, p->out_c_stride})
+        if (s < 0) return DIMSUM_ERR_STRIDE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (p->dtype) {
+        case DIMSUM_F32: return launch_conv_chunk<float>(*p, s);
+        case DIMSUM_F16: return launch_conv_chunk<__half>(*p, s);
+        default: return launch_conv_chunk<__hip_bfloat16>(*p, s);
+    }
+}
 
 extern "C" int dimsum_causal_conv1d_fwd(const dimsum_conv_params_t *p, void *stream) {
     using namespace dimsum;

@@ -17,13 +17,24 @@
 // what it wrote itself), then the tiles are walked from the last to the first: the tile's kT states are rebuilt from the saved one and the
 // adjoint recurrence runs backwards over them. Sums over a group's channels (input-dependent dB / dC: a DPP wave reduction per value) and
 // over the batch (dA, constant dB / dC, dD, ddelta_bias) are fp32 atomics into zero-filled outputs: not bit-repeatable.
+// A carried state (dimsum_ssm_scan_carry_fwd, forward only) is a load before the walk and a store after it: the states live in registers, each
+// (channel, state) in exactly one lane, so that lane reads its h0 element, walks the sequence and writes its hT element -- hT may be h0.
 #include "common.hpp"
 
 namespace dimsum {
 
+// the carried state of dimsum_ssm_scan_carry_fwd: both pointers NULL for every other entry point
+struct gen_carry_t {
+    const void *h0_ptr;
+    void *hT_ptr;
+    int64_t h0_batch_stride, h0_d_stride, h0_dstate_stride, hT_batch_stride, hT_d_stride, hT_dstate_stride;
+    int32_t f32;                           // the state is float (pairs, with complex A); else of the I/O type
+};
+
 struct gen_args_t {
     dimsum_ssm_general_params_t f;
     dimsum_ssm_general_bwd_params_t b;     // b.fwd is not used (f is)
+    gen_carry_t c;                         // forward only
     int32_t cblocks;                       // 64-channel blocks per group
     int64_t dpad;                          // padded channel count of the saved states: n_groups * cblocks * 64
 };
@@ -127,8 +138,15 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
     load_weight_rows<kCplx, kNB>(p.A_ptr, p.A_d_stride, p.A_dstate_stride, q, N, A);
     if constexpr (!kVarB) load_weight_rows<kCplx, kNB>(p.B_ptr, p.B_d_stride, p.B_dstate_stride, q, N, Bc);
     if constexpr (!kVarC) load_weight_rows<kCplx, kNB>(p.C_ptr, p.C_d_stride, p.C_dstate_stride, q, N, Cc);
+    // the carried state: this lane's own elements, read before the walk and written after it (hT may be h0: no other lane touches them);
+    // states beyond dstate and masked channels stay 0
 #pragma unroll
-    for (int j = 0; j < kNB * kK; ++j) h[j] = 0.f;
+    for (int j = 0; j < kNB; ++j) {
+        const bool ok = a.c.h0_ptr && q.live && q.n0 + j < N;
+        const int64_t off = q.b * a.c.h0_batch_stride + q.d * a.c.h0_d_stride + (q.n0 + j) * a.c.h0_dstate_stride;
+#pragma unroll
+        for (int c = 0; c < kK; ++c) h[j * kK + c] = !ok ? 0.f : (kCplx || a.c.f32) ? ld_f32<float>(a.c.h0_ptr, off * kK + c) : ld_f32<T>(a.c.h0_ptr, off);
+    }
     const float bias = (p.delta_bias_ptr && q.live) ? reinterpret_cast<const float *>(p.delta_bias_ptr)[q.d] : 0.f;
     const float Dd = (p.D_ptr && q.live) ? reinterpret_cast<const float *>(p.D_ptr)[q.d] : 0.f;
     const bool sp = p.delta_softplus != 0;
@@ -209,6 +227,21 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
             }
         }
         __syncthreads();
+    }
+    if (a.c.hT_ptr && q.live) {
+#pragma unroll
+        for (int j = 0; j < kNB; ++j) {
+            if (q.n0 + j >= N) continue;
+            const int64_t off = q.b * a.c.hT_batch_stride + q.d * a.c.hT_d_stride + (q.n0 + j) * a.c.hT_dstate_stride;
+            if constexpr (kCplx) {
+                reinterpret_cast<float *>(a.c.hT_ptr)[off * 2] = h[2 * j];
+                reinterpret_cast<float *>(a.c.hT_ptr)[off * 2 + 1] = h[2 * j + 1];
+            } else if (a.c.f32) {
+                reinterpret_cast<float *>(a.c.hT_ptr)[off] = h[j];
+            } else {
+                reinterpret_cast<T *>(a.c.hT_ptr)[off] = from_f32<T>(h[j]);
+            }
+        }
     }
 }
 
@@ -558,6 +591,29 @@ extern "C" int dimsum_ssm_scan_general_fwd(const dimsum_ssm_general_params_t *p,
     gen_args_t a;
     memset(&a, 0, sizeof(a));
     a.f = *p;
+    return gen_run(a, true, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dimsum_ssm_scan_carry_fwd(const dimsum_ssm_carry_params_t *p, void *stream) {
+    using namespace dimsum;
+    if (!p) return DIMSUM_ERR_NULL;
+    if (p->struct_size != sizeof(dimsum_ssm_carry_params_t)) return DIMSUM_ERR_ABI;
+    const bool carried = p->h0_ptr || p->hT_ptr;
+    int rc = gen_check(p->scan, true);
+    // gen_check stops at its first failure, in the documented order: the state's dtype belongs right after the scan's, before any stride
+    if (rc != DIMSUM_OK && rc != DIMSUM_ERR_STRIDE) return rc;
+    if (carried && p->state_dtype != DIMSUM_F32 && (p->scan.is_complex || p->state_dtype != p->scan.dtype)) return DIMSUM_ERR_DTYPE;
+    if (rc != DIMSUM_OK) return rc;
+    for (int64_t s : {p->h0_batch_stride, p->h0_d_stride, p->h0_dstate_stride, p->hT_batch_stride, p->hT_d_stride, p->hT_dstate_stride})
+        if (carried && s < 0) return DIMSUM_ERR_STRIDE;
+    gen_args_t a;
+    memset(&a, 0, sizeof(a));
+    a.f = p->scan;
+    a.c.h0_ptr = p->h0_ptr;
+    a.c.hT_ptr = p->hT_ptr;
+    a.c.h0_batch_stride = p->h0_batch_stride, a.c.h0_d_stride = p->h0_d_stride, a.c.h0_dstate_stride = p->h0_dstate_stride;
+    a.c.hT_batch_stride = p->hT_batch_stride, a.c.hT_d_stride = p->hT_d_stride, a.c.hT_dstate_stride = p->hT_dstate_stride;
+    a.c.f32 = p->state_dtype == DIMSUM_F32;
     return gen_run(a, true, reinterpret_cast<hipStream_t>(stream));
 }
 

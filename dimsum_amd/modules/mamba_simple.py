@@ -8,9 +8,10 @@ the two kernels of csrc/mixer_step.hip update in place. The caller advances `seq
 a prompt shorter than d_conv leaves its tokens zero-padded on the left in conv_state (what a causal conv sees before the first token; upstream
 Mamba pads the same way) where the reference's `conv_state.copy_(x[:, :, -d_conv:])` (:258) raises a shape error. Refused, with the reason in
 the message: scan_type "v2" (the backward-direction twin has no causal recurrence), the zigzag scan types (a permuted sequence has no
-token-by-token order) and the operand-image input `x3` (inference images and a cache do not combine). Continuing a cached sequence with
-more than one token per call is not implemented (it would need a scan that starts from a carried state). The recurrent form is for inference:
-the cache is filled without autograd edges and the two step kernels have no backward.
+token-by-token order) and the operand-image input `x3` (inference images and a cache do not combine). A cached sequence is continued by
+more than one token per call through `extend` (a causal conv and a scan that enter with the cache's states and leave the new ones behind;
+`dimsum_amd.utils.chunked_prefill` walks a long prompt with it); `step` and `forward` at `seqlen_offset > 0` keep taking one token. The
+recurrent form is for inference: the cache is filled without autograd edges and the step and extend kernels have no backward.
 
 Differences that do not change results:
   * `cond_proj(c)` is numerically dead in the reference (its output only donates a buffer to the conv kernel,
@@ -209,6 +210,35 @@ class _MambaBase(nn.Module):
             y = selective_state_update(ssm_state, x, dt, A, B, C, self.D, z=z, dt_bias=self.dt_proj.bias, dt_softplus=True)
         out = F.linear(y, self.out_proj.weight, self.out_proj.bias)
         return out.unsqueeze(1), conv_state, ssm_state
+
+    @torch.no_grad()
+    def extend(self, hidden_states, conv_state, ssm_state):
+        """any number of tokens on carried states, the sibling of `step`: hidden_states (B, T, d_model), T >= 1 -> (out (B, T, d_model),
+        conv_state, ssm_state), both states updated in place: in_proj (d-major, as _mix forms xz) -> causal_conv1d_chunk -> x_proj / dt_proj
+        (the general path of mamba_inner_fn) -> the scan entered with ssm_state and leaving it (csrc/ssm_scan_general.hip) with the z gate ->
+        out_proj. No host read and no allocation depends on data: one call can be captured on a single stream."""
+        self._refuse_recurrent()
+        bsz, T, _ = hidden_states.shape
+        assert T >= 1, "extend needs at least one token"
+        D, R, N = self.d_inner, self.dt_rank, self.d_state
+        xz = gemm.matmul_wx(self.in_proj.weight, hidden_states.reshape(bsz * T, -1).t()).view(2 * D, bsz, T).permute(1, 0, 2)
+        if self.in_proj.bias is not None:
+            xz = xz + self.in_proj.bias.to(xz.dtype).view(1, -1, 1)
+        x, z = xz[:, :D], xz[:, D:]
+        cw = self.conv1d.weight
+        conv_out = native.causal_conv1d_chunk(x, conv_state, cw.reshape(cw.shape[0], cw.shape[-1]), self.conv1d.bias, True)
+        conv_rows = conv_out.permute(1, 0, 2).reshape(D, bsz * T)                           # "b d l -> d (b l)": a view of a d-major conv_out
+        x_dbl_t = self.x_proj.weight @ conv_rows                                            # (R + 2N, b l)
+        delta = (self.dt_proj.weight @ x_dbl_t[:R]).view(D, bsz, T).permute(1, 0, 2)        # without the bias: the scan adds it
+        Bm = x_dbl_t[R:R + N].view(N, bsz, T).permute(1, 0, 2).unsqueeze(1)                 # (b, 1, N, l) views, unit stride along l
+        Cm = x_dbl_t[R + N:].view(N, bsz, T).permute(1, 0, 2).unsqueeze(1)
+        A = gemm.neg_exp(self.A_log)
+        y = native.selective_scan_carry_fwd(conv_out, delta, A, Bm, Cm, self.D.float(), z, self.dt_proj.bias.float(), True, ssm_state, ssm_state)
+        if self.out_proj.bias is None:
+            out = gemm.linear(y.transpose(1, 2), self.out_proj.weight)
+        else:
+            out = F.linear(y.transpose(1, 2), self.out_proj.weight, self.out_proj.bias)
+        return out, conv_state, ssm_state
 
     def _forward_cached(self, hidden_states, cond, inference_params, x3):
         """forward(inference_params=...): a prompt at seqlen_offset 0 (fused path + the states it leaves behind), one step after it"""

@@ -410,6 +410,40 @@ def causal_conv1d_update(x, conv_state, weight, bias, silu_activation):
     return out
 
 
+def causal_conv1d_chunk(x, conv_state, weight, bias, silu_activation):
+    """-> out (batch, dim, seqlen) in x's layout: causal_conv1d_update for any number of tokens (no reference counterpart). The conv sees
+    conv_state[.., 1:] to the left of x; conv_state (batch, dim, width) becomes the last `width` values of concat(conv_state, x), in place.
+    x needs stride(-1) == 1; its batch and channel strides and all of conv_state's are free. Weights are used in fp32.
+    Shape, dtype and stride refusals first (they need no GPU), the device last."""
+    _check(x.dim() == 3 and x.dtype in _DT, "causal_conv1d_chunk: x must be (batch, dim, seqlen) in float32, float16 or bfloat16")
+    batch, dim, seqlen = x.shape
+    _check(batch >= 1 and dim >= 1 and seqlen >= 1, "causal_conv1d_chunk: x must not be empty")
+    _check(weight.dim() == 2 and weight.shape[0] == dim, "causal_conv1d_chunk: weight must be (dim, width)")
+    width = weight.shape[1]
+    _check(2 <= width <= 4, "causal_conv1d_chunk only supports width between 2 and 4")
+    _check(conv_state.dim() == 3 and tuple(conv_state.shape) == (batch, dim, width) and conv_state.dtype == x.dtype,
+           "causal_conv1d_chunk: conv_state must be (batch, dim, width) of x's dtype")
+    if bias is not None:
+        _check(tuple(bias.shape) == (dim,), "causal_conv1d_chunk: bias must be (dim,)")
+    _check(x.stride(2) == 1 or seqlen == 1, "causal_conv1d_chunk: x.stride(-1) must be 1")
+    _gpu(x, conv_state, weight, bias)
+    weight = weight.float()
+    bias = bias.float().contiguous() if bias is not None else None
+    out = torch.empty_like(x)           # x's layout: d-major in the mixer
+    if out.stride(2) != 1 and seqlen > 1:
+        out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+    P = _lib.ConvChunkParams()
+    P.batch, P.dim, P.seqlen, P.width, P.silu_activation, P.dtype = batch, dim, seqlen, width, int(bool(silu_activation)), _DT[x.dtype]
+    P.x_batch_stride, P.x_c_stride = x.stride(0), x.stride(1)
+    P.state_batch_stride, P.state_c_stride, P.state_w_stride = conv_state.stride()
+    P.weight_c_stride, P.weight_width_stride = weight.stride()
+    P.out_batch_stride, P.out_c_stride = out.stride(0), out.stride(1)
+    P.x_ptr, P.weight_ptr, P.bias_ptr, P.conv_state_ptr, P.out_ptr = _ptr(x), _ptr(weight), _ptr(bias), _ptr(conv_state), _ptr(out)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dimsum_causal_conv1d_chunk(P, _stream(x)), "causal_conv1d_chunk")
+    return out
+
+
 def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False, dt_proj=None):
     """-> out (batch, dim), like the reference's selective_state_update: state (batch, dim, dstate) <- state exp(dt' A) + dt' B x in place,
     dt' = [softplus](dt + dt_bias); out = sum_n state C + D x, times silu(z). fp32 arithmetic; x, dt, z share one dtype, state and B / C
@@ -769,6 +803,47 @@ def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softpl
         with torch.cuda.device(u.device):
             _lib.check(_lib.load().dimsum_ssm_scan_general_fwd(P, _stream(u)), "selective_scan_general_fwd")
     return [out, x] + ([out_z] if z is not None else [])
+
+
+def _check_carried_state(t, name, u, A):
+    batch, dim, _ = u.shape
+    want = torch.complex64 if A.is_complex() else None
+    _check(t.dim() == 3 and tuple(t.shape) == (batch, dim, A.shape[1]), f"selective_scan_carry: {name} must be (batch, dim, dstate)")
+    _check(t.dtype == want if want is not None else t.dtype in (torch.float32, u.dtype),
+           f"selective_scan_carry: {name} must be float32 or of u's dtype (complex64 with complex A)")
+
+
+def selective_scan_carry_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, initial_state, final_state):
+    """-> out (batch, dim, seqlen), gated by silu(z) where z is given: the general forward (selective_scan_general_fwd's operands) entered
+    with the carried state `initial_state` (batch, dim, dstate) instead of zeros -- None means zeros -- and leaving the state after the last
+    step in `final_state` -- None means not wanted. Both are float32 or of u's dtype (complex64 with complex A), with free strides, and
+    may be the SAME tensor: a cache, or a strided slice of one, updated in place. Inference only: there is no backward.
+    Shape, dtype and stride refusals first (they need no GPU), the device last."""
+    for t, name in ((initial_state, "initial_state"), (final_state, "final_state")):
+        if t is not None:
+            _check_carried_state(t, name, u, A)
+    if initial_state is not None and final_state is not None:
+        _check(initial_state.dtype == final_state.dtype, "selective_scan_carry: initial_state and final_state must share one dtype")
+        _check(initial_state.data_ptr() != final_state.data_ptr() or initial_state.stride() == final_state.stride(),
+               "selective_scan_carry: an in-place update needs final_state to be initial_state (same strides)")
+    flags = _check_ssm_general(u, delta, A, B, C, D, z, delta_bias)
+    _gpu(initial_state, final_state)
+    _check(u.numel() > 0, "selective_scan_carry: u must not be empty")
+    out = torch.empty_like(delta) if z is None else None       # with z only the gated output is stored
+    out_z = torch.empty_like(z) if z is not None else None
+    P = _lib.SsmCarryParams()
+    _fill_ssm_general(P.scan, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, None, out_z, flags)
+    state = initial_state if initial_state is not None else final_state
+    if state is not None:
+        P.state_dtype = _lib.F32 if state.dtype in (torch.float32, torch.complex64) else _DT[state.dtype]
+    if initial_state is not None:
+        P.h0_batch_stride, P.h0_d_stride, P.h0_dstate_stride = initial_state.stride()
+    if final_state is not None:
+        P.hT_batch_stride, P.hT_d_stride, P.hT_dstate_stride = final_state.stride()
+    P.h0_ptr, P.hT_ptr = _ptr(initial_state), _ptr(final_state)
+    with torch.cuda.device(u.device):
+        _lib.check(_lib.load().dimsum_ssm_scan_carry_fwd(P, _stream(u)), "selective_scan_carry_fwd")
+    return out_z if z is not None else out
 
 
 def selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, dB=None, dC=None):

@@ -40,6 +40,34 @@ def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None):
     return native.causal_conv1d_update(x, conv_state, weight, bias, activation in ("silu", "swish"))
 
 
+def causal_conv1d_chunk(x, conv_state, weight, bias=None, activation=None):
+    """any number of tokens of the causal conv1d on a carried state, on the HIP kernel (csrc/causal_conv1d.hip): causal_conv1d_update for a
+    block of tokens. x: (batch, dim, seqlen) with stride(-1) == 1, conv_state: (batch, dim, width) -- the conv sees its last width - 1 columns
+    to the left of x, and it becomes the last `width` values of concat(conv_state, x), IN PLACE --, weight: (dim, width), bias: (dim,)
+    -> out (batch, dim, seqlen). Inference only."""
+    if activation not in (None, "silu", "swish"):
+        raise NotImplementedError("activation must be None, silu, or swish")
+    return native.causal_conv1d_chunk(x, conv_state, weight, bias, activation in ("silu", "swish"))
+
+
+def causal_conv1d_chunk_torch(x, conv_state, weight, bias=None, activation=None):
+    """causal_conv1d_chunk written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer): with
+    v = concat(conv_state[.., 1:], x) along the sequence, out[.., t] = act(bias + sum_k weight[:, k] v[.., t + k]); conv_state receives the
+    last `width` values of concat(conv_state, x). What the tests compare the kernel with; never a fallback: nothing in the package calls it."""
+    silu = {None: False, "silu": True, "swish": True}.get(activation)
+    if silu is None:
+        raise NotImplementedError(f"causal_conv1d_chunk_torch: activation {activation!r} (None, 'silu' or 'swish')")
+    width, seqlen = weight.shape[-1], x.shape[-1]
+    assert conv_state.shape == (*x.shape[:2], width) and weight.shape == (x.shape[1], width)
+    both = torch.cat([conv_state, x], dim=-1)                                           # (batch, dim, width + seqlen)
+    windows = both[..., 1:].unfold(-1, width, 1)                                        # (batch, dim, seqlen, width)
+    pre = (windows * weight[None, :, None, :]).sum(-1)
+    if bias is not None:
+        pre = pre + bias[None, :, None]
+    conv_state.copy_(both[..., -width:])
+    return (pre * torch.sigmoid(pre) if silu else pre).to(x.dtype)
+
+
 def causal_conv1d_update_torch(x, conv_state, weight, bias=None, activation=None):
     """The step of the causal conv1d written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer):
     the window a causal conv of width W sees at the new token is the last W - 1 columns of the state followed by x; the output is the dot

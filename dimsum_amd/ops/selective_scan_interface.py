@@ -20,6 +20,8 @@ selective_scan_fn takes everything the reference's does: any dstate in 1..256, c
 real with a last axis of 2 seqlen). What the tuned kernels are not built for -- native.scan_takes_general_path -- runs on the general kernels
 (csrc/ssm_scan_general.hip); every other call takes the path it always took. mamba_inner_fn and its _cond / _no_out_proj forms run any dstate
 in 1..256 the same way, without the fused extras (dt_proj inside the scan, out_z operand images, f16s training).
+selective_scan_fn(..., initial_state=h) starts from a carried (batch, dim, dstate) state instead of zeros (inference only, no graph): the general
+kernel's carried-state entry point for every dstate; without it the routing is what it was.
 Not implemented (raise): complex A and constant B / C inside mamba_inner_fn* and bimamba_inner_fn; a dstate outside {4, 8, 16, 32} inside
 bimamba_inner_fn.
 """
@@ -83,8 +85,28 @@ class SelectiveScanFn(torch.autograd.Function):
         return (du, ddelta, dA, dB, dC, dD if ctx.has_D else None, dz, ddelta_bias if ctx.has_bias else None, None, None, None)
 
 
-def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False):
-    """out (or (out, last_state)); the gradient of last_state is not propagated (as in the reference)."""
+def _selective_scan_carry(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, initial_state):
+    """selective_scan_fn(initial_state=...): the general kernel for every dstate (csrc/ssm_scan_general.hip, dimsum_ssm_scan_carry_fwd), no graph"""
+    if _will_backprop(u, delta, A, B, C, D, z, delta_bias, initial_state):
+        raise NotImplementedError("selective_scan_fn: a carried state (initial_state) is an inference argument -- the scan that starts from it has "
+                                  "no backward; call it under torch.no_grad() or on inputs that do not require grad")
+    with torch.no_grad():
+        u, delta, B, C, z = (_last_contig(t) for t in (u, delta, B, C, z))
+        B = B.unsqueeze(1) if B.dim() == 3 else B
+        C = C.unsqueeze(1) if C.dim() == 3 else C
+        last = torch.empty_like(initial_state) if return_last_state else None
+        out = native.selective_scan_carry_fwd(u, delta, A, B, C, D.contiguous() if D is not None else None, z, delta_bias, delta_softplus,
+                                              initial_state, last)
+    return out if not return_last_state else (out, last)
+
+
+def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False, initial_state=None):
+    """out (or (out, last_state)); the gradient of last_state is not propagated (as in the reference).
+    initial_state (batch, dim, dstate), float32 or of u's dtype (complex64 with complex A): the scan starts from it instead of from zeros --
+    a cached sequence continued by seqlen tokens; last_state then comes back in its dtype. An inference argument: no graph is recorded, and
+    inputs that require grad under grad mode are refused. Such a call runs on the general kernel whatever the dstate."""
+    if initial_state is not None:
+        return _selective_scan_carry(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, initial_state)
     return SelectiveScanFn.apply(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state,
                                  _will_backprop(u, delta, A, B, C, D, z, delta_bias))
 

@@ -1,5 +1,6 @@
 """selective_state_update -- same API as mamba/mamba_ssm/ops/triton/selective_state_update.py:115-190 (Triton there), on the HIP kernel
-of csrc/mixer_step.hip: one token of the selective scan on a carried state."""
+of csrc/mixer_step.hip: one token of the selective scan on a carried state. Next to its plain-torch restatement, the restatement of the
+scan entered with a carried state for any number of tokens (selective_scan_fn(initial_state=...), csrc/ssm_scan_general.hip)."""
 import torch
 
 from .. import native
@@ -35,3 +36,48 @@ def selective_state_update_torch(state, x, dt, A, B, C, D=None, z=None, dt_bias=
         y = y * zw * torch.sigmoid(zw)
     state.copy_(h)
     return y.to(x.dtype)
+
+
+def selective_scan_carry_torch(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, initial_state=None):
+    """The selective scan entered with a carried state, written out in plain torch, in the precision of its inputs (float64 / complex128
+    inputs give that answer), per batch row b, channel d, state n and step t:
+        dt[b, d, t]  = delta (+ delta_bias), through softplus if asked (torch's threshold of 20)
+        h[b, d, n]  <- h[b, d, n] exp(dt A[d, n]) + dt u[b, d, t] B[.., n, t],   h before the first step = initial_state (zeros if None)
+        y[b, d, t]   = sum_n h[b, d, n] C[.., n, t]   (complex A: twice its real part)   (+ D[d] u[b, d, t]), times z sigmoid(z) if z is given
+    B / C: input-dependent (batch, dstate, seqlen) or (batch, groups, dstate, seqlen) -- with complex A a real last axis of 2 seqlen, (re, im)
+    interleaved, or complex -- or constant (dim, dstate). -> (out (batch, dim, seqlen) of u's dtype, the state after the last step (batch, dim,
+    dstate)); initial_state is left as it is. What the tests compare the kernel with; never a fallback: nothing in the package calls it."""
+    batch, dim, L = u.shape
+    cplx = A.is_complex()
+    work = torch.promote_types(u.dtype, A.real.dtype if cplx else A.dtype)
+    cwork = torch.promote_types(work, A.dtype)
+    dt = delta.to(work) if delta_bias is None else delta.to(work) + delta_bias.to(work)[None, :, None]
+    if delta_softplus:
+        dt = torch.where(dt > 20, dt, torch.log1p(torch.exp(dt.clamp(max=20))))
+    uw = u.to(work)
+
+    def per_channel(M):      # -> (batch or 1, dim, dstate, seqlen or 1)
+        if M.dim() == 2:
+            return M.to(cwork)[None, :, :, None]
+        if M.dim() == 3:
+            M = M.unsqueeze(1)
+        if cplx and not M.is_complex():
+            M = torch.view_as_complex(M.to(work).reshape(*M.shape[:-1], L, 2).contiguous())
+        return M.to(cwork).repeat_interleave(dim // M.shape[1], dim=1)
+
+    Bf, Cf = per_channel(B), per_channel(C)
+    Aw = A.to(cwork)
+    h = torch.zeros(batch, dim, A.shape[1], dtype=cwork, device=u.device) if initial_state is None else initial_state.to(cwork).clone()
+    ys = []
+    for t in range(L):
+        step = dt[:, :, t, None]
+        h = h * torch.exp(step * Aw[None]) + (step * uw[:, :, t, None]) * Bf[..., t if Bf.shape[-1] > 1 else 0]
+        y = (h * Cf[..., t if Cf.shape[-1] > 1 else 0]).sum(-1)
+        ys.append(2 * y.real if cplx else y)
+    out = torch.stack(ys, dim=-1)
+    if D is not None:
+        out = out + D.to(work)[None, :, None] * uw
+    if z is not None:
+        zw = z.to(work)
+        out = out * zw * torch.sigmoid(zw)
+    return out.to(u.dtype), h

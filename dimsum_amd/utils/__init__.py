@@ -19,6 +19,22 @@ class InferenceParams:
 
 
 @torch.no_grad()
+def chunked_prefill(mixer, hidden_states, inference_params, chunk, *cond):
+    """a prompt (B, L, d_model) through a Mamba / CondMamba in pieces of `chunk` tokens, in memory bounded by the piece: the first piece goes
+    through forward(inference_params=...) at offset 0 (the fused prompt path, which fills the cache), the rest through `extend` on the cached
+    states. *cond: what the mixer's forward takes after hidden_states (CondMamba's cond_emb). Advances inference_params.seqlen_offset by L
+    -> the concatenated output (B, L, d_model)."""
+    assert chunk >= 1 and inference_params.seqlen_offset == 0, "chunked_prefill starts a sequence: seqlen_offset must be 0"
+    L = hidden_states.shape[1]
+    outs = [mixer(hidden_states[:, :chunk], *cond, inference_params=inference_params)]
+    states = inference_params.key_value_memory_dict[mixer.layer_idx]
+    for t in range(chunk, L, chunk):
+        outs.append(mixer.extend(hidden_states[:, t:t + chunk], *states)[0])
+    inference_params.seqlen_offset += L
+    return torch.cat(outs, dim=1)
+
+
+@torch.no_grad()
 def rerandomize_zeros(model, std=0.02, seed=0):
     """The reference initialisation is adaLN-zero + zero final layer, so a freshly initialised DiM outputs exactly 0
     (dimsum/models_dim.py:1762-1770; SURVEY finding 5). Benchmarks with random-init weights re-draw every all-zero

@@ -16,6 +16,7 @@
  *   dimsum_causal_conv1d_cl_fwd / _cl_bwd <- the same two entries on channel-last operands   causal-conv1d/csrc/causal_conv1d.cpp:242-247, 376-379
  *   dimsum_causal_conv1d_update <- causal_conv1d_cuda.causal_conv1d_update        causal-conv1d/csrc/causal_conv1d.cpp:512-569
  *   dimsum_selective_state_update <- selective_state_update (Triton)              mamba/mamba_ssm/ops/triton/selective_state_update.py:115-190
+ *   dimsum_causal_conv1d_chunk / dimsum_ssm_scan_carry_fwd <- no counterpart: the conv and the scan entered with a cache's states, any number of tokens
  *   dimsum_norm_fwd / _bwd     <- _layer_norm_fwd / _layer_norm_bwd (Triton)     mamba/mamba_ssm/ops/triton/layernorm.py:120-364
  *   dimsum_token_transform     <- einops/flip/local_scan/DWT/DCT chains          dimsum/models_dim.py:572-604,656-705,876-928,1496-1524
  *   dimsum_xattn_fusion_fwd/_bwd <- F.scaled_dot_product_attention x2 (+ autograd)  dimsum/attention_fusion.py:44-75
@@ -306,6 +307,34 @@ int dimsum_ssm_scan_general_fwd(const dimsum_ssm_general_params_t *p, void *stre
 int dimsum_ssm_scan_general_bwd(const dimsum_ssm_general_bwd_params_t *p, void *stream);
 /* the backward's workspace; -1 on an invalid shape */
 int64_t dimsum_ssm_scan_general_bwd_workspace_bytes(int32_t batch, int32_t dim, int32_t seqlen, int32_t dstate, int32_t n_groups, int32_t is_complex);
+
+/* The general forward on a CARRIED state (inference only, no backward): the scan enters with h0 instead of zeros and leaves the state after
+ * the last step in hT -- a cached sequence continued by any number of tokens (no reference counterpart: selective_scan_cuda.fwd hands a
+ * state out through x and takes none in). `scan` is read exactly as dimsum_ssm_scan_general_fwd reads it (scan.struct_size is ignored); with
+ * h0_ptr == hT_ptr == NULL the launch IS that entry point's, bit for bit.
+ *   h0, hT : (batch, dim, dstate), each with its own three ELEMENT strides (a slice of a larger cache is a view). `state_dtype` is
+ *       DIMSUM_F32 or == scan.dtype -- the rule of dimsum_selective_state_update; with scan.is_complex the state is complex64 (a float pair
+ *       per element, strides in complex elements) and state_dtype must be DIMSUM_F32. h0_ptr NULL = start from zero; hT_ptr NULL = not wanted.
+ *   In place: hT_ptr may EQUAL h0_ptr with equal strides (a cache updated in place). The lane that owns (channel, state) reads its h0
+ *       element before it walks the sequence and writes its hT element after it, and no other lane touches that element. Any other overlap
+ *       of the two is undefined.
+ *   Arithmetic is fp32 throughout: a 16-bit state is widened on load and rounded once, on the store.
+ *   x keeps its meaning: [2n] = the running product of exp(delta A_n) counted from THIS call's first step, [2n + 1] = the state h_n, which
+ *       includes what h0 carried in.
+ * Checks, in the order of the general entry points: NULL struct / struct_size (DIMSUM_ERR_ABI) / required pointers / shape / dtype (scan.dtype,
+ * then state_dtype where a state pointer is set: DIMSUM_ERR_DTYPE) / negative strides, the state's included, or a misaligned x
+ * (DIMSUM_ERR_STRIDE). Nothing is launched before all of them pass. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_ssm_carry_params_t) */
+    int32_t state_dtype;      /* dimsum_dtype_t of h0 / hT */
+    dimsum_ssm_general_params_t scan;
+    int64_t h0_batch_stride, h0_d_stride, h0_dstate_stride;
+    int64_t hT_batch_stride, hT_d_stride, hT_dstate_stride;
+    const void *h0_ptr;       /* NULL = zero */
+    void *hT_ptr;             /* NULL = not wanted; may equal h0_ptr */
+} dimsum_ssm_carry_params_t;
+
+int dimsum_ssm_scan_carry_fwd(const dimsum_ssm_carry_params_t *p, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Training-step tail: global gradient-norm clip + AdamW + parameter EMA over a list of fp32 tensors, two launches
@@ -628,6 +657,34 @@ typedef struct {
 } dimsum_conv_update_params_t;
 
 int dimsum_causal_conv1d_update(const dimsum_conv_update_params_t *p, void *stream);
+
+/* dimsum_causal_conv1d_chunk: dimsum_causal_conv1d_update for any number of tokens per call (no reference counterpart: its update takes one
+ * token, its sequence kernel starts from zeros). With v = concat(conv_state[b, d, 1:], x[b, d, :]):
+ *     out[b, d, t] = act(bias[d] + sum_k weight[d, k] v[t + k]);   conv_state[b, d, :] <- the last `width` values of concat(conv_state, x)
+ *   x, out (batch, dim, seqlen) of `dtype` with innermost stride 1 and free batch / channel strides (the d-major half of an in_proj output is
+ *   a view); out must not overlap x. conv_state (batch, dim, width) of `dtype`, three free ELEMENT strides, updated IN PLACE: its values are
+ *   moved, never converted (seqlen < width keeps the newest width - seqlen old ones in front of x; seqlen == 1 leaves exactly what
+ *   dimsum_causal_conv1d_update leaves). weight (dim, width), bias (dim): f32; bias_ptr may be NULL.
+ *   One wave owns whole (batch, channel) rows, as in the sequence kernel (csrc/causal_conv1d.hip): lane k < width reads conv_state[k] before
+ *   the row is walked and the same lane writes it afterwards, so the in-place update cannot race. 16-byte accesses where seqlen, the strides
+ *   and the bases of x and out allow, element accesses otherwise.
+ * Checks in order: NULL struct, struct_size (DIMSUM_ERR_ABI), required pointers, width 2..4 / batch, dim, seqlen >= 1 (DIMSUM_ERR_SHAPE), dtype,
+ * negative strides (DIMSUM_ERR_STRIDE). */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_conv_chunk_params_t) */
+    int32_t batch, dim, seqlen, width;
+    int32_t silu_activation;  /* bool */
+    int32_t dtype;            /* of x / conv_state / out */
+    int32_t reserved;         /* 0 */
+    int64_t x_batch_stride, x_c_stride;
+    int64_t state_batch_stride, state_c_stride, state_w_stride;
+    int64_t weight_c_stride, weight_width_stride;
+    int64_t out_batch_stride, out_c_stride;
+    const void *x_ptr, *weight_ptr, *bias_ptr;   /* bias_ptr may be NULL */
+    void *conv_state_ptr, *out_ptr;
+} dimsum_conv_chunk_params_t;
+
+int dimsum_causal_conv1d_chunk(const dimsum_conv_chunk_params_t *p, void *stream);
 
 /* dimsum_selective_state_update  <- selective_state_update (Triton, no ROCm path)   mamba/mamba_ssm/ops/triton/selective_state_update.py:115-190
  *   (semantics of selective_state_update_ref, :193-228), f32 arithmetic throughout:
