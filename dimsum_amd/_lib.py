@@ -231,6 +231,21 @@ class StateUpdateParams(_Sized):
                 + [("ext", C.POINTER(StateUpdateExt))])
 
 
+class DecodeLinearParams(_Sized):
+    """dimsum_decode_linear_params_t: the weight-streaming linear layer of a decode step, with the add + norm prologue and the conv-update epilogue"""
+    _fields_ = ([("struct_size", u32)]
+                + [(n, i32) for n in ("batch", "n", "k", "dtype", "residual_dtype", "norm", "conv_dim", "conv_width", "silu_activation")]
+                + [("eps", f32), ("reserved", i32)]
+                + [(n, i64) for n in ("x_row_stride", "w_row_stride", "y_row_stride", "residual_row_stride", "residual_out_row_stride",
+                                      "state_batch_stride", "state_c_stride", "state_w_stride", "conv_weight_c_stride", "conv_weight_width_stride")]
+                + [(n, vp) for n in ("x_ptr", "w_ptr", "bias_ptr", "residual_ptr", "norm_weight_ptr", "norm_bias_ptr", "conv_weight_ptr", "conv_bias_ptr",
+                                     "y_ptr", "residual_out_ptr", "conv_state_ptr")])
+
+
+DECODE_NORM_NONE, DECODE_NORM_LAYER, DECODE_NORM_RMS = 0, 1, 2
+DECODE_MAX_BATCH = 16
+
+
 class NormParams(_Sized):
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("rows", "cols", "is_rms_norm", "x_dtype", "residual_dtype", "out_dtype")]
                 + [("eps", f32)]
@@ -388,6 +403,7 @@ EXPORTS = (
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
     "dimsum_einfft_dft", "dimsum_einfft_idft_real", "dimsum_einfft_mlp_fwd", "dimsum_einfft_mlp_bwd",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd", "dimsum_causal_conv1d_update", "dimsum_selective_state_update",
+    "dimsum_decode_linear",
     "dimsum_causal_conv1d_cl_fwd", "dimsum_causal_conv1d_cl_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
@@ -421,7 +437,8 @@ _SIGNATURES = (
         ("dimsum_moe_gemm_dgrad", MoeGemmDgradParams), ("dimsum_moe_gemm_wgrad", MoeGemmWgradParams),
         ("dimsum_moe_gemm_f16s", MoeGemmF16sParams), ("dimsum_moe_permute_f16s", MoePermuteF16sParams), ("dimsum_moe_act_fwd_f16s", MoeActF16sParams),
         ("dimsum_causal_conv1d_cl_fwd", ConvClParams), ("dimsum_causal_conv1d_cl_bwd", ConvClBwdParams),
-        ("dimsum_ssm_scan_carry_fwd", SsmCarryParams), ("dimsum_causal_conv1d_chunk", ConvChunkParams))]
+        ("dimsum_ssm_scan_carry_fwd", SsmCarryParams), ("dimsum_causal_conv1d_chunk", ConvChunkParams),
+        ("dimsum_decode_linear", DecodeLinearParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

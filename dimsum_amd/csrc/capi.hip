@@ -11,6 +11,7 @@ extern "C" const char *dimsum_status_string(int status) {
         case DIMSUM_ERR_UNSUPPORTED: return "valid in the reference but out of scope here (complex A, constant B/C)";
         case DIMSUM_ERR_LAUNCH: return "HIP kernel launch failed";
         case DIMSUM_ERR_ABI: return "struct_size of a parameter struct (or of its extension) does not match this library: the caller was built against another include/dimsum_hip.h";
+        case DIMSUM_ERR_ALIAS: return "an output overlaps an input that the kernel's other workgroups still read";
         default: return "unknown status";
     }
 }

@@ -12,6 +12,8 @@ token-by-token order) and the operand-image input `x3` (inference images and a c
 more than one token per call through `extend` (a causal conv and a scan that enter with the cache's states and leave the new ones behind;
 `dimsum_amd.utils.chunked_prefill` walks a long prompt with it); `step` and `forward` at `seqlen_offset > 0` keep taking one token. The
 recurrent form is for inference: the cache is filled without autograd edges and the step and extend kernels have no backward.
+`Block` (mamba_simple.py:383-436) wraps a mixer with its add + norm; for one token of a cached sequence it runs the mixer's `step_fused`: the
+same step on the weight-streaming kernel of csrc/decode_step.hip, four launches per layer.
 
 Differences that do not change results:
   * `cond_proj(c)` is numerically dead in the reference (its output only donates a buffer to the conv kernel,
@@ -22,6 +24,7 @@ Differences that do not change results:
   * the zigzag gather / inverse gather (mamba_simple.py:627-657) are index_selects on the token axis.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -29,10 +32,21 @@ import torch.nn.functional as F
 
 from .. import gemm, native
 from ..ops.causal_conv1d_interface import causal_conv1d_update
+from ..ops.layernorm import RMSNorm, layer_norm_fn
 from ..ops.selective_scan_interface import (mamba_inner_fn_cond, mamba_inner_fn_no_out_proj_cond)
 from ..ops.selective_state_update import selective_state_update
 
 _ZIGZAG = ("zigma", "sweep", "jpeg")
+
+
+def fused_decode_enabled(batch, dtype):
+    """DIMSUM_FUSED_DECODE, read at call time: 0 sends every decode step through the unfused `step`, 1 takes the fused step wherever it serves
+    (tests and tools/bench_decode.py run both); unset: where it measured faster than the unfused step eager AND replayed from a graph
+    (DESIGN.md section 3.16): float32 at batch <= 4"""
+    v = os.environ.get("DIMSUM_FUSED_DECODE", "")
+    if v in ("0", "1"):
+        return v == "1"
+    return dtype == torch.float32 and batch <= 4
 
 
 class _MambaBase(nn.Module):
@@ -211,6 +225,40 @@ class _MambaBase(nn.Module):
         out = F.linear(y, self.out_proj.weight, self.out_proj.bias)
         return out.unsqueeze(1), conv_state, ssm_state
 
+    def fused_step_serves(self, hidden, norm, conv_state, ssm_state):
+        """whether `step_fused` takes this token: hidden (B <= 16, d_model), every parameter of the mixer and of `norm` of hidden's dtype T, a
+        conv state of T and an SSM state the state-update kernel pairs with T (float32 or T), a conv width the epilogue has"""
+        if self.scan_type == "v2" or self._is_zigzag() or not 2 <= self.d_conv <= 4 or self.d_state > 256:
+            return False
+        T = hidden.dtype
+        params = [self.in_proj.weight, self.in_proj.bias, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
+                  self.dt_proj.bias, self.A_log, self.D, self.out_proj.weight, self.out_proj.bias, norm.weight, norm.bias]
+        return (native.decode_linear_serves(hidden, self.in_proj.weight, *params) and conv_state.dtype == T
+                and ssm_state.dtype in (torch.float32, T))
+
+    def step_fused(self, hidden, residual, norm, residual_dtype, conv_state, ssm_state):
+        """one token through "add -> norm -> mixer" as four dependent launches of the library (csrc/decode_step.hip, csrc/mixer_step.hip) plus
+        neg_exp: hidden (B, d_model), the previous layer's mixer output (or the embedding); residual (B, d_model) or None; norm: the block's
+        LayerNorm / RMSNorm module; residual_dtype: of the residual stream this call returns (the incoming one's when there is one)
+        -> (out (B, d_model) WITHOUT the residual add: it lives in the next caller's prologue, residual_out (B, d_model)).
+          1. in_proj with the add + norm prologue and the conv-update epilogue  2. x_proj  3. the state update, dt_proj inside it where the
+          kernel takes it (float32; a 16-bit dt_proj is one more decode_linear)  4. out_proj with its bias"""
+        D, R, N = self.d_inner, self.dt_rank, self.d_state
+        cw = self.conv1d.weight
+        xz, residual_out = native.decode_linear(hidden, self.in_proj.weight, self.in_proj.bias,
+                                                norm=(norm.weight, norm.bias, norm.eps, isinstance(norm, RMSNorm)), residual=residual,
+                                                residual_out=residual_dtype,
+                                                conv=(conv_state, cw.reshape(cw.shape[0], cw.shape[-1]), self.conv1d.bias, True))
+        x, z = xz[:, :D], xz[:, D:]                                                          # views: the kernels take the strides
+        x_db = native.decode_linear(x, self.x_proj.weight)
+        dt, B, C = x_db[:, :R], x_db[:, R:R + N], x_db[:, R + N:]
+        A = gemm.neg_exp(self.A_log)
+        if hidden.dtype == torch.float32:
+            y = native.selective_state_update(ssm_state, x, None, A, B, C, self.D, z, self.dt_proj.bias, True, dt_proj=(self.dt_proj.weight, dt))
+        else:
+            y = native.selective_state_update(ssm_state, x, native.decode_linear(dt, self.dt_proj.weight), A, B, C, self.D, z, self.dt_proj.bias, True)
+        return native.decode_linear(y, self.out_proj.weight, self.out_proj.bias), residual_out
+
     @torch.no_grad()
     def extend(self, hidden_states, conv_state, ssm_state):
         """any number of tokens on carried states, the sibling of `step`: hidden_states (B, T, d_model), T >= 1 -> (out (B, T, d_model),
@@ -270,3 +318,51 @@ class CondMamba(_MambaBase):
         if inference_params is not None:
             return self._forward_cached(hidden_states, cond, inference_params, x3)
         return self._mix(hidden_states, cond, x3=x3)
+
+
+class Block(nn.Module):
+    """Add -> LayerNorm / RMSNorm -> mixer, returning (hidden_states, residual): the block of mamba_simple.py:383-436, same constructor,
+    forward contract and state-dict keys (`mixer.*`, `norm.*`). One token of a cached sequence (seqlen 1 at seqlen_offset > 0) goes through
+    the mixer's `step_fused` when `fused_add_norm` is set, `fused_decode_enabled` (DIMSUM_FUSED_DECODE) and `fused_step_serves` say so: the add + norm is then
+    the prologue of in_proj's launch. Everything else -- prompts, training, larger batches, mixed parameter dtypes -- runs the fused add + norm
+    kernel (or, without fused_add_norm, the modules) and the mixer's forward, with the same results."""
+
+    def __init__(self, dim, mixer_cls, norm_cls=nn.LayerNorm, fused_add_norm=False, residual_in_fp32=False):
+        super().__init__()
+        self.residual_in_fp32 = residual_in_fp32
+        self.fused_add_norm = fused_add_norm
+        self.mixer = mixer_cls(dim)
+        self.norm = norm_cls(dim)
+        if self.fused_add_norm:
+            assert isinstance(self.norm, (nn.LayerNorm, RMSNorm)), "Only LayerNorm and RMSNorm are supported for fused_add_norm"
+
+    def _fused_decode_states(self, hidden_states, residual, inference_params):
+        """the layer's (conv_state, ssm_state) when this call is one token that the fused decode step serves, else None"""
+        if not (self.fused_add_norm and inference_params is not None and inference_params.seqlen_offset > 0 and hidden_states.dim() == 3
+                and hidden_states.shape[1] == 1 and hasattr(self.mixer, "step_fused") and fused_decode_enabled(hidden_states.shape[0], hidden_states.dtype)
+                and not torch.is_grad_enabled()):
+            return None
+        if residual is not None and residual.dtype not in (torch.float32, hidden_states.dtype):
+            return None
+        states = self.mixer._get_states_from_cache(inference_params, hidden_states.shape[0])
+        return states if self.mixer.fused_step_serves(hidden_states[:, 0], self.norm, *states) else None
+
+    def forward(self, hidden_states, residual=None, inference_params=None):
+        states = self._fused_decode_states(hidden_states, residual, inference_params)
+        if states is not None:
+            res_dtype = residual.dtype if residual is not None else (torch.float32 if self.residual_in_fp32 else hidden_states.dtype)
+            out, residual = self.mixer.step_fused(hidden_states[:, 0], None if residual is None else residual[:, 0], self.norm, res_dtype, *states)
+            return out.unsqueeze(1), residual.unsqueeze(1)
+        if not self.fused_add_norm:
+            residual = (hidden_states + residual) if residual is not None else hidden_states
+            hidden_states = self.norm(residual.to(dtype=self.norm.weight.dtype))
+            if self.residual_in_fp32:
+                residual = residual.to(torch.float32)
+        else:
+            hidden_states, residual = layer_norm_fn(hidden_states, self.norm.weight, self.norm.bias, residual=residual, eps=self.norm.eps, prenorm=True,
+                                                    residual_in_fp32=self.residual_in_fp32, is_rms_norm=isinstance(self.norm, RMSNorm))
+        hidden_states = self.mixer(hidden_states, inference_params=inference_params)
+        return hidden_states, residual
+
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+        return self.mixer.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, **kwargs)

@@ -503,6 +503,76 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
     return out
 
 
+def decode_linear_serves(x, weight, *others):
+    """whether dimsum_decode_linear takes this call: (batch <= 16, K) rows of one 16/32-bit float dtype shared by every other operand"""
+    return (x.dim() == 2 and 1 <= x.shape[0] <= _lib.DECODE_MAX_BATCH and x.dtype in _DT and weight.dtype == x.dtype
+            and all(t is None or t.dtype == x.dtype for t in others))
+
+
+def decode_linear(x, weight, bias=None, norm=None, residual=None, residual_out=None, conv=None):
+    """-> y (batch, N), or (y, residual_out) when `residual_out` is asked for: y = x' @ weight^T (+ bias) on csrc/decode_step.hip, batch <= 16;
+    x (batch, K), weight (N, K), bias (N) share one dtype T.
+    norm = (norm_weight (K), norm_bias (K) or None, eps, is_rms_norm): x' = norm(x (+ residual)) * norm_weight (+ norm_bias) in the same launch;
+    residual (batch, K) is float32 or T. residual_out: None, or the dtype (float32 or T, == residual's when one is given) in which
+    x (+ residual) is also returned -- a fresh buffer, never a view of x or residual. Without `norm`, x' = x.
+    conv = (conv_state (batch, D, W) of T, conv_weight (D, W), conv_bias (D) or None, silu): the outputs n < D go through one in-place
+    step of the causal conv1d (causal_conv1d_update) before they are stored; y[:, :D] is the conv output, y[:, D:] the plain outputs."""
+    _check(x.dim() == 2 and x.dtype in _DT and x.stride(1) == 1, "decode_linear: x must be (batch, K) with unit row stride in float32, float16 or bfloat16")
+    batch, K = x.shape
+    _check(1 <= batch <= _lib.DECODE_MAX_BATCH, f"decode_linear: batch must be 1..{_lib.DECODE_MAX_BATCH}")
+    _check(weight.dim() == 2 and weight.shape[1] == K and weight.dtype == x.dtype and weight.stride(1) == 1 and K >= 1 and weight.shape[0] >= 1,
+           "decode_linear: weight must be (N, K) of x's dtype with unit row stride")
+    N = weight.shape[0]
+    if bias is not None:
+        _check(tuple(bias.shape) == (N,) and bias.dtype == x.dtype, "decode_linear: bias must be (N,) of x's dtype")
+        bias = bias.contiguous()
+    _check(norm is not None or (residual is None and residual_out is None), "decode_linear: residual / residual_out belong to the norm prologue")
+    P = _lib.DecodeLinearParams()
+    P.batch, P.n, P.k, P.dtype, P.residual_dtype = batch, N, K, _DT[x.dtype], _DT[x.dtype]
+    keep = []
+    res_out = None
+    if norm is not None:
+        nw, nb, eps, is_rms = norm
+        _check(tuple(nw.shape) == (K,) and nw.dtype == x.dtype and (nb is None or (tuple(nb.shape) == (K,) and nb.dtype == x.dtype)),
+               "decode_linear: norm weight / bias must be (K,) of x's dtype")
+        nw, nb = nw.contiguous(), None if nb is None else nb.contiguous()
+        keep += [nw, nb]
+        P.norm, P.eps = (_lib.DECODE_NORM_RMS if is_rms else _lib.DECODE_NORM_LAYER), float(eps)
+        P.norm_weight_ptr, P.norm_bias_ptr = _ptr(nw), _ptr(nb)
+        res_dtype = residual.dtype if residual is not None else residual_out
+        if res_dtype is not None:
+            _check(res_dtype in (torch.float32, x.dtype), "decode_linear: the residual stream must be float32 or of x's dtype")
+            P.residual_dtype = _DT[res_dtype]
+        if residual is not None:
+            _check(residual.shape == x.shape and residual.stride(1) == 1, "decode_linear: residual must be (batch, K) with unit row stride")
+            _check(residual_out in (None, residual.dtype), "decode_linear: residual_out must have the residual's dtype")
+            P.residual_ptr, P.residual_row_stride = _ptr(residual), residual.stride(0)
+        if residual_out is not None:
+            res_out = torch.empty((batch, K), device=x.device, dtype=res_dtype)
+            P.residual_out_ptr, P.residual_out_row_stride = _ptr(res_out), res_out.stride(0)
+    y = torch.empty((batch, N), device=x.device, dtype=x.dtype)
+    if conv is not None:
+        state, cw, cb, silu = conv
+        _check(cw.dim() == 2 and 1 <= cw.shape[0] <= N and cw.dtype == x.dtype, "decode_linear: conv weight must be (D <= N, width) of x's dtype")
+        D, W = cw.shape
+        _check(2 <= W <= 4, "decode_linear: the conv epilogue only supports width between 2 and 4")
+        _check(tuple(state.shape) == (batch, D, W) and state.dtype == x.dtype, "decode_linear: conv_state must be (batch, D, width) of x's dtype")
+        if cb is not None:
+            _check(tuple(cb.shape) == (D,) and cb.dtype == x.dtype, "decode_linear: conv bias must be (D,) of x's dtype")
+            cb = cb.contiguous()
+            keep.append(cb)
+        P.conv_dim, P.conv_width, P.silu_activation = D, W, int(bool(silu))
+        P.state_batch_stride, P.state_c_stride, P.state_w_stride = state.stride()
+        P.conv_weight_c_stride, P.conv_weight_width_stride = cw.stride()
+        P.conv_weight_ptr, P.conv_bias_ptr, P.conv_state_ptr = _ptr(cw), _ptr(cb), _ptr(state)
+    _gpu(x, weight, bias, residual, *(norm[:2] if norm is not None else ()), *(conv[:3] if conv is not None else ()))     # the device last
+    P.x_row_stride, P.w_row_stride, P.y_row_stride = x.stride(0), weight.stride(0), y.stride(0)
+    P.x_ptr, P.w_ptr, P.bias_ptr, P.y_ptr = _ptr(x), _ptr(weight), _ptr(bias), _ptr(y)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dimsum_decode_linear(P, _stream(x)), "decode_linear")
+    return y if residual_out is None else (y, res_out)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # fused add + RMSNorm / LayerNorm   (Triton _layer_norm_fwd / _layer_norm_bwd, ops/triton/layernorm.py:120-364)
 # ---------------------------------------------------------------------------------------------------------------------

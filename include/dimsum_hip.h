@@ -65,7 +65,8 @@ typedef enum {
     DIMSUM_ERR_STRIDE = 4,        /* stride not supported (innermost != 1, overflow) */
     DIMSUM_ERR_UNSUPPORTED = 5,   /* valid in the reference but not served by THIS entry point (the tuned scan: complex A, constant B/C -> dimsum_ssm_scan_general_*; fusions a kernel does not offer) */
     DIMSUM_ERR_LAUNCH = 6,        /* hipGetLastError() after the launch */
-    DIMSUM_ERR_ABI = 7            /* struct_size of a parameter struct does not match this library (stale / foreign header) */
+    DIMSUM_ERR_ABI = 7,           /* struct_size of a parameter struct does not match this library (stale / foreign header) */
+    DIMSUM_ERR_ALIAS = 8          /* an output overlaps an input that other workgroups still read (dimsum_decode_linear: residual_out) */
 } dimsum_status_t;
 
 typedef enum { DIMSUM_F32 = 0, DIMSUM_F16 = 1, DIMSUM_BF16 = 2 } dimsum_dtype_t;
@@ -721,6 +722,46 @@ typedef struct {
 } dimsum_state_update_params_t;
 
 int dimsum_selective_state_update(const dimsum_state_update_params_t *p, void *stream);
+
+/* dimsum_decode_linear: the weight-streaming linear layer of a decode step (no reference counterpart as a kernel: Mamba.step and Block.forward,
+ * mamba_simple.py:299-344, :408-432, run a fused add + norm launch, F.linear GEMVs and causal_conv1d_update as launches of their own).
+ *     y[b, n] = sum_k x'[b, k] W[n, k] (+ bias[n])      batch 1..16 (else DIMSUM_ERR_SHAPE), any n, k >= 1, fp32 accumulation
+ *   x (batch, k), W (n, k), bias (n), y (batch, n): all of `dtype`, unit innermost stride, free row strides. W is read exactly once (16-byte
+ *   streaming loads where its base and row stride allow, element loads otherwise and after the last whole piece of a row). No atomics and no
+ *   split-K across workgroups: two launches from equal inputs are bit-identical.
+ *   Prologue (norm != 0): r = x (+ residual); x' = norm(r) * norm_weight (+ norm_bias), rounded to `dtype` (what the unfused norm hands to
+ *   the GEMV); norm 1 = LayerNorm, 2 = RMSNorm, statistics in fp32 on the unrounded r. residual, residual_out (batch, k): `residual_dtype`,
+ *   DIMSUM_F32 or == dtype; norm_weight, norm_bias (k): `dtype`. residual_out = r is written by ONE workgroup while the others still read x
+ *   and residual: a residual_out that overlaps either is DIMSUM_ERR_ALIAS. Without the prologue x' = x, and residual / residual_out /
+ *   norm_bias must be NULL (DIMSUM_ERR_UNSUPPORTED).
+ *   Epilogue (conv_dim > 0) on the outputs n < conv_dim: one step of dimsum_causal_conv1d_update by the lane that holds y[b, n]:
+ *     conv_state[b, n, :] <- its last conv_width - 1 columns, then y[b, n] rounded to `dtype`;
+ *     y[b, n] <- act(conv_bias[n] + sum_w conv_weight[n, w] conv_state[b, n, w]),  act = SiLU when silu_activation
+ *   conv_state (batch, conv_dim, conv_width), conv_weight (conv_dim, conv_width), conv_bias (conv_dim): `dtype`, free ELEMENT strides; width 2..4.
+ *   y is ONE (batch, n) buffer: with the epilogue its columns [0, conv_dim) hold the conv output and [conv_dim, n) the plain outputs (the
+ *   mixer's x and z halves are views of it).
+ * Checks, in this order: NULL struct / struct_size (DIMSUM_ERR_ABI) / required pointers (x, W, y; norm_weight with norm; conv_weight and
+ * conv_state with conv_dim) / shape (batch, n, k, norm, conv_dim, conv_width) / dtype (dtype, then residual_dtype) / pointers that need the
+ * prologue (DIMSUM_ERR_UNSUPPORTED) / negative strides (DIMSUM_ERR_STRIDE) / residual_out overlapping x, then residual (DIMSUM_ERR_ALIAS).
+ * Nothing is launched before all of them pass. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_decode_linear_params_t) as the caller compiled it; anything else -> DIMSUM_ERR_ABI */
+    int32_t batch, n, k;
+    int32_t dtype;            /* of x, W, bias, y, the norm and conv weights, conv_state */
+    int32_t residual_dtype;   /* of residual / residual_out: DIMSUM_F32 or == dtype */
+    int32_t norm;             /* 0: no prologue, 1: LayerNorm, 2: RMSNorm */
+    int32_t conv_dim;         /* 0: no epilogue */
+    int32_t conv_width;
+    int32_t silu_activation;  /* bool */
+    float eps;
+    int32_t reserved;         /* 0 */
+    int64_t x_row_stride, w_row_stride, y_row_stride, residual_row_stride, residual_out_row_stride;
+    int64_t state_batch_stride, state_c_stride, state_w_stride, conv_weight_c_stride, conv_weight_width_stride;
+    const void *x_ptr, *w_ptr, *bias_ptr, *residual_ptr, *norm_weight_ptr, *norm_bias_ptr, *conv_weight_ptr, *conv_bias_ptr;
+    void *y_ptr, *residual_out_ptr, *conv_state_ptr;
+} dimsum_decode_linear_params_t;
+
+int dimsum_decode_linear(const dimsum_decode_linear_params_t *p, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused residual-add + RMSNorm / LayerNorm over rows (M, N), f32 statistics.

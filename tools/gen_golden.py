@@ -1018,6 +1018,63 @@ def gen_moe(ns):
                    "procedural_fill(module, <tag>.seed); x, dout: stored", **arrs)
 
 
+LM_TINY = dict(d_model=64, n_layer=2, vocab_size=90, pad_vocab_size_multiple=8, ssm_cfg=dict(d_state=16, d_conv=4, expand=2))
+LM_VARIANTS = tuple((f"rms{r}_fp32res{f}", dict(rms_norm=bool(r), residual_in_fp32=bool(f), fused_add_norm=True)) for r in (0, 1) for f in (0, 1))
+LM_B, LM_PROMPT, LM_STEPS = 2, 9, 7
+
+
+def gen_lm(_ns=None):
+    """tests/golden/lm_tiny_<variant>.npz: the reference's MambaLMHeadModel (mixer_seq_simple.py:166-226) on its slow path in fp32 at LM_TINY for
+    rms_norm x residual_in_fp32: the weights (procedural_fill with the first seed whose greedy continuation is decided by a clear margin), the
+    prompt's logits, the logits of LM_STEPS cached greedy steps (Mamba.step, mamba_simple.py:299-344), the generated ids and min_gap, the
+    smallest top-1 minus top-2 logit over the generated steps. tests/golden/lm_keys.json: state-dict keys and shapes."""
+    import json
+    lm = ref_shim.load_lm()
+    for tag, flags in LM_VARIANTS:
+        for seed in range(11, 40):
+            torch.manual_seed(0)
+            m = lm.mss.MambaLMHeadModel(**LM_TINY, **flags).eval()
+            procedural_fill(m, seed=seed)
+            m.tie_weights()
+            ref_shim.slow_path(m)
+            prompt = T(np.random.RandomState(seed).randint(0, LM_TINY["vocab_size"], size=(LM_B, LM_PROMPT)).astype(np.int64))
+            with torch.no_grad():
+                p = lm.gen.InferenceParams(max_seqlen=LM_PROMPT + LM_STEPS, max_batch_size=LM_B)
+                prompt_logits = m(prompt, inference_params=p).logits
+                full_logits = m(prompt).logits
+                assert torch.allclose(prompt_logits, full_logits, rtol=1e-5, atol=1e-6)
+                p.seqlen_offset = LM_PROMPT
+                tok = prompt_logits[:, -1].argmax(-1, keepdim=True)
+                ids, steps = [tok], []
+                gaps = [prompt_logits[:, -1].topk(2).values]
+                for _ in range(LM_STEPS):
+                    logits = m(tok, inference_params=p, num_last_tokens=1).logits[:, 0]
+                    p.seqlen_offset += 1
+                    steps.append(logits)
+                    gaps.append(logits.topk(2).values)
+                    tok = logits.argmax(-1, keepdim=True)
+                    ids.append(tok)
+            steps = torch.stack(steps, 1)                                   # (B, LM_STEPS, vocab)
+            top2 = torch.stack(gaps, 1)                                     # every row an argmax was taken from
+            min_gap = float((top2[..., 0] - top2[..., 1]).min())
+            max_logit = float(torch.maximum(prompt_logits.abs().max(), steps.abs().max()))
+            if min_gap >= 1e-3 * max_logit:
+                break
+        assert min_gap >= 1e-3 * max_logit, (tag, min_gap, max_logit)
+        arrs = {"w." + k: v for k, v in m.state_dict().items()}
+        save(f"lm_tiny_{tag}", f"reference MambaLMHeadModel (mamba/mamba_ssm/models/mixer_seq_simple.py:166-226) slow path, fp32, {LM_TINY}, {flags}, "
+             f"procedural_fill seed {seed}; prompt (B {LM_B}, {LM_PROMPT} tokens) -> prompt_logits; {LM_STEPS} greedy cached steps -> step_logits "
+             "(B, steps, vocab); ids (B, steps + 1): the argmax of the prompt's last row, then of every step; min_gap: the smallest top-1 minus "
+             "top-2 logit over the rows those argmaxes were taken from; w.*: the state dict", prompt=prompt, prompt_logits=prompt_logits,
+             step_logits=steps, ids=torch.cat(ids, 1), min_gap=np.float64(min_gap), max_logit=np.float64(max_logit), seed=np.int64(seed), **arrs)
+    doc = {name: [[k, list(v.shape)] for k, v in lm.mss.MambaLMHeadModel(**LM_TINY, rms_norm=rms, fused_add_norm=True).state_dict().items()]
+           for name, rms in (("layer_norm", False), ("rms_norm", True))}
+    with open(os.path.join(OUT, "lm_keys.json"), "w") as f:
+        json.dump(doc, f, indent=0)
+        f.write("\n")
+    print(f"  lm_keys.json: {len(doc['layer_norm'])} / {len(doc['rms_norm'])} keys")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -1037,7 +1094,7 @@ def main():
         "transport_blur": lambda: gen_transport_blur(ns),
         "block_linear_window": lambda: gen_block_linear_window(ns), "tiny_linear_window": lambda: gen_model_tiny_linear_window(ns),
         "pe": lambda: gen_pe(ns), "einfft": lambda: gen_einfft(ns), "dit_keys": lambda: gen_dit_keys(ns), "step": lambda: gen_step(ns),
-        "scan_general": lambda: gen_scan_general(ns), "moe": lambda: gen_moe(ns),
+        "scan_general": lambda: gen_scan_general(ns), "moe": lambda: gen_moe(ns), "lm": lambda: gen_lm(ns),
     }
     for k, fn in steps.items():
         if args.only is None or k in args.only:

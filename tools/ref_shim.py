@@ -203,6 +203,32 @@ def load_transport():
     return transport
 
 
+def load_lm():
+    """The reference's language model (mamba/mamba_ssm/models/mixer_seq_simple.py: MixerModel, MambaLMHeadModel) on its CPU refs. Its imports
+    reach for `transformers` (generation output classes, hub helpers), absent from this image and irrelevant to a forward: stand-in modules
+    with those names, nothing behind them. fused_add_norm maps to the reference's own rms_norm_ref / layer_norm_ref, as in load(); the step's
+    two operators map to their *_ref functions."""
+    if "lm" in _LOADED:
+        return _LOADED["lm"]
+    ns = load()
+    if "transformers" not in sys.modules:
+        tr, gen, ut, hub = (types.ModuleType(n) for n in ("transformers", "transformers.generation", "transformers.utils", "transformers.utils.hub"))
+        gen.GreedySearchDecoderOnlyOutput = gen.SampleDecoderOnlyOutput = types.SimpleNamespace
+        ut.CONFIG_NAME, ut.WEIGHTS_NAME = "config.json", "pytorch_model.bin"
+        hub.cached_file = None
+        tr.generation, tr.utils, ut.hub = gen, ut, hub
+        sys.modules.update({"transformers": tr, "transformers.generation": gen, "transformers.utils": ut, "transformers.utils.hub": hub})
+    import mamba_ssm.models.mixer_seq_simple as mss
+    import mamba_ssm.utils.generation as rgen
+    from mamba_ssm.ops.triton.selective_state_update import selective_state_update_ref
+    assert os.path.realpath(mss.__file__).startswith(os.path.realpath(REF)), mss.__file__
+    mss.rms_norm_fn, mss.layer_norm_fn, mss.RMSNorm = ns.ln.rms_norm_fn, ns.ln.layer_norm_fn, ns.ln.RMSNorm
+    ns.ms.causal_conv1d_update = ns.cci.causal_conv1d_update_ref
+    ns.ms.selective_state_update = selective_state_update_ref
+    _LOADED["lm"] = types.SimpleNamespace(mss=mss, gen=rgen)
+    return _LOADED["lm"]
+
+
 def slow_path(model):
     """Force every mixer onto the pure-PyTorch path (mamba_simple.py:658-700). The slow path drops the zigzag gather
     that the fast path applies around mamba_inner_fn (mamba_simple.py:627-657, SURVEY finding 3), so mixers with a
