@@ -34,10 +34,8 @@ The operands are converted on every call -- weights too (a cached copy could not
 EMA updates, load_state_dict do not bump a tensor's version counter) -- except inside `frozen_weights()`, the scope a sampler
 opens around its NFE loop, where each weight image is built once. Outputs stay fp32."""
 import contextlib
-
-import threading
-
 import os
+import threading
 
 import torch
 import torch.nn.functional as F
@@ -90,27 +88,59 @@ def weight_image(weight):
     return _cached("w3", weight, lambda: native.split3_rows(weight.detach(), left=False))
 
 
+def out_proj_route(xz, weight, rows, seqlen, scan_kernel=1, planes=True, f16=True):
+    """which carrier serves MambaInnerFn's inference out_proj: `rows` tokens (seqlen per sequence) of a (d_model, d_inner) weight behind a scan on
+    `scan_kernel` lanes per channel (native.scan_fwd_kernel_for). In order of precedence:
+      "f16_convert"  policy "f16s" where a STATE-SPLIT scan kernel serves the launch (scan_kernel != 1: fewer than 2048 waves, e.g. DiM-XL/2 at 512 px,
+                     batch 64): those kernels write fp32 out_z (16 channels per wave: no wave sees a 64-channel block), a conversion pass
+                     (native.rows_block_f16s, 6 bytes per element) builds the block-scaled image the 64-channel kernel would have written and the same
+                     TN product follows (out_proj_f16), not the library's fp32 GEMM (three products + a transposing read: 361 -> ~200 us at XL/2-512).
+                     Ahead of the planes (three products): 22.97 -> 22.77 ms per DiM-L/2 forward at batch 32, 176.6 -> 170.6 ms at DiM-XL/2 512 px
+                     (whose d_model 576 the planes' TN product does not take)
+      "planes"       out_z leaves the scan as its split-bf16 pair of planes (the same 4 bytes per element) and out_proj runs on gemm_tn's transposing
+                     read straight from them (fp32 under allow_tf32: the products the library's fp32 GEMM spends there too, without its conversion of
+                     the d-major operand: 0.26 -> 0.17 ms per mixer at 65536 tokens). DIMSUM_OUT_PROJ_PLANES = auto (default): where the scan runs one of its
+                     state-split kernels (underfilled launches: DiM-XL/2 at 512 px 320.5 -> 315.7 ms per forward, the scan +1.5 %); the 64-channel
+                     kernel of a full chip is VALU-bound and pays +5 % for the conversion in its epilogue (0.338 -> 0.356 ms) against -0.06 ms in
+                     out_proj: -0.7 % per DiM-L/2 forward, but the headline kernel's roofline fraction 0.51 -> 0.49 -- left to `1` (always);
+                     `0` = never. tools/scratch/ab_planes.sh.
+      "f16_scan"     policy "f16s" on the 64-channel kernel: out_z leaves the scan as block-scaled fp16 (out_z_f16=True, half the bytes) and out_proj
+                     is ONE fp16 product per element on the hand-written TN GEMM (out_proj_f16) instead of the library's fp32 GEMM
+      "none"         the fp32 out_z and the library's GEMM (never an error).
+    DIMSUM_OUT_PROJ_F16=0 switches both fp16 routes off. `planes` / `f16` = False: the caller cannot take that route."""
+    env, D, n_out = os.environ.get, weight.shape[1], weight.shape[0]
+    # shared, because BOTH kernels must take the operands: the TN GEMM wants whole 64-row reduction tiles, at least two per piece (d_inner % 64, >= 128),
+    # 256-token panels and 32-bit in-tile offsets of the (2 d_inner, rows) plane pair (native.gemm_tn_supported); the scan's plane / fp16 epilogue is
+    # part of its 16-byte vector path (ssm_scan_fwd.hip: every xz row base 4-element aligned; seqlen % 8 is checked by the caller)
+    if not (_policy in ("default", "f16s") and torch.backends.cuda.matmul.allow_tf32 and env("DIMSUM_SPLIT3", "1") != "0" and own_gemm_enabled()
+            and xz.is_cuda and xz.dtype == torch.float32 and weight.dtype == torch.float32 and weight.stride(1) == 1
+            and rows % 256 == 0 and D % 64 == 0 and D >= 128 and 128 * rows + 512 < 2 ** 31
+            and xz.data_ptr() % 16 == 0 and all(st % 4 == 0 for st in xz.stride()[:-1]) and xz.stride(-1) == 1
+            and rows >= int(env("DIMSUM_SPLIT3_MIN_ROWS", "8192"))):
+        return "none"
+    # per route: policy and switch, scan kernel, d_model (whole 256-column panels of the TN kernel, or weight rows zero-padded to them), d_inner
+    f16 = f16 and _policy == "f16s" and env("DIMSUM_OUT_PROJ_F16", "1") != "0" and seqlen % 32 == 0        # (whole 32-step tiles)
+    mode = env("DIMSUM_OUT_PROJ_PLANES", "auto")
+    if f16 and scan_kernel != 1 and n_out % 4 == 0 and D <= 4096:
+        return "f16_convert"
+    if planes and (mode == "1" or (mode != "0" and scan_kernel != 1)) and n_out % 256 == 0:           # (seqlen % 8: the caller's)
+        return "planes"
+    return "f16_scan" if f16 and scan_kernel == 1 and n_out % 256 == 0 else "none"
+
+
 def out_proj_planes_enabled(xz, weight, rows, scan_kernel=1):
-    """whether MambaInnerFn's out_proj runs as gemm_tn over the scan's split-bf16 out_z planes (inference, fp32 under allow_tf32: the products
-    the library's fp32 GEMM spends there too, without its conversion of the d-major operand): `rows` tokens of a (d_model, d_inner) weight.
-    DIMSUM_OUT_PROJ_PLANES = auto (default): where the scan runs one of its state-split kernels (scan_kernel != 1, underfilled launches:
-    DiM-XL/2 at 512 px 320.5 -> 315.7 ms per forward, the scan +1.5 %); the 64-channel kernel of a full chip is VALU-bound and pays +5 %
-    for the conversion in its epilogue (0.338 -> 0.356 ms) against -0.06 ms in out_proj: -0.7 % per DiM-L/2 forward, but the headline
-    kernel's roofline fraction 0.51 -> 0.49 -- left to `1` (always); `0` = never. tools/scratch/ab_planes.sh."""
-    import os
-    mode = os.environ.get("DIMSUM_OUT_PROJ_PLANES", "auto")
-    if mode == "0" or (mode != "1" and scan_kernel == 1):
-        return False
-    # ... and only where BOTH kernels take the operands (else the fp32 out_z + library GEMM, never an error): the TN GEMM wants whole
-    # 64-row reduction tiles with at least two of them per piece (d_inner % 64, d_inner >= 128), 256-column panels on both sides and
-    # 32-bit in-tile offsets of the (2 d_inner, rows) plane pair (native.gemm_tn_supported); the scan's plane epilogue is part of its
-    # 16-byte vector path (ssm_scan_fwd.hip: every xz row base 4-element aligned; seqlen % 8 is checked by the caller)
-    D = weight.shape[1]
-    return (_policy in ("default", "f16s") and torch.backends.cuda.matmul.allow_tf32 and os.environ.get("DIMSUM_SPLIT3", "1") != "0"
-            and own_gemm_enabled() and xz.is_cuda and xz.dtype == torch.float32 and weight.dtype == torch.float32
-            and weight.stride(1) == 1 and rows % 256 == 0 and weight.shape[0] % 256 == 0 and D % 64 == 0 and D >= 128
-            and 128 * rows + 512 < 2 ** 31 and xz.data_ptr() % 16 == 0 and all(st % 4 == 0 for st in xz.stride()[:-1]) and xz.stride(-1) == 1
-            and rows >= int(os.environ.get("DIMSUM_SPLIT3_MIN_ROWS", "8192")))
+    """whether out_proj_route grants "planes" (the scan's split-bf16 out_z planes + gemm_tn) to a caller that takes no fp16 route"""
+    return out_proj_route(xz, weight, rows, 0, scan_kernel, f16=False) == "planes"
+
+
+def out_proj_f16_enabled(xz, weight, rows, seqlen, scan_kernel=1):
+    """whether out_proj_route grants "f16_scan" (the 64-channel scan kernel's own block-scaled fp16 out_z + one fp16 product)"""
+    return out_proj_route(xz, weight, rows, seqlen, scan_kernel, planes=False) == "f16_scan"
+
+
+def out_proj_f16_convert_enabled(xz, weight, rows, seqlen, scan_kernel):
+    """whether out_proj_route grants "f16_convert" (a state-split scan kernel's fp32 out_z, the conversion pass, one fp16 product)"""
+    return out_proj_route(xz, weight, rows, seqlen, scan_kernel, planes=False) == "f16_convert"
 
 
 def out_proj_planes(planes, weight):
@@ -120,19 +150,6 @@ def out_proj_planes(planes, weight):
     D = weight.shape[1]
     wt = _cached("w3t", weight, lambda: native.split3_rows_t(weight.detach()))
     return native.gemm_tn(planes, wt, alias_rows=D)
-
-
-def out_proj_f16_enabled(xz, weight, rows, seqlen, scan_kernel=1):
-    """whether MambaInnerFn's out_proj runs as ONE fp16 product per element over the scan's block-scaled fp16 out_z (inference under the
-    scaled-fp16 policy; native.selective_scan_fwd(out_z_f16=True) + native.gemm_tn(scales = (table, ..))): the 64-channel scan kernel only
-    (scan_kernel == 1), whole 32-step tiles, the TN GEMM's shapes. DIMSUM_OUT_PROJ_F16=0 hands out_proj back to the library's fp32 GEMM."""
-    import os
-    D = weight.shape[1]
-    return (_policy == "f16s" and scan_kernel == 1 and os.environ.get("DIMSUM_OUT_PROJ_F16", "1") != "0" and torch.backends.cuda.matmul.allow_tf32
-            and os.environ.get("DIMSUM_SPLIT3", "1") != "0" and own_gemm_enabled() and xz.is_cuda and xz.dtype == torch.float32
-            and weight.dtype == torch.float32 and weight.stride(1) == 1 and rows % 256 == 0 and seqlen % 32 == 0 and weight.shape[0] % 256 == 0
-            and D % 64 == 0 and D >= 128 and 128 * rows + 512 < 2 ** 31 and xz.data_ptr() % 16 == 0
-            and all(st % 4 == 0 for st in xz.stride()[:-1]) and xz.stride(-1) == 1 and rows >= int(os.environ.get("DIMSUM_SPLIT3_MIN_ROWS", "8192")))
 
 
 def _pad_cols_256(t):
@@ -145,21 +162,6 @@ def _pad_cols_256(t):
     buf = torch.zeros(t.shape[:-1] + (Np,), device=t.device, dtype=t.dtype)
     buf[..., :N] = t
     return buf[..., :N]
-
-
-def out_proj_f16_convert_enabled(xz, weight, rows, seqlen, scan_kernel):
-    """whether MambaInnerFn's out_proj runs as ONE fp16 product per element where a STATE-SPLIT scan kernel serves the launch (scan_kernel != 1: fewer
-    than 2048 waves, e.g. DiM-XL/2 at 512 px, batch 64): those kernels write fp32 out_z (16 channels per wave: no wave sees a 64-channel block), a
-    conversion pass (native.rows_block_f16s, 6 bytes per element) builds the block-scaled image the 64-channel kernel would have written and the same
-    TN product follows (out_proj_f16) -- instead of the library's fp32 GEMM on the d-major operand (three products + a transposing read: 361 -> ~200 us
-    per mixer at XL/2-512). DIMSUM_OUT_PROJ_F16=0 switches it off."""
-    import os
-    D = weight.shape[1]
-    return (_policy == "f16s" and scan_kernel != 1 and os.environ.get("DIMSUM_OUT_PROJ_F16", "1") != "0" and torch.backends.cuda.matmul.allow_tf32
-            and os.environ.get("DIMSUM_SPLIT3", "1") != "0" and own_gemm_enabled() and xz.is_cuda and xz.dtype == torch.float32
-            and weight.dtype == torch.float32 and weight.stride(1) == 1 and rows % 256 == 0 and seqlen % 32 == 0 and weight.shape[0] % 4 == 0
-            and D % 64 == 0 and 128 <= D <= 4096 and 128 * rows + 512 < 2 ** 31 and xz.data_ptr() % 16 == 0
-            and all(st % 4 == 0 for st in xz.stride()[:-1]) and xz.stride(-1) == 1 and rows >= int(os.environ.get("DIMSUM_SPLIT3_MIN_ROWS", "8192")))
 
 
 def weight_f16s_t(weight):
@@ -380,7 +382,6 @@ def split3_enabled(x, weight, producer="token", left=True):
     on the hand-written GEMM) or "f16s" (policy "f16s": scaled-fp16 images, ONE product):
     the value is what the producer kernels take as their `split3` argument. producer: which kernel family writes the image ("token":
     csrc/token_transform.hip, "norm": csrc/norm.hip) -- their scaled-fp16 variants hold rows of different width."""
-    import os
     mode = "f16s" if _policy == "f16s" else True
     if mode == "f16s" and x.shape[-1] > (1024 if producer == "token" else 2048):
         mode = True        # the token passes hold one channel group per thread (C <= 1024), the norm passes a row in registers (<= 2048):
@@ -524,7 +525,6 @@ def forward_scope(model, rows):
     seen); inside a frozen_weights() scope, under hipGraph capture (the conversion kernels must be part of the graph and their outputs
     live in its pool: _cached bypasses the cache there) or another policy this is a no-op. Under autograd (training under the policy) the same
     launch serves the training forward's weight images (weight_f16s_train, gated_bound_train)."""
-    import os
     from . import native
     first = next(model.parameters(), None)
     # under autograd (training on the single-product carrier, section 3.7 of DESIGN.md) the scope serves the forward's weight images too:
@@ -642,7 +642,6 @@ def neg_exp(a_log):
 
 def own_gemm_enabled():
     """the image GEMMs run on this package's MFMA kernel (csrc/gemm_nt_kernel.hpp); DIMSUM_GEMM_NT=0 hands them back to the library"""
-    import os
     return os.environ.get("DIMSUM_GEMM_NT", "1") != "0"
 
 
@@ -794,7 +793,6 @@ def split3_train_enabled(x, weight):
     inference. -> False, True (split-bf16 images: three bf16 products per fp32 product) or "f16s" (policy "f16s": scaled-fp16 images, ONE fp16
     product per element in the forward, the input-gradient AND the weight-gradient GEMMs -- the reference trains under TF32 too,
     dimsum/train.py:20-21; DIMSUM_F16S_TRAIN=0 keeps the three-product images under that policy)"""
-    import os
     if not (_policy in ("default", "f16s") and torch.backends.cuda.matmul.allow_tf32 and os.environ.get("DIMSUM_SPLIT3", "1") != "0"
             and os.environ.get("DIMSUM_SPLIT3_TRAIN", "1") != "0" and x.is_cuda and x.dtype == torch.float32
             and weight.dtype == torch.float32 and x.shape[-1] % 4 == 0 and torch.is_grad_enabled()
@@ -810,7 +808,6 @@ def split3_train_enabled(x, weight):
 def attn_bwd_f16_enabled(qkv):
     """the attention backward pair (csrc/xattn_fusion_bwd.hip) on the single-product fp16 carrier: the "f16s" policy's training arithmetic
     (split3_train_enabled's switches, no row threshold: the kernels are the same at every size)"""
-    import os
     return bool(_policy == "f16s" and torch.backends.cuda.matmul.allow_tf32 and os.environ.get("DIMSUM_F16S_TRAIN", "1") != "0"
                 and os.environ.get("DIMSUM_SPLIT3_TRAIN", "1") != "0" and os.environ.get("DIMSUM_SPLIT3", "1") != "0"
                 and qkv.is_cuda and qkv.dtype == torch.float32 and not torch.is_autocast_enabled("cuda"))

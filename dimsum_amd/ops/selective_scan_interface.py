@@ -26,6 +26,7 @@ Not implemented (raise): complex A and constant B / C inside mamba_inner_fn* and
 bimamba_inner_fn.
 """
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
@@ -148,6 +149,133 @@ def _rows(t):   # "b d l -> d (b l)" as a view-friendly reshape
     return t.permute(1, 0, 2).reshape(d, b * l)
 
 
+def _delta(delta_proj_weight, dt_rows, bsz, L):   # dt_proj over the (R, b l) rows, written d-major: (b, d, l) with strides (L, bL, 1), no transpose
+    return (delta_proj_weight @ dt_rows).view(delta_proj_weight.shape[0], bsz, L).permute(1, 0, 2)
+
+
+def _prologue(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias):
+    """shared by both mixers -> xz (unit last stride), conv weight (d, w), conv bias, x, z, the four projection operands (cast under autocast)"""
+    if torch.is_autocast_enabled("cuda"):
+        adt = torch.get_autocast_dtype("cuda")
+        x_proj_weight, delta_proj_weight = x_proj_weight.to(adt), delta_proj_weight.to(adt)
+        out_proj_weight = out_proj_weight.to(adt) if out_proj_weight is not None else None
+        out_proj_bias = out_proj_bias.to(adt) if out_proj_bias is not None else None
+    xz = _last_contig(xz)
+    conv_w = conv1d_weight.reshape(conv1d_weight.shape[0], conv1d_weight.shape[-1])     # "d 1 w -> d w"
+    x, z = xz.chunk(2, dim=1)
+    return xz, conv_w, conv1d_bias.contiguous() if conv1d_bias is not None else None, x, z, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias
+
+
+def _conv(x, conv_w, conv_b, conv_done=False, init_states=None, d_major=False):
+    """causal conv1d + SiLU of the x half. conv_done: x already holds it. d_major (the bidirectional mixer): written d-major, so that x_proj reads its
+    (d, b l) rows without a transposing copy. `init_states` is numerically dead in the reference (its buffer is overwritten with the plain conv
+    result, causal_conv1d.cpp:326-329). A full-size buffer is honoured as the output buffer; anything else (e.g. the (batch, d_inner) cond_proj
+    output CondMamba passes) only keeps the autograd edge."""
+    if conv_done:
+        return x
+    if d_major:
+        return native.causal_conv1d_fwd(x, conv_w, conv_b, True, out=x.new_empty(x.shape[1], x.shape[0], x.shape[2]).permute(1, 0, 2))
+    if init_states is not None and init_states.shape == x.shape and init_states.dtype == x.dtype and init_states.stride(-1) == 1:
+        return native.causal_conv1d_fwd_cond(x, conv_w, conv_b, True, init_states)
+    return native.causal_conv1d_fwd(x, conv_w, conv_b, True)
+
+
+_Proj = namedtuple("_Proj", "x_dbl x_dbl_t delta Bm Cm")     # x_dbl: what the backward gets (None: inference), x_dbl_t: (R + 2N, b l) or None, delta: None = fused
+
+
+def _project(conv_out, x_proj_weight, delta_proj_weight, N, B_proj_bias, C_proj_bias, training, dt_fusion=None, transposed=None):
+    """conv_out -> x_proj -> delta, B, C. Layouts chosen like the reference (:622-626): the GEMM writes delta d-major so that it needs no transpose.
+    THE layout rule (transposed=None; the bidirectional mixer asks for True): x_dbl transposed where no projection bias is added and conv_out's (d, b l)
+    rows are contiguous; in training only on the GPU outside autocast (DIMSUM_XDBL_T_TRAIN=0: the reference's row-major layout).
+    dt_fusion = (z, A) where the caller's launch lets the scan form delta itself (inference without the `out` / `x` stores)."""
+    bsz, d_inner, L = conv_out.shape
+    R = delta_proj_weight.shape[1]
+    conv_rows = _rows(conv_out)
+    if transposed is None:
+        transposed = (B_proj_bias is None and C_proj_bias is None and conv_rows.stride(1) == 1 and (not training or (
+            conv_out.is_cuda and not torch.is_autocast_enabled("cuda") and os.environ.get("DIMSUM_XDBL_T_TRAIN", "1") != "0")))
+    if transposed:
+        # x_proj written transposed, (R + 2N, b l): its rows are the d-major delta input, B and C as the scan reads them -- (b, 1, N, l) views with strides
+        # (l, ., b l, 1) -- without the two transposing copies per mixer. Training keeps it as x_dbl: B and C are read in place by both scan kernels, and the
+        # backward writes dB / dC straight into the rows of d x_dbl^T -- 7 transposing / slicing copies per mixer less than the (b l, R + 2N) layout of the
+        # reference (:840-860)
+        x_dbl_t = x_proj_weight @ (conv_rows if conv_rows.stride(1) == 1 else conv_rows.contiguous())
+        # dt_proj inside the scan (csrc/ssm_scan_fwd_kernel.hpp, kDt): where the 64-channel kernel serves the launch, delta = W_dt x_dbl[:R] is formed tile by
+        # tile on the matrix cores and the (b, d, l) tensor never exists: one GEMM launch and 2 b d l 4 bytes less per mixer. The launch keeps no `out` / `x`
+        # stores then (DIMSUM_SCAN_INFER_STORES=1, the reference interface's launch, takes the GEMM). Only under allow_tf32 (the reference's own setting,
+        # train.py:20-21): the in-scan product is three bf16 products per fp32 product (2e-5 relative, what the library's TF32-policy GEMM spends) -- with the
+        # flag off the reference multiplies in exact fp32 and so does this path (the library's fp32 GEMM), which also keeps bench.py's exact-fp32 leg exact.
+        fused = (dt_fusion is not None and not torch.is_autocast_enabled("cuda") and os.environ.get("DIMSUM_SCAN_DT_PROJ", "1") != "0"
+                 and torch.backends.cuda.matmul.allow_tf32 and native.scan_dt_proj_supported(conv_out, dt_fusion[0], dt_fusion[1], delta_proj_weight, x_dbl_t[:R]))
+        delta = None if fused else _delta(delta_proj_weight, x_dbl_t[:R], bsz, L)
+        Bm = x_dbl_t[R:R + N] if B_proj_bias is None else x_dbl_t[R:R + N] + B_proj_bias.to(x_dbl_t.dtype)[:, None]
+        Cm = x_dbl_t[R + N:] if C_proj_bias is None else x_dbl_t[R + N:] + C_proj_bias.to(x_dbl_t.dtype)[:, None]
+        return _Proj(x_dbl_t if training else None, x_dbl_t, delta, Bm.view(N, bsz, L).permute(1, 0, 2).unsqueeze(1), Cm.view(N, bsz, L).permute(1, 0, 2).unsqueeze(1))
+    x_dbl = F.linear(conv_out.transpose(1, 2).reshape(bsz * L, d_inner), x_proj_weight)        # (b l, R + 2N)
+    delta = _delta(delta_proj_weight, x_dbl[:, :R].t(), bsz, L)
+    Bm = x_dbl[:, R:R + N] if B_proj_bias is None else x_dbl[:, R:R + N] + B_proj_bias.to(x_dbl.dtype)
+    Cm = x_dbl[:, -N:] if C_proj_bias is None else x_dbl[:, -N:] + C_proj_bias.to(x_dbl.dtype)
+    Bm = Bm.reshape(bsz, L, N).permute(0, 2, 1).unsqueeze(1).contiguous()                       # (b, 1, N, l)
+    Cm = Cm.reshape(bsz, L, N).permute(0, 2, 1).unsqueeze(1).contiguous()
+    return _Proj(x_dbl, None, delta, Bm, Cm)
+
+
+def _out_proj_route(xz, conv_out, z, A, groups, out_proj_weight, out_proj_bias, general, training, keep):
+    """gemm.out_proj_route for this launch: the planes unless training (only: a prompt pass that keeps the stores may take them), the two fp16 routes
+    unless the scan keeps its `out` / `x` stores (training, last_state, DIMSUM_SCAN_INFER_STORES=1) or autocast is on"""
+    bsz, d_inner, L = conv_out.shape
+    planes, f16 = not training and L % 8 == 0 and d_inner % 64 == 0, not keep and not torch.is_autocast_enabled("cuda")
+    if general or out_proj_weight is None or out_proj_bias is not None or not xz.is_cuda or not (planes or f16):
+        return "none"
+    route = gemm.out_proj_route(xz, out_proj_weight, bsz * L, L, native.scan_fwd_kernel_for(bsz, d_inner, L, A.shape[-1], groups), planes, f16)
+    return "none" if route == "f16_scan" and not native.scan_out_z_f16_supported(conv_out, z, A, groups) else route
+
+
+def _dbc_into(dx_dbl, R, N, bsz, L):   # dB / dC land in rows R .. R + 2N of d x_dbl^T (R + 2N, b l): the (b, 1, N, l) views the scan backward writes through
+    return {"dB": dx_dbl[R:R + N].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1), "dC": dx_dbl[R + N:].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)}
+
+
+def _bwd_tail_t(s, x, conv_out, ddelta, dx_dbl, du, dx):
+    """the backward behind the scan on the transposed x_dbl (R + 2N, b l) of the saved record s, rows R.. of dx_dbl already written: d dt_proj.weight,
+    dx_dbl[:R], d x_proj.weight, d conv_out = du + W_x^T dx_dbl, the conv backward (dx in place) -> (dx_proj_weight, ddelta_proj_weight, dconv_w, dconv_b)"""
+    bsz, d_inner, L = x.shape
+    R = s.delta_proj_weight.shape[1]
+    ddelta2, conv_rows = _rows(ddelta), _rows(conv_out)                                         # (d, b l) views
+    conv_rows = conv_rows if conv_rows.stride(1) == 1 else conv_rows.contiguous()
+    ddelta_proj_weight = gemm.mm_nt_rows(ddelta2, s.x_dbl[:R])                                  # "dB,rB->dr", sliced reduction
+    torch.mm(s.delta_proj_weight.t(), ddelta2, out=dx_dbl[:R])                                  # "dr,dB->rB"
+    dx_proj_weight = gemm.mm_nt_rows(dx_dbl, conv_rows)                                         # "rB,dB->rd", sliced reduction
+    dconv2 = _rows(du)                         # (d, b l) view of the scan's own du: the product is added in place (no copy of the addend)
+    dconv2 = dconv2.addmm_(s.x_proj_weight.t(), dx_dbl) if dconv2.stride(1) == 1 else torch.addmm(dconv2, s.x_proj_weight.t(), dx_dbl)
+    _, dconv_w, dconv_b = native.causal_conv1d_bwd(x, s.conv_w, s.conv_b, dconv2.view(d_inner, bsz, L).permute(1, 0, 2), dx, True)
+    return dx_proj_weight, ddelta_proj_weight, dconv_w, dconv_b
+
+
+def _bwd_tail_rows(s, x, conv_out, ddelta, dx_dbl, du, dx, dB, dC, has_Bb, has_Cb):
+    """the same on the row-major x_dbl (b l, R + 2N) of the reference, dB / dC copied into its columns -> (.., dB_proj_bias, dC_proj_bias)"""
+    bsz, d_inner, L = x.shape
+    R, N = s.delta_proj_weight.shape[1], dB.shape[2]
+    dBf = dB.squeeze(1).permute(0, 2, 1).reshape(bsz * L, N)                                        # "b 1 n l -> (b l) n"
+    dCf = dC.squeeze(1).permute(0, 2, 1).reshape(bsz * L, N)
+    dB_proj_bias, dC_proj_bias = dBf.sum(0) if has_Bb else None, dCf.sum(0) if has_Cb else None
+    dx_dbl[:, R:R + N] = dBf
+    dx_dbl[:, -N:] = dCf
+    ddelta2 = _rows(ddelta)                                                                         # (d, b l)
+    ddelta_proj_weight = gemm.mm_nn_rows(ddelta2, s.x_dbl[:, :R])                                   # "dB,Br->dr", sliced reduction
+    dx_dbl[:, :R] = ddelta2.t() @ s.delta_proj_weight                                               # "dB,dr->Br"
+    dconv2 = _rows(du)                                                                              # (d, b l)
+    dx_proj_weight = gemm.mm_nn_rows(_rows(conv_out), dx_dbl).t()                                   # "Br,Bd->rd", sliced reduction
+    dconv2 = torch.addmm(dconv2, s.x_proj_weight.t(), dx_dbl.t())
+    _, dconv_w, dconv_b = native.causal_conv1d_bwd(x, s.conv_w, s.conv_b, dconv2.view(d_inner, bsz, L).permute(1, 0, 2), dx, True)
+    return dx_proj_weight, ddelta_proj_weight, dconv_w, dconv_b, dB_proj_bias, dC_proj_bias
+
+
+# what _MambaInner saves, in ctx.save_for_backward's order; the last five: the fp32 out_z (kept for d out_proj.weight) or, on the scaled-fp16 training
+# carrier, the images of out_z and W_out^T
+_MambaSaved = namedtuple("_MambaSaved", "xz conv_w conv_b x_dbl x_proj_weight delta_proj_weight out_proj_weight conv_out delta A Bm Cm D delta_bias "
+                                        "scan_x out ckpt kept_out_z oz16_data oz16_inv wt16_data wt16_inv", defaults=(None,) * 5)
+
+
 class _MambaInner(torch.autograd.Function):
     """conv1d(silu) -> x_proj -> dt_proj -> selective scan (+ silu(z) gate) [-> out_proj]."""
 
@@ -157,9 +285,12 @@ class _MambaInner(torch.autograd.Function):
                 A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus, init_states, has_out_proj, checkpoint_lvl,
                 need_ckpt=False, conv_done=False, f16s_train=False, last_state=None):
         # complex A and constant B / C are refused here (selective_scan_fn takes them); any dstate in 1..256 runs
+        # need_ckpt (= training: autograd will record this call; decided by the caller: grad mode is off in here): the tile-boundary states ride along to
+        # the backward (one activation tensor): it then needs no sweep of its own to rebuild them. They depend on (conv_out, delta, A, B) only, which
+        # the backward recomputes identically.
         # conv_done (inference extra, not in the reference's signature): xz[:, :d_inner] already holds the causal conv1d + SiLU of the in_proj
         # output (the GEMM's epilogue formed it, modules/mamba_simple.py) -- the conv kernel is skipped
-        # f16s_train (training extra, decided by the caller like need_ckpt: grad mode is off in here): out_proj's forward, input-gradient and
+        # f16s_train (training extra, decided by the caller like need_ckpt): out_proj's forward, input-gradient and
         # weight-gradient GEMMs as ONE fp16 product per element over scaled-fp16 images (gemm.py, policy "f16s")
         # last_state (recurrent-form extra): a (batch, d_inner, dstate) buffer that receives the scan's state after the last step, as
         # selective_scan_fn(return_last_state=True) returns it (:39) -- the ssm_state a prompt leaves in an inference cache. The launch keeps the
@@ -170,262 +301,163 @@ class _MambaInner(torch.autograd.Function):
             raise NotImplementedError("mamba_inner_fn: complex A is outside this build's scope")
         if B is not None or C is not None:
             raise NotImplementedError("mamba_inner_fn: constant B/C is outside this build's scope")
-        L = xz.shape[-1]
-        R = delta_proj_weight.shape[1]
-        N = A.shape[-1]
+        L, N, training = xz.shape[-1], A.shape[-1], need_ckpt
         # a dstate the tuned kernels are not built for: the plain sequence on the general kernels (csrc/ssm_scan_general.hip), none of the fused
         # extras below. conv_done is honoured: it says what xz already holds.
         general = xz.is_cuda and native.scan_takes_general_path(N, force=native.scan_general_forced())
-        if torch.is_autocast_enabled("cuda"):
-            adt = torch.get_autocast_dtype("cuda")
-            x_proj_weight, delta_proj_weight = x_proj_weight.to(adt), delta_proj_weight.to(adt)
-            if has_out_proj:
-                out_proj_weight = out_proj_weight.to(adt)
-                out_proj_bias = out_proj_bias.to(adt) if out_proj_bias is not None else None
-        xz = _last_contig(xz)
-        conv_w = conv1d_weight.reshape(conv1d_weight.shape[0], conv1d_weight.shape[-1])     # "d 1 w -> d w"
-        conv_b = conv1d_bias.contiguous() if conv1d_bias is not None else None
-        x, z = xz.chunk(2, dim=1)
-        # `init_states` is numerically dead in the reference (its buffer is overwritten with the plain conv result,
-        # causal_conv1d.cpp:326-329). A full-size buffer is honoured as the output buffer; anything else (e.g. the
-        # (batch, d_inner) cond_proj output CondMamba passes) only keeps the autograd edge.
-        if conv_done:
-            conv_out = x
-        elif init_states is not None and init_states.shape == x.shape and init_states.dtype == x.dtype and init_states.stride(-1) == 1:
-            conv_out = native.causal_conv1d_fwd_cond(x, conv_w, conv_b, True, init_states)
-        else:
-            conv_out = native.causal_conv1d_fwd(x, conv_w, conv_b, True)
-        bsz, d_inner = conv_out.shape[0], conv_out.shape[1]
-        keep_stores = need_ckpt or last_state is not None or os.environ.get("DIMSUM_SCAN_INFER_STORES", "0") == "1"      # (see `keep` below)
-        # layouts chosen like the reference (:622-626): the GEMM writes delta d-major so that it needs no transpose
-        conv_rows = _rows(conv_out)
-        if not need_ckpt and B_proj_bias is None and C_proj_bias is None and conv_rows.stride(1) == 1:
-            # inference: x_proj written transposed, (R + 2N, b l): its rows are the d-major delta input, B and C as the scan reads
-            # them -- (b, 1, N, l) views with strides (l, ., b l, 1) -- without the two transposing copies per mixer
-            x_dbl_t = x_proj_weight @ conv_rows                                                          # (R + 2N, b l)
-            x_dbl = None
-            # dt_proj inside the scan (csrc/ssm_scan_fwd_kernel.hpp, kDt): where the 64-channel kernel serves the launch, delta = W_dt x_dbl[:R] is
-            # formed tile by tile on the matrix cores and the (b, d, l) tensor never exists: one GEMM launch and 2 b d l 4 bytes less per mixer.
-            # The launch keeps no `out` / `x` stores then (DIMSUM_SCAN_INFER_STORES=1, the reference interface's launch, takes the GEMM).
-            # Only under allow_tf32 (the reference's own setting, train.py:20-21): the in-scan product is three bf16 products per fp32 product
-            # (2e-5 relative, what the library's TF32-policy GEMM spends) -- with the flag off the reference multiplies in exact fp32 and so
-            # does this path (the library's fp32 GEMM), which also keeps bench.py's exact-fp32 reference leg exact.
-            dt_fused = (not general and not keep_stores and not torch.is_autocast_enabled("cuda") and os.environ.get("DIMSUM_SCAN_DT_PROJ", "1") != "0"
-                        and torch.backends.cuda.matmul.allow_tf32
-                        and native.scan_dt_proj_supported(conv_out, z, A, delta_proj_weight, x_dbl_t[:R]))
-            delta = None if dt_fused else (delta_proj_weight @ x_dbl_t[:R]).view(d_inner, bsz, L).permute(1, 0, 2)
-            Bm = x_dbl_t[R:R + N].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)
-            Cm = x_dbl_t[R + N:].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)
-        elif need_ckpt and B_proj_bias is None and C_proj_bias is None and conv_rows.stride(1) == 1 and xz.is_cuda \
-                and not torch.is_autocast_enabled("cuda") and os.environ.get("DIMSUM_XDBL_T_TRAIN", "1") != "0":
-            # training, the same transposed x_proj: B and C are read in place by both scan kernels, and the backward writes dB / dC straight into
-            # the rows of d x_dbl^T -- 7 transposing / slicing copies per mixer less than the (b l, R + 2N) layout of the reference (:840-860)
-            x_dbl = x_dbl_t = x_proj_weight @ conv_rows                                                  # (R + 2N, b l), saved as x_dbl
-            dt_fused = False
-            delta = (delta_proj_weight @ x_dbl_t[:R]).view(d_inner, bsz, L).permute(1, 0, 2)
-            Bm = x_dbl_t[R:R + N].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)
-            Cm = x_dbl_t[R + N:].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)
-        else:
-            x_dbl_t = None
-            x_dbl = F.linear(conv_out.transpose(1, 2).reshape(bsz * L, d_inner), x_proj_weight)        # (b l, R + 2N)
-            delta = (delta_proj_weight @ x_dbl[:, :R].t()).view(d_inner, bsz, L).permute(1, 0, 2)       # (b, d, l), strides (L, bL, 1)
-            Bm = x_dbl[:, R:R + N]
-            Cm = x_dbl[:, -N:]
-            if B_proj_bias is not None:
-                Bm = Bm + B_proj_bias.to(Bm.dtype)
-            if C_proj_bias is not None:
-                Cm = Cm + C_proj_bias.to(Cm.dtype)
-            Bm = Bm.reshape(bsz, L, N).permute(0, 2, 1).unsqueeze(1).contiguous()                       # (b, 1, N, l)
-            Cm = Cm.reshape(bsz, L, N).permute(0, 2, 1).unsqueeze(1).contiguous()
-        D = D.contiguous() if D is not None else None
-        # the tile-boundary states ride along to the backward (one activation tensor): it then needs no sweep of
-        # its own to rebuild them. They depend on (conv_out, delta, A, B) only, which the backward recomputes identically.
-        need = need_ckpt        # decided by the caller (grad mode is off in here)
+        xz, conv_w, conv_b, x, z, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias = _prologue(
+            xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight if has_out_proj else None, out_proj_bias if has_out_proj else None)
+        conv_out = _conv(x, conv_w, conv_b, conv_done, init_states)
+        bsz = conv_out.shape[0]
         # `out` (ungated) and the chunk states `x` only serve the backward. The reference's kernel always stores them
         # (selective_scan_fwd_kernel.cuh:239-254); here an inference call (nothing to differentiate) passes NULL out_ptr / x_ptr and the
         # kernel skips both stores: 1.082 instead of 1.384 GB per launch at DiM-L/2, batch 256 (SURVEY 8(d)'s "inference-only lower bound"),
         # same arithmetic, bit-identical out_z. DIMSUM_SCAN_INFER_STORES=1 restores the reference interface's stores (bench.py prices
         # that launch too, as `roofline_full_interface`).
-        keep = need or keep_stores
-        # inference under allow_tf32: out_z leaves the scan as its split-bf16 pair of planes (the same 4 bytes per element) and out_proj runs
-        # on the hand-written kernel's transposing-read variant straight from them (0.26 -> 0.17 ms per mixer at 65536 tokens)
-        scan_k = native.scan_fwd_kernel_for(bsz, d_inner, L, N, Bm.shape[1]) if xz.is_cuda and not general else 1
-        # ... under the scaled-fp16 policy where a state-split kernel serves the launch (fp32 out_z: 16 channels per wave, no wave sees a 64-channel
-        # block): ONE fp16 product behind a conversion pass that builds the block-scaled image (gemm.out_proj_f16_convert_enabled); takes precedence
-        # over the planes (three products): 22.97 -> 22.77 ms per DiM-L/2 forward at batch 32, 176.6 -> 170.6 ms at DiM-XL/2 512 px (whose d_model
-        # 576 the planes' TN product does not take)
-        conv16 = (not general and has_out_proj and not keep and out_proj_bias is None and xz.is_cuda and not torch.is_autocast_enabled("cuda")
-                  and gemm.out_proj_f16_convert_enabled(xz, out_proj_weight, bsz * L, L, scan_k))
-        planes = (not general and has_out_proj and not need and not conv16 and out_proj_bias is None and L % 8 == 0
-                  and d_inner % 64 == 0 and xz.is_cuda
-                  and gemm.out_proj_planes_enabled(xz, out_proj_weight, bsz * L, scan_k))
-        # inference under the scaled-fp16 policy on the 64-channel kernel: out_z leaves the scan as block-scaled fp16 (half the bytes) and
-        # out_proj is ONE fp16 product per element on the hand-written TN GEMM (gemm.out_proj_f16) instead of the library's fp32 GEMM
-        z16 = (not general and has_out_proj and not keep and not planes and not conv16 and out_proj_bias is None and xz.is_cuda and not torch.is_autocast_enabled("cuda")
-               and native.scan_out_z_f16_supported(conv_out, z, A, Bm.shape[1])
-               and gemm.out_proj_f16_enabled(xz, out_proj_weight, bsz * L, L, scan_k))
+        keep = training or last_state is not None or os.environ.get("DIMSUM_SCAN_INFER_STORES", "0") == "1"
+        proj = _project(conv_out, x_proj_weight, delta_proj_weight, N, B_proj_bias, C_proj_bias, training, None if general or keep else (z, A))
+        x_dbl, delta, Bm, Cm = proj.x_dbl, proj.delta, proj.Bm, proj.Cm
+        D = D.contiguous() if D is not None else None
+        route = _out_proj_route(xz, conv_out, z, A, Bm.shape[1], out_proj_weight, out_proj_bias, general, training, keep)
         if general:
             out, scan_x, out_z = native.selective_scan_general_fwd(conv_out, delta, A.contiguous(), Bm, Cm, D, z, delta_bias, delta_softplus, need_out=keep, need_x=keep)
             rest = [None]
         else:
             out, scan_x, out_z, *rest = native.selective_scan_fwd(conv_out, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus,
-                                                                  need_out=keep, need_x=keep, need_ckpt=need, **({"out_z_planes": True} if planes else {}),
-                                                                  **({"out_z_f16": True} if z16 else {}),
-                                                                  **({"dt_proj": (delta_proj_weight, x_dbl_t[:R])} if delta is None else {}))
+                                                                  need_out=keep, need_x=keep, need_ckpt=training, **({"out_z_planes": True} if route == "planes" else {}),
+                                                                  **({"out_z_f16": True} if route == "f16_scan" else {}),
+                                                                  **({"dt_proj": (delta_proj_weight, proj.x_dbl_t[:delta_proj_weight.shape[1]])} if delta is None else {}))
         if last_state is not None:
             last_state.copy_(scan_x[:, :, -1, 1::2])
-        if z16:
-            return gemm.out_proj_f16(out_z[0], out_z[1], out_proj_weight).view(bsz, L, out_proj_weight.shape[0])
-        if conv16:
+        # the routed product. The conversion route on an out_z whose (d, b l) rows the conversion pass does not take goes on with the fp32 out_z below.
+        y = None
+        if route == "f16_scan":
+            y = gemm.out_proj_f16(out_z[0], out_z[1], out_proj_weight)
+        elif route == "planes":
+            y = gemm.out_proj_planes(out_z, out_proj_weight)
+        elif route == "f16_convert":
             oz_rows = _rows(out_z)
             if oz_rows.stride(1) == 1 and oz_rows.stride(0) % 4 == 0:
-                img, tab = native.rows_block_f16s(oz_rows)
-                return gemm.out_proj_f16(img, tab, out_proj_weight).view(bsz, L, out_proj_weight.shape[0])
-        if planes:
-            return gemm.out_proj_planes(out_z, out_proj_weight).view(bsz, L, out_proj_weight.shape[0])
-        ckpt = rest[0] if need else None
-        ctx.general = general
-        ctx.delta_softplus, ctx.has_out_proj, ctx.checkpoint_lvl = delta_softplus, has_out_proj, checkpoint_lvl
-        ctx.xdbl_t = x_dbl is not None and x_dbl is x_dbl_t       # (training: x_dbl is saved as its transpose)
+                y = gemm.out_proj_f16(*native.rows_block_f16s(oz_rows), out_proj_weight)
+        if y is not None:
+            return y.view(bsz, L, out_proj_weight.shape[0])
+        ckpt = rest[0] if training else None
+        ctx.general, ctx.delta_softplus, ctx.has_out_proj, ctx.checkpoint_lvl = general, delta_softplus, has_out_proj, checkpoint_lvl
+        ctx.xdbl_t = x_dbl is not None and x_dbl is proj.x_dbl_t       # (training: x_dbl is saved as its transpose)
         ctx.flags = (conv1d_bias is not None, D is not None, delta_bias is not None, B_proj_bias is not None,
                      C_proj_bias is not None, has_out_proj and out_proj_bias is not None)
         if checkpoint_lvl >= 1:
             conv_out, delta = None, None            # recomputed in the backward (:663-664)
-        keep_out_z = has_out_proj and need and (general or os.environ.get("DIMSUM_RECOMPUTE_OUT_Z", "0") != "1")     # (the general backward does not recompute it)
-        f16s = bool(f16s_train) and not general and has_out_proj and need and out_proj_bias is None and keep_out_z
-        ctx.f16s = f16s
-        if f16s:
+        keep_out_z = has_out_proj and training and (general or os.environ.get("DIMSUM_RECOMPUTE_OUT_Z", "0") != "1")     # (the general backward does not recompute it)
+        ctx.f16s = bool(f16s_train) and not general and out_proj_bias is None and keep_out_z
+        saved = _MambaSaved(xz, conv_w, conv_b, x_dbl, x_proj_weight, delta_proj_weight, out_proj_weight, conv_out, delta, A, Bm, Cm, D, delta_bias,
+                            scan_x, out, ckpt, out_z if keep_out_z and not ctx.f16s else None)
+        if ctx.f16s:
             # out = out_z^T W_out^T as the TN product of two images whose rows are the reduction index (channels): out_z (d, b l) with one scale per
             # channel, W_out^T (d, e) with one per channel -> per-reduction-row factors. The image replaces the fp32 out_z among the saved tensors
             # (d out_proj.weight reads it again): half the bytes kept per mixer.
             oz16 = native.rows_f16s(_rows(out_z))
             wt16 = gemm.weight_t_f16s_train(out_proj_weight)
             y = native.gemm_tn(oz16.data, wt16.data, row_invs=(oz16.inv, wt16.inv))
-            ctx.save_for_backward(xz, conv_w, conv_b, x_dbl, x_proj_weight, delta_proj_weight, out_proj_weight, conv_out, delta, A, Bm, Cm, D, delta_bias,
-                                  scan_x, out, ckpt, None, oz16.data, oz16.inv, wt16.data, wt16.inv)
+            ctx.save_for_backward(*saved[:18], oz16.data, oz16.inv, wt16.data, wt16.inv)
             return y.view(bsz, L, out_proj_weight.shape[0])
-        ctx.save_for_backward(xz, conv_w, conv_b, x_dbl, x_proj_weight, delta_proj_weight,
-                              out_proj_weight if has_out_proj else None, conv_out, delta, A, Bm, Cm, D, delta_bias, scan_x, out, ckpt,
-                              out_z if keep_out_z else None, None, None, None, None)
+        ctx.save_for_backward(*saved)
         if not has_out_proj:
             return out_z                                                                                # (b, d, l)
-        if out_proj_bias is None:
-            return gemm.linear(out_z.transpose(1, 2), out_proj_weight)                                   # (b, l, d_model)
-        return F.linear(out_z.transpose(1, 2), out_proj_weight, out_proj_bias)
+        oz_t = out_z.transpose(1, 2)
+        return gemm.linear(oz_t, out_proj_weight) if out_proj_bias is None else F.linear(oz_t, out_proj_weight, out_proj_bias)    # (b, l, d_model)
 
     @staticmethod
     @custom_bwd(device_type="cuda")
     def backward(ctx, dout):
-        (xz, conv_w, conv_b, x_dbl, x_proj_weight, delta_proj_weight, out_proj_weight, conv_out, delta, A, Bm, Cm, D,
-         delta_bias, scan_x, out, ckpt, kept_out_z, oz16_data, oz16_inv, wt16_data, wt16_inv) = ctx.saved_tensors
+        s = _MambaSaved._make(ctx.saved_tensors)
+        xz, x_dbl, conv_out, delta, A = s.xz, s.x_dbl, s.conv_out, s.delta, s.A
         has_conv_b, has_D, has_dbias, has_Bb, has_Cb, has_ob = ctx.flags
-        L = xz.shape[-1]
-        R = delta_proj_weight.shape[1]
-        N = A.shape[-1]
+        L, R, N = xz.shape[-1], s.delta_proj_weight.shape[1], A.shape[-1]
         x, z = xz.chunk(2, dim=1)
         bsz, d_inner = x.shape[0], x.shape[1]
         dout = _last_contig(dout)
         if ctx.checkpoint_lvl == 1:
-            conv_out = native.causal_conv1d_fwd(x, conv_w, conv_b, True)         # the NON-cond entry, as in :929
-            delta = (delta_proj_weight @ (x_dbl[:R] if ctx.xdbl_t else x_dbl[:, :R].t())).view(d_inner, bsz, L).permute(1, 0, 2)
+            conv_out = native.causal_conv1d_fwd(x, s.conv_w, s.conv_b, True)         # the NON-cond entry, as in :929
+            delta = _delta(s.delta_proj_weight, x_dbl[:R] if ctx.xdbl_t else x_dbl[:, :R].t(), bsz, L)
         dxz = torch.empty_like(xz)
         dx, dz = dxz.chunk(2, dim=1)
         dout16 = None
         if ctx.f16s:
             # dout_y (d, b l) = W_out^T dout^T as an NT product of the images of W_out^T (one scale per channel = output row) and dout (one per token)
             dout16 = native.rows_f16s(dout.reshape(bsz * L, -1))
-            dout_y = native.gemm_nt(wt16_data, dout16.data, scales=(wt16_inv, dout16.inv)).view(d_inner, bsz, L).permute(1, 0, 2)
+            dout_y = native.gemm_nt(s.wt16_data, dout16.data, scales=(s.wt16_inv, dout16.inv)).view(d_inner, bsz, L).permute(1, 0, 2)
         elif ctx.has_out_proj:
             dout2 = dout.reshape(bsz * L, -1).t()                                                       # "b l e -> e (b l)"
-            dout_y = (out_proj_weight.t() @ dout2).view(d_inner, bsz, L).permute(1, 0, 2)               # d-major like delta
+            dout_y = (s.out_proj_weight.t() @ dout2).view(d_inner, bsz, L).permute(1, 0, 2)             # d-major like delta
         else:
             dout_y = dout
-        recompute = ctx.has_out_proj and kept_out_z is None and not ctx.f16s     # only d out_proj.weight needs out_z
+        recompute = ctx.has_out_proj and s.kept_out_z is None and not ctx.f16s     # only d out_proj.weight needs out_z
         dx_dbl = torch.empty_like(x_dbl)
-        into = {}
-        if ctx.xdbl_t:      # dB / dC land in rows R .. R + 2N of d x_dbl^T (R + 2N, b l)
-            into = {"dB": dx_dbl[R:R + N].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1), "dC": dx_dbl[R + N:].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)}
+        into = _dbc_into(dx_dbl, R, N, bsz, L) if ctx.xdbl_t else {}
         if ctx.general:
             dconv_out, ddelta, dA, dB, dC, dD, ddelta_bias, dz = native.selective_scan_general_bwd(
-                conv_out, delta, A.contiguous(), Bm, Cm, D, z, delta_bias, dout_y, out, dz, ctx.delta_softplus, **into)
+                conv_out, delta, A.contiguous(), s.Bm, s.Cm, s.D, z, s.delta_bias, dout_y, s.out, dz, ctx.delta_softplus, **into)
             rest = []
         else:
             dconv_out, ddelta, dA, dB, dC, dD, ddelta_bias, dz, *rest = native.selective_scan_bwd(
-                conv_out, delta, A, Bm, Cm, D, z, delta_bias, dout_y, scan_x, out, dz, ctx.delta_softplus, recompute, ckpt=ckpt, **into)
-        out_z = rest[0] if recompute else kept_out_z
-        dout_proj_weight = dout_proj_bias = None
+                conv_out, delta, A, s.Bm, s.Cm, s.D, z, s.delta_bias, dout_y, s.scan_x, s.out, dz, ctx.delta_softplus, recompute, ckpt=s.ckpt, **into)
+        out_z = rest[0] if recompute else s.kept_out_z
+        dout_proj_weight = dout_proj_bias = dB_proj_bias = dC_proj_bias = None
         if ctx.f16s:
             # "eB,dB->ed" as the mixed-layout product out_z (d, B) dout (B, e): the saved image's rows run along the reduction, dout's over it
-            dout_proj_weight = native.gemm_nn(oz16_data, oz16_inv, dout16.data, dout16.inv).t()
+            dout_proj_weight = native.gemm_nn(s.oz16_data, s.oz16_inv, dout16.data, dout16.inv).t()
         elif ctx.has_out_proj:
             # "eB,dB->ed": a (d_model, d_inner) output over a b*l-long reduction -- sliced, it would fill 8 of 256 CUs otherwise
             dout_proj_weight = gemm.mm_nn_rows(_rows(out_z), dout.reshape(bsz * L, -1)).t()
         if ctx.has_out_proj:
             dout_proj_bias = dout.sum(dim=(0, 1)) if has_ob else None
         if ctx.xdbl_t:
-            ddelta2, conv_rows = _rows(ddelta), _rows(conv_out)                                         # (d, b l) views
-            conv_rows = conv_rows if conv_rows.stride(1) == 1 else conv_rows.contiguous()
-            ddelta_proj_weight = gemm.mm_nt_rows(ddelta2, x_dbl[:R])                                    # "dB,rB->dr", sliced reduction
-            torch.mm(delta_proj_weight.t(), ddelta2, out=dx_dbl[:R])                                    # "dr,dB->rB"
-            dx_proj_weight = gemm.mm_nt_rows(dx_dbl, conv_rows)                                         # "rB,dB->rd", sliced reduction
-            dconv2 = _rows(dconv_out)                  # (d, b l) view of the scan's own du: the product is added in place (no copy of the addend)
-            dconv2 = dconv2.addmm_(x_proj_weight.t(), dx_dbl) if dconv2.stride(1) == 1 else torch.addmm(dconv2, x_proj_weight.t(), dx_dbl)
-            dconv_out = dconv2.view(d_inner, bsz, L).permute(1, 0, 2)
-            _, dconv_w, dconv_b = native.causal_conv1d_bwd(x, conv_w, conv_b, dconv_out, dx, True)
-            return (dxz, dconv_w.unsqueeze(1), dconv_b if has_conv_b else None, dx_proj_weight, ddelta_proj_weight,
-                    dout_proj_weight, dout_proj_bias, dA, None, None, dD if has_D else None,
-                    ddelta_bias if has_dbias else None, None, None, None, None, None, None, None, None, None, None)
-        dBf = dB.squeeze(1).permute(0, 2, 1).reshape(bsz * L, N)                                        # "b 1 n l -> (b l) n"
-        dCf = dC.squeeze(1).permute(0, 2, 1).reshape(bsz * L, N)
-        dB_proj_bias = dBf.sum(0) if has_Bb else None
-        dC_proj_bias = dCf.sum(0) if has_Cb else None
-        dx_dbl[:, R:R + N] = dBf
-        dx_dbl[:, -N:] = dCf
-        ddelta2 = _rows(ddelta)                                                                         # (d, b l)
-        ddelta_proj_weight = gemm.mm_nn_rows(ddelta2, x_dbl[:, :R])                                     # "dB,Br->dr", sliced reduction
-        dx_dbl[:, :R] = ddelta2.t() @ delta_proj_weight                                                 # "dB,dr->Br"
-        dconv2 = _rows(dconv_out)                                                                       # (d, b l)
-        dx_proj_weight = gemm.mm_nn_rows(_rows(conv_out), dx_dbl).t()                                   # "Br,Bd->rd", sliced reduction
-        dconv2 = torch.addmm(dconv2, x_proj_weight.t(), dx_dbl.t())
-        dconv_out = dconv2.view(d_inner, bsz, L).permute(1, 0, 2)
-        _, dconv_w, dconv_b = native.causal_conv1d_bwd(x, conv_w, conv_b, dconv_out, dx, True)
+            dx_proj_weight, ddelta_proj_weight, dconv_w, dconv_b = _bwd_tail_t(s, x, conv_out, ddelta, dx_dbl, dconv_out, dx)
+        else:
+            dx_proj_weight, ddelta_proj_weight, dconv_w, dconv_b, dB_proj_bias, dC_proj_bias = _bwd_tail_rows(
+                s, x, conv_out, ddelta, dx_dbl, dconv_out, dx, dB, dC, has_Bb, has_Cb)
         return (dxz, dconv_w.unsqueeze(1), dconv_b if has_conv_b else None, dx_proj_weight, ddelta_proj_weight,
                 dout_proj_weight, dout_proj_bias, dA, None, None, dD if has_D else None,
                 ddelta_bias if has_dbias else None, dB_proj_bias, dC_proj_bias, None, None, None, None, None, None, None, None)
 
 
+def _mamba_inner(has_out_proj, xz, *a, init_states=None, conv_done=False, last_state=None):
+    """a: conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias, B_proj_bias, C_proj_bias,
+    delta_softplus -- _MambaInner.apply's order"""
+    wb = _will_backprop(xz, *a[:-1], init_states)
+    return _MambaInner.apply(xz, *a, init_states, has_out_proj, _checkpoint_lvl(), wb, conv_done, _f16s_train(xz, a[4], wb), last_state)
+
+
 def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A,
                    B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True):
-    wb = _will_backprop(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias,
-                        B_proj_bias, C_proj_bias, None)
-    return _MambaInner.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight,
-                             out_proj_bias, A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus, None, True, _checkpoint_lvl(),
-                             wb, False, _f16s_train(xz, out_proj_weight, wb))
+    return _mamba_inner(True, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias,
+                        B_proj_bias, C_proj_bias, delta_softplus)
 
 
 def mamba_inner_fn_cond(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                         A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None,
                         delta_softplus=True, init_states=None, conv_done=False, last_state=None):
-    wb = _will_backprop(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias,
-                        B_proj_bias, C_proj_bias, init_states)
-    return _MambaInner.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight,
-                             out_proj_bias, A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus, init_states,
-                             True, _checkpoint_lvl(), wb, conv_done, _f16s_train(xz, out_proj_weight, wb), last_state)
+    return _mamba_inner(True, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias,
+                        B_proj_bias, C_proj_bias, delta_softplus, init_states=init_states, conv_done=conv_done, last_state=last_state)
 
 
 def mamba_inner_fn_no_out_proj(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, B=None, C=None,
                                D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True):
-    return _MambaInner.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, None, None, A, B, C, D,
-                             delta_bias, B_proj_bias, C_proj_bias, delta_softplus, None, False, _checkpoint_lvl(),
-                             _will_backprop(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, None))
+    return _mamba_inner(False, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, None, None, A, B, C, D, delta_bias,
+                        B_proj_bias, C_proj_bias, delta_softplus)
 
 
 def mamba_inner_fn_no_out_proj_cond(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, B=None, C=None,
                                     D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True,
                                     init_states=None):
-    return _MambaInner.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, None, None, A, B, C, D,
-                             delta_bias, B_proj_bias, C_proj_bias, delta_softplus, init_states, False, _checkpoint_lvl(),
-                             _will_backprop(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, init_states))
+    return _mamba_inner(False, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, None, None, A, B, C, D, delta_bias,
+                        B_proj_bias, C_proj_bias, delta_softplus, init_states=init_states)
+
+
+# what _BiMambaInner saves, in ctx.save_for_backward's order
+_BiSaved = namedtuple("_BiSaved", "xz conv_w conv_b x_dbl x_proj_weight delta_proj_weight out_proj_weight conv_out delta A A_b Bm Cm D delta_bias "
+                                  "out out_b ckpt ckpt_b kept_out_z")
 
 
 class _BiMambaInner(torch.autograd.Function):
@@ -447,39 +479,16 @@ class _BiMambaInner(torch.autograd.Function):
         if B is not None or C is not None:
             raise NotImplementedError("bimamba_inner_fn: constant B/C is outside this build's scope")
         native._gpu(xz, conv1d_weight, x_proj_weight, delta_proj_weight, out_proj_weight, A, A_b)
-        L = xz.shape[-1]
-        R = delta_proj_weight.shape[1]
-        N = A.shape[-1]
-        if torch.is_autocast_enabled("cuda"):
-            adt = torch.get_autocast_dtype("cuda")
-            x_proj_weight, delta_proj_weight, out_proj_weight = x_proj_weight.to(adt), delta_proj_weight.to(adt), out_proj_weight.to(adt)
-            out_proj_bias = out_proj_bias.to(adt) if out_proj_bias is not None else None
-        xz = _last_contig(xz)
-        conv_w = conv1d_weight.reshape(conv1d_weight.shape[0], conv1d_weight.shape[-1])     # "d 1 w -> d w"
-        conv_b = conv1d_bias.contiguous() if conv1d_bias is not None else None
-        x, z = xz.chunk(2, dim=1)
-        bsz, d_inner = x.shape[0], x.shape[1]
-        # shared by both directions (the reference's too); written d-major, so that x_proj reads its (d, b l) rows without a transposing copy
-        conv_out = native.causal_conv1d_fwd(x, conv_w, conv_b, True, out=x.new_empty(d_inner, bsz, L).permute(1, 0, 2))
-        conv_rows = _rows(conv_out)
-        conv_rows = conv_rows if conv_rows.stride(1) == 1 else conv_rows.contiguous()
-        x_dbl = x_proj_weight @ conv_rows                                                            # (R + 2N, b l)
-        delta = (delta_proj_weight @ x_dbl[:R]).view(d_inner, bsz, L).permute(1, 0, 2)               # (b, d, l), strides (L, bL, 1)
-        Bm, Cm = x_dbl[R:R + N], x_dbl[R + N:]
-        if B_proj_bias is not None:
-            Bm = Bm + B_proj_bias.to(Bm.dtype)[:, None]
-        if C_proj_bias is not None:
-            Cm = Cm + C_proj_bias.to(Cm.dtype)[:, None]
-        Bm = Bm.view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)                                        # (b, 1, N, l) views, unit stride along l
-        Cm = Cm.view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)
+        xz, conv_w, conv_b, x, z, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias = _prologue(
+            xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias)
+        conv_out = _conv(x, conv_w, conv_b, d_major=True)                                              # shared by both directions (the reference's too)
+        x_dbl, _, delta, Bm, Cm = _project(conv_out, x_proj_weight, delta_proj_weight, A.shape[-1], B_proj_bias, C_proj_bias, need_ckpt, transposed=True)
         D = D.contiguous() if D is not None else None
         A, A_b = A.contiguous(), A_b.contiguous()
         out, out_b, out_z, *ck = native.selective_scan_bidir_fwd(conv_out, delta, A, A_b, Bm, Cm, D, z, delta_bias, delta_softplus,
                                                                 need_out=need_ckpt, need_ckpt=need_ckpt)
-        if out_proj_bias is None:
-            y = gemm.linear(out_z.transpose(1, 2), out_proj_weight)                                    # (b, l, d_model)
-        else:
-            y = F.linear(out_z.transpose(1, 2), out_proj_weight, out_proj_bias)
+        oz_t = out_z.transpose(1, 2)
+        y = gemm.linear(oz_t, out_proj_weight) if out_proj_bias is None else F.linear(oz_t, out_proj_weight, out_proj_bias)       # (b, l, d_model)
         if not need_ckpt:
             return y
         ctx.delta_softplus, ctx.checkpoint_lvl = delta_softplus, checkpoint_lvl
@@ -488,59 +497,48 @@ class _BiMambaInner(torch.autograd.Function):
         if checkpoint_lvl >= 1:
             conv_out, delta = None, None            # recomputed in the backward (:1095-1096)
         keep_out_z = os.environ.get("DIMSUM_RECOMPUTE_OUT_Z", "0") != "1"
-        ctx.save_for_backward(xz, conv_w, conv_b, x_dbl, x_proj_weight, delta_proj_weight, out_proj_weight, conv_out, delta, A, A_b, Bm, Cm,
-                              D, delta_bias, out, out_b, ck[0], ck[1], out_z if keep_out_z else None)
+        ctx.save_for_backward(*_BiSaved(xz, conv_w, conv_b, x_dbl, x_proj_weight, delta_proj_weight, out_proj_weight, conv_out, delta, A, A_b, Bm, Cm,
+                                        D, delta_bias, out, out_b, ck[0], ck[1], out_z if keep_out_z else None))
         return y
 
     @staticmethod
     @custom_bwd(device_type="cuda")
     def backward(ctx, dout):
-        (xz, conv_w, conv_b, x_dbl, x_proj_weight, delta_proj_weight, out_proj_weight, conv_out, delta, A, A_b, Bm, Cm, D, delta_bias,
-         out, out_b, ckpt, ckpt_b, kept_out_z) = ctx.saved_tensors
+        s = _BiSaved._make(ctx.saved_tensors)
+        xz, x_dbl, conv_out, delta = s.xz, s.x_dbl, s.conv_out, s.delta
         has_conv_b, has_D, has_dbias, has_Bb, has_Cb, has_ob = ctx.flags
-        L = xz.shape[-1]
-        R = delta_proj_weight.shape[1]
-        N = A.shape[-1]
+        L, R, N = xz.shape[-1], s.delta_proj_weight.shape[1], s.A.shape[-1]
         x, z = xz.chunk(2, dim=1)
         bsz, d_inner = x.shape[0], x.shape[1]
         dout = _last_contig(dout)
         if ctx.checkpoint_lvl == 1:
-            conv_out = native.causal_conv1d_fwd(x, conv_w, conv_b, True)
-            delta = (delta_proj_weight @ x_dbl[:R]).view(d_inner, bsz, L).permute(1, 0, 2)
+            conv_out = native.causal_conv1d_fwd(x, s.conv_w, s.conv_b, True)
+            delta = _delta(s.delta_proj_weight, x_dbl[:R], bsz, L)
         dxz = torch.empty_like(xz)
         dx, dz = dxz.chunk(2, dim=1)
         dout2 = dout.reshape(bsz * L, -1).t()                                                          # "b l e -> e (b l)"
-        dout_y = (out_proj_weight.t() @ dout2).view(d_inner, bsz, L).permute(1, 0, 2)                 # d-major like delta
-        recompute = kept_out_z is None
+        dout_y = (s.out_proj_weight.t() @ dout2).view(d_inner, bsz, L).permute(1, 0, 2)               # d-major like delta
+        recompute = s.kept_out_z is None
         dx_dbl = torch.empty_like(x_dbl)                                                               # (R + 2N, b l)
-        into = {}
-        if x_dbl.dtype == torch.float32:     # dB / dC land in rows R .. R + 2N of d x_dbl^T (the kernel's dB / dC are fp32)
-            into = {"dB": dx_dbl[R:R + N].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1), "dC": dx_dbl[R + N:].view(N, bsz, L).permute(1, 0, 2).unsqueeze(1)}
+        into = _dbc_into(dx_dbl, R, N, bsz, L) if x_dbl.dtype == torch.float32 else {}                 # (the kernel's dB / dC are fp32)
         # dz: both directions' parts, written into dxz's z half (the reference keeps only the forward direction's there)
         du, ddelta, dA, dA_b, dB, dC, dD, ddelta_bias, dz, *rest = native.selective_scan_bidir_bwd(
-            conv_out, delta, A, A_b, Bm, Cm, D, z, delta_bias, dout_y, out, out_b, ckpt, ckpt_b, ctx.delta_softplus, recompute, dz=dz, **into)
+            conv_out, delta, s.A, s.A_b, s.Bm, s.Cm, s.D, z, s.delta_bias, dout_y, s.out, s.out_b, s.ckpt, s.ckpt_b, ctx.delta_softplus, recompute,
+            dz=dz, **into)
         if not into:
             dx_dbl[R:R + N] = dB.squeeze(1).permute(1, 0, 2).reshape(N, bsz * L)
             dx_dbl[R + N:] = dC.squeeze(1).permute(1, 0, 2).reshape(N, bsz * L)
-        out_z = rest[0] if recompute else kept_out_z
+        out_z = rest[0] if recompute else s.kept_out_z
         dB_proj_bias = dx_dbl[R:R + N].float().sum(1) if has_Bb else None
         dC_proj_bias = dx_dbl[R + N:].float().sum(1) if has_Cb else None
         # "eB,dB->ed": a (d_model, d_inner) output over a b*l-long reduction
         dout_proj_weight = gemm.mm_nn_rows(_rows(out_z), dout.reshape(bsz * L, -1)).t()
         dout_proj_bias = dout.sum(dim=(0, 1)) if has_ob else None
-        ddelta2, conv_rows = _rows(ddelta), _rows(conv_out)                                             # (d, b l) views
-        conv_rows = conv_rows if conv_rows.stride(1) == 1 else conv_rows.contiguous()
-        ddelta_proj_weight = gemm.mm_nt_rows(ddelta2, x_dbl[:R])                                        # "dB,rB->dr", sliced reduction
-        torch.mm(delta_proj_weight.t(), ddelta2, out=dx_dbl[:R])                                        # "dr,dB->rB"
-        dx_proj_weight = gemm.mm_nt_rows(dx_dbl, conv_rows)                                             # "rB,dB->rd", sliced reduction
-        dconv2 = _rows(du)                      # (d, b l) view of the scan's own du: the product is added in place
-        dconv2 = dconv2.addmm_(x_proj_weight.t(), dx_dbl) if dconv2.stride(1) == 1 else torch.addmm(dconv2, x_proj_weight.t(), dx_dbl)
-        dconv_out = dconv2.view(d_inner, bsz, L).permute(1, 0, 2)
-        _, dconv_w, dconv_b = native.causal_conv1d_bwd(x, conv_w, conv_b, dconv_out, dx, True)
+        dx_proj_weight, ddelta_proj_weight, dconv_w, dconv_b = _bwd_tail_t(s, x, conv_out, ddelta, dx_dbl, du, dx)
         return (dxz, dconv_w.unsqueeze(1), dconv_b if has_conv_b else None, dx_proj_weight, ddelta_proj_weight,
                 dout_proj_weight, dout_proj_bias, dA, dA_b, None, None, dD if has_D else None,
                 ddelta_bias if has_dbias else None,
-                dB_proj_bias.to(Bm.dtype) if has_Bb else None, dC_proj_bias.to(Cm.dtype) if has_Cb else None, None, None, None)
+                dB_proj_bias.to(s.Bm.dtype) if has_Bb else None, dC_proj_bias.to(s.Cm.dtype) if has_Cb else None, None, None, None)
 
 
 def bimamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, A_b,
