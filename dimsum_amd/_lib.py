@@ -246,6 +246,17 @@ DECODE_NORM_NONE, DECODE_NORM_LAYER, DECODE_NORM_RMS = 0, 1, 2
 DECODE_MAX_BATCH = 16
 
 
+class CrossEntropyParams(_Sized):
+    """dimsum_cross_entropy_params_t: the LM loss over rows of logits (fwd) and its gradient, optionally in place (bwd)"""
+    _fields_ = ([("struct_size", u32), ("dtype", i32)]
+                + [(n, i64) for n in ("rows", "vocab", "logits_row_stride", "dlogits_row_stride", "dloss_stride", "ignore_index")]
+                + [(n, f32) for n in ("label_smoothing", "logit_scale", "lse_square_scale")] + [("reserved", i32)]
+                + [(n, vp) for n in ("logits_ptr", "labels_ptr", "dloss_ptr", "loss_ptr", "lse_ptr", "z_loss_ptr", "dlogits_ptr")])
+
+
+CROSS_ENTROPY_WAVE_ROW_MAX = 4096        # kCeWaveRowMax: a row of up to this many logits is one wave's, a longer one a workgroup's
+
+
 class NormParams(_Sized):
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("rows", "cols", "is_rms_norm", "x_dtype", "residual_dtype", "out_dtype")]
                 + [("eps", f32)]
@@ -403,7 +414,7 @@ EXPORTS = (
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
     "dimsum_einfft_dft", "dimsum_einfft_idft_real", "dimsum_einfft_mlp_fwd", "dimsum_einfft_mlp_bwd",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd", "dimsum_causal_conv1d_update", "dimsum_selective_state_update",
-    "dimsum_decode_linear",
+    "dimsum_decode_linear", "dimsum_cross_entropy_fwd", "dimsum_cross_entropy_bwd",
     "dimsum_causal_conv1d_cl_fwd", "dimsum_causal_conv1d_cl_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
@@ -438,7 +449,8 @@ _SIGNATURES = (
         ("dimsum_moe_gemm_f16s", MoeGemmF16sParams), ("dimsum_moe_permute_f16s", MoePermuteF16sParams), ("dimsum_moe_act_fwd_f16s", MoeActF16sParams),
         ("dimsum_causal_conv1d_cl_fwd", ConvClParams), ("dimsum_causal_conv1d_cl_bwd", ConvClBwdParams),
         ("dimsum_ssm_scan_carry_fwd", SsmCarryParams), ("dimsum_causal_conv1d_chunk", ConvChunkParams),
-        ("dimsum_decode_linear", DecodeLinearParams))]
+        ("dimsum_decode_linear", DecodeLinearParams), ("dimsum_cross_entropy_fwd", CrossEntropyParams),
+        ("dimsum_cross_entropy_bwd", CrossEntropyParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

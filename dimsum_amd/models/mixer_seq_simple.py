@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from .. import native
 from ..modules.mamba_simple import Block, Mamba, fused_decode_enabled
+from ..ops.cross_entropy import linear_cross_entropy
 from ..ops.layernorm import RMSNorm, layer_norm_fn
 from ..utils.generation import GenerationMixin
 
@@ -132,6 +133,19 @@ class MambaLMHeadModel(nn.Module, GenerationMixin):
         if num_last_tokens > 0:
             hidden_states = hidden_states[:, -num_last_tokens:]
         return CausalLMOutput(logits=self.lm_head(hidden_states))
+
+    def loss(self, input_ids, labels=None, *, chunk_rows=4096, ignore_index=-100, label_smoothing=0.0, lse_square_scale=0.0, reduction="mean"):
+        """-> the scalar training loss (no reference counterpart as a method: its recipes run a fused cross-entropy on forward()'s logits).
+        The backbone, then the head product and the cross-entropy chunk_rows tokens at a time on csrc/cross_entropy.hip
+        (ops.linear_cross_entropy): the (batch * seqlen, vocab) logits never exist. labels (batch, seqlen) int64, ignore_index where a
+        position does not count; None = next-token prediction: input_ids shifted left, the last position ignored. Only the first
+        config["vocab_size"] rows of lm_head.weight are classes: the vocabulary padding takes no part and gets a zero gradient."""
+        hidden_states = self.backbone(input_ids)
+        if labels is None:
+            labels = torch.cat([input_ids[:, 1:], input_ids.new_full((input_ids.shape[0], 1), ignore_index)], dim=1)
+        return linear_cross_entropy(hidden_states, self.lm_head.weight, labels, self.lm_head.bias, chunk_rows=chunk_rows, reduction=reduction,
+                                    vocab_size=self.config["vocab_size"], label_smoothing=label_smoothing, lse_square_scale=lse_square_scale,
+                                    ignore_index=ignore_index)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name, device=None, dtype=None, **kwargs):

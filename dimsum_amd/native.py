@@ -574,7 +574,60 @@ def decode_linear(x, weight, bias=None, norm=None, residual=None, residual_out=N
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# fused add + RMSNorm / LayerNorm   (Triton _layer_norm_fwd / _layer_norm_bwd, ops/triton/layernorm.py:120-364)
+# the LM loss over rows of logits   (csrc/cross_entropy.hip; the reference's training recipes use a fused cross-entropy here)
+# ---------------------------------------------------------------------------------------------------------------------
+def _cross_entropy_params(logits, labels, label_smoothing, logit_scale, lse_square_scale, ignore_index, what):
+    _check(logits.dim() == 2 and logits.dtype in _DT and logits.shape[0] >= 1 and logits.shape[1] >= 1,
+           f"{what}: logits must be (rows >= 1, vocab >= 1) in float32, float16 or bfloat16")
+    M, V = logits.shape
+    _check(logits.stride(1) == 1 and (M == 1 or logits.stride(0) >= V),
+           f"{what}: logits must have unit column stride and a row stride >= vocab (a [..., :vocab] view of a padded buffer is fine)")
+    _check(tuple(labels.shape) == (M,) and labels.dtype == torch.int64, f"{what}: labels must be (rows,) int64")
+    _check(0.0 <= float(label_smoothing) < 1.0, f"{what}: label_smoothing must be in [0, 1)")
+    P = _lib.CrossEntropyParams()
+    P.dtype, P.rows, P.vocab, P.logits_row_stride = _DT[logits.dtype], M, V, max(logits.stride(0), V)
+    P.ignore_index, P.label_smoothing, P.logit_scale, P.lse_square_scale = int(ignore_index), float(label_smoothing), float(logit_scale), float(lse_square_scale)
+    return P
+
+
+def cross_entropy_fwd(logits, labels, label_smoothing=0.0, logit_scale=1.0, lse_square_scale=0.0, ignore_index=-100):
+    """-> (loss, lse, z_loss), each (rows,); loss and z_loss float32, lse float64 (what the backward needs to form exp(s - lse) to fp32 accuracy
+    under any row offset): with s = logit_scale * logits[m, :], lse = logsumexp(s), z_loss = lse_square_scale * lse^2,
+    loss = lse - (1 - label_smoothing) s[label] - (label_smoothing / vocab) sum(s) + z_loss, in ONE read of the logits.
+    logits (rows, vocab) float32 / float16 / bfloat16, unit column stride, any row stride >= vocab; labels (rows,) int64.
+    label == ignore_index: loss = z_loss = 0; another label outside [0, vocab): loss = NaN."""
+    P = _cross_entropy_params(logits, labels, label_smoothing, logit_scale, lse_square_scale, ignore_index, "cross_entropy_fwd")
+    _gpu(logits, labels)
+    labels = labels.contiguous()
+    loss, z_loss = (torch.empty(logits.shape[0], device=logits.device, dtype=torch.float32) for _ in range(2))
+    lse = torch.empty(logits.shape[0], device=logits.device, dtype=torch.float64)
+    P.logits_ptr, P.labels_ptr, P.loss_ptr, P.lse_ptr, P.z_loss_ptr = _ptr(logits), _ptr(labels), _ptr(loss), _ptr(lse), _ptr(z_loss)
+    with torch.cuda.device(logits.device):
+        _lib.check(_lib.load().dimsum_cross_entropy_fwd(P, _stream(logits)), "cross_entropy_fwd")
+    return loss, lse, z_loss
+
+
+def cross_entropy_bwd(dloss, logits, lse, labels, label_smoothing=0.0, logit_scale=1.0, lse_square_scale=0.0, ignore_index=-100, inplace=False):
+    """-> dlogits (rows, vocab) of the logits' dtype: dloss[m] * logit_scale * ((1 + 2 lse_square_scale lse) softmax(s) - (1 - label_smoothing)
+    onehot(label) - label_smoothing / vocab), one read and one write of the logits from the forward's lse. dloss (rows,) float32 with any
+    stride >= 0 (an expanded scalar is read in place). inplace: the gradient replaces the logits and the returned tensor IS `logits`.
+    A row with label == ignore_index is zeros; with another label outside [0, vocab) it is NaN."""
+    P = _cross_entropy_params(logits, labels, label_smoothing, logit_scale, lse_square_scale, ignore_index, "cross_entropy_bwd")
+    M, V = logits.shape
+    _check(tuple(dloss.shape) == (M,) and dloss.dtype == torch.float32 and dloss.stride(0) >= 0, "cross_entropy_bwd: dloss must be (rows,) float32")
+    _check(tuple(lse.shape) == (M,) and lse.dtype == torch.float64, "cross_entropy_bwd: lse must be (rows,) float64, as cross_entropy_fwd returns it")
+    _gpu(dloss, logits, lse, labels)
+    labels, lse = labels.contiguous(), lse.contiguous()
+    dlogits = logits if inplace else torch.empty((M, V), device=logits.device, dtype=logits.dtype)
+    P.dlogits_row_stride, P.dloss_stride = max(dlogits.stride(0), V), dloss.stride(0)
+    P.logits_ptr, P.labels_ptr, P.lse_ptr, P.dloss_ptr, P.dlogits_ptr = _ptr(logits), _ptr(labels), _ptr(lse), _ptr(dloss), _ptr(dlogits)
+    with torch.cuda.device(logits.device):
+        _lib.check(_lib.load().dimsum_cross_entropy_bwd(P, _stream(logits)), "cross_entropy_bwd")
+    return dlogits
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# fused add + RMSNorm / LayerNorm  (Triton _layer_norm_fwd / _layer_norm_bwd, ops/triton/layernorm.py:120-364)
 # ---------------------------------------------------------------------------------------------------------------------
 def layer_norm_fwd(x, weight, bias, eps, residual=None, out_dtype=None, residual_dtype=None, is_rms_norm=False,
                    x_bias=None, mod_scale=None, mod_shift=None, rows_per_batch=0, split3=False):

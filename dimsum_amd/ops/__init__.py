@@ -6,6 +6,7 @@ from .causal_conv1d_interface import (  # noqa: F401
     causal_conv1d_update,
     causal_conv1d_update_torch,
 )
+from .cross_entropy import CrossEntropyLoss, cross_entropy_loss, cross_entropy_torch, linear_cross_entropy  # noqa: F401
 from .layernorm import RMSNorm, layer_norm_fn, rms_norm_fn  # noqa: F401
 from .moe import moe_act, moe_act_torch, switch_mlp_fn, switch_mlp_torch  # noqa: F401
 from .selective_scan_interface import (  # noqa: F401

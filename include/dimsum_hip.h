@@ -763,6 +763,41 @@ typedef struct {
 
 int dimsum_decode_linear(const dimsum_decode_linear_params_t *p, void *stream);
 
+/* dimsum_cross_entropy_fwd / _bwd: the LM training loss over rows of logits and its gradient (csrc/cross_entropy.hip; the reference's training
+ * recipes use a fused cross-entropy in this place). Per row m, with s = logit_scale * logits[m, :] and eps = label_smoothing:
+ *     lse = logsumexp(s)      z = lse_square_scale * lse^2      loss = lse - (1 - eps) s[label] - (eps / vocab) sum(s) + z
+ *     dlogits[m, v] = dloss[m] * logit_scale * ((1 + 2 lse_square_scale lse) exp(s_v - lse) - (1 - eps) [v == label] - eps / vocab)
+ *   logits (rows, vocab) of `dtype`, unit column stride, any row stride >= vocab (a [..., :vocab] view of a padded buffer is read in place:
+ *   nothing beyond column vocab - 1 of a row is read or written); no alignment is asked of the base (rows that start 16-byte aligned move in
+ *   16-byte pieces, others element by element, with the same bits). labels (rows) int64; loss, z_loss (rows) f32, lse (rows) f64, contiguous;
+ *   z_loss may be NULL. lse is a double so that the backward's exp(s_v - lse) keeps fp32 accuracy whatever the row's offset (an fp32 lse of
+ *   80 is known to 4e-6 only, and so would be every probability). Row offsets are 64-bit.
+ *   label == ignore_index: loss = z_loss = 0 and a zero gradient row; lse is still written. Any other label outside [0, vocab): loss = NaN
+ *   and a NaN gradient row; nothing outside the row is touched.
+ *   fwd reads logits, labels; writes loss, lse, z_loss. bwd reads logits, labels, lse, dloss ((rows) f32, any element stride >= 0: 0 is an
+ *   expanded scalar); writes dlogits (rows, vocab) of `dtype` with row stride dlogits_row_stride >= vocab. dlogits may BE logits (equal
+ *   pointers and equal row strides: the in-place backward); any other overlap of the two is DIMSUM_ERR_ALIAS.
+ *   No atomics; the summation order depends on vocab and dtype alone: two launches on equal inputs are bit-identical, and a row's results do
+ *   not depend on `rows` or on the row's index.
+ * Checks, in this order: NULL struct / struct_size (DIMSUM_ERR_ABI) / required pointers (logits, labels, lse; fwd: loss; bwd: dloss, dlogits) /
+ * shape (rows in [1, 2^31), vocab in [1, 2^31 - 16)) / dtype / strides (logits_row_stride < vocab; bwd: dlogits_row_stride < vocab,
+ * dloss_stride < 0) / bwd: dlogits overlapping logits other than in place (DIMSUM_ERR_ALIAS) / unsupported (label_smoothing outside [0, 1),
+ * a non-finite logit_scale or lse_square_scale). Nothing is launched before all of them pass. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_cross_entropy_params_t) as the caller compiled it; anything else -> DIMSUM_ERR_ABI */
+    int32_t dtype;            /* of logits and dlogits */
+    int64_t rows, vocab;
+    int64_t logits_row_stride, dlogits_row_stride, dloss_stride;
+    int64_t ignore_index;
+    float label_smoothing, logit_scale, lse_square_scale;
+    int32_t reserved;         /* 0 */
+    const void *logits_ptr, *labels_ptr, *dloss_ptr;
+    void *loss_ptr, *lse_ptr, *z_loss_ptr, *dlogits_ptr;     /* lse: written by fwd, read by bwd */
+} dimsum_cross_entropy_params_t;
+
+int dimsum_cross_entropy_fwd(const dimsum_cross_entropy_params_t *p, void *stream);
+int dimsum_cross_entropy_bwd(const dimsum_cross_entropy_params_t *p, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused residual-add + RMSNorm / LayerNorm over rows (M, N), f32 statistics.
  *   r = x (+ x_bias) (+ residual) ; residual_out = r (if residual_out_ptr) ; y = norm(r) * weight (+ bias)
