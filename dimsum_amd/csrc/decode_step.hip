@@ -22,6 +22,9 @@
 //     to its share of the weights. One workgroup per group of rows; no grid-stride loop.
 //   * Prologue: every workgroup recomputes the `batch` row statistics (fp32, two passes for LayerNorm as csrc/norm.hip) from x (+ residual) in
 //     L2; workgroup 0 alone writes residual_out. The host refuses a residual_out that overlaps x or residual (other workgroups still read them).
+//     LayerNorm's second pass also sums r - mean: the mean of a K-term fp32 sum is off by an ulp or two of ITSELF, which on rows far from
+//     zero (mean 64, unit spread) is 1e-5 of the spread and shifts every x' alike; r - mean is exact there, so sum(r - mean) / K recovers what
+//     the mean lost, and x' = ((r - mean) - corr) * rstd, var = mean(d^2) - corr^2. RMSNorm has mean = corr = 0: its arithmetic is unchanged.
 //   * Epilogue: the lane holding y[b, n], n < conv_dim, rolls conv_state[b, n, :], appends y rounded to T and computes
 //     act(bias_c[n] + sum_w Wc[n, w] state[w]) with the expressions of causal_conv1d_update_kernel. Only that lane touches that state row.
 #include "common.hpp"
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(kMaxThreads) void decode_linear_kernel(const dimsum
     constexpr int kChunk = kChunkPieces * E;                // elements of K per chunk
     constexpr int V = kRows * kBatch;
     __shared__ u32x4 xs[kBatch * kChunkPieces];
-    __shared__ float s_mean[kMaxBatch], s_rstd[kMaxBatch];
+    __shared__ float s_mean[kMaxBatch], s_corr[kMaxBatch], s_rstd[kMaxBatch];
     T *xs_t = reinterpret_cast<T *>(xs);
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -142,20 +145,23 @@ __global__ __launch_bounds__(kMaxThreads) void decode_linear_kernel(const dimsum
                 s += rms ? r * r : r;
             }
             s = wave_sum_all(s);
-            float mean = 0.f, var;
+            float mean = 0.f, corr = 0.f, var;
             if (rms) {
                 var = s * inv_k;
             } else {
                 mean = s * inv_k;
-                float v2 = 0.f;
+                float v1 = 0.f, v2 = 0.f;
                 for (int k = lane; k < K; k += kWave) {
                     const float d = stream_value<T>(p, b, k) - mean;
+                    v1 += d;
                     v2 += d * d;
                 }
-                var = wave_sum_all(v2) * inv_k;
+                corr = wave_sum_all(v1) * inv_k;     // what the rounded K-term sum left of the mean: rows far from zero (see the header)
+                var = fmaxf(wave_sum_all(v2) * inv_k - corr * corr, 0.f);
             }
             if (lane == 0) {
                 s_mean[b] = mean;
+                s_corr[b] = corr;
                 s_rstd[b] = 1.0f / sqrtf(var + p.eps);
             }
         }
@@ -199,7 +205,7 @@ __global__ __launch_bounds__(kMaxThreads) void decode_linear_kernel(const dimsum
                     if (b < B) {
                         v = stream_value<T>(p, b, k0 + k);
                         if (p.norm) {
-                            v = (v - s_mean[b]) * s_rstd[b] * to_f32<T>(nw[k0 + k]);
+                            v = ((v - s_mean[b]) - s_corr[b]) * s_rstd[b] * to_f32<T>(nw[k0 + k]);
                             if (nb) v += to_f32<T>(nb[k0 + k]);
                         }
                     }

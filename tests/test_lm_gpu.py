@@ -62,6 +62,8 @@ def test_decode_linear_against_float64(shape, dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=str)
 def test_two_launches_are_bit_identical_and_rows_do_not_depend_on_the_grid(dtype):
+    """of the grid, only the batch tile varies here; the same rows on 1 / 4 / 8 waves and under one and four rows per wave are
+    test_decode_paths_gpu.py::test_rows_do_not_depend_on_the_grid"""
     from dimsum_amd import native
     for N, K in ((1001, 128), (96, 260), (16389, 40)):
         x, w, b = linear_case(16, N, K, dtype, seed=3)
