@@ -257,6 +257,13 @@ class CrossEntropyParams(_Sized):
 CROSS_ENTROPY_WAVE_ROW_MAX = 4096        # kCeWaveRowMax: a row of up to this many logits is one wave's, a longer one a workgroup's
 
 
+class SampleLogitsParams(_Sized):
+    """dimsum_sample_logits_params_t: one token per row of logits under top-k / top-p / temperature, drawn with the caller's uniforms"""
+    _fields_ = ([("struct_size", u32), ("dtype", i32)] + [(n, i64) for n in ("rows", "vocab", "logits_row_stride")]
+                + [("top_k", i32), ("top_p", f32), ("temperature", f32), ("reserved", i32)]
+                + [(n, vp) for n in ("logits_ptr", "u_ptr", "out_ptr", "row_index_ptr", "out_table_ptr")] + [("table_steps", i64)])
+
+
 class NormParams(_Sized):
     _fields_ = ([("struct_size", u32)] + [(n, i32) for n in ("rows", "cols", "is_rms_norm", "x_dtype", "residual_dtype", "out_dtype")]
                 + [("eps", f32)]
@@ -414,7 +421,7 @@ EXPORTS = (
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
     "dimsum_einfft_dft", "dimsum_einfft_idft_real", "dimsum_einfft_mlp_fwd", "dimsum_einfft_mlp_bwd",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd", "dimsum_causal_conv1d_update", "dimsum_selective_state_update",
-    "dimsum_decode_linear", "dimsum_cross_entropy_fwd", "dimsum_cross_entropy_bwd",
+    "dimsum_decode_linear", "dimsum_cross_entropy_fwd", "dimsum_cross_entropy_bwd", "dimsum_sample_logits",
     "dimsum_causal_conv1d_cl_fwd", "dimsum_causal_conv1d_cl_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
@@ -450,7 +457,7 @@ _SIGNATURES = (
         ("dimsum_causal_conv1d_cl_fwd", ConvClParams), ("dimsum_causal_conv1d_cl_bwd", ConvClBwdParams),
         ("dimsum_ssm_scan_carry_fwd", SsmCarryParams), ("dimsum_causal_conv1d_chunk", ConvChunkParams),
         ("dimsum_decode_linear", DecodeLinearParams), ("dimsum_cross_entropy_fwd", CrossEntropyParams),
-        ("dimsum_cross_entropy_bwd", CrossEntropyParams))]
+        ("dimsum_cross_entropy_bwd", CrossEntropyParams), ("dimsum_sample_logits", SampleLogitsParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

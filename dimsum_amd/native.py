@@ -627,6 +627,54 @@ def cross_entropy_bwd(dloss, logits, lse, labels, label_smoothing=0.0, logit_sca
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the token sampler of the decode loop   (csrc/sample_logits.hip; the reference's sample(), utils/generation.py:55-80, in one launch)
+# ---------------------------------------------------------------------------------------------------------------------
+def sample_logits(logits, u, top_k=1, top_p=0.0, temperature=1.0, out=None, row_index=None, out_table=None):
+    """-> tokens (rows,) int64 (`out` when given): one token per row of logits (rows, vocab) float32 / float16 / bfloat16, unit column stride,
+    any row stride >= vocab. top_k == 1: argmax (the lowest index among equal maxima; u may be None). Otherwise among the top_k highest
+    ranks (top_k <= 0 or >= vocab: all; equal logits rank by ascending index), then without the tokens whose higher-ranked mass is
+    >= top_p (0 < top_p < 1), p ~ exp((l - max) / temperature), by the inverse CDF in ascending index at the row's uniform: u[r], u (rows,)
+    float32 -- or, with row_index (a one-element int64 DEVICE tensor holding a step number), u[step, r] of u (steps, rows); out_table
+    (steps, rows) int64 then also receives the token at [step, r]. The kernel draws no random numbers; every value written is in [0, vocab)."""
+    _check(logits.dim() == 2 and logits.dtype in _DT and logits.shape[0] >= 1 and logits.shape[1] >= 1,
+           "sample_logits: logits must be (rows >= 1, vocab >= 1) in float32, float16 or bfloat16")
+    M, V = logits.shape
+    _check(logits.stride(1) == 1 and (M == 1 or logits.stride(0) >= V),
+           "sample_logits: logits must have unit column stride and a row stride >= vocab (a [..., :vocab] view of a padded buffer is fine)")
+    temperature = float(temperature)
+    _check(temperature > 0.0 and temperature != float("inf"), "sample_logits: temperature must be finite and > 0")
+    top_k = int(top_k)
+    _check(-2 ** 31 <= top_k < 2 ** 31, "sample_logits: top_k must fit 32 bits")
+    steps = 0
+    if row_index is not None:
+        _check(row_index.dtype == torch.int64 and row_index.numel() == 1, "sample_logits: row_index must be one int64 on the device")
+        _check(u is not None and u.dim() == 2, "sample_logits: with row_index, u must be (steps, rows)")
+        steps = u.shape[0]
+    else:
+        _check(out_table is None, "sample_logits: out_table needs row_index")
+    if u is not None:
+        _check(u.dtype == torch.float32 and u.is_contiguous() and tuple(u.shape) == ((steps, M) if row_index is not None else (M,)),
+               "sample_logits: u must be contiguous float32, (rows,) or with row_index (steps, rows)")
+    else:
+        _check(top_k == 1, "sample_logits: only top_k == 1 draws nothing: u is required")
+    if out_table is not None:
+        _check(out_table.dtype == torch.int64 and out_table.is_contiguous() and tuple(out_table.shape) == (steps, M),
+               "sample_logits: out_table must be contiguous int64 (steps, rows), as u")
+    if out is None:
+        out = torch.empty(M, device=logits.device, dtype=torch.int64)
+    else:
+        _check(out.dtype == torch.int64 and out.numel() == M and out.is_contiguous(), "sample_logits: out must be contiguous int64 with one element per row")
+    _gpu(logits, u, out, row_index, out_table)
+    P = _lib.SampleLogitsParams()
+    P.dtype, P.rows, P.vocab, P.logits_row_stride = _DT[logits.dtype], M, V, max(logits.stride(0), V)
+    P.top_k, P.top_p, P.temperature, P.table_steps = top_k, float(top_p), temperature, steps
+    P.logits_ptr, P.u_ptr, P.out_ptr, P.row_index_ptr, P.out_table_ptr = _ptr(logits), _ptr(u), _ptr(out), _ptr(row_index), _ptr(out_table)
+    with torch.cuda.device(logits.device):
+        _lib.check(_lib.load().dimsum_sample_logits(P, _stream(logits)), "sample_logits")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # fused add + RMSNorm / LayerNorm  (Triton _layer_norm_fwd / _layer_norm_bwd, ops/triton/layernorm.py:120-364)
 # ---------------------------------------------------------------------------------------------------------------------
 def layer_norm_fwd(x, weight, bias, eps, residual=None, out_dtype=None, residual_dtype=None, is_rms_norm=False,

@@ -4,16 +4,20 @@ of mamba/mamba_ssm/utils/generation.py, minus `transformers`: `generate(return_d
 
 cg=True: one decode step (the model's forward on a (batch, 1) token buffer at seqlen_offset > 0) is captured per batch size into a hipGraph,
 on the capture's single stream -- the step has no parallel branches -- after warm-up runs on a side stream, and replayed from static buffers;
-sampling stays outside the graph. The cache (states, graphs) hangs on the model as `_decoding_cache` and is reused by later calls that fit it.
+sampling stays outside the graph unless fused sampling is asked for (`fused_sampling=` / DIMSUM_FUSED_SAMPLING=1, off by default): the sampler
+is then ONE launch of csrc/sample_logits.hip per token on a table of uniforms drawn once per call, and under cg=True it is part of the
+captured step, which writes the token straight into its own input buffer: a token is one graph replay. The cache (states, graphs) hangs on the model as `_decoding_cache` and is reused by later calls that fit it.
 `decode` and the capture run under torch.no_grad(), not the reference's inference_mode: a capture begun in inference mode makes the generator's
 graph-safe state inference tensors, and every later capture of the process outside inference mode then fails on their in-place update."""
 import dataclasses
 import gc
+import os
 from typing import Callable, Optional
 
 import torch
 
 from . import InferenceParams
+from .. import native
 
 
 @dataclasses.dataclass
@@ -59,12 +63,91 @@ def sample(logits, top_k=1, top_p=0.0, temperature=1.0, generator=None):
     return torch.multinomial(torch.softmax(logits_top, dim=-1), num_samples=1, generator=generator).squeeze(dim=-1)
 
 
+def sample_fused(logits, u, top_k=1, top_p=0.0, temperature=1.0):
+    """`sample` in one launch of csrc/sample_logits.hip: logits (batch, vocab) -> token ids (batch,), with the argument meanings of `sample`
+    and u (batch,) float32 uniforms in [0, 1) in the place of `generator`: the token is a pure function of (logits, top_k, top_p, temperature,
+    u). Same distribution as `sample`; equal logits rank by ascending index (include/dimsum_hip.h, dimsum_sample_logits)."""
+    return native.sample_logits(logits, u, top_k=top_k, top_p=top_p, temperature=temperature)
+
+
+def fused_sampling_enabled(fused_sampling=None):
+    """the argument when given; else DIMSUM_FUSED_SAMPLING, read at call time: 1 = on, anything else (and unset) = off"""
+    if fused_sampling is not None:
+        return bool(fused_sampling)
+    return os.environ.get("DIMSUM_FUSED_SAMPLING", "") == "1"
+
+
+def _decode_fused(input_ids, model, max_length, top_k, top_p, temperature, eos_token_id, vocab_size, cg, generator, uniforms, output_scores):
+    """`decode` on the fused sampler. uniforms (max_length, batch): row i draws the i-th new token. Eager: one sample_logits launch per token
+    on the step's row. cg: the captured step samples from its own logits into its own input buffer and files the token in the cache's token
+    table at the cache's step counter; the host only replays (and reads the newest token when it has to look for eos_token_id)."""
+    batch_size, seqlen_og = input_ids.shape
+    device = input_ids.device
+    if uniforms is None:
+        uniforms = torch.rand((max_length, batch_size), device=device, dtype=torch.float32, generator=generator)
+    elif tuple(uniforms.shape) != (max_length, batch_size) or uniforms.dtype != torch.float32:
+        raise ValueError(f"decode: uniforms must be (max_length, batch) = ({max_length}, {batch_size}) float32, got {tuple(uniforms.shape)} {uniforms.dtype}")
+    kw = dict(top_k=top_k, top_p=top_p, temperature=temperature)
+    if cg:
+        sampling = (int(top_k), float(top_p), float(temperature), vocab_size)
+        cache = model._decoding_cache = update_graph_cache(model, getattr(model, "_decoding_cache", None), batch_size, seqlen_og, max_length,
+                                                           sampling=sampling)
+        inference_params = cache.params_for(batch_size)
+        inference_params.reset(max_length, batch_size)
+        step = cache.callables[(batch_size, 1) + sampling]
+        table, counter, tokens = cache.sampling_buffers(batch_size)
+        table[:max_length].copy_(uniforms)
+        counter.zero_()
+        tokens.zero_()
+    else:
+        inference_params = InferenceParams(max_seqlen=max_length, max_batch_size=batch_size)
+        table = uniforms.to(device).contiguous()
+        tokens = torch.zeros((max_length, batch_size), dtype=torch.long, device=device)
+    scores, n = [], 0
+    while True:
+        if n == 0:
+            logits = model(input_ids, inference_params=inference_params, num_last_tokens=1).logits[:, -1]
+        elif cg:
+            logits = step()[:, -1]                          # forward, sample, count: tokens[n] and the next input are in place
+        else:
+            logits = model(tokens[n - 1].unsqueeze(1), inference_params=inference_params, num_last_tokens=1).logits[:, -1]
+        inference_params.seqlen_offset += seqlen_og if n == 0 else 1
+        view = logits[..., :vocab_size] if vocab_size is not None else logits     # a view: the row stride limits the classes
+        if output_scores:
+            scores.append(view.clone() if cg and n > 0 else view)                 # the graph's logits are a static buffer
+        if cg and n == 0:
+            native.sample_logits(view, table, out=step.input_ids, row_index=counter, out_table=tokens, **kw)
+            counter.add_(1)
+        elif not cg:
+            native.sample_logits(view, table[n], out=tokens[n], **kw)
+        n += 1
+        if eos_token_id is not None and bool((tokens[n - 1] == eos_token_id).all()):
+            break
+        if inference_params.seqlen_offset >= max_length - 1:
+            break
+    return GenerationOutput(sequences=torch.cat([input_ids, tokens[:n].t()], dim=1), scores=tuple(scores))
+
+
 @torch.no_grad()
 def decode(input_ids, model, max_length, top_k=1, top_p=0.0, temperature=1.0, eos_token_id=None, teacher_outputs=None, vocab_size=None, cg=False,
-           enable_timing=False, generator=None):
+           enable_timing=False, generator=None, fused_sampling=None, uniforms=None, output_scores=True):
     """greedy / top-k / top-p decoding of input_ids (batch, seqlen), all rows of one length, up to max_length tokens in all; stops early once
     every row's newest token is eos_token_id. teacher_outputs (batch, seqlen'): tokens taken instead of sampled ones (testing).
+    fused_sampling (None: DIMSUM_FUSED_SAMPLING, off when unset): sample with `sample_fused` on a (max_length, batch) float32 table of
+    uniforms -- `uniforms`, or one torch.rand(generator=generator) draw per call -- whose row i draws the i-th new token; with cg=True the
+    sampler is part of the captured step. teacher_outputs keeps the unfused sampler. output_scores=False lets the fused path skip the
+    per-token copy of the logits.
     -> GenerationOutput(sequences (batch, <= max_length), scores: one (batch, vocab) per generated token)"""
+    if teacher_outputs is None and fused_sampling_enabled(fused_sampling):
+        if enable_timing:
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+        out = _decode_fused(input_ids, model, max_length, top_k, top_p, temperature, eos_token_id, vocab_size, cg, generator, uniforms, output_scores)
+        if enable_timing:
+            end.record()
+            torch.cuda.synchronize()
+            print(f"Prompt processing + decoding time: {start.elapsed_time(end):.0f}ms")
+        return out
     batch_size, seqlen_og = input_ids.shape
     teacher_output_len = teacher_outputs.shape[1] if teacher_outputs is not None else 0
     if cg:
@@ -118,8 +201,8 @@ class GenerationMixin:
         raise NotImplementedError
 
     def generate(self, input_ids, max_length, top_k=1, top_p=0.0, temperature=1.0, return_dict_in_generate=False, output_scores=False, **kwargs):
-        """kwargs: cg, eos_token_id, teacher_outputs, vocab_size, enable_timing, generator (see `decode`)"""
-        output = decode(input_ids, self, max_length, top_k=top_k, top_p=top_p, temperature=temperature, **kwargs)
+        """kwargs: cg, eos_token_id, teacher_outputs, vocab_size, enable_timing, generator, fused_sampling, uniforms (see `decode`)"""
+        output = decode(input_ids, self, max_length, top_k=top_k, top_p=top_p, temperature=temperature, output_scores=output_scores, **kwargs)
         if not output_scores:
             output.scores = None
         return output if return_dict_in_generate else output.sequences
@@ -127,7 +210,9 @@ class GenerationMixin:
 
 @dataclasses.dataclass
 class DecodingCGCache:
-    """the states of a model for up to max_batch_size sequences of max_seqlen tokens and one captured decode step per (batch, seqlen 1)"""
+    """the states of a model for up to max_batch_size sequences of max_seqlen tokens and one captured decode step per (batch, seqlen 1) -- and,
+    for fused sampling, per (batch, seqlen 1, top_k, top_p, temperature, vocab_size): the sampler's parameters are baked into its graph node.
+    Those steps share three static buffers: the uniforms, the token table (both (max_seqlen, batch) over one flat allocation) and the step counter."""
     max_batch_size: int = 0
     max_seqlen: int = 0
     device = None
@@ -138,6 +223,14 @@ class DecodingCGCache:
     run: Optional[Callable] = None
     n_captures: int = 0                                     # graphs captured so far (tests count them)
     batch_params: dict = dataclasses.field(default_factory=dict)
+    sample_u: Optional[torch.Tensor] = None                 # (max_seqlen * max_batch_size,) float32
+    sample_tokens: Optional[torch.Tensor] = None            # (max_seqlen * max_batch_size,) int64
+    sample_counter: Optional[torch.Tensor] = None           # (1,) int64: the step the next sample belongs to
+
+    def sampling_buffers(self, batch_size):
+        """-> (uniforms, counter, tokens): the (max_seqlen, batch_size) views that the captured sampling steps of this batch size address"""
+        n = self.max_seqlen * batch_size
+        return self.sample_u[:n].view(self.max_seqlen, batch_size), self.sample_counter, self.sample_tokens[:n].view(self.max_seqlen, batch_size)
 
     def params_for(self, batch_size):
         """the InferenceParams of a batch of this size: the first batch_size rows of every cached state, as views"""
@@ -150,8 +243,9 @@ class DecodingCGCache:
 
 
 @torch.no_grad()
-def update_graph_cache(model, cache, batch_size, seqlen_og, max_seqlen, decoding_seqlens=(1,), dtype=None, n_warmups=2):
-    """-> the cache, (re)allocated when the device, dtype, batch size or length outgrow it, holding a captured step for this batch size"""
+def update_graph_cache(model, cache, batch_size, seqlen_og, max_seqlen, decoding_seqlens=(1,), dtype=None, n_warmups=2, sampling=None):
+    """-> the cache, (re)allocated when the device, dtype, batch size or length outgrow it, holding a captured step for this batch size.
+    sampling = (top_k, top_p, temperature, vocab_size): the step that also samples (fused sampling), keyed apart from the plain one"""
     if cache is None:
         cache = DecodingCGCache()
     param_example = next(iter(model.parameters()))
@@ -162,6 +256,7 @@ def update_graph_cache(model, cache, batch_size, seqlen_og, max_seqlen, decoding
         cache.callables, cache.batch_params = {}, {}      # the graphs hold the old states' addresses: drop them with the states
         cache.mempool = None
         cache.inference_params = None
+        cache.sample_u = cache.sample_tokens = cache.sample_counter = None
         gc.collect()
         cache.device, cache.dtype = device, dtype
         cache.max_batch_size, cache.max_seqlen = batch_size, max_seqlen
@@ -169,11 +264,17 @@ def update_graph_cache(model, cache, batch_size, seqlen_og, max_seqlen, decoding
         cache.inference_params = InferenceParams(max_seqlen=max_seqlen, max_batch_size=batch_size, seqlen_offset=seqlen_og,
                                                  key_value_memory_dict=inf_cache)
         cache.mempool = torch.cuda.graphs.graph_pool_handle()
+    if sampling is not None and cache.sample_u is None:
+        n = cache.max_seqlen * cache.max_batch_size
+        cache.sample_u = torch.zeros(n, dtype=torch.float32, device=device)
+        cache.sample_tokens = torch.zeros(n, dtype=torch.long, device=device)
+        cache.sample_counter = torch.zeros(1, dtype=torch.long, device=device)
     for decoding_seqlen in decoding_seqlens:
-        if (batch_size, decoding_seqlen) not in cache.callables:
-            cache.callables[batch_size, decoding_seqlen] = capture_graph(model, cache.params_for(batch_size), batch_size, max_seqlen,
-                                                                         decoding_seqlen=decoding_seqlen, mempool=cache.mempool,
-                                                                         n_warmups=n_warmups)
+        key = (batch_size, decoding_seqlen) + (tuple(sampling) if sampling is not None else ())
+        if key not in cache.callables:
+            cache.callables[key] = capture_graph(model, cache.params_for(batch_size), batch_size, max_seqlen, decoding_seqlen=decoding_seqlen,
+                                                 mempool=cache.mempool, n_warmups=n_warmups, sampling=sampling,
+                                                 sampling_buffers=cache.sampling_buffers(batch_size) if sampling is not None else None)
             cache.n_captures += 1
 
     def dispatch(input_ids, seqlen):
@@ -184,12 +285,31 @@ def update_graph_cache(model, cache, batch_size, seqlen_og, max_seqlen, decoding
     return cache
 
 
-def capture_graph(model, inference_params, batch_size, max_seqlen, decoding_seqlen=1, mempool=None, n_warmups=2):
+def capture_graph(model, inference_params, batch_size, max_seqlen, decoding_seqlen=1, mempool=None, n_warmups=2, sampling=None,
+                  sampling_buffers=None):
     """one forward of the model on a static (batch_size, decoding_seqlen) token buffer at seqlen_offset > 0, captured -> run(new_input_ids,
     seqlen) that copies the tokens in, replays and returns a copy of the logits. The warm-up runs (library handles, the allocator's blocks) go
-    to a side stream before the capture; the capture itself records on one stream."""
+    to a side stream before the capture; the capture itself records on one stream.
+    sampling = (top_k, top_p, temperature, vocab_size) with sampling_buffers = (uniforms, counter, tokens): the step goes on, on the same
+    stream, with sample_logits on its own logits at the counter's step -- the token lands in the static token buffer (the next replay's
+    input) and in `tokens` -- and counter += 1 -> step() that only replays and returns the static logits (no copy in, no clone);
+    step.input_ids is the static token buffer, for the caller to put the first token in."""
     device = next(iter(model.parameters())).device
     input_ids = torch.full((batch_size, decoding_seqlen), 0, dtype=torch.long, device=device)
+    if sampling is not None:
+        assert decoding_seqlen == 1, "a step that samples feeds itself: one token per row"
+        top_k, top_p, temperature, vocab_size = sampling
+        table, counter, tokens = sampling_buffers
+
+    def forward():
+        logits = model(input_ids, inference_params=inference_params, num_last_tokens=decoding_seqlen).logits
+        if sampling is not None:
+            last = logits[:, -1]
+            native.sample_logits(last[..., :vocab_size] if vocab_size is not None else last, table, top_k=top_k, top_p=top_p,
+                                 temperature=temperature, out=input_ids, row_index=counter, out_table=tokens)
+            counter.add_(1)
+        return logits
+
     seqlen_offset_og = inference_params.seqlen_offset
     inference_params.seqlen_offset = max_seqlen - decoding_seqlen
     assert inference_params.seqlen_offset > 0, "a decode step is captured at seqlen_offset > 0: max_seqlen must exceed the step's length"
@@ -197,17 +317,22 @@ def capture_graph(model, inference_params, batch_size, max_seqlen, decoding_seql
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
         for _ in range(n_warmups):
-            logits = model(input_ids, inference_params=inference_params, num_last_tokens=decoding_seqlen).logits
+            logits = forward()
         s.synchronize()
     torch.cuda.current_stream().wait_stream(s)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph, pool=mempool):
-        logits = model(input_ids, inference_params=inference_params, num_last_tokens=decoding_seqlen).logits
+        logits = forward()
 
     def run(new_input_ids, seqlen):
         input_ids.copy_(new_input_ids)
         graph.replay()
         return logits.clone()
 
+    def step():
+        graph.replay()
+        return logits
+
+    step.input_ids = input_ids
     inference_params.seqlen_offset = seqlen_offset_og
-    return run
+    return run if sampling is None else step

@@ -798,6 +798,48 @@ typedef struct {
 int dimsum_cross_entropy_fwd(const dimsum_cross_entropy_params_t *p, void *stream);
 int dimsum_cross_entropy_bwd(const dimsum_cross_entropy_params_t *p, void *stream);
 
+/* dimsum_sample_logits: one token id per row of logits under top-k / top-p / temperature, drawn with a uniform number the caller supplies
+ * (csrc/sample_logits.hip; the distribution of the reference's sample(), mamba_ssm/utils/generation.py:55-80, stated without a sort). Nothing
+ * in the kernel generates random numbers: out[r] is a pure function of (logits[r, :], top_k, top_p, temperature, u of the row).
+ *   RANK: the tokens of a row by descending logit; equal logits rank by ascending index (torch.topk / sort leave this open). NaN counts as
+ *   -inf, -0 as +0.
+ *   top_k == 1: the rank-0 token (argmax, the lowest index among equal maxima); u is not read and may be NULL.
+ *   Otherwise the KEPT set starts as the top_k highest ranks; top_k <= 0 or >= vocab: all tokens. Inside it p_v ~ exp((l_v - max) / temperature).
+ *   With 0 < top_p < 1 a token is then dropped iff the kept-set probability mass of the tokens ranked strictly above it is >= top_p (the
+ *   reference's "ascending inclusive cumulative sum <= 1 - top_p is removed", restated from the top); top_p outside (0, 1): no cut.
+ *   DRAW: the inverse CDF over the kept tokens in ascending vocabulary index (not rank order: the distribution does not depend on the order):
+ *   the first kept v whose running mass exceeds u * Z, Z the kept mass; u is clamped into [0, 1) (NaN -> 0).
+ *   -inf logits have probability 0 and are never returned while the row has a finite logit; a row with none yields token 0.
+ *   ARITHMETIC: a weight exp2((l_v - max) log2(e) / temperature) is cut to 40 fractional bits and every mass is a 64-bit INTEGER sum of weights:
+ *   sums are exact in any order and the comparisons with top_p * Z and u * Z are integer comparisons (target ceil(top_p Z), floor(u Z) + 1). A
+ *   token whose weight is below 2^-40 of the maximum's has mass 0. Two launches on equal inputs are bit-identical; a row's token depends
+ *   neither on `rows`, nor on the row's index, nor on the alignment of its base.
+ *   SAFETY: whatever the inputs, the value written is in [0, vocab).
+ *   logits (rows, vocab) of `dtype`, unit column stride, any row stride >= vocab (a [..., :vocab] view of a padded buffer is read in place);
+ *   no alignment is asked of the base. Row offsets are 64-bit. u: f32; out: int64 (rows).
+ *   row_index (optional): a DEVICE int64; the row's uniform is u[step * rows + r] instead of u[r], step = row_index[0] clamped into
+ *   [0, table_steps). out_table (optional, needs row_index): int64 (table_steps, rows); the token is also written to out_table[step * rows + r].
+ *   With the two a replayed graph finds its step's uniforms and files its token with no host work.
+ * Checks, in this order: NULL struct / struct_size (DIMSUM_ERR_ABI) / required pointers (logits, out; u unless top_k == 1; row_index with
+ * out_table) / dtype / shape (rows in [1, 2^31), vocab in [1, 2^31 - 16), temperature finite and > 0, table_steps >= 1 with row_index) /
+ * stride (logits_row_stride < vocab) / out, then out_table, overlapping the logits (DIMSUM_ERR_ALIAS). Nothing is launched before all pass. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_sample_logits_params_t) as the caller compiled it; anything else -> DIMSUM_ERR_ABI */
+    int32_t dtype;            /* of logits */
+    int64_t rows, vocab;
+    int64_t logits_row_stride;
+    int32_t top_k;
+    float top_p, temperature;
+    int32_t reserved;         /* 0 */
+    const void *logits_ptr, *u_ptr;
+    void *out_ptr;
+    const void *row_index_ptr;  /* optional from here on */
+    void *out_table_ptr;
+    int64_t table_steps;      /* rows of u and out_table that row_index may address */
+} dimsum_sample_logits_params_t;
+
+int dimsum_sample_logits(const dimsum_sample_logits_params_t *p, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused residual-add + RMSNorm / LayerNorm over rows (M, N), f32 statistics.
  *   r = x (+ x_bias) (+ residual) ; residual_out = r (if residual_out_ptr) ; y = norm(r) * weight (+ bias)

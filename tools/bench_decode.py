@@ -8,7 +8,15 @@ decode steps between two device synchronisations (greedy sampling outside the gr
 rounds per path after a warm-up round of each. Both paths decode the same tokens from the same prompt and their logits are compared first.
 
     python tools/bench_decode.py [--steps 256] [--rounds 5] [--out decode_bench.json]
-prints one JSON line per configuration and a markdown table at the end."""
+prints one JSON line per configuration and a markdown table at the end.
+
+With --fused-sampling {0,1,both} the tool measures the SAMPLER instead (DIMSUM_FUSED_DECODE left as it is): generate() of `steps` tokens under
+--top-k / --top-p / --temperature with the fused sampler (csrc/sample_logits.hip; under cg inside the captured step) and with the unfused
+`sample` (the baseline), alternating round by round when both are asked for; tokens/s = batch * steps / wall time of the whole call between
+two device synchronisations, the prompt's forward included on both sides. It ends with the sampler kernel's time per launch on (batch, 50280)
+logits: device events around 200 back-to-back launches.
+
+    python tools/bench_decode.py --fused-sampling both --top-k 50 --top-p 0.9 [--batches 1 8] [--dtypes float32 bfloat16] [--modes eager graph]"""
 import argparse
 import json
 import os
@@ -55,14 +63,93 @@ def timed_decode(model, prompt, steps, cg, fused):
         return time.perf_counter() - t0, logits
 
 
+def timed_generate(model, prompt, steps, cg, fused_sampling, args):
+    """-> (seconds for generate() of `steps` tokens, the sequences)"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    seq = model.generate(prompt, max_length=PROMPT + steps, cg=cg, top_k=args.top_k, top_p=args.top_p, temperature=args.temperature,
+                         vocab_size=SHAPE["vocab_size"], fused_sampling=fused_sampling, generator=torch.Generator("cuda").manual_seed(1))
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, seq
+
+
+def sampler_kernel_time(args, dtype, batch, launches=200):
+    """-> microseconds per sample_logits launch on (batch, 50280) logits read through the padded row stride"""
+    from dimsum_amd import native
+    V = SHAPE["vocab_size"]
+    g = torch.Generator("cuda").manual_seed(0)
+    logits = (torch.randn(batch, V + 8, device="cuda", generator=g) * 4).to(dtype)[:, :V]
+    u = torch.rand(batch, device="cuda", generator=g)
+    out = torch.empty(batch, dtype=torch.long, device="cuda")
+    kw = dict(top_k=args.top_k, top_p=args.top_p, temperature=args.temperature, out=out)
+    for _ in range(10):
+        native.sample_logits(logits, u, **kw)
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(launches):
+        native.sample_logits(logits, u, **kw)
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) * 1e3 / launches
+
+
+def sampling_bench(args):
+    from dimsum_amd.models.mixer_seq_simple import MambaLMHeadModel
+    sides = {"0": [False], "1": [True], "both": [True, False]}[args.fused_sampling]
+    setting = dict(top_k=args.top_k, top_p=args.top_p, temperature=args.temperature)
+    rows = []
+    for name in args.dtypes:
+        dtype = getattr(torch, name)
+        torch.manual_seed(0)
+        model = MambaLMHeadModel(**SHAPE, device="cuda", dtype=dtype).eval()
+        for batch in args.batches:
+            prompt = torch.randint(0, SHAPE["vocab_size"], (batch, PROMPT), device="cuda", generator=torch.Generator("cuda").manual_seed(batch))
+            for mode in args.modes:
+                cg = mode == "graph"
+                model._decoding_cache = None
+                for f in sides:                                                 # warm-up (and capture)
+                    timed_generate(model, prompt, min(args.steps, 32), cg, f, args)
+                    timed_generate(model, prompt, args.steps, cg, f, args)
+                times = {f: [] for f in sides}
+                for _ in range(args.rounds):
+                    for f in sides:
+                        times[f].append(timed_generate(model, prompt, args.steps, cg, f, args)[0])
+                row = dict(setting, dtype=name, batch=batch, mode=mode, steps=args.steps, rounds=args.rounds)
+                for f in sides:
+                    side = "fused" if f else "unfused"
+                    row[f"{side}_tokens_per_s"] = round(batch * args.steps / statistics.median(times[f]), 1)
+                    row[f"spread_{side}"] = round(max(times[f]) / min(times[f]), 3)
+                if len(sides) == 2:
+                    row["ratio"] = round(row["fused_tokens_per_s"] / row["unfused_tokens_per_s"], 3)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+            model._decoding_cache = None
+            row = dict(setting, dtype=name, batch=batch, sampler_kernel_us_per_launch=round(sampler_kernel_time(args, dtype, batch), 1))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        del model
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--batches", type=int, nargs="*", default=[1, 8, 16])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fused-sampling", choices=["0", "1", "both"], default=None, help="measure the sampler: fused, unfused or the two alternating")
+    ap.add_argument("--top-k", type=int, default=1)
+    ap.add_argument("--top-p", type=float, default=0.0)
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--dtypes", nargs="*", default=["float32", "bfloat16"])
+    ap.add_argument("--modes", nargs="*", choices=["eager", "graph"], default=["eager", "graph"])
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_decode needs the GPU"
+    if args.fused_sampling is not None:
+        return sampling_bench(args)
     from dimsum_amd.models.mixer_seq_simple import MambaLMHeadModel
     rows = []
     for dtype in (torch.float32, torch.bfloat16):
