@@ -103,6 +103,16 @@ class SsmCarryParams(_Sized):
                 + [("h0_ptr", vp), ("hT_ptr", vp)])
 
 
+class SsmVarlenParams(_Sized):
+    """dimsum_ssm_varlen_params_t: the general forward on packed rows -- a (batch, seqlen) int32 sequence id per token, the state restarts where it changes"""
+    _fields_ = [("struct_size", u32), ("reserved", u32), ("scan", SsmGeneralParams), ("seq_idx_ptr", vp), ("seq_idx_batch_stride", i64)]
+
+
+class SsmVarlenBwdParams(_Sized):
+    """dimsum_ssm_varlen_bwd_params_t"""
+    _fields_ = [("struct_size", u32), ("reserved", u32), ("bwd", SsmGeneralBwdParams), ("seq_idx_ptr", vp), ("seq_idx_batch_stride", i64)]
+
+
 class OptimParams(_Sized):
     """dimsum_optim_params_t: device tables of the tensor list + hyper-parameters of one clip / AdamW / EMA step"""
     _fields_ = ([("struct_size", u32), ("n_tensors", i32), ("n_chunks", i32), ("n_partials", i32)]
@@ -180,6 +190,16 @@ class ConvBwdParams(_Sized):
                 + [(n, i64) for n in ("dout_batch_stride", "dout_c_stride", "dx_batch_stride", "dx_c_stride",
                                       "dweight_c_stride", "dweight_width_stride")]
                 + [(n, vp) for n in ("dout_ptr", "dx_ptr", "dweight_ptr", "dbias_ptr")])
+
+
+class ConvVarlenParams(_Sized):
+    """dimsum_conv_varlen_params_t: the causal conv1d on packed rows -- taps that cross a change of the (batch, seqlen) int32 sequence id are dropped"""
+    _fields_ = [("struct_size", u32), ("reserved", u32), ("conv", ConvParams), ("seq_idx_ptr", vp), ("seq_idx_batch_stride", i64)]
+
+
+class ConvVarlenBwdParams(_Sized):
+    """dimsum_conv_varlen_bwd_params_t"""
+    _fields_ = [("struct_size", u32), ("reserved", u32), ("conv", ConvBwdParams), ("seq_idx_ptr", vp), ("seq_idx_batch_stride", i64)]
 
 
 class ConvClParams(_Sized):
@@ -416,6 +436,7 @@ EXPORTS = (
     "dimsum_ssm_scan_bidir_fwd", "dimsum_ssm_scan_bidir_bwd", "dimsum_ssm_scan_bidir_fwd_variant",
     "dimsum_ssm_scan_general_fwd", "dimsum_ssm_scan_general_bwd", "dimsum_ssm_scan_general_bwd_workspace_bytes",
     "dimsum_ssm_scan_carry_fwd", "dimsum_causal_conv1d_chunk",
+    "dimsum_causal_conv1d_varlen_fwd", "dimsum_causal_conv1d_varlen_bwd", "dimsum_ssm_scan_varlen_fwd", "dimsum_ssm_scan_varlen_bwd",
     "dimsum_optim_grad_sumsq", "dimsum_optim_adamw_ema_step", "dimsum_optim_write_ptrs",
     "dimsum_fm_plan", "dimsum_fm_loss_fwd", "dimsum_fm_loss_bwd",
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
@@ -457,7 +478,9 @@ _SIGNATURES = (
         ("dimsum_causal_conv1d_cl_fwd", ConvClParams), ("dimsum_causal_conv1d_cl_bwd", ConvClBwdParams),
         ("dimsum_ssm_scan_carry_fwd", SsmCarryParams), ("dimsum_causal_conv1d_chunk", ConvChunkParams),
         ("dimsum_decode_linear", DecodeLinearParams), ("dimsum_cross_entropy_fwd", CrossEntropyParams),
-        ("dimsum_cross_entropy_bwd", CrossEntropyParams), ("dimsum_sample_logits", SampleLogitsParams))]
+        ("dimsum_cross_entropy_bwd", CrossEntropyParams), ("dimsum_sample_logits", SampleLogitsParams),
+        ("dimsum_causal_conv1d_varlen_fwd", ConvVarlenParams), ("dimsum_causal_conv1d_varlen_bwd", ConvVarlenBwdParams),
+        ("dimsum_ssm_scan_varlen_fwd", SsmVarlenParams), ("dimsum_ssm_scan_varlen_bwd", SsmVarlenBwdParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

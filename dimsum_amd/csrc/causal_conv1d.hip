@@ -12,7 +12,15 @@
 // half of it at L = 256). Weights and bias are wave-uniform (scalar loads). The backward walks the row from the end
 // so the gradient halo is carried the same way, keeps dweight/dbias partial sums in registers across all the batch
 // rows a wave owns and issues ONE atomic per wave per tap (the reference: one per block per row).
+//
+// Packed rows (dimsum_causal_conv1d_varlen_fwd / _bwd, kVarlen): a per-token sequence id rides along, loaded like x (16 bytes per lane, its
+// halo from the neighbouring lane and across steps from registers). Tap j of position t counts iff the ids of t-j .. t are pairwise equal
+// from one position to the next (no boundary in (t-j, t]); a masked value is replaced by 0 with a select, never multiplied away, so what
+// lies beyond a boundary cannot reach the result whatever it holds. Ids are only compared. The backward applies the same rule to the
+// gradient halo, which comes from the right. kVarlen = false compiles to the kernels as they were.
 #include "common.hpp"
+
+#include <type_traits>
 
 namespace dimsum {
 
@@ -22,6 +30,14 @@ __device__ __forceinline__ float lane_up(float v, float carry_for_lane0) {   // 
 }
 __device__ __forceinline__ float lane_down(float v, float carry_for_lane63) {
     const float t = __shfl_down(v, 1, kWave);
+    return (threadIdx.x & (kWave - 1)) == kWave - 1 ? carry_for_lane63 : t;
+}
+__device__ __forceinline__ int lane_up_i(int v, int carry_for_lane0) {
+    const int t = __shfl_up(v, 1, kWave);
+    return (threadIdx.x & (kWave - 1)) == 0 ? carry_for_lane0 : t;
+}
+__device__ __forceinline__ int lane_down_i(int v, int carry_for_lane63) {
+    const int t = __shfl_down(v, 1, kWave);
     return (threadIdx.x & (kWave - 1)) == kWave - 1 ? carry_for_lane63 : t;
 }
 __device__ __forceinline__ float wave_sum(float v) {
@@ -57,9 +73,40 @@ __device__ __forceinline__ void store_row4(T *row, int t, int L, const f32x4 &v)
     }
 }
 
+// four sequence ids of a packed row, positions t .. t+3 (beyond the row: 0 -- nothing is stored there and the gradients there are 0)
+struct alignas(16) i32x4 { int v[4]; };
+template <bool kVec> __device__ __forceinline__ i32x4 load_ids4(const int32_t *row, int t, int L) {
+    i32x4 r = {{0, 0, 0, 0}};
+    if constexpr (kVec) {
+        if (t < L) r = *reinterpret_cast<const i32x4 *>(row + t);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (t + e < L) r.v[e] = row[t + e];
+    }
+    return r;
+}
+
+// the kernel argument of the packed-row kernels: the plain one + the ids, (batch, seqlen) int32 with unit stride along seqlen
+struct conv_varlen_args_t {
+    dimsum_conv_params_t p;
+    const int32_t *seq_idx;
+    int64_t seq_batch_stride;
+};
+struct conv_varlen_bwd_args_t {
+    dimsum_conv_bwd_params_t q;
+    const int32_t *seq_idx;
+    int64_t seq_batch_stride;
+};
+__device__ __forceinline__ const dimsum_conv_params_t &conv_base(const dimsum_conv_params_t &a) { return a; }
+__device__ __forceinline__ const dimsum_conv_params_t &conv_base(const conv_varlen_args_t &a) { return a.p; }
+__device__ __forceinline__ const dimsum_conv_bwd_params_t &conv_base(const dimsum_conv_bwd_params_t &a) { return a; }
+__device__ __forceinline__ const dimsum_conv_bwd_params_t &conv_base(const conv_varlen_bwd_args_t &a) { return a.q; }
+
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T, bool kVec>
-__global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(const dimsum_conv_params_t p) {
+template <typename T, bool kVec, bool kVarlen>
+__global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(const std::conditional_t<kVarlen, conv_varlen_args_t, dimsum_conv_params_t> a) {
+    const dimsum_conv_params_t &p = conv_base(a);
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t rows = (int64_t)p.batch * p.dim;
@@ -72,6 +119,8 @@ __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(const dimsum_con
         T *o[kR];
         float w4[kR][4], bias[kR], c1[kR], c2[kR], c3[kR];   // taps right-aligned into 4 slots: w4[3] multiplies x[t], w4[2] x[t-1], ...
         bool ok[kR];
+        const int32_t *sq[kR];                               // kVarlen: the row's ids and those of t0-1, t0-2, t0-3 carried like c1 .. c3
+        int i1[kR], i2[kR], i3[kR];
 #pragma unroll
         for (int r = 0; r < kR; ++r) {
             const int64_t row = min(row0 + r * gstride, rows - 1);
@@ -84,20 +133,44 @@ __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(const dimsum_con
             for (int k = 0; k < 4; ++k) w4[r][k] = (k >= 4 - W) ? wp[(k - (4 - W)) * p.weight_width_stride] : 0.f;
             bias[r] = p.bias_ptr ? reinterpret_cast<const float *>(p.bias_ptr)[d] : 0.f;
             c1[r] = c2[r] = c3[r] = 0.f;                     // x[t0-1], x[t0-2], x[t0-3] carried across 256-element steps
+            if constexpr (kVarlen) {
+                sq[r] = a.seq_idx + (int64_t)b * a.seq_batch_stride;
+                i1[r] = i2[r] = i3[r] = 0;                   // before the row: the x halo there is 0, whatever the comparison says
+            }
         }
         for (int t0 = 0; t0 < L; t0 += 4 * kWave) {
             const int t = t0 + lane * 4;
             f32x4 v[kR];
+            i32x4 id[kR];
 #pragma unroll
-            for (int r = 0; r < kR; ++r) v[r] = load_row4<T, kVec>(x[r], t, L);
+            for (int r = 0; r < kR; ++r) {
+                v[r] = load_row4<T, kVec>(x[r], t, L);
+                if constexpr (kVarlen) id[r] = load_ids4<kVec>(sq[r], t, L);
+            }
 #pragma unroll
             for (int r = 0; r < kR; ++r) {
                 const float m1 = lane_up(v[r].v[3], c1[r]), m2 = lane_up(v[r].v[2], c2[r]), m3 = lane_up(v[r].v[1], c3[r]);
                 f32x4 q;
+                if constexpr (kVarlen) {
+                    // the mask on both halo routes: the ids of t-1 .. t-3 come from the neighbouring lane or, for lane 0, from the step before
+                    const int j1 = lane_up_i(id[r].v[3], i1[r]), j2 = lane_up_i(id[r].v[2], i2[r]), j3 = lane_up_i(id[r].v[1], i3[r]);
+                    const int I[7] = {j3, j2, j1, id[r].v[0], id[r].v[1], id[r].v[2], id[r].v[3]};          // ids of t-3 .. t+3
+                    const float xs[7] = {m3, m2, m1, v[r].v[0], v[r].v[1], v[r].v[2], v[r].v[3]};         // x[t-3] .. x[t+3]
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const bool k1 = I[e + 3] == I[e + 2], k2 = k1 && I[e + 2] == I[e + 1], k3 = k2 && I[e + 1] == I[e];
+                        q.v[e] = bias[r] + w4[r][0] * (k3 ? xs[e] : 0.f) + w4[r][1] * (k2 ? xs[e + 1] : 0.f) + w4[r][2] * (k1 ? xs[e + 2] : 0.f) +
+                                 w4[r][3] * xs[e + 3];
+                    }
+                    i1[r] = __shfl(id[r].v[3], kWave - 1, kWave);
+                    i2[r] = __shfl(id[r].v[2], kWave - 1, kWave);
+                    i3[r] = __shfl(id[r].v[1], kWave - 1, kWave);
+                } else {
                 q.v[0] = bias[r] + w4[r][0] * m3 + w4[r][1] * m2 + w4[r][2] * m1 + w4[r][3] * v[r].v[0];
                 q.v[1] = bias[r] + w4[r][0] * m2 + w4[r][1] * m1 + w4[r][2] * v[r].v[0] + w4[r][3] * v[r].v[1];
                 q.v[2] = bias[r] + w4[r][0] * m1 + w4[r][1] * v[r].v[0] + w4[r][2] * v[r].v[1] + w4[r][3] * v[r].v[2];
                 q.v[3] = bias[r] + w4[r][0] * v[r].v[0] + w4[r][1] * v[r].v[1] + w4[r][2] * v[r].v[2] + w4[r][3] * v[r].v[3];
+                }
                 if (p.silu_activation) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) q.v[e] *= sigmoidf_fast(q.v[e]);   // out / (1 + exp(-out)), causal_conv1d_fwd.cu:113-118
@@ -188,8 +261,9 @@ __global__ __launch_bounds__(256) void causal_conv1d_chunk_kernel(const dimsum_c
 
 // ---------------------------------------------------------------------------------------------------------------------
 // backward. grid = (dim, n_split): wave (d, s) owns batch rows b = s, s + n_split*4, ... of channel d.
-template <typename T, bool kVec>
-__global__ __launch_bounds__(256) void causal_conv1d_bwd_kernel(const dimsum_conv_bwd_params_t q) {
+template <typename T, bool kVec, bool kVarlen>
+__global__ __launch_bounds__(256) void causal_conv1d_bwd_kernel(const std::conditional_t<kVarlen, conv_varlen_bwd_args_t, dimsum_conv_bwd_params_t> a) {
+    const dimsum_conv_bwd_params_t &q = conv_base(a);
     const dimsum_conv_params_t &p = q.fwd;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -208,6 +282,9 @@ __global__ __launch_bounds__(256) void causal_conv1d_bwd_kernel(const dimsum_con
         const T *go = reinterpret_cast<const T *>(q.dout_ptr) + (int64_t)b * q.dout_batch_stride + (int64_t)d * q.dout_c_stride;
         T *dx = reinterpret_cast<T *>(q.dx_ptr) + (int64_t)b * q.dx_batch_stride + (int64_t)d * q.dx_c_stride;
         float g1 = 0.f, g2 = 0.f, g3 = 0.f;   // g[t0+256], g[t0+257], g[t0+258] of the step processed before (later in time)
+        const int32_t *sq = nullptr;          // kVarlen: the row's ids; those of t0+256 .. t0+258 carried like g1 .. g3
+        int n1 = 0, n2 = 0, n3 = 0;
+        if constexpr (kVarlen) sq = a.seq_idx + (int64_t)b * a.seq_batch_stride;
         for (int step = n_steps - 1; step >= 0; --step) {
             const int t0 = step * 4 * kWave, t = t0 + lane * 4;
             const f32x4 v = load_row4<T, kVec>(x, t, L);
@@ -217,6 +294,51 @@ __global__ __launch_bounds__(256) void causal_conv1d_bwd_kernel(const dimsum_con
             if (t0 > 0) { c1 = to_f32<T>(x[t0 - 1]); c2 = to_f32<T>(x[t0 - 2]); c3 = to_f32<T>(x[t0 - 3]); }
             const float m1 = lane_up(v.v[3], c1), m2 = lane_up(v.v[2], c2), m3 = lane_up(v.v[1], c3);
             const float xs[7] = {m3, m2, m1, v.v[0], v.v[1], v.v[2], v.v[3]};   // x[t-3] .. x[t+3]
+            if constexpr (kVarlen) {
+                // ids of t-3 .. t+6: the left three like the x halo (neighbour lane, memory for lane 0), the right three like the gradient
+                // halo (neighbour lane, the step processed before for lane 63). E[k]: no boundary at position t-2+k.
+                const i32x4 id = load_ids4<kVec>(sq, t, L);
+                int l1 = 0, l2 = 0, l3 = 0;
+                if (t0 > 0) { l1 = sq[t0 - 1]; l2 = sq[t0 - 2]; l3 = sq[t0 - 3]; }
+                const int I[10] = {lane_up_i(id.v[1], l3), lane_up_i(id.v[2], l2), lane_up_i(id.v[3], l1), id.v[0], id.v[1], id.v[2], id.v[3],
+                                   lane_down_i(id.v[0], n1), lane_down_i(id.v[1], n2), lane_down_i(id.v[2], n3)};
+                bool E[9];
+#pragma unroll
+                for (int k = 0; k < 9; ++k) E[k] = I[k] == I[k + 1];
+                float xm[4][3];                                                  // x[t+e-1], x[t+e-2], x[t+e-3] as position t+e sees them
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool k1 = E[e + 2], k2 = k1 && E[e + 1], k3 = k2 && E[e];
+                    xm[e][0] = k1 ? xs[e + 2] : 0.f;
+                    xm[e][1] = k2 ? xs[e + 1] : 0.f;
+                    xm[e][2] = k3 ? xs[e] : 0.f;
+                    if (p.silu_activation) {
+                        const float pre = bias + w4[0] * xm[e][2] + w4[1] * xm[e][1] + w4[2] * xm[e][0] + w4[3] * xs[e + 3];
+                        g.v[e] *= silu_grad(pre);
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    db += g.v[e];
+                    dw[0] = fmaf(g.v[e], xm[e][2], dw[0]);
+                    dw[1] = fmaf(g.v[e], xm[e][1], dw[1]);
+                    dw[2] = fmaf(g.v[e], xm[e][0], dw[2]);
+                    dw[3] = fmaf(g.v[e], xs[e + 3], dw[3]);
+                }
+                const float p1 = lane_down(g.v[0], g1), p2 = lane_down(g.v[1], g2), p3 = lane_down(g.v[2], g3);
+                const float gs[7] = {g.v[0], g.v[1], g.v[2], g.v[3], p1, p2, p3};   // g[t] .. g[t+6]
+                f32x4 r;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    // g[t+e+j] reaches dx[t+e] iff no boundary in (t+e, t+e+j]
+                    const bool k1 = E[e + 3], k2 = k1 && E[e + 4], k3 = k2 && E[e + 5];
+                    r.v[e] = w4[3] * gs[e] + w4[2] * (k1 ? gs[e + 1] : 0.f) + w4[1] * (k2 ? gs[e + 2] : 0.f) + w4[0] * (k3 ? gs[e + 3] : 0.f);
+                }
+                store_row4<T, kVec>(dx, t, L, r);
+                n1 = __shfl(id.v[0], 0, kWave);
+                n2 = __shfl(id.v[1], 0, kWave);
+                n3 = __shfl(id.v[2], 0, kWave);
+            } else {
             if (p.silu_activation) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -237,6 +359,7 @@ __global__ __launch_bounds__(256) void causal_conv1d_bwd_kernel(const dimsum_con
 #pragma unroll
             for (int e = 0; e < 4; ++e) r.v[e] = w4[3] * gs[e] + w4[2] * gs[e + 1] + w4[1] * gs[e + 2] + w4[0] * gs[e + 3];
             store_row4<T, kVec>(dx, t, L, r);
+            }
             g1 = __shfl(g.v[0], 0, kWave);
             g2 = __shfl(g.v[1], 0, kWave);
             g3 = __shfl(g.v[2], 0, kWave);
@@ -266,16 +389,24 @@ template <typename T> static bool vec_ok(const void *ptr, int64_t s0, int64_t s1
     return L % 4 == 0 && aligned_to<T>(ptr, 4 * sizeof(T)) && s0 % 4 == 0 && s1 % 4 == 0;
 }
 
-template <typename T> static int launch_conv_fwd(const dimsum_conv_params_t &p, hipStream_t s) {
+// the ids of a packed row are read as 16-byte vectors where x is: a 16-byte aligned base and a batch stride that keeps every row so
+static bool ids_vec_ok(const int32_t *seq_idx, int64_t batch_stride) { return aligned_to<int32_t>(seq_idx, 16) && batch_stride % 4 == 0; }
+
+// seq_idx == nullptr: the plain kernels, launched exactly as before
+template <typename T> static int launch_conv_fwd(const dimsum_conv_params_t &p, hipStream_t s, const int32_t *seq_idx = nullptr, int64_t seq_batch_stride = 0) {
     const bool vec = vec_ok<T>(p.x_ptr, p.x_batch_stride, p.x_c_stride, p.seqlen) &&
                      vec_ok<T>(p.out_ptr, p.out_batch_stride, p.out_c_stride, p.seqlen);
     const int64_t rows = (int64_t)p.batch * p.dim;
     const int grid = (int)((rows + 15) / 16 < 256 * 32 ? (rows + 15) / 16 : 256 * 32);   // 4 waves x 4 rows per workgroup and pass (a 2x larger grid measured slower)
-    if (vec) hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true>), dim3(grid), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false>), dim3(grid), dim3(256), 0, s, p);
+    if (seq_idx) {
+        const conv_varlen_args_t a = {p, seq_idx, seq_batch_stride};
+        if (vec && ids_vec_ok(seq_idx, seq_batch_stride)) hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true, true>), dim3(grid), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false, true>), dim3(grid), dim3(256), 0, s, a);
+    } else if (vec) hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true, false>), dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false, false>), dim3(grid), dim3(256), 0, s, p);
     return launch_status();
 }
-template <typename T> static int launch_conv_bwd(const dimsum_conv_bwd_params_t &q, hipStream_t s) {
+template <typename T> static int launch_conv_bwd(const dimsum_conv_bwd_params_t &q, hipStream_t s, const int32_t *seq_idx = nullptr, int64_t seq_batch_stride = 0) {
     const dimsum_conv_params_t &p = q.fwd;
     const bool vec = vec_ok<T>(p.x_ptr, p.x_batch_stride, p.x_c_stride, p.seqlen) &&
                      vec_ok<T>(q.dout_ptr, q.dout_batch_stride, q.dout_c_stride, p.seqlen) &&
@@ -283,8 +414,12 @@ template <typename T> static int launch_conv_bwd(const dimsum_conv_bwd_params_t 
     // enough waves to fill the chip while keeping >= 4 batch rows per wave when the batch allows it
     int split = 1;
     while ((int64_t)p.dim * split < 2048 && split * 4 < p.batch) split *= 2;
-    if (vec) hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, true>), dim3(p.dim, split), dim3(256), 0, s, q);
-    else hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, false>), dim3(p.dim, split), dim3(256), 0, s, q);
+    if (seq_idx) {
+        const conv_varlen_bwd_args_t a = {q, seq_idx, seq_batch_stride};
+        if (vec && ids_vec_ok(seq_idx, seq_batch_stride)) hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, true, true>), dim3(p.dim, split), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, false, true>), dim3(p.dim, split), dim3(256), 0, s, a);
+    } else if (vec) hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, true, false>), dim3(p.dim, split), dim3(256), 0, s, q);
+    else hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, false, false>), dim3(p.dim, split), dim3(256), 0, s, q);
     return launch_status();
 }
 
@@ -347,5 +482,52 @@ extern "C" int dimsum_causal_conv1d_bwd(const dimsum_conv_bwd_params_t *q, void 
         case DIMSUM_F32: return launch_conv_bwd<float>(*q, s);
         case DIMSUM_F16: return launch_conv_bwd<__half>(*q, s);
         default: return launch_conv_bwd<__hip_bfloat16>(*q, s);
+    }
+}
+
+// packed rows: the checks of the plain entry points in their order, then the ids (NULL, then a batch stride that lets rows overlap)
+static int conv_varlen_ids_check(const void *seq_idx, int64_t batch_stride, int32_t batch, int32_t seqlen) {
+    if (!seq_idx) return DIMSUM_ERR_NULL;
+    if (batch_stride < 0 || (batch > 1 && batch_stride < seqlen)) return DIMSUM_ERR_STRIDE;
+    return DIMSUM_OK;
+}
+
+extern "C" int dimsum_causal_conv1d_varlen_fwd(const dimsum_conv_varlen_params_t *v, void *stream) {
+    using namespace dimsum;
+    if (!v) return DIMSUM_ERR_NULL;
+    if (v->struct_size != sizeof(dimsum_conv_varlen_params_t)) return DIMSUM_ERR_ABI;
+    const dimsum_conv_params_t *p = &v->conv;
+    if (!p->out_ptr) return DIMSUM_ERR_NULL;
+    int rc = conv_check(*p);
+    if (rc != DIMSUM_OK) return rc;
+    rc = conv_varlen_ids_check(v->seq_idx_ptr, v->seq_idx_batch_stride, p->batch, p->seqlen);
+    if (rc != DIMSUM_OK) return rc;
+    if (p->batch == 0) return DIMSUM_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int32_t *ids = reinterpret_cast<const int32_t *>(v->seq_idx_ptr);
+    switch (p->dtype) {
+        case DIMSUM_F32: return launch_conv_fwd<float>(*p, s, ids, v->seq_idx_batch_stride);
+        case DIMSUM_F16: return launch_conv_fwd<__half>(*p, s, ids, v->seq_idx_batch_stride);
+        default: return launch_conv_fwd<__hip_bfloat16>(*p, s, ids, v->seq_idx_batch_stride);
+    }
+}
+
+extern "C" int dimsum_causal_conv1d_varlen_bwd(const dimsum_conv_varlen_bwd_params_t *v, void *stream) {
+    using namespace dimsum;
+    if (!v) return DIMSUM_ERR_NULL;
+    if (v->struct_size != sizeof(dimsum_conv_varlen_bwd_params_t)) return DIMSUM_ERR_ABI;
+    const dimsum_conv_bwd_params_t *q = &v->conv;
+    if (!q->dout_ptr || !q->dx_ptr || !q->dweight_ptr) return DIMSUM_ERR_NULL;
+    int rc = conv_check(q->fwd);
+    if (rc != DIMSUM_OK) return rc;
+    rc = conv_varlen_ids_check(v->seq_idx_ptr, v->seq_idx_batch_stride, q->fwd.batch, q->fwd.seqlen);
+    if (rc != DIMSUM_OK) return rc;
+    if (q->fwd.batch == 0) return DIMSUM_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int32_t *ids = reinterpret_cast<const int32_t *>(v->seq_idx_ptr);
+    switch (q->fwd.dtype) {
+        case DIMSUM_F32: return launch_conv_bwd<float>(*q, s, ids, v->seq_idx_batch_stride);
+        case DIMSUM_F16: return launch_conv_bwd<__half>(*q, s, ids, v->seq_idx_batch_stride);
+        default: return launch_conv_bwd<__hip_bfloat16>(*q, s, ids, v->seq_idx_batch_stride);
     }
 }

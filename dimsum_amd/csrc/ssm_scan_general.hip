@@ -19,6 +19,10 @@
 // over the batch (dA, constant dB / dC, dD, ddelta_bias) are fp32 atomics into zero-filled outputs: not bit-repeatable.
 // A carried state (dimsum_ssm_scan_carry_fwd, forward only) is a load before the walk and a store after it: the states live in registers, each
 // (channel, state) in exactly one lane, so that lane reads its h0 element, walks the sequence and writes its hT element -- hT may be h0.
+// Packed rows (dimsum_ssm_scan_varlen_fwd / _bwd, kVarlen; real A, input-dependent B / C): a per-token sequence id rides along. Once per tile
+// a wave reads the tile's kT ids and the one before them -- the row is the workgroup's, so the addresses and the resulting kT-bit reset
+// mask are wave-uniform and every wave of the workgroup forms the same mask -- and at a set bit the step starts from h = 0 (a select on
+// h_{t-1}, so nothing of the previous segment survives, not even a NaN). The backward masks a_t h_{t-1} and the adjoint hand-over the same way.
 #include "common.hpp"
 
 namespace dimsum {
@@ -37,6 +41,8 @@ struct gen_args_t {
     gen_carry_t c;                         // forward only
     int32_t cblocks;                       // 64-channel blocks per group
     int64_t dpad;                          // padded channel count of the saved states: n_groups * cblocks * 64
+    const int32_t *seq_idx;                // packed rows (kVarlen): (batch, seqlen) ids, rows seq_batch_stride apart; else NULL
+    int64_t seq_batch_stride;
 };
 
 constexpr int kGenChunk = 2048;            // selective_scan.cpp:307
@@ -115,9 +121,25 @@ __device__ __forceinline__ float delta_of(float raw, float bias, bool softplus) 
     return softplus ? softplus_ref(x) : x;
 }
 
+// the reset mask of one tile of a packed row: bit i = position t0 + i is a boundary (its id differs from the one before it; position 0 and
+// the positions beyond the row never are). `ids` is the workgroup's row: uniform addresses, a scalar result.
+template <int kT> __device__ __forceinline__ unsigned reset_mask(const int32_t *ids, int t0, int L) {
+    unsigned m = 0;
+    int prev = ids[t0 > 0 ? t0 - 1 : 0];
+#pragma unroll
+    for (int i = 0; i < kT; ++i) {
+        const int t = t0 + i;
+        const int cur = ids[t < L ? t : L - 1];
+        if (t > 0 && t < L && cur != prev) m |= 1u << i;
+        prev = cur;
+    }
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)m);
+}
+
 // ---- forward ---------------------------------------------------------------------------------------------------------------------------------
-template <typename T, bool kCplx, bool kVarB, bool kVarC, int kNB, int kMaxThreads>
+template <typename T, bool kCplx, bool kVarB, bool kVarC, int kNB, int kMaxThreads, bool kVarlen>
 __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const gen_args_t a) {
+    static_assert(!kVarlen || (!kCplx && kVarB && kVarC), "packed rows: real A with input-dependent B and C");
     using Cfg = GenCfg<kCplx, kNB>;
     constexpr int kK = Cfg::kK, kT = Cfg::kT, kRow = Cfg::kRow;
     extern __shared__ float red[];                      // [wave][step][lane]
@@ -152,8 +174,15 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
     const bool sp = p.delta_softplus != 0;
     const int64_t u_row = q.b * p.u_batch_stride + q.d * p.u_d_stride, dl_row = q.b * p.delta_batch_stride + q.d * p.delta_d_stride;
     float sumdt = 0.f, sumdt_lo = 0.f;                  // x's running product = exp(A sum dt); compensated: the phase of a complex product is A.im sum dt
+    const int32_t *ids = kVarlen ? a.seq_idx + (int64_t)q.b * a.seq_batch_stride : nullptr;
+    bool cut = false;                                   // kVarlen: a boundary lies behind: the running product is 0 from there on
 
     for (int t0 = 0; t0 < L; t0 += kT) {
+        unsigned rm = 0;
+        if constexpr (kVarlen) {
+            rm = reset_mask<kT>(ids, t0, L);
+            cut = cut || rm != 0;
+        }
         float uv[kT], dt[kT], y[kT];
 #pragma unroll
         for (int i = 0; i < kT; ++i) {
@@ -186,7 +215,7 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
                     y[i] += 2.f * (cr * h[2 * j] - ci * h[2 * j + 1]);          // 2 Re(C h): selective_scan_fwd_kernel.cuh, selective_scan_ref :163-164
                 } else {
                     const float bv = kVarB ? lane_value(bt, j * kRow + i) : Bc[j], cv = kVarC ? lane_value(ct, j * kRow + i) : Cc[j];
-                    h[j] = fmaf(pr, h[j], dtu * bv);
+                    h[j] = fmaf(pr, kVarlen && ((rm >> i) & 1u) ? 0.f : h[j], dtu * bv);
                     y[i] = fmaf(h[j], cv, y[i]);
                 }
             }
@@ -202,7 +231,7 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
                 decay<kCplx>(sumdt, A[j * kK], kCplx ? A[j * kK + kK - 1] : 0.f, pr, pi);
                 if (q.n0 + j < N) {
                     float *e = xr + (int64_t)(q.n0 + j) * 2 * kK;
-                    e[0] = pr;
+                    e[0] = kVarlen && cut ? 0.f : pr;
                     if constexpr (kCplx) { e[1] = pi; e[2] = h[2 * j]; e[3] = h[2 * j + 1]; }
                     else e[1] = h[j];
                 }
@@ -247,8 +276,9 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
 
 // ---- backward --------------------------------------------------------------------------------------------------------------------------------
 // gradients follow torch.autograd's convention for complex leaves: grad = dL/dRe + i dL/dIm, propagated with conjugates
-template <typename T, bool kCplx, bool kVarB, bool kVarC, int kNB, int kMaxThreads>
+template <typename T, bool kCplx, bool kVarB, bool kVarC, int kNB, int kMaxThreads, bool kVarlen>
 __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const gen_args_t a) {
+    static_assert(!kVarlen || (!kCplx && kVarB && kVarC), "packed rows: real A with input-dependent B and C");
     using Cfg = GenCfg<kCplx, kNB>;
     constexpr int kK = Cfg::kK, kT = Cfg::kT, kRow = Cfg::kRow, kS = kNB * kK;
     extern __shared__ float red[];                      // [wave][du | ddelta][step][lane]
@@ -279,6 +309,8 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const
     // saved states: (batch, tile, state real, padded channel) f32; this lane's column
     float *ck = reinterpret_cast<float *>(r.workspace_ptr) + ((int64_t)q.b * ntiles * N * kK) * a.dpad + (int64_t)blockIdx.x * 64 + q.lane;
 
+    const int32_t *ids = kVarlen ? a.seq_idx + (int64_t)q.b * a.seq_batch_stride : nullptr;
+
     // 1. forward sweep: the state before every tile
 #pragma unroll
     for (int j = 0; j < kS; ++j) h[j] = 0.f;
@@ -291,6 +323,8 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const
                 for (int c = 0; c < kK; ++c) ck[((int64_t)tile * N * kK + (q.n0 + j) * kK + c) * a.dpad] = h[j * kK + c];
             }
         if (tile == ntiles - 1) break;
+        unsigned rm = 0;
+        if constexpr (kVarlen) rm = reset_mask<kT>(ids, t0, L);
         float bt = 0.f;
         if constexpr (kVarB) bt = load_bc_tile<T, kCplx, kNB>(p.B_ptr, p.B_batch_stride, p.B_group_stride, p.B_dstate_stride, q, N, L, t0);
 #pragma unroll
@@ -310,7 +344,7 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const
                     h[2 * j + 1] = fmaf(pr, hi, fmaf(pi, hr, dtu * bi));
                 } else {
                     const float bv = kVarB ? lane_value(bt, j * kRow + i) : Bc[j];
-                    h[j] = fmaf(pr, h[j], dtu * bv);
+                    h[j] = fmaf(pr, kVarlen && ((rm >> i) & 1u) ? 0.f : h[j], dtu * bv);
                 }
             }
         }
@@ -323,6 +357,8 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const
     float dD = 0.f, dbias = 0.f;
     for (int tile = ntiles - 1; tile >= 0; --tile) {
         const int t0 = tile * kT;
+        unsigned rm = 0;
+        if constexpr (kVarlen) rm = reset_mask<kT>(ids, t0, L);
         float uv[kT], dt[kT], dy[kT], du[kT], ddt[kT], hs[kT][kS];
 #pragma unroll
         for (int i = 0; i < kT; ++i) {
@@ -361,7 +397,7 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const
                     hs[i][2 * j + 1] = h[2 * j + 1];
                 } else {
                     const float bv = kVarB ? lane_value(bt, j * kRow + i) : Bc[j];
-                    h[j] = fmaf(pr, h[j], dtu * bv);
+                    h[j] = fmaf(pr, kVarlen && ((rm >> i) & 1u) ? 0.f : h[j], dtu * bv);
                     hs[i][j] = h[j];
                 }
             }
@@ -413,7 +449,8 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const
                     const float bv = kVarB ? lane_value(bt, j * kRow + i) : Bc[j], cv = kVarC ? lane_value(ct, j * kRow + i) : Cc[j];
                     const float hv = hs[i][j];
                     const float g = fmaf(cv, dy[i], gc[j]);
-                    const float ah = fmaf(-dtu, bv, hv);
+                    const bool rst = kVarlen && ((rm >> i) & 1u);            // a boundary: a_t h_{t-1} is 0 by definition, not by cancellation
+                    const float ah = rst ? 0.f : fmaf(-dtu, bv, hv);
                     const float bg = bv * g, qg = ah * g;
                     du[i] = fmaf(dt[i], bg, du[i]);
                     ddt[i] += uv[i] * bg + A[j] * qg;
@@ -431,7 +468,7 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const
                     } else {
                         dCc[j] += dc;
                     }
-                    gc[j] = pr * g;
+                    gc[j] = rst ? 0.f : pr * g;                             // nothing is handed to the previous segment
                 }
             }
         }
@@ -535,6 +572,14 @@ static int gen_check(const dimsum_ssm_general_params_t &p, bool forward) {
     return DIMSUM_OK;
 }
 
+// packed rows, behind the general checks: the ids (NULL, then a batch stride that lets rows overlap), then what has no kVarlen instantiation
+static int gen_varlen_check(const dimsum_ssm_general_params_t &p, const void *seq_idx, int64_t seq_batch_stride) {
+    if (!seq_idx) return DIMSUM_ERR_NULL;
+    if (seq_batch_stride < 0 || (p.batch > 1 && seq_batch_stride < p.seqlen)) return DIMSUM_ERR_STRIDE;
+    if (p.is_complex || !p.is_variable_B || !p.is_variable_C) return DIMSUM_ERR_UNSUPPORTED;
+    return DIMSUM_OK;
+}
+
 template <typename T, bool kCplx, bool kVarB, bool kVarC> static int gen_launch(const gen_args_t &a, bool forward, hipStream_t s) {
     const dimsum_ssm_general_params_t &p = a.f;
     const int nb = gen_nb(p.dstate), W = (p.dstate + nb - 1) / nb;
@@ -544,12 +589,25 @@ template <typename T, bool kCplx, bool kVarB, bool kVarC> static int gen_launch(
     // up to 64 states a workgroup is at most 4 waves, one per SIMD: the kernel may use the whole register file (512 per lane); above, up to
     // 16 waves share it (128 each)
     const bool small = W <= 4;
+    if constexpr (!kCplx && kVarB && kVarC) {
+        if (a.seq_idx) {            // packed rows: the same launch shape on the kVarlen instantiations
+            if (forward) {
+                if (small) hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, 16, 256, true>), grid, block, lds, s, a);
+                else hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, 16, 1024, true>), grid, block, lds, s, a);
+            } else {
+                if (small) hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, 16, 256, true>), grid, block, lds, s, a);
+                else hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, 16, 1024, true>), grid, block, lds, s, a);
+            }
+            return launch_status();
+        }
+    }
+    if (a.seq_idx) return DIMSUM_ERR_UNSUPPORTED;
     if (forward) {
-        if (small) hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, 16, 256>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, 16, 1024>), grid, block, lds, s, a);
+        if (small) hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, 16, 256, false>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, 16, 1024, false>), grid, block, lds, s, a);
     } else {
-        if (small) hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, 16, 256>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, 16, 1024>), grid, block, lds, s, a);
+        if (small) hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, 16, 256, false>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, 16, 1024, false>), grid, block, lds, s, a);
     }
     return launch_status();
 }
@@ -623,10 +681,9 @@ extern "C" int64_t dimsum_ssm_scan_general_bwd_workspace_bytes(int32_t batch, in
     return gen_ckpt_bytes(batch, dim, seqlen, dstate, n_groups, is_complex != 0);
 }
 
-extern "C" int dimsum_ssm_scan_general_bwd(const dimsum_ssm_general_bwd_params_t *p, void *stream) {
+// the backward's checks behind NULL / struct_size and its launch; seq_idx != NULL: packed rows
+static int dimsum_gen_bwd_run(const dimsum_ssm_general_bwd_params_t *p, const void *seq_idx, int64_t seq_batch_stride, bool varlen, void *stream) {
     using namespace dimsum;
-    if (!p) return DIMSUM_ERR_NULL;
-    if (p->struct_size != sizeof(dimsum_ssm_general_bwd_params_t)) return DIMSUM_ERR_ABI;
     const dimsum_ssm_general_params_t &f = p->fwd;
     int rc = gen_check(f, false);
     if (rc == DIMSUM_ERR_NULL) return rc;
@@ -639,9 +696,43 @@ extern "C" int dimsum_ssm_scan_general_bwd(const dimsum_ssm_general_bwd_params_t
         if (s < 0) return DIMSUM_ERR_STRIDE;
     if (!aligned_to<float>(p->workspace_ptr, 16)) return DIMSUM_ERR_STRIDE;
     if (p->workspace_bytes < gen_ckpt_bytes(f.batch, f.dim, f.seqlen, f.dstate, f.n_groups, f.is_complex != 0)) return DIMSUM_ERR_SHAPE;
+    if (varlen) {
+        rc = gen_varlen_check(f, seq_idx, seq_batch_stride);
+        if (rc != DIMSUM_OK) return rc;
+    }
     gen_args_t a;
     memset(&a, 0, sizeof(a));
     a.f = f;
     a.b = *p;
+    a.seq_idx = reinterpret_cast<const int32_t *>(seq_idx);
+    a.seq_batch_stride = seq_batch_stride;
     return gen_run(a, false, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dimsum_ssm_scan_general_bwd(const dimsum_ssm_general_bwd_params_t *p, void *stream) {
+    if (!p) return DIMSUM_ERR_NULL;
+    if (p->struct_size != sizeof(dimsum_ssm_general_bwd_params_t)) return DIMSUM_ERR_ABI;
+    return dimsum_gen_bwd_run(p, nullptr, 0, false, stream);
+}
+
+extern "C" int dimsum_ssm_scan_varlen_bwd(const dimsum_ssm_varlen_bwd_params_t *p, void *stream) {
+    if (!p) return DIMSUM_ERR_NULL;
+    if (p->struct_size != sizeof(dimsum_ssm_varlen_bwd_params_t)) return DIMSUM_ERR_ABI;
+    return dimsum_gen_bwd_run(&p->bwd, p->seq_idx_ptr, p->seq_idx_batch_stride, true, stream);
+}
+
+extern "C" int dimsum_ssm_scan_varlen_fwd(const dimsum_ssm_varlen_params_t *p, void *stream) {
+    using namespace dimsum;
+    if (!p) return DIMSUM_ERR_NULL;
+    if (p->struct_size != sizeof(dimsum_ssm_varlen_params_t)) return DIMSUM_ERR_ABI;
+    int rc = gen_check(p->scan, true);
+    if (rc != DIMSUM_OK) return rc;
+    rc = gen_varlen_check(p->scan, p->seq_idx_ptr, p->seq_idx_batch_stride);
+    if (rc != DIMSUM_OK) return rc;
+    gen_args_t a;
+    memset(&a, 0, sizeof(a));
+    a.f = p->scan;
+    a.seq_idx = reinterpret_cast<const int32_t *>(p->seq_idx_ptr);
+    a.seq_batch_stride = p->seq_idx_batch_stride;
+    return gen_run(a, true, reinterpret_cast<hipStream_t>(stream));
 }

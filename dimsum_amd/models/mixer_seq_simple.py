@@ -70,13 +70,15 @@ class MixerModel(nn.Module):
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
         return {i: layer.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, **kwargs) for i, layer in enumerate(self.layers)}
 
-    def forward(self, input_ids, inference_params=None, final_norm=True):
-        """-> the normed hidden states (B, L, d_model); final_norm=False (no reference counterpart): (hidden_states, residual) of the last block,
+    def forward(self, input_ids, inference_params=None, final_norm=True, seq_idx=None):
+        """seq_idx (B, L) int32: packed rows -- the sequences of one row do not see each other in any mixer (modules/mamba_simple.py).
+        -> the normed hidden states (B, L, d_model); final_norm=False (no reference counterpart): (hidden_states, residual) of the last block,
         for a caller that folds the last add + norm_f into its own launch (MambaLMHeadModel's decode step)"""
         hidden_states = self.embedding(input_ids)
         residual = None
         for layer in self.layers:
-            hidden_states, residual = layer(hidden_states, residual, inference_params=inference_params)
+            hidden_states, residual = layer(hidden_states, residual, inference_params=inference_params,
+                                            **({"seq_idx": seq_idx} if seq_idx is not None else {}))
         if not final_norm:
             return hidden_states, residual
         if not self.fused_add_norm:
@@ -117,8 +119,17 @@ class MambaLMHeadModel(nn.Module, GenerationMixin):
         return (input_ids.shape[0] <= 16 and w.dtype in (torch.float32, torch.float16, torch.bfloat16)
                 and all(t is None or t.dtype == w.dtype for t in (self.lm_head.bias, b.norm_f.weight, b.norm_f.bias)))
 
-    def forward(self, input_ids, position_ids=None, inference_params=None, num_last_tokens=0):
-        """position_ids: accepted and unused, as in the reference. num_last_tokens > 0: logits of the last n tokens only"""
+    def forward(self, input_ids, position_ids=None, inference_params=None, num_last_tokens=0, seq_idx=None):
+        """position_ids: accepted and unused, as in the reference. num_last_tokens > 0: logits of the last n tokens only.
+        seq_idx (B, L) int32: packed rows (several documents per row, or a left-padded prompt whose padding is a segment of its own); with
+        inference_params at seqlen_offset == 0 the cache is left holding every row's last segment; at seqlen_offset > 0 it raises"""
+        if seq_idx is not None:
+            if inference_params is not None and inference_params.seqlen_offset > 0:
+                raise ValueError("seq_idx at seqlen_offset > 0: sequence ids belong to the prompt pass (seqlen_offset == 0)")
+            hidden_states = self.backbone(input_ids, inference_params=inference_params, seq_idx=seq_idx)
+            if num_last_tokens > 0:
+                hidden_states = hidden_states[:, -num_last_tokens:]
+            return CausalLMOutput(logits=self.lm_head(hidden_states))
         if self._fused_head(input_ids, inference_params):
             hidden, residual = self.backbone(input_ids, inference_params=inference_params, final_norm=False)
             nf = self.backbone.norm_f
@@ -134,13 +145,17 @@ class MambaLMHeadModel(nn.Module, GenerationMixin):
             hidden_states = hidden_states[:, -num_last_tokens:]
         return CausalLMOutput(logits=self.lm_head(hidden_states))
 
-    def loss(self, input_ids, labels=None, *, chunk_rows=4096, ignore_index=-100, label_smoothing=0.0, lse_square_scale=0.0, reduction="mean"):
+    def loss(self, input_ids, labels=None, *, chunk_rows=4096, ignore_index=-100, label_smoothing=0.0, lse_square_scale=0.0, reduction="mean",
+             seq_idx=None):
         """-> the scalar training loss (no reference counterpart as a method: its recipes run a fused cross-entropy on forward()'s logits).
         The backbone, then the head product and the cross-entropy chunk_rows tokens at a time on csrc/cross_entropy.hip
         (ops.linear_cross_entropy): the (batch * seqlen, vocab) logits never exist. labels (batch, seqlen) int64, ignore_index where a
         position does not count; None = next-token prediction: input_ids shifted left, the last position ignored. Only the first
-        config["vocab_size"] rows of lm_head.weight are classes: the vocabulary padding takes no part and gets a zero gradient."""
-        hidden_states = self.backbone(input_ids)
+        config["vocab_size"] rows of lm_head.weight are classes: the vocabulary padding takes no part and gets a zero gradient.
+        seq_idx (batch, seqlen) int32: packed rows, handed to the backbone. The loss's own arithmetic does not change: the caller marks what
+        does not count -- a document's last token must not predict the next document's first -- e.g. with
+        labels = dimsum_amd.utils.packed_labels(input_ids, seq_idx)."""
+        hidden_states = self.backbone(input_ids) if seq_idx is None else self.backbone(input_ids, seq_idx=seq_idx)
         if labels is None:
             labels = torch.cat([input_ids[:, 1:], input_ids.new_full((input_ids.shape[0], 1), ignore_index)], dim=1)
         return linear_cross_entropy(hidden_states, self.lm_head.weight, labels, self.lm_head.bias, chunk_rows=chunk_rows, reduction=reduction,

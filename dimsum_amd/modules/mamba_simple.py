@@ -12,6 +12,10 @@ token-by-token order) and the operand-image input `x3` (inference images and a c
 more than one token per call through `extend` (a causal conv and a scan that enter with the cache's states and leave the new ones behind;
 `dimsum_amd.utils.chunked_prefill` walks a long prompt with it); `step` and `forward` at `seqlen_offset > 0` keep taking one token. The
 recurrent form is for inference: the cache is filled without autograd edges and the step and extend kernels have no backward.
+Packed rows: `Mamba.forward(..., seq_idx=ids)` with ids (B, L) int32 keeps the sequences of one row apart (ops/selective_scan_interface.py: the
+packed-row route of mamba_inner_fn). With a cache at `seqlen_offset == 0` the states left behind are those of every row's LAST segment: ssm_state
+its final state, conv_state its last inputs with whatever belongs to an earlier segment zeroed -- so a prompt left-padded with its padding as a
+segment of its own prefills as if it stood alone. Refused with seq_idx: scan types other than "none", `x3`, CondMamba's cond, `seqlen_offset > 0`.
 `Block` (mamba_simple.py:383-436) wraps a mixer with its add + norm; for one token of a cached sequence it runs the mixer's `step_fused`: the
 same step on the weight-streaming kernel of csrc/decode_step.hip, four launches per layer.
 
@@ -117,8 +121,24 @@ class _MambaBase(nn.Module):
         gathers its tokens itself"""
         return not (self._is_zigzag() and not getattr(self, "_zigzag_folded", False))
 
-    def _mix(self, hidden_states, cond, x3=None, states=None):
-        """states: the (conv_state, ssm_state) of an inference cache, filled from this call's sequence (forward(inference_params=...))"""
+    def _refuse_seq_idx(self, seq_idx, hidden_states, cond, x3):
+        if self.scan_type != "none":
+            raise NotImplementedError(f'seq_idx with scan_type "{self.scan_type}" is not built: only the plain causal mixer ("none") has a '
+                                      "packed-row form (the backward twin and the zigzag orders read a row in another order)")
+        if x3 is not None:
+            raise NotImplementedError("seq_idx with an operand-image input (x3) is not built: the in_proj + conv epilogue takes no sequence ids; "
+                                      "pass hidden_states")
+        if cond is not None:
+            raise NotImplementedError("seq_idx with a conditional conv entry (cond) is not built")
+        if not (torch.is_tensor(seq_idx) and seq_idx.dtype == torch.int32 and tuple(seq_idx.shape) == tuple(hidden_states.shape[:2])):
+            raise ValueError(f"seq_idx must be an int32 (batch, seqlen) = {tuple(hidden_states.shape[:2])} tensor")
+
+    def _mix(self, hidden_states, cond, x3=None, states=None, seq_idx=None):
+        """states: the (conv_state, ssm_state) of an inference cache, filled from this call's sequence (forward(inference_params=...));
+        seq_idx: packed rows (module docstring)"""
+        if seq_idx is not None:
+            self._refuse_seq_idx(seq_idx, hidden_states, cond, x3)
+            seq_idx = seq_idx.contiguous()
         bsz, L, _ = (hidden_states if x3 is None else x3).shape
         own_gather = self._is_zigzag() and not getattr(self, "_zigzag_folded", False)   # folded: the enclosing block's token
         if own_gather:                                                                  # tables already include the path
@@ -147,7 +167,14 @@ class _MambaBase(nn.Module):
             # the last d_conv inputs of the conv (mamba_simple.py:258), zero-padded on the left when the prompt is shorter (module docstring)
             xin = xz[:, :self.d_inner]
             with torch.no_grad():       # the cache is data for the next calls, never an autograd edge
-                states[0].copy_(xin[:, :, -self.d_conv:] if L >= self.d_conv else F.pad(xin, (self.d_conv - L, 0)))
+                tail = xin[:, :, -self.d_conv:]
+                if seq_idx is not None and L > 1:
+                    # only the last segment's inputs: position p of the tail stays iff no boundary lies in (p, L - 1] (on the device: no host read)
+                    ids = seq_idx[:, -self.d_conv:]
+                    same = (ids[:, 1:] == ids[:, :-1]).flip(1).cumprod(1).flip(1).bool()
+                    keep = torch.cat([same, same.new_ones(bsz, 1)], dim=1)
+                    tail = torch.where(keep[:, None, :], tail, torch.zeros_like(tail))
+                states[0].copy_(tail if L >= self.d_conv else F.pad(tail, (self.d_conv - L, 0)))
         # recomputed on every call (two tiny launches): a cached copy could not see in-place parameter updates made through
         # `.data` (EMA, load_state_dict), which do not bump the version counter, and would be frozen into a captured hipGraph
         A = gemm.neg_exp(self.A_log)
@@ -165,7 +192,7 @@ class _MambaBase(nn.Module):
         out = mamba_inner_fn_cond(xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
                                   self.out_proj.weight, self.out_proj.bias, A, None, None, self.D.float(),
                                   delta_bias=self.dt_proj.bias.float(), delta_softplus=True, init_states=cond, conv_done=conv_done,
-                                  last_state=None if states is None else states[1])
+                                  last_state=None if states is None else states[1], **({"seq_idx": seq_idx} if seq_idx is not None else {}))
         if own_gather:
             out = out.index_select(1, self.zigzag_paths_reverse[self.layer_idx])
         return out
@@ -288,20 +315,30 @@ class _MambaBase(nn.Module):
             out = F.linear(y.transpose(1, 2), self.out_proj.weight, self.out_proj.bias)
         return out, conv_state, ssm_state
 
-    def _forward_cached(self, hidden_states, cond, inference_params, x3):
+    def _forward_cached(self, hidden_states, cond, inference_params, x3, seq_idx=None):
         """forward(inference_params=...): a prompt at seqlen_offset 0 (fused path + the states it leaves behind), one step after it"""
         self._refuse_recurrent(x3)
         conv_state, ssm_state = self._get_states_from_cache(inference_params, hidden_states.shape[0])
         if inference_params.seqlen_offset > 0:
+            if seq_idx is not None:
+                raise ValueError("seq_idx at seqlen_offset > 0: sequence ids belong to the prompt pass (seqlen_offset == 0); a decode step "
+                                 "continues every row's last segment")
             return self.step(hidden_states, conv_state, ssm_state)[0]       # the states are updated in place
-        return self._mix(hidden_states, cond, states=(conv_state, ssm_state))
+        if seq_idx is None:
+            return self._mix(hidden_states, cond, states=(conv_state, ssm_state))
+        return self._mix(hidden_states, cond, states=(conv_state, ssm_state), seq_idx=seq_idx)
 
 
 class Mamba(_MambaBase):
-    def forward(self, hidden_states, cond_emb=None, inference_params=None, x3=None):
+    def forward(self, hidden_states, cond_emb=None, inference_params=None, x3=None, seq_idx=None):
         """hidden_states: (B, L, D) -> (B, L, D).  cond_emb: accepted and unused, as in the reference (mamba_simple.py:162): the DiM blocks
         call every mixer as mixer(x, c).  x3: the input as a split-bf16 operand image instead (inference, gemm.py).
-        inference_params: a dimsum_amd.utils.InferenceParams -- the recurrent form, see the module docstring."""
+        inference_params: a dimsum_amd.utils.InferenceParams -- the recurrent form, see the module docstring.
+        seq_idx: (B, L) int32 sequence ids of packed rows, see the module docstring; None: the call it always was."""
+        if seq_idx is not None:
+            if inference_params is not None:
+                return self._forward_cached(hidden_states, None, inference_params, x3, seq_idx=seq_idx)
+            return self._mix(hidden_states, None, x3=x3, seq_idx=seq_idx)
         if inference_params is not None:
             return self._forward_cached(hidden_states, None, inference_params, x3)
         return self._mix(hidden_states, None, x3=x3)
@@ -347,7 +384,10 @@ class Block(nn.Module):
         states = self.mixer._get_states_from_cache(inference_params, hidden_states.shape[0])
         return states if self.mixer.fused_step_serves(hidden_states[:, 0], self.norm, *states) else None
 
-    def forward(self, hidden_states, residual=None, inference_params=None):
+    def forward(self, hidden_states, residual=None, inference_params=None, seq_idx=None):
+        """seq_idx: handed to the mixer (packed rows; a prompt or training pass, never a decode step)"""
+        if seq_idx is not None and inference_params is not None and inference_params.seqlen_offset > 0:
+            raise ValueError("seq_idx at seqlen_offset > 0: sequence ids belong to the prompt pass (seqlen_offset == 0)")
         states = self._fused_decode_states(hidden_states, residual, inference_params)
         if states is not None:
             res_dtype = residual.dtype if residual is not None else (torch.float32 if self.residual_in_fp32 else hidden_states.dtype)
@@ -361,7 +401,7 @@ class Block(nn.Module):
         else:
             hidden_states, residual = layer_norm_fn(hidden_states, self.norm.weight, self.norm.bias, residual=residual, eps=self.norm.eps, prenorm=True,
                                                     residual_in_fp32=self.residual_in_fp32, is_rms_norm=isinstance(self.norm, RMSNorm))
-        hidden_states = self.mixer(hidden_states, inference_params=inference_params)
+        hidden_states = self.mixer(hidden_states, inference_params=inference_params, **({"seq_idx": seq_idx} if seq_idx is not None else {}))
         return hidden_states, residual
 
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):

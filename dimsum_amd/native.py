@@ -377,6 +377,70 @@ def causal_conv1d_bwd(x, weight, bias, dout, dx, silu_activation):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# packed rows (upstream Mamba's seq_idx): several sequences in one (batch, seqlen) row that must not see each other
+# ---------------------------------------------------------------------------------------------------------------------
+def _check_seq_idx(seq_idx, batch, seqlen, who):
+    """seq_idx: (batch, seqlen) int32, contiguous. Its values are only ever compared: any content is safe. The device is checked last."""
+    _check(torch.is_tensor(seq_idx) and seq_idx.dtype == torch.int32 and tuple(seq_idx.shape) == (batch, seqlen) and seq_idx.is_contiguous(),
+           f"{who}: seq_idx must be a contiguous int32 (batch, seqlen) = ({batch}, {seqlen}) tensor")
+
+
+def causal_conv1d_varlen_fwd(x, weight, bias, silu_activation, seq_idx, out=None):
+    """causal_conv1d_fwd on packed rows -> out (batch, dim, seqlen): tap j of position t counts iff no boundary (a change of seq_idx) lies
+    in (t - j, t]. x (batch, dim, seqlen) with unit stride along seqlen and free batch / channel strides (a half of xz, a d-major view);
+    a channel-last x is refused: those kernels take no seq_idx."""
+    _check(x.dim() == 3, "causal_conv1d: x must be (batch, dim, seqlen)")
+    _check_seq_idx(seq_idx, x.shape[0], x.shape[2], "causal_conv1d_varlen_fwd")
+    _check(not _check_conv(x, weight, bias), "causal_conv1d_varlen_fwd: seq_idx needs a seqlen-contiguous x (the channel-last kernels take none)")
+    _gpu(seq_idx)
+    weight = weight.float()
+    bias = bias.float().contiguous() if bias is not None else None
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _gpu(out)
+        _check(out.shape == x.shape and out.dtype == x.dtype and out.stride(2) == 1, "causal_conv1d_varlen_fwd: bad out")
+    if x.numel() > 0:
+        P = _lib.ConvVarlenParams()
+        _fill_conv(P.conv, x, weight, bias, silu_activation, out)
+        P.seq_idx_ptr, P.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dimsum_causal_conv1d_varlen_fwd(P, _stream(x)), "causal_conv1d_varlen_fwd")
+    return out
+
+
+def causal_conv1d_varlen_bwd(x, weight, bias, dout, dx, silu_activation, seq_idx):
+    """-> [dx, dweight, dbias] of causal_conv1d_varlen_fwd: dx[t] collects from the later positions of its own segment only; dweight sums
+    the unmasked (tap, position) pairs, dbias every position"""
+    _check(x.dim() == 3, "causal_conv1d: x must be (batch, dim, seqlen)")
+    _check_seq_idx(seq_idx, x.shape[0], x.shape[2], "causal_conv1d_varlen_bwd")
+    _check(not _check_conv(x, weight, bias), "causal_conv1d_varlen_bwd: seq_idx needs a seqlen-contiguous x (the channel-last kernels take none)")
+    _gpu(dout, dx, seq_idx)
+    _check(dout.shape == x.shape and dout.dtype == x.dtype and (dout.stride(2) == 1 or dout.shape[2] == 1), "causal_conv1d_varlen_bwd: bad dout")
+    if dx is None:
+        dx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+    else:
+        _check(dx.shape == x.shape and dx.dtype == x.dtype and dx.stride(2) == 1, "causal_conv1d_varlen_bwd: bad dx")
+    w32 = weight.float()
+    b32 = bias.float().contiguous() if bias is not None else None
+    acc = _zeros(weight.numel() + (weight.shape[0] if bias is not None else 0), x.device)
+    dweight = acc[:weight.numel()].view(weight.shape)
+    dbias = acc[weight.numel():] if bias is not None else None
+    if x.numel() > 0:
+        V = _lib.ConvVarlenBwdParams()
+        Q = V.conv
+        _fill_conv(Q.fwd, x, w32, b32, silu_activation, None)
+        Q.dout_batch_stride, Q.dout_c_stride = dout.stride(0), dout.stride(1)
+        Q.dx_batch_stride, Q.dx_c_stride = dx.stride(0), dx.stride(1)
+        Q.dweight_c_stride, Q.dweight_width_stride = dweight.stride(0), dweight.stride(1)
+        Q.dout_ptr, Q.dx_ptr, Q.dweight_ptr, Q.dbias_ptr = _ptr(dout), _ptr(dx), _ptr(dweight), _ptr(dbias)
+        V.seq_idx_ptr, V.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dimsum_causal_conv1d_varlen_bwd(V, _stream(x)), "causal_conv1d_varlen_bwd")
+    return [dx, dweight.to(weight.dtype), dbias.to(bias.dtype) if bias is not None else None]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the recurrent form: causal_conv1d_cuda.causal_conv1d_update (causal_conv1d.cpp:512-569) and the Triton
 # selective_state_update (ops/triton/selective_state_update.py:115-190). Both update their state IN PLACE; every operand
 # may be a strided view (csrc/mixer_step.hip addresses with one element stride per dim).
@@ -958,17 +1022,49 @@ def _fill_ssm_general(P, u, delta, A, B, C, D, z, delta_bias, delta_softplus, ou
     P.out_ptr, P.x_ptr, P.out_z_ptr = _ptr(out), _ptr(x), _ptr(out_z)
 
 
-def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=True, need_x=True):
+def _check_scan_seq_idx(seq_idx, u, flags, who):
+    """packed rows, behind the general checks: the ids, then what the packed kernels are not built for"""
+    _check_seq_idx(seq_idx, u.shape[0], u.shape[2], who)
+    cplx, var_B, var_C, _ = flags
+    _check(not cplx, f"{who}: seq_idx with a complex A is not built (the packed-row kernels are instantiated for real A with input-dependent B and C)")
+    _check(var_B and var_C, f"{who}: seq_idx with a constant B or C is not built (the packed-row kernels are instantiated for real A with "
+                            "input-dependent B and C)")
+    _gpu(seq_idx)
+
+
+def selective_scan_varlen_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, seq_idx, need_out=True, need_x=True):
+    """selective_scan_general_fwd on packed rows: seq_idx (batch, seqlen) int32, the state restarts at every position whose id differs from
+    the one before it. x[:, :, -1, 1::2] is the state of the row's last segment. Real A, input-dependent B / C, any dstate in 1..256."""
+    _check(seq_idx is not None, "selective_scan_varlen_fwd: seq_idx is required")
+    return selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=need_out, need_x=need_x, seq_idx=seq_idx)
+
+
+def selective_scan_varlen_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, seq_idx, dB=None, dC=None):
+    """selective_scan_general_bwd on packed rows: the adjoint state is not handed across a boundary and the terms through a_t h_{t-1} vanish there"""
+    _check(seq_idx is not None, "selective_scan_varlen_bwd: seq_idx is required")
+    return selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, dB=dB, dC=dC, seq_idx=seq_idx)
+
+
+def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=True, need_x=True, *, seq_idx=None):
     """-> [out, x, (out_z)] like selective_scan_cuda.fwd, on the general kernels: A float32 or complex64 (dim, dstate), dstate 1..256; B / C
     input-dependent (batch, groups, dstate, seqlen) -- (.., 2 seqlen) reals with complex A -- or constant (dim, dstate) of A's dtype.
-    x is (batch, dim, n_chunks, 2 dstate) of A's dtype. None of the inference extras of selective_scan_fwd."""
+    x is (batch, dim, n_chunks, 2 dstate) of A's dtype. None of the inference extras of selective_scan_fwd.
+    seq_idx: selective_scan_varlen_fwd's (packed rows)."""
     flags = _check_ssm_general(u, delta, A, B, C, D, z, delta_bias)
+    if seq_idx is not None:
+        _check_scan_seq_idx(seq_idx, u, flags, "selective_scan_varlen_fwd")
     batch, dim, seqlen = u.shape
     dstate = A.shape[1]
     out = torch.empty_like(delta) if need_out else None
     x = torch.empty((batch, dim, (seqlen + 2047) // 2048, dstate * 2), device=u.device, dtype=A.dtype) if need_x else None
     out_z = torch.empty_like(z) if z is not None else None
-    if u.numel() > 0:
+    if u.numel() > 0 and seq_idx is not None:
+        V = _lib.SsmVarlenParams()
+        _fill_ssm_general(V.scan, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags)
+        V.seq_idx_ptr, V.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
+        with torch.cuda.device(u.device):
+            _lib.check(_lib.load().dimsum_ssm_scan_varlen_fwd(V, _stream(u)), "selective_scan_varlen_fwd")
+    elif u.numel() > 0:
         P = _lib.SsmGeneralParams()
         _fill_ssm_general(P, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags)
         with torch.cuda.device(u.device):
@@ -1017,12 +1113,14 @@ def selective_scan_carry_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus
     return out_z if z is not None else out
 
 
-def selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, dB=None, dC=None):
+def selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, dB=None, dC=None, *, seq_idx=None):
     """-> [du, ddelta, dA, dB, dC, dD, ddelta_bias, (dz)] like selective_scan_cuda.bwd (without recompute_out_z), on the general kernels.
     dA / constant dB / dC come back in A's dtype, input-dependent dB / dC in B's / C's; a caller may hand in fp32 buffers of B's / C's shape
     (unit stride along the sequence) for input-dependent dB / dC: they are zero-filled here (the kernel adds into them) and returned as they are."""
     flags = _check_ssm_general(u, delta, A, B, C, D, z, delta_bias)
     cplx, var_B, var_C, groups = flags
+    if seq_idx is not None:
+        _check_scan_seq_idx(seq_idx, u, flags, "selective_scan_varlen_bwd")
     _gpu(dout, out, dz)
     batch, dim, seqlen = u.shape
     dstate = A.shape[1]
@@ -1047,7 +1145,8 @@ def selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, d
     dD = torch.zeros_like(D) if D is not None else None
     ddelta_bias = torch.zeros_like(delta_bias) if delta_bias is not None else None
     if u.numel() > 0:
-        Q = _lib.SsmGeneralBwdParams()
+        V = _lib.SsmVarlenBwdParams() if seq_idx is not None else None
+        Q = V.bwd if V is not None else _lib.SsmGeneralBwdParams()
         _fill_ssm_general(Q.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out if z is not None else None, None, None, flags)
         Q.dout_batch_stride, Q.dout_d_stride = dout.stride(0), dout.stride(1)
         Q.dA_d_stride, Q.dA_dstate_stride = dA.stride(0), dA.stride(1)
@@ -1066,7 +1165,11 @@ def selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, d
         ws = torch.empty((nbytes + 3) // 4, device=u.device, dtype=torch.float32)
         Q.workspace_ptr, Q.workspace_bytes = _ptr(ws), nbytes
         with torch.cuda.device(u.device):
-            _lib.check(_lib.load().dimsum_ssm_scan_general_bwd(Q, _stream(u)), "selective_scan_general_bwd")
+            if V is not None:
+                V.seq_idx_ptr, V.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
+                _lib.check(_lib.load().dimsum_ssm_scan_varlen_bwd(V, _stream(u)), "selective_scan_varlen_bwd")
+            else:
+                _lib.check(_lib.load().dimsum_ssm_scan_general_bwd(Q, _stream(u)), "selective_scan_general_bwd")
         del ws
     res = [du, ddelta, dA, dB.to(B.dtype) if var_B and own[0] else dB, dC.to(C.dtype) if var_C and own[1] else dC, dD, ddelta_bias]
     if z is not None:

@@ -26,9 +26,60 @@ class CausalConv1dFn(torch.autograd.Function):
         return dx, dweight, dbias if bias is not None else None, None
 
 
-def causal_conv1d_fn(x, weight, bias=None, activation=None):
-    """x: (batch, dim, seqlen), weight: (dim, width), bias: (dim,), activation: None | "silu" | "swish"."""
+class CausalConv1dVarlenFn(torch.autograd.Function):
+    """causal_conv1d_fn(seq_idx=...): packed rows on the kVarlen kernels of csrc/causal_conv1d.hip"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, activation, seq_idx):
+        if activation not in (None, "silu", "swish"):
+            raise NotImplementedError("activation must be None, silu, or swish")
+        if x.stride(2) != 1:
+            x = x.contiguous()          # the packed-row kernels read seqlen-contiguous rows (free batch and channel strides)
+        bias = bias.contiguous() if bias is not None else None
+        ctx.save_for_backward(x, weight, bias, seq_idx)
+        ctx.activation = activation in ("silu", "swish")
+        return native.causal_conv1d_varlen_fwd(x, weight, bias, ctx.activation, seq_idx)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, bias, seq_idx = ctx.saved_tensors
+        if dout.stride(2) != 1:
+            dout = dout.contiguous()
+        dx, dweight, dbias = native.causal_conv1d_varlen_bwd(x, weight, bias, dout, None, ctx.activation, seq_idx)
+        return dx, dweight, dbias if bias is not None else None, None, None
+
+
+def causal_conv1d_fn(x, weight, bias=None, activation=None, seq_idx=None):
+    """x: (batch, dim, seqlen), weight: (dim, width), bias: (dim,), activation: None | "silu" | "swish".
+    seq_idx (batch, seqlen) int32, contiguous: packed rows -- a tap that would reach across a change of the id is dropped (position t >= 1 is
+    a boundary iff seq_idx[b, t] != seq_idx[b, t - 1]; the values are only compared). None: the call it always was."""
+    if seq_idx is not None:
+        return CausalConv1dVarlenFn.apply(x, weight, bias, activation, seq_idx)
     return CausalConv1dFn.apply(x, weight, bias, activation)
+
+
+def causal_conv1d_varlen_torch(x, weight, bias=None, activation=None, seq_idx=None):
+    """causal_conv1d_fn(seq_idx=...) written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer): a
+    loop over the positions, tap j of position t counted iff t - j >= 0 and no boundary lies in (t - j, t]. Differentiable. What the tests
+    compare the kernels with and what CPU tests put in their place; never a fallback: nothing in the package calls it."""
+    silu = {None: False, "silu": True, "swish": True}.get(activation)
+    if silu is None:
+        raise NotImplementedError(f"causal_conv1d_varlen_torch: activation {activation!r} (None, 'silu' or 'swish')")
+    batch, dim, seqlen = x.shape
+    width = weight.shape[-1]
+    assert weight.shape == (dim, width) and (seq_idx is None or tuple(seq_idx.shape) == (batch, seqlen))
+    zero = x.new_zeros(batch, dim)
+    cols = []
+    for t in range(seqlen):
+        pre = x[:, :, t] * weight[:, width - 1]
+        same = torch.ones(batch, dtype=torch.bool, device=x.device)               # no boundary in (t - j, t] so far
+        for j in range(1, min(width, t + 1)):
+            if seq_idx is not None:
+                same = same & (seq_idx[:, t - j + 1] == seq_idx[:, t - j])
+            pre = pre + torch.where(same[:, None], x[:, :, t - j], zero) * weight[:, width - 1 - j]
+        cols.append(pre if bias is None else pre + bias)
+    pre = torch.stack(cols, dim=-1)
+    return (pre * torch.sigmoid(pre) if silu else pre).to(x.dtype)
 
 
 def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None):

@@ -22,7 +22,12 @@ real with a last axis of 2 seqlen). What the tuned kernels are not built for -- 
 in 1..256 the same way, without the fused extras (dt_proj inside the scan, out_z operand images, f16s training).
 selective_scan_fn(..., initial_state=h) starts from a carried (batch, dim, dstate) state instead of zeros (inference only, no graph): the general
 kernel's carried-state entry point for every dstate; without it the routing is what it was.
-Not implemented (raise): complex A and constant B / C inside mamba_inner_fn* and bimamba_inner_fn; a dstate outside {4, 8, 16, 32} inside
+seq_idx (batch, seqlen) int32 -- packed rows, upstream Mamba's per-token sequence id: the sequences of one row do not see each other (the conv
+drops the taps that cross a change of the id, the scan restarts its state there). selective_scan_fn(seq_idx=...) runs the packed-row
+instantiations of the general kernels whatever the dstate; mamba_inner_fn / mamba_inner_fn_no_out_proj(seq_idx=...) run the plain sequence
+conv -> x_proj / dt_proj -> scan -> out_proj on them under autograd, none of the fused extras. seq_idx=None is the call it always was.
+Not implemented (raise): seq_idx with complex A, constant B / C, a carried initial_state, conv_done, the _cond forms' init_states (bimamba_inner_fn has no such argument);
+complex A and constant B / C inside mamba_inner_fn* and bimamba_inner_fn; a dstate outside {4, 8, 16, 32} inside
 bimamba_inner_fn.
 """
 import os
@@ -33,6 +38,7 @@ import torch.nn.functional as F
 from torch.amp import custom_bwd, custom_fwd
 
 from .. import gemm, native
+from .causal_conv1d_interface import causal_conv1d_fn
 
 
 def _last_contig(t):
@@ -86,6 +92,74 @@ class SelectiveScanFn(torch.autograd.Function):
         return (du, ddelta, dA, dB, dC, dD if ctx.has_D else None, dz, ddelta_bias if ctx.has_bias else None, None, None, None)
 
 
+class SelectiveScanVarlenFn(torch.autograd.Function):
+    """selective_scan_fn(seq_idx=...): packed rows on the kVarlen instantiations of csrc/ssm_scan_general.hip, whatever the dstate"""
+
+    @staticmethod
+    def forward(ctx, u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, seq_idx):
+        u, delta, B, C, z = (_last_contig(t) for t in (u, delta, B, C, z))
+        D = D.contiguous() if D is not None else None
+        ctx.squeeze_B, ctx.squeeze_C = B.dim() == 3, C.dim() == 3
+        B = B.unsqueeze(1) if ctx.squeeze_B else B
+        C = C.unsqueeze(1) if ctx.squeeze_C else C
+        ctx.delta_softplus, ctx.has_z, ctx.has_D, ctx.has_bias = delta_softplus, z is not None, D is not None, delta_bias is not None
+        out, x, *rest = native.selective_scan_varlen_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, seq_idx)
+        ctx.save_for_backward(u, delta, A, B, C, D, z, delta_bias, out if ctx.has_z else None, seq_idx)
+        res = rest[0] if ctx.has_z else out
+        return res if not return_last_state else (res, x[:, :, -1, 1::2])      # the state of the row's last segment
+
+    @staticmethod
+    def backward(ctx, dout, *args):
+        u, delta, A, B, C, D, z, delta_bias, out, seq_idx = ctx.saved_tensors
+        du, ddelta, dA, dB, dC, dD, ddelta_bias, *rest = native.selective_scan_varlen_bwd(
+            u, delta, A, B, C, D, z, delta_bias, _last_contig(dout), out, None, ctx.delta_softplus, seq_idx)
+        dB = dB.squeeze(1) if ctx.squeeze_B else dB
+        dC = dC.squeeze(1) if ctx.squeeze_C else dC
+        return (du, ddelta, dA, dB, dC, dD if ctx.has_D else None, rest[0] if ctx.has_z else None, ddelta_bias if ctx.has_bias else None,
+                None, None, None)
+
+
+def _refuse_varlen_scan(who, A, B, C):
+    """what the packed-row scan kernels are not instantiated for (nothing asks for these combinations)"""
+    if A.is_complex():
+        raise NotImplementedError(f"{who}: seq_idx with a complex A is not built: the packed-row scan kernels are instantiated for real A with "
+                                  "input-dependent B and C")
+    if (B is not None and B.dim() < 3) or (C is not None and C.dim() < 3):
+        raise NotImplementedError(f"{who}: seq_idx with a constant (dim, dstate) B or C is not built: the packed-row scan kernels are "
+                                  "instantiated for real A with input-dependent B and C")
+
+
+def selective_scan_varlen_torch(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False, seq_idx=None):
+    """selective_scan_fn(seq_idx=...) written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer): a
+    loop over the positions, h_t = (1 - r_t) exp(dt_t A) h_{t-1} + dt_t B_t u_t with r_t = 1 where seq_idx changes; real A, B / C
+    (batch, dstate, seqlen) or (batch, groups, dstate, seqlen). Differentiable. What the tests compare the kernels with and what CPU tests put
+    in their place; never a fallback: nothing in the package calls it."""
+    batch, dim, seqlen = u.shape
+    N = A.shape[-1]
+    B4 = B.unsqueeze(1) if B.dim() == 3 else B
+    C4 = C.unsqueeze(1) if C.dim() == 3 else C
+    rep = dim // B4.shape[1]
+    dt = delta if delta_bias is None else delta + delta_bias[None, :, None]
+    if delta_softplus:
+        dt = torch.where(dt <= 20.0, F.softplus(dt), dt)
+    h = u.new_zeros(batch, dim, N)
+    ys = []
+    for t in range(seqlen):
+        if seq_idx is not None and t > 0:
+            h = torch.where((seq_idx[:, t] != seq_idx[:, t - 1])[:, None, None], torch.zeros_like(h), h)
+        Bt = B4[:, :, :, t].repeat_interleave(rep, dim=1)                         # (batch, dim, dstate)
+        Ct = C4[:, :, :, t].repeat_interleave(rep, dim=1)
+        h = torch.exp(dt[:, :, t, None] * A[None]) * h + (dt[:, :, t] * u[:, :, t])[:, :, None] * Bt
+        ys.append((h * Ct).sum(-1))
+    y = torch.stack(ys, dim=-1)
+    if D is not None:
+        y = y + D[None, :, None] * u
+    if z is not None:
+        y = y * (z * torch.sigmoid(z))
+    y = y.to(u.dtype)
+    return y if not return_last_state else (y, h)
+
+
 def _selective_scan_carry(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, initial_state):
     """selective_scan_fn(initial_state=...): the general kernel for every dstate (csrc/ssm_scan_general.hip, dimsum_ssm_scan_carry_fwd), no graph"""
     if _will_backprop(u, delta, A, B, C, D, z, delta_bias, initial_state):
@@ -101,11 +175,21 @@ def _selective_scan_carry(u, delta, A, B, C, D, z, delta_bias, delta_softplus, r
     return out if not return_last_state else (out, last)
 
 
-def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False, initial_state=None):
+def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False, initial_state=None,
+                      seq_idx=None):
     """out (or (out, last_state)); the gradient of last_state is not propagated (as in the reference).
     initial_state (batch, dim, dstate), float32 or of u's dtype (complex64 with complex A): the scan starts from it instead of from zeros --
     a cached sequence continued by seqlen tokens; last_state then comes back in its dtype. An inference argument: no graph is recorded, and
-    inputs that require grad under grad mode are refused. Such a call runs on the general kernel whatever the dstate."""
+    inputs that require grad under grad mode are refused. Such a call runs on the general kernel whatever the dstate.
+    seq_idx (batch, seqlen) int32, contiguous: packed rows -- position t >= 1 is a boundary iff seq_idx[b, t] != seq_idx[b, t - 1] (the values
+    are only compared), and the state restarts there: every segment gets what it gets as a row of its own, last_state is the last
+    segment's. With autograd. Runs the packed-row general kernels whatever the dstate; real A and input-dependent B / C only."""
+    if seq_idx is not None:
+        if initial_state is not None:
+            raise NotImplementedError("selective_scan_fn: seq_idx together with a carried initial_state is not built: a packed row starts from "
+                                      "zero state (there is no packed-row form of the carried-state kernel)")
+        _refuse_varlen_scan("selective_scan_fn", A, B, C)
+        return SelectiveScanVarlenFn.apply(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, seq_idx)
     if initial_state is not None:
         return _selective_scan_carry(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, initial_state)
     return SelectiveScanFn.apply(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state,
@@ -422,35 +506,77 @@ class _MambaInner(torch.autograd.Function):
                 ddelta_bias if has_dbias else None, dB_proj_bias, dC_proj_bias, None, None, None, None, None, None, None, None)
 
 
-def _mamba_inner(has_out_proj, xz, *a, init_states=None, conv_done=False, last_state=None):
+def _mamba_inner_varlen(has_out_proj, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D,
+                        delta_bias, B_proj_bias, C_proj_bias, delta_softplus, seq_idx, last_state=None):
+    """mamba_inner_fn(seq_idx=...): the general route's plain sequence on packed rows, conv -> x_proj / dt_proj -> scan -> out_proj, each piece
+    under its own autograd node (causal_conv1d_fn and selective_scan_fn with seq_idx; the projections are GEMMs): no dt_proj in the scan, no
+    operand images, no f16s training, no saved-state extras. last_state receives the state of every row's last segment."""
+    if A.is_complex():
+        raise NotImplementedError("mamba_inner_fn: complex A is outside this build's scope")
+    if B is not None or C is not None:
+        raise NotImplementedError("mamba_inner_fn: constant B/C is outside this build's scope")
+    xz, conv_w, conv_b, x, z, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias = _prologue(
+        xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight if has_out_proj else None, out_proj_bias if has_out_proj else None)
+    bsz, d_inner, L = x.shape
+    N, R = A.shape[-1], delta_proj_weight.shape[1]
+    conv_out = causal_conv1d_fn(x, conv_w, conv_b, "silu", seq_idx)
+    x_dbl = F.linear(conv_out.transpose(1, 2).reshape(bsz * L, d_inner), x_proj_weight)            # (b l, R + 2N)
+    delta = _delta(delta_proj_weight, x_dbl[:, :R].t(), bsz, L)
+    Bm = x_dbl[:, R:R + N] if B_proj_bias is None else x_dbl[:, R:R + N] + B_proj_bias.to(x_dbl.dtype)
+    Cm = x_dbl[:, -N:] if C_proj_bias is None else x_dbl[:, -N:] + C_proj_bias.to(x_dbl.dtype)
+    Bm = Bm.reshape(bsz, L, N).permute(0, 2, 1).unsqueeze(1).contiguous()                           # (b, 1, N, l)
+    Cm = Cm.reshape(bsz, L, N).permute(0, 2, 1).unsqueeze(1).contiguous()
+    out_z = selective_scan_fn(conv_out, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, return_last_state=last_state is not None, seq_idx=seq_idx)
+    if last_state is not None:
+        out_z, last = out_z
+        with torch.no_grad():
+            last_state.copy_(last)
+    if not has_out_proj:
+        return out_z
+    oz_t = out_z.transpose(1, 2)
+    return gemm.linear(oz_t, out_proj_weight) if out_proj_bias is None else F.linear(oz_t, out_proj_weight, out_proj_bias)
+
+
+def _mamba_inner(has_out_proj, xz, *a, init_states=None, conv_done=False, last_state=None, seq_idx=None):
     """a: conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias, B_proj_bias, C_proj_bias,
     delta_softplus -- _MambaInner.apply's order"""
+    if seq_idx is not None:
+        if conv_done:
+            raise NotImplementedError("mamba_inner_fn: conv_done with seq_idx is not built: the in_proj + conv epilogue takes no sequence ids, so "
+                                      "xz cannot already hold the packed-row conv")
+        if init_states is not None:
+            raise NotImplementedError("mamba_inner_fn_cond: init_states with seq_idx is not built: the conditional entry has no packed-row form")
+        return _mamba_inner_varlen(has_out_proj, xz, *a, seq_idx, last_state=last_state)
     wb = _will_backprop(xz, *a[:-1], init_states)
     return _MambaInner.apply(xz, *a, init_states, has_out_proj, _checkpoint_lvl(), wb, conv_done, _f16s_train(xz, a[4], wb), last_state)
 
 
 def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A,
-                   B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True):
+                   B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True, seq_idx=None):
     return _mamba_inner(True, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias,
-                        B_proj_bias, C_proj_bias, delta_softplus)
+                        B_proj_bias, C_proj_bias, delta_softplus, **({"seq_idx": seq_idx} if seq_idx is not None else {}))
 
 
 def mamba_inner_fn_cond(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                         A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None,
-                        delta_softplus=True, init_states=None, conv_done=False, last_state=None):
+                        delta_softplus=True, init_states=None, conv_done=False, last_state=None, seq_idx=None):
+    """seq_idx: the packed-row route of mamba_inner_fn (last_state is honoured); init_states or conv_done with it raise NotImplementedError"""
     return _mamba_inner(True, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias,
-                        B_proj_bias, C_proj_bias, delta_softplus, init_states=init_states, conv_done=conv_done, last_state=last_state)
+                        B_proj_bias, C_proj_bias, delta_softplus, init_states=init_states, conv_done=conv_done, last_state=last_state,
+                        **({"seq_idx": seq_idx} if seq_idx is not None else {}))
 
 
 def mamba_inner_fn_no_out_proj(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, B=None, C=None,
-                               D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True):
+                               D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True, seq_idx=None):
     return _mamba_inner(False, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, None, None, A, B, C, D, delta_bias,
-                        B_proj_bias, C_proj_bias, delta_softplus)
+                        B_proj_bias, C_proj_bias, delta_softplus, **({"seq_idx": seq_idx} if seq_idx is not None else {}))
 
 
 def mamba_inner_fn_no_out_proj_cond(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, B=None, C=None,
                                     D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True,
-                                    init_states=None):
+                                    init_states=None, seq_idx=None):
+    if seq_idx is not None:
+        raise NotImplementedError("mamba_inner_fn_no_out_proj_cond: seq_idx is not built for the conditional form; call mamba_inner_fn_no_out_proj")
     return _mamba_inner(False, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, None, None, A, B, C, D, delta_bias,
                         B_proj_bias, C_proj_bias, delta_softplus, init_states=init_states)
 
@@ -543,7 +669,8 @@ class _BiMambaInner(torch.autograd.Function):
 
 def bimamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, A_b,
                      B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True):
-    """the fused bidirectional Mamba mixer (selective_scan_interface.py:1351-1388): real A / A_b, input-dependent B / C, -> (b, l, d_model)"""
+    """the fused bidirectional Mamba mixer (selective_scan_interface.py:1351-1388): real A / A_b, input-dependent B / C, -> (b, l, d_model).
+    It takes no seq_idx (its signature is the reference's): the bidirectional scan kernels have no packed-row form."""
     wb = _will_backprop(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, A_b, B, C, D,
                         delta_bias, B_proj_bias, C_proj_bias)
     return _BiMambaInner.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,

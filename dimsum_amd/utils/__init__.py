@@ -34,6 +34,33 @@ def chunked_prefill(mixer, hidden_states, inference_params, chunk, *cond):
     return torch.cat(outs, dim=1)
 
 
+def seq_idx_from_lengths(lengths, seqlen=None, device=None):
+    """one row's sequence ids from its segment lengths -> (seqlen,) int32: 0 for the first `lengths[0]` positions, 1 for the next
+    `lengths[1]`, ... seqlen defaults to sum(lengths); a trailing remainder becomes a segment of its own (the next id). Stack the rows of a
+    batch with torch.stack. E.g. a prompt of 3 tokens left-padded to 9: seq_idx_from_lengths([6, 3])."""
+    lengths = [int(n) for n in lengths]
+    if any(n < 0 for n in lengths):
+        raise ValueError(f"seq_idx_from_lengths: negative length in {lengths}")
+    total = sum(lengths)
+    seqlen = total if seqlen is None else int(seqlen)
+    if total > seqlen:
+        raise ValueError(f"seq_idx_from_lengths: the lengths sum to {total}, more than seqlen = {seqlen}")
+    if total < seqlen:
+        lengths = lengths + [seqlen - total]
+    return torch.repeat_interleave(torch.arange(len(lengths), dtype=torch.int32), torch.tensor(lengths, dtype=torch.long)).to(device)
+
+
+def packed_labels(input_ids, seq_idx, ignore_index=-100):
+    """next-token labels of packed rows -> (batch, seqlen) int64: labels[b, t] = input_ids[b, t + 1] where t + 1 belongs to the segment of
+    t, else ignore_index -- the first token of every segment is nobody's target, and the row's last position has none. What
+    MambaLMHeadModel.loss(input_ids, labels, seq_idx=seq_idx) wants."""
+    assert input_ids.shape == seq_idx.shape and input_ids.dim() == 2
+    labels = torch.full_like(input_ids, ignore_index, dtype=torch.long)
+    same = seq_idx[:, 1:] == seq_idx[:, :-1]
+    labels[:, :-1] = torch.where(same, input_ids[:, 1:].long(), labels[:, :-1])
+    return labels
+
+
 @torch.no_grad()
 def rerandomize_zeros(model, std=0.02, seed=0):
     """The reference initialisation is adaLN-zero + zero final layer, so a freshly initialised DiM outputs exactly 0

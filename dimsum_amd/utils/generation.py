@@ -77,7 +77,8 @@ def fused_sampling_enabled(fused_sampling=None):
     return os.environ.get("DIMSUM_FUSED_SAMPLING", "") == "1"
 
 
-def _decode_fused(input_ids, model, max_length, top_k, top_p, temperature, eos_token_id, vocab_size, cg, generator, uniforms, output_scores):
+def _decode_fused(input_ids, model, max_length, top_k, top_p, temperature, eos_token_id, vocab_size, cg, generator, uniforms, output_scores,
+                  seq_idx=None):
     """`decode` on the fused sampler. uniforms (max_length, batch): row i draws the i-th new token. Eager: one sample_logits launch per token
     on the step's row. cg: the captured step samples from its own logits into its own input buffer and files the token in the cache's token
     table at the cache's step counter; the host only replays (and reads the newest token when it has to look for eos_token_id)."""
@@ -106,7 +107,7 @@ def _decode_fused(input_ids, model, max_length, top_k, top_p, temperature, eos_t
     scores, n = [], 0
     while True:
         if n == 0:
-            logits = model(input_ids, inference_params=inference_params, num_last_tokens=1).logits[:, -1]
+            logits = model(input_ids, inference_params=inference_params, num_last_tokens=1, **_prompt_kw(seq_idx)).logits[:, -1]
         elif cg:
             logits = step()[:, -1]                          # forward, sample, count: tokens[n] and the next input are in place
         else:
@@ -128,21 +129,30 @@ def _decode_fused(input_ids, model, max_length, top_k, top_p, temperature, eos_t
     return GenerationOutput(sequences=torch.cat([input_ids, tokens[:n].t()], dim=1), scores=tuple(scores))
 
 
+def _prompt_kw(seq_idx):
+    """what the prompt forward gets beyond the usual: the sequence ids of a packed / left-padded prompt, when there are any"""
+    return {} if seq_idx is None else {"seq_idx": seq_idx}
+
+
 @torch.no_grad()
 def decode(input_ids, model, max_length, top_k=1, top_p=0.0, temperature=1.0, eos_token_id=None, teacher_outputs=None, vocab_size=None, cg=False,
-           enable_timing=False, generator=None, fused_sampling=None, uniforms=None, output_scores=True):
+           enable_timing=False, generator=None, fused_sampling=None, uniforms=None, output_scores=True, seq_idx=None):
     """greedy / top-k / top-p decoding of input_ids (batch, seqlen), all rows of one length, up to max_length tokens in all; stops early once
     every row's newest token is eos_token_id. teacher_outputs (batch, seqlen'): tokens taken instead of sampled ones (testing).
     fused_sampling (None: DIMSUM_FUSED_SAMPLING, off when unset): sample with `sample_fused` on a (max_length, batch) float32 table of
     uniforms -- `uniforms`, or one torch.rand(generator=generator) draw per call -- whose row i draws the i-th new token; with cg=True the
     sampler is part of the captured step. teacher_outputs keeps the unfused sampler. output_scores=False lets the fused path skip the
     per-token copy of the logits.
+    seq_idx (batch, seqlen) int32: sequence ids of the prompt, handed to the prompt forward only -- rows of different lengths are left-padded
+    to one length with the padding as a segment of its own (dimsum_amd.utils.seq_idx_from_lengths([pad, n])), and every row then prefills and
+    decodes as if it stood alone. The decode steps continue every row's last segment and take no ids.
     -> GenerationOutput(sequences (batch, <= max_length), scores: one (batch, vocab) per generated token)"""
     if teacher_outputs is None and fused_sampling_enabled(fused_sampling):
         if enable_timing:
             start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             start.record()
-        out = _decode_fused(input_ids, model, max_length, top_k, top_p, temperature, eos_token_id, vocab_size, cg, generator, uniforms, output_scores)
+        out = _decode_fused(input_ids, model, max_length, top_k, top_p, temperature, eos_token_id, vocab_size, cg, generator, uniforms, output_scores,
+                            seq_idx=seq_idx)
         if enable_timing:
             end.record()
             torch.cuda.synchronize()
@@ -162,7 +172,7 @@ def decode(input_ids, model, max_length, top_k=1, top_p=0.0, temperature=1.0, eo
     def get_logits(ids):
         decoding = inference_params.seqlen_offset > 0
         if not cg or not decoding:
-            logits = model(ids, inference_params=inference_params, num_last_tokens=1).logits.squeeze(dim=1)
+            logits = model(ids, inference_params=inference_params, num_last_tokens=1, **({} if decoding else _prompt_kw(seq_idx))).logits.squeeze(dim=1)
         else:
             logits = model._decoding_cache.run(ids, inference_params.seqlen_offset).squeeze(dim=1)
         return logits[..., :vocab_size] if vocab_size is not None else logits
@@ -201,7 +211,7 @@ class GenerationMixin:
         raise NotImplementedError
 
     def generate(self, input_ids, max_length, top_k=1, top_p=0.0, temperature=1.0, return_dict_in_generate=False, output_scores=False, **kwargs):
-        """kwargs: cg, eos_token_id, teacher_outputs, vocab_size, enable_timing, generator, fused_sampling, uniforms (see `decode`)"""
+        """kwargs: cg, eos_token_id, teacher_outputs, vocab_size, enable_timing, generator, fused_sampling, uniforms, seq_idx (see `decode`)"""
         output = decode(input_ids, self, max_length, top_k=top_k, top_p=top_p, temperature=temperature, output_scores=output_scores, **kwargs)
         if not output_scores:
             output.scores = None

@@ -337,6 +337,36 @@ typedef struct {
 
 int dimsum_ssm_scan_carry_fwd(const dimsum_ssm_carry_params_t *p, void *stream);
 
+/* The general scan on PACKED rows (upstream Mamba's seq_idx; see dimsum_conv_varlen_params_t for seq_idx and what a boundary is). With
+ * r_t = 1 at a boundary and 0 elsewhere:
+ *     h_t = (1 - r_t) exp(dt_t A) h_{t-1} + dt_t B_t u_t        (the state restarts; h_{t-1} is dropped by a select, not multiplied by 0)
+ *   and everything else as dimsum_ssm_scan_general_fwd: the last chunk's x holds h_{L-1}, the state of the row's last segment; the running
+ *   product in x is 0 from the row's first boundary on. Backward: g_t = C_t dy_t + (1 - r_{t+1}) a_{t+1} g_{t+1}; the dA and ddelta terms
+ *   through a_t h_{t-1} vanish at a boundary (masked explicitly).
+ * Real A with input-dependent B and C only (any dstate in 1..256, n_groups, every dtype): complex A or a constant B / C is
+ * DIMSUM_ERR_UNSUPPORTED. There is no carried-state form. `scan` / `bwd` are read exactly as the general entry points read them (their
+ * struct_size is ignored); the backward's workspace is dimsum_ssm_scan_general_bwd_workspace_bytes(...).
+ * Checks: NULL struct / struct_size (DIMSUM_ERR_ABI) / the general entry point's checks in their order / seq_idx_ptr NULL (DIMSUM_ERR_NULL) /
+ * a negative seq_idx_batch_stride or one below seqlen with batch > 1 (DIMSUM_ERR_STRIDE) / complex A or constant B / C. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_ssm_varlen_params_t) */
+    uint32_t reserved;        /* 0 */
+    dimsum_ssm_general_params_t scan;
+    const void *seq_idx_ptr;
+    int64_t seq_idx_batch_stride;
+} dimsum_ssm_varlen_params_t;
+
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_ssm_varlen_bwd_params_t) */
+    uint32_t reserved;        /* 0 */
+    dimsum_ssm_general_bwd_params_t bwd;
+    const void *seq_idx_ptr;
+    int64_t seq_idx_batch_stride;
+} dimsum_ssm_varlen_bwd_params_t;
+
+int dimsum_ssm_scan_varlen_fwd(const dimsum_ssm_varlen_params_t *p, void *stream);
+int dimsum_ssm_scan_varlen_bwd(const dimsum_ssm_varlen_bwd_params_t *p, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Training-step tail: global gradient-norm clip + AdamW + parameter EMA over a list of fp32 tensors, two launches
  * (<- torch.nn.utils.clip_grad_norm_, torch.optim.AdamW.step and update_ema of dimsum/train.py:55-64,317-321).
@@ -591,6 +621,35 @@ typedef struct {
 
 int dimsum_causal_conv1d_fwd(const dimsum_conv_params_t *p, void *stream);
 int dimsum_causal_conv1d_bwd(const dimsum_conv_bwd_params_t *p, void *stream);
+
+/* The same conv on PACKED rows (upstream Mamba's seq_idx): several sequences share one (batch, seqlen) row and must not see each other.
+ *   seq_idx : (batch, seqlen) int32, unit stride along seqlen, rows seq_idx_batch_stride ELEMENTS apart. Position t >= 1 of a row is a
+ *       boundary iff seq_idx[b, t] != seq_idx[b, t - 1]; position 0 never is. The values are only compared with each other -- never an
+ *       index or an offset: any int32 content is memory-safe.
+ *   out[b, d, t] = act(bias[d] + sum_j W[d, width - 1 - j] x[b, d, t - j]) over the taps j with t - j >= 0 and no boundary in (t - j, t].
+ *   Backward: dx[t] collects only from later positions of its own segment; dweight sums the unmasked (tap, position) pairs, dbias every
+ *       position. A masked value is replaced by 0 (a select), so what lies beyond a boundary cannot reach a result whatever it holds.
+ * `conv` is read exactly as dimsum_causal_conv1d_fwd / _bwd read it (conv.struct_size is ignored). Checks: NULL struct / struct_size
+ * (DIMSUM_ERR_ABI) / the plain entry point's checks in their order / seq_idx_ptr NULL (DIMSUM_ERR_NULL) / a negative seq_idx_batch_stride or
+ * one below seqlen with batch > 1 (DIMSUM_ERR_STRIDE). Only the seqlen-contiguous layout; the channel-last kernels take no seq_idx. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_conv_varlen_params_t) */
+    uint32_t reserved;        /* 0 */
+    dimsum_conv_params_t conv;
+    const void *seq_idx_ptr;
+    int64_t seq_idx_batch_stride;
+} dimsum_conv_varlen_params_t;
+
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_conv_varlen_bwd_params_t) */
+    uint32_t reserved;        /* 0 */
+    dimsum_conv_bwd_params_t conv;
+    const void *seq_idx_ptr;
+    int64_t seq_idx_batch_stride;
+} dimsum_conv_varlen_bwd_params_t;
+
+int dimsum_causal_conv1d_varlen_fwd(const dimsum_conv_varlen_params_t *p, void *stream);
+int dimsum_causal_conv1d_varlen_bwd(const dimsum_conv_varlen_bwd_params_t *p, void *stream);
 
 /* The same conv on CHANNEL-LAST operands (causal_conv1d_channellast_fwd_kernel / _bwd_kernel, causal-conv1d/csrc/
  * causal_conv1d_fwd.cu:193-319, causal_conv1d_bwd.cu:306-494; host checks causal_conv1d.cpp:242-247, 376-379, 395-396):
