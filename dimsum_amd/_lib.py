@@ -262,6 +262,21 @@ class DecodeLinearParams(_Sized):
                                      "y_ptr", "residual_out_ptr", "conv_state_ptr")])
 
 
+class ConvUpdateSlotsParams(_Sized):
+    """dimsum_conv_update_slots_params_t: dimsum_causal_conv1d_update on a pool of states -- row b works on conv_state[slots[b]], slots[b] < 0 is a padding row"""
+    _fields_ = [("struct_size", u32), ("num_slots", i32), ("conv", ConvUpdateParams), ("slots_ptr", vp), ("slots_stride", i64)]
+
+
+class StateUpdateSlotsParams(_Sized):
+    """dimsum_state_update_slots_params_t: dimsum_selective_state_update on a pool of states, addressed like ConvUpdateSlotsParams"""
+    _fields_ = [("struct_size", u32), ("num_slots", i32), ("update", StateUpdateParams), ("slots_ptr", vp), ("slots_stride", i64)]
+
+
+class DecodeLinearSlotsParams(_Sized):
+    """dimsum_decode_linear_slots_params_t: dimsum_decode_linear whose conv epilogue works on a pool of conv states, addressed like ConvUpdateSlotsParams"""
+    _fields_ = [("struct_size", u32), ("num_slots", i32), ("linear", DecodeLinearParams), ("slots_ptr", vp), ("slots_stride", i64)]
+
+
 DECODE_NORM_NONE, DECODE_NORM_LAYER, DECODE_NORM_RMS = 0, 1, 2
 DECODE_MAX_BATCH = 16
 
@@ -443,6 +458,7 @@ EXPORTS = (
     "dimsum_einfft_dft", "dimsum_einfft_idft_real", "dimsum_einfft_mlp_fwd", "dimsum_einfft_mlp_bwd",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd", "dimsum_causal_conv1d_update", "dimsum_selective_state_update",
     "dimsum_decode_linear", "dimsum_cross_entropy_fwd", "dimsum_cross_entropy_bwd", "dimsum_sample_logits",
+    "dimsum_causal_conv1d_update_slots", "dimsum_selective_state_update_slots", "dimsum_decode_linear_slots",
     "dimsum_causal_conv1d_cl_fwd", "dimsum_causal_conv1d_cl_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
@@ -480,7 +496,9 @@ _SIGNATURES = (
         ("dimsum_decode_linear", DecodeLinearParams), ("dimsum_cross_entropy_fwd", CrossEntropyParams),
         ("dimsum_cross_entropy_bwd", CrossEntropyParams), ("dimsum_sample_logits", SampleLogitsParams),
         ("dimsum_causal_conv1d_varlen_fwd", ConvVarlenParams), ("dimsum_causal_conv1d_varlen_bwd", ConvVarlenBwdParams),
-        ("dimsum_ssm_scan_varlen_fwd", SsmVarlenParams), ("dimsum_ssm_scan_varlen_bwd", SsmVarlenBwdParams))]
+        ("dimsum_ssm_scan_varlen_fwd", SsmVarlenParams), ("dimsum_ssm_scan_varlen_bwd", SsmVarlenBwdParams),
+        ("dimsum_causal_conv1d_update_slots", ConvUpdateSlotsParams), ("dimsum_selective_state_update_slots", StateUpdateSlotsParams),
+        ("dimsum_decode_linear_slots", DecodeLinearSlotsParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

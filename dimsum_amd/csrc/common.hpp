@@ -258,6 +258,17 @@ inline int ssm_args_from(const dimsum_ssm_params_t *p, ssm_args_t &a, bool check
 // ---- host ----------------------------------------------------------------------------------------------------------
 inline int launch_status() { return hipGetLastError() == hipSuccess ? DIMSUM_OK : DIMSUM_ERR_LAUNCH; }
 
+// The own checks of a slot-indexed entry point (dimsum_*_slots_params_t: struct_size, num_slots, <the plain struct>, slots_ptr, slots_stride),
+// in the header's order, before the embedded struct is looked at. The VALUES of the slots are the caller's contract: never read here.
+template <typename V> inline int slots_check(const V *v) {
+    if (!v) return DIMSUM_ERR_NULL;
+    if (v->struct_size != sizeof(V)) return DIMSUM_ERR_ABI;
+    if (v->num_slots < 1) return DIMSUM_ERR_SHAPE;
+    if (!v->slots_ptr) return DIMSUM_ERR_NULL;
+    if (v->slots_stride < 0) return DIMSUM_ERR_STRIDE;
+    return DIMSUM_OK;
+}
+
 // Kernel-boundary timing (dimsum_ssm_ext_t.timing_start_event / timing_stop_event): hipExtLaunchKernelGGL records the events
 // at the begin / end of the kernel's own dispatch packet -- what rocprofv3 reports -- instead of as separate commands around it.
 #define DIMSUM_LAUNCH_EV(KERNEL, GRID, BLOCK, STREAM, EV0, EV1, ...)                                              \

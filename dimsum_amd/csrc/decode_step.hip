@@ -27,7 +27,13 @@
 //     the mean lost, and x' = ((r - mean) - corr) * rstd, var = mean(d^2) - corr^2. RMSNorm has mean = corr = 0: its arithmetic is unchanged.
 //   * Epilogue: the lane holding y[b, n], n < conv_dim, rolls conv_state[b, n, :], appends y rounded to T and computes
 //     act(bias_c[n] + sum_w Wc[n, w] state[w]) with the expressions of causal_conv1d_update_kernel. Only that lane touches that state row.
+//   * Slot-indexed conv states (dimsum_decode_linear_slots, kSlots): conv_state is a pool and the lane holding y[b, n] works on
+//     conv_state[slots[b], n, :]; slots[b] < 0 stores a zero and touches no state; the plain columns are written as ever. A template flag on
+//     the kernel: one epilogue for both forms, and kSlots = false (the plain struct as the kernel's first argument, the state row b) compiles
+//     to the kernel as it was. The index is trusted: < num_slots and unique per launch is the caller's contract (include/dimsum_hip.h).
 #include "common.hpp"
+
+#include <type_traits>
 
 namespace dimsum {
 
@@ -113,10 +119,21 @@ template <typename T> __device__ __forceinline__ float stream_value(const dimsum
     return r;
 }
 
+// the slot form's first kernel argument: the plain parameters and the (batch) int32 slot index of the conv epilogue's states
+struct decode_slots_args_t {
+    dimsum_decode_linear_params_t p;
+    const int32_t *slots;
+    int64_t slots_stride;
+};
+__device__ __forceinline__ const dimsum_decode_linear_params_t &decode_base(const dimsum_decode_linear_params_t &a) { return a; }
+__device__ __forceinline__ const dimsum_decode_linear_params_t &decode_base(const decode_slots_args_t &a) { return a.p; }
+
 // T: x, W, bias, y, norm and conv weights, conv state. kBatch: the batch rounded up to a power of two (rows beyond p.batch are zeros in LDS).
 // kRows: output rows per wave. blockDim.x / 64 waves; workgroup g owns rows [g * waves * kRows, (g + 1) * waves * kRows).
-template <typename T, int kBatch, int kRows>
-__global__ __launch_bounds__(kMaxThreads) void decode_linear_kernel(const dimsum_decode_linear_params_t p, const decode_flags_t fl) {
+template <typename T, int kBatch, int kRows, bool kSlots>
+__global__ __launch_bounds__(kMaxThreads) void decode_linear_kernel(
+    const std::conditional_t<kSlots, decode_slots_args_t, dimsum_decode_linear_params_t> ka, const decode_flags_t fl) {
+    const dimsum_decode_linear_params_t &p = decode_base(ka);
     constexpr int E = Piece<T>::kElems;
     constexpr int kChunk = kChunkPieces * E;                // elements of K per chunk
     constexpr int V = kRows * kBatch;
@@ -273,7 +290,15 @@ __global__ __launch_bounds__(kMaxThreads) void decode_linear_kernel(const dimsum
     }
     // ---- one step of the causal conv1d on channel n (conv_update_row of csrc/mixer_step.hip, element path) ----
     const int W = p.conv_width;
-    T *st = reinterpret_cast<T *>(p.conv_state_ptr) + (int64_t)b * p.state_batch_stride + n * p.state_c_stride;
+    int64_t sb = b;                 // the row of conv_state this batch row works on
+    if constexpr (kSlots) {
+        sb = ka.slots[b * ka.slots_stride];
+        if (sb < 0) {               // a padding row: no state touched, a zero where the conv output goes
+            *y = from_f32<T>(0.f);
+            return;
+        }
+    }
+    T *st = reinterpret_cast<T *>(p.conv_state_ptr) + sb * p.state_batch_stride + n * p.state_c_stride;
     T s[4];     // the NEW state, right-aligned into 4 slots
 #pragma unroll
     for (int k = 0; k < 3; ++k) s[k] = (k >= 4 - W) ? st[(k - (4 - W) + 1) * p.state_w_stride] : from_f32<T>(0.f);
@@ -291,7 +316,7 @@ __global__ __launch_bounds__(kMaxThreads) void decode_linear_kernel(const dimsum
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-template <typename T, int kBatch> static int launch_decode_linear(const dimsum_decode_linear_params_t &p, hipStream_t s) {
+template <typename T, int kBatch> static int launch_decode_linear(const dimsum_decode_linear_params_t &p, hipStream_t s, const int32_t *slots, int64_t slots_stride) {
     decode_flags_t fl;
     fl.vec_w = aligned_to<T>(p.w_ptr, 16) && (p.n == 1 || (p.w_row_stride * (int64_t)sizeof(T)) % 16 == 0);
     fl.vec_x = !p.norm && aligned_to<T>(p.x_ptr, 16) && (p.batch == 1 || (p.x_row_stride * (int64_t)sizeof(T)) % 16 == 0);
@@ -299,17 +324,21 @@ template <typename T, int kBatch> static int launch_decode_linear(const dimsum_d
     const int64_t wave_rows = ((int64_t)p.n + rows - 1) / rows;
     const int waves = wave_rows <= 512 ? 1 : (p.batch <= 4 ? 4 : kMaxThreads / kWave);
     const dim3 grid((unsigned)((wave_rows + waves - 1) / waves)), block((unsigned)(waves * kWave));
-    if (rows == 4) hipLaunchKernelGGL((decode_linear_kernel<T, kBatch, 4>), grid, block, 0, s, p, fl);
-    else hipLaunchKernelGGL((decode_linear_kernel<T, kBatch, 1>), grid, block, 0, s, p, fl);
+    if (slots) {
+        const decode_slots_args_t a = {p, slots, slots_stride};
+        if (rows == 4) hipLaunchKernelGGL((decode_linear_kernel<T, kBatch, 4, true>), grid, block, 0, s, a, fl);
+        else hipLaunchKernelGGL((decode_linear_kernel<T, kBatch, 1, true>), grid, block, 0, s, a, fl);
+    } else if (rows == 4) hipLaunchKernelGGL((decode_linear_kernel<T, kBatch, 4, false>), grid, block, 0, s, p, fl);
+    else hipLaunchKernelGGL((decode_linear_kernel<T, kBatch, 1, false>), grid, block, 0, s, p, fl);
     return launch_status();
 }
 
-template <typename T> static int dispatch_decode_linear(const dimsum_decode_linear_params_t &p, hipStream_t s) {
-    if (p.batch == 1) return launch_decode_linear<T, 1>(p, s);
-    if (p.batch == 2) return launch_decode_linear<T, 2>(p, s);
-    if (p.batch <= 4) return launch_decode_linear<T, 4>(p, s);
-    if (p.batch <= 8) return launch_decode_linear<T, 8>(p, s);
-    return launch_decode_linear<T, 16>(p, s);
+template <typename T> static int dispatch_decode_linear(const dimsum_decode_linear_params_t &p, hipStream_t s, const int32_t *slots, int64_t slots_stride) {
+    if (p.batch == 1) return launch_decode_linear<T, 1>(p, s, slots, slots_stride);
+    if (p.batch == 2) return launch_decode_linear<T, 2>(p, s, slots, slots_stride);
+    if (p.batch <= 4) return launch_decode_linear<T, 4>(p, s, slots, slots_stride);
+    if (p.batch <= 8) return launch_decode_linear<T, 8>(p, s, slots, slots_stride);
+    return launch_decode_linear<T, 16>(p, s, slots, slots_stride);
 }
 
 // [ptr, ptr + ((rows - 1) * stride + cols) * elem) of two (rows, cols) operands with unit column stride
@@ -319,12 +348,8 @@ static bool rows_overlap(const void *a, int64_t a_stride, size_t a_elem, const v
     return a0 < b1 && b0 < a1;
 }
 
-}  // namespace dimsum
-
-extern "C" int dimsum_decode_linear(const dimsum_decode_linear_params_t *p, void *stream) {
-    using namespace dimsum;
-    if (!p) return DIMSUM_ERR_NULL;
-    if (p->struct_size != sizeof(dimsum_decode_linear_params_t)) return DIMSUM_ERR_ABI;
+// the checks of dimsum_decode_linear after NULL / struct_size, and the launch; slots != nullptr: the slot form
+static int decode_linear_run(const dimsum_decode_linear_params_t *p, hipStream_t s, const int32_t *slots, int64_t slots_stride) {
     if (!p->x_ptr || !p->w_ptr || !p->y_ptr) return DIMSUM_ERR_NULL;
     if (p->norm && !p->norm_weight_ptr) return DIMSUM_ERR_NULL;
     if (p->conv_dim && (!p->conv_weight_ptr || !p->conv_state_ptr)) return DIMSUM_ERR_NULL;
@@ -344,10 +369,26 @@ extern "C" int dimsum_decode_linear(const dimsum_decode_linear_params_t *p, void
         if (p->residual_ptr && rows_overlap(p->residual_out_ptr, p->residual_out_row_stride, rs, p->residual_ptr, p->residual_row_stride, rs, p->batch, p->k))
             return DIMSUM_ERR_ALIAS;
     }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (p->dtype) {
-        case DIMSUM_F32: return dispatch_decode_linear<float>(*p, s);
-        case DIMSUM_F16: return dispatch_decode_linear<__half>(*p, s);
-        default: return dispatch_decode_linear<__hip_bfloat16>(*p, s);
+        case DIMSUM_F32: return dispatch_decode_linear<float>(*p, s, slots, slots_stride);
+        case DIMSUM_F16: return dispatch_decode_linear<__half>(*p, s, slots, slots_stride);
+        default: return dispatch_decode_linear<__hip_bfloat16>(*p, s, slots, slots_stride);
     }
+}
+
+}  // namespace dimsum
+
+extern "C" int dimsum_decode_linear(const dimsum_decode_linear_params_t *p, void *stream) {
+    using namespace dimsum;
+    if (!p) return DIMSUM_ERR_NULL;
+    if (p->struct_size != sizeof(dimsum_decode_linear_params_t)) return DIMSUM_ERR_ABI;
+    return decode_linear_run(p, reinterpret_cast<hipStream_t>(stream), nullptr, 0);
+}
+
+extern "C" int dimsum_decode_linear_slots(const dimsum_decode_linear_slots_params_t *v, void *stream) {
+    using namespace dimsum;
+    const int rc = slots_check(v);
+    if (rc != DIMSUM_OK) return rc;
+    if (v->linear.conv_dim == 0) return DIMSUM_ERR_UNSUPPORTED;       // no epilogue, no state to index
+    return decode_linear_run(&v->linear, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const int32_t *>(v->slots_ptr), v->slots_stride);
 }

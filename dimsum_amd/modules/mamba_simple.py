@@ -221,6 +221,9 @@ class _MambaBase(nn.Module):
         """this layer's (conv_state, ssm_state) in inference_params.key_value_memory_dict, created on first use (mamba_simple.py:355-380)"""
         assert self.layer_idx is not None
         if self.layer_idx not in inference_params.key_value_memory_dict:
+            if getattr(inference_params, "state_indices", None) is not None:
+                raise ValueError("state_indices need a pool of states in key_value_memory_dict (allocate_inference_cache(num_slots, ...)): a "
+                                 "cache created on first use has one row per batch row, not one per slot")
             conv_state = torch.zeros(batch_size, self.d_inner, self.d_conv, device=self.conv1d.weight.device, dtype=self.conv1d.weight.dtype)
             ssm_state = torch.zeros(batch_size, self.d_inner, self.d_state, device=self.dt_proj.weight.device, dtype=self.dt_proj.weight.dtype)
             inference_params.key_value_memory_dict[self.layer_idx] = (conv_state, ssm_state)
@@ -231,24 +234,27 @@ class _MambaBase(nn.Module):
                 ssm_state.zero_()
         return conv_state, ssm_state
 
-    def step(self, hidden_states, conv_state, ssm_state):
+    def step(self, hidden_states, conv_state, ssm_state, state_indices=None):
         """one token: hidden_states (B, 1, d_model) -> (out (B, 1, d_model), conv_state, ssm_state), both states updated in place
-        (mamba_simple.py:299-344): in_proj -> causal_conv1d_update -> x_proj -> selective_state_update -> out_proj"""
+        (mamba_simple.py:299-344): in_proj -> causal_conv1d_update -> x_proj -> selective_state_update -> out_proj.
+        state_indices (B,) int32: the states are pools (num_slots, ...) and row b works on slot state_indices[b] (InferenceParams)"""
         self._refuse_recurrent()
         assert hidden_states.shape[1] == 1, "Only support decoding with 1 token at a time for now"
+        slots = {} if state_indices is None else {"state_indices": state_indices}
         xz = F.linear(hidden_states.squeeze(1), self.in_proj.weight, self.in_proj.bias)     # (B, 2 d_inner)
         x, z = xz.chunk(2, dim=-1)                                                            # views: the kernels take the strides
         cw = self.conv1d.weight
-        x = causal_conv1d_update(x, conv_state, cw.reshape(cw.shape[0], cw.shape[-1]), self.conv1d.bias, self.activation)
+        x = causal_conv1d_update(x, conv_state, cw.reshape(cw.shape[0], cw.shape[-1]), self.conv1d.bias, self.activation, **slots)
         x_db = F.linear(x, self.x_proj.weight)                                                # (B, dt_rank + 2 d_state)
         dt, B, C = torch.split(x_db, [self.dt_rank, self.d_state, self.d_state], dim=-1)
         A = gemm.neg_exp(self.A_log)
         if x.dtype == torch.float32 and self.dt_proj.weight.dtype == torch.float32:
             # dt_proj inside the state update (csrc/mixer_step.hip): one GEMV launch less per step, which is bound by its launches
-            y = native.selective_state_update(ssm_state, x, None, A, B, C, self.D, z, self.dt_proj.bias, True, dt_proj=(self.dt_proj.weight, dt))
+            y = native.selective_state_update(ssm_state, x, None, A, B, C, self.D, z, self.dt_proj.bias, True, dt_proj=(self.dt_proj.weight, dt),
+                                              **slots)
         else:
             dt = F.linear(dt, self.dt_proj.weight)                                            # without the bias: the kernel adds it (:324-325)
-            y = selective_state_update(ssm_state, x, dt, A, B, C, self.D, z=z, dt_bias=self.dt_proj.bias, dt_softplus=True)
+            y = selective_state_update(ssm_state, x, dt, A, B, C, self.D, z=z, dt_bias=self.dt_proj.bias, dt_softplus=True, **slots)
         out = F.linear(y, self.out_proj.weight, self.out_proj.bias)
         return out.unsqueeze(1), conv_state, ssm_state
 
@@ -263,36 +269,44 @@ class _MambaBase(nn.Module):
         return (native.decode_linear_serves(hidden, self.in_proj.weight, *params) and conv_state.dtype == T
                 and ssm_state.dtype in (torch.float32, T))
 
-    def step_fused(self, hidden, residual, norm, residual_dtype, conv_state, ssm_state):
+    def step_fused(self, hidden, residual, norm, residual_dtype, conv_state, ssm_state, state_indices=None):
         """one token through "add -> norm -> mixer" as four dependent launches of the library (csrc/decode_step.hip, csrc/mixer_step.hip) plus
         neg_exp: hidden (B, d_model), the previous layer's mixer output (or the embedding); residual (B, d_model) or None; norm: the block's
         LayerNorm / RMSNorm module; residual_dtype: of the residual stream this call returns (the incoming one's when there is one)
         -> (out (B, d_model) WITHOUT the residual add: it lives in the next caller's prologue, residual_out (B, d_model)).
           1. in_proj with the add + norm prologue and the conv-update epilogue  2. x_proj  3. the state update, dt_proj inside it where the
-          kernel takes it (float32; a 16-bit dt_proj is one more decode_linear)  4. out_proj with its bias"""
+          kernel takes it (float32; a 16-bit dt_proj is one more decode_linear)  4. out_proj with its bias
+        state_indices (B,) int32: the states are pools and launches 1 and 3 address slot state_indices[b] for row b (same launch count)"""
         D, R, N = self.d_inner, self.dt_rank, self.d_state
         cw = self.conv1d.weight
+        slots = {} if state_indices is None else {"state_indices": state_indices}
         xz, residual_out = native.decode_linear(hidden, self.in_proj.weight, self.in_proj.bias,
                                                 norm=(norm.weight, norm.bias, norm.eps, isinstance(norm, RMSNorm)), residual=residual,
                                                 residual_out=residual_dtype,
-                                                conv=(conv_state, cw.reshape(cw.shape[0], cw.shape[-1]), self.conv1d.bias, True))
+                                                conv=(conv_state, cw.reshape(cw.shape[0], cw.shape[-1]), self.conv1d.bias, True), **slots)
         x, z = xz[:, :D], xz[:, D:]                                                          # views: the kernels take the strides
         x_db = native.decode_linear(x, self.x_proj.weight)
         dt, B, C = x_db[:, :R], x_db[:, R:R + N], x_db[:, R + N:]
         A = gemm.neg_exp(self.A_log)
         if hidden.dtype == torch.float32:
-            y = native.selective_state_update(ssm_state, x, None, A, B, C, self.D, z, self.dt_proj.bias, True, dt_proj=(self.dt_proj.weight, dt))
+            y = native.selective_state_update(ssm_state, x, None, A, B, C, self.D, z, self.dt_proj.bias, True, dt_proj=(self.dt_proj.weight, dt),
+                                              **slots)
         else:
-            y = native.selective_state_update(ssm_state, x, native.decode_linear(dt, self.dt_proj.weight), A, B, C, self.D, z, self.dt_proj.bias, True)
+            y = native.selective_state_update(ssm_state, x, native.decode_linear(dt, self.dt_proj.weight), A, B, C, self.D, z, self.dt_proj.bias, True,
+                                              **slots)
         return native.decode_linear(y, self.out_proj.weight, self.out_proj.bias), residual_out
 
     @torch.no_grad()
-    def extend(self, hidden_states, conv_state, ssm_state):
+    def extend(self, hidden_states, conv_state, ssm_state, state_indices=None):
         """any number of tokens on carried states, the sibling of `step`: hidden_states (B, T, d_model), T >= 1 -> (out (B, T, d_model),
         conv_state, ssm_state), both states updated in place: in_proj (d-major, as _mix forms xz) -> causal_conv1d_chunk -> x_proj / dt_proj
         (the general path of mamba_inner_fn) -> the scan entered with ssm_state and leaving it (csrc/ssm_scan_general.hip) with the z gate ->
-        out_proj. No host read and no allocation depends on data: one call can be captured on a single stream."""
+        out_proj. No host read and no allocation depends on data: one call can be captured on a single stream.
+        state_indices is refused: the chunk kernels address a batch's own states; a slot of a pool is extended through a view pool[s:s+1]."""
         self._refuse_recurrent()
+        if state_indices is not None:
+            raise NotImplementedError("extend with state_indices is not built: causal_conv1d_chunk and the carried scan take no slot index (only "
+                                      "the one-token step kernels do); extend slot s of a pool through the views pool[s:s+1]")
         bsz, T, _ = hidden_states.shape
         assert T >= 1, "extend needs at least one token"
         D, R, N = self.d_inner, self.dt_rank, self.d_state
@@ -317,12 +331,21 @@ class _MambaBase(nn.Module):
 
     def _forward_cached(self, hidden_states, cond, inference_params, x3, seq_idx=None):
         """forward(inference_params=...): a prompt at seqlen_offset 0 (fused path + the states it leaves behind), one step after it"""
+        state_indices = getattr(inference_params, "state_indices", None)
+        if state_indices is not None and (self.scan_type == "v2" or self._is_zigzag()):
+            raise NotImplementedError(f'state_indices with scan_type "{self.scan_type}" is not built: only the plain causal mixer ("none") runs '
+                                      "token by token, so only it has states to index")
         self._refuse_recurrent(x3)
+        if state_indices is not None and inference_params.seqlen_offset == 0:
+            raise ValueError("state_indices at seqlen_offset == 0: a prompt is prefilled into slot s of a pool through the views pool[s:s+1] "
+                             "with state_indices=None; the slot index belongs to the decode steps (seqlen_offset > 0)")
         conv_state, ssm_state = self._get_states_from_cache(inference_params, hidden_states.shape[0])
         if inference_params.seqlen_offset > 0:
             if seq_idx is not None:
                 raise ValueError("seq_idx at seqlen_offset > 0: sequence ids belong to the prompt pass (seqlen_offset == 0); a decode step "
                                  "continues every row's last segment")
+            if state_indices is not None:
+                return self.step(hidden_states, conv_state, ssm_state, state_indices=state_indices)[0]
             return self.step(hidden_states, conv_state, ssm_state)[0]       # the states are updated in place
         if seq_idx is None:
             return self._mix(hidden_states, cond, states=(conv_state, ssm_state))
@@ -381,7 +404,7 @@ class Block(nn.Module):
             return None
         if residual is not None and residual.dtype not in (torch.float32, hidden_states.dtype):
             return None
-        states = self.mixer._get_states_from_cache(inference_params, hidden_states.shape[0])
+        states = self.mixer._get_states_from_cache(inference_params, hidden_states.shape[0])       # with state_indices: the pools (num_slots, ...)
         return states if self.mixer.fused_step_serves(hidden_states[:, 0], self.norm, *states) else None
 
     def forward(self, hidden_states, residual=None, inference_params=None, seq_idx=None):
@@ -391,7 +414,9 @@ class Block(nn.Module):
         states = self._fused_decode_states(hidden_states, residual, inference_params)
         if states is not None:
             res_dtype = residual.dtype if residual is not None else (torch.float32 if self.residual_in_fp32 else hidden_states.dtype)
-            out, residual = self.mixer.step_fused(hidden_states[:, 0], None if residual is None else residual[:, 0], self.norm, res_dtype, *states)
+            slots = getattr(inference_params, "state_indices", None)
+            out, residual = self.mixer.step_fused(hidden_states[:, 0], None if residual is None else residual[:, 0], self.norm, res_dtype, *states,
+                                                  **({} if slots is None else {"state_indices": slots}))
             return out.unsqueeze(1), residual.unsqueeze(1)
         if not self.fused_add_norm:
             residual = (hidden_states + residual) if residual is not None else hidden_states

@@ -445,24 +445,48 @@ def causal_conv1d_varlen_bwd(x, weight, bias, dout, dx, silu_activation, seq_idx
 # selective_state_update (ops/triton/selective_state_update.py:115-190). Both update their state IN PLACE; every operand
 # may be a strided view (csrc/mixer_step.hip addresses with one element stride per dim).
 # ---------------------------------------------------------------------------------------------------------------------
-def causal_conv1d_update(x, conv_state, weight, bias, silu_activation):
+def _check_state_indices(state_indices, x, who):
+    """state_indices: int32 (batch,) -- row b of the call works on state[state_indices[b]] of a pool (num_slots, ...), a negative entry is a
+    padding row (no state touched, zero output). Dtype, rank and length first (they need no GPU), the device last. The VALUES stay on the
+    device: that they are below num_slots and that no slot is named twice is the caller's contract (include/dimsum_hip.h)."""
+    _check(x.dim() == 2, f"{who}: x must be (batch, dim)")
+    _check(torch.is_tensor(state_indices) and state_indices.dtype == torch.int32, f"{who}: state_indices must be an int32 tensor")
+    _check(state_indices.dim() == 1, f"{who}: state_indices must be 1-D, one slot per batch row")
+    _check(state_indices.shape[0] == x.shape[0], f"{who}: state_indices must have batch = {x.shape[0]} entries, got {state_indices.shape[0]}")
+    _check(state_indices.is_cuda and state_indices.device == x.device, f"{who}: state_indices must be a GPU tensor on x's device")
+
+
+def _fill_slots(S, state_indices, pool):
+    S.slots_ptr, S.slots_stride, S.num_slots = _ptr(state_indices), state_indices.stride(0), pool.shape[0]
+
+
+def causal_conv1d_update(x, conv_state, weight, bias, silu_activation, state_indices=None):
     """-> out (batch, dim), like causal_conv1d_cuda.causal_conv1d_update: conv_state (batch, dim, width) is shifted left by one and x
-    appended, in place; out = act(sum_w conv_state * weight + bias). Weights are used in fp32."""
+    appended, in place; out = act(sum_w conv_state * weight + bias). Weights are used in fp32.
+    state_indices (batch,) int32 (upstream Mamba's conv_state_indices): conv_state is a pool (num_slots, dim, width) and row b works on
+    conv_state[state_indices[b]]; a negative entry touches no state and gives a zero row. None: the call it always was."""
+    if state_indices is not None:
+        _check_state_indices(state_indices, x, "causal_conv1d_update")
     _gpu(x, conv_state, weight, bias)
     _check(x.dim() == 2 and x.dtype in _DT, "causal_conv1d_update: x must be (batch, dim) in float32, float16 or bfloat16")
     batch, dim = x.shape
     _check(weight.dim() == 2 and weight.shape[0] == dim, "causal_conv1d_update: weight must be (dim, width)")
     width = weight.shape[1]
     _check(2 <= width <= 4, "causal_conv1d_update only supports width between 2 and 4")
-    _check(tuple(conv_state.shape) == (batch, dim, width) and conv_state.dtype == x.dtype,
-           "causal_conv1d_update: conv_state must be (batch, dim, width) of x's dtype")
+    if state_indices is None:
+        _check(tuple(conv_state.shape) == (batch, dim, width) and conv_state.dtype == x.dtype,
+               "causal_conv1d_update: conv_state must be (batch, dim, width) of x's dtype")
+    else:
+        _check(conv_state.dim() == 3 and conv_state.shape[0] >= 1 and tuple(conv_state.shape[1:]) == (dim, width) and conv_state.dtype == x.dtype,
+               "causal_conv1d_update: with state_indices conv_state must be a pool (num_slots >= 1, dim, width) of x's dtype")
     if bias is not None:
         _check(tuple(bias.shape) == (dim,), "causal_conv1d_update: bias must be (dim,)")
     weight = weight.float()
     bias = bias.float().contiguous() if bias is not None else None
     out = torch.empty_like(x)
     if x.numel() > 0:
-        P = _lib.ConvUpdateParams()
+        S = None if state_indices is None else _lib.ConvUpdateSlotsParams()
+        P = _lib.ConvUpdateParams() if S is None else S.conv
         P.batch, P.dim, P.width, P.silu_activation, P.dtype = batch, dim, width, int(bool(silu_activation)), _DT[x.dtype]
         P.x_batch_stride, P.x_c_stride = x.stride()
         P.state_batch_stride, P.state_c_stride, P.state_w_stride = conv_state.stride()
@@ -470,7 +494,11 @@ def causal_conv1d_update(x, conv_state, weight, bias, silu_activation):
         P.out_batch_stride, P.out_c_stride = out.stride()
         P.x_ptr, P.weight_ptr, P.bias_ptr, P.conv_state_ptr, P.out_ptr = _ptr(x), _ptr(weight), _ptr(bias), _ptr(conv_state), _ptr(out)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dimsum_causal_conv1d_update(P, _stream(x)), "causal_conv1d_update")
+            if S is None:
+                _lib.check(_lib.load().dimsum_causal_conv1d_update(P, _stream(x)), "causal_conv1d_update")
+            else:
+                _fill_slots(S, state_indices, conv_state)
+                _lib.check(_lib.load().dimsum_causal_conv1d_update_slots(S, _stream(x)), "causal_conv1d_update (state_indices)")
     return out
 
 
@@ -508,16 +536,24 @@ def causal_conv1d_chunk(x, conv_state, weight, bias, silu_activation):
     return out
 
 
-def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False, dt_proj=None):
+def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False, dt_proj=None, state_indices=None):
     """-> out (batch, dim), like the reference's selective_state_update: state (batch, dim, dstate) <- state exp(dt' A) + dt' B x in place,
     dt' = [softplus](dt + dt_bias); out = sum_n state C + D x, times silu(z). fp32 arithmetic; x, dt, z share one dtype, state and B / C
     are float32 or that dtype.
     `dt_proj=(dt_w (dim, R) float32, dt_x (batch, R))` (no reference counterpart): dt = dt_x @ dt_w^T is formed inside the kernel and `dt`
-    must be None -- one GEMV launch less per step."""
+    must be None -- one GEMV launch less per step.
+    state_indices (batch,) int32 (upstream Mamba's state_batch_indices): state is a pool (num_slots, dim, dstate) and row b works on
+    state[state_indices[b]]; a negative entry touches no state and gives a zero row. None: the call it always was."""
+    if state_indices is not None:
+        _check_state_indices(state_indices, x, "selective_state_update")
     _gpu(state, x, dt, A, B, C, D, z, dt_bias)
     _check(x.dim() == 2 and x.dtype in _DT, "selective_state_update: x must be (batch, dim) in float32, float16 or bfloat16")
     batch, dim = x.shape
-    _check(state.dim() == 3 and tuple(state.shape[:2]) == (batch, dim), "selective_state_update: state must be (batch, dim, dstate)")
+    if state_indices is None:
+        _check(state.dim() == 3 and tuple(state.shape[:2]) == (batch, dim), "selective_state_update: state must be (batch, dim, dstate)")
+    else:
+        _check(state.dim() == 3 and state.shape[0] >= 1 and state.shape[1] == dim,
+               "selective_state_update: with state_indices state must be a pool (num_slots >= 1, dim, dstate)")
     dstate = state.shape[2]
     _check(1 <= dstate <= 256 or state.numel() == 0, "selective_state_update only supports state dimension between 1 and 256")
     _check(state.dtype in (torch.float32, x.dtype), "selective_state_update: state must be float32 or of x's dtype")
@@ -541,8 +577,9 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
     if z is not None:
         _check(z.shape == x.shape and z.dtype == x.dtype, "selective_state_update: z must be (batch, dim) of x's dtype")
     out = torch.empty_like(x)
-    if state.numel() > 0:
-        P = _lib.StateUpdateParams()
+    if state.numel() > 0 and x.numel() > 0:
+        S = None if state_indices is None else _lib.StateUpdateSlotsParams()
+        P = _lib.StateUpdateParams() if S is None else S.update
         P.batch, P.dim, P.dstate, P.dt_softplus = batch, dim, dstate, int(bool(dt_softplus))
         P.dtype, P.state_dtype, P.bc_dtype = _DT[x.dtype], _DT[state.dtype], _DT[B.dtype]
         P.state_batch_stride, P.state_d_stride, P.state_n_stride = state.stride()
@@ -563,7 +600,11 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
         P.state_ptr, P.x_ptr, P.dt_ptr, P.A_ptr, P.B_ptr, P.C_ptr = _ptr(state), _ptr(x), _ptr(dt), _ptr(A), _ptr(B), _ptr(C)
         P.D_ptr, P.z_ptr, P.dt_bias_ptr, P.out_ptr = _ptr(D), _ptr(z), _ptr(dt_bias), _ptr(out)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dimsum_selective_state_update(P, _stream(x)), "selective_state_update")
+            if S is None:
+                _lib.check(_lib.load().dimsum_selective_state_update(P, _stream(x)), "selective_state_update")
+            else:
+                _fill_slots(S, state_indices, state)
+                _lib.check(_lib.load().dimsum_selective_state_update_slots(S, _stream(x)), "selective_state_update (state_indices)")
     return out
 
 
@@ -573,14 +614,19 @@ def decode_linear_serves(x, weight, *others):
             and all(t is None or t.dtype == x.dtype for t in others))
 
 
-def decode_linear(x, weight, bias=None, norm=None, residual=None, residual_out=None, conv=None):
+def decode_linear(x, weight, bias=None, norm=None, residual=None, residual_out=None, conv=None, state_indices=None):
     """-> y (batch, N), or (y, residual_out) when `residual_out` is asked for: y = x' @ weight^T (+ bias) on csrc/decode_step.hip, batch <= 16;
     x (batch, K), weight (N, K), bias (N) share one dtype T.
     norm = (norm_weight (K), norm_bias (K) or None, eps, is_rms_norm): x' = norm(x (+ residual)) * norm_weight (+ norm_bias) in the same launch;
     residual (batch, K) is float32 or T. residual_out: None, or the dtype (float32 or T, == residual's when one is given) in which
     x (+ residual) is also returned -- a fresh buffer, never a view of x or residual. Without `norm`, x' = x.
     conv = (conv_state (batch, D, W) of T, conv_weight (D, W), conv_bias (D) or None, silu): the outputs n < D go through one in-place
-    step of the causal conv1d (causal_conv1d_update) before they are stored; y[:, :D] is the conv output, y[:, D:] the plain outputs."""
+    step of the causal conv1d (causal_conv1d_update) before they are stored; y[:, :D] is the conv output, y[:, D:] the plain outputs.
+    state_indices (batch,) int32, with `conv` only: conv_state is a pool (num_slots, D, W) and row b's epilogue works on
+    conv_state[state_indices[b]]; a negative entry touches no state and leaves zeros in y[b, :D] (y[b, D:] is written as ever)."""
+    if state_indices is not None:
+        _check(conv is not None, "decode_linear: state_indices address the conv epilogue's states and need `conv`")
+        _check_state_indices(state_indices, x, "decode_linear")
     _check(x.dim() == 2 and x.dtype in _DT and x.stride(1) == 1, "decode_linear: x must be (batch, K) with unit row stride in float32, float16 or bfloat16")
     batch, K = x.shape
     _check(1 <= batch <= _lib.DECODE_MAX_BATCH, f"decode_linear: batch must be 1..{_lib.DECODE_MAX_BATCH}")
@@ -591,7 +637,8 @@ def decode_linear(x, weight, bias=None, norm=None, residual=None, residual_out=N
         _check(tuple(bias.shape) == (N,) and bias.dtype == x.dtype, "decode_linear: bias must be (N,) of x's dtype")
         bias = bias.contiguous()
     _check(norm is not None or (residual is None and residual_out is None), "decode_linear: residual / residual_out belong to the norm prologue")
-    P = _lib.DecodeLinearParams()
+    S = None if state_indices is None else _lib.DecodeLinearSlotsParams()
+    P = _lib.DecodeLinearParams() if S is None else S.linear
     P.batch, P.n, P.k, P.dtype, P.residual_dtype = batch, N, K, _DT[x.dtype], _DT[x.dtype]
     keep = []
     res_out = None
@@ -620,7 +667,11 @@ def decode_linear(x, weight, bias=None, norm=None, residual=None, residual_out=N
         _check(cw.dim() == 2 and 1 <= cw.shape[0] <= N and cw.dtype == x.dtype, "decode_linear: conv weight must be (D <= N, width) of x's dtype")
         D, W = cw.shape
         _check(2 <= W <= 4, "decode_linear: the conv epilogue only supports width between 2 and 4")
-        _check(tuple(state.shape) == (batch, D, W) and state.dtype == x.dtype, "decode_linear: conv_state must be (batch, D, width) of x's dtype")
+        if state_indices is None:
+            _check(tuple(state.shape) == (batch, D, W) and state.dtype == x.dtype, "decode_linear: conv_state must be (batch, D, width) of x's dtype")
+        else:
+            _check(state.dim() == 3 and state.shape[0] >= 1 and tuple(state.shape[1:]) == (D, W) and state.dtype == x.dtype,
+                   "decode_linear: with state_indices conv_state must be a pool (num_slots >= 1, D, width) of x's dtype")
         if cb is not None:
             _check(tuple(cb.shape) == (D,) and cb.dtype == x.dtype, "decode_linear: conv bias must be (D,) of x's dtype")
             cb = cb.contiguous()
@@ -633,7 +684,11 @@ def decode_linear(x, weight, bias=None, norm=None, residual=None, residual_out=N
     P.x_row_stride, P.w_row_stride, P.y_row_stride = x.stride(0), weight.stride(0), y.stride(0)
     P.x_ptr, P.w_ptr, P.bias_ptr, P.y_ptr = _ptr(x), _ptr(weight), _ptr(bias), _ptr(y)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().dimsum_decode_linear(P, _stream(x)), "decode_linear")
+        if S is None:
+            _lib.check(_lib.load().dimsum_decode_linear(P, _stream(x)), "decode_linear")
+        else:
+            _fill_slots(S, state_indices, conv[0])
+            _lib.check(_lib.load().dimsum_decode_linear_slots(S, _stream(x)), "decode_linear (state_indices)")
     return y if residual_out is None else (y, res_out)
 
 

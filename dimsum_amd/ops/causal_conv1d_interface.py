@@ -82,13 +82,18 @@ def causal_conv1d_varlen_torch(x, weight, bias=None, activation=None, seq_idx=No
     return (pre * torch.sigmoid(pre) if silu else pre).to(x.dtype)
 
 
-def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None):
+def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None, state_indices=None):
     """one token of the causal conv1d on a carried state (causal_conv1d_interface.py:64-76), on the HIP kernel.
     x: (batch, dim), conv_state: (batch, dim, width) -- shifted left by one and x appended, IN PLACE --, weight: (dim, width), bias: (dim,)
-    -> out (batch, dim). Every operand may be a strided view."""
+    -> out (batch, dim). Every operand may be a strided view.
+    state_indices (batch,) int32 (upstream Mamba's conv_state_indices): conv_state is a pool (num_slots, dim, width), row b works on
+    conv_state[state_indices[b]], a negative entry is a padding row (no state touched, zero output). Entries must be < num_slots and no slot
+    may be named twice: neither is checked (it would take a device read)."""
     if activation not in (None, "silu", "swish"):
         raise NotImplementedError("activation must be None, silu, or swish")
-    return native.causal_conv1d_update(x, conv_state, weight, bias, activation in ("silu", "swish"))
+    if state_indices is None:
+        return native.causal_conv1d_update(x, conv_state, weight, bias, activation in ("silu", "swish"))
+    return native.causal_conv1d_update(x, conv_state, weight, bias, activation in ("silu", "swish"), state_indices=state_indices)
 
 
 def causal_conv1d_chunk(x, conv_state, weight, bias=None, activation=None):
@@ -119,11 +124,29 @@ def causal_conv1d_chunk_torch(x, conv_state, weight, bias=None, activation=None)
     return (pre * torch.sigmoid(pre) if silu else pre).to(x.dtype)
 
 
-def causal_conv1d_update_torch(x, conv_state, weight, bias=None, activation=None):
+def _slot_rows(state_indices, batch):
+    """the restatements' view of state_indices: ([rows b with a slot], [their slots]) as Python lists (a host read: test infrastructure)"""
+    assert state_indices.dim() == 1 and state_indices.shape[0] == batch and state_indices.dtype == torch.int32
+    slots = state_indices.tolist()
+    live = [b for b, s in enumerate(slots) if s >= 0]
+    return live, [slots[b] for b in live]
+
+
+def causal_conv1d_update_torch(x, conv_state, weight, bias=None, activation=None, state_indices=None):
     """The step of the causal conv1d written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer):
     the window a causal conv of width W sees at the new token is the last W - 1 columns of the state followed by x; the output is the dot
     product of that window with the taps, plus bias, through SiLU if asked. conv_state receives the window. What the tests compare the
-    kernel with; never a fallback: nothing in the package calls it."""
+    kernel with; never a fallback: nothing in the package calls it.
+    state_indices (batch,) int32: conv_state is a pool and row b works on conv_state[state_indices[b]]; rows with a negative entry are
+    skipped -- no slot is read or written -- and give zeros."""
+    if state_indices is not None:
+        live, slots = _slot_rows(state_indices, x.shape[0])
+        out = torch.zeros_like(x)
+        if live:
+            rows = conv_state[slots]                                                    # a gathered copy
+            out[live] = causal_conv1d_update_torch(x[live], rows, weight, bias, activation)
+            conv_state[slots] = rows
+        return out
     silu = {None: False, "silu": True, "swish": True}.get(activation)
     if silu is None:
         raise NotImplementedError(f"causal_conv1d_update_torch: activation {activation!r} (None, 'silu' or 'swish')")

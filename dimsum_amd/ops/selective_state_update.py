@@ -6,19 +6,36 @@ import torch
 from .. import native
 
 
-def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False):
+def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False, state_indices=None):
     """state: (batch, dim, dstate), updated IN PLACE; x, dt: (batch, dim); A: (dim, dstate); B, C: (batch, dstate); D, dt_bias: (dim,);
-    z: (batch, dim) -> out (batch, dim). fp32 arithmetic; state and B / C may be float32 next to 16-bit x. Operands may be strided views."""
-    return native.selective_state_update(state, x, dt, A.float(), B, C, D, z, dt_bias, dt_softplus)
+    z: (batch, dim) -> out (batch, dim). fp32 arithmetic; state and B / C may be float32 next to 16-bit x. Operands may be strided views.
+    state_indices (batch,) int32 (upstream Mamba's state_batch_indices): state is a pool (num_slots, dim, dstate), row b works on
+    state[state_indices[b]], a negative entry is a padding row (no state touched, zero output). Entries must be < num_slots and no slot may
+    be named twice: neither is checked (it would take a device read)."""
+    if state_indices is None:
+        return native.selective_state_update(state, x, dt, A.float(), B, C, D, z, dt_bias, dt_softplus)
+    return native.selective_state_update(state, x, dt, A.float(), B, C, D, z, dt_bias, dt_softplus, state_indices=state_indices)
 
 
-def selective_state_update_torch(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False):
+def selective_state_update_torch(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False, state_indices=None):
     """One step of the discretised state-space recurrence written out in plain torch, in the precision of its inputs (float64 inputs give
     the float64 answer), per batch row b, channel d and state n:
         step[b, d] = dt (+ dt_bias), through softplus if asked (torch's threshold of 20)
         h[b, d, n] <- h[b, d, n] exp(step[b, d] A[d, n]) + step[b, d] x[b, d] B[b, n]
         y[b, d]     = sum_n h[b, d, n] C[b, n] (+ D[d] x[b, d]), times z sigmoid(z) if z is given
-    `state` receives h. What the tests compare the kernel with; never a fallback: nothing in the package calls it."""
+    `state` receives h. What the tests compare the kernel with; never a fallback: nothing in the package calls it.
+    state_indices (batch,) int32: state is a pool and row b works on state[state_indices[b]]; rows with a negative entry are skipped -- no
+    slot is read or written -- and give zeros."""
+    if state_indices is not None:
+        from .causal_conv1d_interface import _slot_rows
+        live, slots = _slot_rows(state_indices, x.shape[0])
+        out = torch.zeros_like(x)
+        if live:
+            rows = state[slots]                                                         # a gathered copy
+            out[live] = selective_state_update_torch(rows, x[live], dt[live], A, B[live], C[live], D, None if z is None else z[live], dt_bias,
+                                                     dt_softplus)
+            state[slots] = rows
+        return out
     step = dt if dt_bias is None else dt + dt_bias.unsqueeze(0)
     if dt_softplus:
         step = torch.where(step > 20, step, torch.log1p(torch.exp(step.clamp(max=20))))

@@ -1,5 +1,6 @@
 """small host utilities"""
 import dataclasses
+from typing import Optional
 
 import torch
 
@@ -8,11 +9,16 @@ import torch
 class InferenceParams:
     """what a caller hands to Mamba / CondMamba.forward(inference_params=...) to run a sequence token by token: the per-layer
     (conv_state, ssm_state) caches keyed by layer_idx and how many tokens they have seen. Same fields and `reset` as the reference's
-    (mamba/mamba_ssm/utils/generation.py:12-28), minus what only its generation loop reads."""
+    (mamba/mamba_ssm/utils/generation.py:12-28), minus what only its generation loop reads.
+    state_indices (no reference counterpart; upstream Mamba's state_batch_indices): None, or an int32 (batch,) device tensor that makes the
+    cached states a POOL (num_slots, ...) -- row b of a decode step (seqlen_offset > 0) works on slot state_indices[b], a negative entry is
+    a padding row. A prompt (seqlen_offset == 0) takes no indices: it is prefilled into slot s through a view pool[s:s+1]. `reset` leaves it
+    alone (the tensor is a static buffer of whoever schedules the batch: dimsum_amd.utils.serving.DecodeEngine)."""
     max_seqlen: int
     max_batch_size: int
     seqlen_offset: int = 0
     key_value_memory_dict: dict = dataclasses.field(default_factory=dict)
+    state_indices: Optional[torch.Tensor] = None
 
     def reset(self, max_seqlen, max_batch_size):
         self.max_seqlen, self.max_batch_size, self.seqlen_offset = max_seqlen, max_batch_size, 0
@@ -25,6 +31,9 @@ def chunked_prefill(mixer, hidden_states, inference_params, chunk, *cond):
     states. *cond: what the mixer's forward takes after hidden_states (CondMamba's cond_emb). Advances inference_params.seqlen_offset by L
     -> the concatenated output (B, L, d_model)."""
     assert chunk >= 1 and inference_params.seqlen_offset == 0, "chunked_prefill starts a sequence: seqlen_offset must be 0"
+    if getattr(inference_params, "state_indices", None) is not None:
+        raise NotImplementedError("chunked_prefill with state_indices is not built: `extend` works on a batch's own states; prefill a slot of "
+                                  "a pool through a view, pool[s:s+1], with state_indices=None")
     L = hidden_states.shape[1]
     outs = [mixer(hidden_states[:, :chunk], *cond, inference_params=inference_params)]
     states = inference_params.key_value_memory_dict[mixer.layer_idx]

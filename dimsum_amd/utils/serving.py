@@ -1,0 +1,244 @@
+"""Continuous batching on the recurrent form: `DecodeEngine`, a host-side scheduler that keeps requests of different lengths in ONE decode
+batch of a fixed size and reuses a finished request's place at once (no reference counterpart: mamba/mamba_ssm/utils/generation.py decodes a
+batch that lives and dies together).
+
+A Mamba layer's state per request is a fixed (d_inner, d_conv) + (d_inner, d_state), with no position-dependent cache, so membership is one
+indirection: the engine owns a POOL of `num_slots` states per layer (allocate_inference_cache(num_slots, ...)) and a per-row slot index, an
+int32 device tensor that rides in InferenceParams.state_indices and is read by the step kernels themselves (csrc/mixer_step.hip,
+csrc/decode_step.hip). Idle rows carry slot -1: they touch no state and stay finite. With cg=True the step -- the
+model's forward at the fixed batch `max_batch` plus, with fused sampling, the sampler writing into the step's own token buffer -- is captured
+into ONE hipGraph per engine (`n_captures == 1`) that serves every membership: between replays the host only rewrites static buffers (the
+slots, the token of a newly admitted row, the step's uniforms).
+
+Scheduling, chosen for simplicity: `submit` only queues. `step` first admits queued requests while a row and a slot are free -- each is
+prefilled ALONE, eagerly, at batch 1, through the existing prompt path on the views pool[s:s+1] (which overwrites both states of the slot
+completely: `_mix` copies the conv tail into conv_state and the scan's last state into ssm_state, so slots are not zeroed on release), and its
+first token is sampled ON THE DEVICE from the prompt's logits into the row's place in the token buffer -- then runs one decode step of every
+live row. So a prefill stalls the decode batch, and an admitted request always takes a row for at least one step: a request that its first
+token already ends (max_new_tokens 1, or eos) is retired after that step and the step's token of its row is dropped.
+
+Host reads: exactly one per step -- the batch's tokens after the decode step (the step's (max_batch,) tokens together with the first tokens
+of the rows admitted in this step, ONE small device-to-host copy), which the host needs to see eos_token_id and to report the tokens. It is
+the engine's only host read: an admission reads nothing, and the slots are never read back.
+
+Documented limits: prefill stalls the batch; new requests are not prefilled together in one packed launch (that needs per-document final states
+out of the packed-row scan); max_batch above 16 runs the unfused step (with slots); no prefix or state sharing between requests; no preemption.
+Sampling: `fused_sampling=True` draws token i of a request with uniforms[i] of THAT request (given to `submit`, or drawn there from the
+engine's generator) whichever row and step it lands on, so a request's output does not depend on its neighbours or on the schedule;
+`fused_sampling=False` runs generation.sample() per step on the batch's logits, whose multinomial draws (top_k != 1) come from one shared
+generator and do depend on the schedule."""
+import collections
+import dataclasses
+from typing import Optional
+
+import torch
+
+from . import InferenceParams
+from .. import native
+from .generation import sample
+
+
+@dataclasses.dataclass
+class _Request:
+    rid: int
+    prompt: torch.Tensor                      # (L,) int64 on the model's device
+    max_new_tokens: int
+    uniforms: Optional[torch.Tensor]          # (max_new_tokens,) float32 on the host, or None (unfused sampling)
+    tokens: list = dataclasses.field(default_factory=list)
+    scores: list = dataclasses.field(default_factory=list)
+    slot: int = -1
+    row: int = -1
+    finished: bool = False
+
+
+class DecodeEngine:
+    """eng = DecodeEngine(model, max_batch, num_slots=None, max_seqlen=..., top_k=1, top_p=0.0, temperature=1.0, eos_token_id=None,
+                          vocab_size=None, cg=True, fused_sampling=True)
+    rid = eng.submit(prompt_ids, max_new_tokens, uniforms=None)    1-D prompt; uniforms (max_new_tokens,) float32 pins the draws
+    events = eng.step()                                            [(rid, token, finished)]: admissions' first tokens, then one decode step
+    results = eng.run()                                            until idle -> {rid: LongTensor prompt + generated}
+    model: a MambaLMHeadModel (anything with allocate_inference_cache and forward(ids, inference_params=, num_last_tokens=) -> .logits).
+    num_slots (default max_batch) >= max_batch states per layer. max_seqlen: what allocate_inference_cache is told (Mamba states do not
+    depend on it). vocab_size: the classes of a padded head, as in generate(). output_scores=True keeps every token's logits row
+    (`scores(rid)`). generator: with fused sampling a CPU generator from which `submit` draws a request's uniforms on the host; without it
+    the device generator handed to sample(). Bookkeeping the tests read: `n_captures`, `free_slots`, `rows`, `slot_history` [(rid, slot)] in admission order.
+    See the module docstring for the schedule, the host reads and the limits."""
+
+    def __init__(self, model, max_batch, num_slots=None, *, max_seqlen, top_k=1, top_p=0.0, temperature=1.0, eos_token_id=None, vocab_size=None,
+                 cg=True, fused_sampling=True, output_scores=False, generator=None):
+        num_slots = max_batch if num_slots is None else int(num_slots)
+        if max_batch < 1 or num_slots < max_batch:
+            raise ValueError(f"DecodeEngine: need max_batch >= 1 and num_slots >= max_batch, got {max_batch} and {num_slots}")
+        self.model, self.max_batch, self.num_slots, self.max_seqlen = model, int(max_batch), num_slots, int(max_seqlen)
+        self.top_k, self.top_p, self.temperature = int(top_k), float(top_p), float(temperature)
+        self.eos_token_id, self.vocab_size = eos_token_id, vocab_size
+        self.cg, self.fused_sampling, self.output_scores, self.generator = bool(cg), bool(fused_sampling), bool(output_scores), generator
+        param = next(iter(model.parameters()))
+        self.device = param.device
+        with torch.no_grad():
+            self.pool = model.allocate_inference_cache(num_slots, self.max_seqlen, param.dtype)
+        # the static buffers of the step: every row's slot (-1 = idle), its newest token, its uniform; and the first tokens of the rows
+        # admitted since the last step, waiting for the step's host read
+        self.slots = torch.full((self.max_batch,), -1, dtype=torch.int32, device=self.device)
+        self.input_ids = torch.zeros((self.max_batch, 1), dtype=torch.long, device=self.device)
+        self.u = torch.zeros(self.max_batch, dtype=torch.float32, device=self.device)
+        self.first = torch.zeros(self.max_batch, dtype=torch.long, device=self.device)
+        self._fresh = set()                                 # rows admitted since the last step
+        self.params = InferenceParams(max_seqlen=self.max_seqlen, max_batch_size=self.max_batch, seqlen_offset=1, key_value_memory_dict=self.pool,
+                                      state_indices=self.slots)
+        self.free_slots = list(range(num_slots))
+        self.rows = [None] * self.max_batch                 # row -> rid
+        self.queue = collections.deque()
+        self.requests = {}
+        self.slot_history = []
+        self.n_captures = 0
+        self._next_rid = 0
+        self._graph = self._logits = None
+
+    # ---- the request side --------------------------------------------------------------------------------------------------------------------
+    def submit(self, prompt_ids, max_new_tokens, uniforms=None):
+        """queues a request -> its id. prompt_ids: 1-D, at least one token. uniforms (max_new_tokens,) float32 in [0, 1): draw i of this
+        request (fused sampling); None: drawn here from the engine's generator."""
+        prompt = torch.as_tensor(prompt_ids, dtype=torch.long)
+        if prompt.dim() != 1 or prompt.numel() < 1 or int(max_new_tokens) < 1:
+            raise ValueError("DecodeEngine.submit: prompt_ids must be 1-D with at least one token, max_new_tokens >= 1")
+        max_new_tokens = int(max_new_tokens)
+        if self.fused_sampling:
+            if uniforms is None:
+                uniforms = torch.rand(max_new_tokens, dtype=torch.float32, generator=self.generator)       # on the host: a CPU generator
+            uniforms = torch.as_tensor(uniforms).detach().to("cpu")
+            if tuple(uniforms.shape) != (max_new_tokens,) or uniforms.dtype != torch.float32:
+                raise ValueError(f"DecodeEngine.submit: uniforms must be (max_new_tokens,) = ({max_new_tokens},) float32, got {tuple(uniforms.shape)} {uniforms.dtype}")
+        elif uniforms is not None:
+            raise ValueError("DecodeEngine.submit: uniforms pin the draws of the fused sampler; this engine runs sample() (fused_sampling=False)")
+        rid = self._next_rid
+        self._next_rid += 1
+        self.requests[rid] = _Request(rid, prompt.to(self.device), max_new_tokens, uniforms)
+        self.queue.append(rid)
+        return rid
+
+    def idle(self):
+        return not self.queue and all(r is None for r in self.rows)
+
+    def sequence(self, rid):
+        """-> LongTensor (prompt + generated so far) on the host"""
+        r = self.requests[rid]
+        return torch.cat([r.prompt.cpu(), torch.tensor(r.tokens, dtype=torch.long)])
+
+    def scores(self, rid):
+        """-> the (vocab,) logits rows the request's tokens were chosen from, in order (output_scores=True)"""
+        return list(self.requests[rid].scores)
+
+    def run(self):
+        """steps until the queue and the batch are empty -> {rid: LongTensor prompt + generated} of every request submitted so far"""
+        while not self.idle():
+            self.step()
+        return {rid: self.sequence(rid) for rid in self.requests}
+
+    # ---- sampling ----------------------------------------------------------------------------------------------------------------------------
+    def _view(self, logits):
+        return logits[..., :self.vocab_size] if self.vocab_size is not None else logits
+
+    def _sample_into(self, logits, u, out):
+        """one token per row of logits -> out (rows,) / (rows, 1) int64, by the fused sampler (u (rows,)) or sample()"""
+        if self.fused_sampling:
+            native.sample_logits(self._view(logits), u, top_k=self.top_k, top_p=self.top_p, temperature=self.temperature, out=out)
+        else:
+            out.copy_(sample(self._view(logits), top_k=self.top_k, top_p=self.top_p, temperature=self.temperature,
+                             generator=self.generator).view(out.shape))
+
+    # ---- admission ---------------------------------------------------------------------------------------------------------------------------
+    def _done(self, r, token):
+        return len(r.tokens) >= r.max_new_tokens or (self.eos_token_id is not None and token == self.eos_token_id)
+
+    def _admit(self):
+        while self.queue and self.free_slots and None in self.rows:
+            r = self.requests[self.queue.popleft()]
+            slot, row = self.free_slots.pop(0), self.rows.index(None)
+            self.slot_history.append((r.rid, slot))
+            views = {k: tuple(t[slot:slot + 1] for t in states) for k, states in self.pool.items()}
+            prefill = InferenceParams(max_seqlen=self.max_seqlen, max_batch_size=1, key_value_memory_dict=views)
+            logits = self.model(r.prompt.unsqueeze(0), inference_params=prefill, num_last_tokens=1).logits[:, -1]
+            if self.output_scores:
+                r.scores.append(self._view(logits)[0].clone())
+            first = self.first[row:row + 1]
+            self._sample_into(logits, None if r.uniforms is None else r.uniforms[:1].to(self.device), first)      # stays on the device
+            self.input_ids[row:row + 1].copy_(first.view(1, 1))
+            self.slots[row:row + 1].fill_(slot)
+            r.slot, r.row, self.rows[row] = slot, row, r.rid
+            self._fresh.add(row)
+
+    # ---- the step ----------------------------------------------------------------------------------------------------------------------------
+    def _forward(self):
+        logits = self.model(self.input_ids, inference_params=self.params, num_last_tokens=1).logits[:, -1]
+        if self.fused_sampling:
+            self._sample_into(logits, self.u, self.input_ids)       # the step feeds itself: the token lands in its own input buffer
+        return logits
+
+    def _capture(self, n_warmups=2):
+        """the one graph of this engine. Warm-up runs on a side stream with every row idle (slot -1: no state of the pool is touched); the
+        live membership is put back before the capture, which records but does not run."""
+        live = self.slots.clone()
+        tokens = self.input_ids.clone()
+        self.slots.fill_(-1)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(n_warmups):
+                self._forward()
+            s.synchronize()
+        torch.cuda.current_stream().wait_stream(s)
+        self.slots.copy_(live)
+        self.input_ids.copy_(tokens)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self._logits = self._forward()
+        self.n_captures += 1
+
+    def _book(self, r, token, events):
+        r.tokens.append(token)
+        r.finished = self._done(r, token)
+        events.append((r.rid, token, r.finished))
+
+    def _retire(self, row, r):
+        self.free_slots.append(r.slot)
+        self.rows[row] = None
+        self.slots[row:row + 1].fill_(-1)
+        r.slot = r.row = -1
+
+    @torch.no_grad()
+    def step(self):
+        """admits what fits, then one decode step of every live request -> [(rid, token, finished)]: per row, the first token of a request
+        admitted in this step, then the step's token"""
+        self._admit()
+        live = [(row, self.requests[rid]) for row, rid in enumerate(self.rows) if rid is not None]
+        if not live:
+            return []
+        fresh, self._fresh = self._fresh, set()
+        if self.fused_sampling:
+            u = torch.zeros(self.max_batch, dtype=torch.float32)
+            for row, r in live:
+                i = len(r.tokens) + (row in fresh)           # a fresh row's first token is not in the book yet
+                u[row] = r.uniforms[i] if i < r.max_new_tokens else 0.0
+            self.u.copy_(u)
+        if self.cg:
+            if self._graph is None:
+                self._capture()
+            self._graph.replay()
+            logits = self._logits
+        else:
+            logits = self._forward()
+        if not self.fused_sampling:
+            self._sample_into(logits, None, self.input_ids)
+        tokens = torch.cat([self.first, self.input_ids[:, 0]]).tolist()      # the engine's only host read: 2 max_batch tokens, one copy
+        events = []
+        for row, r in live:
+            if row in fresh:
+                self._book(r, tokens[row], events)
+            if not r.finished:                               # else ended by its first token: the step's token of this row is dropped
+                if self.output_scores:
+                    r.scores.append(self._view(logits)[row].clone())
+                self._book(r, tokens[self.max_batch + row], events)
+            if r.finished:
+                self._retire(row, r)
+        return events

@@ -822,6 +822,55 @@ typedef struct {
 
 int dimsum_decode_linear(const dimsum_decode_linear_params_t *p, void *stream);
 
+/* Slot-indexed states (upstream Mamba's conv_state_indices / state_batch_indices; no reference counterpart): the three launches of a decode
+ * step that touch a carried state, on a POOL of states with a per-row slot index read on the device -- requests of different lengths share
+ * one decode batch, and one captured graph serves every membership of it, because the host only rewrites a few ints between replays.
+ *   slots : int32, one entry per batch row, slots_stride ELEMENTS apart (a device pointer; never read by the host).
+ *   The state tensor of the embedded struct (conv.conv_state_ptr / update.state_ptr / linear.conv_state_ptr) is the pool
+ *   (num_slots, dim, width | dstate) with the same three free ELEMENT strides as ever (its batch stride is the SLOT stride); num_slots is
+ *   independent of batch. Row b reads and writes state[slots[b]] where the plain entry point addresses state[b]; every other operand
+ *   (x, dt, z, B, C, dt_x, out, y) stays indexed by b. The arithmetic is the plain entry point's, expression by expression in the same
+ *   order (the same device function, entered with another row address): on equal state rows the results are bit-identical. The 16-byte and
+ *   element-walk predicates are evaluated on the pool: base alignment, unit inner stride, row and slot stride multiples of 4 elements.
+ *   slots[b] < 0 is a PADDING row: no state element of any slot is read or written and the row's outputs are zeros -- out[b, :] of the two
+ *   update entries; y[b, 0 : conv_dim) of dimsum_decode_linear_slots, whose plain columns y[b, conv_dim : n) are the GEMV of whatever x'
+ *   held, written as ever. Everything downstream of a padding row stays finite without the host's help.
+ * THE CALLER'S CONTRACT, which the host cannot check without a device read and therefore does not check: every slots[b] is < num_slots
+ * (a larger one addresses memory outside the pool), and no non-negative slot is named by two rows of one launch (the two rows race on one
+ * state). Both are undefined behaviour. dimsum_amd.utils.serving.DecodeEngine guarantees them by construction (a free list of slots).
+ * Checks, in this order: NULL struct (DIMSUM_ERR_NULL) / struct_size (DIMSUM_ERR_ABI, before anything else is read) / num_slots < 1
+ * (DIMSUM_ERR_SHAPE) / slots_ptr NULL (DIMSUM_ERR_NULL) / a negative slots_stride (DIMSUM_ERR_STRIDE) / then the plain entry point's checks
+ * on the embedded struct in their order (its struct_size is ignored; its `ext` is honoured); dimsum_decode_linear_slots also wants
+ * conv_dim > 0 (DIMSUM_ERR_UNSUPPORTED: without the epilogue there is no state to index). Nothing is launched before all of them pass; no
+ * allocation, no synchronisation. One launch each, as the plain entry points. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_conv_update_slots_params_t) */
+    int32_t num_slots;        /* rows of the pool, >= 1 */
+    dimsum_conv_update_params_t conv;
+    const void *slots_ptr;    /* int32 (batch) */
+    int64_t slots_stride;
+} dimsum_conv_update_slots_params_t;
+
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_state_update_slots_params_t) */
+    int32_t num_slots;
+    dimsum_state_update_params_t update;
+    const void *slots_ptr;
+    int64_t slots_stride;
+} dimsum_state_update_slots_params_t;
+
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_decode_linear_slots_params_t) */
+    int32_t num_slots;
+    dimsum_decode_linear_params_t linear;
+    const void *slots_ptr;
+    int64_t slots_stride;
+} dimsum_decode_linear_slots_params_t;
+
+int dimsum_causal_conv1d_update_slots(const dimsum_conv_update_slots_params_t *p, void *stream);
+int dimsum_selective_state_update_slots(const dimsum_state_update_slots_params_t *p, void *stream);
+int dimsum_decode_linear_slots(const dimsum_decode_linear_slots_params_t *p, void *stream);
+
 /* dimsum_cross_entropy_fwd / _bwd: the LM training loss over rows of logits and its gradient (csrc/cross_entropy.hip; the reference's training
  * recipes use a fused cross-entropy in this place). Per row m, with s = logit_scale * logits[m, :] and eps = label_smoothing:
  *     lse = logsumexp(s)      z = lse_square_scale * lse^2      loss = lse - (1 - eps) s[label] - (eps / vocab) sum(s) + z

@@ -1,0 +1,199 @@
+#!/usr/bin/env python3
+"""Serving throughput of the Mamba language model on a ragged workload: continuous batching (dimsum_amd.utils.serving.DecodeEngine, a slot
+pool and ONE captured step for every membership) against static batches through generate(cg=True), in one process, the two alternating
+round by round; then the time of one captured decode step with and without the slot index at equal batch.
+
+Model: a random-init Mamba-130m shape, as tools/bench_decode.py. Workload, seeded: `--requests` (64) requests, prompts of 16..128 tokens,
+16..256 new tokens each, greedy, no eos (every request runs to its length, so both sides produce the same number of USEFUL tokens: the sum
+of the requests' new tokens).
+  (a) engine: DecodeEngine(max_batch=B, num_slots=B, cg=True): all requests submitted, run() until idle. Each prompt is prefilled alone.
+  (b) static: the requests in submission order in batches of B through generate(cg=True, fused_sampling=True), prompts left-padded to the
+      batch's longest with the padding as a segment of its own (seq_idx), each batch decoding to its longest member: the tokens a shorter
+      member produces beyond its own length are waste.
+Both sides sample with the fused sampler inside the captured step. Useful tokens/s = useful tokens / wall time between two device
+synchronisations, prompt passes included on both sides; the median of `--rounds` rounds after one warm-up round of each (captures, the graph
+cache grown to its final size). DIMSUM_FUSED_DECODE is left as the caller set it (unset: the fused step for float32 at batch <= 4).
+
+Step time: the model's forward on a (B, 1) token buffer at seqlen_offset > 0 captured twice -- on a cache of B rows, and on a pool of B slots
+with state_indices = a permutation of 0..B-1 -- `--steps` replays each between two synchronisations, alternating, median of `--rounds`,
+with DIMSUM_FUSED_DECODE=1 and =0. The un-indexed kernels are the parent commit's instruction for instruction, so the
+first of the two is the parent's step.
+
+    python tools/bench_serve.py [--batches 4 16] [--rounds 5] [--requests 64] [--dtype float32] [--out serve_bench.json]
+prints one JSON line per measurement and two markdown tables at the end."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPE = dict(d_model=768, n_layer=24, vocab_size=50280, pad_vocab_size_multiple=8, rms_norm=True, fused_add_norm=True, residual_in_fp32=True)
+PROMPT_RANGE, NEW_RANGE = (16, 128), (16, 256)
+
+
+def workload(n_requests, seed=0, vocab=SHAPE["vocab_size"]):
+    """-> [(prompt (L,) int64 on the host, new tokens)]: seeded, prompt lengths and new-token counts uniform over their ranges (inclusive)"""
+    g = torch.Generator().manual_seed(seed)
+    lens = torch.randint(PROMPT_RANGE[0], PROMPT_RANGE[1] + 1, (n_requests,), generator=g).tolist()
+    news = torch.randint(NEW_RANGE[0], NEW_RANGE[1] + 1, (n_requests,), generator=g).tolist()
+    return [(torch.randint(0, vocab, (n,), generator=g), m) for n, m in zip(lens, news)]
+
+
+def static_batches(requests, B):
+    """-> [(ids (b, L) left-padded with token 0, seq_idx (b, L) int32, max_length)] of the requests in order, B at a time"""
+    from dimsum_amd.utils import seq_idx_from_lengths
+    out = []
+    for i in range(0, len(requests), B):
+        part = requests[i:i + B]
+        L = max(p.numel() for p, _ in part)
+        ids = torch.stack([torch.cat([p.new_zeros(L - p.numel()), p]) for p, _ in part])
+        seq = torch.stack([seq_idx_from_lengths([L - p.numel(), p.numel()]) for p, _ in part])
+        out.append((ids, seq, L + max(n for _, n in part)))
+    return out
+
+
+def run_engine(eng, requests):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    rids = [eng.submit(p, n) for p, n in requests]
+    out = eng.run()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert all(out[r].numel() == p.numel() + n for r, (p, n) in zip(rids, requests))
+    eng.requests.clear()                                     # the results are out: the next round starts from an empty book
+    return dt
+
+
+def run_static(model, batches):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for ids, seq, max_length in batches:
+        model.generate(ids, max_length=max_length, cg=True, fused_sampling=True, vocab_size=SHAPE["vocab_size"], seq_idx=seq)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def serve_bench(model, requests, B, rounds):
+    from dimsum_amd.utils.serving import DecodeEngine
+    useful = sum(n for _, n in requests)
+    batches = [(ids.cuda(), seq.cuda(), m) for ids, seq, m in static_batches(requests, B)]
+    decoded = sum(ids.shape[0] * (m - ids.shape[1]) for ids, _, m in batches)
+    model._decoding_cache = None
+    eng = DecodeEngine(model, max_batch=B, num_slots=B, max_seqlen=PROMPT_RANGE[1] + NEW_RANGE[1], vocab_size=SHAPE["vocab_size"], cg=True)
+    # the static side's cache at its final size before anything is timed: the longest batch first, so no later batch re-captures
+    longest = max(batches, key=lambda b: b[2])
+    model.generate(longest[0], max_length=longest[2], cg=True, fused_sampling=True, vocab_size=SHAPE["vocab_size"], seq_idx=longest[1])
+    run_engine(eng, requests)                                # warm-up round of each
+    run_static(model, batches)
+    times = {"engine": [], "static": []}
+    for _ in range(rounds):
+        times["engine"].append(run_engine(eng, requests))
+        times["static"].append(run_static(model, batches))
+    row = dict(batch=B, requests=len(requests), useful_tokens=useful, static_decoded_tokens=decoded, rounds=rounds, engine_captures=eng.n_captures)
+    for k, v in times.items():
+        row[f"{k}_tokens_per_s"] = round(useful / statistics.median(v), 1)
+        row[f"spread_{k}"] = round(max(v) / min(v), 3)
+    row["engine_over_static"] = round(row["engine_tokens_per_s"] / row["static_tokens_per_s"], 3)
+    model._decoding_cache = None
+    return row
+
+
+def captured_step(model, params, B):
+    """-> replay(): one forward of the model on a static (B, 1) token buffer at seqlen_offset > 0, captured after two warm-up runs"""
+    ids = torch.zeros(B, 1, dtype=torch.long, device="cuda")
+    step = lambda: model(ids, inference_params=params, num_last_tokens=1).logits
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            step()
+        side.synchronize()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step()
+    return graph.replay
+
+
+def step_bench(model, B, steps, rounds, fused):
+    from dimsum_amd.utils import InferenceParams
+    os.environ["DIMSUM_FUSED_DECODE"] = fused
+    dtype = next(iter(model.parameters())).dtype
+    with torch.no_grad():
+        plain = InferenceParams(max_seqlen=8, max_batch_size=B, seqlen_offset=1, key_value_memory_dict=model.allocate_inference_cache(B, 8, dtype))
+        perm = torch.randperm(B, generator=torch.Generator().manual_seed(B)).to(torch.int32).cuda()
+        pooled = InferenceParams(max_seqlen=8, max_batch_size=B, seqlen_offset=1, key_value_memory_dict=model.allocate_inference_cache(B, 8, dtype),
+                                 state_indices=perm)
+        sides = {"plain": captured_step(model, plain, B), "slots": captured_step(model, pooled, B)}
+
+    def timed(replay):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            replay()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps * 1e6
+
+    for r in sides.values():
+        timed(r)
+    times = {k: [] for k in sides}
+    for _ in range(rounds):
+        for k, r in sides.items():
+            times[k].append(timed(r))
+    row = dict(batch=B, fused_decode=fused, steps=steps, rounds=rounds)
+    for k, v in times.items():
+        row[f"{k}_step_us"] = round(statistics.median(v), 1)
+        row[f"spread_{k}"] = round(max(v) / min(v), 3)
+    row["slots_over_plain"] = round(row["slots_step_us"] / row["plain_step_us"], 4)
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="*", default=[4, 16])
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--requests", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=512, help="replays per timed window of the step comparison")
+    ap.add_argument("--dtype", default="float32")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_serve needs the GPU"
+    from dimsum_amd.models.mixer_seq_simple import MambaLMHeadModel
+    policy = os.environ.get("DIMSUM_FUSED_DECODE")
+    torch.manual_seed(0)
+    model = MambaLMHeadModel(**SHAPE, device="cuda", dtype=getattr(torch, args.dtype)).eval()
+    requests = workload(args.requests, args.seed)
+    serve, steps = [], []
+    for B in args.batches:
+        row = dict(serve_bench(model, requests, B, args.rounds), dtype=args.dtype, fused_decode=policy or "unset")
+        serve.append(row)
+        print(json.dumps(row), flush=True)
+    for B in args.batches:
+        for fused in ("1", "0"):
+            row = dict(step_bench(model, B, args.steps, args.rounds, fused), dtype=args.dtype)
+            steps.append(row)
+            print(json.dumps(row), flush=True)
+    if policy is None:
+        os.environ.pop("DIMSUM_FUSED_DECODE", None)
+    else:
+        os.environ["DIMSUM_FUSED_DECODE"] = policy
+    print("\n| B | useful tokens | engine tok/s | static tok/s | engine / static | static decoded tokens |\n|---|---|---|---|---|---|")
+    for r in serve:
+        print(f"| {r['batch']} | {r['useful_tokens']} | {r['engine_tokens_per_s']:.0f} | {r['static_tokens_per_s']:.0f} | {r['engine_over_static']:.2f} | "
+              f"{r['static_decoded_tokens']} |")
+    print("\n| B | DIMSUM_FUSED_DECODE | un-indexed step us | slot-indexed step us | slots / plain |\n|---|---|---|---|---|")
+    for r in steps:
+        print(f"| {r['batch']} | {r['fused_decode']} | {r['plain_step_us']:.1f} | {r['slots_step_us']:.1f} | {r['slots_over_plain']:.3f} |")
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(dict(serve=serve, step=steps), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
