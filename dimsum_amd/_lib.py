@@ -113,6 +113,14 @@ class SsmVarlenBwdParams(_Sized):
     _fields_ = [("struct_size", u32), ("reserved", u32), ("bwd", SsmGeneralBwdParams), ("seq_idx_ptr", vp), ("seq_idx_batch_stride", i64)]
 
 
+class SsmVarlenStatesParams(_Sized):
+    """dimsum_ssm_varlen_states_params_t: SsmVarlenParams + end_slots (batch, seqlen) int32 -- where it is >= 0 the state after that position
+    goes into that slot of a (num_slots, dim, dstate) pool"""
+    _fields_ = ([("struct_size", u32), ("num_slots", i32), ("varlen", SsmVarlenParams), ("end_slots_ptr", vp), ("end_slots_batch_stride", i64),
+                 ("state_ptr", vp)] + [(n, i64) for n in ("state_slot_stride", "state_d_stride", "state_dstate_stride")]
+                + [("state_f32", i32), ("reserved", i32)])
+
+
 class OptimParams(_Sized):
     """dimsum_optim_params_t: device tables of the tensor list + hyper-parameters of one clip / AdamW / EMA step"""
     _fields_ = ([("struct_size", u32), ("n_tensors", i32), ("n_chunks", i32), ("n_partials", i32)]
@@ -200,6 +208,14 @@ class ConvVarlenParams(_Sized):
 class ConvVarlenBwdParams(_Sized):
     """dimsum_conv_varlen_bwd_params_t"""
     _fields_ = [("struct_size", u32), ("reserved", u32), ("conv", ConvBwdParams), ("seq_idx_ptr", vp), ("seq_idx_batch_stride", i64)]
+
+
+class ConvVarlenStatesParams(_Sized):
+    """dimsum_conv_varlen_states_params_t: ConvVarlenParams + end_slots (batch, seqlen) int32 -- where it is >= 0 the conv state of the segment
+    ending there goes into that slot of a (num_slots, dim, width) pool of x's dtype"""
+    _fields_ = ([("struct_size", u32), ("num_slots", i32), ("varlen", ConvVarlenParams), ("end_slots_ptr", vp), ("end_slots_batch_stride", i64),
+                 ("state_ptr", vp)] + [(n, i64) for n in ("state_slot_stride", "state_c_stride", "state_w_stride")]
+                + [("state_dtype", i32), ("reserved", i32)])
 
 
 class ConvClParams(_Sized):
@@ -452,6 +468,7 @@ EXPORTS = (
     "dimsum_ssm_scan_general_fwd", "dimsum_ssm_scan_general_bwd", "dimsum_ssm_scan_general_bwd_workspace_bytes",
     "dimsum_ssm_scan_carry_fwd", "dimsum_causal_conv1d_chunk",
     "dimsum_causal_conv1d_varlen_fwd", "dimsum_causal_conv1d_varlen_bwd", "dimsum_ssm_scan_varlen_fwd", "dimsum_ssm_scan_varlen_bwd",
+    "dimsum_causal_conv1d_varlen_states_fwd", "dimsum_ssm_scan_varlen_states_fwd",
     "dimsum_optim_grad_sumsq", "dimsum_optim_adamw_ema_step", "dimsum_optim_write_ptrs",
     "dimsum_fm_plan", "dimsum_fm_loss_fwd", "dimsum_fm_loss_bwd",
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
@@ -498,7 +515,8 @@ _SIGNATURES = (
         ("dimsum_causal_conv1d_varlen_fwd", ConvVarlenParams), ("dimsum_causal_conv1d_varlen_bwd", ConvVarlenBwdParams),
         ("dimsum_ssm_scan_varlen_fwd", SsmVarlenParams), ("dimsum_ssm_scan_varlen_bwd", SsmVarlenBwdParams),
         ("dimsum_causal_conv1d_update_slots", ConvUpdateSlotsParams), ("dimsum_selective_state_update_slots", StateUpdateSlotsParams),
-        ("dimsum_decode_linear_slots", DecodeLinearSlotsParams))]
+        ("dimsum_decode_linear_slots", DecodeLinearSlotsParams),
+        ("dimsum_causal_conv1d_varlen_states_fwd", ConvVarlenStatesParams), ("dimsum_ssm_scan_varlen_states_fwd", SsmVarlenStatesParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

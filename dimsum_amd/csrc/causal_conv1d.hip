@@ -18,6 +18,13 @@
 // from one position to the next (no boundary in (t-j, t]); a masked value is replaced by 0 with a select, never multiplied away, so what
 // lies beyond a boundary cannot reach the result whatever it holds. Ids are only compared. The backward applies the same rule to the
 // gradient halo, which comes from the right. kVarlen = false compiles to the kernels as they were.
+//
+// Per-segment states (dimsum_causal_conv1d_varlen_states_fwd, kEmit on top of kVarlen, forward only): a second int32 row, end_slots, is
+// loaded like the ids. For output element t the lane holds the masked taps x[t], k1 ? x[t-1] : 0, ... -- the conv state of a segment that
+// ends at t, zero-padded on the left -- and where end_slots[t] >= 0 it stores the last `width` of them to pool[slot, d, 0 : width),
+// x[t] last (the layout causal_conv1d_update shifts). The values are the loaded x elements: widened to fp32 on the load and narrowed back
+// on the store, which is the identity on every T. A row the kernel clamped onto the last one stores nothing. kEmit = false compiles to the
+// kernels as they were.
 #include "common.hpp"
 
 #include <type_traits>
@@ -98,14 +105,27 @@ struct conv_varlen_bwd_args_t {
     const int32_t *seq_idx;
     int64_t seq_batch_stride;
 };
+// the kEmit forward: + end_slots, (batch, seqlen) int32 laid out like seq_idx, and the pool (num_slots, dim, width) of x's dtype
+struct conv_states_args_t {
+    conv_varlen_args_t v;
+    const int32_t *end_slots;
+    int64_t end_batch_stride;
+    void *pool;
+    int64_t pool_slot_stride, pool_c_stride, pool_w_stride;
+};
+__device__ __forceinline__ const dimsum_conv_params_t &conv_base(const conv_states_args_t &a) { return a.v.p; }
+__device__ __forceinline__ const conv_varlen_args_t &conv_ids(const conv_varlen_args_t &a) { return a; }
+__device__ __forceinline__ const conv_varlen_args_t &conv_ids(const conv_states_args_t &a) { return a.v; }
 __device__ __forceinline__ const dimsum_conv_params_t &conv_base(const dimsum_conv_params_t &a) { return a; }
 __device__ __forceinline__ const dimsum_conv_params_t &conv_base(const conv_varlen_args_t &a) { return a.p; }
 __device__ __forceinline__ const dimsum_conv_bwd_params_t &conv_base(const dimsum_conv_bwd_params_t &a) { return a; }
 __device__ __forceinline__ const dimsum_conv_bwd_params_t &conv_base(const conv_varlen_bwd_args_t &a) { return a.q; }
 
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T, bool kVec, bool kVarlen>
-__global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(const std::conditional_t<kVarlen, conv_varlen_args_t, dimsum_conv_params_t> a) {
+template <typename T, bool kVec, bool kVarlen, bool kEmit = false>
+__global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(
+    const std::conditional_t<kEmit, conv_states_args_t, std::conditional_t<kVarlen, conv_varlen_args_t, dimsum_conv_params_t>> a) {
+    static_assert(!kEmit || kVarlen, "per-segment states belong to packed rows");
     const dimsum_conv_params_t &p = conv_base(a);
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -121,6 +141,8 @@ __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(const std::condi
         bool ok[kR];
         const int32_t *sq[kR];                               // kVarlen: the row's ids and those of t0-1, t0-2, t0-3 carried like c1 .. c3
         int i1[kR], i2[kR], i3[kR];
+        const int32_t *eq[kR];                               // kEmit: the row's end_slots and its channel's place in the pool
+        T *pl[kR];
 #pragma unroll
         for (int r = 0; r < kR; ++r) {
             const int64_t row = min(row0 + r * gstride, rows - 1);
@@ -134,18 +156,23 @@ __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(const std::condi
             bias[r] = p.bias_ptr ? reinterpret_cast<const float *>(p.bias_ptr)[d] : 0.f;
             c1[r] = c2[r] = c3[r] = 0.f;                     // x[t0-1], x[t0-2], x[t0-3] carried across 256-element steps
             if constexpr (kVarlen) {
-                sq[r] = a.seq_idx + (int64_t)b * a.seq_batch_stride;
+                sq[r] = conv_ids(a).seq_idx + (int64_t)b * conv_ids(a).seq_batch_stride;
                 i1[r] = i2[r] = i3[r] = 0;                   // before the row: the x halo there is 0, whatever the comparison says
+            }
+            if constexpr (kEmit) {
+                eq[r] = a.end_slots + (int64_t)b * a.end_batch_stride;
+                pl[r] = reinterpret_cast<T *>(a.pool) + (int64_t)d * a.pool_c_stride;
             }
         }
         for (int t0 = 0; t0 < L; t0 += 4 * kWave) {
             const int t = t0 + lane * 4;
             f32x4 v[kR];
-            i32x4 id[kR];
+            i32x4 id[kR], es[kR];
 #pragma unroll
             for (int r = 0; r < kR; ++r) {
                 v[r] = load_row4<T, kVec>(x[r], t, L);
                 if constexpr (kVarlen) id[r] = load_ids4<kVec>(sq[r], t, L);
+                if constexpr (kEmit) es[r] = load_ids4<kVec>(eq[r], t, L);
             }
 #pragma unroll
             for (int r = 0; r < kR; ++r) {
@@ -161,6 +188,16 @@ __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(const std::condi
                         const bool k1 = I[e + 3] == I[e + 2], k2 = k1 && I[e + 2] == I[e + 1], k3 = k2 && I[e + 1] == I[e];
                         q.v[e] = bias[r] + w4[r][0] * (k3 ? xs[e] : 0.f) + w4[r][1] * (k2 ? xs[e + 1] : 0.f) + w4[r][2] * (k1 ? xs[e + 2] : 0.f) +
                                  w4[r][3] * xs[e + 3];
+                        if constexpr (kEmit) {
+                            // a segment ends at t + e: its conv state is the masked taps. load_ids4 reads 0 beyond the row, a valid slot: t + e < L
+                            if (ok[r] && t + e < L && es[r].v[e] >= 0) {
+                                T *st = pl[r] + (int64_t)es[r].v[e] * a.pool_slot_stride;
+                                const float tap[4] = {k3 ? xs[e] : 0.f, k2 ? xs[e + 1] : 0.f, k1 ? xs[e + 2] : 0.f, xs[e + 3]};
+#pragma unroll
+                                for (int k = 0; k < 4; ++k)
+                                    if (k >= 4 - W) st[(int64_t)(k - (4 - W)) * a.pool_w_stride] = from_f32<T>(tap[k]);
+                            }
+                        }
                     }
                     i1[r] = __shfl(id[r].v[3], kWave - 1, kWave);
                     i2[r] = __shfl(id[r].v[2], kWave - 1, kWave);
@@ -393,12 +430,19 @@ template <typename T> static bool vec_ok(const void *ptr, int64_t s0, int64_t s1
 static bool ids_vec_ok(const int32_t *seq_idx, int64_t batch_stride) { return aligned_to<int32_t>(seq_idx, 16) && batch_stride % 4 == 0; }
 
 // seq_idx == nullptr: the plain kernels, launched exactly as before
-template <typename T> static int launch_conv_fwd(const dimsum_conv_params_t &p, hipStream_t s, const int32_t *seq_idx = nullptr, int64_t seq_batch_stride = 0) {
+// st != nullptr: the kEmit kernels (st->v is filled here)
+template <typename T> static int launch_conv_fwd(const dimsum_conv_params_t &p, hipStream_t s, const int32_t *seq_idx = nullptr, int64_t seq_batch_stride = 0,
+                                                 conv_states_args_t *st = nullptr) {
     const bool vec = vec_ok<T>(p.x_ptr, p.x_batch_stride, p.x_c_stride, p.seqlen) &&
                      vec_ok<T>(p.out_ptr, p.out_batch_stride, p.out_c_stride, p.seqlen);
     const int64_t rows = (int64_t)p.batch * p.dim;
     const int grid = (int)((rows + 15) / 16 < 256 * 32 ? (rows + 15) / 16 : 256 * 32);   // 4 waves x 4 rows per workgroup and pass (a 2x larger grid measured slower)
-    if (seq_idx) {
+    if (st) {
+        st->v = {p, seq_idx, seq_batch_stride};
+        if (vec && ids_vec_ok(seq_idx, seq_batch_stride) && ids_vec_ok(st->end_slots, st->end_batch_stride))
+            hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true, true, true>), dim3(grid), dim3(256), 0, s, *st);
+        else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false, true, true>), dim3(grid), dim3(256), 0, s, *st);
+    } else if (seq_idx) {
         const conv_varlen_args_t a = {p, seq_idx, seq_batch_stride};
         if (vec && ids_vec_ok(seq_idx, seq_batch_stride)) hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true, true>), dim3(grid), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false, true>), dim3(grid), dim3(256), 0, s, a);
@@ -529,5 +573,36 @@ extern "C" int dimsum_causal_conv1d_varlen_bwd(const dimsum_conv_varlen_bwd_para
         case DIMSUM_F32: return launch_conv_bwd<float>(*q, s, ids, v->seq_idx_batch_stride);
         case DIMSUM_F16: return launch_conv_bwd<__half>(*q, s, ids, v->seq_idx_batch_stride);
         default: return launch_conv_bwd<__hip_bfloat16>(*q, s, ids, v->seq_idx_batch_stride);
+    }
+}
+
+extern "C" int dimsum_causal_conv1d_varlen_states_fwd(const dimsum_conv_varlen_states_params_t *e, void *stream) {
+    using namespace dimsum;
+    if (!e) return DIMSUM_ERR_NULL;
+    if (e->struct_size != sizeof(dimsum_conv_varlen_states_params_t)) return DIMSUM_ERR_ABI;
+    if (e->num_slots < 1) return DIMSUM_ERR_SHAPE;
+    if (!e->end_slots_ptr || !e->state_ptr) return DIMSUM_ERR_NULL;
+    const dimsum_conv_params_t *p = &e->varlen.conv;
+    if (e->end_slots_batch_stride < 0 || (p->batch > 1 && e->end_slots_batch_stride < p->seqlen)) return DIMSUM_ERR_STRIDE;
+    if (e->state_slot_stride < 0 || e->state_c_stride < 0 || e->state_w_stride < 0) return DIMSUM_ERR_STRIDE;
+    if (!p->out_ptr) return DIMSUM_ERR_NULL;
+    int rc = conv_check(*p);
+    if (rc != DIMSUM_OK) return rc;
+    rc = conv_varlen_ids_check(e->varlen.seq_idx_ptr, e->varlen.seq_idx_batch_stride, p->batch, p->seqlen);
+    if (rc != DIMSUM_OK) return rc;
+    if (e->state_dtype != p->dtype) return DIMSUM_ERR_UNSUPPORTED;      // the state is x's elements, moved
+    if (p->batch == 0) return DIMSUM_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int32_t *ids = reinterpret_cast<const int32_t *>(e->varlen.seq_idx_ptr);
+    conv_states_args_t st;
+    memset(&st, 0, sizeof(st));
+    st.end_slots = reinterpret_cast<const int32_t *>(e->end_slots_ptr);
+    st.end_batch_stride = e->end_slots_batch_stride;
+    st.pool = e->state_ptr;
+    st.pool_slot_stride = e->state_slot_stride, st.pool_c_stride = e->state_c_stride, st.pool_w_stride = e->state_w_stride;
+    switch (p->dtype) {
+        case DIMSUM_F32: return launch_conv_fwd<float>(*p, s, ids, e->varlen.seq_idx_batch_stride, &st);
+        case DIMSUM_F16: return launch_conv_fwd<__half>(*p, s, ids, e->varlen.seq_idx_batch_stride, &st);
+        default: return launch_conv_fwd<__hip_bfloat16>(*p, s, ids, e->varlen.seq_idx_batch_stride, &st);
     }
 }

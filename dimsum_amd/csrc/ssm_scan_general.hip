@@ -23,7 +23,13 @@
 // a wave reads the tile's kT ids and the one before them -- the row is the workgroup's, so the addresses and the resulting kT-bit reset
 // mask are wave-uniform and every wave of the workgroup forms the same mask -- and at a set bit the step starts from h = 0 (a select on
 // h_{t-1}, so nothing of the previous segment survives, not even a NaN). The backward masks a_t h_{t-1} and the adjoint hand-over the same way.
+// Per-segment states (dimsum_ssm_scan_varlen_states_fwd, kEmit on top of kVarlen): a second int32 row, end_slots, rides next to the ids and is
+// read the same way (uniform addresses, a kT-bit wave-uniform mask). After a step whose bit is set every lane stores the h[j] it has just
+// computed -- the value the next step would read -- to pool[slot, d, n0 + j]: one lane per (channel, state), as for hT. The stores sit
+// behind a uniform branch inside the statically unrolled tile loop; kEmit = false compiles to the kernels as they were.
 #include "common.hpp"
+
+#include <type_traits>
 
 namespace dimsum {
 
@@ -43,6 +49,15 @@ struct gen_args_t {
     int64_t dpad;                          // padded channel count of the saved states: n_groups * cblocks * 64
     const int32_t *seq_idx;                // packed rows (kVarlen): (batch, seqlen) ids, rows seq_batch_stride apart; else NULL
     int64_t seq_batch_stride;
+};
+
+// the kernel argument of the kEmit kernels: the plain one + where the per-segment states go
+struct gen_emit_args_t : gen_args_t {
+    const int32_t *end_slots;              // (batch, seqlen) int32, rows end_batch_stride apart: >= 0 = store the state after this position into that slot
+    int64_t end_batch_stride;
+    void *pool;                            // (num_slots, dim, dstate), three free element strides
+    int64_t pool_slot_stride, pool_d_stride, pool_dstate_stride;
+    int32_t pool_f32;                      // the pool is float; else of the I/O type
 };
 
 constexpr int kGenChunk = 2048;            // selective_scan.cpp:307
@@ -136,10 +151,25 @@ template <int kT> __device__ __forceinline__ unsigned reset_mask(const int32_t *
     return (unsigned)__builtin_amdgcn_readfirstlane((int)m);
 }
 
+// the slots of one tile of end_slots and their mask: bit i = the state after position t0 + i is stored into slot[i] (>= 0; positions beyond
+// the row never store). The row is the workgroup's, as for reset_mask: uniform addresses, scalar results.
+template <int kT> __device__ __forceinline__ unsigned emit_mask(const int32_t *ends, int t0, int L, int (&slot)[kT]) {
+    unsigned m = 0;
+#pragma unroll
+    for (int i = 0; i < kT; ++i) {
+        const int t = t0 + i;
+        const int s = __builtin_amdgcn_readfirstlane(ends[t < L ? t : L - 1]);
+        slot[i] = s;
+        if (t < L && s >= 0) m |= 1u << i;
+    }
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)m);
+}
+
 // ---- forward ---------------------------------------------------------------------------------------------------------------------------------
-template <typename T, bool kCplx, bool kVarB, bool kVarC, int kNB, int kMaxThreads, bool kVarlen>
-__global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const gen_args_t a) {
+template <typename T, bool kCplx, bool kVarB, bool kVarC, int kNB, int kMaxThreads, bool kVarlen, bool kEmit = false>
+__global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const std::conditional_t<kEmit, gen_emit_args_t, gen_args_t> a) {
     static_assert(!kVarlen || (!kCplx && kVarB && kVarC), "packed rows: real A with input-dependent B and C");
+    static_assert(!kEmit || kVarlen, "per-segment states belong to packed rows");
     using Cfg = GenCfg<kCplx, kNB>;
     constexpr int kK = Cfg::kK, kT = Cfg::kT, kRow = Cfg::kRow;
     extern __shared__ float red[];                      // [wave][step][lane]
@@ -176,6 +206,8 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
     float sumdt = 0.f, sumdt_lo = 0.f;                  // x's running product = exp(A sum dt); compensated: the phase of a complex product is A.im sum dt
     const int32_t *ids = kVarlen ? a.seq_idx + (int64_t)q.b * a.seq_batch_stride : nullptr;
     bool cut = false;                                   // kVarlen: a boundary lies behind: the running product is 0 from there on
+    const int32_t *ends = nullptr;                      // kEmit: the row's end_slots
+    if constexpr (kEmit) ends = a.end_slots + (int64_t)q.b * a.end_batch_stride;
 
     for (int t0 = 0; t0 < L; t0 += kT) {
         unsigned rm = 0;
@@ -183,6 +215,9 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
             rm = reset_mask<kT>(ids, t0, L);
             cut = cut || rm != 0;
         }
+        unsigned em = 0;
+        int eslot[kT];
+        if constexpr (kEmit) em = emit_mask<kT>(ends, t0, L, eslot);
         float uv[kT], dt[kT], y[kT];
 #pragma unroll
         for (int i = 0; i < kT; ++i) {
@@ -217,6 +252,18 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
                     const float bv = kVarB ? lane_value(bt, j * kRow + i) : Bc[j], cv = kVarC ? lane_value(ct, j * kRow + i) : Cc[j];
                     h[j] = fmaf(pr, kVarlen && ((rm >> i) & 1u) ? 0.f : h[j], dtu * bv);
                     y[i] = fmaf(h[j], cv, y[i]);
+                }
+            }
+            if constexpr (kEmit) {
+                if ((em >> i) & 1u) {                   // wave-uniform: a segment ends at t0 + i; this lane's states, as hT writes them
+                    const int64_t base = (int64_t)eslot[i] * a.pool_slot_stride + (int64_t)q.d * a.pool_d_stride;
+#pragma unroll
+                    for (int j = 0; j < kNB; ++j) {
+                        if (!q.live || q.n0 + j >= N) continue;
+                        const int64_t off = base + (int64_t)(q.n0 + j) * a.pool_dstate_stride;
+                        if (a.pool_f32) reinterpret_cast<float *>(a.pool)[off] = h[j];
+                        else reinterpret_cast<T *>(a.pool)[off] = from_f32<T>(h[j]);
+                    }
                 }
             }
         }
@@ -638,6 +685,28 @@ static int gen_run(gen_args_t &a, bool forward, hipStream_t s) {
     }
 }
 
+// packed rows with per-segment states: the launch shape of the kVarlen forward on the kEmit instantiations
+template <typename T> static int gen_emit_launch(const gen_emit_args_t &e, hipStream_t s) {
+    const dimsum_ssm_general_params_t &p = e.f;
+    const int nb = gen_nb(p.dstate), W = (p.dstate + nb - 1) / nb;
+    const int kT = gen_tile_steps(p.dstate, false);
+    const dim3 grid((unsigned)(p.n_groups * e.cblocks), (unsigned)p.batch), block((unsigned)(64 * W));
+    const size_t lds = (size_t)W * kT * 64 * sizeof(float);
+    if (W <= 4) hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, false, true, true, 16, 256, true, true>), grid, block, lds, s, e);
+    else hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, false, true, true, 16, 1024, true, true>), grid, block, lds, s, e);
+    return launch_status();
+}
+
+static int gen_emit_run(gen_emit_args_t &e, hipStream_t s) {
+    e.cblocks = (e.f.dim / e.f.n_groups + 63) / 64;
+    e.dpad = (int64_t)e.f.n_groups * e.cblocks * 64;
+    switch (e.f.dtype) {
+        case DIMSUM_F32: return gen_emit_launch<float>(e, s);
+        case DIMSUM_F16: return gen_emit_launch<__half>(e, s);
+        default: return gen_emit_launch<__hip_bfloat16>(e, s);
+    }
+}
+
 }  // namespace dimsum
 
 extern "C" int dimsum_ssm_scan_general_fwd(const dimsum_ssm_general_params_t *p, void *stream) {
@@ -735,4 +804,30 @@ extern "C" int dimsum_ssm_scan_varlen_fwd(const dimsum_ssm_varlen_params_t *p, v
     a.seq_idx = reinterpret_cast<const int32_t *>(p->seq_idx_ptr);
     a.seq_batch_stride = p->seq_idx_batch_stride;
     return gen_run(a, true, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dimsum_ssm_scan_varlen_states_fwd(const dimsum_ssm_varlen_states_params_t *p, void *stream) {
+    using namespace dimsum;
+    if (!p) return DIMSUM_ERR_NULL;
+    if (p->struct_size != sizeof(dimsum_ssm_varlen_states_params_t)) return DIMSUM_ERR_ABI;
+    if (p->num_slots < 1) return DIMSUM_ERR_SHAPE;
+    if (!p->end_slots_ptr || !p->state_ptr) return DIMSUM_ERR_NULL;
+    const dimsum_ssm_general_params_t &f = p->varlen.scan;
+    if (p->end_slots_batch_stride < 0 || (f.batch > 1 && p->end_slots_batch_stride < f.seqlen)) return DIMSUM_ERR_STRIDE;
+    if (p->state_slot_stride < 0 || p->state_d_stride < 0 || p->state_dstate_stride < 0) return DIMSUM_ERR_STRIDE;
+    int rc = gen_check(f, true);
+    if (rc != DIMSUM_OK) return rc;
+    rc = gen_varlen_check(f, p->varlen.seq_idx_ptr, p->varlen.seq_idx_batch_stride);
+    if (rc != DIMSUM_OK) return rc;
+    gen_emit_args_t e;
+    memset(&e, 0, sizeof(e));
+    e.f = f;
+    e.seq_idx = reinterpret_cast<const int32_t *>(p->varlen.seq_idx_ptr);
+    e.seq_batch_stride = p->varlen.seq_idx_batch_stride;
+    e.end_slots = reinterpret_cast<const int32_t *>(p->end_slots_ptr);
+    e.end_batch_stride = p->end_slots_batch_stride;
+    e.pool = p->state_ptr;
+    e.pool_slot_stride = p->state_slot_stride, e.pool_d_stride = p->state_d_stride, e.pool_dstate_stride = p->state_dstate_stride;
+    e.pool_f32 = p->state_f32 != 0 || f.dtype == DIMSUM_F32;
+    return gen_emit_run(e, reinterpret_cast<hipStream_t>(stream));
 }

@@ -119,14 +119,27 @@ class MambaLMHeadModel(nn.Module, GenerationMixin):
         return (input_ids.shape[0] <= 16 and w.dtype in (torch.float32, torch.float16, torch.bfloat16)
                 and all(t is None or t.dtype == w.dtype for t in (self.lm_head.bias, b.norm_f.weight, b.norm_f.bias)))
 
-    def forward(self, input_ids, position_ids=None, inference_params=None, num_last_tokens=0, seq_idx=None):
+    def forward(self, input_ids, position_ids=None, inference_params=None, num_last_tokens=0, seq_idx=None, logits_positions=None):
         """position_ids: accepted and unused, as in the reference. num_last_tokens > 0: logits of the last n tokens only.
         seq_idx (B, L) int32: packed rows (several documents per row, or a left-padded prompt whose padding is a segment of its own); with
-        inference_params at seqlen_offset == 0 the cache is left holding every row's last segment; at seqlen_offset > 0 it raises"""
+        inference_params at seqlen_offset == 0 the cache is left holding every row's last segment (with inference_params.prefill_slots: every
+        segment's states go to its slot of the pools); at seqlen_offset > 0 it raises.
+        logits_positions (S,) int64 on the device, with seq_idx: flattened positions b * L + t -- the final hidden rows are gathered there
+        (index_select, no host read), the head runs on those S rows only and .logits is (S, V). Not together with num_last_tokens > 0."""
+        if logits_positions is not None:
+            if seq_idx is None:
+                raise ValueError("logits_positions without seq_idx: they name the last tokens of a packed row's segments (plan_packed_prefill)")
+            if num_last_tokens > 0:
+                raise ValueError("logits_positions together with num_last_tokens > 0: both choose the rows the head runs on; pass one")
+            if not (torch.is_tensor(logits_positions) and logits_positions.dtype == torch.int64 and logits_positions.dim() == 1):
+                raise ValueError("logits_positions must be a 1-D int64 tensor of flattened positions b * seqlen + t")
         if seq_idx is not None:
             if inference_params is not None and inference_params.seqlen_offset > 0:
                 raise ValueError("seq_idx at seqlen_offset > 0: sequence ids belong to the prompt pass (seqlen_offset == 0)")
             hidden_states = self.backbone(input_ids, inference_params=inference_params, seq_idx=seq_idx)
+            if logits_positions is not None:
+                rows = hidden_states.reshape(-1, hidden_states.shape[-1]).index_select(0, logits_positions)
+                return CausalLMOutput(logits=self.lm_head(rows))
             if num_last_tokens > 0:
                 hidden_states = hidden_states[:, -num_last_tokens:]
             return CausalLMOutput(logits=self.lm_head(hidden_states))

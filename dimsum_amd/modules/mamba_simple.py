@@ -133,9 +133,13 @@ class _MambaBase(nn.Module):
         if not (torch.is_tensor(seq_idx) and seq_idx.dtype == torch.int32 and tuple(seq_idx.shape) == tuple(hidden_states.shape[:2])):
             raise ValueError(f"seq_idx must be an int32 (batch, seqlen) = {tuple(hidden_states.shape[:2])} tensor")
 
-    def _mix(self, hidden_states, cond, x3=None, states=None, seq_idx=None):
+    def _mix(self, hidden_states, cond, x3=None, states=None, seq_idx=None, prefill_slots=None):
         """states: the (conv_state, ssm_state) of an inference cache, filled from this call's sequence (forward(inference_params=...));
-        seq_idx: packed rows (module docstring)"""
+        seq_idx: packed rows (module docstring); prefill_slots (B, L) int32 with both: `states` are POOLS and the conv and scan kernels store
+        every segment's states into the slot named at its last position (InferenceParams.prefill_slots) -- no torch op touches the states"""
+        if prefill_slots is not None:
+            self._refuse_prefill_slots(prefill_slots, hidden_states, cond, x3, states, seq_idx)
+            prefill_slots = prefill_slots.contiguous()
         if seq_idx is not None:
             self._refuse_seq_idx(seq_idx, hidden_states, cond, x3)
             seq_idx = seq_idx.contiguous()
@@ -163,7 +167,10 @@ class _MambaBase(nn.Module):
             xz = gemm.matmul_wx(self.in_proj.weight, hidden_states.reshape(bsz * L, -1).t()).view(2 * self.d_inner, bsz, L).permute(1, 0, 2)
         if self.in_proj.bias is not None:
             xz = xz + self.in_proj.bias.to(xz.dtype).view(1, -1, 1)
-        if states is not None:
+        if prefill_slots is not None and states[0].dtype != xz.dtype:
+            raise NotImplementedError(f"prefill_slots: the conv pool is {states[0].dtype} but the activations are {xz.dtype}: the conv kernel moves "
+                                      "x's elements into the pool, it does not convert them (allocate the pool in the activations' dtype)")
+        if states is not None and prefill_slots is None:
             # the last d_conv inputs of the conv (mamba_simple.py:258), zero-padded on the left when the prompt is shorter (module docstring)
             xin = xz[:, :self.d_inner]
             with torch.no_grad():       # the cache is data for the next calls, never an autograd edge
@@ -189,6 +196,12 @@ class _MambaBase(nn.Module):
                                                     delta_softplus=True, init_states=cond)
             y = (out + out_b.flip([-1])).transpose(1, 2)
             return nn.functional.linear(y, self.out_proj.weight, self.out_proj.bias)
+        if prefill_slots is not None:
+            out = mamba_inner_fn_cond(xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
+                                      self.out_proj.weight, self.out_proj.bias, A, None, None, self.D.float(),
+                                      delta_bias=self.dt_proj.bias.float(), delta_softplus=True, seq_idx=seq_idx, end_slots=prefill_slots,
+                                      conv_state=states[0], ssm_state=states[1])
+            return out
         out = mamba_inner_fn_cond(xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
                                   self.out_proj.weight, self.out_proj.bias, A, None, None, self.D.float(),
                                   delta_bias=self.dt_proj.bias.float(), delta_softplus=True, init_states=cond, conv_done=conv_done,
@@ -196,6 +209,26 @@ class _MambaBase(nn.Module):
         if own_gather:
             out = out.index_select(1, self.zigzag_paths_reverse[self.layer_idx])
         return out
+
+    def _refuse_prefill_slots(self, prefill_slots, hidden_states, cond, x3, states, seq_idx):
+        """what a packed prompt pass into slots is not built for, each with its reason; the VALUES of prefill_slots are never read"""
+        if seq_idx is None:
+            raise ValueError("prefill_slots without seq_idx: per-segment states belong to packed rows (pass seq_idx; one request alone is an "
+                             "all-equal id row)")
+        if self.scan_type == "v2" or self._is_zigzag():
+            raise NotImplementedError(f'prefill_slots with scan_type "{self.scan_type}" is not built: only the plain causal mixer ("none") has '
+                                      "states to leave behind")
+        if cond is not None:
+            raise NotImplementedError("prefill_slots with a conditional conv entry (cond) is not built")
+        if x3 is not None:
+            raise NotImplementedError("prefill_slots with an operand-image input (x3) is not built: pass hidden_states")
+        if states is None:
+            raise ValueError("prefill_slots need the pools of an inference cache (forward(inference_params=...))")
+        if not (torch.is_tensor(prefill_slots) and prefill_slots.dtype == torch.int32 and tuple(prefill_slots.shape) == tuple(hidden_states.shape[:2])):
+            raise ValueError(f"prefill_slots must be an int32 (batch, seqlen) = {tuple(hidden_states.shape[:2])} tensor")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("prefill_slots is an inference argument: the pass that stores states has no backward; call it under "
+                                      "torch.no_grad()")
 
     # ---- the recurrent form (mamba_simple.py:299-380) ------------------------------------------------------------------------------------------
     def _refuse_recurrent(self, x3=None):
@@ -297,13 +330,16 @@ class _MambaBase(nn.Module):
         return native.decode_linear(y, self.out_proj.weight, self.out_proj.bias), residual_out
 
     @torch.no_grad()
-    def extend(self, hidden_states, conv_state, ssm_state, state_indices=None):
+    def extend(self, hidden_states, conv_state, ssm_state, state_indices=None, prefill_slots=None):
         """any number of tokens on carried states, the sibling of `step`: hidden_states (B, T, d_model), T >= 1 -> (out (B, T, d_model),
         conv_state, ssm_state), both states updated in place: in_proj (d-major, as _mix forms xz) -> causal_conv1d_chunk -> x_proj / dt_proj
         (the general path of mamba_inner_fn) -> the scan entered with ssm_state and leaving it (csrc/ssm_scan_general.hip) with the z gate ->
         out_proj. No host read and no allocation depends on data: one call can be captured on a single stream.
         state_indices is refused: the chunk kernels address a batch's own states; a slot of a pool is extended through a view pool[s:s+1]."""
         self._refuse_recurrent()
+        if prefill_slots is not None:
+            raise NotImplementedError("extend with prefill_slots is not built: continuing a slot's state from a packed pass would need a carried "
+                                      "state per segment; a packed prompt is one pass at seqlen_offset == 0")
         if state_indices is not None:
             raise NotImplementedError("extend with state_indices is not built: causal_conv1d_chunk and the carried scan take no slot index (only "
                                       "the one-token step kernels do); extend slot s of a pool through the views pool[s:s+1]")
@@ -336,6 +372,21 @@ class _MambaBase(nn.Module):
             raise NotImplementedError(f'state_indices with scan_type "{self.scan_type}" is not built: only the plain causal mixer ("none") runs '
                                       "token by token, so only it has states to index")
         self._refuse_recurrent(x3)
+        prefill_slots = getattr(inference_params, "prefill_slots", None)
+        if prefill_slots is not None:
+            if seq_idx is None:
+                raise ValueError("prefill_slots without seq_idx: per-segment states belong to packed rows (pass seq_idx; one request alone is "
+                                 "an all-equal id row)")
+            if inference_params.seqlen_offset > 0:
+                raise ValueError("prefill_slots at seqlen_offset > 0: they belong to the packed prompt pass (seqlen_offset == 0); clear "
+                                 "inference_params.prefill_slots before the decode steps")
+            if state_indices is not None:
+                raise ValueError("prefill_slots together with state_indices: the first belong to a packed prompt pass, the second to the decode "
+                                 "steps; set one of them")
+            if self.layer_idx not in inference_params.key_value_memory_dict:
+                raise ValueError("prefill_slots need a pool of states in key_value_memory_dict (allocate_inference_cache(num_slots, ...))")
+            states = inference_params.key_value_memory_dict[self.layer_idx]
+            return self._mix(hidden_states, cond, states=states, seq_idx=seq_idx, prefill_slots=prefill_slots)
         if state_indices is not None and inference_params.seqlen_offset == 0:
             raise ValueError("state_indices at seqlen_offset == 0: a prompt is prefilled into slot s of a pool through the views pool[s:s+1] "
                              "with state_indices=None; the slot index belongs to the decode steps (seqlen_offset > 0)")

@@ -409,6 +409,47 @@ def causal_conv1d_varlen_fwd(x, weight, bias, silu_activation, seq_idx, out=None
     return out
 
 
+def _check_end_slots(end_slots, batch, seqlen, who):
+    """end_slots: (batch, seqlen) int32, contiguous -- where it is >= 0 the state after that position goes into that slot of a pool. Dtype,
+    rank, shape and contiguity here, the device by the caller, last. The VALUES stay on the device: that the non-negative ones are below
+    num_slots and that none appears twice in one launch is the caller's contract (include/dimsum_hip.h)."""
+    _check(torch.is_tensor(end_slots) and end_slots.dtype == torch.int32 and tuple(end_slots.shape) == (batch, seqlen) and end_slots.is_contiguous(),
+           f"{who}: end_slots must be a contiguous int32 (batch, seqlen) = ({batch}, {seqlen}) tensor")
+
+
+def causal_conv1d_varlen_states_fwd(x, weight, bias, silu_activation, seq_idx, end_slots, conv_state, out=None):
+    """causal_conv1d_varlen_fwd that also stores per-segment conv states -> out: where end_slots[b, t] = s >= 0, conv_state[s, :, :] becomes
+    the last `width` inputs of the segment ending at t (zero-padded on the left when the segment is shorter), x[b, :, t] last -- the window
+    causal_conv1d_update shifts. conv_state: a pool (num_slots, dim, width) of x's dtype with free strides; slots nobody names are not
+    touched. Inference only. The slots' values are the caller's contract (_check_end_slots)."""
+    who = "causal_conv1d_varlen_states_fwd"
+    _check(x.dim() == 3, "causal_conv1d: x must be (batch, dim, seqlen)")
+    _check_seq_idx(seq_idx, x.shape[0], x.shape[2], who)
+    _check_end_slots(end_slots, x.shape[0], x.shape[2], who)
+    _check(torch.is_tensor(conv_state) and conv_state.dim() == 3 and conv_state.shape[0] >= 1 and tuple(conv_state.shape[1:]) == (x.shape[1], weight.shape[-1]),
+           f"{who}: conv_state must be a pool (num_slots >= 1, dim, width)")
+    _check(conv_state.dtype == x.dtype, f"{who}: conv_state must have x's dtype {x.dtype}, got {conv_state.dtype} (the state is x's elements, moved, not converted)")
+    _check(not _check_conv(x, weight, bias), f"{who}: seq_idx needs a seqlen-contiguous x (the channel-last kernels take none)")
+    _gpu(seq_idx, end_slots, conv_state)
+    weight = weight.float()
+    bias = bias.float().contiguous() if bias is not None else None
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _gpu(out)
+        _check(out.shape == x.shape and out.dtype == x.dtype and out.stride(2) == 1, f"{who}: bad out")
+    if x.numel() > 0:
+        E = _lib.ConvVarlenStatesParams()
+        _fill_conv(E.varlen.conv, x, weight, bias, silu_activation, out)
+        E.varlen.seq_idx_ptr, E.varlen.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
+        E.num_slots, E.end_slots_ptr, E.end_slots_batch_stride = conv_state.shape[0], _ptr(end_slots), end_slots.stride(0)
+        E.state_ptr, E.state_dtype = _ptr(conv_state), _DT[conv_state.dtype]
+        E.state_slot_stride, E.state_c_stride, E.state_w_stride = conv_state.stride()
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dimsum_causal_conv1d_varlen_states_fwd(E, _stream(x)), who)
+    return out
+
+
 def causal_conv1d_varlen_bwd(x, weight, bias, dout, dx, silu_activation, seq_idx):
     """-> [dx, dweight, dbias] of causal_conv1d_varlen_fwd: dx[t] collects from the later positions of its own segment only; dweight sums
     the unmasked (tap, position) pairs, dbias every position"""
@@ -1094,26 +1135,55 @@ def selective_scan_varlen_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplu
     return selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=need_out, need_x=need_x, seq_idx=seq_idx)
 
 
+def selective_scan_varlen_states_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, seq_idx, end_slots, ssm_state, need_out=True, need_x=True):
+    """selective_scan_varlen_fwd that also stores per-segment states -> [out, x, (out_z)], exactly that function's: where end_slots[b, t] =
+    s >= 0, ssm_state[s, :, :] becomes h_t, the state after position t (what step t + 1 would read). ssm_state: a pool (num_slots, dim,
+    dstate), float32 or of u's dtype, with free strides; slots nobody names are not touched. Inference only. The slots' values are the
+    caller's contract (_check_end_slots)."""
+    who = "selective_scan_varlen_states_fwd"
+    _check(seq_idx is not None, f"{who}: seq_idx is required")
+    _check(torch.is_tensor(u) and u.dim() == 3, "selective_scan_general: u must be (batch, dim, seqlen) float32, float16 or bfloat16")
+    _check_end_slots(end_slots, u.shape[0], u.shape[2], who)
+    _check(torch.is_tensor(ssm_state) and ssm_state.dim() == 3 and ssm_state.shape[0] >= 1 and tuple(ssm_state.shape[1:]) == (u.shape[1], A.shape[1]),
+           f"{who}: ssm_state must be a pool (num_slots >= 1, dim, dstate)")
+    _check(ssm_state.dtype in (torch.float32, u.dtype), f"{who}: ssm_state must be float32 or of u's dtype {u.dtype}, got {ssm_state.dtype}")
+    return selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=need_out, need_x=need_x, seq_idx=seq_idx,
+                                      end_slots=end_slots, ssm_state=ssm_state)
+
+
 def selective_scan_varlen_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, seq_idx, dB=None, dC=None):
     """selective_scan_general_bwd on packed rows: the adjoint state is not handed across a boundary and the terms through a_t h_{t-1} vanish there"""
     _check(seq_idx is not None, "selective_scan_varlen_bwd: seq_idx is required")
     return selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, dB=dB, dC=dC, seq_idx=seq_idx)
 
 
-def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=True, need_x=True, *, seq_idx=None):
+def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=True, need_x=True, *, seq_idx=None, end_slots=None,
+                               ssm_state=None):
     """-> [out, x, (out_z)] like selective_scan_cuda.fwd, on the general kernels: A float32 or complex64 (dim, dstate), dstate 1..256; B / C
     input-dependent (batch, groups, dstate, seqlen) -- (.., 2 seqlen) reals with complex A -- or constant (dim, dstate) of A's dtype.
     x is (batch, dim, n_chunks, 2 dstate) of A's dtype. None of the inference extras of selective_scan_fwd.
-    seq_idx: selective_scan_varlen_fwd's (packed rows)."""
+    seq_idx: selective_scan_varlen_fwd's (packed rows); end_slots / ssm_state: selective_scan_varlen_states_fwd's, which checks them."""
     flags = _check_ssm_general(u, delta, A, B, C, D, z, delta_bias)
     if seq_idx is not None:
         _check_scan_seq_idx(seq_idx, u, flags, "selective_scan_varlen_fwd")
+    _check(end_slots is None or seq_idx is not None, "selective_scan_general_fwd: end_slots belong to packed rows (seq_idx)")
+    if end_slots is not None:
+        _gpu(end_slots, ssm_state)
     batch, dim, seqlen = u.shape
     dstate = A.shape[1]
     out = torch.empty_like(delta) if need_out else None
     x = torch.empty((batch, dim, (seqlen + 2047) // 2048, dstate * 2), device=u.device, dtype=A.dtype) if need_x else None
     out_z = torch.empty_like(z) if z is not None else None
-    if u.numel() > 0 and seq_idx is not None:
+    if u.numel() > 0 and end_slots is not None:
+        E = _lib.SsmVarlenStatesParams()
+        _fill_ssm_general(E.varlen.scan, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags)
+        E.varlen.seq_idx_ptr, E.varlen.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
+        E.num_slots, E.end_slots_ptr, E.end_slots_batch_stride = ssm_state.shape[0], _ptr(end_slots), end_slots.stride(0)
+        E.state_ptr, E.state_f32 = _ptr(ssm_state), int(ssm_state.dtype == torch.float32)
+        E.state_slot_stride, E.state_d_stride, E.state_dstate_stride = ssm_state.stride()
+        with torch.cuda.device(u.device):
+            _lib.check(_lib.load().dimsum_ssm_scan_varlen_states_fwd(E, _stream(u)), "selective_scan_varlen_states_fwd")
+    elif u.numel() > 0 and seq_idx is not None:
         V = _lib.SsmVarlenParams()
         _fill_ssm_general(V.scan, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags)
         V.seq_idx_ptr, V.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)

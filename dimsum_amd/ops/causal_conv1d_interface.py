@@ -49,35 +49,75 @@ class CausalConv1dVarlenFn(torch.autograd.Function):
         return dx, dweight, dbias if bias is not None else None, None, None
 
 
-def causal_conv1d_fn(x, weight, bias=None, activation=None, seq_idx=None):
+def _conv_varlen_states(x, weight, bias, activation, seq_idx, end_slots, conv_state):
+    """causal_conv1d_fn(seq_idx=, end_slots=, conv_state=): the kEmit kernels of csrc/causal_conv1d.hip, no graph"""
+    if activation not in (None, "silu", "swish"):
+        raise NotImplementedError("activation must be None, silu, or swish")
+    if end_slots is None or conv_state is None:
+        raise ValueError("causal_conv1d_fn: end_slots and conv_state go together (where to store, and the pool to store into)")
+    if seq_idx is None:
+        raise ValueError("causal_conv1d_fn: end_slots without seq_idx: per-segment states belong to packed rows (pass seq_idx; one segment is an "
+                         "all-equal id row)")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias, conv_state)):
+        raise NotImplementedError("causal_conv1d_fn: end_slots / conv_state are inference arguments -- the pass that stores states has no "
+                                  "backward; call it under torch.no_grad() or on inputs that do not require grad")
+    with torch.no_grad():
+        if x.stride(2) != 1:
+            x = x.contiguous()
+        return native.causal_conv1d_varlen_states_fwd(x, weight, bias.contiguous() if bias is not None else None, activation in ("silu", "swish"),
+                                                      seq_idx, end_slots, conv_state)
+
+
+def causal_conv1d_fn(x, weight, bias=None, activation=None, seq_idx=None, end_slots=None, conv_state=None):
     """x: (batch, dim, seqlen), weight: (dim, width), bias: (dim,), activation: None | "silu" | "swish".
     seq_idx (batch, seqlen) int32, contiguous: packed rows -- a tap that would reach across a change of the id is dropped (position t >= 1 is
-    a boundary iff seq_idx[b, t] != seq_idx[b, t - 1]; the values are only compared). None: the call it always was."""
+    a boundary iff seq_idx[b, t] != seq_idx[b, t - 1]; the values are only compared). None: the call it always was.
+    end_slots (batch, seqlen) int32, contiguous, with seq_idx and conv_state (num_slots, dim, width) of x's dtype: where end_slots[b, t] =
+    s >= 0 the conv state of the segment ending at t -- its last `width` inputs, zero-padded on the left, x[b, :, t] last -- is stored into
+    conv_state[s], IN PLACE; negative entries store nothing and unnamed slots are not touched. Entries must be < num_slots and none may
+    appear twice: neither is checked (it would take a device read). Inference arguments: no graph is recorded."""
+    if end_slots is not None or conv_state is not None:
+        return _conv_varlen_states(x, weight, bias, activation, seq_idx, end_slots, conv_state)
     if seq_idx is not None:
         return CausalConv1dVarlenFn.apply(x, weight, bias, activation, seq_idx)
     return CausalConv1dFn.apply(x, weight, bias, activation)
 
 
-def causal_conv1d_varlen_torch(x, weight, bias=None, activation=None, seq_idx=None):
+def causal_conv1d_varlen_torch(x, weight, bias=None, activation=None, seq_idx=None, end_slots=None, conv_state=None):
     """causal_conv1d_fn(seq_idx=...) written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer): a
     loop over the positions, tap j of position t counted iff t - j >= 0 and no boundary lies in (t - j, t]. Differentiable. What the tests
-    compare the kernels with and what CPU tests put in their place; never a fallback: nothing in the package calls it."""
+    compare the kernels with and what CPU tests put in their place; never a fallback: nothing in the package calls it.
+    end_slots / conv_state: causal_conv1d_fn's -- where end_slots[b, t] = s >= 0, conv_state[s, :, width - 1 - j] receives the masked tap j of
+    position t (a host read of end_slots: test infrastructure)."""
     silu = {None: False, "silu": True, "swish": True}.get(activation)
     if silu is None:
         raise NotImplementedError(f"causal_conv1d_varlen_torch: activation {activation!r} (None, 'silu' or 'swish')")
     batch, dim, seqlen = x.shape
     width = weight.shape[-1]
     assert weight.shape == (dim, width) and (seq_idx is None or tuple(seq_idx.shape) == (batch, seqlen))
+    assert (end_slots is None) == (conv_state is None) and (end_slots is None or seq_idx is not None)
+    ends = None
+    if end_slots is not None:
+        assert end_slots.dtype == torch.int32 and tuple(end_slots.shape) == (batch, seqlen) and tuple(conv_state.shape[1:]) == (dim, width)
+        ends = end_slots.tolist()
     zero = x.new_zeros(batch, dim)
     cols = []
     for t in range(seqlen):
         pre = x[:, :, t] * weight[:, width - 1]
         same = torch.ones(batch, dtype=torch.bool, device=x.device)               # no boundary in (t - j, t] so far
+        taps = [x[:, :, t]]                                                        # the masked taps j = 0 .. width - 1 of position t
         for j in range(1, min(width, t + 1)):
             if seq_idx is not None:
                 same = same & (seq_idx[:, t - j + 1] == seq_idx[:, t - j])
-            pre = pre + torch.where(same[:, None], x[:, :, t - j], zero) * weight[:, width - 1 - j]
+            taps.append(torch.where(same[:, None], x[:, :, t - j], zero))
+            pre = pre + taps[j] * weight[:, width - 1 - j]
         cols.append(pre if bias is None else pre + bias)
+        if ends is not None:
+            for b in range(batch):
+                if ends[b][t] >= 0:
+                    with torch.no_grad():
+                        for j in range(width):
+                            conv_state[ends[b][t], :, width - 1 - j] = (taps[j][b] if j < len(taps) else zero[b]).to(conv_state.dtype)
     pre = torch.stack(cols, dim=-1)
     return (pre * torch.sigmoid(pre) if silu else pre).to(x.dtype)
 

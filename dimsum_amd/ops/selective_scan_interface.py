@@ -129,13 +129,42 @@ def _refuse_varlen_scan(who, A, B, C):
                                   "instantiated for real A with input-dependent B and C")
 
 
-def selective_scan_varlen_torch(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False, seq_idx=None):
+def _selective_scan_varlen_states(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, seq_idx, end_slots, ssm_state):
+    """selective_scan_fn(seq_idx=, end_slots=, ssm_state=): the kEmit instantiations of csrc/ssm_scan_general.hip, no graph"""
+    if end_slots is None or ssm_state is None:
+        raise ValueError("selective_scan_fn: end_slots and ssm_state go together (where to store, and the pool to store into)")
+    if seq_idx is None:
+        raise ValueError("selective_scan_fn: end_slots without seq_idx: per-segment states belong to packed rows (pass seq_idx; one segment is an "
+                         "all-equal id row)")
+    _refuse_varlen_scan("selective_scan_fn", A, B, C)
+    if _will_backprop(u, delta, A, B, C, D, z, delta_bias, ssm_state):
+        raise NotImplementedError("selective_scan_fn: end_slots / ssm_state are inference arguments -- the scan that stores per-segment states "
+                                  "has no backward; call it under torch.no_grad() or on inputs that do not require grad")
+    with torch.no_grad():
+        u, delta, B, C, z = (_last_contig(t) for t in (u, delta, B, C, z))
+        B = B.unsqueeze(1) if B.dim() == 3 else B
+        C = C.unsqueeze(1) if C.dim() == 3 else C
+        out, x, *rest = native.selective_scan_varlen_states_fwd(u, delta, A, B, C, D.contiguous() if D is not None else None, z, delta_bias,
+                                                                delta_softplus, seq_idx, end_slots, ssm_state, need_x=return_last_state)
+    res = rest[0] if z is not None else out
+    return res if not return_last_state else (res, x[:, :, -1, 1::2])
+
+
+def selective_scan_varlen_torch(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False, seq_idx=None,
+                                end_slots=None, ssm_state=None):
     """selective_scan_fn(seq_idx=...) written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer): a
     loop over the positions, h_t = (1 - r_t) exp(dt_t A) h_{t-1} + dt_t B_t u_t with r_t = 1 where seq_idx changes; real A, B / C
     (batch, dstate, seqlen) or (batch, groups, dstate, seqlen). Differentiable. What the tests compare the kernels with and what CPU tests put
-    in their place; never a fallback: nothing in the package calls it."""
+    in their place; never a fallback: nothing in the package calls it.
+    end_slots / ssm_state: selective_scan_fn's -- where end_slots[b, t] = s >= 0, ssm_state[s] receives h_t of row b (a host read of
+    end_slots: test infrastructure)."""
     batch, dim, seqlen = u.shape
     N = A.shape[-1]
+    assert (end_slots is None) == (ssm_state is None) and (end_slots is None or seq_idx is not None)
+    ends = None
+    if end_slots is not None:
+        assert end_slots.dtype == torch.int32 and tuple(end_slots.shape) == (batch, seqlen) and tuple(ssm_state.shape[1:]) == (dim, N)
+        ends = end_slots.tolist()
     B4 = B.unsqueeze(1) if B.dim() == 3 else B
     C4 = C.unsqueeze(1) if C.dim() == 3 else C
     rep = dim // B4.shape[1]
@@ -151,6 +180,11 @@ def selective_scan_varlen_torch(u, delta, A, B, C, D=None, z=None, delta_bias=No
         Ct = C4[:, :, :, t].repeat_interleave(rep, dim=1)
         h = torch.exp(dt[:, :, t, None] * A[None]) * h + (dt[:, :, t] * u[:, :, t])[:, :, None] * Bt
         ys.append((h * Ct).sum(-1))
+        if ends is not None:
+            for b in range(batch):
+                if ends[b][t] >= 0:
+                    with torch.no_grad():
+                        ssm_state[ends[b][t]] = h[b].to(ssm_state.dtype)
     y = torch.stack(ys, dim=-1)
     if D is not None:
         y = y + D[None, :, None] * u
@@ -176,14 +210,23 @@ def _selective_scan_carry(u, delta, A, B, C, D, z, delta_bias, delta_softplus, r
 
 
 def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False, initial_state=None,
-                      seq_idx=None):
+                      seq_idx=None, end_slots=None, ssm_state=None):
     """out (or (out, last_state)); the gradient of last_state is not propagated (as in the reference).
     initial_state (batch, dim, dstate), float32 or of u's dtype (complex64 with complex A): the scan starts from it instead of from zeros --
     a cached sequence continued by seqlen tokens; last_state then comes back in its dtype. An inference argument: no graph is recorded, and
     inputs that require grad under grad mode are refused. Such a call runs on the general kernel whatever the dstate.
     seq_idx (batch, seqlen) int32, contiguous: packed rows -- position t >= 1 is a boundary iff seq_idx[b, t] != seq_idx[b, t - 1] (the values
     are only compared), and the state restarts there: every segment gets what it gets as a row of its own, last_state is the last
-    segment's. With autograd. Runs the packed-row general kernels whatever the dstate; real A and input-dependent B / C only."""
+    segment's. With autograd. Runs the packed-row general kernels whatever the dstate; real A and input-dependent B / C only.
+    end_slots (batch, seqlen) int32, contiguous, with seq_idx and ssm_state (num_slots, dim, dstate), float32 or of u's dtype: where
+    end_slots[b, t] = s >= 0 the state after position t is stored into ssm_state[s], IN PLACE; negative entries store nothing and unnamed
+    slots are not touched. Entries must be < num_slots and none may appear twice: neither is checked (it would take a device read).
+    Inference arguments: no graph is recorded."""
+    if end_slots is not None or ssm_state is not None:
+        if initial_state is not None:
+            raise NotImplementedError("selective_scan_fn: end_slots together with a carried initial_state is not built: a packed row starts "
+                                      "from zero state")
+        return _selective_scan_varlen_states(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, seq_idx, end_slots, ssm_state)
     if seq_idx is not None:
         if initial_state is not None:
             raise NotImplementedError("selective_scan_fn: seq_idx together with a carried initial_state is not built: a packed row starts from "
@@ -507,10 +550,17 @@ class _MambaInner(torch.autograd.Function):
 
 
 def _mamba_inner_varlen(has_out_proj, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D,
-                        delta_bias, B_proj_bias, C_proj_bias, delta_softplus, seq_idx, last_state=None):
+                        delta_bias, B_proj_bias, C_proj_bias, delta_softplus, seq_idx, last_state=None, end_slots=None, conv_state=None, ssm_state=None):
     """mamba_inner_fn(seq_idx=...): the general route's plain sequence on packed rows, conv -> x_proj / dt_proj -> scan -> out_proj, each piece
     under its own autograd node (causal_conv1d_fn and selective_scan_fn with seq_idx; the projections are GEMMs): no dt_proj in the scan, no
-    operand images, no f16s training, no saved-state extras. last_state receives the state of every row's last segment."""
+    operand images, no f16s training, no saved-state extras. last_state receives the state of every row's last segment.
+    end_slots with the pools conv_state and ssm_state (inference): the conv and the scan store every segment's states into its slot
+    themselves (causal_conv1d_fn / selective_scan_fn); last_state is then not taken."""
+    emit = end_slots is not None or conv_state is not None or ssm_state is not None
+    if emit and (end_slots is None or conv_state is None or ssm_state is None):
+        raise ValueError("mamba_inner_fn_cond: end_slots, conv_state and ssm_state go together")
+    if emit and last_state is not None:
+        raise ValueError("mamba_inner_fn_cond: last_state together with end_slots: the per-segment states go to the pools, there is no row state to return")
     if A.is_complex():
         raise NotImplementedError("mamba_inner_fn: complex A is outside this build's scope")
     if B is not None or C is not None:
@@ -519,14 +569,15 @@ def _mamba_inner_varlen(has_out_proj, xz, conv1d_weight, conv1d_bias, x_proj_wei
         xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight if has_out_proj else None, out_proj_bias if has_out_proj else None)
     bsz, d_inner, L = x.shape
     N, R = A.shape[-1], delta_proj_weight.shape[1]
-    conv_out = causal_conv1d_fn(x, conv_w, conv_b, "silu", seq_idx)
+    conv_out = causal_conv1d_fn(x, conv_w, conv_b, "silu", seq_idx, **({"end_slots": end_slots, "conv_state": conv_state} if emit else {}))
     x_dbl = F.linear(conv_out.transpose(1, 2).reshape(bsz * L, d_inner), x_proj_weight)            # (b l, R + 2N)
     delta = _delta(delta_proj_weight, x_dbl[:, :R].t(), bsz, L)
     Bm = x_dbl[:, R:R + N] if B_proj_bias is None else x_dbl[:, R:R + N] + B_proj_bias.to(x_dbl.dtype)
     Cm = x_dbl[:, -N:] if C_proj_bias is None else x_dbl[:, -N:] + C_proj_bias.to(x_dbl.dtype)
     Bm = Bm.reshape(bsz, L, N).permute(0, 2, 1).unsqueeze(1).contiguous()                           # (b, 1, N, l)
     Cm = Cm.reshape(bsz, L, N).permute(0, 2, 1).unsqueeze(1).contiguous()
-    out_z = selective_scan_fn(conv_out, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, return_last_state=last_state is not None, seq_idx=seq_idx)
+    out_z = selective_scan_fn(conv_out, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, return_last_state=last_state is not None, seq_idx=seq_idx,
+                              **({"end_slots": end_slots, "ssm_state": ssm_state} if emit else {}))
     if last_state is not None:
         out_z, last = out_z
         with torch.no_grad():
@@ -537,7 +588,7 @@ def _mamba_inner_varlen(has_out_proj, xz, conv1d_weight, conv1d_bias, x_proj_wei
     return gemm.linear(oz_t, out_proj_weight) if out_proj_bias is None else F.linear(oz_t, out_proj_weight, out_proj_bias)
 
 
-def _mamba_inner(has_out_proj, xz, *a, init_states=None, conv_done=False, last_state=None, seq_idx=None):
+def _mamba_inner(has_out_proj, xz, *a, init_states=None, conv_done=False, last_state=None, seq_idx=None, **emit):
     """a: conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias, B_proj_bias, C_proj_bias,
     delta_softplus -- _MambaInner.apply's order"""
     if seq_idx is not None:
@@ -546,7 +597,9 @@ def _mamba_inner(has_out_proj, xz, *a, init_states=None, conv_done=False, last_s
                                       "xz cannot already hold the packed-row conv")
         if init_states is not None:
             raise NotImplementedError("mamba_inner_fn_cond: init_states with seq_idx is not built: the conditional entry has no packed-row form")
-        return _mamba_inner_varlen(has_out_proj, xz, *a, seq_idx, last_state=last_state)
+        return _mamba_inner_varlen(has_out_proj, xz, *a, seq_idx, last_state=last_state, **emit)
+    if emit:
+        raise ValueError("mamba_inner_fn_cond: end_slots without seq_idx: per-segment states belong to packed rows")
     wb = _will_backprop(xz, *a[:-1], init_states)
     return _MambaInner.apply(xz, *a, init_states, has_out_proj, _checkpoint_lvl(), wb, conv_done, _f16s_train(xz, a[4], wb), last_state)
 
@@ -559,11 +612,15 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
 
 def mamba_inner_fn_cond(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                         A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None,
-                        delta_softplus=True, init_states=None, conv_done=False, last_state=None, seq_idx=None):
-    """seq_idx: the packed-row route of mamba_inner_fn (last_state is honoured); init_states or conv_done with it raise NotImplementedError"""
+                        delta_softplus=True, init_states=None, conv_done=False, last_state=None, seq_idx=None, end_slots=None, conv_state=None,
+                        ssm_state=None):
+    """seq_idx: the packed-row route of mamba_inner_fn (last_state is honoured); init_states or conv_done with it raise NotImplementedError.
+    end_slots (batch, seqlen) int32 with the pools conv_state (num_slots, d_inner, d_conv) and ssm_state (num_slots, d_inner, d_state), and
+    seq_idx: the packed PROMPT pass -- every segment's states are stored into its slot by the conv and scan kernels (inference only)"""
+    emit = {k: v for k, v in (("end_slots", end_slots), ("conv_state", conv_state), ("ssm_state", ssm_state)) if v is not None}
     return _mamba_inner(True, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias,
                         B_proj_bias, C_proj_bias, delta_softplus, init_states=init_states, conv_done=conv_done, last_state=last_state,
-                        **({"seq_idx": seq_idx} if seq_idx is not None else {}))
+                        **({"seq_idx": seq_idx} if seq_idx is not None else {}), **emit)
 
 
 def mamba_inner_fn_no_out_proj(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, B=None, C=None,

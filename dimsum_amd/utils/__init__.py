@@ -13,12 +13,17 @@ class InferenceParams:
     state_indices (no reference counterpart; upstream Mamba's state_batch_indices): None, or an int32 (batch,) device tensor that makes the
     cached states a POOL (num_slots, ...) -- row b of a decode step (seqlen_offset > 0) works on slot state_indices[b], a negative entry is
     a padding row. A prompt (seqlen_offset == 0) takes no indices: it is prefilled into slot s through a view pool[s:s+1]. `reset` leaves it
-    alone (the tensor is a static buffer of whoever schedules the batch: dimsum_amd.utils.serving.DecodeEngine)."""
+    alone (the tensor is a static buffer of whoever schedules the batch: dimsum_amd.utils.serving.DecodeEngine).
+    prefill_slots (no reference counterpart): None, or an int32 (batch, seqlen) device tensor for a PACKED prompt pass (seqlen_offset == 0
+    with seq_idx): the cached states are the pools, and where prefill_slots[b, t] = s >= 0 the conv and SSM states after position t of row b
+    are stored into slot s by the conv and scan kernels themselves; negative entries store nothing (plan_packed_prefill builds it). The
+    non-negative entries must be < num_slots and pairwise different: not checked (it would take a device read). `reset` leaves it alone."""
     max_seqlen: int
     max_batch_size: int
     seqlen_offset: int = 0
     key_value_memory_dict: dict = dataclasses.field(default_factory=dict)
     state_indices: Optional[torch.Tensor] = None
+    prefill_slots: Optional[torch.Tensor] = None
 
     def reset(self, max_seqlen, max_batch_size):
         self.max_seqlen, self.max_batch_size, self.seqlen_offset = max_seqlen, max_batch_size, 0
@@ -34,6 +39,9 @@ def chunked_prefill(mixer, hidden_states, inference_params, chunk, *cond):
     if getattr(inference_params, "state_indices", None) is not None:
         raise NotImplementedError("chunked_prefill with state_indices is not built: `extend` works on a batch's own states; prefill a slot of "
                                   "a pool through a view, pool[s:s+1], with state_indices=None")
+    if getattr(inference_params, "prefill_slots", None) is not None:
+        raise NotImplementedError("chunked_prefill with prefill_slots is not built: `extend` continues a batch's own states and takes no "
+                                  "sequence ids; a packed prompt is one pass (forward(seq_idx=..., inference_params=...))")
     L = hidden_states.shape[1]
     outs = [mixer(hidden_states[:, :chunk], *cond, inference_params=inference_params)]
     states = inference_params.key_value_memory_dict[mixer.layer_idx]
@@ -57,6 +65,42 @@ def seq_idx_from_lengths(lengths, seqlen=None, device=None):
     if total < seqlen:
         lengths = lengths + [seqlen - total]
     return torch.repeat_interleave(torch.arange(len(lengths), dtype=torch.int32), torch.tensor(lengths, dtype=torch.long)).to(device)
+
+
+def plan_packed_prefill(lengths, slots, rows=1, pad_multiple=1):
+    """the layout of one packed prompt pass over several new requests, on the host (nothing is read from a device): segment i has
+    lengths[i] >= 1 tokens and its states go to slot slots[i]. The segments are placed in order, each onto the currently shortest of `rows`
+    rows (the lowest such row on a tie); the rows are then padded to one length, a multiple of pad_multiple, and a row's padding is a segment
+    of its own that stores nothing.
+    -> dict(seq_idx (rows, seqlen) int32, end_slots (rows, seqlen) int32: slots[i] at segment i's last position and -1 everywhere else,
+            segments [(row, start)] per segment, logits_positions (n,) int64: row * seqlen + start + length - 1 per segment, seqlen)
+    CPU tensors; rows that got no segment are all padding. What MambaLMHeadModel.forward(seq_idx=, logits_positions=) and
+    InferenceParams.prefill_slots take."""
+    lengths, slots = [int(n) for n in lengths], [int(s) for s in slots]
+    rows, pad_multiple = int(rows), int(pad_multiple)
+    if len(lengths) != len(slots) or not lengths:
+        raise ValueError(f"plan_packed_prefill: one slot per segment and at least one segment, got {len(lengths)} lengths and {len(slots)} slots")
+    if min(lengths) < 1 or min(slots) < 0 or len(set(slots)) != len(slots):
+        raise ValueError(f"plan_packed_prefill: lengths must be >= 1 and slots non-negative and pairwise different, got {lengths} and {slots}")
+    if rows < 1 or pad_multiple < 1:
+        raise ValueError(f"plan_packed_prefill: rows and pad_multiple must be >= 1, got {rows} and {pad_multiple}")
+    fill, segments = [0] * rows, []
+    for n in lengths:
+        r = min(range(rows), key=lambda i: (fill[i], i))
+        segments.append((r, fill[r]))
+        fill[r] += n
+    seqlen = -(-max(fill) // pad_multiple) * pad_multiple
+    seq_idx = torch.zeros(rows, seqlen, dtype=torch.int32)
+    end_slots = torch.full((rows, seqlen), -1, dtype=torch.int32)
+    count = [0] * rows
+    for (r, start), n, s in zip(segments, lengths, slots):
+        seq_idx[r, start:start + n] = count[r]
+        end_slots[r, start + n - 1] = s
+        count[r] += 1
+    for r in range(rows):
+        seq_idx[r, fill[r]:] = count[r]          # the padding: a segment of its own
+    pos = torch.tensor([r * seqlen + start + n - 1 for (r, start), n in zip(segments, lengths)], dtype=torch.int64)
+    return {"seq_idx": seq_idx, "end_slots": end_slots, "segments": segments, "logits_positions": pos, "seqlen": seqlen}
 
 
 def packed_labels(input_ids, seq_idx, ignore_index=-100):

@@ -21,19 +21,28 @@ Host reads: exactly one per step -- the batch's tokens after the decode step (th
 of the rows admitted in this step, ONE small device-to-host copy), which the host needs to see eos_token_id and to report the tokens. It is
 the engine's only host read: an admission reads nothing, and the slots are never read back.
 
-Documented limits: prefill stalls the batch; new requests are not prefilled together in one packed launch (that needs per-document final states
-out of the packed-row scan); max_batch above 16 runs the unfused step (with slots); no prefix or state sharing between requests; no preemption.
+Packed prefill (`packed_prefill=True`, or DIMSUM_PACKED_PREFILL=1; off by default): an admission takes EVERY queued request that fits -- a row
+and a slot free, and the prompt tokens within `max_prefill_tokens` if given (one request always fits) -- packs the prompts into
+`prefill_rows` rows (utils.plan_packed_prefill) and runs ONE model pass with seq_idx and InferenceParams.prefill_slots on the pool itself:
+the conv and scan kernels store every request's states into its slot (csrc/causal_conv1d.hip, csrc/ssm_scan_general.hip; DESIGN.md section
+3.20). The head runs on the requests' last tokens only (logits_positions), ONE sampler launch draws all first tokens, and device index ops
+scatter them and the slots into the step's buffers. An admission still reads nothing back. The packed pass runs the general scan kernels
+whatever the d_state, so a request's first logits agree with its alone prefill to rounding, not bit for bit.
+
+Documented limits: prefill stalls the batch; a packed admission starts every slot from zero state (no chunked prefill into slots, no
+continuation of a slot); max_batch above 16 runs the unfused step (with slots); no prefix or state sharing between requests; no preemption.
 Sampling: `fused_sampling=True` draws token i of a request with uniforms[i] of THAT request (given to `submit`, or drawn there from the
 engine's generator) whichever row and step it lands on, so a request's output does not depend on its neighbours or on the schedule;
 `fused_sampling=False` runs generation.sample() per step on the batch's logits, whose multinomial draws (top_k != 1) come from one shared
 generator and do depend on the schedule."""
 import collections
 import dataclasses
+import os
 from typing import Optional
 
 import torch
 
-from . import InferenceParams
+from . import InferenceParams, plan_packed_prefill
 from .. import native
 from .generation import sample
 
@@ -53,7 +62,7 @@ class _Request:
 
 class DecodeEngine:
     """eng = DecodeEngine(model, max_batch, num_slots=None, max_seqlen=..., top_k=1, top_p=0.0, temperature=1.0, eos_token_id=None,
-                          vocab_size=None, cg=True, fused_sampling=True)
+                          vocab_size=None, cg=True, fused_sampling=True, packed_prefill=False, prefill_rows=1, max_prefill_tokens=None)
     rid = eng.submit(prompt_ids, max_new_tokens, uniforms=None)    1-D prompt; uniforms (max_new_tokens,) float32 pins the draws
     events = eng.step()                                            [(rid, token, finished)]: admissions' first tokens, then one decode step
     results = eng.run()                                            until idle -> {rid: LongTensor prompt + generated}
@@ -61,11 +70,12 @@ class DecodeEngine:
     num_slots (default max_batch) >= max_batch states per layer. max_seqlen: what allocate_inference_cache is told (Mamba states do not
     depend on it). vocab_size: the classes of a padded head, as in generate(). output_scores=True keeps every token's logits row
     (`scores(rid)`). generator: with fused sampling a CPU generator from which `submit` draws a request's uniforms on the host; without it
-    the device generator handed to sample(). Bookkeeping the tests read: `n_captures`, `free_slots`, `rows`, `slot_history` [(rid, slot)] in admission order.
+    the device generator handed to sample(). packed_prefill / prefill_rows / max_prefill_tokens: one packed prompt pass per admission (module
+    docstring; None = DIMSUM_PACKED_PREFILL=1). `n_prefill_passes` counts the model's prompt passes. Bookkeeping the tests read: `n_captures`, `free_slots`, `rows`, `slot_history` [(rid, slot)] in admission order.
     See the module docstring for the schedule, the host reads and the limits."""
 
     def __init__(self, model, max_batch, num_slots=None, *, max_seqlen, top_k=1, top_p=0.0, temperature=1.0, eos_token_id=None, vocab_size=None,
-                 cg=True, fused_sampling=True, output_scores=False, generator=None):
+                 cg=True, fused_sampling=True, output_scores=False, generator=None, packed_prefill=None, prefill_rows=1, max_prefill_tokens=None):
         num_slots = max_batch if num_slots is None else int(num_slots)
         if max_batch < 1 or num_slots < max_batch:
             raise ValueError(f"DecodeEngine: need max_batch >= 1 and num_slots >= max_batch, got {max_batch} and {num_slots}")
@@ -73,6 +83,12 @@ class DecodeEngine:
         self.top_k, self.top_p, self.temperature = int(top_k), float(top_p), float(temperature)
         self.eos_token_id, self.vocab_size = eos_token_id, vocab_size
         self.cg, self.fused_sampling, self.output_scores, self.generator = bool(cg), bool(fused_sampling), bool(output_scores), generator
+        self.packed_prefill = os.environ.get("DIMSUM_PACKED_PREFILL", "0") == "1" if packed_prefill is None else bool(packed_prefill)
+        self.prefill_rows = int(prefill_rows)
+        self.max_prefill_tokens = None if max_prefill_tokens is None else int(max_prefill_tokens)
+        if self.prefill_rows < 1 or (self.max_prefill_tokens is not None and self.max_prefill_tokens < 1):
+            raise ValueError(f"DecodeEngine: prefill_rows and max_prefill_tokens must be >= 1, got {prefill_rows} and {max_prefill_tokens}")
+        self.n_prefill_passes = 0
         param = next(iter(model.parameters()))
         self.device = param.device
         with torch.no_grad():
@@ -151,7 +167,45 @@ class DecodeEngine:
     def _done(self, r, token):
         return len(r.tokens) >= r.max_new_tokens or (self.eos_token_id is not None and token == self.eos_token_id)
 
+    def _admit_packed(self):
+        """every queued request that fits, in ONE packed prompt pass (module docstring)"""
+        batch, budget = [], self.max_prefill_tokens
+        free_rows = [row for row, rid in enumerate(self.rows) if rid is None]
+        while self.queue and len(batch) < min(len(self.free_slots), len(free_rows)):
+            r = self.requests[self.queue[0]]
+            if batch and budget is not None and sum(b.prompt.numel() for b in batch) + r.prompt.numel() > budget:
+                break
+            batch.append(self.requests[self.queue.popleft()])
+        if not batch:
+            return
+        slots, rows = [self.free_slots.pop(0) for _ in batch], free_rows[:len(batch)]
+        plan = plan_packed_prefill([r.prompt.numel() for r in batch], slots, rows=self.prefill_rows)
+        ids = torch.zeros((self.prefill_rows, plan["seqlen"]), dtype=torch.long)
+        dev = lambda t: t.to(self.device, non_blocking=True)
+        ids = dev(ids)
+        for r, (prow, start) in zip(batch, plan["segments"]):
+            ids[prow, start:start + r.prompt.numel()].copy_(r.prompt)
+        prefill = InferenceParams(max_seqlen=self.max_seqlen, max_batch_size=self.prefill_rows, key_value_memory_dict=self.pool,
+                                  prefill_slots=dev(plan["end_slots"]))
+        logits = self.model(ids, inference_params=prefill, seq_idx=dev(plan["seq_idx"]), logits_positions=dev(plan["logits_positions"])).logits
+        self.n_prefill_passes += 1
+        u = None if not self.fused_sampling else dev(torch.stack([r.uniforms[0] for r in batch]))
+        first = torch.empty(len(batch), dtype=torch.long, device=self.device)
+        self._sample_into(logits, u, first)                                      # (S, V) -> (S,): stays on the device
+        row_idx = dev(torch.tensor(rows, dtype=torch.long))
+        self.first.index_copy_(0, row_idx, first)
+        self.input_ids.index_copy_(0, row_idx, first.view(-1, 1))
+        self.slots.index_copy_(0, row_idx, dev(torch.tensor(slots, dtype=torch.int32)))
+        for i, (r, slot, row) in enumerate(zip(batch, slots, rows)):
+            self.slot_history.append((r.rid, slot))
+            if self.output_scores:
+                r.scores.append(self._view(logits)[i].clone())
+            r.slot, r.row, self.rows[row] = slot, row, r.rid
+            self._fresh.add(row)
+
     def _admit(self):
+        if self.packed_prefill:
+            return self._admit_packed()
         while self.queue and self.free_slots and None in self.rows:
             r = self.requests[self.queue.popleft()]
             slot, row = self.free_slots.pop(0), self.rows.index(None)
@@ -159,6 +213,7 @@ class DecodeEngine:
             views = {k: tuple(t[slot:slot + 1] for t in states) for k, states in self.pool.items()}
             prefill = InferenceParams(max_seqlen=self.max_seqlen, max_batch_size=1, key_value_memory_dict=views)
             logits = self.model(r.prompt.unsqueeze(0), inference_params=prefill, num_last_tokens=1).logits[:, -1]
+            self.n_prefill_passes += 1
             if self.output_scores:
                 r.scores.append(self._view(logits)[0].clone())
             first = self.first[row:row + 1]

@@ -367,6 +367,29 @@ typedef struct {
 int dimsum_ssm_scan_varlen_fwd(const dimsum_ssm_varlen_params_t *p, void *stream);
 int dimsum_ssm_scan_varlen_bwd(const dimsum_ssm_varlen_bwd_params_t *p, void *stream);
 
+/* dimsum_ssm_scan_varlen_fwd that also leaves PER-SEGMENT states in a pool (forward only; see dimsum_conv_varlen_states_params_t for
+ * end_slots and the caller's contract): where end_slots[b, t] = s >= 0 the state h_t -- the value step t + 1 would read -- is stored to
+ * state[s, d, n] for every channel d and state n < dstate, by the one lane that holds it. `state` is (num_slots, dim, dstate) with three
+ * free ELEMENT strides, float32 (state_f32 != 0) or of scan.dtype (rounded once, on the store, as hT of dimsum_ssm_scan_carry_fwd).
+ * out, out_z, x and the last chunk's state are exactly what dimsum_ssm_scan_varlen_fwd gives on the same inputs.
+ * Checks, in this order: NULL struct / struct_size (DIMSUM_ERR_ABI, before anything else is read) / num_slots < 1 (DIMSUM_ERR_SHAPE) /
+ * end_slots_ptr or state_ptr NULL (DIMSUM_ERR_NULL) / a negative end_slots_batch_stride or one below seqlen with batch > 1, or a negative
+ * state stride (DIMSUM_ERR_STRIDE) / dimsum_ssm_scan_varlen_fwd's checks on the embedded struct in their order (its struct_size is ignored).
+ * Nothing is launched, allocated or synchronised before all of them pass. One launch. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_ssm_varlen_states_params_t) */
+    int32_t num_slots;        /* rows of the pool, >= 1 */
+    dimsum_ssm_varlen_params_t varlen;
+    const void *end_slots_ptr;        /* int32 (batch, seqlen), unit stride along seqlen */
+    int64_t end_slots_batch_stride;
+    void *state_ptr;
+    int64_t state_slot_stride, state_d_stride, state_dstate_stride;
+    int32_t state_f32;        /* != 0: the pool is float32; 0: of scan.dtype */
+    int32_t reserved;         /* 0 */
+} dimsum_ssm_varlen_states_params_t;
+
+int dimsum_ssm_scan_varlen_states_fwd(const dimsum_ssm_varlen_states_params_t *p, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Training-step tail: global gradient-norm clip + AdamW + parameter EMA over a list of fp32 tensors, two launches
  * (<- torch.nn.utils.clip_grad_norm_, torch.optim.AdamW.step and update_ema of dimsum/train.py:55-64,317-321).
@@ -650,6 +673,35 @@ typedef struct {
 
 int dimsum_causal_conv1d_varlen_fwd(const dimsum_conv_varlen_params_t *p, void *stream);
 int dimsum_causal_conv1d_varlen_bwd(const dimsum_conv_varlen_bwd_params_t *p, void *stream);
+
+/* dimsum_causal_conv1d_varlen_fwd that also leaves PER-SEGMENT conv states in a pool (forward only): one packed prompt pass over several
+ * requests writes every request's state into that request's slot (the pool of the *_slots decode entries below).
+ *   end_slots : (batch, seqlen) int32, unit stride along seqlen, rows end_slots_batch_stride ELEMENTS apart; it rides next to seq_idx.
+ *       end_slots[b, t] = s >= 0: the state after position t of row b is stored into slot s. A negative entry stores nothing (padding, and
+ *       every position that is not a segment's last). The contract does not depend on where the boundaries lie.
+ *   state : (num_slots, dim, width) of conv.dtype (state_dtype, else DIMSUM_ERR_UNSUPPORTED), three free ELEMENT strides.
+ *       state[s, d, width - 1 - j] = x[b, d, t - j] for the taps j < width with t - j >= 0 and no boundary in (t - j, t], else 0: the
+ *       window dimsum_causal_conv1d_update shifts, zero-padded on the left for a segment shorter than width. The x elements are moved,
+ *       not converted. out is exactly dimsum_causal_conv1d_varlen_fwd's.
+ * THE CALLER'S CONTRACT (the one of the slot-indexed decode entries; not checkable without a device read, so not checked): every
+ * non-negative entry is < num_slots, and no non-negative value appears twice in one launch. Both are undefined behaviour otherwise.
+ * Checks, in this order: NULL struct / struct_size (DIMSUM_ERR_ABI, before anything else is read) / num_slots < 1 (DIMSUM_ERR_SHAPE) /
+ * end_slots_ptr or state_ptr NULL (DIMSUM_ERR_NULL) / a negative end_slots_batch_stride or one below seqlen with batch > 1, or a negative
+ * state stride (DIMSUM_ERR_STRIDE) / dimsum_causal_conv1d_varlen_fwd's checks on the embedded struct in their order (its struct_size is
+ * ignored) / state_dtype != conv.dtype (DIMSUM_ERR_UNSUPPORTED). Nothing is launched, allocated or synchronised before all of them pass. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_conv_varlen_states_params_t) */
+    int32_t num_slots;        /* rows of the pool, >= 1 */
+    dimsum_conv_varlen_params_t varlen;
+    const void *end_slots_ptr;
+    int64_t end_slots_batch_stride;
+    void *state_ptr;
+    int64_t state_slot_stride, state_c_stride, state_w_stride;
+    int32_t state_dtype;      /* dimsum_dtype_t of the pool: must equal conv.dtype */
+    int32_t reserved;         /* 0 */
+} dimsum_conv_varlen_states_params_t;
+
+int dimsum_causal_conv1d_varlen_states_fwd(const dimsum_conv_varlen_states_params_t *p, void *stream);
 
 /* The same conv on CHANNEL-LAST operands (causal_conv1d_channellast_fwd_kernel / _bwd_kernel, causal-conv1d/csrc/
  * causal_conv1d_fwd.cu:193-319, causal_conv1d_bwd.cu:306-494; host checks causal_conv1d.cpp:242-247, 376-379, 395-396):

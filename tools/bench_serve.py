@@ -19,7 +19,12 @@ with state_indices = a permutation of 0..B-1 -- `--steps` replays each between t
 with DIMSUM_FUSED_DECODE=1 and =0. The un-indexed kernels are the parent commit's instruction for instruction, so the
 first of the two is the parent's step.
 
-    python tools/bench_serve.py [--batches 4 16] [--rounds 5] [--requests 64] [--dtype float32] [--out serve_bench.json]
+--packed-prefill off (default): the engine admits every prompt alone, as above. on: the engine of (a) runs DecodeEngine(packed_prefill=True).
+both: instead of the two comparisons above, the engine with packed admission against the same engine with alone admission on the same
+workload (alternating round by round after a warm-up round of each; median and max / min spread of `--rounds`), then an admission-only
+timing: k = 1, 4, 16 prompts of 64 tokens admitted into an idle engine of max_batch 16, packed against alone, between two synchronisations.
+
+    python tools/bench_serve.py [--batches 4 16] [--rounds 5] [--requests 64] [--dtype float32] [--packed-prefill off|on|both] [--out serve_bench.json]
 prints one JSON line per measurement and two markdown tables at the end."""
 import argparse
 import json
@@ -78,13 +83,74 @@ def run_static(model, batches):
     return time.perf_counter() - t0
 
 
-def serve_bench(model, requests, B, rounds):
+def packed_bench(model, requests, B, rounds):
+    """the engine with packed admission against the same engine with alone admission (the default), alternating round by round"""
+    from dimsum_amd.utils.serving import DecodeEngine
+    useful = sum(n for _, n in requests)
+    kw = dict(max_batch=B, num_slots=B, max_seqlen=PROMPT_RANGE[1] + NEW_RANGE[1], vocab_size=SHAPE["vocab_size"], cg=True)
+    engines = {"alone": DecodeEngine(model, packed_prefill=False, **kw), "packed": DecodeEngine(model, packed_prefill=True, **kw)}
+    for eng in engines.values():
+        run_engine(eng, requests)                            # warm-up round of each (the capture)
+    times = {k: [] for k in engines}
+    for _ in range(rounds):
+        for k, eng in engines.items():
+            times[k].append(run_engine(eng, requests))
+    row = dict(batch=B, requests=len(requests), useful_tokens=useful, rounds=rounds,
+               prompt_passes={k: eng.n_prefill_passes // (rounds + 1) for k, eng in engines.items()})
+    for k, v in times.items():
+        row[f"{k}_tokens_per_s"] = round(useful / statistics.median(v), 1)
+        row[f"spread_{k}"] = round(max(v) / min(v), 3)
+    row["packed_over_alone"] = round(row["packed_tokens_per_s"] / row["alone_tokens_per_s"], 3)
+    return row
+
+
+def admission_bench(model, k, rounds, prompt_len=64, B=16):
+    """the time of admitting k prompts of prompt_len tokens into an idle engine (prompt passes, first-token sampling, the scatter into the
+    step's buffers; no decode step), packed against alone"""
+    from dimsum_amd.utils.serving import DecodeEngine
+    g = torch.Generator().manual_seed(k)
+    prompts = [torch.randint(0, SHAPE["vocab_size"], (prompt_len,), generator=g) for _ in range(k)]
+    kw = dict(max_batch=B, num_slots=B, max_seqlen=PROMPT_RANGE[1] + NEW_RANGE[1], vocab_size=SHAPE["vocab_size"], cg=True)
+    engines = {"alone": DecodeEngine(model, packed_prefill=False, **kw), "packed": DecodeEngine(model, packed_prefill=True, **kw)}
+
+    def timed(eng):
+        for p in prompts:
+            eng.submit(p, 1)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            eng._admit()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        for row, rid in enumerate(eng.rows):                 # back to idle without a decode step: the slots are free again
+            if rid is not None:
+                eng._retire(row, eng.requests[rid])
+        eng._fresh.clear()
+        eng.requests.clear()
+        return dt * 1e3
+
+    for eng in engines.values():
+        timed(eng)
+    times = {n: [] for n in engines}
+    for _ in range(rounds):
+        for n, eng in engines.items():
+            times[n].append(timed(eng))
+    row = dict(prompts=k, prompt_len=prompt_len, rounds=rounds)
+    for n, v in times.items():
+        row[f"{n}_ms"] = round(statistics.median(v), 3)
+        row[f"spread_{n}"] = round(max(v) / min(v), 3)
+    row["alone_over_packed"] = round(row["alone_ms"] / row["packed_ms"], 3)
+    return row
+
+
+def serve_bench(model, requests, B, rounds, packed=False):
     from dimsum_amd.utils.serving import DecodeEngine
     useful = sum(n for _, n in requests)
     batches = [(ids.cuda(), seq.cuda(), m) for ids, seq, m in static_batches(requests, B)]
     decoded = sum(ids.shape[0] * (m - ids.shape[1]) for ids, _, m in batches)
     model._decoding_cache = None
-    eng = DecodeEngine(model, max_batch=B, num_slots=B, max_seqlen=PROMPT_RANGE[1] + NEW_RANGE[1], vocab_size=SHAPE["vocab_size"], cg=True)
+    eng = DecodeEngine(model, max_batch=B, num_slots=B, max_seqlen=PROMPT_RANGE[1] + NEW_RANGE[1], vocab_size=SHAPE["vocab_size"], cg=True,
+                       packed_prefill=packed)
     # the static side's cache at its final size before anything is timed: the longest batch first, so no later batch re-captures
     longest = max(batches, key=lambda b: b[2])
     model.generate(longest[0], max_length=longest[2], cg=True, fused_sampling=True, vocab_size=SHAPE["vocab_size"], seq_idx=longest[1])
@@ -161,6 +227,7 @@ def main():
     ap.add_argument("--steps", type=int, default=512, help="replays per timed window of the step comparison")
     ap.add_argument("--dtype", default="float32")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--packed-prefill", choices=["off", "on", "both"], default="off")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_serve needs the GPU"
@@ -169,9 +236,25 @@ def main():
     torch.manual_seed(0)
     model = MambaLMHeadModel(**SHAPE, device="cuda", dtype=getattr(torch, args.dtype)).eval()
     requests = workload(args.requests, args.seed)
+    if args.packed_prefill == "both":
+        packed = [dict(packed_bench(model, requests, B, args.rounds), dtype=args.dtype, fused_decode=policy or "unset") for B in args.batches]
+        admit = [dict(admission_bench(model, k, args.rounds), dtype=args.dtype) for k in (1, 4, 16)]
+        for row in packed + admit:
+            print(json.dumps(row), flush=True)
+        print("\n| B | useful tokens | alone tok/s (spread) | packed tok/s (spread) | packed / alone | prompt passes alone / packed |\n|---|---|---|---|---|---|")
+        for r in packed:
+            print(f"| {r['batch']} | {r['useful_tokens']} | {r['alone_tokens_per_s']:.0f} ({r['spread_alone']:.3f}) | {r['packed_tokens_per_s']:.0f} "
+                  f"({r['spread_packed']:.3f}) | {r['packed_over_alone']:.3f} | {r['prompt_passes']['alone']} / {r['prompt_passes']['packed']} |")
+        print("\n| prompts x 64 tokens | alone ms (spread) | packed ms (spread) | alone / packed |\n|---|---|---|---|")
+        for r in admit:
+            print(f"| {r['prompts']} | {r['alone_ms']:.2f} ({r['spread_alone']:.3f}) | {r['packed_ms']:.2f} ({r['spread_packed']:.3f}) | {r['alone_over_packed']:.2f} |")
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(dict(packed=packed, admission=admit), f, indent=1)
+        return
     serve, steps = [], []
     for B in args.batches:
-        row = dict(serve_bench(model, requests, B, args.rounds), dtype=args.dtype, fused_decode=policy or "unset")
+        row = dict(serve_bench(model, requests, B, args.rounds, packed=args.packed_prefill == "on"), dtype=args.dtype, fused_decode=policy or "unset")
         serve.append(row)
         print(json.dumps(row), flush=True)
     for B in args.batches:
