@@ -113,13 +113,13 @@ struct conv_states_args_t {
     void *pool;
     int64_t pool_slot_stride, pool_c_stride, pool_w_stride;
 };
-__device__ __forceinline__ const dimsum_conv_params_t &conv_base(const conv_states_args_t &a) { return a.v.p; }
+__host__ __device__ __forceinline__ const dimsum_conv_params_t &conv_base(const conv_states_args_t &a) { return a.v.p; }
 __device__ __forceinline__ const conv_varlen_args_t &conv_ids(const conv_varlen_args_t &a) { return a; }
 __device__ __forceinline__ const conv_varlen_args_t &conv_ids(const conv_states_args_t &a) { return a.v; }
-__device__ __forceinline__ const dimsum_conv_params_t &conv_base(const dimsum_conv_params_t &a) { return a; }
-__device__ __forceinline__ const dimsum_conv_params_t &conv_base(const conv_varlen_args_t &a) { return a.p; }
-__device__ __forceinline__ const dimsum_conv_bwd_params_t &conv_base(const dimsum_conv_bwd_params_t &a) { return a; }
-__device__ __forceinline__ const dimsum_conv_bwd_params_t &conv_base(const conv_varlen_bwd_args_t &a) { return a.q; }
+__host__ __device__ __forceinline__ const dimsum_conv_params_t &conv_base(const dimsum_conv_params_t &a) { return a; }
+__host__ __device__ __forceinline__ const dimsum_conv_params_t &conv_base(const conv_varlen_args_t &a) { return a.p; }
+__host__ __device__ __forceinline__ const dimsum_conv_bwd_params_t &conv_base(const dimsum_conv_bwd_params_t &a) { return a; }
+__host__ __device__ __forceinline__ const dimsum_conv_bwd_params_t &conv_base(const conv_varlen_bwd_args_t &a) { return a.q; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 template <typename T, bool kVec, bool kVarlen, bool kEmit = false>
@@ -415,55 +415,55 @@ __global__ __launch_bounds__(256) void causal_conv1d_bwd_kernel(const std::condi
     }
 }
 
-static int conv_check(const dimsum_conv_params_t &p) {
-    if (!p.x_ptr || !p.weight_ptr) return DIMSUM_ERR_NULL;
-    if (p.width < 2 || p.width > 4) return DIMSUM_ERR_SHAPE;   // causal_conv1d.cpp:248
-    if (p.batch < 0 || p.dim <= 0 || p.seqlen <= 0) return DIMSUM_ERR_SHAPE;
-    if (p.dtype < DIMSUM_F32 || p.dtype > DIMSUM_BF16) return DIMSUM_ERR_DTYPE;
-    return DIMSUM_OK;
-}
+// ---------------------------------------------------------------------------------------------------------------------
+// host. One check (conv_checks), one launch per direction (launch_conv_fwd / _bwd pick kVec), one dtype switch (dispatch_dtype). A new
+// variant is a template flag on the kernel, an argument struct behind conv_base, and an entry point that adds its own checks around these.
 template <typename T> static bool vec_ok(const void *ptr, int64_t s0, int64_t s1, int L) {
     return L % 4 == 0 && aligned_to<T>(ptr, 4 * sizeof(T)) && s0 % 4 == 0 && s1 % 4 == 0;
 }
-
 // the ids of a packed row are read as 16-byte vectors where x is: a 16-byte aligned base and a batch stride that keeps every row so
-static bool ids_vec_ok(const int32_t *seq_idx, int64_t batch_stride) { return aligned_to<int32_t>(seq_idx, 16) && batch_stride % 4 == 0; }
+static bool ids_vec_ok(const void *ids, int64_t batch_stride) { return aligned_to<int32_t>(ids, 16) && batch_stride % 4 == 0; }
+// a (batch, seqlen) int32 operand with unit stride along seqlen: its rows must not run backwards or overlap
+static bool ids_stride_bad(int64_t batch_stride, const dimsum_conv_params_t &p) { return batch_stride < 0 || (p.batch > 1 && batch_stride < p.seqlen); }
 
-// seq_idx == nullptr: the plain kernels, launched exactly as before
-// st != nullptr: the kEmit kernels (st->v is filled here)
-template <typename T> static int launch_conv_fwd(const dimsum_conv_params_t &p, hipStream_t s, const int32_t *seq_idx = nullptr, int64_t seq_batch_stride = 0,
-                                                 conv_states_args_t *st = nullptr) {
-    const bool vec = vec_ok<T>(p.x_ptr, p.x_batch_stride, p.x_c_stride, p.seqlen) &&
+// What the five seqlen-contiguous entry points share, after their own NULL / struct_size test, in this order: the pointers written to (out;
+// q != nullptr, a backward: dout, dx, dweight), the inputs, width and sizes (causal_conv1d.cpp:248), the dtype, then with `packed` the ids
+// (NULL, then a batch stride that lets rows overlap). DIMSUM_OK with batch == 0 is the caller's early return.
+static int conv_checks(const dimsum_conv_params_t &p, const dimsum_conv_bwd_params_t *q, bool packed = false, const void *seq_idx = nullptr,
+                       int64_t seq_batch_stride = 0) {
+    if (q ? !q->dout_ptr || !q->dx_ptr || !q->dweight_ptr : !p.out_ptr) return DIMSUM_ERR_NULL;
+    if (!p.x_ptr || !p.weight_ptr) return DIMSUM_ERR_NULL;
+    if (p.width < 2 || p.width > 4 || p.batch < 0 || p.dim <= 0 || p.seqlen <= 0) return DIMSUM_ERR_SHAPE;
+    if (p.dtype < DIMSUM_F32 || p.dtype > DIMSUM_BF16) return DIMSUM_ERR_DTYPE;
+    if (packed && !seq_idx) return DIMSUM_ERR_NULL;
+    if (packed && ids_stride_bad(seq_batch_stride, p)) return DIMSUM_ERR_STRIDE;
+    return DIMSUM_OK;
+}
+
+// Args: dimsum_conv_params_t, conv_varlen_args_t (kVarlen) or conv_states_args_t (kEmit). ids_vec: every int32 row operand of Args may be
+// read as 16-byte vectors
+template <typename T, bool kVarlen, bool kEmit, typename Args> static int launch_conv_fwd(const Args &a, hipStream_t s, bool ids_vec = true) {
+    const dimsum_conv_params_t &p = conv_base(a);
+    const bool vec = ids_vec && vec_ok<T>(p.x_ptr, p.x_batch_stride, p.x_c_stride, p.seqlen) &&
                      vec_ok<T>(p.out_ptr, p.out_batch_stride, p.out_c_stride, p.seqlen);
     const int64_t rows = (int64_t)p.batch * p.dim;
     const int grid = (int)((rows + 15) / 16 < 256 * 32 ? (rows + 15) / 16 : 256 * 32);   // 4 waves x 4 rows per workgroup and pass (a 2x larger grid measured slower)
-    if (st) {
-        st->v = {p, seq_idx, seq_batch_stride};
-        if (vec && ids_vec_ok(seq_idx, seq_batch_stride) && ids_vec_ok(st->end_slots, st->end_batch_stride))
-            hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true, true, true>), dim3(grid), dim3(256), 0, s, *st);
-        else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false, true, true>), dim3(grid), dim3(256), 0, s, *st);
-    } else if (seq_idx) {
-        const conv_varlen_args_t a = {p, seq_idx, seq_batch_stride};
-        if (vec && ids_vec_ok(seq_idx, seq_batch_stride)) hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true, true>), dim3(grid), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false, true>), dim3(grid), dim3(256), 0, s, a);
-    } else if (vec) hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true, false>), dim3(grid), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false, false>), dim3(grid), dim3(256), 0, s, p);
+    if (vec) hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true, kVarlen, kEmit>), dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false, kVarlen, kEmit>), dim3(grid), dim3(256), 0, s, a);
     return launch_status();
 }
-template <typename T> static int launch_conv_bwd(const dimsum_conv_bwd_params_t &q, hipStream_t s, const int32_t *seq_idx = nullptr, int64_t seq_batch_stride = 0) {
+// Args: dimsum_conv_bwd_params_t or conv_varlen_bwd_args_t (kVarlen)
+template <typename T, bool kVarlen, typename Args> static int launch_conv_bwd(const Args &a, hipStream_t s, bool ids_vec = true) {
+    const dimsum_conv_bwd_params_t &q = conv_base(a);
     const dimsum_conv_params_t &p = q.fwd;
-    const bool vec = vec_ok<T>(p.x_ptr, p.x_batch_stride, p.x_c_stride, p.seqlen) &&
+    const bool vec = ids_vec && vec_ok<T>(p.x_ptr, p.x_batch_stride, p.x_c_stride, p.seqlen) &&
                      vec_ok<T>(q.dout_ptr, q.dout_batch_stride, q.dout_c_stride, p.seqlen) &&
                      vec_ok<T>(q.dx_ptr, q.dx_batch_stride, q.dx_c_stride, p.seqlen);
     // enough waves to fill the chip while keeping >= 4 batch rows per wave when the batch allows it
     int split = 1;
     while ((int64_t)p.dim * split < 2048 && split * 4 < p.batch) split *= 2;
-    if (seq_idx) {
-        const conv_varlen_bwd_args_t a = {q, seq_idx, seq_batch_stride};
-        if (vec && ids_vec_ok(seq_idx, seq_batch_stride)) hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, true, true>), dim3(p.dim, split), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, false, true>), dim3(p.dim, split), dim3(256), 0, s, a);
-    } else if (vec) hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, true, false>), dim3(p.dim, split), dim3(256), 0, s, q);
-    else hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, false, false>), dim3(p.dim, split), dim3(256), 0, s, q);
+    if (vec) hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, true, kVarlen>), dim3(p.dim, split), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((causal_conv1d_bwd_kernel<T, false, kVarlen>), dim3(p.dim, split), dim3(256), 0, s, a);
     return launch_status();
 }
 
@@ -486,123 +486,72 @@ extern "C" int dimsum_causal_conv1d_chunk(const dimsum_conv_chunk_params_t *p, v
     if (!p->x_ptr || !p->weight_ptr || !p->conv_state_ptr || !p->out_ptr) return DIMSUM_ERR_NULL;
     if (p->width < 2 || p->width > 4 || p->batch < 1 || p->dim < 1 || p->seqlen < 1) return DIMSUM_ERR_SHAPE;
     if (p->dtype < DIMSUM_F32 || p->dtype > DIMSUM_BF16) return DIMSUM_ERR_DTYPE;
-    for (int64_t s : {p->x_batch_stride, p->x_c_stride, p->state_batch_stride, p->state_c_stride, p->state_w_stride, p->weight_c_stride,
-                      p->weight_width_stride, p->out_batch_stride, p->out_c_stride})
-        if (s < 0) return DIMSUM_ERR_STRIDE;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (p->dtype) {
-        case DIMSUM_F32: return launch_conv_chunk<float>(*p, s);
-        case DIMSUM_F16: return launch_conv_chunk<__half>(*p, s);
-        default: return launch_conv_chunk<__hip_bfloat16>(*p, s);
-    }
+    if (any_negative({p->x_batch_stride, p->x_c_stride, p->state_batch_stride, p->state_c_stride, p->state_w_stride, p->weight_c_stride,
+                      p->weight_width_stride, p->out_batch_stride, p->out_c_stride}))
+        return DIMSUM_ERR_STRIDE;
+    return dispatch_dtype(p->dtype, [&](auto t) { return launch_conv_chunk<decltype(t)>(*p, reinterpret_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int dimsum_causal_conv1d_fwd(const dimsum_conv_params_t *p, void *stream) {
     using namespace dimsum;
     if (!p) return DIMSUM_ERR_NULL;
     if (p->struct_size != sizeof(dimsum_conv_params_t)) return DIMSUM_ERR_ABI;
-    if (!p->out_ptr) return DIMSUM_ERR_NULL;
-    const int rc = conv_check(*p);
-    if (rc != DIMSUM_OK) return rc;
-    if (p->batch == 0) return DIMSUM_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (p->dtype) {
-        case DIMSUM_F32: return launch_conv_fwd<float>(*p, s);
-        case DIMSUM_F16: return launch_conv_fwd<__half>(*p, s);
-        default: return launch_conv_fwd<__hip_bfloat16>(*p, s);
-    }
+    const int rc = conv_checks(*p, nullptr);
+    if (rc != DIMSUM_OK || p->batch == 0) return rc;
+    return dispatch_dtype(p->dtype, [&](auto t) { return launch_conv_fwd<decltype(t), false, false>(*p, reinterpret_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int dimsum_causal_conv1d_bwd(const dimsum_conv_bwd_params_t *q, void *stream) {
     using namespace dimsum;
     if (!q) return DIMSUM_ERR_NULL;
     if (q->struct_size != sizeof(dimsum_conv_bwd_params_t)) return DIMSUM_ERR_ABI;
-    if (!q->dout_ptr || !q->dx_ptr || !q->dweight_ptr) return DIMSUM_ERR_NULL;
-    const int rc = conv_check(q->fwd);
-    if (rc != DIMSUM_OK) return rc;
-    if (q->fwd.batch == 0) return DIMSUM_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (q->fwd.dtype) {
-        case DIMSUM_F32: return launch_conv_bwd<float>(*q, s);
-        case DIMSUM_F16: return launch_conv_bwd<__half>(*q, s);
-        default: return launch_conv_bwd<__hip_bfloat16>(*q, s);
-    }
-}
-
-// packed rows: the checks of the plain entry points in their order, then the ids (NULL, then a batch stride that lets rows overlap)
-static int conv_varlen_ids_check(const void *seq_idx, int64_t batch_stride, int32_t batch, int32_t seqlen) {
-    if (!seq_idx) return DIMSUM_ERR_NULL;
-    if (batch_stride < 0 || (batch > 1 && batch_stride < seqlen)) return DIMSUM_ERR_STRIDE;
-    return DIMSUM_OK;
+    const int rc = conv_checks(q->fwd, q);
+    if (rc != DIMSUM_OK || q->fwd.batch == 0) return rc;
+    return dispatch_dtype(q->fwd.dtype, [&](auto t) { return launch_conv_bwd<decltype(t), false>(*q, reinterpret_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int dimsum_causal_conv1d_varlen_fwd(const dimsum_conv_varlen_params_t *v, void *stream) {
     using namespace dimsum;
     if (!v) return DIMSUM_ERR_NULL;
     if (v->struct_size != sizeof(dimsum_conv_varlen_params_t)) return DIMSUM_ERR_ABI;
-    const dimsum_conv_params_t *p = &v->conv;
-    if (!p->out_ptr) return DIMSUM_ERR_NULL;
-    int rc = conv_check(*p);
-    if (rc != DIMSUM_OK) return rc;
-    rc = conv_varlen_ids_check(v->seq_idx_ptr, v->seq_idx_batch_stride, p->batch, p->seqlen);
-    if (rc != DIMSUM_OK) return rc;
-    if (p->batch == 0) return DIMSUM_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int32_t *ids = reinterpret_cast<const int32_t *>(v->seq_idx_ptr);
-    switch (p->dtype) {
-        case DIMSUM_F32: return launch_conv_fwd<float>(*p, s, ids, v->seq_idx_batch_stride);
-        case DIMSUM_F16: return launch_conv_fwd<__half>(*p, s, ids, v->seq_idx_batch_stride);
-        default: return launch_conv_fwd<__hip_bfloat16>(*p, s, ids, v->seq_idx_batch_stride);
-    }
+    const int rc = conv_checks(v->conv, nullptr, true, v->seq_idx_ptr, v->seq_idx_batch_stride);
+    if (rc != DIMSUM_OK || v->conv.batch == 0) return rc;
+    const conv_varlen_args_t a = {v->conv, reinterpret_cast<const int32_t *>(v->seq_idx_ptr), v->seq_idx_batch_stride};
+    const bool ids_vec = ids_vec_ok(a.seq_idx, a.seq_batch_stride);
+    return dispatch_dtype(a.p.dtype, [&](auto t) { return launch_conv_fwd<decltype(t), true, false>(a, reinterpret_cast<hipStream_t>(stream), ids_vec); });
 }
 
 extern "C" int dimsum_causal_conv1d_varlen_bwd(const dimsum_conv_varlen_bwd_params_t *v, void *stream) {
     using namespace dimsum;
     if (!v) return DIMSUM_ERR_NULL;
     if (v->struct_size != sizeof(dimsum_conv_varlen_bwd_params_t)) return DIMSUM_ERR_ABI;
-    const dimsum_conv_bwd_params_t *q = &v->conv;
-    if (!q->dout_ptr || !q->dx_ptr || !q->dweight_ptr) return DIMSUM_ERR_NULL;
-    int rc = conv_check(q->fwd);
-    if (rc != DIMSUM_OK) return rc;
-    rc = conv_varlen_ids_check(v->seq_idx_ptr, v->seq_idx_batch_stride, q->fwd.batch, q->fwd.seqlen);
-    if (rc != DIMSUM_OK) return rc;
-    if (q->fwd.batch == 0) return DIMSUM_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int32_t *ids = reinterpret_cast<const int32_t *>(v->seq_idx_ptr);
-    switch (q->fwd.dtype) {
-        case DIMSUM_F32: return launch_conv_bwd<float>(*q, s, ids, v->seq_idx_batch_stride);
-        case DIMSUM_F16: return launch_conv_bwd<__half>(*q, s, ids, v->seq_idx_batch_stride);
-        default: return launch_conv_bwd<__hip_bfloat16>(*q, s, ids, v->seq_idx_batch_stride);
-    }
+    const int rc = conv_checks(v->conv.fwd, &v->conv, true, v->seq_idx_ptr, v->seq_idx_batch_stride);
+    if (rc != DIMSUM_OK || v->conv.fwd.batch == 0) return rc;
+    const conv_varlen_bwd_args_t a = {v->conv, reinterpret_cast<const int32_t *>(v->seq_idx_ptr), v->seq_idx_batch_stride};
+    const bool ids_vec = ids_vec_ok(a.seq_idx, a.seq_batch_stride);
+    return dispatch_dtype(a.q.fwd.dtype, [&](auto t) { return launch_conv_bwd<decltype(t), true>(a, reinterpret_cast<hipStream_t>(stream), ids_vec); });
 }
 
 extern "C" int dimsum_causal_conv1d_varlen_states_fwd(const dimsum_conv_varlen_states_params_t *e, void *stream) {
     using namespace dimsum;
     if (!e) return DIMSUM_ERR_NULL;
     if (e->struct_size != sizeof(dimsum_conv_varlen_states_params_t)) return DIMSUM_ERR_ABI;
+    // the entry's own fields first, in the header's order; the state's dtype after the shared checks have vouched for conv.dtype
     if (e->num_slots < 1) return DIMSUM_ERR_SHAPE;
     if (!e->end_slots_ptr || !e->state_ptr) return DIMSUM_ERR_NULL;
-    const dimsum_conv_params_t *p = &e->varlen.conv;
-    if (e->end_slots_batch_stride < 0 || (p->batch > 1 && e->end_slots_batch_stride < p->seqlen)) return DIMSUM_ERR_STRIDE;
-    if (e->state_slot_stride < 0 || e->state_c_stride < 0 || e->state_w_stride < 0) return DIMSUM_ERR_STRIDE;
-    if (!p->out_ptr) return DIMSUM_ERR_NULL;
-    int rc = conv_check(*p);
+    const dimsum_conv_params_t &p = e->varlen.conv;
+    if (ids_stride_bad(e->end_slots_batch_stride, p) || any_negative({e->state_slot_stride, e->state_c_stride, e->state_w_stride})) return DIMSUM_ERR_STRIDE;
+    const int rc = conv_checks(p, nullptr, true, e->varlen.seq_idx_ptr, e->varlen.seq_idx_batch_stride);
     if (rc != DIMSUM_OK) return rc;
-    rc = conv_varlen_ids_check(e->varlen.seq_idx_ptr, e->varlen.seq_idx_batch_stride, p->batch, p->seqlen);
-    if (rc != DIMSUM_OK) return rc;
-    if (e->state_dtype != p->dtype) return DIMSUM_ERR_UNSUPPORTED;      // the state is x's elements, moved
-    if (p->batch == 0) return DIMSUM_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int32_t *ids = reinterpret_cast<const int32_t *>(e->varlen.seq_idx_ptr);
-    conv_states_args_t st;
-    memset(&st, 0, sizeof(st));
-    st.end_slots = reinterpret_cast<const int32_t *>(e->end_slots_ptr);
-    st.end_batch_stride = e->end_slots_batch_stride;
-    st.pool = e->state_ptr;
-    st.pool_slot_stride = e->state_slot_stride, st.pool_c_stride = e->state_c_stride, st.pool_w_stride = e->state_w_stride;
-    switch (p->dtype) {
-        case DIMSUM_F32: return launch_conv_fwd<float>(*p, s, ids, e->varlen.seq_idx_batch_stride, &st);
-        case DIMSUM_F16: return launch_conv_fwd<__half>(*p, s, ids, e->varlen.seq_idx_batch_stride, &st);
-        default: return launch_conv_fwd<__hip_bfloat16>(*p, s, ids, e->varlen.seq_idx_batch_stride, &st);
-    }
+    if (e->state_dtype != p.dtype) return DIMSUM_ERR_UNSUPPORTED;      // the state is x's elements, moved
+    if (p.batch == 0) return DIMSUM_OK;
+    conv_states_args_t a;
+    memset(&a, 0, sizeof(a));
+    a.v = {p, reinterpret_cast<const int32_t *>(e->varlen.seq_idx_ptr), e->varlen.seq_idx_batch_stride};
+    a.end_slots = reinterpret_cast<const int32_t *>(e->end_slots_ptr);
+    a.end_batch_stride = e->end_slots_batch_stride;
+    a.pool = e->state_ptr;
+    a.pool_slot_stride = e->state_slot_stride, a.pool_c_stride = e->state_c_stride, a.pool_w_stride = e->state_w_stride;
+    const bool ids_vec = ids_vec_ok(a.v.seq_idx, a.v.seq_batch_stride) && ids_vec_ok(a.end_slots, a.end_batch_stride);
+    return dispatch_dtype(p.dtype, [&](auto t) { return launch_conv_fwd<decltype(t), true, true>(a, reinterpret_cast<hipStream_t>(stream), ids_vec); });
 }

@@ -319,11 +319,6 @@ static int conv_cl_check(const dimsum_conv_cl_params_t &p) {
     if (p.dtype < DIMSUM_F32 || p.dtype > DIMSUM_BF16) return DIMSUM_ERR_DTYPE;
     return DIMSUM_OK;
 }
-static bool any_negative(std::initializer_list<int64_t> strides) {
-    for (int64_t s : strides)
-        if (s < 0) return true;
-    return false;
-}
 // 16-byte accesses along the channels: whole vectors only, every row 16-byte aligned
 template <typename T> static bool cl_vec_ok(const void *ptr, int64_t batch_stride, int64_t l_stride, int dim) {
     constexpr int V = 16 / sizeof(T);
@@ -375,12 +370,7 @@ extern "C" int dimsum_causal_conv1d_cl_fwd(const dimsum_conv_cl_params_t *p, voi
     if (any_negative({p->x_batch_stride, p->x_l_stride, p->weight_c_stride, p->weight_width_stride, p->out_batch_stride, p->out_l_stride}))
         return DIMSUM_ERR_STRIDE;
     if (p->batch == 0) return DIMSUM_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (p->dtype) {
-        case DIMSUM_F32: return launch_conv_cl_fwd<float>(*p, s);
-        case DIMSUM_F16: return launch_conv_cl_fwd<__half>(*p, s);
-        default: return launch_conv_cl_fwd<__hip_bfloat16>(*p, s);
-    }
+    return dispatch_dtype(p->dtype, [&](auto t) { return launch_conv_cl_fwd<decltype(t)>(*p, reinterpret_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int dimsum_causal_conv1d_cl_bwd(const dimsum_conv_cl_bwd_params_t *q, void *stream) {
@@ -395,10 +385,5 @@ extern "C" int dimsum_causal_conv1d_cl_bwd(const dimsum_conv_cl_bwd_params_t *q,
                       q->dx_batch_stride, q->dx_l_stride, q->dweight_c_stride, q->dweight_width_stride}))
         return DIMSUM_ERR_STRIDE;
     if (p.batch == 0) return DIMSUM_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (p.dtype) {
-        case DIMSUM_F32: return launch_conv_cl_bwd<float>(*q, s);
-        case DIMSUM_F16: return launch_conv_cl_bwd<__half>(*q, s);
-        default: return launch_conv_cl_bwd<__hip_bfloat16>(*q, s);
-    }
+    return dispatch_dtype(p.dtype, [&](auto t) { return launch_conv_cl_bwd<decltype(t)>(*q, reinterpret_cast<hipStream_t>(stream)); });
 }

@@ -258,6 +258,21 @@ inline int ssm_args_from(const dimsum_ssm_params_t *p, ssm_args_t &a, bool check
 // ---- host ----------------------------------------------------------------------------------------------------------
 inline int launch_status() { return hipGetLastError() == hipSuccess ? DIMSUM_OK : DIMSUM_ERR_LAUNCH; }
 
+// f(T{}) with T the element type of a DIMSUM_F32 / F16 / BF16 operand (the entry point has refused every other dtype): `[&](auto t) { ... decltype(t) ... }`
+template <typename F> inline int dispatch_dtype(int dtype, F &&f) {
+    switch (dtype) {
+        case DIMSUM_F32: return f(float{});
+        case DIMSUM_F16: return f(__half{});
+        default: return f(__hip_bfloat16{});
+    }
+}
+
+inline bool any_negative(std::initializer_list<int64_t> strides) {
+    for (int64_t s : strides)
+        if (s < 0) return true;
+    return false;
+}
+
 // The own checks of a slot-indexed entry point (dimsum_*_slots_params_t: struct_size, num_slots, <the plain struct>, slots_ptr, slots_stride),
 // in the header's order, before the embedded struct is looked at. The VALUES of the slots are the caller's contract: never read here.
 template <typename V> inline int slots_check(const V *v) {

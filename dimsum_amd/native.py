@@ -242,6 +242,10 @@ def selective_scan_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need
 
 # ---------------------------------------------------------------------------------------------------------------------
 # causal_conv1d_cuda.*   (causal-conv1d/csrc/causal_conv1d.cpp:221-577)
+# One forward and one backward take every variant as a keyword (packed rows: seq_idx; per-segment states: end_slots + conv_state), with one
+# operand check, one out / dx allocate-or-check, one fp32 conversion, one branch per parameter struct and one launch (_conv_launch), in
+# _conv_fwd / _conv_bwd; the named variants are wrappers that insist on their arguments. A new variant is a keyword here, a struct branch,
+# and a template flag in csrc/causal_conv1d.hip.
 # ---------------------------------------------------------------------------------------------------------------------
 def _check_conv(x, weight, bias):
     """the checks of both layouts -> True when x is channel-last and goes to the (batch, seqlen, dim) kernels. A tensor the
@@ -261,9 +265,43 @@ def _check_conv(x, weight, bias):
     return channel_last
 
 
+def _check_token_ids(t, name, batch, seqlen, who):
+    """a per-token int32 operand (seq_idx; end_slots: where it is >= 0 the state after that position goes into that slot of a pool): (batch,
+    seqlen), contiguous. Dtype, rank, shape and contiguity here, the device by the caller, last. The VALUES stay on the device: seq_idx is only
+    ever compared; that the non-negative end_slots are below num_slots and that none appears twice in one launch is the caller's contract
+    (include/dimsum_hip.h)."""
+    _check(torch.is_tensor(t) and t.dtype == torch.int32 and tuple(t.shape) == (batch, seqlen) and t.is_contiguous(),
+           f"{who}: {name} must be a contiguous int32 (batch, seqlen) = ({batch}, {seqlen}) tensor")
+
+
+def _check_seq_idx(seq_idx, batch, seqlen, who):
+    _check_token_ids(seq_idx, "seq_idx", batch, seqlen, who)
+
+
+def _check_end_slots(end_slots, batch, seqlen, who):
+    _check_token_ids(end_slots, "end_slots", batch, seqlen, who)
+
+
 def _is_channel_last(t):
     """(batch, dim, seqlen) with channel stride 1: what the channel-last kernels address"""
     return t.stride(1) == 1 or t.shape[1] == 1
+
+
+def _new_channel_last(x):
+    """an uninitialised (batch, dim, seqlen) tensor like x whose memory is (batch, seqlen, dim)"""
+    batch, dim, seqlen = x.shape
+    return x.new_empty(batch, seqlen, dim).transpose(1, 2)
+
+
+def _conv_f32(weight, bias):
+    """the kernels read weights and bias as fp32, the bias densely: -> (weight, bias) so (fp32 operands are not copied)"""
+    return weight.float(), bias.float().contiguous() if bias is not None else None
+
+
+def _conv_launch(entry, P, x, who):
+    """the conv section's launch: library entry point `entry` on the current stream of x's device"""
+    with torch.cuda.device(x.device):
+        _lib.check(getattr(_lib.load(), entry)(P, _stream(x)), who)
 
 
 def _fill_conv(P, x, weight, bias, silu, out):
@@ -287,41 +325,82 @@ def _fill_conv_cl(P, x, weight, bias, silu, out):
         P.out_batch_stride, P.out_l_stride, P.out_ptr = out.stride(0), out.stride(2), _ptr(out)
 
 
+def _fill_conv_bwd(Q, dout, dx, dweight, dbias, channel_last):
+    """what dimsum_conv_bwd_params_t / dimsum_conv_cl_bwd_params_t hold beyond their forward struct"""
+    if channel_last:
+        Q.dout_batch_stride, Q.dout_l_stride = dout.stride(0), dout.stride(2)
+        Q.dx_batch_stride, Q.dx_l_stride = dx.stride(0), dx.stride(2)
+    else:
+        Q.dout_batch_stride, Q.dout_c_stride = dout.stride(0), dout.stride(1)
+        Q.dx_batch_stride, Q.dx_c_stride = dx.stride(0), dx.stride(1)
+    Q.dweight_c_stride, Q.dweight_width_stride = dweight.stride(0), dweight.stride(1)
+    Q.dout_ptr, Q.dx_ptr, Q.dweight_ptr, Q.dbias_ptr = _ptr(dout), _ptr(dx), _ptr(dweight), _ptr(dbias)
+
+
 CONV_CL_CHUNK = 64        # DIMSUM_CONV_CL_CHUNK: tokens one wave of the channel-last kernels walks; the next chunk re-reads width - 1 halo rows
 
 
-def _new_channel_last(x):
-    """an uninitialised (batch, dim, seqlen) tensor like x whose memory is (batch, seqlen, dim)"""
-    batch, dim, seqlen = x.shape
-    return x.new_empty(batch, seqlen, dim).transpose(1, 2)
-
-
-def causal_conv1d_fwd(x, weight, bias, silu_activation, out=None):
+def causal_conv1d_fwd(x, weight, bias, silu_activation, out=None, *, seq_idx=None, end_slots=None, conv_state=None):
     """-> out (batch, dim, seqlen), like causal_conv1d_cuda.causal_conv1d_fwd. Weights are used in fp32. A channel-last x (channel stride 1,
     e.g. the transpose of a (batch, seqlen, dim) activation or of one half of a (batch, seqlen, 2 dim) buffer) is read as it is and out
-    is channel-last too."""
+    is channel-last too.
+    seq_idx: causal_conv1d_varlen_fwd's (packed rows); end_slots / conv_state: causal_conv1d_varlen_states_fwd's. Both need a
+    seqlen-contiguous x."""
+    who = ("causal_conv1d_varlen_states_fwd" if end_slots is not None or conv_state is not None else
+           "causal_conv1d_varlen_fwd" if seq_idx is not None else "causal_conv1d_fwd")
+    return _conv_fwd(who, x, weight, bias, silu_activation, out, seq_idx, end_slots, conv_state)
+
+
+def _conv_fwd(who, x, weight, bias, silu_activation, out, seq_idx=None, end_slots=None, conv_state=None):
+    """every forward of the (batch, dim, seqlen) conv; `who` names the variant: causal_conv1d_fwd (plain or channel-last), _varlen_fwd
+    (seq_idx), _varlen_states_fwd (+ end_slots, conv_state). The shape, dtype and stride refusals of the packed-row operands come first
+    (they need no GPU)."""
+    states, packed = who == "causal_conv1d_varlen_states_fwd", who != "causal_conv1d_fwd"
+    if packed:
+        _check(x.dim() == 3, "causal_conv1d: x must be (batch, dim, seqlen)")
+        _check_token_ids(seq_idx, "seq_idx", x.shape[0], x.shape[2], who)
+    if states:
+        _check_token_ids(end_slots, "end_slots", x.shape[0], x.shape[2], who)
+        _check(torch.is_tensor(conv_state) and conv_state.dim() == 3 and conv_state.shape[0] >= 1 and tuple(conv_state.shape[1:]) == (x.shape[1], weight.shape[-1]),
+               f"{who}: conv_state must be a pool (num_slots >= 1, dim, width)")
+        _check(conv_state.dtype == x.dtype, f"{who}: conv_state must have x's dtype {x.dtype}, got {conv_state.dtype} (the state is x's elements, moved, not converted)")
     channel_last = _check_conv(x, weight, bias)
-    weight = weight.float()
-    bias = bias.float().contiguous() if bias is not None else None
-    if channel_last:
-        if out is None:
-            out = _new_channel_last(x)
-        else:
-            _gpu(out)
-            _check(out.shape == x.shape and out.dtype == x.dtype and _is_channel_last(out), "causal_conv1d_fwd: out must be channel-last like x")
-        if x.numel() > 0:
-            P = _lib.ConvClParams()
-            _fill_conv_cl(P, x, weight, bias, silu_activation, out)
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.load().dimsum_causal_conv1d_cl_fwd(P, _stream(x)), "causal_conv1d_fwd")
-        return out
+    if packed:
+        if channel_last:
+            raise RuntimeError(f"{who}: seq_idx needs a seqlen-contiguous x (the channel-last kernels take none)")
+        _gpu(seq_idx, end_slots, conv_state)
+    weight, bias = _conv_f32(weight, bias)
     if out is None:
-        out = torch.empty_like(x)       # inherits x's layout like the reference (causal_conv1d.cpp:262): d-major in Mamba
-    if x.numel() > 0:
+        out = _new_channel_last(x) if channel_last else torch.empty_like(x)   # x's layout like the reference (causal_conv1d.cpp:262): d-major in Mamba
+    elif channel_last:
+        _gpu(out)
+        _check(out.shape == x.shape and out.dtype == x.dtype and _is_channel_last(out), "causal_conv1d_fwd: out must be channel-last like x")
+    elif packed:
+        _gpu(out)
+        _check(out.shape == x.shape and out.dtype == x.dtype and out.stride(2) == 1, f"{who}: bad out")
+    if x.numel() == 0:
+        return out
+    if channel_last:
+        P = _lib.ConvClParams()
+        _fill_conv_cl(P, x, weight, bias, silu_activation, out)
+        _conv_launch("dimsum_causal_conv1d_cl_fwd", P, x, who)
+    elif states:
+        P = _lib.ConvVarlenStatesParams()
+        _fill_conv(P.varlen.conv, x, weight, bias, silu_activation, out)
+        P.varlen.seq_idx_ptr, P.varlen.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
+        P.num_slots, P.end_slots_ptr, P.end_slots_batch_stride = conv_state.shape[0], _ptr(end_slots), end_slots.stride(0)
+        P.state_ptr, P.state_dtype = _ptr(conv_state), _DT[conv_state.dtype]
+        P.state_slot_stride, P.state_c_stride, P.state_w_stride = conv_state.stride()
+        _conv_launch("dimsum_causal_conv1d_varlen_states_fwd", P, x, who)
+    elif packed:
+        P = _lib.ConvVarlenParams()
+        _fill_conv(P.conv, x, weight, bias, silu_activation, out)
+        P.seq_idx_ptr, P.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
+        _conv_launch("dimsum_causal_conv1d_varlen_fwd", P, x, who)
+    else:
         P = _lib.ConvParams()
         _fill_conv(P, x, weight, bias, silu_activation, out)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dimsum_causal_conv1d_fwd(P, _stream(x)), "causal_conv1d_fwd")
+        _conv_launch("dimsum_causal_conv1d_fwd", P, x, who)
     return out
 
 
@@ -332,153 +411,70 @@ def causal_conv1d_fwd_cond(x, weight, bias, silu_activation, init_x):
     return causal_conv1d_fwd(x, weight, bias, silu_activation, out=init_x)
 
 
-def causal_conv1d_bwd(x, weight, bias, dout, dx, silu_activation):
-    """-> [dx, dweight, dbias] like causal_conv1d_cuda.causal_conv1d_bwd (dx may be a caller-provided view). With a channel-last x, dx is
-    channel-last and a dout of any other layout is brought there once (causal_conv1d.cpp:379)."""
-    channel_last = _check_conv(x, weight, bias)
-    _gpu(dout, dx)
-    if channel_last:
-        _check(dout.shape == x.shape and dout.dtype == x.dtype, "causal_conv1d_bwd: bad dout")
-        if not _is_channel_last(dout):
-            dout = dout.transpose(1, 2).contiguous().transpose(1, 2)
-        if dx is None:
-            dx = _new_channel_last(x)
-        else:
-            _check(dx.shape == x.shape and dx.dtype == x.dtype and _is_channel_last(dx), "causal_conv1d_bwd: bad dx")
-    else:
-        _check(dout.shape == x.shape and dout.dtype == x.dtype and (dout.stride(2) == 1 or dout.shape[2] == 1), "causal_conv1d_bwd: bad dout")
-        if dx is None:
-            dx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
-        else:
-            _check(dx.shape == x.shape and dx.dtype == x.dtype and dx.stride(2) == 1, "causal_conv1d_bwd: bad dx")
-    w32 = weight.float()
-    b32 = bias.float().contiguous() if bias is not None else None
-    # fp32 accumulate, then cast (cpp:405-425); ONE zero-filled buffer for both accumulators (one fill launch instead of two)
-    acc = _zeros(weight.numel() + (weight.shape[0] if bias is not None else 0), x.device)
-    dweight = acc[:weight.numel()].view(weight.shape)
-    dbias = acc[weight.numel():] if bias is not None else None
-    if x.numel() > 0:
-        Q = _lib.ConvClBwdParams() if channel_last else _lib.ConvBwdParams()
-        if channel_last:
-            _fill_conv_cl(Q.fwd, x, w32, b32, silu_activation, None)
-            Q.dout_batch_stride, Q.dout_l_stride = dout.stride(0), dout.stride(2)
-            Q.dx_batch_stride, Q.dx_l_stride = dx.stride(0), dx.stride(2)
-        else:
-            _fill_conv(Q.fwd, x, w32, b32, silu_activation, None)
-            Q.dout_batch_stride, Q.dout_c_stride = dout.stride(0), dout.stride(1)
-            Q.dx_batch_stride, Q.dx_c_stride = dx.stride(0), dx.stride(1)
-        Q.dweight_c_stride, Q.dweight_width_stride = dweight.stride(0), dweight.stride(1)
-        Q.dout_ptr, Q.dx_ptr, Q.dweight_ptr, Q.dbias_ptr = _ptr(dout), _ptr(dx), _ptr(dweight), _ptr(dbias)
-        with torch.cuda.device(x.device):
-            lib = _lib.load()
-            launch = lib.dimsum_causal_conv1d_cl_bwd if channel_last else lib.dimsum_causal_conv1d_bwd
-            _lib.check(launch(Q, _stream(x)), "causal_conv1d_bwd")
-    return [dx, dweight.to(weight.dtype), dbias.to(bias.dtype) if bias is not None else None]
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# packed rows (upstream Mamba's seq_idx): several sequences in one (batch, seqlen) row that must not see each other
-# ---------------------------------------------------------------------------------------------------------------------
-def _check_seq_idx(seq_idx, batch, seqlen, who):
-    """seq_idx: (batch, seqlen) int32, contiguous. Its values are only ever compared: any content is safe. The device is checked last."""
-    _check(torch.is_tensor(seq_idx) and seq_idx.dtype == torch.int32 and tuple(seq_idx.shape) == (batch, seqlen) and seq_idx.is_contiguous(),
-           f"{who}: seq_idx must be a contiguous int32 (batch, seqlen) = ({batch}, {seqlen}) tensor")
-
-
 def causal_conv1d_varlen_fwd(x, weight, bias, silu_activation, seq_idx, out=None):
     """causal_conv1d_fwd on packed rows -> out (batch, dim, seqlen): tap j of position t counts iff no boundary (a change of seq_idx) lies
     in (t - j, t]. x (batch, dim, seqlen) with unit stride along seqlen and free batch / channel strides (a half of xz, a d-major view);
     a channel-last x is refused: those kernels take no seq_idx."""
-    _check(x.dim() == 3, "causal_conv1d: x must be (batch, dim, seqlen)")
-    _check_seq_idx(seq_idx, x.shape[0], x.shape[2], "causal_conv1d_varlen_fwd")
-    _check(not _check_conv(x, weight, bias), "causal_conv1d_varlen_fwd: seq_idx needs a seqlen-contiguous x (the channel-last kernels take none)")
-    _gpu(seq_idx)
-    weight = weight.float()
-    bias = bias.float().contiguous() if bias is not None else None
-    if out is None:
-        out = torch.empty_like(x)
-    else:
-        _gpu(out)
-        _check(out.shape == x.shape and out.dtype == x.dtype and out.stride(2) == 1, "causal_conv1d_varlen_fwd: bad out")
-    if x.numel() > 0:
-        P = _lib.ConvVarlenParams()
-        _fill_conv(P.conv, x, weight, bias, silu_activation, out)
-        P.seq_idx_ptr, P.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dimsum_causal_conv1d_varlen_fwd(P, _stream(x)), "causal_conv1d_varlen_fwd")
-    return out
-
-
-def _check_end_slots(end_slots, batch, seqlen, who):
-    """end_slots: (batch, seqlen) int32, contiguous -- where it is >= 0 the state after that position goes into that slot of a pool. Dtype,
-    rank, shape and contiguity here, the device by the caller, last. The VALUES stay on the device: that the non-negative ones are below
-    num_slots and that none appears twice in one launch is the caller's contract (include/dimsum_hip.h)."""
-    _check(torch.is_tensor(end_slots) and end_slots.dtype == torch.int32 and tuple(end_slots.shape) == (batch, seqlen) and end_slots.is_contiguous(),
-           f"{who}: end_slots must be a contiguous int32 (batch, seqlen) = ({batch}, {seqlen}) tensor")
+    return _conv_fwd("causal_conv1d_varlen_fwd", x, weight, bias, silu_activation, out, seq_idx)
 
 
 def causal_conv1d_varlen_states_fwd(x, weight, bias, silu_activation, seq_idx, end_slots, conv_state, out=None):
     """causal_conv1d_varlen_fwd that also stores per-segment conv states -> out: where end_slots[b, t] = s >= 0, conv_state[s, :, :] becomes
     the last `width` inputs of the segment ending at t (zero-padded on the left when the segment is shorter), x[b, :, t] last -- the window
     causal_conv1d_update shifts. conv_state: a pool (num_slots, dim, width) of x's dtype with free strides; slots nobody names are not
-    touched. Inference only. The slots' values are the caller's contract (_check_end_slots)."""
-    who = "causal_conv1d_varlen_states_fwd"
-    _check(x.dim() == 3, "causal_conv1d: x must be (batch, dim, seqlen)")
-    _check_seq_idx(seq_idx, x.shape[0], x.shape[2], who)
-    _check_end_slots(end_slots, x.shape[0], x.shape[2], who)
-    _check(torch.is_tensor(conv_state) and conv_state.dim() == 3 and conv_state.shape[0] >= 1 and tuple(conv_state.shape[1:]) == (x.shape[1], weight.shape[-1]),
-           f"{who}: conv_state must be a pool (num_slots >= 1, dim, width)")
-    _check(conv_state.dtype == x.dtype, f"{who}: conv_state must have x's dtype {x.dtype}, got {conv_state.dtype} (the state is x's elements, moved, not converted)")
-    _check(not _check_conv(x, weight, bias), f"{who}: seq_idx needs a seqlen-contiguous x (the channel-last kernels take none)")
-    _gpu(seq_idx, end_slots, conv_state)
-    weight = weight.float()
-    bias = bias.float().contiguous() if bias is not None else None
-    if out is None:
-        out = torch.empty_like(x)
+    touched. Inference only. The slots' values are the caller's contract (_check_token_ids)."""
+    return _conv_fwd("causal_conv1d_varlen_states_fwd", x, weight, bias, silu_activation, out, seq_idx, end_slots, conv_state)
+
+
+def causal_conv1d_bwd(x, weight, bias, dout, dx, silu_activation, *, seq_idx=None):
+    """-> [dx, dweight, dbias] like causal_conv1d_cuda.causal_conv1d_bwd (dx may be a caller-provided view). With a channel-last x, dx is
+    channel-last and a dout of any other layout is brought there once (causal_conv1d.cpp:379).
+    seq_idx: causal_conv1d_varlen_bwd's (packed rows, a seqlen-contiguous x)."""
+    return _conv_bwd("causal_conv1d_varlen_bwd" if seq_idx is not None else "causal_conv1d_bwd", x, weight, bias, dout, dx, silu_activation, seq_idx)
+
+
+def _conv_bwd(who, x, weight, bias, dout, dx, silu_activation, seq_idx=None):
+    """every backward of the (batch, dim, seqlen) conv; `who` names the variant: causal_conv1d_bwd (plain or channel-last) or _varlen_bwd (seq_idx)"""
+    packed = who == "causal_conv1d_varlen_bwd"
+    if packed:
+        _check(x.dim() == 3, "causal_conv1d: x must be (batch, dim, seqlen)")
+        _check_token_ids(seq_idx, "seq_idx", x.shape[0], x.shape[2], who)
+    channel_last = _check_conv(x, weight, bias)
+    _check(not (packed and channel_last), f"{who}: seq_idx needs a seqlen-contiguous x (the channel-last kernels take none)")
+    _gpu(dout, dx, seq_idx)
+    _check(dout.shape == x.shape and dout.dtype == x.dtype and (channel_last or dout.stride(2) == 1 or dout.shape[2] == 1), f"{who}: bad dout")
+    if channel_last and not _is_channel_last(dout):
+        dout = dout.transpose(1, 2).contiguous().transpose(1, 2)
+    if dx is None:
+        dx = _new_channel_last(x) if channel_last else torch.empty(x.shape, device=x.device, dtype=x.dtype)
     else:
-        _gpu(out)
-        _check(out.shape == x.shape and out.dtype == x.dtype and out.stride(2) == 1, f"{who}: bad out")
+        _check(dx.shape == x.shape and dx.dtype == x.dtype and (_is_channel_last(dx) if channel_last else dx.stride(2) == 1), f"{who}: bad dx")
+    w32, b32 = _conv_f32(weight, bias)
+    # fp32 accumulate, then cast (cpp:405-425); ONE zero-filled buffer for both accumulators (one fill launch instead of two)
+    acc = _zeros(weight.numel() + (weight.shape[0] if bias is not None else 0), x.device)
+    dweight = acc[:weight.numel()].view(weight.shape)
+    dbias = acc[weight.numel():] if bias is not None else None
     if x.numel() > 0:
-        E = _lib.ConvVarlenStatesParams()
-        _fill_conv(E.varlen.conv, x, weight, bias, silu_activation, out)
-        E.varlen.seq_idx_ptr, E.varlen.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
-        E.num_slots, E.end_slots_ptr, E.end_slots_batch_stride = conv_state.shape[0], _ptr(end_slots), end_slots.stride(0)
-        E.state_ptr, E.state_dtype = _ptr(conv_state), _DT[conv_state.dtype]
-        E.state_slot_stride, E.state_c_stride, E.state_w_stride = conv_state.stride()
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dimsum_causal_conv1d_varlen_states_fwd(E, _stream(x)), who)
-    return out
+        if packed:
+            P = _lib.ConvVarlenBwdParams()
+            Q, entry = P.conv, "dimsum_causal_conv1d_varlen_bwd"
+            P.seq_idx_ptr, P.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
+        elif channel_last:
+            P = Q = _lib.ConvClBwdParams()
+            entry = "dimsum_causal_conv1d_cl_bwd"
+        else:
+            P = Q = _lib.ConvBwdParams()
+            entry = "dimsum_causal_conv1d_bwd"
+        (_fill_conv_cl if channel_last else _fill_conv)(Q.fwd, x, w32, b32, silu_activation, None)
+        _fill_conv_bwd(Q, dout, dx, dweight, dbias, channel_last)
+        _conv_launch(entry, P, x, who)
+    return [dx, dweight.to(weight.dtype), dbias.to(bias.dtype) if bias is not None else None]
 
 
 def causal_conv1d_varlen_bwd(x, weight, bias, dout, dx, silu_activation, seq_idx):
     """-> [dx, dweight, dbias] of causal_conv1d_varlen_fwd: dx[t] collects from the later positions of its own segment only; dweight sums
     the unmasked (tap, position) pairs, dbias every position"""
-    _check(x.dim() == 3, "causal_conv1d: x must be (batch, dim, seqlen)")
-    _check_seq_idx(seq_idx, x.shape[0], x.shape[2], "causal_conv1d_varlen_bwd")
-    _check(not _check_conv(x, weight, bias), "causal_conv1d_varlen_bwd: seq_idx needs a seqlen-contiguous x (the channel-last kernels take none)")
-    _gpu(dout, dx, seq_idx)
-    _check(dout.shape == x.shape and dout.dtype == x.dtype and (dout.stride(2) == 1 or dout.shape[2] == 1), "causal_conv1d_varlen_bwd: bad dout")
-    if dx is None:
-        dx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
-    else:
-        _check(dx.shape == x.shape and dx.dtype == x.dtype and dx.stride(2) == 1, "causal_conv1d_varlen_bwd: bad dx")
-    w32 = weight.float()
-    b32 = bias.float().contiguous() if bias is not None else None
-    acc = _zeros(weight.numel() + (weight.shape[0] if bias is not None else 0), x.device)
-    dweight = acc[:weight.numel()].view(weight.shape)
-    dbias = acc[weight.numel():] if bias is not None else None
-    if x.numel() > 0:
-        V = _lib.ConvVarlenBwdParams()
-        Q = V.conv
-        _fill_conv(Q.fwd, x, w32, b32, silu_activation, None)
-        Q.dout_batch_stride, Q.dout_c_stride = dout.stride(0), dout.stride(1)
-        Q.dx_batch_stride, Q.dx_c_stride = dx.stride(0), dx.stride(1)
-        Q.dweight_c_stride, Q.dweight_width_stride = dweight.stride(0), dweight.stride(1)
-        Q.dout_ptr, Q.dx_ptr, Q.dweight_ptr, Q.dbias_ptr = _ptr(dout), _ptr(dx), _ptr(dweight), _ptr(dbias)
-        V.seq_idx_ptr, V.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dimsum_causal_conv1d_varlen_bwd(V, _stream(x)), "causal_conv1d_varlen_bwd")
-    return [dx, dweight.to(weight.dtype), dbias.to(bias.dtype) if bias is not None else None]
+    return _conv_bwd("causal_conv1d_varlen_bwd", x, weight, bias, dout, dx, silu_activation, seq_idx)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -501,6 +497,34 @@ def _fill_slots(S, state_indices, pool):
     S.slots_ptr, S.slots_stride, S.num_slots = _ptr(state_indices), state_indices.stride(0), pool.shape[0]
 
 
+def _check_conv_carried(who, x, conv_state, weight, bias, pool=False):
+    """weight, width, state and bias of the carried-state pair (causal_conv1d_update / _chunk), in this order; x is (batch, dim[, seqlen]).
+    On the serving path: a message is only put together when its refusal fires."""
+    batch, dim = x.shape[0], x.shape[1]
+    if not (weight.dim() == 2 and weight.shape[0] == dim):
+        raise RuntimeError(f"{who}: weight must be (dim, width)")
+    width = weight.shape[1]
+    if not 2 <= width <= 4:
+        raise RuntimeError(f"{who} only supports width between 2 and 4")
+    if pool:
+        if not (conv_state.dim() == 3 and conv_state.shape[0] >= 1 and tuple(conv_state.shape[1:]) == (dim, width) and conv_state.dtype == x.dtype):
+            raise RuntimeError(f"{who}: with state_indices conv_state must be a pool (num_slots >= 1, dim, width) of x's dtype")
+    elif not (conv_state.dim() == 3 and tuple(conv_state.shape) == (batch, dim, width) and conv_state.dtype == x.dtype):
+        raise RuntimeError(f"{who}: conv_state must be (batch, dim, width) of x's dtype")
+    if bias is not None and tuple(bias.shape) != (dim,):
+        raise RuntimeError(f"{who}: bias must be (dim,)")
+
+
+def _fill_conv_carried(P, x, conv_state, weight, bias, silu, out):
+    """what dimsum_conv_update_params_t and dimsum_conv_chunk_params_t share (the chunk's seqlen is its own); weight and bias as _conv_f32 made them"""
+    P.batch, P.dim, P.width, P.silu_activation, P.dtype = x.shape[0], x.shape[1], weight.shape[1], int(bool(silu)), _DT[x.dtype]
+    P.x_batch_stride, P.x_c_stride = x.stride(0), x.stride(1)
+    P.state_batch_stride, P.state_c_stride, P.state_w_stride = conv_state.stride()
+    P.weight_c_stride, P.weight_width_stride = weight.stride()
+    P.out_batch_stride, P.out_c_stride = out.stride(0), out.stride(1)
+    P.x_ptr, P.weight_ptr, P.bias_ptr, P.conv_state_ptr, P.out_ptr = _ptr(x), _ptr(weight), _ptr(bias), _ptr(conv_state), _ptr(out)
+
+
 def causal_conv1d_update(x, conv_state, weight, bias, silu_activation, state_indices=None):
     """-> out (batch, dim), like causal_conv1d_cuda.causal_conv1d_update: conv_state (batch, dim, width) is shifted left by one and x
     appended, in place; out = act(sum_w conv_state * weight + bias). Weights are used in fp32.
@@ -510,36 +534,18 @@ def causal_conv1d_update(x, conv_state, weight, bias, silu_activation, state_ind
         _check_state_indices(state_indices, x, "causal_conv1d_update")
     _gpu(x, conv_state, weight, bias)
     _check(x.dim() == 2 and x.dtype in _DT, "causal_conv1d_update: x must be (batch, dim) in float32, float16 or bfloat16")
-    batch, dim = x.shape
-    _check(weight.dim() == 2 and weight.shape[0] == dim, "causal_conv1d_update: weight must be (dim, width)")
-    width = weight.shape[1]
-    _check(2 <= width <= 4, "causal_conv1d_update only supports width between 2 and 4")
-    if state_indices is None:
-        _check(tuple(conv_state.shape) == (batch, dim, width) and conv_state.dtype == x.dtype,
-               "causal_conv1d_update: conv_state must be (batch, dim, width) of x's dtype")
-    else:
-        _check(conv_state.dim() == 3 and conv_state.shape[0] >= 1 and tuple(conv_state.shape[1:]) == (dim, width) and conv_state.dtype == x.dtype,
-               "causal_conv1d_update: with state_indices conv_state must be a pool (num_slots >= 1, dim, width) of x's dtype")
-    if bias is not None:
-        _check(tuple(bias.shape) == (dim,), "causal_conv1d_update: bias must be (dim,)")
-    weight = weight.float()
-    bias = bias.float().contiguous() if bias is not None else None
+    _check_conv_carried("causal_conv1d_update", x, conv_state, weight, bias, pool=state_indices is not None)
+    weight, bias = _conv_f32(weight, bias)
     out = torch.empty_like(x)
     if x.numel() > 0:
         S = None if state_indices is None else _lib.ConvUpdateSlotsParams()
         P = _lib.ConvUpdateParams() if S is None else S.conv
-        P.batch, P.dim, P.width, P.silu_activation, P.dtype = batch, dim, width, int(bool(silu_activation)), _DT[x.dtype]
-        P.x_batch_stride, P.x_c_stride = x.stride()
-        P.state_batch_stride, P.state_c_stride, P.state_w_stride = conv_state.stride()
-        P.weight_c_stride, P.weight_width_stride = weight.stride()
-        P.out_batch_stride, P.out_c_stride = out.stride()
-        P.x_ptr, P.weight_ptr, P.bias_ptr, P.conv_state_ptr, P.out_ptr = _ptr(x), _ptr(weight), _ptr(bias), _ptr(conv_state), _ptr(out)
-        with torch.cuda.device(x.device):
-            if S is None:
-                _lib.check(_lib.load().dimsum_causal_conv1d_update(P, _stream(x)), "causal_conv1d_update")
-            else:
-                _fill_slots(S, state_indices, conv_state)
-                _lib.check(_lib.load().dimsum_causal_conv1d_update_slots(S, _stream(x)), "causal_conv1d_update (state_indices)")
+        _fill_conv_carried(P, x, conv_state, weight, bias, silu_activation, out)
+        if S is None:
+            _conv_launch("dimsum_causal_conv1d_update", P, x, "causal_conv1d_update")
+        else:
+            _fill_slots(S, state_indices, conv_state)
+            _conv_launch("dimsum_causal_conv1d_update_slots", S, x, "causal_conv1d_update (state_indices)")
     return out
 
 
@@ -551,29 +557,17 @@ def causal_conv1d_chunk(x, conv_state, weight, bias, silu_activation):
     _check(x.dim() == 3 and x.dtype in _DT, "causal_conv1d_chunk: x must be (batch, dim, seqlen) in float32, float16 or bfloat16")
     batch, dim, seqlen = x.shape
     _check(batch >= 1 and dim >= 1 and seqlen >= 1, "causal_conv1d_chunk: x must not be empty")
-    _check(weight.dim() == 2 and weight.shape[0] == dim, "causal_conv1d_chunk: weight must be (dim, width)")
-    width = weight.shape[1]
-    _check(2 <= width <= 4, "causal_conv1d_chunk only supports width between 2 and 4")
-    _check(conv_state.dim() == 3 and tuple(conv_state.shape) == (batch, dim, width) and conv_state.dtype == x.dtype,
-           "causal_conv1d_chunk: conv_state must be (batch, dim, width) of x's dtype")
-    if bias is not None:
-        _check(tuple(bias.shape) == (dim,), "causal_conv1d_chunk: bias must be (dim,)")
+    _check_conv_carried("causal_conv1d_chunk", x, conv_state, weight, bias)
     _check(x.stride(2) == 1 or seqlen == 1, "causal_conv1d_chunk: x.stride(-1) must be 1")
     _gpu(x, conv_state, weight, bias)
-    weight = weight.float()
-    bias = bias.float().contiguous() if bias is not None else None
+    weight, bias = _conv_f32(weight, bias)
     out = torch.empty_like(x)           # x's layout: d-major in the mixer
     if out.stride(2) != 1 and seqlen > 1:
         out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
     P = _lib.ConvChunkParams()
-    P.batch, P.dim, P.seqlen, P.width, P.silu_activation, P.dtype = batch, dim, seqlen, width, int(bool(silu_activation)), _DT[x.dtype]
-    P.x_batch_stride, P.x_c_stride = x.stride(0), x.stride(1)
-    P.state_batch_stride, P.state_c_stride, P.state_w_stride = conv_state.stride()
-    P.weight_c_stride, P.weight_width_stride = weight.stride()
-    P.out_batch_stride, P.out_c_stride = out.stride(0), out.stride(1)
-    P.x_ptr, P.weight_ptr, P.bias_ptr, P.conv_state_ptr, P.out_ptr = _ptr(x), _ptr(weight), _ptr(bias), _ptr(conv_state), _ptr(out)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().dimsum_causal_conv1d_chunk(P, _stream(x)), "causal_conv1d_chunk")
+    P.seqlen = seqlen
+    _fill_conv_carried(P, x, conv_state, weight, bias, silu_activation, out)
+    _conv_launch("dimsum_causal_conv1d_chunk", P, x, "causal_conv1d_chunk")
     return out
 
 

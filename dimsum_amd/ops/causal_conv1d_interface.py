@@ -4,16 +4,21 @@ import torch
 from .. import native
 
 
+def _silu_flag(activation, who=None):
+    """activation None | "silu" | "swish" -> whether SiLU is applied; anything else is refused (who: a plain-torch restatement names itself)"""
+    if activation not in (None, "silu", "swish"):
+        raise NotImplementedError("activation must be None, silu, or swish" if who is None else f"{who}: activation {activation!r} (None, 'silu' or 'swish')")
+    return activation is not None
+
+
 class CausalConv1dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias=None, activation=None):
-        if activation not in (None, "silu", "swish"):
-            raise NotImplementedError("activation must be None, silu, or swish")
+        ctx.activation = _silu_flag(activation)
         if x.stride(2) != 1 and x.stride(1) != 1:
             x = x.contiguous()          # neither seqlen-contiguous nor channel-last (causal_conv1d_interface.py:15-16)
         bias = bias.contiguous() if bias is not None else None
         ctx.save_for_backward(x, weight, bias)
-        ctx.activation = activation in ("silu", "swish")
         return native.causal_conv1d_fwd(x, weight, bias, ctx.activation)
 
     @staticmethod
@@ -31,13 +36,11 @@ class CausalConv1dVarlenFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, activation, seq_idx):
-        if activation not in (None, "silu", "swish"):
-            raise NotImplementedError("activation must be None, silu, or swish")
+        ctx.activation = _silu_flag(activation)
         if x.stride(2) != 1:
             x = x.contiguous()          # the packed-row kernels read seqlen-contiguous rows (free batch and channel strides)
         bias = bias.contiguous() if bias is not None else None
         ctx.save_for_backward(x, weight, bias, seq_idx)
-        ctx.activation = activation in ("silu", "swish")
         return native.causal_conv1d_varlen_fwd(x, weight, bias, ctx.activation, seq_idx)
 
     @staticmethod
@@ -51,8 +54,7 @@ class CausalConv1dVarlenFn(torch.autograd.Function):
 
 def _conv_varlen_states(x, weight, bias, activation, seq_idx, end_slots, conv_state):
     """causal_conv1d_fn(seq_idx=, end_slots=, conv_state=): the kEmit kernels of csrc/causal_conv1d.hip, no graph"""
-    if activation not in (None, "silu", "swish"):
-        raise NotImplementedError("activation must be None, silu, or swish")
+    silu = _silu_flag(activation)
     if end_slots is None or conv_state is None:
         raise ValueError("causal_conv1d_fn: end_slots and conv_state go together (where to store, and the pool to store into)")
     if seq_idx is None:
@@ -64,8 +66,7 @@ def _conv_varlen_states(x, weight, bias, activation, seq_idx, end_slots, conv_st
     with torch.no_grad():
         if x.stride(2) != 1:
             x = x.contiguous()
-        return native.causal_conv1d_varlen_states_fwd(x, weight, bias.contiguous() if bias is not None else None, activation in ("silu", "swish"),
-                                                      seq_idx, end_slots, conv_state)
+        return native.causal_conv1d_varlen_states_fwd(x, weight, bias.contiguous() if bias is not None else None, silu, seq_idx, end_slots, conv_state)
 
 
 def causal_conv1d_fn(x, weight, bias=None, activation=None, seq_idx=None, end_slots=None, conv_state=None):
@@ -89,9 +90,7 @@ def causal_conv1d_varlen_torch(x, weight, bias=None, activation=None, seq_idx=No
     compare the kernels with and what CPU tests put in their place; never a fallback: nothing in the package calls it.
     end_slots / conv_state: causal_conv1d_fn's -- where end_slots[b, t] = s >= 0, conv_state[s, :, width - 1 - j] receives the masked tap j of
     position t (a host read of end_slots: test infrastructure)."""
-    silu = {None: False, "silu": True, "swish": True}.get(activation)
-    if silu is None:
-        raise NotImplementedError(f"causal_conv1d_varlen_torch: activation {activation!r} (None, 'silu' or 'swish')")
+    silu = _silu_flag(activation, "causal_conv1d_varlen_torch")
     batch, dim, seqlen = x.shape
     width = weight.shape[-1]
     assert weight.shape == (dim, width) and (seq_idx is None or tuple(seq_idx.shape) == (batch, seqlen))
@@ -129,11 +128,10 @@ def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None, stat
     state_indices (batch,) int32 (upstream Mamba's conv_state_indices): conv_state is a pool (num_slots, dim, width), row b works on
     conv_state[state_indices[b]], a negative entry is a padding row (no state touched, zero output). Entries must be < num_slots and no slot
     may be named twice: neither is checked (it would take a device read)."""
-    if activation not in (None, "silu", "swish"):
-        raise NotImplementedError("activation must be None, silu, or swish")
+    silu = _silu_flag(activation)
     if state_indices is None:
-        return native.causal_conv1d_update(x, conv_state, weight, bias, activation in ("silu", "swish"))
-    return native.causal_conv1d_update(x, conv_state, weight, bias, activation in ("silu", "swish"), state_indices=state_indices)
+        return native.causal_conv1d_update(x, conv_state, weight, bias, silu)
+    return native.causal_conv1d_update(x, conv_state, weight, bias, silu, state_indices=state_indices)
 
 
 def causal_conv1d_chunk(x, conv_state, weight, bias=None, activation=None):
@@ -141,18 +139,14 @@ def causal_conv1d_chunk(x, conv_state, weight, bias=None, activation=None):
     block of tokens. x: (batch, dim, seqlen) with stride(-1) == 1, conv_state: (batch, dim, width) -- the conv sees its last width - 1 columns
     to the left of x, and it becomes the last `width` values of concat(conv_state, x), IN PLACE --, weight: (dim, width), bias: (dim,)
     -> out (batch, dim, seqlen). Inference only."""
-    if activation not in (None, "silu", "swish"):
-        raise NotImplementedError("activation must be None, silu, or swish")
-    return native.causal_conv1d_chunk(x, conv_state, weight, bias, activation in ("silu", "swish"))
+    return native.causal_conv1d_chunk(x, conv_state, weight, bias, _silu_flag(activation))
 
 
 def causal_conv1d_chunk_torch(x, conv_state, weight, bias=None, activation=None):
     """causal_conv1d_chunk written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer): with
     v = concat(conv_state[.., 1:], x) along the sequence, out[.., t] = act(bias + sum_k weight[:, k] v[.., t + k]); conv_state receives the
     last `width` values of concat(conv_state, x). What the tests compare the kernel with; never a fallback: nothing in the package calls it."""
-    silu = {None: False, "silu": True, "swish": True}.get(activation)
-    if silu is None:
-        raise NotImplementedError(f"causal_conv1d_chunk_torch: activation {activation!r} (None, 'silu' or 'swish')")
+    silu = _silu_flag(activation, "causal_conv1d_chunk_torch")
     width, seqlen = weight.shape[-1], x.shape[-1]
     assert conv_state.shape == (*x.shape[:2], width) and weight.shape == (x.shape[1], width)
     both = torch.cat([conv_state, x], dim=-1)                                           # (batch, dim, width + seqlen)
@@ -187,9 +181,7 @@ def causal_conv1d_update_torch(x, conv_state, weight, bias=None, activation=None
             out[live] = causal_conv1d_update_torch(x[live], rows, weight, bias, activation)
             conv_state[slots] = rows
         return out
-    silu = {None: False, "silu": True, "swish": True}.get(activation)
-    if silu is None:
-        raise NotImplementedError(f"causal_conv1d_update_torch: activation {activation!r} (None, 'silu' or 'swish')")
+    silu = _silu_flag(activation, "causal_conv1d_update_torch")
     width = weight.shape[-1]
     window = torch.cat([conv_state[..., 1:], x.unsqueeze(-1)], dim=-1)                  # (batch, dim, width)
     assert window.shape == conv_state.shape and weight.shape == (x.shape[1], width)

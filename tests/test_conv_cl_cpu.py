@@ -1,12 +1,12 @@
 """The channel-last causal conv1d without a GPU: the two entries in the header, the loader and the built library, the layout of their
 parameter structs, the library's host-side refusals (they return before any launch), and the layout routing of dimsum_amd.native and
 causal_conv1d_fn, observed through stand-ins for the library calls that record the struct they are given."""
-import contextlib
 import ctypes
 
 import pytest
 import torch
 
+from test_conv_host_cpu import routed  # noqa: F401  (the recording library: a fixture both files use)
 from test_host_logic import _header_layout
 
 OK, ERR_NULL, ERR_DTYPE, ERR_SHAPE, ERR_STRIDE, ERR_ABI = 0, 1, 2, 3, 4, 7
@@ -108,44 +108,6 @@ def test_cpu_tensors_are_refused():
 # ---------------------------------------------------------------------------------------------------------------------
 # routing
 # ---------------------------------------------------------------------------------------------------------------------
-def _snapshot(P):
-    return {f: (_snapshot(getattr(P, f)) if f == "fwd" else getattr(P, f)) for f, _ in P._fields_}
-
-
-class _RecordingLib:
-    """stands in for the loaded library: every dimsum_* call records (name, the fields of its struct) and reports success"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("dimsum_"):
-            raise AttributeError(name)
-        return lambda P, stream: self.calls.append((name, _snapshot(P))) or 0
-
-
-@pytest.fixture
-def routed(monkeypatch):
-    """dimsum_amd.native on CPU tensors with the device-facing pieces replaced: -> (the recording library, the list of the
-    (shape, stride) of every non-contiguous 3-D tensor .contiguous() copied)"""
-    from dimsum_amd import _lib, native
-    lib, copies = _RecordingLib(), []
-    monkeypatch.setattr(_lib, "load", lambda: lib)
-    monkeypatch.setattr(native, "_gpu", lambda *ts: None)
-    monkeypatch.setattr(native, "_stream", lambda t: None)
-    monkeypatch.setattr(native, "_zeros", lambda n, device: torch.zeros(n))
-    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
-    plain = torch.Tensor.contiguous
-
-    def counting(self, *a, **k):
-        if self.dim() == 3 and not self.is_contiguous():
-            copies.append((tuple(self.shape), self.stride()))
-        return plain(self, *a, **k)
-
-    monkeypatch.setattr(torch.Tensor, "contiguous", counting)
-    return lib, copies
-
-
 B, D, L, W = 2, 8, 5, 4
 
 

@@ -360,12 +360,12 @@ def test_no_seq_idx_calls_native_as_before(monkeypatch):
     from dimsum_amd import native
     from dimsum_amd.modules.mamba_simple import Mamba
     calls = []
-    with cpu_oracle_backend():
+    with cpu_oracle_backend(), monkeypatch.context() as spy:      # the spies come off before the backend does: neither outlives this test
         for name in ("causal_conv1d_fwd", "causal_conv1d_bwd", "selective_scan_fwd", "selective_scan_bwd", "causal_conv1d_varlen_fwd",
                      "causal_conv1d_varlen_bwd", "selective_scan_varlen_fwd", "selective_scan_varlen_bwd", "selective_scan_general_fwd",
                      "selective_scan_general_bwd"):
             real = getattr(native, name)
-            monkeypatch.setattr(native, name, lambda *a, _n=name, _r=real, **k: calls.append((_n, len(a), tuple(sorted(k)))) or _r(*a, **k))
+            spy.setattr(native, name, lambda *a, _n=name, _r=real, **k: calls.append((_n, len(a), tuple(sorted(k)))) or _r(*a, **k))
         torch.manual_seed(0)
         m = Mamba(32, d_state=16, d_conv=4, expand=2, layer_idx=0)
         x = torch.randn(2, 12, 32, requires_grad=True)
