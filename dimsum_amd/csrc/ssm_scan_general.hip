@@ -590,11 +590,12 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
-static int gen_nb(int) { return 16; }       // states per wave: <= 4 waves up to 64 states (256 work-items: the whole register file), else <= 16
-static int gen_tile_steps(int dstate, bool cplx) { return 64 / gen_nb(dstate) / (cplx ? 2 : 1); }
+// One check (gen_check; an entry's own fields around it), one fill (gen_fill), one launch (gen_run -> gen_launch). DESIGN.md section 3.14a.
+constexpr int kGenNB = 16;                  // states per wave: <= 4 waves up to 64 states (256 work-items: the whole register file), else <= 16
+static int gen_tile_steps(bool cplx) { return 64 / kGenNB / (cplx ? 2 : 1); }
 
 static int64_t gen_ckpt_bytes(int32_t batch, int32_t dim, int32_t seqlen, int32_t dstate, int32_t n_groups, bool cplx) {
-    const int kT = gen_tile_steps(dstate, cplx);
+    const int kT = gen_tile_steps(cplx);
     const int64_t ntiles = (seqlen + kT - 1) / kT, cblocks = (dim / n_groups + 63) / 64;
     return (int64_t)batch * ntiles * dstate * (cplx ? 2 : 1) * (n_groups * cblocks * 64) * (int64_t)sizeof(float);
 }
@@ -603,108 +604,112 @@ static bool gen_shape_ok(int32_t batch, int32_t dim, int32_t seqlen, int32_t dst
     return batch >= 1 && batch <= 65535 && dim >= 1 && seqlen >= 1 && dstate >= 1 && dstate <= 256 && n_groups >= 1 && dim % n_groups == 0;
 }
 
-// the checks of both entry points, in this order: required pointers, shape, dtype, strides
-static int gen_check(const dimsum_ssm_general_params_t &p, bool forward) {
+struct gen_ids_t {                          // the seq_idx of a packed-row entry, as its struct names it
+    const void *ptr;
+    int64_t batch_stride;
+};
+
+// a (batch, seqlen) int32 row operand (seq_idx, end_slots): a batch stride that lets rows overlap
+static bool gen_row_stride_bad(int64_t batch_stride, const dimsum_ssm_general_params_t &p) { return batch_stride < 0 || (p.batch > 1 && batch_stride < p.seqlen); }
+
+// packed rows, behind the general checks: the ids (NULL, then their batch stride), then what has no kVarlen instantiation
+static int gen_varlen_check(const dimsum_ssm_general_params_t &p, const gen_ids_t &ids) {
+    if (!ids.ptr) return DIMSUM_ERR_NULL;
+    if (gen_row_stride_bad(ids.batch_stride, p)) return DIMSUM_ERR_STRIDE;
+    if (p.is_complex || !p.is_variable_B || !p.is_variable_C) return DIMSUM_ERR_UNSUPPORTED;
+    return DIMSUM_OK;
+}
+
+// THE check of every entry point, behind its own NULL / struct_size test, in this order: required pointers, shape, dtype, strides; then, where
+// the entry has ids and nothing of its own in between, gen_varlen_check
+static int gen_check(const dimsum_ssm_general_params_t &p, bool forward, const gen_ids_t *ids = nullptr) {
     if (!p.A_ptr || !p.B_ptr || !p.C_ptr || !p.u_ptr || !p.delta_ptr) return DIMSUM_ERR_NULL;
     if (forward && p.z_ptr && !p.out_z_ptr) return DIMSUM_ERR_NULL;
     if (!gen_shape_ok(p.batch, p.dim, p.seqlen, p.dstate, p.n_groups)) return DIMSUM_ERR_SHAPE;
     if (p.n_chunks != (p.seqlen + kGenChunk - 1) / kGenChunk) return DIMSUM_ERR_SHAPE;
     if (!p.is_variable_B && !p.is_variable_C && p.n_groups != 1) return DIMSUM_ERR_SHAPE;      // groups belong to input-dependent B / C
     if (p.dtype < DIMSUM_F32 || p.dtype > DIMSUM_BF16) return DIMSUM_ERR_DTYPE;
-    for (int64_t s : {p.A_d_stride, p.A_dstate_stride, p.B_batch_stride, p.B_d_stride, p.B_group_stride, p.B_dstate_stride, p.C_batch_stride, p.C_d_stride,
+    if (any_negative({p.A_d_stride, p.A_dstate_stride, p.B_batch_stride, p.B_d_stride, p.B_group_stride, p.B_dstate_stride, p.C_batch_stride, p.C_d_stride,
                       p.C_group_stride, p.C_dstate_stride, p.u_batch_stride, p.u_d_stride, p.delta_batch_stride, p.delta_d_stride, p.z_batch_stride,
-                      p.z_d_stride, p.out_batch_stride, p.out_d_stride, p.out_z_batch_stride, p.out_z_d_stride})
-        if (s < 0) return DIMSUM_ERR_STRIDE;
+                      p.z_d_stride, p.out_batch_stride, p.out_d_stride, p.out_z_batch_stride, p.out_z_d_stride}))
+        return DIMSUM_ERR_STRIDE;
     if (p.x_ptr && !aligned_to<float>(p.x_ptr, 8)) return DIMSUM_ERR_STRIDE;
-    return DIMSUM_OK;
+    return ids ? gen_varlen_check(p, *ids) : DIMSUM_OK;
 }
 
-// packed rows, behind the general checks: the ids (NULL, then a batch stride that lets rows overlap), then what has no kVarlen instantiation
-static int gen_varlen_check(const dimsum_ssm_general_params_t &p, const void *seq_idx, int64_t seq_batch_stride) {
-    if (!seq_idx) return DIMSUM_ERR_NULL;
-    if (seq_batch_stride < 0 || (p.batch > 1 && seq_batch_stride < p.seqlen)) return DIMSUM_ERR_STRIDE;
-    if (p.is_complex || !p.is_variable_B || !p.is_variable_C) return DIMSUM_ERR_UNSUPPORTED;
-    return DIMSUM_OK;
+// THE fill: the kernel argument of an entry -- zeroed, the scan's struct, the ids where it has them; what else an entry has it sets itself
+template <typename Args> static Args gen_fill(const dimsum_ssm_general_params_t &f, const gen_ids_t *ids = nullptr) {
+    Args a;
+    memset(&a, 0, sizeof(a));
+    a.f = f;
+    if (ids) a.seq_idx = reinterpret_cast<const int32_t *>(ids->ptr), a.seq_batch_stride = ids->batch_stride;
+    return a;
 }
 
-template <typename T, bool kCplx, bool kVarB, bool kVarC> static int gen_launch(const gen_args_t &a, bool forward, hipStream_t s) {
+// THE launch: kFwd / kVarlen / kEmit pick the kernel family, Args (gen_args_t; gen_emit_args_t with kEmit) is its argument. One launch shape for all.
+template <typename T, bool kCplx, bool kVarB, bool kVarC, bool kFwd, bool kVarlen, bool kEmit, typename Args> static int gen_launch(const Args &a, hipStream_t s) {
     const dimsum_ssm_general_params_t &p = a.f;
-    const int nb = gen_nb(p.dstate), W = (p.dstate + nb - 1) / nb;
-    const int kT = gen_tile_steps(p.dstate, kCplx);
+    const int W = (p.dstate + kGenNB - 1) / kGenNB, kT = gen_tile_steps(kCplx);
     const dim3 grid((unsigned)(p.n_groups * a.cblocks), (unsigned)p.batch), block((unsigned)(64 * W));
-    const size_t lds = (size_t)W * kT * 64 * sizeof(float) * (forward ? 1 : 2);
+    const size_t lds = (size_t)W * kT * 64 * sizeof(float) * (kFwd ? 1 : 2);
+    auto launch = [&](auto max_threads) {
+        constexpr int kMax = decltype(max_threads)::value;
+        if constexpr (kFwd) hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, kGenNB, kMax, kVarlen, kEmit>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, kGenNB, kMax, kVarlen>), grid, block, lds, s, a);
+    };
     // up to 64 states a workgroup is at most 4 waves, one per SIMD: the kernel may use the whole register file (512 per lane); above, up to
     // 16 waves share it (128 each)
-    const bool small = W <= 4;
-    if constexpr (!kCplx && kVarB && kVarC) {
-        if (a.seq_idx) {            // packed rows: the same launch shape on the kVarlen instantiations
-            if (forward) {
-                if (small) hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, 16, 256, true>), grid, block, lds, s, a);
-                else hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, 16, 1024, true>), grid, block, lds, s, a);
-            } else {
-                if (small) hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, 16, 256, true>), grid, block, lds, s, a);
-                else hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, 16, 1024, true>), grid, block, lds, s, a);
-            }
-            return launch_status();
-        }
-    }
-    if (a.seq_idx) return DIMSUM_ERR_UNSUPPORTED;
-    if (forward) {
-        if (small) hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, 16, 256, false>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, 16, 1024, false>), grid, block, lds, s, a);
-    } else {
-        if (small) hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, 16, 256, false>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, 16, 1024, false>), grid, block, lds, s, a);
-    }
+    if (W <= 4) launch(std::integral_constant<int, 256>{});
+    else launch(std::integral_constant<int, 1024>{});
     return launch_status();
 }
 
-template <typename T> static int gen_dispatch(const gen_args_t &a, bool forward, hipStream_t s) {
-    const bool c = a.f.is_complex != 0, vb = a.f.is_variable_B != 0, vc = a.f.is_variable_C != 0;
-#define DIMSUM_GEN_CASE(C, VB, VC) \
-    if (c == C && vb == VB && vc == VC) return gen_launch<T, C, VB, VC>(a, forward, s)
-    DIMSUM_GEN_CASE(false, true, true);
-    DIMSUM_GEN_CASE(false, true, false);
-    DIMSUM_GEN_CASE(false, false, true);
-    DIMSUM_GEN_CASE(false, false, false);
-    DIMSUM_GEN_CASE(true, true, true);
-    DIMSUM_GEN_CASE(true, true, false);
-    DIMSUM_GEN_CASE(true, false, true);
-    DIMSUM_GEN_CASE(true, false, false);
-#undef DIMSUM_GEN_CASE
-    return DIMSUM_ERR_UNSUPPORTED;
-}
-
-static int gen_run(gen_args_t &a, bool forward, hipStream_t s) {
+// THE run of every entry point, behind its checks: the padded channel counts, the element type, the (complex, varB, varC) case. Packed rows
+// (kVarlen, and kEmit on top of it) exist for real A with input-dependent B / C alone: gen_varlen_check lets nothing else through.
+template <bool kFwd, bool kVarlen, bool kEmit = false, typename Args> static int gen_run(Args &a, void *stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     a.cblocks = (a.f.dim / a.f.n_groups + 63) / 64;
     a.dpad = (int64_t)a.f.n_groups * a.cblocks * 64;
-    switch (a.f.dtype) {
-        case DIMSUM_F32: return gen_dispatch<float>(a, forward, s);
-        case DIMSUM_F16: return gen_dispatch<__half>(a, forward, s);
-        default: return gen_dispatch<__hip_bfloat16>(a, forward, s);
-    }
+    return dispatch_dtype(a.f.dtype, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (kVarlen) {
+            return gen_launch<T, false, true, true, kFwd, true, kEmit>(a, s);
+        } else {
+            const bool c = a.f.is_complex != 0, vb = a.f.is_variable_B != 0, vc = a.f.is_variable_C != 0;
+#define DIMSUM_GEN_CASE(C, VB, VC) \
+    if (c == C && vb == VB && vc == VC) return gen_launch<T, C, VB, VC, kFwd, false, false>(a, s)
+            DIMSUM_GEN_CASE(false, true, true);
+            DIMSUM_GEN_CASE(false, true, false);
+            DIMSUM_GEN_CASE(false, false, true);
+            DIMSUM_GEN_CASE(false, false, false);
+            DIMSUM_GEN_CASE(true, true, true);
+            DIMSUM_GEN_CASE(true, true, false);
+            DIMSUM_GEN_CASE(true, false, true);
+#undef DIMSUM_GEN_CASE
+            return gen_launch<T, true, false, false, kFwd, false, false>(a, s);      // the eighth of eight
+        }
+    });
 }
 
-// packed rows with per-segment states: the launch shape of the kVarlen forward on the kEmit instantiations
-template <typename T> static int gen_emit_launch(const gen_emit_args_t &e, hipStream_t s) {
-    const dimsum_ssm_general_params_t &p = e.f;
-    const int nb = gen_nb(p.dstate), W = (p.dstate + nb - 1) / nb;
-    const int kT = gen_tile_steps(p.dstate, false);
-    const dim3 grid((unsigned)(p.n_groups * e.cblocks), (unsigned)p.batch), block((unsigned)(64 * W));
-    const size_t lds = (size_t)W * kT * 64 * sizeof(float);
-    if (W <= 4) hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, false, true, true, 16, 256, true, true>), grid, block, lds, s, e);
-    else hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, false, true, true, 16, 1024, true, true>), grid, block, lds, s, e);
-    return launch_status();
-}
-
-static int gen_emit_run(gen_emit_args_t &e, hipStream_t s) {
-    e.cblocks = (e.f.dim / e.f.n_groups + 63) / 64;
-    e.dpad = (int64_t)e.f.n_groups * e.cblocks * 64;
-    switch (e.f.dtype) {
-        case DIMSUM_F32: return gen_emit_launch<float>(e, s);
-        case DIMSUM_F16: return gen_emit_launch<__half>(e, s);
-        default: return gen_emit_launch<__hip_bfloat16>(e, s);
-    }
+// the backward's checks behind NULL / struct_size and its launch; ids != NULL: packed rows
+static int gen_bwd(const dimsum_ssm_general_bwd_params_t *p, const gen_ids_t *ids, void *stream) {
+    const dimsum_ssm_general_params_t &f = p->fwd;
+    const int rc = gen_check(f, false);
+    if (rc == DIMSUM_ERR_NULL) return rc;
+    if (!p->dout_ptr || !p->dA_ptr || !p->dB_ptr || !p->dC_ptr || !p->du_ptr || !p->ddelta_ptr || !p->workspace_ptr) return DIMSUM_ERR_NULL;
+    if (f.z_ptr && (!p->dz_ptr || !f.out_ptr)) return DIMSUM_ERR_NULL;
+    if (rc != DIMSUM_OK) return rc;
+    if (any_negative({p->dout_batch_stride, p->dout_d_stride, p->dA_d_stride, p->dA_dstate_stride, p->dB_batch_stride, p->dB_d_stride, p->dB_group_stride,
+                      p->dB_dstate_stride, p->dC_batch_stride, p->dC_d_stride, p->dC_group_stride, p->dC_dstate_stride, p->du_batch_stride, p->du_d_stride,
+                      p->dz_batch_stride, p->dz_d_stride, p->ddelta_batch_stride, p->ddelta_d_stride}))
+        return DIMSUM_ERR_STRIDE;
+    if (!aligned_to<float>(p->workspace_ptr, 16)) return DIMSUM_ERR_STRIDE;
+    if (p->workspace_bytes < gen_ckpt_bytes(f.batch, f.dim, f.seqlen, f.dstate, f.n_groups, f.is_complex != 0)) return DIMSUM_ERR_SHAPE;
+    if (ids)
+        if (const int rc_ids = gen_varlen_check(f, *ids)) return rc_ids;
+    gen_args_t a = gen_fill<gen_args_t>(f, ids);
+    a.b = *p;
+    return ids ? gen_run<false, true>(a, stream) : gen_run<false, false>(a, stream);
 }
 
 }  // namespace dimsum
@@ -713,12 +718,9 @@ extern "C" int dimsum_ssm_scan_general_fwd(const dimsum_ssm_general_params_t *p,
     using namespace dimsum;
     if (!p) return DIMSUM_ERR_NULL;
     if (p->struct_size != sizeof(dimsum_ssm_general_params_t)) return DIMSUM_ERR_ABI;
-    const int rc = gen_check(*p, true);
-    if (rc != DIMSUM_OK) return rc;
-    gen_args_t a;
-    memset(&a, 0, sizeof(a));
-    a.f = *p;
-    return gen_run(a, true, reinterpret_cast<hipStream_t>(stream));
+    if (const int rc = gen_check(*p, true)) return rc;
+    gen_args_t a = gen_fill<gen_args_t>(*p);
+    return gen_run<true, false>(a, stream);
 }
 
 extern "C" int dimsum_ssm_scan_carry_fwd(const dimsum_ssm_carry_params_t *p, void *stream) {
@@ -726,22 +728,17 @@ extern "C" int dimsum_ssm_scan_carry_fwd(const dimsum_ssm_carry_params_t *p, voi
     if (!p) return DIMSUM_ERR_NULL;
     if (p->struct_size != sizeof(dimsum_ssm_carry_params_t)) return DIMSUM_ERR_ABI;
     const bool carried = p->h0_ptr || p->hT_ptr;
-    int rc = gen_check(p->scan, true);
+    const int rc = gen_check(p->scan, true);
     // gen_check stops at its first failure, in the documented order: the state's dtype belongs right after the scan's, before any stride
     if (rc != DIMSUM_OK && rc != DIMSUM_ERR_STRIDE) return rc;
     if (carried && p->state_dtype != DIMSUM_F32 && (p->scan.is_complex || p->state_dtype != p->scan.dtype)) return DIMSUM_ERR_DTYPE;
     if (rc != DIMSUM_OK) return rc;
-    for (int64_t s : {p->h0_batch_stride, p->h0_d_stride, p->h0_dstate_stride, p->hT_batch_stride, p->hT_d_stride, p->hT_dstate_stride})
-        if (carried && s < 0) return DIMSUM_ERR_STRIDE;
-    gen_args_t a;
-    memset(&a, 0, sizeof(a));
-    a.f = p->scan;
-    a.c.h0_ptr = p->h0_ptr;
-    a.c.hT_ptr = p->hT_ptr;
-    a.c.h0_batch_stride = p->h0_batch_stride, a.c.h0_d_stride = p->h0_d_stride, a.c.h0_dstate_stride = p->h0_dstate_stride;
-    a.c.hT_batch_stride = p->hT_batch_stride, a.c.hT_d_stride = p->hT_d_stride, a.c.hT_dstate_stride = p->hT_dstate_stride;
-    a.c.f32 = p->state_dtype == DIMSUM_F32;
-    return gen_run(a, true, reinterpret_cast<hipStream_t>(stream));
+    if (carried && any_negative({p->h0_batch_stride, p->h0_d_stride, p->h0_dstate_stride, p->hT_batch_stride, p->hT_d_stride, p->hT_dstate_stride}))
+        return DIMSUM_ERR_STRIDE;
+    gen_args_t a = gen_fill<gen_args_t>(p->scan);
+    a.c = {p->h0_ptr, p->hT_ptr, p->h0_batch_stride, p->h0_d_stride, p->h0_dstate_stride, p->hT_batch_stride, p->hT_d_stride, p->hT_dstate_stride,
+           p->state_dtype == DIMSUM_F32};
+    return gen_run<true, false>(a, stream);
 }
 
 extern "C" int64_t dimsum_ssm_scan_general_bwd_workspace_bytes(int32_t batch, int32_t dim, int32_t seqlen, int32_t dstate, int32_t n_groups, int32_t is_complex) {
@@ -750,60 +747,27 @@ extern "C" int64_t dimsum_ssm_scan_general_bwd_workspace_bytes(int32_t batch, in
     return gen_ckpt_bytes(batch, dim, seqlen, dstate, n_groups, is_complex != 0);
 }
 
-// the backward's checks behind NULL / struct_size and its launch; seq_idx != NULL: packed rows
-static int dimsum_gen_bwd_run(const dimsum_ssm_general_bwd_params_t *p, const void *seq_idx, int64_t seq_batch_stride, bool varlen, void *stream) {
-    using namespace dimsum;
-    const dimsum_ssm_general_params_t &f = p->fwd;
-    int rc = gen_check(f, false);
-    if (rc == DIMSUM_ERR_NULL) return rc;
-    if (!p->dout_ptr || !p->dA_ptr || !p->dB_ptr || !p->dC_ptr || !p->du_ptr || !p->ddelta_ptr || !p->workspace_ptr) return DIMSUM_ERR_NULL;
-    if (f.z_ptr && (!p->dz_ptr || !f.out_ptr)) return DIMSUM_ERR_NULL;
-    if (rc != DIMSUM_OK) return rc;
-    for (int64_t s : {p->dout_batch_stride, p->dout_d_stride, p->dA_d_stride, p->dA_dstate_stride, p->dB_batch_stride, p->dB_d_stride, p->dB_group_stride,
-                      p->dB_dstate_stride, p->dC_batch_stride, p->dC_d_stride, p->dC_group_stride, p->dC_dstate_stride, p->du_batch_stride, p->du_d_stride,
-                      p->dz_batch_stride, p->dz_d_stride, p->ddelta_batch_stride, p->ddelta_d_stride})
-        if (s < 0) return DIMSUM_ERR_STRIDE;
-    if (!aligned_to<float>(p->workspace_ptr, 16)) return DIMSUM_ERR_STRIDE;
-    if (p->workspace_bytes < gen_ckpt_bytes(f.batch, f.dim, f.seqlen, f.dstate, f.n_groups, f.is_complex != 0)) return DIMSUM_ERR_SHAPE;
-    if (varlen) {
-        rc = gen_varlen_check(f, seq_idx, seq_batch_stride);
-        if (rc != DIMSUM_OK) return rc;
-    }
-    gen_args_t a;
-    memset(&a, 0, sizeof(a));
-    a.f = f;
-    a.b = *p;
-    a.seq_idx = reinterpret_cast<const int32_t *>(seq_idx);
-    a.seq_batch_stride = seq_batch_stride;
-    return gen_run(a, false, reinterpret_cast<hipStream_t>(stream));
-}
-
 extern "C" int dimsum_ssm_scan_general_bwd(const dimsum_ssm_general_bwd_params_t *p, void *stream) {
     if (!p) return DIMSUM_ERR_NULL;
     if (p->struct_size != sizeof(dimsum_ssm_general_bwd_params_t)) return DIMSUM_ERR_ABI;
-    return dimsum_gen_bwd_run(p, nullptr, 0, false, stream);
+    return dimsum::gen_bwd(p, nullptr, stream);
 }
 
 extern "C" int dimsum_ssm_scan_varlen_bwd(const dimsum_ssm_varlen_bwd_params_t *p, void *stream) {
     if (!p) return DIMSUM_ERR_NULL;
     if (p->struct_size != sizeof(dimsum_ssm_varlen_bwd_params_t)) return DIMSUM_ERR_ABI;
-    return dimsum_gen_bwd_run(&p->bwd, p->seq_idx_ptr, p->seq_idx_batch_stride, true, stream);
+    const dimsum::gen_ids_t ids{p->seq_idx_ptr, p->seq_idx_batch_stride};
+    return dimsum::gen_bwd(&p->bwd, &ids, stream);
 }
 
 extern "C" int dimsum_ssm_scan_varlen_fwd(const dimsum_ssm_varlen_params_t *p, void *stream) {
     using namespace dimsum;
     if (!p) return DIMSUM_ERR_NULL;
     if (p->struct_size != sizeof(dimsum_ssm_varlen_params_t)) return DIMSUM_ERR_ABI;
-    int rc = gen_check(p->scan, true);
-    if (rc != DIMSUM_OK) return rc;
-    rc = gen_varlen_check(p->scan, p->seq_idx_ptr, p->seq_idx_batch_stride);
-    if (rc != DIMSUM_OK) return rc;
-    gen_args_t a;
-    memset(&a, 0, sizeof(a));
-    a.f = p->scan;
-    a.seq_idx = reinterpret_cast<const int32_t *>(p->seq_idx_ptr);
-    a.seq_batch_stride = p->seq_idx_batch_stride;
-    return gen_run(a, true, reinterpret_cast<hipStream_t>(stream));
+    const gen_ids_t ids{p->seq_idx_ptr, p->seq_idx_batch_stride};
+    if (const int rc = gen_check(p->scan, true, &ids)) return rc;
+    gen_args_t a = gen_fill<gen_args_t>(p->scan, &ids);
+    return gen_run<true, true>(a, stream);
 }
 
 extern "C" int dimsum_ssm_scan_varlen_states_fwd(const dimsum_ssm_varlen_states_params_t *p, void *stream) {
@@ -813,21 +777,14 @@ extern "C" int dimsum_ssm_scan_varlen_states_fwd(const dimsum_ssm_varlen_states_
     if (p->num_slots < 1) return DIMSUM_ERR_SHAPE;
     if (!p->end_slots_ptr || !p->state_ptr) return DIMSUM_ERR_NULL;
     const dimsum_ssm_general_params_t &f = p->varlen.scan;
-    if (p->end_slots_batch_stride < 0 || (f.batch > 1 && p->end_slots_batch_stride < f.seqlen)) return DIMSUM_ERR_STRIDE;
-    if (p->state_slot_stride < 0 || p->state_d_stride < 0 || p->state_dstate_stride < 0) return DIMSUM_ERR_STRIDE;
-    int rc = gen_check(f, true);
-    if (rc != DIMSUM_OK) return rc;
-    rc = gen_varlen_check(f, p->varlen.seq_idx_ptr, p->varlen.seq_idx_batch_stride);
-    if (rc != DIMSUM_OK) return rc;
-    gen_emit_args_t e;
-    memset(&e, 0, sizeof(e));
-    e.f = f;
-    e.seq_idx = reinterpret_cast<const int32_t *>(p->varlen.seq_idx_ptr);
-    e.seq_batch_stride = p->varlen.seq_idx_batch_stride;
+    if (gen_row_stride_bad(p->end_slots_batch_stride, f) || any_negative({p->state_slot_stride, p->state_d_stride, p->state_dstate_stride})) return DIMSUM_ERR_STRIDE;
+    const gen_ids_t ids{p->varlen.seq_idx_ptr, p->varlen.seq_idx_batch_stride};
+    if (const int rc = gen_check(f, true, &ids)) return rc;
+    gen_emit_args_t e = gen_fill<gen_emit_args_t>(f, &ids);
     e.end_slots = reinterpret_cast<const int32_t *>(p->end_slots_ptr);
     e.end_batch_stride = p->end_slots_batch_stride;
     e.pool = p->state_ptr;
     e.pool_slot_stride = p->state_slot_stride, e.pool_d_stride = p->state_d_stride, e.pool_dstate_stride = p->state_dstate_stride;
     e.pool_f32 = p->state_f32 != 0 || f.dtype == DIMSUM_F32;
-    return gen_emit_run(e, reinterpret_cast<hipStream_t>(stream));
+    return gen_run<true, true, true>(e, stream);
 }

@@ -1087,6 +1087,18 @@ def _check_ssm_general(u, delta, A, B, C, D, z, delta_bias):
     return cplx, var[0], var[1], groups
 
 
+def _fill_bc_strides(P, name, t, var):
+    """the stride fields of B / C / dB / dC: input-dependent (batch, groups, dstate, seqlen) -> batch / group / dstate, constant (dim, dstate) -> d / dstate"""
+    for axis, stride in zip(("batch", "group", "dstate") if var else ("d", "dstate"), t.stride()):
+        setattr(P, f"{name}_{axis}_stride", stride)
+
+
+def _scan_launch(entry, P, u):
+    """the general scan's launch: the library's dimsum_ssm_scan_<entry> on the current stream of u's device"""
+    with torch.cuda.device(u.device):
+        _lib.check(getattr(_lib.load(), "dimsum_ssm_scan_" + entry)(P, _stream(u)), "selective_scan_" + entry)
+
+
 def _fill_ssm_general(P, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags):
     cplx, var_B, var_C, groups = flags
     batch, dim, seqlen = u.shape
@@ -1094,11 +1106,7 @@ def _fill_ssm_general(P, u, delta, A, B, C, D, z, delta_bias, delta_softplus, ou
     P.delta_softplus, P.dtype = int(bool(delta_softplus)), _DT[u.dtype]
     P.is_variable_B, P.is_variable_C, P.is_complex = int(var_B), int(var_C), int(cplx)
     P.A_d_stride, P.A_dstate_stride = A.stride(0), A.stride(1)
-    for t, name, var in ((B, "B", var_B), (C, "C", var_C)):
-        if var:
-            setattr(P, name + "_batch_stride", t.stride(0)), setattr(P, name + "_group_stride", t.stride(1)), setattr(P, name + "_dstate_stride", t.stride(2))
-        else:
-            setattr(P, name + "_d_stride", t.stride(0)), setattr(P, name + "_dstate_stride", t.stride(1))
+    _fill_bc_strides(P, "B", B, var_B), _fill_bc_strides(P, "C", C, var_C)
     P.u_batch_stride, P.u_d_stride = u.stride(0), u.stride(1)
     P.delta_batch_stride, P.delta_d_stride = delta.stride(0), delta.stride(1)
     if z is not None:
@@ -1126,7 +1134,7 @@ def selective_scan_varlen_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplu
     """selective_scan_general_fwd on packed rows: seq_idx (batch, seqlen) int32, the state restarts at every position whose id differs from
     the one before it. x[:, :, -1, 1::2] is the state of the row's last segment. Real A, input-dependent B / C, any dstate in 1..256."""
     _check(seq_idx is not None, "selective_scan_varlen_fwd: seq_idx is required")
-    return selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=need_out, need_x=need_x, seq_idx=seq_idx)
+    return _scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out, need_x, seq_idx=seq_idx)
 
 
 def selective_scan_varlen_states_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, seq_idx, end_slots, ssm_state, need_out=True, need_x=True):
@@ -1141,14 +1149,13 @@ def selective_scan_varlen_states_fwd(u, delta, A, B, C, D, z, delta_bias, delta_
     _check(torch.is_tensor(ssm_state) and ssm_state.dim() == 3 and ssm_state.shape[0] >= 1 and tuple(ssm_state.shape[1:]) == (u.shape[1], A.shape[1]),
            f"{who}: ssm_state must be a pool (num_slots >= 1, dim, dstate)")
     _check(ssm_state.dtype in (torch.float32, u.dtype), f"{who}: ssm_state must be float32 or of u's dtype {u.dtype}, got {ssm_state.dtype}")
-    return selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=need_out, need_x=need_x, seq_idx=seq_idx,
-                                      end_slots=end_slots, ssm_state=ssm_state)
+    return _scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out, need_x, seq_idx=seq_idx, end_slots=end_slots, ssm_state=ssm_state)
 
 
 def selective_scan_varlen_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, seq_idx, dB=None, dC=None):
     """selective_scan_general_bwd on packed rows: the adjoint state is not handed across a boundary and the terms through a_t h_{t-1} vanish there"""
     _check(seq_idx is not None, "selective_scan_varlen_bwd: seq_idx is required")
-    return selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, dB=dB, dC=dC, seq_idx=seq_idx)
+    return _scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, dB, dC, seq_idx=seq_idx)
 
 
 def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=True, need_x=True, *, seq_idx=None, end_slots=None,
@@ -1156,7 +1163,8 @@ def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softpl
     """-> [out, x, (out_z)] like selective_scan_cuda.fwd, on the general kernels: A float32 or complex64 (dim, dstate), dstate 1..256; B / C
     input-dependent (batch, groups, dstate, seqlen) -- (.., 2 seqlen) reals with complex A -- or constant (dim, dstate) of A's dtype.
     x is (batch, dim, n_chunks, 2 dstate) of A's dtype. None of the inference extras of selective_scan_fwd.
-    seq_idx: selective_scan_varlen_fwd's (packed rows); end_slots / ssm_state: selective_scan_varlen_states_fwd's, which checks them."""
+    seq_idx: selective_scan_varlen_fwd's (packed rows); end_slots / ssm_state: selective_scan_varlen_states_fwd's, which checks them.
+    One struct per variant, each holding the one before it; _fill_ssm_general fills the innermost."""
     flags = _check_ssm_general(u, delta, A, B, C, D, z, delta_bias)
     if seq_idx is not None:
         _check_scan_seq_idx(seq_idx, u, flags, "selective_scan_varlen_fwd")
@@ -1168,26 +1176,19 @@ def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softpl
     out = torch.empty_like(delta) if need_out else None
     x = torch.empty((batch, dim, (seqlen + 2047) // 2048, dstate * 2), device=u.device, dtype=A.dtype) if need_x else None
     out_z = torch.empty_like(z) if z is not None else None
-    if u.numel() > 0 and end_slots is not None:
-        E = _lib.SsmVarlenStatesParams()
-        _fill_ssm_general(E.varlen.scan, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags)
-        E.varlen.seq_idx_ptr, E.varlen.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
-        E.num_slots, E.end_slots_ptr, E.end_slots_batch_stride = ssm_state.shape[0], _ptr(end_slots), end_slots.stride(0)
-        E.state_ptr, E.state_f32 = _ptr(ssm_state), int(ssm_state.dtype == torch.float32)
-        E.state_slot_stride, E.state_d_stride, E.state_dstate_stride = ssm_state.stride()
-        with torch.cuda.device(u.device):
-            _lib.check(_lib.load().dimsum_ssm_scan_varlen_states_fwd(E, _stream(u)), "selective_scan_varlen_states_fwd")
-    elif u.numel() > 0 and seq_idx is not None:
-        V = _lib.SsmVarlenParams()
-        _fill_ssm_general(V.scan, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags)
-        V.seq_idx_ptr, V.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
-        with torch.cuda.device(u.device):
-            _lib.check(_lib.load().dimsum_ssm_scan_varlen_fwd(V, _stream(u)), "selective_scan_varlen_fwd")
-    elif u.numel() > 0:
-        P = _lib.SsmGeneralParams()
-        _fill_ssm_general(P, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags)
-        with torch.cuda.device(u.device):
-            _lib.check(_lib.load().dimsum_ssm_scan_general_fwd(P, _stream(u)), "selective_scan_general_fwd")
+    if u.numel() > 0:
+        if end_slots is not None:
+            entry, P = "varlen_states_fwd", _lib.SsmVarlenStatesParams()
+            P.num_slots, P.end_slots_ptr, P.end_slots_batch_stride = ssm_state.shape[0], _ptr(end_slots), end_slots.stride(0)
+            P.state_ptr, P.state_f32 = _ptr(ssm_state), int(ssm_state.dtype == torch.float32)
+            P.state_slot_stride, P.state_d_stride, P.state_dstate_stride = ssm_state.stride()
+        else:
+            entry, P = ("varlen_fwd", _lib.SsmVarlenParams()) if seq_idx is not None else ("general_fwd", _lib.SsmGeneralParams())
+        V = P.varlen if end_slots is not None else P              # with packed rows: the struct that holds the ids and the scan
+        if seq_idx is not None:
+            V.seq_idx_ptr, V.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
+        _fill_ssm_general(V.scan if seq_idx is not None else P, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags)
+        _scan_launch(entry, P, u)
     return [out, x] + ([out_z] if z is not None else [])
 
 
@@ -1227,15 +1228,15 @@ def selective_scan_carry_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus
     if final_state is not None:
         P.hT_batch_stride, P.hT_d_stride, P.hT_dstate_stride = final_state.stride()
     P.h0_ptr, P.hT_ptr = _ptr(initial_state), _ptr(final_state)
-    with torch.cuda.device(u.device):
-        _lib.check(_lib.load().dimsum_ssm_scan_carry_fwd(P, _stream(u)), "selective_scan_carry_fwd")
+    _scan_launch("carry_fwd", P, u)
     return out_z if z is not None else out
 
 
 def selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, dB=None, dC=None, *, seq_idx=None):
     """-> [du, ddelta, dA, dB, dC, dD, ddelta_bias, (dz)] like selective_scan_cuda.bwd (without recompute_out_z), on the general kernels.
     dA / constant dB / dC come back in A's dtype, input-dependent dB / dC in B's / C's; a caller may hand in fp32 buffers of B's / C's shape
-    (unit stride along the sequence) for input-dependent dB / dC: they are zero-filled here (the kernel adds into them) and returned as they are."""
+    (unit stride along the sequence) for input-dependent dB / dC: they are zero-filled here (the kernel adds into them) and returned as they are.
+    seq_idx: selective_scan_varlen_bwd's (packed rows), whose struct holds the plain one."""
     flags = _check_ssm_general(u, delta, A, B, C, D, z, delta_bias)
     cplx, var_B, var_C, groups = flags
     if seq_idx is not None:
@@ -1264,16 +1265,14 @@ def selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, d
     dD = torch.zeros_like(D) if D is not None else None
     ddelta_bias = torch.zeros_like(delta_bias) if delta_bias is not None else None
     if u.numel() > 0:
-        V = _lib.SsmVarlenBwdParams() if seq_idx is not None else None
-        Q = V.bwd if V is not None else _lib.SsmGeneralBwdParams()
+        entry, P = ("varlen_bwd", _lib.SsmVarlenBwdParams()) if seq_idx is not None else ("general_bwd", _lib.SsmGeneralBwdParams())
+        Q = P.bwd if seq_idx is not None else P
+        if seq_idx is not None:
+            P.seq_idx_ptr, P.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
         _fill_ssm_general(Q.fwd, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out if z is not None else None, None, None, flags)
         Q.dout_batch_stride, Q.dout_d_stride = dout.stride(0), dout.stride(1)
         Q.dA_d_stride, Q.dA_dstate_stride = dA.stride(0), dA.stride(1)
-        for t, name, var in ((dB, "dB", var_B), (dC, "dC", var_C)):
-            if var:
-                setattr(Q, name + "_batch_stride", t.stride(0)), setattr(Q, name + "_group_stride", t.stride(1)), setattr(Q, name + "_dstate_stride", t.stride(2))
-            else:
-                setattr(Q, name + "_d_stride", t.stride(0)), setattr(Q, name + "_dstate_stride", t.stride(1))
+        _fill_bc_strides(Q, "dB", dB, var_B), _fill_bc_strides(Q, "dC", dC, var_C)
         Q.du_batch_stride, Q.du_d_stride = du.stride(0), du.stride(1)
         Q.ddelta_batch_stride, Q.ddelta_d_stride = ddelta.stride(0), ddelta.stride(1)
         if dz is not None:
@@ -1283,17 +1282,16 @@ def selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, d
         nbytes = _lib.load().dimsum_ssm_scan_general_bwd_workspace_bytes(batch, dim, seqlen, dstate, groups, int(cplx))
         ws = torch.empty((nbytes + 3) // 4, device=u.device, dtype=torch.float32)
         Q.workspace_ptr, Q.workspace_bytes = _ptr(ws), nbytes
-        with torch.cuda.device(u.device):
-            if V is not None:
-                V.seq_idx_ptr, V.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
-                _lib.check(_lib.load().dimsum_ssm_scan_varlen_bwd(V, _stream(u)), "selective_scan_varlen_bwd")
-            else:
-                _lib.check(_lib.load().dimsum_ssm_scan_general_bwd(Q, _stream(u)), "selective_scan_general_bwd")
+        _scan_launch(entry, P, u)
         del ws
     res = [du, ddelta, dA, dB.to(B.dtype) if var_B and own[0] else dB, dC.to(C.dtype) if var_C and own[1] else dC, dD, ddelta_bias]
     if z is not None:
         res.append(dz)
     return res
+
+
+# what the named wrappers enter: the two bodies themselves, so that a stand-in for a public name never reroutes another public function
+_scan_general_fwd, _scan_general_bwd = selective_scan_general_fwd, selective_scan_general_bwd
 
 
 # ---------------------------------------------------------------------------------------------------------------------

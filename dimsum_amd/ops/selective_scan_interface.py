@@ -45,24 +45,31 @@ def _last_contig(t):
     return t if t is None or t.stride(-1) == 1 else t.contiguous()
 
 
+def _scan_operands(u, delta, B, C, D, z):
+    """the operands as every route of selective_scan_fn hands them to native: unit stride along the sequence, four-dim B / C, a dense D
+    -> (u, delta, B, C, D, z, B was three-dim, C was three-dim)"""
+    u, delta, B, C, z = (_last_contig(t) for t in (u, delta, B, C, z))
+    squeeze_B, squeeze_C = B.dim() == 3, C.dim() == 3
+    return (u, delta, B.unsqueeze(1) if squeeze_B else B, C.unsqueeze(1) if squeeze_C else C, D.contiguous() if D is not None else None, z,
+            squeeze_B, squeeze_C)
+
+
+def _scan_grads(ctx, du, ddelta, dA, dB, dC, dD, ddelta_bias, *rest):
+    """native's backward list -> the gradients of forward's eleven arguments: dB / dC in the caller's rank, nothing for an absent D / z /
+    delta_bias nor for the three arguments that are no tensors"""
+    return (du, ddelta, dA, dB.squeeze(1) if ctx.squeeze_B else dB, dC.squeeze(1) if ctx.squeeze_C else dC, dD if ctx.has_D else None,
+            rest[0] if ctx.has_z else None, ddelta_bias if ctx.has_bias else None, None, None, None)
+
+
 class SelectiveScanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False,
                 need_ckpt=False):
-        u, delta, B, C, z = (_last_contig(t) for t in (u, delta, B, C, z))
-        D = D.contiguous() if D is not None else None
-        var_B, var_C = B.dim() >= 3, C.dim() >= 3
-        ctx.squeeze_B, ctx.squeeze_C = B.dim() == 3, C.dim() == 3
-        if ctx.squeeze_B:
-            B = B.unsqueeze(1)
-        if ctx.squeeze_C:
-            C = C.unsqueeze(1)
-        ctx.delta_softplus = delta_softplus
-        ctx.has_z = z is not None
-        ctx.has_D, ctx.has_bias = D is not None, delta_bias is not None
+        u, delta, B, C, D, z, ctx.squeeze_B, ctx.squeeze_C = _scan_operands(u, delta, B, C, D, z)
+        ctx.delta_softplus, ctx.has_z, ctx.has_D, ctx.has_bias = delta_softplus, z is not None, D is not None, delta_bias is not None
         # the general kernels (csrc/ssm_scan_general.hip) serve what the tuned ones are not built for: constant B / C, complex A, other dstates
         # (GPU tensors only: anything else keeps going to native.selective_scan_fwd, which refuses it -- or to what stands in for it in tests)
-        ctx.general = u.is_cuda and native.scan_takes_general_path(A.shape[-1], A.is_complex(), var_B, var_C, force=native.scan_general_forced())
+        ctx.general = u.is_cuda and native.scan_takes_general_path(A.shape[-1], A.is_complex(), B.dim() >= 3, C.dim() >= 3, force=native.scan_general_forced())
         if ctx.general:
             out, x, *rest = native.selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus)
             ckpt = None
@@ -81,15 +88,8 @@ class SelectiveScanFn(torch.autograd.Function):
         u, delta, A, B, C, D, z, delta_bias, x, out, ckpt = ctx.saved_tensors
         dout = _last_contig(dout)
         if ctx.general:
-            du, ddelta, dA, dB, dC, dD, ddelta_bias, *rest = native.selective_scan_general_bwd(
-                u, delta, A, B, C, D, z, delta_bias, dout, out, None, ctx.delta_softplus)
-        else:
-            du, ddelta, dA, dB, dC, dD, ddelta_bias, *rest = native.selective_scan_bwd(
-                u, delta, A, B, C, D, z, delta_bias, dout, x, out, None, ctx.delta_softplus, False, ckpt=ckpt)
-        dz = rest[0] if ctx.has_z else None
-        dB = dB.squeeze(1) if ctx.squeeze_B else dB
-        dC = dC.squeeze(1) if ctx.squeeze_C else dC
-        return (du, ddelta, dA, dB, dC, dD if ctx.has_D else None, dz, ddelta_bias if ctx.has_bias else None, None, None, None)
+            return _scan_grads(ctx, *native.selective_scan_general_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, None, ctx.delta_softplus))
+        return _scan_grads(ctx, *native.selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, out, None, ctx.delta_softplus, False, ckpt=ckpt))
 
 
 class SelectiveScanVarlenFn(torch.autograd.Function):
@@ -97,11 +97,7 @@ class SelectiveScanVarlenFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, seq_idx):
-        u, delta, B, C, z = (_last_contig(t) for t in (u, delta, B, C, z))
-        D = D.contiguous() if D is not None else None
-        ctx.squeeze_B, ctx.squeeze_C = B.dim() == 3, C.dim() == 3
-        B = B.unsqueeze(1) if ctx.squeeze_B else B
-        C = C.unsqueeze(1) if ctx.squeeze_C else C
+        u, delta, B, C, D, z, ctx.squeeze_B, ctx.squeeze_C = _scan_operands(u, delta, B, C, D, z)
         ctx.delta_softplus, ctx.has_z, ctx.has_D, ctx.has_bias = delta_softplus, z is not None, D is not None, delta_bias is not None
         out, x, *rest = native.selective_scan_varlen_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, seq_idx)
         ctx.save_for_backward(u, delta, A, B, C, D, z, delta_bias, out if ctx.has_z else None, seq_idx)
@@ -111,12 +107,8 @@ class SelectiveScanVarlenFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, *args):
         u, delta, A, B, C, D, z, delta_bias, out, seq_idx = ctx.saved_tensors
-        du, ddelta, dA, dB, dC, dD, ddelta_bias, *rest = native.selective_scan_varlen_bwd(
-            u, delta, A, B, C, D, z, delta_bias, _last_contig(dout), out, None, ctx.delta_softplus, seq_idx)
-        dB = dB.squeeze(1) if ctx.squeeze_B else dB
-        dC = dC.squeeze(1) if ctx.squeeze_C else dC
-        return (du, ddelta, dA, dB, dC, dD if ctx.has_D else None, rest[0] if ctx.has_z else None, ddelta_bias if ctx.has_bias else None,
-                None, None, None)
+        return _scan_grads(ctx, *native.selective_scan_varlen_bwd(u, delta, A, B, C, D, z, delta_bias, _last_contig(dout), out, None, ctx.delta_softplus,
+                                                                  seq_idx))
 
 
 def _refuse_varlen_scan(who, A, B, C):
@@ -141,11 +133,9 @@ def _selective_scan_varlen_states(u, delta, A, B, C, D, z, delta_bias, delta_sof
         raise NotImplementedError("selective_scan_fn: end_slots / ssm_state are inference arguments -- the scan that stores per-segment states "
                                   "has no backward; call it under torch.no_grad() or on inputs that do not require grad")
     with torch.no_grad():
-        u, delta, B, C, z = (_last_contig(t) for t in (u, delta, B, C, z))
-        B = B.unsqueeze(1) if B.dim() == 3 else B
-        C = C.unsqueeze(1) if C.dim() == 3 else C
-        out, x, *rest = native.selective_scan_varlen_states_fwd(u, delta, A, B, C, D.contiguous() if D is not None else None, z, delta_bias,
-                                                                delta_softplus, seq_idx, end_slots, ssm_state, need_x=return_last_state)
+        u, delta, B, C, D, z, _, _ = _scan_operands(u, delta, B, C, D, z)
+        out, x, *rest = native.selective_scan_varlen_states_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, seq_idx, end_slots, ssm_state,
+                                                                need_x=return_last_state)
     res = rest[0] if z is not None else out
     return res if not return_last_state else (res, x[:, :, -1, 1::2])
 
@@ -200,12 +190,9 @@ def _selective_scan_carry(u, delta, A, B, C, D, z, delta_bias, delta_softplus, r
         raise NotImplementedError("selective_scan_fn: a carried state (initial_state) is an inference argument -- the scan that starts from it has "
                                   "no backward; call it under torch.no_grad() or on inputs that do not require grad")
     with torch.no_grad():
-        u, delta, B, C, z = (_last_contig(t) for t in (u, delta, B, C, z))
-        B = B.unsqueeze(1) if B.dim() == 3 else B
-        C = C.unsqueeze(1) if C.dim() == 3 else C
+        u, delta, B, C, D, z, _, _ = _scan_operands(u, delta, B, C, D, z)
         last = torch.empty_like(initial_state) if return_last_state else None
-        out = native.selective_scan_carry_fwd(u, delta, A, B, C, D.contiguous() if D is not None else None, z, delta_bias, delta_softplus,
-                                              initial_state, last)
+        out = native.selective_scan_carry_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, initial_state, last)
     return out if not return_last_state else (out, last)
 
 
