@@ -465,8 +465,9 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const
                     // y = 2 Re(C h): g = 2 conj(C) dy + carry;  dC = 2 conj(h) dy
                     const float gr = fmaf(2.f * cr, dy[i], gc[2 * j]), gi = fmaf(-2.f * ci, dy[i], gc[2 * j + 1]);
                     const float dcr = 2.f * hr * dy[i], dci = -2.f * hi * dy[i];
-                    // a h_{t-1} = h_t - dt u B
-                    const float ahr = fmaf(-dtu, br, hr), ahi = fmaf(-dtu, bi, hi);
+                    // a h_{t-1} = h_t - dt u B; at the row's first step h_{-1} = 0: 0 by definition, not the rounding of dt u B left by the difference
+                    const bool first = t0 + i == 0;
+                    const float ahr = first ? 0.f : fmaf(-dtu, br, hr), ahi = first ? 0.f : fmaf(-dtu, bi, hi);
                     // conj(B) g, conj(a h_{t-1}) g
                     const float bgr = br * gr + bi * gi;
                     const float qr = ahr * gr + ahi * gi, qi = ahr * gi - ahi * gr;
@@ -496,7 +497,8 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_bwd_kernel(const
                     const float bv = kVarB ? lane_value(bt, j * kRow + i) : Bc[j], cv = kVarC ? lane_value(ct, j * kRow + i) : Cc[j];
                     const float hv = hs[i][j];
                     const float g = fmaf(cv, dy[i], gc[j]);
-                    const bool rst = kVarlen && ((rm >> i) & 1u);            // a boundary: a_t h_{t-1} is 0 by definition, not by cancellation
+                    // a boundary, or the row's first step (h_{-1} = 0): a_t h_{t-1} is 0 by definition, not by cancellation
+                    const bool rst = (kVarlen && ((rm >> i) & 1u)) || t0 + i == 0;
                     const float ah = rst ? 0.f : fmaf(-dtu, bv, hv);
                     const float bg = bv * g, qg = ah * g;
                     du[i] = fmaf(dt[i], bg, du[i]);

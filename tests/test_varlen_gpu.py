@@ -257,7 +257,7 @@ def test_later_segments_do_not_see_the_first_one():
     def later(t):
         return [t[r, ..., e:] for r, e in enumerate(first)]
 
-    for dim, N in ((72, 16), (64, 64), (64, 5)):
+    for dim, N in ((72, 16), (64, 64), (64, 5), (72, 72)):                  # 72 states: the 1024-work-item builds, a half-empty fifth wave
         c, dout = scan_case(seq, dim, N, seed=dim + N)
         runs = []
         for big in (False, True):
