@@ -121,6 +121,14 @@ class SsmVarlenStatesParams(_Sized):
                 + [("state_f32", i32), ("reserved", i32)])
 
 
+class SsmVarlenResumeParams(_Sized):
+    """dimsum_ssm_varlen_resume_params_t: SsmVarlenStatesParams + start_slots (batch, seqlen) int32 -- where it is >= 0 (a segment's first
+    position) the segment continues that row of a (n_init, dim, dstate) tensor of states, which may be the pool itself"""
+    _fields_ = ([("struct_size", u32), ("n_init", i32), ("states", SsmVarlenStatesParams), ("start_slots_ptr", vp), ("start_slots_batch_stride", i64),
+                 ("init_ptr", vp)] + [(n, i64) for n in ("init_slot_stride", "init_d_stride", "init_dstate_stride")]
+                + [("init_f32", i32), ("reserved", i32)])
+
+
 class OptimParams(_Sized):
     """dimsum_optim_params_t: device tables of the tensor list + hyper-parameters of one clip / AdamW / EMA step"""
     _fields_ = ([("struct_size", u32), ("n_tensors", i32), ("n_chunks", i32), ("n_partials", i32)]
@@ -216,6 +224,14 @@ class ConvVarlenStatesParams(_Sized):
     _fields_ = ([("struct_size", u32), ("num_slots", i32), ("varlen", ConvVarlenParams), ("end_slots_ptr", vp), ("end_slots_batch_stride", i64),
                  ("state_ptr", vp)] + [(n, i64) for n in ("state_slot_stride", "state_c_stride", "state_w_stride")]
                 + [("state_dtype", i32), ("reserved", i32)])
+
+
+class ConvVarlenResumeParams(_Sized):
+    """dimsum_conv_varlen_resume_params_t: ConvVarlenStatesParams + start_slots (batch, seqlen) int32 -- where it is >= 0 (a segment's first
+    position) the taps that reach before the segment read that row of a (n_init, dim, width) tensor of conv states of x's dtype"""
+    _fields_ = ([("struct_size", u32), ("n_init", i32), ("states", ConvVarlenStatesParams), ("start_slots_ptr", vp), ("start_slots_batch_stride", i64),
+                 ("init_ptr", vp)] + [(n, i64) for n in ("init_slot_stride", "init_c_stride", "init_w_stride")]
+                + [("init_dtype", i32), ("reserved", i32)])
 
 
 class ConvClParams(_Sized):
@@ -469,6 +485,7 @@ EXPORTS = (
     "dimsum_ssm_scan_carry_fwd", "dimsum_causal_conv1d_chunk",
     "dimsum_causal_conv1d_varlen_fwd", "dimsum_causal_conv1d_varlen_bwd", "dimsum_ssm_scan_varlen_fwd", "dimsum_ssm_scan_varlen_bwd",
     "dimsum_causal_conv1d_varlen_states_fwd", "dimsum_ssm_scan_varlen_states_fwd",
+    "dimsum_causal_conv1d_varlen_resume_fwd", "dimsum_ssm_scan_varlen_resume_fwd",
     "dimsum_optim_grad_sumsq", "dimsum_optim_adamw_ema_step", "dimsum_optim_write_ptrs",
     "dimsum_fm_plan", "dimsum_fm_loss_fwd", "dimsum_fm_loss_bwd",
     "dimsum_pos_rope", "dimsum_pos_cpe_fwd", "dimsum_pos_cpe_bwd",
@@ -516,7 +533,8 @@ _SIGNATURES = (
         ("dimsum_ssm_scan_varlen_fwd", SsmVarlenParams), ("dimsum_ssm_scan_varlen_bwd", SsmVarlenBwdParams),
         ("dimsum_causal_conv1d_update_slots", ConvUpdateSlotsParams), ("dimsum_selective_state_update_slots", StateUpdateSlotsParams),
         ("dimsum_decode_linear_slots", DecodeLinearSlotsParams),
-        ("dimsum_causal_conv1d_varlen_states_fwd", ConvVarlenStatesParams), ("dimsum_ssm_scan_varlen_states_fwd", SsmVarlenStatesParams))]
+        ("dimsum_causal_conv1d_varlen_states_fwd", ConvVarlenStatesParams), ("dimsum_ssm_scan_varlen_states_fwd", SsmVarlenStatesParams),
+        ("dimsum_causal_conv1d_varlen_resume_fwd", ConvVarlenResumeParams), ("dimsum_ssm_scan_varlen_resume_fwd", SsmVarlenResumeParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream
     + [(name, C.c_int, [vp] * nptr + [i64, i64, vp]) for name, nptr in (
         ("dimsum_gated_gelu_fwd", 3), ("dimsum_gated_gelu_bwd", 5), ("dimsum_gated_gelu_fwd_split3", 3), ("dimsum_gated_gelu_bwd_split3", 5),

@@ -25,6 +25,14 @@
 // x[t] last (the layout causal_conv1d_update shifts). The values are the loaded x elements: widened to fp32 on the load and narrowed back
 // on the store, which is the identity on every T. A row the kernel clamped onto the last one stores nothing. kEmit = false compiles to the
 // kernels as they were.
+//
+// Resumed segments (dimsum_causal_conv1d_varlen_resume_fwd, kStart on top of kEmit, forward only): a third int32 row, start_slots, travels as
+// the ids do (16 bytes per lane, the halo from the neighbouring lane and across steps from registers), because the output at t + e needs the
+// entry of a segment that began up to width - 2 positions earlier. Where such an entry s >= 0 lies dl <= 2 positions before an output of
+// its segment, the taps k > dl -- masked to 0 without it -- are loaded from init[s, d, width - (k - dl)]; the same taps are what kEmit
+// stores, so a stored state is the last `width` values of concat(init[s], the segment). The loads sit behind a per-lane branch that only a
+// lane with a start entry in its window takes. init must not overlap a slot stored in the same launch: the lanes that read a slot are not
+// the lane that writes it. kStart = false compiles to the kernels as they were.
 #include "common.hpp"
 
 #include <type_traits>
@@ -113,6 +121,14 @@ struct conv_states_args_t {
     void *pool;
     int64_t pool_slot_stride, pool_c_stride, pool_w_stride;
 };
+// the kStart forward: + start_slots, laid out like end_slots, and init (n_init, dim, width) of x's dtype. Derived: conv_base / conv_ids and
+// every a.<kEmit field> of the kernel serve it as they are
+struct conv_resume_args_t : conv_states_args_t {
+    const int32_t *start_slots;
+    int64_t start_batch_stride;
+    const void *init;
+    int64_t init_slot_stride, init_c_stride, init_w_stride;
+};
 __host__ __device__ __forceinline__ const dimsum_conv_params_t &conv_base(const conv_states_args_t &a) { return a.v.p; }
 __device__ __forceinline__ const conv_varlen_args_t &conv_ids(const conv_varlen_args_t &a) { return a; }
 __device__ __forceinline__ const conv_varlen_args_t &conv_ids(const conv_states_args_t &a) { return a.v; }
@@ -122,10 +138,12 @@ __host__ __device__ __forceinline__ const dimsum_conv_bwd_params_t &conv_base(co
 __host__ __device__ __forceinline__ const dimsum_conv_bwd_params_t &conv_base(const conv_varlen_bwd_args_t &a) { return a.q; }
 
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T, bool kVec, bool kVarlen, bool kEmit = false>
+template <typename T, bool kVec, bool kVarlen, bool kEmit = false, bool kStart = false>
 __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(
-    const std::conditional_t<kEmit, conv_states_args_t, std::conditional_t<kVarlen, conv_varlen_args_t, dimsum_conv_params_t>> a) {
+    const std::conditional_t<kStart, conv_resume_args_t,
+                             std::conditional_t<kEmit, conv_states_args_t, std::conditional_t<kVarlen, conv_varlen_args_t, dimsum_conv_params_t>>> a) {
     static_assert(!kEmit || kVarlen, "per-segment states belong to packed rows");
+    static_assert(!kStart || kEmit, "resumed segments ride on the per-segment-states kernel");
     const dimsum_conv_params_t &p = conv_base(a);
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -143,6 +161,9 @@ __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(
         int i1[kR], i2[kR], i3[kR];
         const int32_t *eq[kR];                               // kEmit: the row's end_slots and its channel's place in the pool
         T *pl[kR];
+        const int32_t *bq[kR];                               // kStart: the row's start_slots, those of t0-1, t0-2 carried like i1, i2 (an entry three
+        int s1[kR], s2[kR];                                  // back serves no tap), and its channel's place in init
+        const T *pin[kR];
 #pragma unroll
         for (int r = 0; r < kR; ++r) {
             const int64_t row = min(row0 + r * gstride, rows - 1);
@@ -163,16 +184,22 @@ __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(
                 eq[r] = a.end_slots + (int64_t)b * a.end_batch_stride;
                 pl[r] = reinterpret_cast<T *>(a.pool) + (int64_t)d * a.pool_c_stride;
             }
+            if constexpr (kStart) {
+                bq[r] = a.start_slots + (int64_t)b * a.start_batch_stride;
+                pin[r] = reinterpret_cast<const T *>(a.init) + (int64_t)d * a.init_c_stride;
+                s1[r] = s2[r] = -1;                          // before the row: no segment begins there
+            }
         }
         for (int t0 = 0; t0 < L; t0 += 4 * kWave) {
             const int t = t0 + lane * 4;
             f32x4 v[kR];
-            i32x4 id[kR], es[kR];
+            i32x4 id[kR], es[kR], bs[kR];
 #pragma unroll
             for (int r = 0; r < kR; ++r) {
                 v[r] = load_row4<T, kVec>(x[r], t, L);
                 if constexpr (kVarlen) id[r] = load_ids4<kVec>(sq[r], t, L);
                 if constexpr (kEmit) es[r] = load_ids4<kVec>(eq[r], t, L);
+                if constexpr (kStart) bs[r] = load_ids4<kVec>(bq[r], t, L);
             }
 #pragma unroll
             for (int r = 0; r < kR; ++r) {
@@ -183,9 +210,16 @@ __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(
                     const int j1 = lane_up_i(id[r].v[3], i1[r]), j2 = lane_up_i(id[r].v[2], i2[r]), j3 = lane_up_i(id[r].v[1], i3[r]);
                     const int I[7] = {j3, j2, j1, id[r].v[0], id[r].v[1], id[r].v[2], id[r].v[3]};          // ids of t-3 .. t+3
                     const float xs[7] = {m3, m2, m1, v[r].v[0], v[r].v[1], v[r].v[2], v[r].v[3]};         // x[t-3] .. x[t+3]
+                    int S[6];                                                                            // kStart: start entries of t-2 .. t+3
+                    if constexpr (kStart) {
+                        S[0] = lane_up_i(bs[r].v[2], s2[r]), S[1] = lane_up_i(bs[r].v[3], s1[r]);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) S[2 + e] = bs[r].v[e];
+                    }
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const bool k1 = I[e + 3] == I[e + 2], k2 = k1 && I[e + 2] == I[e + 1], k3 = k2 && I[e + 1] == I[e];
+                        if constexpr (!kStart) {
                         q.v[e] = bias[r] + w4[r][0] * (k3 ? xs[e] : 0.f) + w4[r][1] * (k2 ? xs[e + 1] : 0.f) + w4[r][2] * (k1 ? xs[e + 2] : 0.f) +
                                  w4[r][3] * xs[e + 3];
                         if constexpr (kEmit) {
@@ -198,10 +232,36 @@ __global__ __launch_bounds__(256) void causal_conv1d_fwd_kernel(
                                     if (k >= 4 - W) st[(int64_t)(k - (4 - W)) * a.pool_w_stride] = from_f32<T>(tap[k]);
                             }
                         }
+                        } else {
+                        float tb[4] = {xs[e + 3], k1 ? xs[e + 2] : 0.f, k2 ? xs[e + 1] : 0.f, k3 ? xs[e] : 0.f};      // the masked taps x[t+e-k]
+                        {
+                            // the nearest start entry at t+e-dl, dl <= 2, with no boundary in (t+e-dl, t+e]: this output's segment is resumed and
+                            // its taps k > dl reach into init. The guards of the kEmit stores: load_ids4 reads 0 beyond the row, a valid slot
+                            const int dl = S[e + 2] >= 0 ? 0 : (k1 && S[e + 1] >= 0) ? 1 : (k2 && S[e] >= 0) ? 2 : -1;
+                            if (ok[r] && t + e < L && dl >= 0) {
+                                const T *in = pin[r] + (int64_t)S[e + 2 - dl] * a.init_slot_stride;
+#pragma unroll
+                                for (int k = 1; k < 4; ++k)                   // x[f - m] = init[s, d, W - m] with f the segment's first position, m = k - dl
+                                    if (k > dl && k < W) tb[k] = to_f32<T>(in[(int64_t)(W - (k - dl)) * a.init_w_stride]);
+                            }
+                        }
+                        q.v[e] = bias[r] + w4[r][0] * tb[3] + w4[r][1] * tb[2] + w4[r][2] * tb[1] + w4[r][3] * tb[0];
+                        // a segment ends at t + e: its conv state is these taps, the substituted ones among them
+                        if (ok[r] && t + e < L && es[r].v[e] >= 0) {
+                            T *st = pl[r] + (int64_t)es[r].v[e] * a.pool_slot_stride;
+#pragma unroll
+                            for (int k = 0; k < 4; ++k)
+                                if (k < W) st[(int64_t)(W - 1 - k) * a.pool_w_stride] = from_f32<T>(tb[k]);
+                        }
+                        }
                     }
                     i1[r] = __shfl(id[r].v[3], kWave - 1, kWave);
                     i2[r] = __shfl(id[r].v[2], kWave - 1, kWave);
                     i3[r] = __shfl(id[r].v[1], kWave - 1, kWave);
+                    if constexpr (kStart) {
+                        s1[r] = __shfl(bs[r].v[3], kWave - 1, kWave);
+                        s2[r] = __shfl(bs[r].v[2], kWave - 1, kWave);
+                    }
                 } else {
                 q.v[0] = bias[r] + w4[r][0] * m3 + w4[r][1] * m2 + w4[r][2] * m1 + w4[r][3] * v[r].v[0];
                 q.v[1] = bias[r] + w4[r][0] * m2 + w4[r][1] * m1 + w4[r][2] * v[r].v[0] + w4[r][3] * v[r].v[1];
@@ -440,16 +500,17 @@ static int conv_checks(const dimsum_conv_params_t &p, const dimsum_conv_bwd_para
     return DIMSUM_OK;
 }
 
-// Args: dimsum_conv_params_t, conv_varlen_args_t (kVarlen) or conv_states_args_t (kEmit). ids_vec: every int32 row operand of Args may be
-// read as 16-byte vectors
-template <typename T, bool kVarlen, bool kEmit, typename Args> static int launch_conv_fwd(const Args &a, hipStream_t s, bool ids_vec = true) {
+// Args: dimsum_conv_params_t, conv_varlen_args_t (kVarlen), conv_states_args_t (kEmit) or conv_resume_args_t (kStart). ids_vec: every int32
+// row operand of Args may be read as 16-byte vectors
+template <typename T, bool kVarlen, bool kEmit, bool kStart = false, typename Args>
+static int launch_conv_fwd(const Args &a, hipStream_t s, bool ids_vec = true) {
     const dimsum_conv_params_t &p = conv_base(a);
     const bool vec = ids_vec && vec_ok<T>(p.x_ptr, p.x_batch_stride, p.x_c_stride, p.seqlen) &&
                      vec_ok<T>(p.out_ptr, p.out_batch_stride, p.out_c_stride, p.seqlen);
     const int64_t rows = (int64_t)p.batch * p.dim;
     const int grid = (int)((rows + 15) / 16 < 256 * 32 ? (rows + 15) / 16 : 256 * 32);   // 4 waves x 4 rows per workgroup and pass (a 2x larger grid measured slower)
-    if (vec) hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true, kVarlen, kEmit>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false, kVarlen, kEmit>), dim3(grid), dim3(256), 0, s, a);
+    if (vec) hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, true, kVarlen, kEmit, kStart>), dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((causal_conv1d_fwd_kernel<T, false, kVarlen, kEmit, kStart>), dim3(grid), dim3(256), 0, s, a);
     return launch_status();
 }
 // Args: dimsum_conv_bwd_params_t or conv_varlen_bwd_args_t (kVarlen)
@@ -475,6 +536,29 @@ template <typename T> static int launch_conv_chunk(const dimsum_conv_chunk_param
     if (vec) hipLaunchKernelGGL((causal_conv1d_chunk_kernel<T, true>), dim3(grid), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((causal_conv1d_chunk_kernel<T, false>), dim3(grid), dim3(256), 0, s, p);
     return launch_status();
+}
+
+// dimsum_causal_conv1d_varlen_states_fwd behind NULL / struct_size: the entry's own fields first, in the header's order; the state's dtype
+// after the shared checks have vouched for conv.dtype. The resume entry runs the same
+static int conv_states_check(const dimsum_conv_varlen_states_params_t &e) {
+    if (e.num_slots < 1) return DIMSUM_ERR_SHAPE;
+    if (!e.end_slots_ptr || !e.state_ptr) return DIMSUM_ERR_NULL;
+    const dimsum_conv_params_t &p = e.varlen.conv;
+    if (ids_stride_bad(e.end_slots_batch_stride, p) || any_negative({e.state_slot_stride, e.state_c_stride, e.state_w_stride})) return DIMSUM_ERR_STRIDE;
+    const int rc = conv_checks(p, nullptr, true, e.varlen.seq_idx_ptr, e.varlen.seq_idx_batch_stride);
+    if (rc != DIMSUM_OK) return rc;
+    return e.state_dtype != p.dtype ? DIMSUM_ERR_UNSUPPORTED : DIMSUM_OK;      // the state is x's elements, moved
+}
+
+// ... and its fill -> whether its int32 rows may be read as 16-byte vectors
+template <typename Args> static bool conv_states_fill(Args &a, const dimsum_conv_varlen_states_params_t &e) {
+    memset(&a, 0, sizeof(a));
+    a.v = {e.varlen.conv, reinterpret_cast<const int32_t *>(e.varlen.seq_idx_ptr), e.varlen.seq_idx_batch_stride};
+    a.end_slots = reinterpret_cast<const int32_t *>(e.end_slots_ptr);
+    a.end_batch_stride = e.end_slots_batch_stride;
+    a.pool = e.state_ptr;
+    a.pool_slot_stride = e.state_slot_stride, a.pool_c_stride = e.state_c_stride, a.pool_w_stride = e.state_w_stride;
+    return ids_vec_ok(a.v.seq_idx, a.v.seq_batch_stride) && ids_vec_ok(a.end_slots, a.end_batch_stride);
 }
 
 }  // namespace dimsum
@@ -536,22 +620,31 @@ extern "C" int dimsum_causal_conv1d_varlen_states_fwd(const dimsum_conv_varlen_s
     using namespace dimsum;
     if (!e) return DIMSUM_ERR_NULL;
     if (e->struct_size != sizeof(dimsum_conv_varlen_states_params_t)) return DIMSUM_ERR_ABI;
-    // the entry's own fields first, in the header's order; the state's dtype after the shared checks have vouched for conv.dtype
-    if (e->num_slots < 1) return DIMSUM_ERR_SHAPE;
-    if (!e->end_slots_ptr || !e->state_ptr) return DIMSUM_ERR_NULL;
+    if (const int rc = conv_states_check(*e)) return rc;
     const dimsum_conv_params_t &p = e->varlen.conv;
-    if (ids_stride_bad(e->end_slots_batch_stride, p) || any_negative({e->state_slot_stride, e->state_c_stride, e->state_w_stride})) return DIMSUM_ERR_STRIDE;
-    const int rc = conv_checks(p, nullptr, true, e->varlen.seq_idx_ptr, e->varlen.seq_idx_batch_stride);
-    if (rc != DIMSUM_OK) return rc;
-    if (e->state_dtype != p.dtype) return DIMSUM_ERR_UNSUPPORTED;      // the state is x's elements, moved
     if (p.batch == 0) return DIMSUM_OK;
     conv_states_args_t a;
-    memset(&a, 0, sizeof(a));
-    a.v = {p, reinterpret_cast<const int32_t *>(e->varlen.seq_idx_ptr), e->varlen.seq_idx_batch_stride};
-    a.end_slots = reinterpret_cast<const int32_t *>(e->end_slots_ptr);
-    a.end_batch_stride = e->end_slots_batch_stride;
-    a.pool = e->state_ptr;
-    a.pool_slot_stride = e->state_slot_stride, a.pool_c_stride = e->state_c_stride, a.pool_w_stride = e->state_w_stride;
-    const bool ids_vec = ids_vec_ok(a.v.seq_idx, a.v.seq_batch_stride) && ids_vec_ok(a.end_slots, a.end_batch_stride);
+    const bool ids_vec = conv_states_fill(a, *e);
     return dispatch_dtype(p.dtype, [&](auto t) { return launch_conv_fwd<decltype(t), true, true>(a, reinterpret_cast<hipStream_t>(stream), ids_vec); });
+}
+
+extern "C" int dimsum_causal_conv1d_varlen_resume_fwd(const dimsum_conv_varlen_resume_params_t *e, void *stream) {
+    using namespace dimsum;
+    if (!e) return DIMSUM_ERR_NULL;
+    if (e->struct_size != sizeof(dimsum_conv_varlen_resume_params_t)) return DIMSUM_ERR_ABI;
+    if (e->n_init < 1) return DIMSUM_ERR_SHAPE;
+    if (!e->start_slots_ptr || !e->init_ptr) return DIMSUM_ERR_NULL;
+    const dimsum_conv_params_t &p = e->states.varlen.conv;
+    if (ids_stride_bad(e->start_slots_batch_stride, p) || any_negative({e->init_slot_stride, e->init_c_stride, e->init_w_stride})) return DIMSUM_ERR_STRIDE;
+    if (const int rc = conv_states_check(e->states)) return rc;
+    if (e->init_dtype != p.dtype) return DIMSUM_ERR_UNSUPPORTED;       // the carried inputs are x's elements, moved
+    if (p.batch == 0) return DIMSUM_OK;
+    conv_resume_args_t a;
+    bool ids_vec = conv_states_fill(a, e->states);
+    a.start_slots = reinterpret_cast<const int32_t *>(e->start_slots_ptr);
+    a.start_batch_stride = e->start_slots_batch_stride;
+    a.init = e->init_ptr;
+    a.init_slot_stride = e->init_slot_stride, a.init_c_stride = e->init_c_stride, a.init_w_stride = e->init_w_stride;
+    ids_vec = ids_vec && ids_vec_ok(a.start_slots, a.start_batch_stride);
+    return dispatch_dtype(p.dtype, [&](auto t) { return launch_conv_fwd<decltype(t), true, true, true>(a, reinterpret_cast<hipStream_t>(stream), ids_vec); });
 }

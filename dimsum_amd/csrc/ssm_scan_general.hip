@@ -27,6 +27,11 @@
 // read the same way (uniform addresses, a kT-bit wave-uniform mask). After a step whose bit is set every lane stores the h[j] it has just
 // computed -- the value the next step would read -- to pool[slot, d, n0 + j]: one lane per (channel, state), as for hT. The stores sit
 // behind a uniform branch inside the statically unrolled tile loop; kEmit = false compiles to the kernels as they were.
+// Resumed segments (dimsum_ssm_scan_varlen_resume_fwd, kStart on top of kEmit): a third int32 row, start_slots, read like end_slots. Before a
+// step whose bit is set every lane loads its h[j] from init[slot, d, n0 + j] -- in place of the 0 a boundary puts in, and at t = 0, where
+// there is no boundary bit -- behind the same kind of uniform branch. init may be the pool: the lane that loads an element at a segment's
+// first step is the lane that stores it at the segment's end, in its own program order, provided no OTHER segment of the launch reads a
+// slot this launch stores. kStart = false compiles to the kernels as they were.
 #include "common.hpp"
 
 #include <type_traits>
@@ -58,6 +63,15 @@ struct gen_emit_args_t : gen_args_t {
     void *pool;                            // (num_slots, dim, dstate), three free element strides
     int64_t pool_slot_stride, pool_d_stride, pool_dstate_stride;
     int32_t pool_f32;                      // the pool is float; else of the I/O type
+};
+
+// the kernel argument of the kStart kernels: the kEmit one + where a segment's first state comes from
+struct gen_start_args_t : gen_emit_args_t {
+    const int32_t *start_slots;            // (batch, seqlen) int32, rows start_batch_stride apart: >= 0 (a segment's first position) = enter it with that row of init
+    int64_t start_batch_stride;
+    const void *init;                      // (n_init, dim, dstate), three free element strides; may be the pool
+    int64_t init_slot_stride, init_d_stride, init_dstate_stride;
+    int32_t init_f32;                      // init is float; else of the I/O type
 };
 
 constexpr int kGenChunk = 2048;            // selective_scan.cpp:307
@@ -152,7 +166,8 @@ template <int kT> __device__ __forceinline__ unsigned reset_mask(const int32_t *
 }
 
 // the slots of one tile of end_slots and their mask: bit i = the state after position t0 + i is stored into slot[i] (>= 0; positions beyond
-// the row never store). The row is the workgroup's, as for reset_mask: uniform addresses, scalar results.
+// the row never store). The row is the workgroup's, as for reset_mask: uniform addresses, scalar results. start_slots is read by the same
+// function: bit i = the state entering position t0 + i is loaded from slot[i].
 template <int kT> __device__ __forceinline__ unsigned emit_mask(const int32_t *ends, int t0, int L, int (&slot)[kT]) {
     unsigned m = 0;
 #pragma unroll
@@ -166,10 +181,12 @@ template <int kT> __device__ __forceinline__ unsigned emit_mask(const int32_t *e
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------------------------
-template <typename T, bool kCplx, bool kVarB, bool kVarC, int kNB, int kMaxThreads, bool kVarlen, bool kEmit = false>
-__global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const std::conditional_t<kEmit, gen_emit_args_t, gen_args_t> a) {
+template <typename T, bool kCplx, bool kVarB, bool kVarC, int kNB, int kMaxThreads, bool kVarlen, bool kEmit = false, bool kStart = false>
+__global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(
+    const std::conditional_t<kStart, gen_start_args_t, std::conditional_t<kEmit, gen_emit_args_t, gen_args_t>> a) {
     static_assert(!kVarlen || (!kCplx && kVarB && kVarC), "packed rows: real A with input-dependent B and C");
     static_assert(!kEmit || kVarlen, "per-segment states belong to packed rows");
+    static_assert(!kStart || kEmit, "resumed segments ride on the per-segment-states kernels");
     using Cfg = GenCfg<kCplx, kNB>;
     constexpr int kK = Cfg::kK, kT = Cfg::kT, kRow = Cfg::kRow;
     extern __shared__ float red[];                      // [wave][step][lane]
@@ -208,6 +225,8 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
     bool cut = false;                                   // kVarlen: a boundary lies behind: the running product is 0 from there on
     const int32_t *ends = nullptr;                      // kEmit: the row's end_slots
     if constexpr (kEmit) ends = a.end_slots + (int64_t)q.b * a.end_batch_stride;
+    const int32_t *starts = nullptr;                    // kStart: the row's start_slots
+    if constexpr (kStart) starts = a.start_slots + (int64_t)q.b * a.start_batch_stride;
 
     for (int t0 = 0; t0 < L; t0 += kT) {
         unsigned rm = 0;
@@ -218,6 +237,12 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
         unsigned em = 0;
         int eslot[kT];
         if constexpr (kEmit) em = emit_mask<kT>(ends, t0, L, eslot);
+        unsigned sm = 0;
+        int sslot[kT];
+        if constexpr (kStart) {
+            sm = emit_mask<kT>(starts, t0, L, sslot);
+            rm &= ~sm;                                  // the loaded state takes the place of the boundary's 0
+        }
         float uv[kT], dt[kT], y[kT];
 #pragma unroll
         for (int i = 0; i < kT; ++i) {
@@ -236,6 +261,20 @@ __global__ __launch_bounds__(kMaxThreads) void ssm_scan_general_fwd_kernel(const
                 const float yk = dt[i] - sumdt_lo, tk = sumdt + yk;      // Kahan
                 sumdt_lo = (tk - sumdt) - yk;
                 sumdt = tk;
+            }
+            if constexpr (kStart) {
+                if ((sm >> i) & 1u) {                   // wave-uniform: a resumed segment begins at t0 + i; this lane's states, as h0 reads them
+                    const int64_t base = (int64_t)sslot[i] * a.init_slot_stride + (int64_t)q.d * a.init_d_stride;
+                    if (a.init_f32) {
+#pragma unroll
+                        for (int j = 0; j < kNB; ++j)
+                            h[j] = q.live && q.n0 + j < N ? ld_f32<float>(a.init, base + (int64_t)(q.n0 + j) * a.init_dstate_stride) : 0.f;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < kNB; ++j)
+                            h[j] = q.live && q.n0 + j < N ? ld_f32<T>(a.init, base + (int64_t)(q.n0 + j) * a.init_dstate_stride) : 0.f;
+                    }
+                }
             }
 #pragma unroll
             for (int j = 0; j < kNB; ++j) {
@@ -648,15 +687,17 @@ template <typename Args> static Args gen_fill(const dimsum_ssm_general_params_t 
     return a;
 }
 
-// THE launch: kFwd / kVarlen / kEmit pick the kernel family, Args (gen_args_t; gen_emit_args_t with kEmit) is its argument. One launch shape for all.
-template <typename T, bool kCplx, bool kVarB, bool kVarC, bool kFwd, bool kVarlen, bool kEmit, typename Args> static int gen_launch(const Args &a, hipStream_t s) {
+// THE launch: kFwd / kVarlen / kEmit / kStart pick the kernel family, Args (gen_args_t; gen_emit_args_t with kEmit; gen_start_args_t with kStart)
+// is its argument. One launch shape for all.
+template <typename T, bool kCplx, bool kVarB, bool kVarC, bool kFwd, bool kVarlen, bool kEmit, bool kStart, typename Args>
+static int gen_launch(const Args &a, hipStream_t s) {
     const dimsum_ssm_general_params_t &p = a.f;
     const int W = (p.dstate + kGenNB - 1) / kGenNB, kT = gen_tile_steps(kCplx);
     const dim3 grid((unsigned)(p.n_groups * a.cblocks), (unsigned)p.batch), block((unsigned)(64 * W));
     const size_t lds = (size_t)W * kT * 64 * sizeof(float) * (kFwd ? 1 : 2);
     auto launch = [&](auto max_threads) {
         constexpr int kMax = decltype(max_threads)::value;
-        if constexpr (kFwd) hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, kGenNB, kMax, kVarlen, kEmit>), grid, block, lds, s, a);
+        if constexpr (kFwd) hipLaunchKernelGGL((ssm_scan_general_fwd_kernel<T, kCplx, kVarB, kVarC, kGenNB, kMax, kVarlen, kEmit, kStart>), grid, block, lds, s, a);
         else hipLaunchKernelGGL((ssm_scan_general_bwd_kernel<T, kCplx, kVarB, kVarC, kGenNB, kMax, kVarlen>), grid, block, lds, s, a);
     };
     // up to 64 states a workgroup is at most 4 waves, one per SIMD: the kernel may use the whole register file (512 per lane); above, up to
@@ -667,19 +708,19 @@ template <typename T, bool kCplx, bool kVarB, bool kVarC, bool kFwd, bool kVarle
 }
 
 // THE run of every entry point, behind its checks: the padded channel counts, the element type, the (complex, varB, varC) case. Packed rows
-// (kVarlen, and kEmit on top of it) exist for real A with input-dependent B / C alone: gen_varlen_check lets nothing else through.
-template <bool kFwd, bool kVarlen, bool kEmit = false, typename Args> static int gen_run(Args &a, void *stream) {
+// (kVarlen, and kEmit and kStart on top of it) exist for real A with input-dependent B / C alone: gen_varlen_check lets nothing else through.
+template <bool kFwd, bool kVarlen, bool kEmit = false, bool kStart = false, typename Args> static int gen_run(Args &a, void *stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     a.cblocks = (a.f.dim / a.f.n_groups + 63) / 64;
     a.dpad = (int64_t)a.f.n_groups * a.cblocks * 64;
     return dispatch_dtype(a.f.dtype, [&](auto t) {
         using T = decltype(t);
         if constexpr (kVarlen) {
-            return gen_launch<T, false, true, true, kFwd, true, kEmit>(a, s);
+            return gen_launch<T, false, true, true, kFwd, true, kEmit, kStart>(a, s);
         } else {
             const bool c = a.f.is_complex != 0, vb = a.f.is_variable_B != 0, vc = a.f.is_variable_C != 0;
 #define DIMSUM_GEN_CASE(C, VB, VC) \
-    if (c == C && vb == VB && vc == VC) return gen_launch<T, C, VB, VC, kFwd, false, false>(a, s)
+    if (c == C && vb == VB && vc == VC) return gen_launch<T, C, VB, VC, kFwd, false, false, false>(a, s)
             DIMSUM_GEN_CASE(false, true, true);
             DIMSUM_GEN_CASE(false, true, false);
             DIMSUM_GEN_CASE(false, false, true);
@@ -688,7 +729,7 @@ template <bool kFwd, bool kVarlen, bool kEmit = false, typename Args> static int
             DIMSUM_GEN_CASE(true, true, false);
             DIMSUM_GEN_CASE(true, false, true);
 #undef DIMSUM_GEN_CASE
-            return gen_launch<T, true, false, false, kFwd, false, false>(a, s);      // the eighth of eight
+            return gen_launch<T, true, false, false, kFwd, false, false, false>(a, s);      // the eighth of eight
         }
     });
 }
@@ -712,6 +753,29 @@ static int gen_bwd(const dimsum_ssm_general_bwd_params_t *p, const gen_ids_t *id
     gen_args_t a = gen_fill<gen_args_t>(f, ids);
     a.b = *p;
     return ids ? gen_run<false, true>(a, stream) : gen_run<false, false>(a, stream);
+}
+
+// dimsum_ssm_scan_varlen_states_fwd behind NULL / struct_size: its own fields, then the packed-row checks; the resume entry runs the same
+static int gen_states_check(const dimsum_ssm_varlen_states_params_t &p) {
+    if (p.num_slots < 1) return DIMSUM_ERR_SHAPE;
+    if (!p.end_slots_ptr || !p.state_ptr) return DIMSUM_ERR_NULL;
+    const dimsum_ssm_general_params_t &f = p.varlen.scan;
+    if (gen_row_stride_bad(p.end_slots_batch_stride, f) || any_negative({p.state_slot_stride, p.state_d_stride, p.state_dstate_stride})) return DIMSUM_ERR_STRIDE;
+    const gen_ids_t ids{p.varlen.seq_idx_ptr, p.varlen.seq_idx_batch_stride};
+    return gen_check(f, true, &ids);
+}
+
+// ... and its fill: the ids, end_slots and the pool
+template <typename Args> static Args gen_states_fill(const dimsum_ssm_varlen_states_params_t &p) {
+    const dimsum_ssm_general_params_t &f = p.varlen.scan;
+    const gen_ids_t ids{p.varlen.seq_idx_ptr, p.varlen.seq_idx_batch_stride};
+    Args e = gen_fill<Args>(f, &ids);
+    e.end_slots = reinterpret_cast<const int32_t *>(p.end_slots_ptr);
+    e.end_batch_stride = p.end_slots_batch_stride;
+    e.pool = p.state_ptr;
+    e.pool_slot_stride = p.state_slot_stride, e.pool_d_stride = p.state_d_stride, e.pool_dstate_stride = p.state_dstate_stride;
+    e.pool_f32 = p.state_f32 != 0 || f.dtype == DIMSUM_F32;
+    return e;
 }
 
 }  // namespace dimsum
@@ -776,17 +840,25 @@ extern "C" int dimsum_ssm_scan_varlen_states_fwd(const dimsum_ssm_varlen_states_
     using namespace dimsum;
     if (!p) return DIMSUM_ERR_NULL;
     if (p->struct_size != sizeof(dimsum_ssm_varlen_states_params_t)) return DIMSUM_ERR_ABI;
-    if (p->num_slots < 1) return DIMSUM_ERR_SHAPE;
-    if (!p->end_slots_ptr || !p->state_ptr) return DIMSUM_ERR_NULL;
-    const dimsum_ssm_general_params_t &f = p->varlen.scan;
-    if (gen_row_stride_bad(p->end_slots_batch_stride, f) || any_negative({p->state_slot_stride, p->state_d_stride, p->state_dstate_stride})) return DIMSUM_ERR_STRIDE;
-    const gen_ids_t ids{p->varlen.seq_idx_ptr, p->varlen.seq_idx_batch_stride};
-    if (const int rc = gen_check(f, true, &ids)) return rc;
-    gen_emit_args_t e = gen_fill<gen_emit_args_t>(f, &ids);
-    e.end_slots = reinterpret_cast<const int32_t *>(p->end_slots_ptr);
-    e.end_batch_stride = p->end_slots_batch_stride;
-    e.pool = p->state_ptr;
-    e.pool_slot_stride = p->state_slot_stride, e.pool_d_stride = p->state_d_stride, e.pool_dstate_stride = p->state_dstate_stride;
-    e.pool_f32 = p->state_f32 != 0 || f.dtype == DIMSUM_F32;
+    if (const int rc = gen_states_check(*p)) return rc;
+    gen_emit_args_t e = gen_states_fill<gen_emit_args_t>(*p);
     return gen_run<true, true, true>(e, stream);
+}
+
+extern "C" int dimsum_ssm_scan_varlen_resume_fwd(const dimsum_ssm_varlen_resume_params_t *p, void *stream) {
+    using namespace dimsum;
+    if (!p) return DIMSUM_ERR_NULL;
+    if (p->struct_size != sizeof(dimsum_ssm_varlen_resume_params_t)) return DIMSUM_ERR_ABI;
+    if (p->n_init < 1) return DIMSUM_ERR_SHAPE;
+    if (!p->start_slots_ptr || !p->init_ptr) return DIMSUM_ERR_NULL;
+    const dimsum_ssm_general_params_t &f = p->states.varlen.scan;
+    if (gen_row_stride_bad(p->start_slots_batch_stride, f) || any_negative({p->init_slot_stride, p->init_d_stride, p->init_dstate_stride})) return DIMSUM_ERR_STRIDE;
+    if (const int rc = gen_states_check(p->states)) return rc;
+    gen_start_args_t e = gen_states_fill<gen_start_args_t>(p->states);
+    e.start_slots = reinterpret_cast<const int32_t *>(p->start_slots_ptr);
+    e.start_batch_stride = p->start_slots_batch_stride;
+    e.init = p->init_ptr;
+    e.init_slot_stride = p->init_slot_stride, e.init_d_stride = p->init_d_stride, e.init_dstate_stride = p->init_dstate_stride;
+    e.init_f32 = p->init_f32 != 0 || f.dtype == DIMSUM_F32;
+    return gen_run<true, true, true, true>(e, stream);
 }

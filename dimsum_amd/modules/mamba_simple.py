@@ -133,10 +133,14 @@ class _MambaBase(nn.Module):
         if not (torch.is_tensor(seq_idx) and seq_idx.dtype == torch.int32 and tuple(seq_idx.shape) == tuple(hidden_states.shape[:2])):
             raise ValueError(f"seq_idx must be an int32 (batch, seqlen) = {tuple(hidden_states.shape[:2])} tensor")
 
-    def _mix(self, hidden_states, cond, x3=None, states=None, seq_idx=None, prefill_slots=None):
+    def _mix(self, hidden_states, cond, x3=None, states=None, seq_idx=None, prefill_slots=None, prefill_starts=None):
         """states: the (conv_state, ssm_state) of an inference cache, filled from this call's sequence (forward(inference_params=...));
         seq_idx: packed rows (module docstring); prefill_slots (B, L) int32 with both: `states` are POOLS and the conv and scan kernels store
-        every segment's states into the slot named at its last position (InferenceParams.prefill_slots) -- no torch op touches the states"""
+        every segment's states into the slot named at its last position (InferenceParams.prefill_slots) -- no torch op touches the states;
+        prefill_starts (InferenceParams.prefill_starts) with those: segments that continue their slot's states -- one index_select takes the
+        conv's carried inputs out of the pool (a snapshot: the conv may not read a slot it stores), the scan reads the SSM pool in place"""
+        if prefill_starts is not None:
+            self._refuse_prefill_starts(prefill_starts, prefill_slots, hidden_states)
         if prefill_slots is not None:
             self._refuse_prefill_slots(prefill_slots, hidden_states, cond, x3, states, seq_idx)
             prefill_slots = prefill_slots.contiguous()
@@ -197,10 +201,16 @@ class _MambaBase(nn.Module):
             y = (out + out_b.flip([-1])).transpose(1, 2)
             return nn.functional.linear(y, self.out_proj.weight, self.out_proj.bias)
         if prefill_slots is not None:
+            starts = {}
+            if prefill_starts is not None:
+                with torch.no_grad():
+                    snapshot = states[0].index_select(0, prefill_starts["start_list"])      # (S_in, d_inner, d_conv): start_rows index it by ordinal
+                starts = dict(start_slots=prefill_starts["start_slots"].contiguous(), start_rows=prefill_starts["start_rows"].contiguous(),
+                              conv_initial_states=snapshot)
             out = mamba_inner_fn_cond(xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
                                       self.out_proj.weight, self.out_proj.bias, A, None, None, self.D.float(),
                                       delta_bias=self.dt_proj.bias.float(), delta_softplus=True, seq_idx=seq_idx, end_slots=prefill_slots,
-                                      conv_state=states[0], ssm_state=states[1])
+                                      conv_state=states[0], ssm_state=states[1], **starts)
             return out
         out = mamba_inner_fn_cond(xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
                                   self.out_proj.weight, self.out_proj.bias, A, None, None, self.D.float(),
@@ -229,6 +239,20 @@ class _MambaBase(nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("prefill_slots is an inference argument: the pass that stores states has no backward; call it under "
                                       "torch.no_grad()")
+
+    def _refuse_prefill_starts(self, prefill_starts, prefill_slots, hidden_states):
+        """prefill_starts ride on prefill_slots (whose refusals -- v2 / zigzag, cond, x3, grad mode -- then apply as they are); the VALUES are
+        never read"""
+        if prefill_slots is None:
+            raise ValueError("prefill_starts without prefill_slots: resumed segments belong to the packed prompt pass into slots (set "
+                             "inference_params.prefill_slots and pass seq_idx)")
+        shape = tuple(hidden_states.shape[:2])
+        ok = isinstance(prefill_starts, dict) and all(torch.is_tensor(prefill_starts.get(k)) for k in ("start_slots", "start_rows", "start_list"))
+        if not (ok and all(prefill_starts[k].dtype == torch.int32 and tuple(prefill_starts[k].shape) == shape for k in ("start_slots", "start_rows"))
+                and prefill_starts["start_list"].dtype == torch.int64 and prefill_starts["start_list"].dim() == 1
+                and prefill_starts["start_list"].numel() >= 1):
+            raise ValueError(f"prefill_starts must hold start_slots and start_rows, int32 (batch, seqlen) = {shape}, and start_list, int64 with at "
+                             "least one slot (plan_packed_prefill(resume=...))")
 
     # ---- the recurrent form (mamba_simple.py:299-380) ------------------------------------------------------------------------------------------
     def _refuse_recurrent(self, x3=None):
@@ -373,6 +397,9 @@ class _MambaBase(nn.Module):
                                       "token by token, so only it has states to index")
         self._refuse_recurrent(x3)
         prefill_slots = getattr(inference_params, "prefill_slots", None)
+        prefill_starts = getattr(inference_params, "prefill_starts", None)
+        if prefill_starts is not None and prefill_slots is None:
+            self._refuse_prefill_starts(prefill_starts, None, hidden_states)
         if prefill_slots is not None:
             if seq_idx is None:
                 raise ValueError("prefill_slots without seq_idx: per-segment states belong to packed rows (pass seq_idx; one request alone is "
@@ -386,7 +413,7 @@ class _MambaBase(nn.Module):
             if self.layer_idx not in inference_params.key_value_memory_dict:
                 raise ValueError("prefill_slots need a pool of states in key_value_memory_dict (allocate_inference_cache(num_slots, ...))")
             states = inference_params.key_value_memory_dict[self.layer_idx]
-            return self._mix(hidden_states, cond, states=states, seq_idx=seq_idx, prefill_slots=prefill_slots)
+            return self._mix(hidden_states, cond, states=states, seq_idx=seq_idx, prefill_slots=prefill_slots, prefill_starts=prefill_starts)
         if state_indices is not None and inference_params.seqlen_offset == 0:
             raise ValueError("state_indices at seqlen_offset == 0: a prompt is prefilled into slot s of a pool through the views pool[s:s+1] "
                              "with state_indices=None; the slot index belongs to the decode steps (seqlen_offset > 0)")

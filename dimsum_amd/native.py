@@ -282,6 +282,11 @@ def _check_end_slots(end_slots, batch, seqlen, who):
     _check_token_ids(end_slots, "end_slots", batch, seqlen, who)
 
 
+def _check_start_slots(start_slots, batch, seqlen, who):
+    """start_slots: where it is >= 0 -- only at a segment's first position -- the segment continues that row of `initial_states`"""
+    _check_token_ids(start_slots, "start_slots", batch, seqlen, who)
+
+
 def _is_channel_last(t):
     """(batch, dim, seqlen) with channel stride 1: what the channel-last kernels address"""
     return t.stride(1) == 1 or t.shape[1] == 1
@@ -351,11 +356,12 @@ def causal_conv1d_fwd(x, weight, bias, silu_activation, out=None, *, seq_idx=Non
     return _conv_fwd(who, x, weight, bias, silu_activation, out, seq_idx, end_slots, conv_state)
 
 
-def _conv_fwd(who, x, weight, bias, silu_activation, out, seq_idx=None, end_slots=None, conv_state=None):
+def _conv_fwd(who, x, weight, bias, silu_activation, out, seq_idx=None, end_slots=None, conv_state=None, start_slots=None, initial_states=None):
     """every forward of the (batch, dim, seqlen) conv; `who` names the variant: causal_conv1d_fwd (plain or channel-last), _varlen_fwd
-    (seq_idx), _varlen_states_fwd (+ end_slots, conv_state). The shape, dtype and stride refusals of the packed-row operands come first
-    (they need no GPU)."""
-    states, packed = who == "causal_conv1d_varlen_states_fwd", who != "causal_conv1d_fwd"
+    (seq_idx), _varlen_states_fwd (+ end_slots, conv_state), _varlen_resume_fwd (+ start_slots, initial_states). The shape, dtype and stride
+    refusals of the packed-row operands come first (they need no GPU)."""
+    resume = who == "causal_conv1d_varlen_resume_fwd"
+    states, packed = resume or who == "causal_conv1d_varlen_states_fwd", who != "causal_conv1d_fwd"
     if packed:
         _check(x.dim() == 3, "causal_conv1d: x must be (batch, dim, seqlen)")
         _check_token_ids(seq_idx, "seq_idx", x.shape[0], x.shape[2], who)
@@ -364,11 +370,17 @@ def _conv_fwd(who, x, weight, bias, silu_activation, out, seq_idx=None, end_slot
         _check(torch.is_tensor(conv_state) and conv_state.dim() == 3 and conv_state.shape[0] >= 1 and tuple(conv_state.shape[1:]) == (x.shape[1], weight.shape[-1]),
                f"{who}: conv_state must be a pool (num_slots >= 1, dim, width)")
         _check(conv_state.dtype == x.dtype, f"{who}: conv_state must have x's dtype {x.dtype}, got {conv_state.dtype} (the state is x's elements, moved, not converted)")
+    if resume:
+        _check_start_slots(start_slots, x.shape[0], x.shape[2], who)
+        _check(torch.is_tensor(initial_states) and initial_states.dim() == 3 and initial_states.shape[0] >= 1
+               and tuple(initial_states.shape[1:]) == (x.shape[1], weight.shape[-1]), f"{who}: initial_states must be (n_init >= 1, dim, width)")
+        _check(initial_states.dtype == x.dtype, f"{who}: initial_states must have x's dtype {x.dtype}, got {initial_states.dtype} (the carried "
+                                                "inputs are x's elements, moved, not converted)")
     channel_last = _check_conv(x, weight, bias)
     if packed:
         if channel_last:
             raise RuntimeError(f"{who}: seq_idx needs a seqlen-contiguous x (the channel-last kernels take none)")
-        _gpu(seq_idx, end_slots, conv_state)
+        _gpu(seq_idx, end_slots, conv_state, start_slots, initial_states)
     weight, bias = _conv_f32(weight, bias)
     if out is None:
         out = _new_channel_last(x) if channel_last else torch.empty_like(x)   # x's layout like the reference (causal_conv1d.cpp:262): d-major in Mamba
@@ -385,13 +397,18 @@ def _conv_fwd(who, x, weight, bias, silu_activation, out, seq_idx=None, end_slot
         _fill_conv_cl(P, x, weight, bias, silu_activation, out)
         _conv_launch("dimsum_causal_conv1d_cl_fwd", P, x, who)
     elif states:
-        P = _lib.ConvVarlenStatesParams()
+        R = _lib.ConvVarlenResumeParams() if resume else None
+        P = R.states if resume else _lib.ConvVarlenStatesParams()
         _fill_conv(P.varlen.conv, x, weight, bias, silu_activation, out)
         P.varlen.seq_idx_ptr, P.varlen.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
         P.num_slots, P.end_slots_ptr, P.end_slots_batch_stride = conv_state.shape[0], _ptr(end_slots), end_slots.stride(0)
         P.state_ptr, P.state_dtype = _ptr(conv_state), _DT[conv_state.dtype]
         P.state_slot_stride, P.state_c_stride, P.state_w_stride = conv_state.stride()
-        _conv_launch("dimsum_causal_conv1d_varlen_states_fwd", P, x, who)
+        if resume:
+            R.n_init, R.start_slots_ptr, R.start_slots_batch_stride = initial_states.shape[0], _ptr(start_slots), start_slots.stride(0)
+            R.init_ptr, R.init_dtype = _ptr(initial_states), _DT[initial_states.dtype]
+            R.init_slot_stride, R.init_c_stride, R.init_w_stride = initial_states.stride()
+        _conv_launch("dimsum_" + who, R if resume else P, x, who)
     elif packed:
         P = _lib.ConvVarlenParams()
         _fill_conv(P.conv, x, weight, bias, silu_activation, out)
@@ -424,6 +441,17 @@ def causal_conv1d_varlen_states_fwd(x, weight, bias, silu_activation, seq_idx, e
     causal_conv1d_update shifts. conv_state: a pool (num_slots, dim, width) of x's dtype with free strides; slots nobody names are not
     touched. Inference only. The slots' values are the caller's contract (_check_token_ids)."""
     return _conv_fwd("causal_conv1d_varlen_states_fwd", x, weight, bias, silu_activation, out, seq_idx, end_slots, conv_state)
+
+
+def causal_conv1d_varlen_resume_fwd(x, weight, bias, silu_activation, seq_idx, end_slots, conv_state, start_slots, initial_states, out=None):
+    """causal_conv1d_varlen_states_fwd whose segments may CONTINUE a carried conv state -> out: where start_slots[b, t] = s >= 0 (allowed only
+    at a segment's first position) the taps of that segment that reach before t read initial_states[s, :, :] -- the last `width` inputs of
+    the earlier piece, newest last -- instead of zeros, and the state stored through end_slots is the last `width` values of
+    concat(initial_states[s], the segment). initial_states: (n_init, dim, width) of x's dtype with free strides; it must not overlap a slot
+    of conv_state that this launch stores (different lanes read and write one slot: the operator checks the storage ranges). Negative
+    entries are what causal_conv1d_varlen_states_fwd does. Inference only. The values of both rows are the caller's contract."""
+    return _conv_fwd("causal_conv1d_varlen_resume_fwd", x, weight, bias, silu_activation, out, seq_idx, end_slots, conv_state, start_slots,
+                     initial_states)
 
 
 def causal_conv1d_bwd(x, weight, bias, dout, dx, silu_activation, *, seq_idx=None):
@@ -1152,6 +1180,29 @@ def selective_scan_varlen_states_fwd(u, delta, A, B, C, D, z, delta_bias, delta_
     return _scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out, need_x, seq_idx=seq_idx, end_slots=end_slots, ssm_state=ssm_state)
 
 
+def selective_scan_varlen_resume_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, seq_idx, end_slots, ssm_state, start_slots, initial_states,
+                                     need_out=True, need_x=True):
+    """selective_scan_varlen_states_fwd whose segments may CONTINUE a carried state -> [out, x, (out_z)]: where start_slots[b, t] = s >= 0
+    (allowed only at a segment's first position) the state entering position t is initial_states[s, :, :] instead of zeros. initial_states:
+    (n_init, dim, dstate), float32 or of u's dtype, with free strides. It MAY be ssm_state itself: one lane owns each (channel, state), loads
+    it at the segment's first step and stores it at the segment's end in its own program order -- provided a slot stored in this launch is
+    read only by the segment that stores it. Inference only. The values of both rows are the caller's contract."""
+    who = "selective_scan_varlen_resume_fwd"
+    _check(seq_idx is not None, f"{who}: seq_idx is required")
+    _check(torch.is_tensor(u) and u.dim() == 3, "selective_scan_general: u must be (batch, dim, seqlen) float32, float16 or bfloat16")
+    _check_end_slots(end_slots, u.shape[0], u.shape[2], who)
+    _check(torch.is_tensor(ssm_state) and ssm_state.dim() == 3 and ssm_state.shape[0] >= 1 and tuple(ssm_state.shape[1:]) == (u.shape[1], A.shape[1]),
+           f"{who}: ssm_state must be a pool (num_slots >= 1, dim, dstate)")
+    _check(ssm_state.dtype in (torch.float32, u.dtype), f"{who}: ssm_state must be float32 or of u's dtype {u.dtype}, got {ssm_state.dtype}")
+    _check_start_slots(start_slots, u.shape[0], u.shape[2], who)
+    _check(torch.is_tensor(initial_states) and initial_states.dim() == 3 and initial_states.shape[0] >= 1
+           and tuple(initial_states.shape[1:]) == (u.shape[1], A.shape[1]), f"{who}: initial_states must be (n_init >= 1, dim, dstate)")
+    _check(initial_states.dtype in (torch.float32, u.dtype),
+           f"{who}: initial_states must be float32 or of u's dtype {u.dtype}, got {initial_states.dtype}")
+    return _scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out, need_x, seq_idx=seq_idx, end_slots=end_slots, ssm_state=ssm_state,
+                             start_slots=start_slots, initial_states=initial_states)
+
+
 def selective_scan_varlen_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz, delta_softplus, seq_idx, dB=None, dC=None):
     """selective_scan_general_bwd on packed rows: the adjoint state is not handed across a boundary and the terms through a_t h_{t-1} vanish there"""
     _check(seq_idx is not None, "selective_scan_varlen_bwd: seq_idx is required")
@@ -1159,26 +1210,35 @@ def selective_scan_varlen_bwd(u, delta, A, B, C, D, z, delta_bias, dout, out, dz
 
 
 def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, need_out=True, need_x=True, *, seq_idx=None, end_slots=None,
-                               ssm_state=None):
+                               ssm_state=None, start_slots=None, initial_states=None):
     """-> [out, x, (out_z)] like selective_scan_cuda.fwd, on the general kernels: A float32 or complex64 (dim, dstate), dstate 1..256; B / C
     input-dependent (batch, groups, dstate, seqlen) -- (.., 2 seqlen) reals with complex A -- or constant (dim, dstate) of A's dtype.
     x is (batch, dim, n_chunks, 2 dstate) of A's dtype. None of the inference extras of selective_scan_fwd.
-    seq_idx: selective_scan_varlen_fwd's (packed rows); end_slots / ssm_state: selective_scan_varlen_states_fwd's, which checks them.
+    seq_idx: selective_scan_varlen_fwd's (packed rows); end_slots / ssm_state: selective_scan_varlen_states_fwd's, which checks them;
+    start_slots / initial_states on top of those: selective_scan_varlen_resume_fwd's, which checks them.
     One struct per variant, each holding the one before it; _fill_ssm_general fills the innermost."""
     flags = _check_ssm_general(u, delta, A, B, C, D, z, delta_bias)
     if seq_idx is not None:
         _check_scan_seq_idx(seq_idx, u, flags, "selective_scan_varlen_fwd")
     _check(end_slots is None or seq_idx is not None, "selective_scan_general_fwd: end_slots belong to packed rows (seq_idx)")
+    _check(start_slots is None or end_slots is not None, "selective_scan_general_fwd: start_slots ride on the per-segment-states entry (end_slots)")
     if end_slots is not None:
-        _gpu(end_slots, ssm_state)
+        _gpu(end_slots, ssm_state, start_slots, initial_states)
     batch, dim, seqlen = u.shape
     dstate = A.shape[1]
     out = torch.empty_like(delta) if need_out else None
     x = torch.empty((batch, dim, (seqlen + 2047) // 2048, dstate * 2), device=u.device, dtype=A.dtype) if need_x else None
     out_z = torch.empty_like(z) if z is not None else None
     if u.numel() > 0:
+        top = None                                                # the outermost struct, where it is not P
         if end_slots is not None:
             entry, P = "varlen_states_fwd", _lib.SsmVarlenStatesParams()
+            if start_slots is not None:
+                entry, top = "varlen_resume_fwd", _lib.SsmVarlenResumeParams()
+                P = top.states
+                top.n_init, top.start_slots_ptr, top.start_slots_batch_stride = initial_states.shape[0], _ptr(start_slots), start_slots.stride(0)
+                top.init_ptr, top.init_f32 = _ptr(initial_states), int(initial_states.dtype == torch.float32)
+                top.init_slot_stride, top.init_d_stride, top.init_dstate_stride = initial_states.stride()
             P.num_slots, P.end_slots_ptr, P.end_slots_batch_stride = ssm_state.shape[0], _ptr(end_slots), end_slots.stride(0)
             P.state_ptr, P.state_f32 = _ptr(ssm_state), int(ssm_state.dtype == torch.float32)
             P.state_slot_stride, P.state_d_stride, P.state_dstate_stride = ssm_state.stride()
@@ -1188,7 +1248,7 @@ def selective_scan_general_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softpl
         if seq_idx is not None:
             V.seq_idx_ptr, V.seq_idx_batch_stride = _ptr(seq_idx), seq_idx.stride(0)
         _fill_ssm_general(V.scan if seq_idx is not None else P, u, delta, A, B, C, D, z, delta_bias, delta_softplus, out, x, out_z, flags)
-        _scan_launch(entry, P, u)
+        _scan_launch(entry, P if top is None else top, u)
     return [out, x] + ([out_z] if z is not None else [])
 
 

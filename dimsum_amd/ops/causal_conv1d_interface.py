@@ -69,14 +69,60 @@ def _conv_varlen_states(x, weight, bias, activation, seq_idx, end_slots, conv_st
         return native.causal_conv1d_varlen_states_fwd(x, weight, bias.contiguous() if bias is not None else None, silu, seq_idx, end_slots, conv_state)
 
 
-def causal_conv1d_fn(x, weight, bias=None, activation=None, seq_idx=None, end_slots=None, conv_state=None):
+def _storage_range(t):
+    """[first, last + 1) byte addresses a strided tensor can touch (positive strides); an empty tensor touches nothing"""
+    if t.numel() == 0:
+        return 0, 0
+    lo = t.data_ptr()
+    return lo, lo + (sum((n - 1) * st for n, st in zip(t.shape, t.stride())) + 1) * t.element_size()
+
+
+def _conv_varlen_resume(x, weight, bias, activation, seq_idx, end_slots, conv_state, start_slots, initial_states):
+    """causal_conv1d_fn(seq_idx=, start_slots=, initial_states=[, end_slots=, conv_state=]): the kStart kernels of csrc/causal_conv1d.hip, no graph"""
+    silu = _silu_flag(activation)
+    if start_slots is None or initial_states is None:
+        raise ValueError("causal_conv1d_fn: start_slots and initial_states go together (which segments continue, and the carried inputs they "
+                         "continue)")
+    if seq_idx is None:
+        raise ValueError("causal_conv1d_fn: start_slots without seq_idx: resumed segments belong to packed rows (pass seq_idx; one segment is an "
+                         "all-equal id row)")
+    if (end_slots is None) != (conv_state is None):
+        raise ValueError("causal_conv1d_fn: end_slots and conv_state go together (where to store, and the pool to store into)")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias, conv_state, initial_states)):
+        raise NotImplementedError("causal_conv1d_fn: start_slots / initial_states are inference arguments -- the pass that continues states has "
+                                  "no backward; call it under torch.no_grad() or on inputs that do not require grad")
+    if end_slots is not None and torch.is_tensor(initial_states) and torch.is_tensor(conv_state):
+        (a0, a1), (b0, b1) = _storage_range(initial_states), _storage_range(conv_state)
+        if initial_states.device == conv_state.device and a0 < b1 and b0 < a1:
+            raise ValueError("causal_conv1d_fn: initial_states overlaps conv_state: the lanes that read a slot's carried inputs are not the lane "
+                             "that stores the slot's new state, so a slot stored in this launch must not be read in it -- pass a snapshot "
+                             "(conv_state.index_select(0, slots)); the scan's initial_states may alias its pool, the conv's may not")
+    with torch.no_grad():
+        if x.stride(2) != 1:
+            x = x.contiguous()
+        if end_slots is None:
+            # a continuation that stores nothing: an all-negative row, and a pool nobody writes (initial_states itself serves)
+            end_slots, conv_state = torch.full_like(start_slots, -1), initial_states
+        return native.causal_conv1d_varlen_resume_fwd(x, weight, bias.contiguous() if bias is not None else None, silu, seq_idx, end_slots, conv_state,
+                                                      start_slots, initial_states)
+
+
+def causal_conv1d_fn(x, weight, bias=None, activation=None, seq_idx=None, end_slots=None, conv_state=None, start_slots=None, initial_states=None):
     """x: (batch, dim, seqlen), weight: (dim, width), bias: (dim,), activation: None | "silu" | "swish".
     seq_idx (batch, seqlen) int32, contiguous: packed rows -- a tap that would reach across a change of the id is dropped (position t >= 1 is
     a boundary iff seq_idx[b, t] != seq_idx[b, t - 1]; the values are only compared). None: the call it always was.
     end_slots (batch, seqlen) int32, contiguous, with seq_idx and conv_state (num_slots, dim, width) of x's dtype: where end_slots[b, t] =
     s >= 0 the conv state of the segment ending at t -- its last `width` inputs, zero-padded on the left, x[b, :, t] last -- is stored into
     conv_state[s], IN PLACE; negative entries store nothing and unnamed slots are not touched. Entries must be < num_slots and none may
-    appear twice: neither is checked (it would take a device read). Inference arguments: no graph is recorded."""
+    appear twice: neither is checked (it would take a device read). Inference arguments: no graph is recorded.
+    start_slots (batch, seqlen) int32, contiguous, with seq_idx and initial_states (n_init, dim, width) of x's dtype: start_slots[b, t] = s >= 0
+    is allowed only at a segment's first position and makes that segment CONTINUE initial_states[s] -- the last `width` inputs of the
+    earlier piece, newest last: the taps that reach before t read them instead of zeros, and a state stored through end_slots is the last
+    `width` values of concat(initial_states[s], the segment). Negative entries: zero state, as without the argument. end_slots / conv_state
+    may be absent (nothing is stored). initial_states must not overlap conv_state (ValueError): pass a snapshot of the slots. Inference
+    arguments."""
+    if start_slots is not None or initial_states is not None:
+        return _conv_varlen_resume(x, weight, bias, activation, seq_idx, end_slots, conv_state, start_slots, initial_states)
     if end_slots is not None or conv_state is not None:
         return _conv_varlen_states(x, weight, bias, activation, seq_idx, end_slots, conv_state)
     if seq_idx is not None:
@@ -84,12 +130,16 @@ def causal_conv1d_fn(x, weight, bias=None, activation=None, seq_idx=None, end_sl
     return CausalConv1dFn.apply(x, weight, bias, activation)
 
 
-def causal_conv1d_varlen_torch(x, weight, bias=None, activation=None, seq_idx=None, end_slots=None, conv_state=None):
+def causal_conv1d_varlen_torch(x, weight, bias=None, activation=None, seq_idx=None, end_slots=None, conv_state=None, start_slots=None,
+                               initial_states=None):
     """causal_conv1d_fn(seq_idx=...) written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer): a
     loop over the positions, tap j of position t counted iff t - j >= 0 and no boundary lies in (t - j, t]. Differentiable. What the tests
     compare the kernels with and what CPU tests put in their place; never a fallback: nothing in the package calls it.
     end_slots / conv_state: causal_conv1d_fn's -- where end_slots[b, t] = s >= 0, conv_state[s, :, width - 1 - j] receives the masked tap j of
-    position t (a host read of end_slots: test infrastructure)."""
+    position t (a host read of end_slots: test infrastructure).
+    start_slots / initial_states: causal_conv1d_fn's -- a segment whose first position t carries start_slots[b, t] = s >= 0 sees
+    initial_states[s, :, width - m] as x[b, :, t - m], m = 1 .. width - 1, and its stored state is the last `width` values of
+    concat(initial_states[s], the segment). initial_states is read before anything is stored: it may be conv_state here."""
     silu = _silu_flag(activation, "causal_conv1d_varlen_torch")
     batch, dim, seqlen = x.shape
     width = weight.shape[-1]
@@ -99,16 +149,38 @@ def causal_conv1d_varlen_torch(x, weight, bias=None, activation=None, seq_idx=No
     if end_slots is not None:
         assert end_slots.dtype == torch.int32 and tuple(end_slots.shape) == (batch, seqlen) and tuple(conv_state.shape[1:]) == (dim, width)
         ends = end_slots.tolist()
+    assert (start_slots is None) == (initial_states is None) and (start_slots is None or seq_idx is not None)
     zero = x.new_zeros(batch, dim)
+    carried = None                                                                 # [b][t] -> {j: the (dim,) value tap j of position t takes from initial_states}
+    if start_slots is not None:
+        assert start_slots.dtype == torch.int32 and tuple(start_slots.shape) == (batch, seqlen) and tuple(initial_states.shape[1:]) == (dim, width)
+        starts, ids, init = start_slots.tolist(), seq_idx.tolist(), initial_states.detach().clone()
+        carried = [[{} for _ in range(seqlen)] for _ in range(batch)]
+        for b in range(batch):
+            for f in range(seqlen):
+                if starts[b][f] < 0:
+                    continue
+                assert f == 0 or ids[b][f] != ids[b][f - 1], "start_slots: a non-negative entry is allowed only at a segment's first position"
+                for t in range(f, min(f + width - 1, seqlen)):
+                    if ids[b][t] != ids[b][f]:
+                        break
+                    for j in range(t - f + 1, width):
+                        carried[b][t][j] = init[starts[b][f], :, width - (j - (t - f))].to(x.dtype)
     cols = []
     for t in range(seqlen):
         pre = x[:, :, t] * weight[:, width - 1]
         same = torch.ones(batch, dtype=torch.bool, device=x.device)               # no boundary in (t - j, t] so far
         taps = [x[:, :, t]]                                                        # the masked taps j = 0 .. width - 1 of position t
-        for j in range(1, min(width, t + 1)):
-            if seq_idx is not None:
-                same = same & (seq_idx[:, t - j + 1] == seq_idx[:, t - j])
-            taps.append(torch.where(same[:, None], x[:, :, t - j], zero))
+        for j in range(1, min(width, t + 1) if carried is None else width):
+            if t - j >= 0:
+                if seq_idx is not None:
+                    same = same & (seq_idx[:, t - j + 1] == seq_idx[:, t - j])
+                tap = torch.where(same[:, None], x[:, :, t - j], zero)
+            else:
+                tap = zero
+            if carried is not None and any(j in carried[b][t] for b in range(batch)):
+                tap = torch.stack([carried[b][t].get(j, tap[b]) for b in range(batch)])
+            taps.append(tap)
             pre = pre + taps[j] * weight[:, width - 1 - j]
         cols.append(pre if bias is None else pre + bias)
         if ends is not None:

@@ -140,17 +140,51 @@ def _selective_scan_varlen_states(u, delta, A, B, C, D, z, delta_bias, delta_sof
     return res if not return_last_state else (res, x[:, :, -1, 1::2])
 
 
+def _selective_scan_varlen_resume(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, seq_idx, end_slots, ssm_state, start_slots,
+                                  initial_states):
+    """selective_scan_fn(seq_idx=, start_slots=, initial_states=[, end_slots=, ssm_state=]): the kStart instantiations of
+    csrc/ssm_scan_general.hip, no graph"""
+    if start_slots is None or initial_states is None:
+        raise ValueError("selective_scan_fn: start_slots and initial_states go together (which segments continue, and the states they continue)")
+    if seq_idx is None:
+        raise ValueError("selective_scan_fn: start_slots without seq_idx: resumed segments belong to packed rows (pass seq_idx; one segment is an "
+                         "all-equal id row)")
+    if (end_slots is None) != (ssm_state is None):
+        raise ValueError("selective_scan_fn: end_slots and ssm_state go together (where to store, and the pool to store into)")
+    _refuse_varlen_scan("selective_scan_fn", A, B, C)
+    if _will_backprop(u, delta, A, B, C, D, z, delta_bias, ssm_state, initial_states):
+        raise NotImplementedError("selective_scan_fn: start_slots / initial_states are inference arguments -- the scan that continues states "
+                                  "has no backward; call it under torch.no_grad() or on inputs that do not require grad")
+    with torch.no_grad():
+        u, delta, B, C, D, z, _, _ = _scan_operands(u, delta, B, C, D, z)
+        if end_slots is None:
+            # a continuation that stores nothing: an all-negative row, and a pool nobody writes (initial_states itself serves)
+            end_slots, ssm_state = torch.full_like(start_slots, -1), initial_states
+        out, x, *rest = native.selective_scan_varlen_resume_fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus, seq_idx, end_slots, ssm_state,
+                                                                start_slots, initial_states, need_x=return_last_state)
+    res = rest[0] if z is not None else out
+    return res if not return_last_state else (res, x[:, :, -1, 1::2])
+
+
 def selective_scan_varlen_torch(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False, seq_idx=None,
-                                end_slots=None, ssm_state=None):
+                                end_slots=None, ssm_state=None, start_slots=None, initial_states=None):
     """selective_scan_fn(seq_idx=...) written out in plain torch, in the precision of its inputs (float64 inputs give the float64 answer): a
     loop over the positions, h_t = (1 - r_t) exp(dt_t A) h_{t-1} + dt_t B_t u_t with r_t = 1 where seq_idx changes; real A, B / C
     (batch, dstate, seqlen) or (batch, groups, dstate, seqlen). Differentiable. What the tests compare the kernels with and what CPU tests put
     in their place; never a fallback: nothing in the package calls it.
     end_slots / ssm_state: selective_scan_fn's -- where end_slots[b, t] = s >= 0, ssm_state[s] receives h_t of row b (a host read of
-    end_slots: test infrastructure)."""
+    end_slots: test infrastructure).
+    start_slots / initial_states: selective_scan_fn's -- where start_slots[b, t] = s >= 0 (a segment's first position) the state entering
+    position t is initial_states[s] instead of zeros. initial_states may be ssm_state: a slot is read at its segment's first step and
+    stored at its segment's end, in that order."""
     batch, dim, seqlen = u.shape
     N = A.shape[-1]
     assert (end_slots is None) == (ssm_state is None) and (end_slots is None or seq_idx is not None)
+    assert (start_slots is None) == (initial_states is None) and (start_slots is None or seq_idx is not None)
+    starts = None
+    if start_slots is not None:
+        assert start_slots.dtype == torch.int32 and tuple(start_slots.shape) == (batch, seqlen) and tuple(initial_states.shape[1:]) == (dim, N)
+        starts = start_slots.tolist()
     ends = None
     if end_slots is not None:
         assert end_slots.dtype == torch.int32 and tuple(end_slots.shape) == (batch, seqlen) and tuple(ssm_state.shape[1:]) == (dim, N)
@@ -166,6 +200,8 @@ def selective_scan_varlen_torch(u, delta, A, B, C, D=None, z=None, delta_bias=No
     for t in range(seqlen):
         if seq_idx is not None and t > 0:
             h = torch.where((seq_idx[:, t] != seq_idx[:, t - 1])[:, None, None], torch.zeros_like(h), h)
+        if starts is not None and any(starts[b][t] >= 0 for b in range(batch)):
+            h = torch.stack([initial_states[starts[b][t]].detach().to(h.dtype) if starts[b][t] >= 0 else h[b] for b in range(batch)])
         Bt = B4[:, :, :, t].repeat_interleave(rep, dim=1)                         # (batch, dim, dstate)
         Ct = C4[:, :, :, t].repeat_interleave(rep, dim=1)
         h = torch.exp(dt[:, :, t, None] * A[None]) * h + (dt[:, :, t] * u[:, :, t])[:, :, None] * Bt
@@ -197,7 +233,7 @@ def _selective_scan_carry(u, delta, A, B, C, D, z, delta_bias, delta_softplus, r
 
 
 def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, return_last_state=False, initial_state=None,
-                      seq_idx=None, end_slots=None, ssm_state=None):
+                      seq_idx=None, end_slots=None, ssm_state=None, start_slots=None, initial_states=None):
     """out (or (out, last_state)); the gradient of last_state is not propagated (as in the reference).
     initial_state (batch, dim, dstate), float32 or of u's dtype (complex64 with complex A): the scan starts from it instead of from zeros --
     a cached sequence continued by seqlen tokens; last_state then comes back in its dtype. An inference argument: no graph is recorded, and
@@ -208,7 +244,18 @@ def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_
     end_slots (batch, seqlen) int32, contiguous, with seq_idx and ssm_state (num_slots, dim, dstate), float32 or of u's dtype: where
     end_slots[b, t] = s >= 0 the state after position t is stored into ssm_state[s], IN PLACE; negative entries store nothing and unnamed
     slots are not touched. Entries must be < num_slots and none may appear twice: neither is checked (it would take a device read).
-    Inference arguments: no graph is recorded."""
+    Inference arguments: no graph is recorded.
+    start_slots (batch, seqlen) int32, contiguous, with seq_idx and initial_states (n_init, dim, dstate), float32 or of u's dtype:
+    start_slots[b, t] = s >= 0 is allowed only at a segment's first position and makes that segment CONTINUE initial_states[s] instead of
+    starting from zeros; negative entries start from zeros. end_slots / ssm_state may be absent (nothing is stored). initial_states MAY BE
+    ssm_state: one lane owns each (channel, state), loads it at the segment's first step and stores it at the segment's end -- provided a
+    slot stored in this call is read only by the segment that stores it (not checked). Inference arguments."""
+    if start_slots is not None or initial_states is not None:
+        if initial_state is not None:
+            raise NotImplementedError("selective_scan_fn: start_slots together with a carried initial_state: a packed row takes its carried "
+                                      "states per segment, through start_slots / initial_states")
+        return _selective_scan_varlen_resume(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, seq_idx, end_slots, ssm_state,
+                                             start_slots, initial_states)
     if end_slots is not None or ssm_state is not None:
         if initial_state is not None:
             raise NotImplementedError("selective_scan_fn: end_slots together with a carried initial_state is not built: a packed row starts "
@@ -537,13 +584,22 @@ class _MambaInner(torch.autograd.Function):
 
 
 def _mamba_inner_varlen(has_out_proj, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D,
-                        delta_bias, B_proj_bias, C_proj_bias, delta_softplus, seq_idx, last_state=None, end_slots=None, conv_state=None, ssm_state=None):
+                        delta_bias, B_proj_bias, C_proj_bias, delta_softplus, seq_idx, last_state=None, end_slots=None, conv_state=None, ssm_state=None,
+                        start_slots=None, start_rows=None, conv_initial_states=None):
     """mamba_inner_fn(seq_idx=...): the general route's plain sequence on packed rows, conv -> x_proj / dt_proj -> scan -> out_proj, each piece
     under its own autograd node (causal_conv1d_fn and selective_scan_fn with seq_idx; the projections are GEMMs): no dt_proj in the scan, no
     operand images, no f16s training, no saved-state extras. last_state receives the state of every row's last segment.
     end_slots with the pools conv_state and ssm_state (inference): the conv and the scan store every segment's states into its slot
-    themselves (causal_conv1d_fn / selective_scan_fn); last_state is then not taken."""
+    themselves (causal_conv1d_fn / selective_scan_fn); last_state is then not taken.
+    start_slots / start_rows / conv_initial_states on top of those: resumed segments. The scan reads ssm_state IN PLACE by start_slots (pool
+    ids); the conv reads conv_initial_states, a snapshot, by start_rows (ordinals into the snapshot): its carried inputs may not alias the
+    pool it stores into."""
     emit = end_slots is not None or conv_state is not None or ssm_state is not None
+    resume = start_slots is not None or start_rows is not None or conv_initial_states is not None
+    if resume and (start_slots is None or start_rows is None or conv_initial_states is None):
+        raise ValueError("mamba_inner_fn_cond: start_slots, start_rows and conv_initial_states go together")
+    if resume and not emit:
+        raise ValueError("mamba_inner_fn_cond: start_slots without end_slots / conv_state / ssm_state: the scan continues the states of the pool")
     if emit and (end_slots is None or conv_state is None or ssm_state is None):
         raise ValueError("mamba_inner_fn_cond: end_slots, conv_state and ssm_state go together")
     if emit and last_state is not None:
@@ -556,7 +612,8 @@ def _mamba_inner_varlen(has_out_proj, xz, conv1d_weight, conv1d_bias, x_proj_wei
         xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight if has_out_proj else None, out_proj_bias if has_out_proj else None)
     bsz, d_inner, L = x.shape
     N, R = A.shape[-1], delta_proj_weight.shape[1]
-    conv_out = causal_conv1d_fn(x, conv_w, conv_b, "silu", seq_idx, **({"end_slots": end_slots, "conv_state": conv_state} if emit else {}))
+    conv_out = causal_conv1d_fn(x, conv_w, conv_b, "silu", seq_idx, **({"end_slots": end_slots, "conv_state": conv_state} if emit else {}),
+                                **({"start_slots": start_rows, "initial_states": conv_initial_states} if resume else {}))
     x_dbl = F.linear(conv_out.transpose(1, 2).reshape(bsz * L, d_inner), x_proj_weight)            # (b l, R + 2N)
     delta = _delta(delta_proj_weight, x_dbl[:, :R].t(), bsz, L)
     Bm = x_dbl[:, R:R + N] if B_proj_bias is None else x_dbl[:, R:R + N] + B_proj_bias.to(x_dbl.dtype)
@@ -564,7 +621,8 @@ def _mamba_inner_varlen(has_out_proj, xz, conv1d_weight, conv1d_bias, x_proj_wei
     Bm = Bm.reshape(bsz, L, N).permute(0, 2, 1).unsqueeze(1).contiguous()                           # (b, 1, N, l)
     Cm = Cm.reshape(bsz, L, N).permute(0, 2, 1).unsqueeze(1).contiguous()
     out_z = selective_scan_fn(conv_out, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, return_last_state=last_state is not None, seq_idx=seq_idx,
-                              **({"end_slots": end_slots, "ssm_state": ssm_state} if emit else {}))
+                              **({"end_slots": end_slots, "ssm_state": ssm_state} if emit else {}),
+                              **({"start_slots": start_slots, "initial_states": ssm_state} if resume else {}))
     if last_state is not None:
         out_z, last = out_z
         with torch.no_grad():
@@ -600,11 +658,14 @@ def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_wei
 def mamba_inner_fn_cond(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                         A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None,
                         delta_softplus=True, init_states=None, conv_done=False, last_state=None, seq_idx=None, end_slots=None, conv_state=None,
-                        ssm_state=None):
+                        ssm_state=None, start_slots=None, start_rows=None, conv_initial_states=None):
     """seq_idx: the packed-row route of mamba_inner_fn (last_state is honoured); init_states or conv_done with it raise NotImplementedError.
     end_slots (batch, seqlen) int32 with the pools conv_state (num_slots, d_inner, d_conv) and ssm_state (num_slots, d_inner, d_state), and
-    seq_idx: the packed PROMPT pass -- every segment's states are stored into its slot by the conv and scan kernels (inference only)"""
-    emit = {k: v for k, v in (("end_slots", end_slots), ("conv_state", conv_state), ("ssm_state", ssm_state)) if v is not None}
+    seq_idx: the packed PROMPT pass -- every segment's states are stored into its slot by the conv and scan kernels (inference only).
+    start_slots / start_rows (batch, seqlen) int32 and conv_initial_states (n, d_inner, d_conv) with those: segments that CONTINUE a slot --
+    the scan reads ssm_state in place by start_slots, the conv reads the snapshot conv_initial_states by start_rows"""
+    emit = {k: v for k, v in (("end_slots", end_slots), ("conv_state", conv_state), ("ssm_state", ssm_state), ("start_slots", start_slots),
+                              ("start_rows", start_rows), ("conv_initial_states", conv_initial_states)) if v is not None}
     return _mamba_inner(True, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias, A, B, C, D, delta_bias,
                         B_proj_bias, C_proj_bias, delta_softplus, init_states=init_states, conv_done=conv_done, last_state=last_state,
                         **({"seq_idx": seq_idx} if seq_idx is not None else {}), **emit)

@@ -17,13 +17,19 @@ class InferenceParams:
     prefill_slots (no reference counterpart): None, or an int32 (batch, seqlen) device tensor for a PACKED prompt pass (seqlen_offset == 0
     with seq_idx): the cached states are the pools, and where prefill_slots[b, t] = s >= 0 the conv and SSM states after position t of row b
     are stored into slot s by the conv and scan kernels themselves; negative entries store nothing (plan_packed_prefill builds it). The
-    non-negative entries must be < num_slots and pairwise different: not checked (it would take a device read). `reset` leaves it alone."""
+    non-negative entries must be < num_slots and pairwise different: not checked (it would take a device read). `reset` leaves it alone.
+    prefill_starts (no reference counterpart): None, or what a packed prompt pass with prefill_slots needs to RESUME segments from the
+    states their slots already hold -- a dict of plan_packed_prefill(resume=...)'s start_slots and start_rows, (batch, seqlen) int32 on the
+    device, and start_list, (S_in,) int64 on the device, the resumed slots in ordinal order. Every mixer snapshots its conv pool over
+    start_list (one index_select) and hands the conv the snapshot with start_rows; the scan reads the SSM pool in place with start_slots.
+    Needs prefill_slots and seq_idx. `reset` leaves it alone."""
     max_seqlen: int
     max_batch_size: int
     seqlen_offset: int = 0
     key_value_memory_dict: dict = dataclasses.field(default_factory=dict)
     state_indices: Optional[torch.Tensor] = None
     prefill_slots: Optional[torch.Tensor] = None
+    prefill_starts: Optional[dict] = None
 
     def reset(self, max_seqlen, max_batch_size):
         self.max_seqlen, self.max_batch_size, self.seqlen_offset = max_seqlen, max_batch_size, 0
@@ -67,7 +73,7 @@ def seq_idx_from_lengths(lengths, seqlen=None, device=None):
     return torch.repeat_interleave(torch.arange(len(lengths), dtype=torch.int32), torch.tensor(lengths, dtype=torch.long)).to(device)
 
 
-def plan_packed_prefill(lengths, slots, rows=1, pad_multiple=1):
+def plan_packed_prefill(lengths, slots, rows=1, pad_multiple=1, resume=None):
     """the layout of one packed prompt pass over several new requests, on the host (nothing is read from a device): segment i has
     lengths[i] >= 1 tokens and its states go to slot slots[i]. The segments are placed in order, each onto the currently shortest of `rows`
     rows (the lowest such row on a tie); the rows are then padded to one length, a multiple of pad_multiple, and a row's padding is a segment
@@ -75,7 +81,12 @@ def plan_packed_prefill(lengths, slots, rows=1, pad_multiple=1):
     -> dict(seq_idx (rows, seqlen) int32, end_slots (rows, seqlen) int32: slots[i] at segment i's last position and -1 everywhere else,
             segments [(row, start)] per segment, logits_positions (n,) int64: row * seqlen + start + length - 1 per segment, seqlen)
     CPU tensors; rows that got no segment are all padding. What MambaLMHeadModel.forward(seq_idx=, logits_positions=) and
-    InferenceParams.prefill_slots take."""
+    InferenceParams.prefill_slots take.
+    resume: None, or one truth value per segment -- resume[i]: segment i CONTINUES the state already in slots[i] (a later piece of a prompt
+    fed in pieces) instead of starting from zeros. The dict then also holds start_slots (rows, seqlen) int32: slots[i] at a resumed
+    segment's first position and -1 everywhere else; start_rows, the same positions holding the segment's ordinal among the resumed ones;
+    start_list (n_resumed,) int64: the resumed slots in ordinal order -- what InferenceParams.prefill_starts takes. resume=None returns
+    exactly the dict above."""
     lengths, slots = [int(n) for n in lengths], [int(s) for s in slots]
     rows, pad_multiple = int(rows), int(pad_multiple)
     if len(lengths) != len(slots) or not lengths:
@@ -84,6 +95,10 @@ def plan_packed_prefill(lengths, slots, rows=1, pad_multiple=1):
         raise ValueError(f"plan_packed_prefill: lengths must be >= 1 and slots non-negative and pairwise different, got {lengths} and {slots}")
     if rows < 1 or pad_multiple < 1:
         raise ValueError(f"plan_packed_prefill: rows and pad_multiple must be >= 1, got {rows} and {pad_multiple}")
+    if resume is not None:
+        resume = [bool(f) for f in resume]
+        if len(resume) != len(lengths):
+            raise ValueError(f"plan_packed_prefill: one resume flag per segment, got {len(resume)} flags for {len(lengths)} segments")
     fill, segments = [0] * rows, []
     for n in lengths:
         r = min(range(rows), key=lambda i: (fill[i], i))
@@ -100,7 +115,15 @@ def plan_packed_prefill(lengths, slots, rows=1, pad_multiple=1):
     for r in range(rows):
         seq_idx[r, fill[r]:] = count[r]          # the padding: a segment of its own
     pos = torch.tensor([r * seqlen + start + n - 1 for (r, start), n in zip(segments, lengths)], dtype=torch.int64)
-    return {"seq_idx": seq_idx, "end_slots": end_slots, "segments": segments, "logits_positions": pos, "seqlen": seqlen}
+    plan = {"seq_idx": seq_idx, "end_slots": end_slots, "segments": segments, "logits_positions": pos, "seqlen": seqlen}
+    if resume is not None:
+        start_slots, start_rows, start_list = torch.full((rows, seqlen), -1, dtype=torch.int32), torch.full((rows, seqlen), -1, dtype=torch.int32), []
+        for (r, start), s, f in zip(segments, slots, resume):
+            if f:
+                start_slots[r, start], start_rows[r, start] = s, len(start_list)
+                start_list.append(s)
+        plan.update(start_slots=start_slots, start_rows=start_rows, start_list=torch.tensor(start_list, dtype=torch.int64))
+    return plan
 
 
 def packed_labels(input_ids, seq_idx, ignore_index=-100):

@@ -29,8 +29,16 @@ the conv and scan kernels store every request's states into its slot (csrc/causa
 scatter them and the slots into the step's buffers. An admission still reads nothing back. The packed pass runs the general scan kernels
 whatever the d_state, so a request's first logits agree with its alone prefill to rounding, not bit for bit.
 
-Documented limits: prefill stalls the batch; a packed admission starts every slot from zero state (no chunked prefill into slots, no
-continuation of a slot); max_batch above 16 runs the unfused step (with slots); no prefix or state sharing between requests; no preemption.
+Chunked prefill (`chunked_prefill=True` on top of packed_prefill and max_prefill_tokens; off by default): an admission NEVER exceeds
+max_prefill_tokens prompt tokens. A prompt that does not fit in what is left of the budget is cut: its first piece claims a row and a slot and
+stores its states there; the request stays "prefilling" -- its row is reserved but its slot is not in the step's slot buffer, so the decode
+step does not touch it, and it gets no logits and no sample. Every following step admits the next pieces of the prefilling requests first, in
+queue order before new requests, as segments that RESUME their slot (plan_packed_prefill(resume=...), InferenceParams.prefill_starts; the
+kStart kernels). The piece that ends the prompt is in logits_positions, is sampled with uniforms[0] and joins the
+decode batch exactly as a packed admission does. So a long prompt delays the live rows by bounded passes instead of one long one.
+
+Documented limits: prefill stalls the batch (by at most max_prefill_tokens tokens per step with chunked_prefill); without chunked_prefill a
+packed admission starts every slot from zero state; a finished request's slot is not kept for a later turn; max_batch above 16 runs the unfused step (with slots); no prefix or state sharing between requests; no preemption.
 Sampling: `fused_sampling=True` draws token i of a request with uniforms[i] of THAT request (given to `submit`, or drawn there from the
 engine's generator) whichever row and step it lands on, so a request's output does not depend on its neighbours or on the schedule;
 `fused_sampling=False` runs generation.sample() per step on the batch's logits, whose multinomial draws (top_k != 1) come from one shared
@@ -58,6 +66,7 @@ class _Request:
     slot: int = -1
     row: int = -1
     finished: bool = False
+    done: int = 0                             # chunked prefill: prompt tokens already prefilled into the slot
 
 
 class DecodeEngine:
@@ -71,11 +80,13 @@ class DecodeEngine:
     depend on it). vocab_size: the classes of a padded head, as in generate(). output_scores=True keeps every token's logits row
     (`scores(rid)`). generator: with fused sampling a CPU generator from which `submit` draws a request's uniforms on the host; without it
     the device generator handed to sample(). packed_prefill / prefill_rows / max_prefill_tokens: one packed prompt pass per admission (module
-    docstring; None = DIMSUM_PACKED_PREFILL=1). `n_prefill_passes` counts the model's prompt passes. Bookkeeping the tests read: `n_captures`, `free_slots`, `rows`, `slot_history` [(rid, slot)] in admission order.
+    docstring; None = DIMSUM_PACKED_PREFILL=1). chunked_prefill: cut prompts to the budget (module docstring). `n_prefill_passes` counts the
+    model's prompt passes, `n_prefill_pieces` the prompt segments in them, `prefill_pass_tokens` the prompt tokens of each chunked pass. Bookkeeping the tests read: `n_captures`, `free_slots`, `rows`, `slot_history` [(rid, slot)] in admission order.
     See the module docstring for the schedule, the host reads and the limits."""
 
     def __init__(self, model, max_batch, num_slots=None, *, max_seqlen, top_k=1, top_p=0.0, temperature=1.0, eos_token_id=None, vocab_size=None,
-                 cg=True, fused_sampling=True, output_scores=False, generator=None, packed_prefill=None, prefill_rows=1, max_prefill_tokens=None):
+                 cg=True, fused_sampling=True, output_scores=False, generator=None, packed_prefill=None, prefill_rows=1, max_prefill_tokens=None,
+                 chunked_prefill=False):
         num_slots = max_batch if num_slots is None else int(num_slots)
         if max_batch < 1 or num_slots < max_batch:
             raise ValueError(f"DecodeEngine: need max_batch >= 1 and num_slots >= max_batch, got {max_batch} and {num_slots}")
@@ -88,7 +99,13 @@ class DecodeEngine:
         self.max_prefill_tokens = None if max_prefill_tokens is None else int(max_prefill_tokens)
         if self.prefill_rows < 1 or (self.max_prefill_tokens is not None and self.max_prefill_tokens < 1):
             raise ValueError(f"DecodeEngine: prefill_rows and max_prefill_tokens must be >= 1, got {prefill_rows} and {max_prefill_tokens}")
-        self.n_prefill_passes = 0
+        self.chunked_prefill = bool(chunked_prefill)
+        if self.chunked_prefill and not (self.packed_prefill and self.max_prefill_tokens is not None):
+            raise ValueError("DecodeEngine: chunked_prefill cuts prompts to the budget of a packed admission: it needs packed_prefill=True and "
+                             "max_prefill_tokens")
+        self.n_prefill_passes = self.n_prefill_pieces = 0
+        self.prefill_pass_tokens = []                       # chunked prefill: prompt tokens of every pass, in order
+        self._prefilling = []                               # chunked prefill: requests whose prompt is partly in their slot, in queue order
         param = next(iter(model.parameters()))
         self.device = param.device
         with torch.no_grad():
@@ -134,7 +151,7 @@ class DecodeEngine:
         return rid
 
     def idle(self):
-        return not self.queue and all(r is None for r in self.rows)
+        return not self.queue and not self._prefilling and all(r is None for r in self.rows)
 
     def sequence(self, rid):
         """-> LongTensor (prompt + generated so far) on the host"""
@@ -189,6 +206,7 @@ class DecodeEngine:
                                   prefill_slots=dev(plan["end_slots"]))
         logits = self.model(ids, inference_params=prefill, seq_idx=dev(plan["seq_idx"]), logits_positions=dev(plan["logits_positions"])).logits
         self.n_prefill_passes += 1
+        self.n_prefill_pieces += len(batch)
         u = None if not self.fused_sampling else dev(torch.stack([r.uniforms[0] for r in batch]))
         first = torch.empty(len(batch), dtype=torch.long, device=self.device)
         self._sample_into(logits, u, first)                                      # (S, V) -> (S,): stays on the device
@@ -203,7 +221,66 @@ class DecodeEngine:
             r.slot, r.row, self.rows[row] = slot, row, r.rid
             self._fresh.add(row)
 
+    def _admit_chunked(self):
+        """_admit_packed under a hard budget: the next pieces of the prefilling requests first, then queued requests, cut where the budget ends
+        (module docstring). Pieces that end their prompt are sampled and join the decode batch; the others only store their states."""
+        budget, batch = self.max_prefill_tokens, []                              # batch: (request, piece length, resumed)
+        for r in self._prefilling:
+            if budget == 0:
+                break
+            n = min(budget, r.prompt.numel() - r.done)
+            batch.append((r, n, True))
+            budget -= n
+        free_rows = [row for row, rid in enumerate(self.rows) if rid is None]
+        while self.queue and budget > 0 and self.free_slots and free_rows:
+            r = self.requests[self.queue.popleft()]
+            r.slot, r.row = self.free_slots.pop(0), free_rows.pop(0)
+            self.rows[r.row] = r.rid                                             # the row is reserved; its entry in self.slots stays -1
+            self.slot_history.append((r.rid, r.slot))
+            n = min(budget, r.prompt.numel())
+            batch.append((r, n, False))
+            budget -= n
+        if not batch:
+            return
+        plan = plan_packed_prefill([n for _, n, _ in batch], [r.slot for r, _, _ in batch], rows=self.prefill_rows, resume=[f for _, _, f in batch])
+        dev = lambda t: t.to(self.device, non_blocking=True)
+        ids = dev(torch.zeros((self.prefill_rows, plan["seqlen"]), dtype=torch.long))
+        for (r, n, _), (prow, start) in zip(batch, plan["segments"]):
+            ids[prow, start:start + n].copy_(r.prompt[r.done:r.done + n])
+        last = [i for i, (r, n, _) in enumerate(batch) if r.done + n == r.prompt.numel()]
+        starts = None
+        if plan["start_list"].numel():
+            starts = {k: dev(plan[k]) for k in ("start_slots", "start_rows", "start_list")}
+        prefill = InferenceParams(max_seqlen=self.max_seqlen, max_batch_size=self.prefill_rows, key_value_memory_dict=self.pool,
+                                  prefill_slots=dev(plan["end_slots"]), prefill_starts=starts)
+        # the head runs on the pieces that end their prompt; a pass of inner pieces alone still needs one position: its logits are dropped
+        pos = plan["logits_positions"][last] if last else plan["logits_positions"][:1]
+        logits = self.model(ids, inference_params=prefill, seq_idx=dev(plan["seq_idx"]), logits_positions=dev(pos)).logits
+        self.n_prefill_passes += 1
+        self.n_prefill_pieces += len(batch)
+        self.prefill_pass_tokens.append(sum(n for _, n, _ in batch))
+        for r, n, _ in batch:
+            r.done += n
+        self._prefilling = ([r for r in self._prefilling if r.done < r.prompt.numel()]
+                            + [r for r, _, resumed in batch if not resumed and r.done < r.prompt.numel()])
+        if not last:
+            return
+        ready = [batch[i][0] for i in last]
+        u = None if not self.fused_sampling else dev(torch.stack([r.uniforms[0] for r in ready]))
+        first = torch.empty(len(ready), dtype=torch.long, device=self.device)
+        self._sample_into(logits, u, first)
+        row_idx = dev(torch.tensor([r.row for r in ready], dtype=torch.long))
+        self.first.index_copy_(0, row_idx, first)
+        self.input_ids.index_copy_(0, row_idx, first.view(-1, 1))
+        self.slots.index_copy_(0, row_idx, dev(torch.tensor([r.slot for r in ready], dtype=torch.int32)))
+        for i, r in enumerate(ready):
+            if self.output_scores:
+                r.scores.append(self._view(logits)[i].clone())
+            self._fresh.add(r.row)
+
     def _admit(self):
+        if self.chunked_prefill:
+            return self._admit_chunked()
         if self.packed_prefill:
             return self._admit_packed()
         while self.queue and self.free_slots and None in self.rows:
@@ -267,6 +344,7 @@ class DecodeEngine:
         admitted in this step, then the step's token"""
         self._admit()
         live = [(row, self.requests[rid]) for row, rid in enumerate(self.rows) if rid is not None]
+        live = [(row, r) for row, r in live if r.done == 0 or r.done == r.prompt.numel()]        # a prefilling request only holds its row
         if not live:
             return []
         fresh, self._fresh = self._fresh, set()

@@ -390,6 +390,30 @@ typedef struct {
 
 int dimsum_ssm_scan_varlen_states_fwd(const dimsum_ssm_varlen_states_params_t *p, void *stream);
 
+/* dimsum_ssm_scan_varlen_states_fwd whose segments may CONTINUE a stored state (forward only; see dimsum_conv_varlen_resume_params_t for
+ * start_slots): where start_slots[b, t] = s >= 0 the state entering position t is init[s, d, n] where the plain entry uses 0 -- at a
+ * boundary, and at t = 0. `init` is (n_init, dim, dstate) with three free ELEMENT strides, float32 (init_f32 != 0) or of scan.dtype.
+ * init MAY BE the pool `states.state_ptr` stores into: each (channel, state) element is loaded, at the segment's first step, and stored, at
+ * the segment's end, by ONE lane in its own program order. For that to hold a slot stored in this launch may be read only by the segment
+ * that stores it (the caller's contract, not checked).
+ * Checks, in this order: NULL struct / struct_size (DIMSUM_ERR_ABI) / n_init < 1 (DIMSUM_ERR_SHAPE) / start_slots_ptr or init_ptr NULL
+ * (DIMSUM_ERR_NULL) / a negative start_slots_batch_stride or one below seqlen with batch > 1, or a negative init stride (DIMSUM_ERR_STRIDE) /
+ * dimsum_ssm_scan_varlen_states_fwd's checks on the embedded struct in their order (its struct_size is ignored). Nothing is launched,
+ * allocated or synchronised before all of them pass. One launch. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_ssm_varlen_resume_params_t) */
+    int32_t n_init;           /* rows of init, >= 1 */
+    dimsum_ssm_varlen_states_params_t states;
+    const void *start_slots_ptr;      /* int32 (batch, seqlen), unit stride along seqlen */
+    int64_t start_slots_batch_stride;
+    const void *init_ptr;
+    int64_t init_slot_stride, init_d_stride, init_dstate_stride;
+    int32_t init_f32;         /* != 0: init is float32; 0: of scan.dtype */
+    int32_t reserved;         /* 0 */
+} dimsum_ssm_varlen_resume_params_t;
+
+int dimsum_ssm_scan_varlen_resume_fwd(const dimsum_ssm_varlen_resume_params_t *p, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Training-step tail: global gradient-norm clip + AdamW + parameter EMA over a list of fp32 tensors, two launches
  * (<- torch.nn.utils.clip_grad_norm_, torch.optim.AdamW.step and update_ema of dimsum/train.py:55-64,317-321).
@@ -702,6 +726,35 @@ typedef struct {
 } dimsum_conv_varlen_states_params_t;
 
 int dimsum_causal_conv1d_varlen_states_fwd(const dimsum_conv_varlen_states_params_t *p, void *stream);
+
+/* dimsum_causal_conv1d_varlen_states_fwd whose segments may CONTINUE a carried conv state (forward only): a long prompt fed in pieces.
+ *   start_slots : (batch, seqlen) int32 laid out like end_slots. start_slots[b, t] = s >= 0 is allowed only where t is the first position
+ *       of a segment (t == 0 or seq_idx[b, t] != seq_idx[b, t - 1]): the segment beginning at t continues init[s]. A negative entry is
+ *       the plain entry's behaviour (zero state, dropped taps). A non-negative entry anywhere else, or one >= n_init, is undefined
+ *       behaviour (not checked: it would take a device read).
+ *   init : (n_init, dim, width) of conv.dtype (init_dtype, else DIMSUM_ERR_UNSUPPORTED), three free ELEMENT strides: the last `width`
+ *       inputs of the earlier piece, newest last. Every tap of an output in [t, t + width - 2] that reaches before t reads
+ *       x[t - k] := init[s, d, width - k] where the plain entry uses 0, and a state stored through end_slots is the last `width` values of
+ *       concat(init[s], the segment) (the carried values shift left in a segment shorter than width - 1). The elements are moved, not
+ *       converted. init MUST NOT OVERLAP a slot of the pool that this launch stores: different lanes (and, in a long row, different loop
+ *       steps) read and write one slot (the caller's contract; the Python operator compares the storage ranges).
+ * Checks, in this order: NULL struct / struct_size (DIMSUM_ERR_ABI) / n_init < 1 (DIMSUM_ERR_SHAPE) / start_slots_ptr or init_ptr NULL
+ * (DIMSUM_ERR_NULL) / a negative start_slots_batch_stride or one below seqlen with batch > 1, or a negative init stride (DIMSUM_ERR_STRIDE) /
+ * dimsum_causal_conv1d_varlen_states_fwd's checks on the embedded struct in their order (its struct_size is ignored) / init_dtype !=
+ * conv.dtype (DIMSUM_ERR_UNSUPPORTED). Nothing is launched, allocated or synchronised before all of them pass. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_conv_varlen_resume_params_t) */
+    int32_t n_init;           /* rows of init, >= 1 */
+    dimsum_conv_varlen_states_params_t states;
+    const void *start_slots_ptr;
+    int64_t start_slots_batch_stride;
+    const void *init_ptr;
+    int64_t init_slot_stride, init_c_stride, init_w_stride;
+    int32_t init_dtype;       /* dimsum_dtype_t of init: must equal conv.dtype */
+    int32_t reserved;         /* 0 */
+} dimsum_conv_varlen_resume_params_t;
+
+int dimsum_causal_conv1d_varlen_resume_fwd(const dimsum_conv_varlen_resume_params_t *p, void *stream);
 
 /* The same conv on CHANNEL-LAST operands (causal_conv1d_channellast_fwd_kernel / _bwd_kernel, causal-conv1d/csrc/
  * causal_conv1d_fwd.cu:193-319, causal_conv1d_bwd.cu:306-494; host checks causal_conv1d.cpp:242-247, 376-379, 395-396):

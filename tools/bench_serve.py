@@ -24,7 +24,11 @@ both: instead of the two comparisons above, the engine with packed admission aga
 workload (alternating round by round after a warm-up round of each; median and max / min spread of `--rounds`), then an admission-only
 timing: k = 1, 4, 16 prompts of 64 tokens admitted into an idle engine of max_batch 16, packed against alone, between two synchronisations.
 
-    python tools/bench_serve.py [--batches 4 16] [--rounds 5] [--requests 64] [--dtype float32] [--packed-prefill off|on|both] [--out serve_bench.json]
+--chunked-prefill both: chunked admission (DecodeEngine(chunked_prefill=True)) against unchunked packed admission at the same
+--max-prefill-tokens, alternating in one process, on the workload with --long-prompts prompts of --long-len tokens among the short ones:
+useful tok/s and the LARGEST single step() wall time (the decode stall), median of --rounds with the spread.
+    python tools/bench_serve.py [--batches 4 16] [--rounds 5] [--requests 64] [--dtype float32] [--packed-prefill off|on|both]
+                                [--chunked-prefill off|on|both --max-prefill-tokens 512 --long-prompts 4 --long-len 4096] [--out serve_bench.json]
 prints one JSON line per measurement and two markdown tables at the end."""
 import argparse
 import json
@@ -104,6 +108,56 @@ def packed_bench(model, requests, B, rounds):
     return row
 
 
+def run_engine_steps(eng, requests):
+    """run_engine, step by step -> (wall time, the largest single step() wall time: what a live decode row waits behind an admission)"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    rids = [eng.submit(p, n) for p, n in requests]
+    worst = 0.0
+    while not eng.idle():
+        t1 = time.perf_counter()
+        eng.step()
+        torch.cuda.synchronize()                             # a step without a live row returns before the host read: its prompt pass counts here
+        worst = max(worst, time.perf_counter() - t1)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert all(eng.sequence(r).numel() == p.numel() + n for r, (p, n) in zip(rids, requests))
+    eng.requests.clear()
+    return dt, worst
+
+
+def chunked_bench(model, requests, B, rounds, budget, long_prompts, long_len, seed=0):
+    """chunked admission against unchunked packed admission at the same max_prefill_tokens, alternating round by round, on the workload
+    with `long_prompts` prompts of `long_len` tokens put among the short ones (evenly spaced)"""
+    from dimsum_amd.utils.serving import DecodeEngine
+    g = torch.Generator().manual_seed(seed + 1)
+    requests = list(requests)
+    for i in range(long_prompts):
+        at = (i + 1) * len(requests) // (long_prompts + 1)
+        requests[at] = (torch.randint(0, SHAPE["vocab_size"], (long_len,), generator=g), requests[at][1])
+    useful = sum(n for _, n in requests)
+    kw = dict(max_batch=B, num_slots=B, max_seqlen=long_len + NEW_RANGE[1], vocab_size=SHAPE["vocab_size"], cg=True, packed_prefill=True,
+              max_prefill_tokens=budget)
+    engines = {"unchunked": DecodeEngine(model, **kw), "chunked": DecodeEngine(model, chunked_prefill=True, **kw)}
+    for eng in engines.values():
+        run_engine_steps(eng, requests)                      # warm-up round of each (the capture)
+    times, worst = {k: [] for k in engines}, {k: [] for k in engines}
+    for _ in range(rounds):
+        for k, eng in engines.items():
+            dt, w = run_engine_steps(eng, requests)
+            times[k].append(dt)
+            worst[k].append(w)
+    row = dict(batch=B, requests=len(requests), useful_tokens=useful, rounds=rounds, max_prefill_tokens=budget, long_prompts=long_prompts,
+               long_len=long_len, prompt_passes={k: eng.n_prefill_passes // (rounds + 1) for k, eng in engines.items()})
+    for k in engines:
+        row[f"{k}_tokens_per_s"] = round(useful / statistics.median(times[k]), 1)
+        row[f"spread_{k}"] = round(max(times[k]) / min(times[k]), 3)
+        row[f"{k}_max_step_ms"] = round(1e3 * statistics.median(worst[k]), 2)
+        row[f"spread_max_step_{k}"] = round(max(worst[k]) / min(worst[k]), 3)
+    row["chunked_over_unchunked"] = round(row["chunked_tokens_per_s"] / row["unchunked_tokens_per_s"], 3)
+    return row
+
+
 def admission_bench(model, k, rounds, prompt_len=64, B=16):
     """the time of admitting k prompts of prompt_len tokens into an idle engine (prompt passes, first-token sampling, the scatter into the
     step's buffers; no decode step), packed against alone"""
@@ -143,14 +197,15 @@ def admission_bench(model, k, rounds, prompt_len=64, B=16):
     return row
 
 
-def serve_bench(model, requests, B, rounds, packed=False):
+def serve_bench(model, requests, B, rounds, packed=False, chunked=None):
     from dimsum_amd.utils.serving import DecodeEngine
     useful = sum(n for _, n in requests)
     batches = [(ids.cuda(), seq.cuda(), m) for ids, seq, m in static_batches(requests, B)]
     decoded = sum(ids.shape[0] * (m - ids.shape[1]) for ids, _, m in batches)
     model._decoding_cache = None
     eng = DecodeEngine(model, max_batch=B, num_slots=B, max_seqlen=PROMPT_RANGE[1] + NEW_RANGE[1], vocab_size=SHAPE["vocab_size"], cg=True,
-                       packed_prefill=packed)
+                       packed_prefill=packed or chunked is not None,
+                       **({"chunked_prefill": True, "max_prefill_tokens": chunked} if chunked is not None else {}))
     # the static side's cache at its final size before anything is timed: the longest batch first, so no later batch re-captures
     longest = max(batches, key=lambda b: b[2])
     model.generate(longest[0], max_length=longest[2], cg=True, fused_sampling=True, vocab_size=SHAPE["vocab_size"], seq_idx=longest[1])
@@ -228,6 +283,11 @@ def main():
     ap.add_argument("--dtype", default="float32")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--packed-prefill", choices=["off", "on", "both"], default="off")
+    ap.add_argument("--chunked-prefill", choices=["off", "on", "both"], default="off",
+                    help="on: the engine of the default comparison admits in chunks; both: chunked against unchunked packed admission")
+    ap.add_argument("--max-prefill-tokens", type=int, default=512, help="the admission budget of --chunked-prefill")
+    ap.add_argument("--long-prompts", type=int, default=4, help="--chunked-prefill both: prompts of --long-len tokens among the short ones")
+    ap.add_argument("--long-len", type=int, default=4096)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_serve needs the GPU"
@@ -236,6 +296,21 @@ def main():
     torch.manual_seed(0)
     model = MambaLMHeadModel(**SHAPE, device="cuda", dtype=getattr(torch, args.dtype)).eval()
     requests = workload(args.requests, args.seed)
+    if args.chunked_prefill == "both":
+        rows = [dict(chunked_bench(model, requests, B, args.rounds, args.max_prefill_tokens, args.long_prompts, args.long_len, args.seed),
+                     dtype=args.dtype, fused_decode=policy or "unset") for B in args.batches]
+        for row in rows:
+            print(json.dumps(row), flush=True)
+        print("\n| B | budget | unchunked tok/s (spread) | chunked tok/s (spread) | chunked / unchunked | largest step ms unchunked (spread) | "
+              "largest step ms chunked (spread) |\n|---|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['batch']} | {r['max_prefill_tokens']} | {r['unchunked_tokens_per_s']:.0f} ({r['spread_unchunked']:.3f}) | "
+                  f"{r['chunked_tokens_per_s']:.0f} ({r['spread_chunked']:.3f}) | {r['chunked_over_unchunked']:.3f} | "
+                  f"{r['unchunked_max_step_ms']:.2f} ({r['spread_max_step_unchunked']:.3f}) | {r['chunked_max_step_ms']:.2f} ({r['spread_max_step_chunked']:.3f}) |")
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(dict(chunked=rows), f, indent=1)
+        return
     if args.packed_prefill == "both":
         packed = [dict(packed_bench(model, requests, B, args.rounds), dtype=args.dtype, fused_decode=policy or "unset") for B in args.batches]
         admit = [dict(admission_bench(model, k, args.rounds), dtype=args.dtype) for k in (1, 4, 16)]
@@ -254,7 +329,8 @@ def main():
         return
     serve, steps = [], []
     for B in args.batches:
-        row = dict(serve_bench(model, requests, B, args.rounds, packed=args.packed_prefill == "on"), dtype=args.dtype, fused_decode=policy or "unset")
+        row = dict(serve_bench(model, requests, B, args.rounds, packed=args.packed_prefill == "on",
+                               chunked=args.max_prefill_tokens if args.chunked_prefill == "on" else None), dtype=args.dtype, fused_decode=policy or "unset")
         serve.append(row)
         print(json.dumps(row), flush=True)
     for B in args.batches:
