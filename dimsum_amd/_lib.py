@@ -309,6 +309,14 @@ class DecodeLinearSlotsParams(_Sized):
     _fields_ = [("struct_size", u32), ("num_slots", i32), ("linear", DecodeLinearParams), ("slots_ptr", vp), ("slots_stride", i64)]
 
 
+class StateCopyParams(_Sized):
+    """dimsum_state_copy_params_t: rows src -> dst of every tensor of a state pool, pairs and the pool's table read on the device"""
+    _fields_ = [("struct_size", u32), ("num_slots", i32), ("n_tensors", i32), ("n_pairs", i32), ("table_ptr", vp), ("pairs_ptr", vp),
+                ("pairs_stride", i64), ("max_row_bytes", i64), ("reserved", i64 * 2)]
+
+
+STATE_COPY_CHUNK_BYTES = 16384           # DIMSUM_STATE_COPY_CHUNK_BYTES
+
 DECODE_NORM_NONE, DECODE_NORM_LAYER, DECODE_NORM_RMS = 0, 1, 2
 DECODE_MAX_BATCH = 16
 
@@ -492,7 +500,7 @@ EXPORTS = (
     "dimsum_einfft_dft", "dimsum_einfft_idft_real", "dimsum_einfft_mlp_fwd", "dimsum_einfft_mlp_bwd",
     "dimsum_causal_conv1d_fwd", "dimsum_causal_conv1d_bwd", "dimsum_causal_conv1d_update", "dimsum_selective_state_update",
     "dimsum_decode_linear", "dimsum_cross_entropy_fwd", "dimsum_cross_entropy_bwd", "dimsum_sample_logits",
-    "dimsum_causal_conv1d_update_slots", "dimsum_selective_state_update_slots", "dimsum_decode_linear_slots",
+    "dimsum_causal_conv1d_update_slots", "dimsum_selective_state_update_slots", "dimsum_decode_linear_slots", "dimsum_state_copy_slots",
     "dimsum_causal_conv1d_cl_fwd", "dimsum_causal_conv1d_cl_bwd",
     "dimsum_norm_fwd", "dimsum_norm_bwd", "dimsum_token_transform", "dimsum_xattn_fusion_fwd", "dimsum_xattn_fusion_bwd",
     "dimsum_gated_gelu_fwd", "dimsum_gated_gelu_bwd", "dimsum_gated_gelu_fwd_split3", "dimsum_gated_gelu_bwd_split3", "dimsum_gated_gelu_bwd_pair", "dimsum_gated_gelu_bwd_f16s", "dimsum_split3", "dimsum_split3_t",
@@ -532,7 +540,7 @@ _SIGNATURES = (
         ("dimsum_causal_conv1d_varlen_fwd", ConvVarlenParams), ("dimsum_causal_conv1d_varlen_bwd", ConvVarlenBwdParams),
         ("dimsum_ssm_scan_varlen_fwd", SsmVarlenParams), ("dimsum_ssm_scan_varlen_bwd", SsmVarlenBwdParams),
         ("dimsum_causal_conv1d_update_slots", ConvUpdateSlotsParams), ("dimsum_selective_state_update_slots", StateUpdateSlotsParams),
-        ("dimsum_decode_linear_slots", DecodeLinearSlotsParams),
+        ("dimsum_decode_linear_slots", DecodeLinearSlotsParams), ("dimsum_state_copy_slots", StateCopyParams),
         ("dimsum_causal_conv1d_varlen_states_fwd", ConvVarlenStatesParams), ("dimsum_ssm_scan_varlen_states_fwd", SsmVarlenStatesParams),
         ("dimsum_causal_conv1d_varlen_resume_fwd", ConvVarlenResumeParams), ("dimsum_ssm_scan_varlen_resume_fwd", SsmVarlenResumeParams))]
     # the gated-GeLU passes: n pointers, rows, cols, stream

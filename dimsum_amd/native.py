@@ -756,7 +756,84 @@ def decode_linear(x, weight, bias=None, norm=None, residual=None, residual_out=N
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the LM loss over rows of logits   (csrc/cross_entropy.hip; the reference's training recipes use a fused cross-entropy here)
+# duplicating slots of a state pool: every layer's conv_state and ssm_state in one launch (csrc/state_copy.hip; no reference counterpart;
+# dimsum_amd/utils/serving.py is the user)
+# ---------------------------------------------------------------------------------------------------------------------
+class StatePoolTable:
+    """what state_copy_slots needs to know about a pool, built once and kept: `tensors` (the pool's tensors in layer order: they stay alive
+    with the table), `num_slots`, `device`, `max_row_bytes`, and `table`, the device int64 (n_tensors, 3) of {base pointer, slot stride in
+    bytes, row bytes} the kernel reads (None on the torch stand-in)"""
+
+    def __init__(self, tensors, num_slots, table=None):
+        self.tensors, self.num_slots, self.table = tensors, num_slots, table
+        self.device = tensors[0].device
+        self.max_row_bytes = max(t[0].numel() * t.element_size() for t in tensors)
+
+
+def state_pool_tensors(pool, who="state_pool_table"):
+    """the checks of a pool that need no GPU -> (its tensors in layer order, num_slots). pool: a key_value_memory_dict, {layer: (conv_state,
+    ssm_state)} with every tensor (num_slots, ...), each slot's row contiguous (the slot stride is free: a view of a larger buffer is fine)"""
+    _check(isinstance(pool, dict) and len(pool) > 0, f"{who}: the pool is a non-empty dict {{layer: (conv_state, ssm_state)}}")
+    tensors = [t for key in sorted(pool) for t in pool[key]]
+    _check(all(torch.is_tensor(t) and t.dim() >= 2 and t.shape[0] >= 1 and t[0].numel() >= 1 for t in tensors),
+           f"{who}: every state of the pool must be a tensor (num_slots >= 1, ...) with non-empty rows")
+    slots = sorted({t.shape[0] for t in tensors})
+    _check(len(slots) == 1, f"{who}: every tensor of the pool must have the same num_slots, got {slots}")
+    _check(all(t[0].is_contiguous() and (t.shape[0] == 1 or t.stride(0) >= t[0].numel()) for t in tensors),
+           f"{who}: every slot's row must be contiguous and the slots must not overlap")
+    devices = sorted({str(t.device) for t in tensors})
+    _check(len(devices) == 1, f"{who}: the pool must live on one device, got {devices}")
+    return tensors, slots[0]
+
+
+def state_pool_table(pool):
+    """-> StatePoolTable of a key_value_memory_dict (see state_pool_tensors). The table's values travel as kernel arguments on the current
+    stream (optim_write_ptrs): no staging buffer, no synchronisation."""
+    tensors, num_slots = state_pool_tensors(pool)
+    _gpu(*tensors)
+    table = torch.empty((len(tensors), 3), dtype=torch.int64, device=tensors[0].device)
+    rows = [v for t in tensors for v in (t.data_ptr(), t.stride(0) * t.element_size(), t[0].numel() * t.element_size())]
+    optim_write_ptrs(table.view(-1), 0, rows)
+    return StatePoolTable(tensors, num_slots, table)
+
+
+def state_copy_pairs(pairs, num_slots, who="state_copy_slots"):
+    """a host list of (src, dst) pairs checked -> int32 (n_pairs, 2) on the host. A pair with a negative index is padding. Refused: an index
+    >= num_slots; a dst named twice; a dst that is also a src (the copy would read a row another pair writes)."""
+    pairs = [(int(s), int(d)) for s, d in pairs]
+    _check(all(s < num_slots and d < num_slots for s, d in pairs), f"{who}: a slot index is out of range for num_slots = {num_slots}: {pairs}")
+    live = [(s, d) for s, d in pairs if s >= 0 and d >= 0]
+    dsts = [d for _, d in live]
+    _check(len(set(dsts)) == len(dsts), f"{who}: a dst slot is named twice: {pairs}")
+    _check(not set(dsts) & {s for s, _ in live}, f"{who}: a dst slot is also a src: {pairs}")
+    return torch.tensor(pairs, dtype=torch.int32).view(-1, 2)
+
+
+def state_copy_slots(table, pairs):
+    """for every pair (src, dst): slot dst of EVERY tensor of the pool := slot src, bit for bit, in ONE launch on the current stream.
+    table: state_pool_table(pool). pairs: a host list of pairs (checked by state_copy_pairs, then uploaded), or a device int32 (n_pairs, 2)
+    tensor taken as is -- the kernel reads it, skips pairs with a negative or out-of-range index, and under graph capture copies what the
+    buffer holds at replay. The result is defined when no dst is another pair's src or dst."""
+    _check(isinstance(table, StatePoolTable) and table.table is not None, "state_copy_slots: table must come from state_pool_table")
+    if not torch.is_tensor(pairs):
+        pairs = state_copy_pairs(pairs, table.num_slots)
+        if pairs.shape[0] == 0:
+            return
+        pairs = pairs.to(table.device, non_blocking=True)
+    _check(pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.stride(1) == 1
+           and (pairs.shape[0] <= 1 or pairs.stride(0) >= 2), "state_copy_slots: pairs must be an int32 (n_pairs, 2) tensor with unit stride along a pair")
+    _check(pairs.is_cuda and pairs.device == table.device, "state_copy_slots: pairs must be a GPU tensor on the pool's device")
+    if pairs.shape[0] == 0:
+        return
+    P = _lib.StateCopyParams()
+    P.num_slots, P.n_tensors, P.n_pairs = table.num_slots, len(table.tensors), pairs.shape[0]
+    P.table_ptr, P.pairs_ptr, P.pairs_stride, P.max_row_bytes = _ptr(table.table), _ptr(pairs), max(pairs.stride(0), 2), table.max_row_bytes
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.load().dimsum_state_copy_slots(P, _stream(pairs)), "state_copy_slots")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the LM loss over rows of logits  (csrc/cross_entropy.hip; the reference's training recipes use a fused cross-entropy here)
 # ---------------------------------------------------------------------------------------------------------------------
 def _cross_entropy_params(logits, labels, label_smoothing, logit_scale, lse_square_scale, ignore_index, what):
     _check(logits.dim() == 2 and logits.dtype in _DT and logits.shape[0] >= 1 and logits.shape[1] >= 1,

@@ -20,3 +20,4 @@ from .selective_scan_interface import (  # noqa: F401
     selective_scan_varlen_torch,
 )
 from .selective_state_update import selective_scan_carry_torch, selective_state_update, selective_state_update_torch  # noqa: F401
+from .state_copy import state_copy_slots_torch, state_pool_table_torch  # noqa: F401

@@ -37,8 +37,19 @@ queue order before new requests, as segments that RESUME their slot (plan_packed
 kStart kernels). The piece that ends the prompt is in logits_positions, is sampled with uniforms[0] and joins the
 decode batch exactly as a packed admission does. So a long prompt delays the live rows by bounded passes instead of one long one.
 
+Held states (chunked_prefill=True only): a held state is a slot the engine does not free -- (slot, tokens consumed,
+pending token or None) under a handle from the request-id counter. `hold(prefix)` queues a prefill-only entry in the same FIFO: admitted in
+pieces like a chunked request, it claims a slot and no row, nothing is sampled, and when its last piece is in the handle is ready.
+`submit(..., start=h)` continues a held state: a fork (move=False) claims a new slot, all forks of one admission are copied by ONE
+native.state_copy_slots launch before the prompt pass, and the request enters it as a resumed piece over [pending] + prompt_ids; a session
+turn (move=True) takes over the handle's slot, no copy, the handle is consumed. A request whose handle is not ready waits at the queue's head.
+`keep=True` turns a finished request's slot into a ready handle under its rid: its last generated token was sampled but never fed, so the
+state covers the prompt and tokens[:-1] and that token is `pending` (a request ended by its first token has fed it in the step of its
+admission: nothing is pending). `submit_n` draws n samples from one prefill; `release(h)` frees a handle; `held` lists the ready ones.
+
 Documented limits: prefill stalls the batch (by at most max_prefill_tokens tokens per step with chunked_prefill); without chunked_prefill a
-packed admission starts every slot from zero state; a finished request's slot is not kept for a later turn; max_batch above 16 runs the unfused step (with slots); no prefix or state sharing between requests; no preemption.
+packed admission starts every slot from zero state; max_batch above 16 runs the unfused step (with slots); no automatic (hash-keyed) prefix
+matching: the caller names the handle; no preemption.
 Sampling: `fused_sampling=True` draws token i of a request with uniforms[i] of THAT request (given to `submit`, or drawn there from the
 engine's generator) whichever row and step it lands on, so a request's output does not depend on its neighbours or on the schedule;
 `fused_sampling=False` runs generation.sample() per step on the batch's logits, whose multinomial draws (top_k != 1) come from one shared
@@ -66,13 +77,32 @@ class _Request:
     slot: int = -1
     row: int = -1
     finished: bool = False
-    done: int = 0                             # chunked prefill: prompt tokens already prefilled into the slot
+    done: int = 0                             # chunked prefill: tokens of `feed` already prefilled into the slot
+    feed: Optional[torch.Tensor] = None       # what the prompt passes consume: the prompt, behind the pending token of the state it starts from
+    history: Optional[torch.Tensor] = None    # the tokens of the held state it starts from (its pending token included), or None
+    start: Optional["_Held"] = None           # the held state it starts from
+    move: bool = False                        # it takes over start's slot (a session turn); else start's slot is copied (a fork)
+    keep: bool = False                        # when it finishes its slot becomes a held state
+    handle: Optional["_Held"] = None          # a prefill-only entry (`hold`): the held state it fills; it takes a slot and no row
+
+
+@dataclasses.dataclass
+class _Held:
+    hid: int
+    tokens: torch.Tensor                      # (consumed,) int64 on the model's device: every token the slot's state covers once it is ready
+    slot: int = -1
+    pending: Optional[int] = None             # a token that was sampled but never fed to the model: whoever continues feeds it first
+    ready: bool = False
+    users: int = 0                            # queued forks that have not been admitted yet
+    auto_release: bool = False                # submit_n: released when its last fork is admitted
 
 
 class DecodeEngine:
     """eng = DecodeEngine(model, max_batch, num_slots=None, max_seqlen=..., top_k=1, top_p=0.0, temperature=1.0, eos_token_id=None,
                           vocab_size=None, cg=True, fused_sampling=True, packed_prefill=False, prefill_rows=1, max_prefill_tokens=None)
     rid = eng.submit(prompt_ids, max_new_tokens, uniforms=None)    1-D prompt; uniforms (max_new_tokens,) float32 pins the draws
+    h = eng.hold(prefix_ids); eng.submit(..., start=h, move=False, keep=False); eng.submit_n(prompt_ids, max_new_tokens, n); eng.release(h);
+    eng.held; eng.context(rid)                                     held states: shared prefixes, forks, kept sessions (module docstring)
     events = eng.step()                                            [(rid, token, finished)]: admissions' first tokens, then one decode step
     results = eng.run()                                            until idle -> {rid: LongTensor prompt + generated}
     model: a MambaLMHeadModel (anything with allocate_inference_cache and forward(ids, inference_params=, num_last_tokens=) -> .logits).
@@ -127,14 +157,100 @@ class DecodeEngine:
         self.n_captures = 0
         self._next_rid = 0
         self._graph = self._logits = None
+        self._handles = {}                                  # held states by handle id, ready or still prefilling
+        self._hold_reqs = {}                                # the prefill-only entries of `hold` until their state is ready
+        self._keeping = set()                               # unfinished requests whose slot will become a held state
+        self._pool_table = None                             # native.state_pool_table(self.pool), built at the first fork
 
     # ---- the request side --------------------------------------------------------------------------------------------------------------------
-    def submit(self, prompt_ids, max_new_tokens, uniforms=None):
-        """queues a request -> its id. prompt_ids: 1-D, at least one token. uniforms (max_new_tokens,) float32 in [0, 1): draw i of this
-        request (fused sampling); None: drawn here from the engine's generator."""
+    def _need_chunked(self, what):
+        if not self.chunked_prefill:
+            raise ValueError(f"DecodeEngine: {what} rides on chunked admission and the resume kernels: it needs an engine with chunked_prefill=True")
+
+    def _handle(self, h):
+        if h not in self._handles:
+            raise KeyError(f"DecodeEngine: {h!r} is not a held state (never held, released, or consumed by a move=True request)")
+        return self._handles[h]
+
+    def _room_to_hold(self, what):
+        if len(self._handles) + len(self._keeping) + 1 >= self.num_slots:
+            raise ValueError(f"DecodeEngine.{what}: every one of the {self.num_slots} slots would then be held and no request could be admitted")
+
+    def _id(self):
+        self._next_rid += 1
+        return self._next_rid - 1
+
+    def hold(self, prefix_ids):
+        """queues a prefill-only entry -> a handle. Admitted like a chunked request, it claims a slot and no row; nothing is sampled. Once all
+        of prefix_ids is in the slot the handle is ready (`held`): submit(..., start=handle) continues from it."""
+        self._need_chunked("hold")
+        prefix = torch.as_tensor(prefix_ids, dtype=torch.long)
+        if prefix.dim() != 1 or prefix.numel() < 1:
+            raise ValueError("DecodeEngine.hold: prefix_ids must be 1-D with at least one token")
+        self._room_to_hold("hold")
+        hid = self._id()
+        prefix = prefix.to(self.device)
+        self._handles[hid] = h = _Held(hid, prefix)
+        self._hold_reqs[hid] = _Request(hid, prefix, 0, None, feed=prefix, handle=h)
+        self.queue.append(hid)
+        return hid
+
+    def release(self, h):
+        """frees a ready held state's slot; the handle is gone"""
+        held = self._handle(h)
+        if not held.ready or held.users:
+            raise ValueError(f"DecodeEngine.release: held state {h} is {'still prefilling' if not held.ready else 'awaited by queued forks'}")
+        del self._handles[h]
+        self.free_slots.append(held.slot)
+
+    @property
+    def held(self):
+        """{handle: (slot, tokens consumed, pending token or None)} of the ready held states"""
+        return {hid: (h.slot, h.tokens.numel(), h.pending) for hid, h in self._handles.items() if h.ready}
+
+    def submit_n(self, prompt_ids, max_new_tokens, n, uniforms=None):
+        """n samples of one prompt -> their ids: the prompt but its last token is prefilled ONCE into a held state, n forks continue it with
+        the last token, and the hold is released when the last fork is admitted. uniforms: (n, max_new_tokens), row i pins sample i."""
         prompt = torch.as_tensor(prompt_ids, dtype=torch.long)
-        if prompt.dim() != 1 or prompt.numel() < 1 or int(max_new_tokens) < 1:
-            raise ValueError("DecodeEngine.submit: prompt_ids must be 1-D with at least one token, max_new_tokens >= 1")
+        if prompt.dim() != 1 or prompt.numel() < 1 or int(n) < 1:
+            raise ValueError("DecodeEngine.submit_n: prompt_ids must be 1-D with at least one token, n >= 1")
+        if uniforms is not None and len(uniforms) != int(n):
+            raise ValueError(f"DecodeEngine.submit_n: uniforms must be (n, max_new_tokens) = ({int(n)}, {int(max_new_tokens)})")
+        rows = [None] * int(n) if uniforms is None else list(uniforms)
+        if prompt.numel() == 1:
+            return [self.submit(prompt, max_new_tokens, u) for u in rows]
+        self._need_chunked("submit_n")
+        h = self.hold(prompt[:-1])
+        try:
+            rids = [self.submit(prompt[-1:], max_new_tokens, u, start=h) for u in rows]
+        except Exception:
+            held = self._handles[h]                          # nothing of a refused call stays queued
+            for rid in [i for i in self.queue if i in self.requests and self.requests[i].start is held]:
+                self.queue.remove(rid)
+                del self.requests[rid]
+            self.queue.remove(h)
+            del self._handles[h], self._hold_reqs[h]
+            raise
+        self._handles[h].auto_release = True
+        return rids
+
+    def submit(self, prompt_ids, max_new_tokens, uniforms=None, start=None, move=False, keep=False):
+        """queues a request -> its id. prompt_ids: 1-D, at least one token. uniforms (max_new_tokens,) float32 in [0, 1): draw i of this
+        request (fused sampling); None: drawn here from the engine's generator.
+        start: a handle (`hold`, or the id of a finished keep=True request) -- the request's context is the held state, then prompt_ids, which
+        may be empty when the state has a pending token. move=False: a fork, the state is copied into a new slot and the handle stays;
+        move=True: a session turn, the request takes over the handle's slot and the handle is consumed. keep=True: when the request
+        finishes its slot is not freed and its id becomes a ready handle (module docstring)."""
+        prompt = torch.as_tensor(prompt_ids, dtype=torch.long)
+        if start is not None or keep or move:
+            self._need_chunked("start= / move= / keep=")
+        if move and start is None:
+            raise ValueError("DecodeEngine.submit: move=True takes over the slot of a held state: it needs start=")
+        held = None if start is None else self._handle(start)
+        fewest = 0 if held is not None and held.pending is not None else 1
+        if prompt.dim() != 1 or prompt.numel() < fewest or int(max_new_tokens) < 1:
+            raise ValueError("DecodeEngine.submit: prompt_ids must be 1-D with at least one token (none is needed behind a held state's pending "
+                             "token), max_new_tokens >= 1")
         max_new_tokens = int(max_new_tokens)
         if self.fused_sampling:
             if uniforms is None:
@@ -144,11 +260,27 @@ class DecodeEngine:
                 raise ValueError(f"DecodeEngine.submit: uniforms must be (max_new_tokens,) = ({max_new_tokens},) float32, got {tuple(uniforms.shape)} {uniforms.dtype}")
         elif uniforms is not None:
             raise ValueError("DecodeEngine.submit: uniforms pin the draws of the fused sampler; this engine runs sample() (fused_sampling=False)")
-        rid = self._next_rid
-        self._next_rid += 1
-        self.requests[rid] = _Request(rid, prompt.to(self.device), max_new_tokens, uniforms)
+        if keep and not (move and held is not None):          # a kept session turn holds what its handle held
+            self._room_to_hold("submit(keep=True)")
+        rid = self._id()
+        prompt = prompt.to(self.device)
+        self.requests[rid] = r = _Request(rid, prompt, max_new_tokens, uniforms, feed=prompt, start=held, move=bool(move), keep=bool(keep))
+        if held is not None:
+            pending = [] if held.pending is None else [torch.tensor([held.pending], dtype=torch.long, device=self.device)]
+            r.history, r.feed = torch.cat([held.tokens] + pending), torch.cat(pending + [prompt])
+            if move:
+                del self._handles[start]
+            else:
+                held.users += 1
+        if keep:
+            self._keeping.add(rid)
         self.queue.append(rid)
         return rid
+
+    def context(self, rid):
+        """-> LongTensor: the full token history of a request -- the held state's tokens it started from, its prompt, what it generated"""
+        r = self.requests[rid]
+        return self.sequence(rid) if r.history is None else torch.cat([r.history.cpu(), self.sequence(rid)])
 
     def idle(self):
         return not self.queue and not self._prefilling and all(r is None for r in self.rows)
@@ -228,26 +360,47 @@ class DecodeEngine:
         for r in self._prefilling:
             if budget == 0:
                 break
-            n = min(budget, r.prompt.numel() - r.done)
+            n = min(budget, r.feed.numel() - r.done)
             batch.append((r, n, True))
             budget -= n
         free_rows = [row for row, rid in enumerate(self.rows) if rid is None]
-        while self.queue and budget > 0 and self.free_slots and free_rows:
-            r = self.requests[self.queue.popleft()]
-            r.slot, r.row = self.free_slots.pop(0), free_rows.pop(0)
-            self.rows[r.row] = r.rid                                             # the row is reserved; its entry in self.slots stays -1
+        new, copies, spent = [], [], []                 # admitted here; (src, dst) of the forks; submit_n holds whose last fork was admitted
+        while self.queue and budget > 0:
+            r = self.requests[self.queue[0]] if self.queue[0] in self.requests else self._hold_reqs[self.queue[0]]
+            held, own_slot = r.start, r.start is None or not r.move
+            if held is not None and not held.ready:                              # its state is still being prefilled: the queue keeps its order
+                break
+            if (own_slot and not self.free_slots) or (r.handle is None and not free_rows):
+                break
+            self.queue.popleft()
+            r.slot = self.free_slots.pop(0) if own_slot else held.slot
+            if held is not None and own_slot:
+                copies.append((held.slot, r.slot))
+                held.users -= 1
+                if held.auto_release and held.users == 0:
+                    spent.append(held)
+            if r.handle is None:
+                r.row = free_rows.pop(0)
+                self.rows[r.row] = r.rid                                         # the row is reserved; its entry in self.slots stays -1
+            else:
+                r.handle.slot = r.slot                                           # a hold takes no row
             self.slot_history.append((r.rid, r.slot))
-            n = min(budget, r.prompt.numel())
-            batch.append((r, n, False))
+            n = min(budget, r.feed.numel())
+            batch.append((r, n, held is not None))                               # a request behind a held state resumes its slot at once
+            new.append(r)
             budget -= n
         if not batch:
             return
+        if copies:                                                               # every fork of this admission: ONE launch, before the pass
+            if self._pool_table is None:
+                self._pool_table = native.state_pool_table(self.pool)
+            native.state_copy_slots(self._pool_table, copies)
         plan = plan_packed_prefill([n for _, n, _ in batch], [r.slot for r, _, _ in batch], rows=self.prefill_rows, resume=[f for _, _, f in batch])
         dev = lambda t: t.to(self.device, non_blocking=True)
         ids = dev(torch.zeros((self.prefill_rows, plan["seqlen"]), dtype=torch.long))
         for (r, n, _), (prow, start) in zip(batch, plan["segments"]):
-            ids[prow, start:start + n].copy_(r.prompt[r.done:r.done + n])
-        last = [i for i, (r, n, _) in enumerate(batch) if r.done + n == r.prompt.numel()]
+            ids[prow, start:start + n].copy_(r.feed[r.done:r.done + n])
+        last = [i for i, (r, n, _) in enumerate(batch) if r.done + n == r.feed.numel() and r.handle is None]
         starts = None
         if plan["start_list"].numel():
             starts = {k: dev(plan[k]) for k in ("start_slots", "start_rows", "start_list")}
@@ -261,8 +414,13 @@ class DecodeEngine:
         self.prefill_pass_tokens.append(sum(n for _, n, _ in batch))
         for r, n, _ in batch:
             r.done += n
-        self._prefilling = ([r for r in self._prefilling if r.done < r.prompt.numel()]
-                            + [r for r, _, resumed in batch if not resumed and r.done < r.prompt.numel()])
+            if r.handle is not None and r.done == r.feed.numel():               # a hold's last piece: nothing is sampled, the state is ready
+                r.handle.ready = True
+                del self._hold_reqs[r.rid]
+        for held in spent:                                                       # stream order: the copies above read the slot before it is reused
+            if self._handles.get(held.hid) is held:
+                self.release(held.hid)
+        self._prefilling = [r for r in self._prefilling + new if r.done < r.feed.numel()]
         if not last:
             return
         ready = [batch[i][0] for i in last]
@@ -332,8 +490,16 @@ class DecodeEngine:
         r.finished = self._done(r, token)
         events.append((r.rid, token, r.finished))
 
-    def _retire(self, row, r):
-        self.free_slots.append(r.slot)
+    def _retire(self, row, r, fed_last=False):
+        if r.keep:
+            # the state covers every token that was FED: the last generated token was sampled and never fed -- unless the request's first
+            # token ended it, which the step of its admission consumed (module docstring, "Scheduling")
+            fed = r.tokens if fed_last else r.tokens[:-1]
+            parts = ([] if r.history is None else [r.history]) + [r.prompt, torch.tensor(fed, dtype=torch.long, device=self.device)]
+            self._handles[r.rid] = _Held(r.rid, torch.cat(parts), r.slot, None if fed_last else r.tokens[-1], ready=True)
+            self._keeping.discard(r.rid)
+        else:
+            self.free_slots.append(r.slot)
         self.rows[row] = None
         self.slots[row:row + 1].fill_(-1)
         r.slot = r.row = -1
@@ -344,7 +510,7 @@ class DecodeEngine:
         admitted in this step, then the step's token"""
         self._admit()
         live = [(row, self.requests[rid]) for row, rid in enumerate(self.rows) if rid is not None]
-        live = [(row, r) for row, r in live if r.done == 0 or r.done == r.prompt.numel()]        # a prefilling request only holds its row
+        live = [(row, r) for row, r in live if r.done == 0 or r.done == r.feed.numel()]          # a prefilling request only holds its row
         if not live:
             return []
         fresh, self._fresh = self._fresh, set()
@@ -368,10 +534,11 @@ class DecodeEngine:
         for row, r in live:
             if row in fresh:
                 self._book(r, tokens[row], events)
+            fed_last = r.finished                            # ended by its first token, which this step has fed to the model
             if not r.finished:                               # else ended by its first token: the step's token of this row is dropped
                 if self.output_scores:
                     r.scores.append(self._view(logits)[row].clone())
                 self._book(r, tokens[self.max_batch + row], events)
             if r.finished:
-                self._retire(row, r)
+                self._retire(row, r, fed_last)
         return events

@@ -976,6 +976,37 @@ int dimsum_causal_conv1d_update_slots(const dimsum_conv_update_slots_params_t *p
 int dimsum_selective_state_update_slots(const dimsum_state_update_slots_params_t *p, void *stream);
 int dimsum_decode_linear_slots(const dimsum_decode_linear_slots_params_t *p, void *stream);
 
+/* dimsum_state_copy_slots: duplicate slots of a state pool -- ONE launch copies, for every pair (src, dst), row `src` onto row `dst` of
+ * EVERY tensor of the pool: all layers' conv_state and ssm_state (csrc/state_copy.hip; no reference counterpart). A move of bits: no
+ * conversion, no arithmetic, plain vector stores, no atomics.
+ *   table : DEVICE memory, n_tensors entries of three int64 each: {base pointer, slot stride in BYTES, row bytes}. Entry i describes a tensor
+ *       whose slot s occupies the row_bytes contiguous bytes at base + s * slot_stride, for s in [0, num_slots). The tensors may differ in
+ *       dtype and row size; slot_stride >= row_bytes (a view of a larger buffer). It is built once per pool and kept.
+ *   pairs : DEVICE int32 (n_pairs, 2), rows pairs_stride ELEMENTS apart (>= 2): pairs[i] = (src, dst), read by the kernel, never by the host,
+ *       so a captured launch copies whatever the buffer holds at replay. A pair with src < 0 or dst < 0 is skipped (the padding convention of
+ *       the *_slots entries), and so is one with an index >= num_slots: no address outside the pool is formed. One src may feed many dst.
+ *       The result is defined when no dst equals another pair's src or dst: THE CALLER'S CONTRACT.
+ *   max_row_bytes : the largest row_bytes of the table (it sizes the grid; a smaller positive value is still correct, only slower).
+ * A tensor whose base, slot stride and row bytes are all multiples of 16 moves in 16-byte pieces, any other in pieces of the largest of
+ * 4, 2, 1 bytes that divides the three; the choice is made on the device, per tensor, and gives the same bits.
+ * Checks, in this order: NULL struct / struct_size (DIMSUM_ERR_ABI) / table_ptr or pairs_ptr NULL (DIMSUM_ERR_NULL) / num_slots < 1, a
+ * negative n_tensors, n_pairs or max_row_bytes, or more (pair, tensor, chunk) workgroups than a grid holds (DIMSUM_ERR_SHAPE) /
+ * pairs_stride < 2 (DIMSUM_ERR_STRIDE). n_pairs == 0, n_tensors == 0 or max_row_bytes == 0 then returns DIMSUM_OK without a launch. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(dimsum_state_copy_params_t) */
+    int32_t num_slots;        /* rows of every tensor of the pool, >= 1 */
+    int32_t n_tensors, n_pairs;
+    const void *table_ptr;
+    const void *pairs_ptr;
+    int64_t pairs_stride;
+    int64_t max_row_bytes;
+    int64_t reserved[2];      /* 0 */
+} dimsum_state_copy_params_t;
+
+#define DIMSUM_STATE_COPY_CHUNK_BYTES 16384   /* one workgroup's share of a row per round: 256 lanes x 4 pieces of 16 bytes */
+
+int dimsum_state_copy_slots(const dimsum_state_copy_params_t *p, void *stream);
+
 /* dimsum_cross_entropy_fwd / _bwd: the LM training loss over rows of logits and its gradient (csrc/cross_entropy.hip; the reference's training
  * recipes use a fused cross-entropy in this place). Per row m, with s = logit_scale * logits[m, :] and eps = label_smoothing:
  *     lse = logsumexp(s)      z = lse_square_scale * lse^2      loss = lse - (1 - eps) s[label] - (eps / vocab) sum(s) + z

@@ -27,8 +27,14 @@ timing: k = 1, 4, 16 prompts of 64 tokens admitted into an idle engine of max_ba
 --chunked-prefill both: chunked admission (DecodeEngine(chunked_prefill=True)) against unchunked packed admission at the same
 --max-prefill-tokens, alternating in one process, on the workload with --long-prompts prompts of --long-len tokens among the short ones:
 useful tok/s and the LARGEST single step() wall time (the decode stall), median of --rounds with the spread.
+--shared-prefix P (on top of --chunked-prefill on): every request's prompt is one common P-token prefix plus its own tail (the workload's
+prompt). Two engines with chunked admission alternate round by round in one process: "full" submits the full prompts, so every request
+prefills the prefix again; "held" prefills it once (`hold`) and submits the tails as forks (`start=`), one state-copy launch per admission. Wall
+times (median, max / min spread) and the prompt tokens that went through the model on each side; then one dimsum_state_copy_slots timing:
+100 launches of 8 pairs on this model's pool between two device events, beside the same copies made layer by layer with index_copy_.
     python tools/bench_serve.py [--batches 4 16] [--rounds 5] [--requests 64] [--dtype float32] [--packed-prefill off|on|both]
-                                [--chunked-prefill off|on|both --max-prefill-tokens 512 --long-prompts 4 --long-len 4096] [--out serve_bench.json]
+                                [--chunked-prefill off|on|both --max-prefill-tokens 512 --long-prompts 4 --long-len 4096] [--shared-prefix 1024]
+                                [--out serve_bench.json]
 prints one JSON line per measurement and two markdown tables at the end."""
 import argparse
 import json
@@ -155,6 +161,89 @@ def chunked_bench(model, requests, B, rounds, budget, long_prompts, long_len, se
         row[f"{k}_max_step_ms"] = round(1e3 * statistics.median(worst[k]), 2)
         row[f"spread_max_step_{k}"] = round(max(worst[k]) / min(worst[k]), 3)
     row["chunked_over_unchunked"] = round(row["chunked_tokens_per_s"] / row["unchunked_tokens_per_s"], 3)
+    return row
+
+
+def shared_prefix_bench(model, requests, B, rounds, budget, P, seed=0):
+    """one common P-token prefix in front of every prompt: full prompts (every request prefills the prefix) against one hold and forks, both
+    with chunked admission under the same budget, alternating round by round"""
+    from dimsum_amd.utils.serving import DecodeEngine
+    prefix = torch.randint(0, SHAPE["vocab_size"], (P,), generator=torch.Generator().manual_seed(seed + 2))
+    useful = sum(n for _, n in requests)
+    kw = dict(max_batch=B, max_seqlen=P + PROMPT_RANGE[1] + NEW_RANGE[1], vocab_size=SHAPE["vocab_size"], cg=True, packed_prefill=True,
+              max_prefill_tokens=budget, chunked_prefill=True)
+    engines = {"full": DecodeEngine(model, num_slots=B, **kw), "held": DecodeEngine(model, num_slots=B + 1, **kw)}      # one slot more: the hold's
+
+    def run(name):
+        eng = engines[name]
+        before = sum(eng.prefill_pass_tokens)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if name == "full":
+            rids = [eng.submit(torch.cat([prefix, p]), n) for p, n in requests]
+        else:
+            h = eng.hold(prefix)
+            rids = [eng.submit(p, n, start=h) for p, n in requests]
+        eng.run()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        assert all(eng.context(r).numel() == P + p.numel() + n for r, (p, n) in zip(rids, requests))
+        if name == "held":
+            eng.release(h)
+        eng.requests.clear()
+        return dt, sum(eng.prefill_pass_tokens) - before
+
+    for name in engines:
+        run(name)                                            # warm-up round of each (the capture)
+    times, tokens = {k: [] for k in engines}, {}
+    for _ in range(rounds):
+        for name in engines:
+            dt, tokens[name] = run(name)
+            times[name].append(dt)
+    row = dict(batch=B, requests=len(requests), useful_tokens=useful, rounds=rounds, max_prefill_tokens=budget, shared_prefix=P, prefill_tokens=tokens)
+    for k, v in times.items():
+        row[f"{k}_s"] = round(statistics.median(v), 4)
+        row[f"spread_{k}"] = round(max(v) / min(v), 3)
+    row["full_over_held"] = round(row["full_s"] / row["held_s"], 3)
+    return row
+
+
+def state_copy_bench(model, pairs=8, launches=100, rounds=5):
+    """dimsum_state_copy_slots (ONE launch for every layer) beside the same copies made layer by layer with index_copy_, on a pool of
+    2 * pairs slots of this model: `launches` copies between two device events, alternating, median of `rounds` -> us per copy of `pairs` slots"""
+    from dimsum_amd import native
+    dtype = next(iter(model.parameters())).dtype
+    pool = model.allocate_inference_cache(2 * pairs, 8, dtype)
+    table = native.state_pool_table(pool)
+    src, dst = torch.arange(pairs, device="cuda"), torch.arange(pairs, 2 * pairs, device="cuda")
+    dev_pairs = torch.stack([src, dst], 1).to(torch.int32)
+
+    def per_layer():
+        for states in pool.values():
+            for t in states:
+                t.index_copy_(0, dst, t.index_select(0, src))
+    sides = {"state_copy_slots": lambda: native.state_copy_slots(table, dev_pairs), "index_copy": per_layer}
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(launches):
+            f()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / launches * 1e3
+    for f in sides.values():
+        timed(f)
+    times = {k: [] for k in sides}
+    for _ in range(rounds):
+        for k, f in sides.items():
+            times[k].append(timed(f))
+    row = dict(pairs=pairs, launches=launches, rounds=rounds, tensors=len(table.tensors),
+               slot_bytes=sum(t[0].numel() * t.element_size() for t in table.tensors))
+    for k, v in times.items():
+        row[f"{k}_us"] = round(statistics.median(v), 1)
+        row[f"spread_{k}"] = round(max(v) / min(v), 3)
+    row["index_copy_over_state_copy"] = round(row["index_copy_us"] / row["state_copy_slots_us"], 2)
     return row
 
 
@@ -288,6 +377,7 @@ def main():
     ap.add_argument("--max-prefill-tokens", type=int, default=512, help="the admission budget of --chunked-prefill")
     ap.add_argument("--long-prompts", type=int, default=4, help="--chunked-prefill both: prompts of --long-len tokens among the short ones")
     ap.add_argument("--long-len", type=int, default=4096)
+    ap.add_argument("--shared-prefix", type=int, default=0, help="with --chunked-prefill on: a common prefix of this many tokens, full prompts against hold + forks")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_serve needs the GPU"
@@ -296,6 +386,24 @@ def main():
     torch.manual_seed(0)
     model = MambaLMHeadModel(**SHAPE, device="cuda", dtype=getattr(torch, args.dtype)).eval()
     requests = workload(args.requests, args.seed)
+    if args.shared_prefix:
+        assert args.chunked_prefill == "on", "--shared-prefix rides on chunked admission: pass --chunked-prefill on"
+        rows = [dict(shared_prefix_bench(model, requests, B, args.rounds, args.max_prefill_tokens, args.shared_prefix, args.seed), dtype=args.dtype,
+                     fused_decode=policy or "unset") for B in args.batches]
+        copy = dict(state_copy_bench(model, rounds=args.rounds), dtype=args.dtype)
+        for row in rows + [copy]:
+            print(json.dumps(row), flush=True)
+        print("\n| B | prefix | full prompts s (spread) | hold + forks s (spread) | full / held | prompt tokens full | prompt tokens held |\n|---|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['batch']} | {r['shared_prefix']} | {r['full_s']:.3f} ({r['spread_full']:.3f}) | {r['held_s']:.3f} ({r['spread_held']:.3f}) | "
+                  f"{r['full_over_held']:.2f} | {r['prefill_tokens']['full']} | {r['prefill_tokens']['held']} |")
+        print("\n| pairs | tensors | bytes per slot | state_copy_slots us (spread) | per-layer index_copy_ us (spread) | index_copy_ / state_copy_slots |\n|---|---|---|---|---|---|")
+        print(f"| {copy['pairs']} | {copy['tensors']} | {copy['slot_bytes']} | {copy['state_copy_slots_us']:.1f} ({copy['spread_state_copy_slots']:.3f}) | "
+              f"{copy['index_copy_us']:.1f} ({copy['spread_index_copy']:.3f}) | {copy['index_copy_over_state_copy']:.2f} |")
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(dict(shared_prefix=rows, state_copy=copy), f, indent=1)
+        return
     if args.chunked_prefill == "both":
         rows = [dict(chunked_bench(model, requests, B, args.rounds, args.max_prefill_tokens, args.long_prompts, args.long_len, args.seed),
                      dtype=args.dtype, fused_decode=policy or "unset") for B in args.batches]
